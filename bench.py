@@ -6,7 +6,11 @@ writes in one kernel), GAE / returns, advantage whitening, then batch_train! for
 (E x 2048 / 128) minibatches of 128 each -- for C2 (E = 32) exactly 81 920 sequential Adam steps per iteration. KL early stopping is OFF in the
 timed configuration so no work is skipped (the early-stopping variant is reported separately under "early_stop").
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c5] [--sync grad|params]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c5] [--sync grad|params] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes what the last timed step computed when --dump-outputs is given, and prints the headline line.
+Everything else the benchmark measures or checks -- the KL-early-stopping leg, the multi-seed population lines, the other BASELINE configs (other_configs),
+the in-run traffic measurement under rocprofv3, the CPU baselines and, at N > 1, the RCCL check after the timed region -- runs only with --full.
 
 N > 1: one rank per GPU (the script re-launches itself under torch.distributed.run when it was started plainly); every rank owns an
 independent-seed shard of E envs (weak scaling) and the replicas exchange GRADIENTS: every minibatch step SUM-all-reduces the flattened local
@@ -78,7 +82,8 @@ class _Solver:      # the fields policy_gradient_training reads from an OnPolicy
         self.agent, self.a_opt, self.c_opt, self.P = crux.PolicyParams(pi), a_opt, c_opt, P
 
 
-def ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync=None):
+def ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync=None, train_info=None):
+    """one PPO iteration; returns (minibatch steps trained, rollout info). `train_info` (a dict) receives the training info of the iteration."""
     info = crux.steps_(sampler, buf, Nsteps=buf.capacity, explore=True, i=it * buf.capacity, reset=True)
     crux.whiten_(buf, "advantage")
     sv = _Solver(crux, pi, a_opt, c_opt, P)
@@ -86,9 +91,13 @@ def ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync=None):
         # single GPU, or a replica group with peer slots attached to the context: the SAME call -- with a group every minibatch step of the two
         # persistent kernels all-reduces its gradient over the GPUs (on_policy.jl:56-78 / training.jl:13-25 with the exchange between :18 and :21)
         ti = crux.policy_gradient_training(sv, buf)
+        if train_info is not None:
+            train_info.update(ti)
         return ti["actor_batches_trained"] + ti["critic_batches_trained"], info
     if sync == "native":   # periodic parameter averaging by the library's RCCL communicator: chunks of SYNC_EVERY epochs + grouped all-reduce, enqueued without a host sync
         ti = crux.policy_gradient_training_synced(sv, buf, SYNC_EVERY)
+        if train_info is not None:
+            train_info.update(ti)
         return ti["actor_batches_trained"] + ti["critic_batches_trained"], info
     nb, e_total, k = 0, a_opt.epochs, SYNC_EVERY       # torch.distributed fallback of the periodic form (host-synchronised per exchange)
     try:
@@ -99,6 +108,8 @@ def ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync=None):
             nb += ti["actor_batches_trained"] + ti["critic_batches_trained"]
             done += a_opt.epochs
             sync((pi.A, pi.C))
+            if train_info is not None:
+                train_info.update(ti)
     finally:
         a_opt.epochs = c_opt.epochs = e_total
     return nb, info
@@ -489,6 +500,44 @@ def params_digest(nets):
     return np.frombuffer(h.digest()[:8], np.int64)[0]
 
 
+DUMP_MAX_ROWS = 65536       # buffer rows written by --dump-outputs: all of C2's 65 536, a fixed seeded sample of C5's 262 144
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, pi, buf, rollout_info, train_info):
+    """--dump-outputs DIR: what the last timed iteration handed its caller, as DIR/<name>.npy (float32 where the library's array is float32, float64 otherwise):
+    parameters and Adam state of actor and critic, every column of the buffer (the rollout with GAE, returns and the whitened advantage), and the numeric
+    entries of the rollout and training info. Returns the number of bytes written."""
+    import re
+    arrs = {}
+    for role, net in (("actor", pi.A), ("critic", pi.C)):
+        m, v, bp = net.adam_state()
+        arrs.update({role + "_params": net.get_params(), role + "_adam_m": m, role + "_adam_v": v, role + "_adam_beta_pow": bp})
+    n = len(buf)
+    rows = np.arange(n) if n <= DUMP_MAX_ROWS else np.sort(np.random.default_rng(20240).choice(n, DUMP_MAX_ROWS, replace=False))
+    arrs["buffer_rows"] = rows.astype(np.float64)
+    for k in buf.keys():
+        col = buf[k][:, rows]
+        arrs["buffer_" + k] = col.astype(np.float32 if col.dtype == np.float32 else np.float64)
+    for prefix, info in (("rollout_info", rollout_info), ("train_info", train_info)):
+        for k, v in sorted((info or {}).items()):
+            if v is None:
+                continue
+            try:
+                a = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                continue
+            if a.dtype == np.float64 and a.size:
+                arrs[prefix + "_" + re.sub(r"[^A-Za-z0-9_.-]", "_", str(k))] = a
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -501,18 +550,22 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-sync", action="store_true", help="exercise the multi-GPU path even at world size 1 (testing)")
     ap.add_argument("--same-device", action="store_true", help="testing on a 1-GPU box: all ranks use device 0 (gloo rendezvous; the peer regions are still exchanged through hipIpc between the processes)")
-    ap.add_argument("--replicas", type=int, default=64, help="also time S independent PPO learners (multi-seed) trained by two batched launches per iteration: the chip-level utilisation line (0 = skip)")
-    ap.add_argument("--replicas-wide", type=int, default=128, help="second multi-seed line with one CU per learner (population > 64): the highest chip utilisation (0 = skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the supplementary configs (C5 shard, off-policy lines)")
-    ap.add_argument("--early-stop", dest="early_stop", action="store_true", default=True, help="also time the KL-early-stopping variant (target_kl = 0.012, the reference's default PPO, rl/ppo.jl:40-65); on by default at N = 1 (BASELINE.md section 3: the metric is reported with KL early stopping on, and with it off)")
+    ap.add_argument("--replicas", type=int, default=64, help="--full: also time S independent PPO learners (multi-seed) trained by two batched launches per iteration: the chip-level utilisation line (0 = skip)")
+    ap.add_argument("--replicas-wide", type=int, default=128, help="--full: second multi-seed line with one CU per learner (population > 64): the highest chip utilisation (0 = skip)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the supplementary configs (C5 shard, off-policy lines)")
+    ap.add_argument("--early-stop", dest="early_stop", action="store_true", default=True, help="also time the KL-early-stopping variant (target_kl = 0.012, the reference's default PPO, rl/ppo.jl:40-65); on by default with --full at N = 1 (BASELINE.md section 3: the metric is reported with KL early stopping on, and with it off)")
     ap.add_argument("--no-early-stop", dest="early_stop", action="store_false")
-    ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false", help="keep the recorded roofline.traffic constant instead of re-measuring it (the default run measures when rocprofv3 is on PATH)")
-    ap.add_argument("--measure-traffic", action="store_true", default=True, help="N = 1: re-measure roofline.traffic in this run -- two child passes of this script under rocprofv3 --pmc FETCH_SIZE / "
+    ap.add_argument("--no-measure-traffic", dest="measure_traffic", action="store_false", help="keep the recorded roofline.traffic constant instead of re-measuring it (a --full run measures when rocprofv3 is on PATH)")
+    ap.add_argument("--measure-traffic", action="store_true", default=True, help="N = 1, with --full: re-measure roofline.traffic in this run -- two child passes of this script under rocprofv3 --pmc FETCH_SIZE / "
                     "--pmc WRITE_SIZE (separate passes, no trace domains), corrected as the microarchitecture guide prescribes; otherwise the recorded constant of profiles/ is reported")
     ap.add_argument("--inject-attach-failure", action="store_true", help="testing: corrupt the peers' IPC handles so that crux_peer_attach fails on every rank and the fallback ladder is taken")
     ap.add_argument("--selftest", action="store_true", help="N > 1: before timing, check the in-kernel gradient exchange across the real devices (identical shards on every rank must "
                     "reproduce an un-grouped learner; distinct shards must leave the replicas bit-identical), print per-rank flag-wait histograms, and run a 2..N-rank RCCL all-reduce "
                     "through the library's communicator (crux_comm_init / crux_allreduce_grads)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: KL early stopping, the multi-seed lines, other_configs, the traffic measurement, "
+                    "the CPU baselines, the RCCL check at N > 1 (each still switched off by its own --no-* / 0 option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed iteration handed its caller (parameters and Adam state of "
+                    "actor and critic, the buffer's columns, the rollout and training info) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -593,13 +646,15 @@ def main():
     barrier()
     ctx.prof_reset(); ctx.prof_enable(True)
     t0 = time.perf_counter()
-    grad_steps = 0
+    grad_steps = 0; train_info = {}
     for _ in range(args.steps):
-        nb, info = ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync); it += 1
+        nb, info = ppo_iteration(crux, pi, buf, sampler, a_opt, c_opt, P, it, sync, train_info=train_info); it += 1
         grad_steps += nb
     barrier()
     dt = time.perf_counter() - t0
     ctx.prof_enable(False)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, pi, buf, info, train_info)
     replicas_identical = None
     if dist is not None:
         tdev = torch.device("cuda", local) if dist.get_backend() == "nccl" else torch.device("cpu")
@@ -619,6 +674,8 @@ def main():
         # RCCL as the library drives it: the params/native form used it in the timed region; otherwise one checked all-reduce through crux_comm_init / crux_allreduce_grads now
         if sync == "native":
             rccl = [{"ok": True, "how": "the timed region ran on the library's RCCL communicator"}] * world
+        elif not args.full:
+            rccl = None        # the separate RCCL check runs with --full
         else:
             # under a watchdog: the timed numbers above must reach the JSON line whatever a second communicator does on a machine this was never run on
             def _rccl():
@@ -633,11 +690,11 @@ def main():
                     "rendezvous_probe_us": {"first_round_stream0": PROBE["us"][0], "slowest_later_round_stream0": PROBE["us"][1], "first_round_stream1": PROBE["us"][2], "slowest_later_round_stream1": PROBE["us"][3],
                                             "note": "crux_peer_probe on rank 0: 256 rendezvous through the peer regions before anything is timed; the first round absorbs the launch skew between the ranks"} if PROBE.get("us") else None,
                     "flag_wait_note": "upper edge (us) of the log2 bin holding the percentile of the per-exchange wait for the slowest peer's flag, both learner streams, workgroups 0 and 1 of every learner",
-                    "rccl_ranks": int(sum(1 for r in rccl if r and r.get("ok"))), "rccl_detail": rccl[0] if rccl else None}
+                    "rccl_ranks": int(sum(1 for r in rccl if r and r.get("ok"))) if rccl is not None else None, "rccl_detail": rccl[0] if rccl else None}
 
     prof = {k: ctx.prof_get(k) for k in ("rollout", "values", "gae", "whiten", "train_actor", "train_critic")}
     early = None
-    if args.early_stop and world == 1:
+    if args.full and args.early_stop and world == 1:
         a_es = crux.TrainingParams(loss=crux.ppo_loss, batch_size=BATCH, epochs=EPOCHS, target_kl=0.012, name="actor_", shuffle_seed=300)
         ctx.sync(); t1 = time.perf_counter(); nbs = 0
         for _ in range(args.steps):
@@ -678,7 +735,7 @@ def main():
             return {"replicas": Sn, "error": repr(e)}
 
     multi = multi_wide = extra = None
-    if world == 1 and not args.force_sync and args.workload == "c2":
+    if args.full and world == 1 and not args.force_sync and args.workload == "c2":
         if args.replicas > 1:
             multi = multi_seed_line(args.replicas)
             if args.replicas_wide > 1:
@@ -691,7 +748,7 @@ def main():
                 extra = {"error": repr(e)}
 
     traffic, traffic_how = (TRAFFIC_RECORDED.get(args.workload) if world == 1 else None), "RECORDED constant (profiles/r05_pmc_traffic*.txt), not measured in this run"
-    if rank == 0 and world == 1 and args.measure_traffic:
+    if args.full and rank == 0 and world == 1 and args.measure_traffic:
         tv, how = measure_traffic(args.workload)
         if tv is not None:
             traffic, traffic_how = tv, how
@@ -749,7 +806,7 @@ def main():
             out["c4_sac_us_per_epoch_async_chains"] = _g("c4_sac", "us_per_epoch_async_chains")
             out["c5_shard_env_steps_per_s"] = _g("c5_shard", "env_steps_per_s")
             out["c5_shard_us_per_grad_step"] = (extra.get("c5_shard", {}).get("roofline", {}) or {}).get("us_per_grad_step") if isinstance(extra, dict) else None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload)
         sys.stdout.flush(); os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist is not None and rccl_hung:

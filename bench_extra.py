@@ -1,5 +1,5 @@
 """Supplementary lines of bench.py's JSON ("other_configs"): the other BASELINE.json configs on ONE MI355X, each with its own roofline and a CPU
-baseline from the oracle timed on a bounded sample of the same workload, so that the driver's default `python bench.py` run records them.
+baseline from the oracle timed on a bounded sample of the same workload, so that `python bench.py --full` records them.
 
   c5  configs[4], one GPU's shard: PPO 128 envs x 2048 steps on the 17-obs / 6-act synthetic env, tanh GaussianPolicy 17-64-64-6 + critic
   c3  configs[2]: DQN + prioritized replay, 8-256-256-4, buffer 1 M, B = 128

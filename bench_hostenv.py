@@ -10,7 +10,7 @@ seam -- not the environment -- is what is timed) is driven through the C ABI exa
     crux_steps_push(buffer, block of E*T transitions, critic)                     ring write + fill_gae! / fill_returns! on the pushed rows
 
 Reported: us per crux_policy_explore call (median and p90 over the run), us per crux_steps_push, env-steps/s end to end, and beside them the DEVICE-environment rollout
-(`crux_rollout`, same policy shape, same E and T) in env-steps/s. `python bench_hostenv.py` prints the three configurations as one JSON line; bench.py's default run
+(`crux_rollout`, same policy shape, same E and T) in env-steps/s. `python bench_hostenv.py` prints the three configurations as one JSON line; `bench.py --full`
 carries them under other_configs.host_env."""
 import ctypes as C
 import json

@@ -287,7 +287,7 @@ def _bench(args, seconds=270):
 def test_bench_launcher_two_ranks_same_device_selftest_c5():
     """the command the driver's SCALE run issues, shrunk to one GPU: relaunch under torch.distributed.run, gloo rendezvous, hipIpc handle exchange, probe iteration, selftest,
     one timed C5-shard iteration per rank through the in-kernel exchange"""
-    out, err = _bench(["--gpus", "2", "--same-device", "--selftest", "--workload", "c5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--replicas", "0"])
+    out, err = _bench(["--full", "--gpus", "2", "--same-device", "--selftest", "--workload", "c5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--replicas", "0"])
     assert out["n_gpus"] == 2 and out["exchange"]["kind"] == "peer_slots_grad_every_step" and out["exchange"]["fell_back"] is False
     assert out["replicas_bit_identical_after_run"] is True
     st = out["selftest"]
@@ -301,7 +301,7 @@ def test_bench_fallback_ladder_when_peer_attach_fails():
     """crux_peer_attach made to fail on every rank (corrupted handles): all ranks agree to leave the in-kernel exchange and land on periodic parameter averaging -- the library's
     RCCL communicator when every rank has its own device, torch.distributed (gloo here: the ranks share the device, where RCCL cannot run) otherwise -- and still finish with
     identical replicas"""
-    out, err = _bench(["--gpus", "2", "--same-device", "--workload", "c5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--replicas", "0", "--inject-attach-failure"])
+    out, err = _bench(["--full", "--gpus", "2", "--same-device", "--workload", "c5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--replicas", "0", "--inject-attach-failure"])
     ex = out["exchange"]
     assert ex["requested"] == "grad" and ex["fell_back"] is True and ex["kind"].startswith(("torch_allreduce_params", "rccl_params")), ex
     assert "cannot attach the peer regions" in err

@@ -5,7 +5,7 @@ ROUND=${ROUND:-r05}; R=$PWD; OUT=$R/gpurun_out/$ROUND; mkdir -p $OUT; export TMP
 PARTS=${1:-"tests bench rocprof phase solve traffic sq px"}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has tests; then timeout 2400 python -m pytest tests -q -m gpu -x 2>&1 | grep -E "passed|failed|error" > $OUT/pytest_gpu.txt; cat $OUT/pytest_gpu.txt; fi
-if has bench; then timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json; echo; fi
+if has bench; then timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 600 $OUT/bench.json; echo; fi
 if has rocprof; then
   (cd /tmp && rm -rf /tmp/kst && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kst -o k -- python $R/bench.py --no-measure-traffic --no-early-stop --replicas 0 --replicas-wide 0 --no-extra --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
    cp /tmp/kst/k_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null || find /tmp/kst -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;)
