@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void k_gemm16(GemmArgs q) { __shared__ float p
 // the executor's form (exec.hip): the variant is data
 struct GemmOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, GemmArgs q, int variant) {
   __shared__ float part[GEMM16_PART];         // one combine buffer for all variants (a static array per template instantiation cost the phase kernel 15 KB of LDS)
-  const int quart = (variant >> 3) & 1;       // bit 0 AV, bit 1 BV, bit 2 split-K over the workgroup's waves, bit 3 the four K quarters walked by one wave
+  const int quart = (variant >> 3) & 1;       // bit 0 AV, bit 1 BV, bit 2 split-K over the workgroup's waves, bit 3 the four K quarters walked by one wave (no launch site sets it now)
   switch (variant & 7) {
     case 0: Gemm16<false, false, false>::run(bid_, q, part, quart); break; case 1: Gemm16<true, false, false>::run(bid_, q, part, quart); break;
     case 2: Gemm16<false, true, false>::run(bid_, q, part, quart); break;  case 3: Gemm16<true, true, false>::run(bid_, q, part, quart); break;
@@ -157,13 +157,10 @@ static int32_t launch_gemm(crux_ctx* c, const GemmArgs& q, hipStream_t st) {
   const dim3 block(256);
   const bool av = vec_ok(q.A, q.sAk, q.sAi, q.K), bv = vec_ok(q.B, q.sBk, q.sBj, q.K);
   constexpr bool no_split = false;
-  if (crux_exec_recording(c)) {                       // fused sequence (exec.hip): the same tile bodies, run by the persistent executor
-    // the stand-alone launch would split K over the four waves of a workgroup here; on the executor's 32 CUs one round of fat blocks beats several rounds of
-    // thin ones, so up to 32 tiles keep the split form and larger GEMMs give each wave a whole tile with the K quarters walked in order (same bits)
-    // (the persistent one-XCD executor prefers fat blocks; the default phase launches run over the whole chip like the stand-alone launches and split whenever those do)
-    const bool persistent = crux_sw().exec_persistent;
-    const bool deep = q.K >= 128 && tiles <= 4096 && !no_split, split = deep && (!persistent || tiles <= 32);
-    crux_exec_push<GemmOp, OP_GEMM>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0) | ((deep && !split) ? 8 : 0)));
+  if (crux_exec_recording(c)) {                       // fused sequence (exec.hip): the same tile bodies, run by the phase launches
+    // the phase launches run over the whole chip like the stand-alone launches and split K over the four waves of a workgroup whenever those do
+    const bool split = q.K >= 128 && tiles <= 4096 && !no_split;
+    crux_exec_push<GemmOp, OP_GEMM>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0)));
     return CRUX_OK;
   }
   if (q.K >= 128 && tiles <= 4096 && !no_split) {     // deep reductions: split K over the workgroup's four waves

@@ -1,10 +1,11 @@
-// exec.h -- the fused-step executor: a recorded sequence of kernel bodies run by ONE persistent launch.
+// exec.h -- the fused-step executor: a recorded sequence of kernel bodies run as a few launches, one per PHASE.
 //
 // The off-policy learners on wide networks (value_training, src/model_free/off_policy.jl:66-111: rand! -> target -> td_error / update_priorities! ->
 // train!(critic) -> train!(actor) -> target update) are chains of 20-70 small dependent kernels; launched one by one each costs ~5 us whatever its
 // size, so an epoch was launch-bound. In record mode the launch sites push an ExecOp {kernel body id, block count, packed arguments}
-// instead of launching; crux_exec_run uploads the list and starts k_exec: G workgroups on ONE XCD walk the list, each taking the blocks
-// b = wg, wg + G, ... of every op, with a counter barrier through the shared L2 between dependent ops (1.3 us instead of a launch).
+// instead of launching. The caller tags every op with a phase (ops of one phase do not depend on each other); crux_exec_run then launches each phase
+// once over the whole chip: k_phase_k with the phase's records in the kernel arguments, or k_phase with them in a device copy of the list when they
+// do not fit (exec.hip). The kernel boundary is the dependency between phases.
 // The bodies are the SAME device functions the stand-alone kernels call (struct XOp::run), so both forms compute identical results.
 #pragma once
 #include "common.h"
@@ -50,17 +51,12 @@ struct ExecRec {
   char* small = nullptr; size_t small_cap = 0, small_off = 0;     // device: per-piece info rows / statistics / status words that outlive the piece until the read-back
   std::vector<ExecReadback> readbacks;
   void* d_ops = nullptr; size_t d_ops_cap = 0;                     // device copy of the op list
-  unsigned* d_ctr = nullptr;                                       // device: barrier counter, abort flag
   void* h_stage = nullptr; size_t h_stage_cap = 0;                 // pinned staging of the op list and of the read-backs
   size_t scratch_floor = 0, scratch_off = 0;                       // scratch requests made while recording are carved one after the other from the pre-sized block
   // chained epochs (crux_dqn_epochs / crux_sac_epochs): several value_training epochs recorded into ONE list, scheduled and run once -- no host round trip between
   // the epochs of an iteration. While `chain` is set the per-epoch entry points append their phase tags (offset by chain_base) instead of scheduling and running.
   bool chain = false, chain_ok = true; int chain_base = 0; std::vector<int> chain_tags;
-  // the two-kernel persistent form of the DQN-family epochs (dqn_persist.h): first op of every recorded epoch; what crux_exec_run launches instead of the phases
-  std::vector<size_t> epoch_marks;
-  struct Dqp { bool on = false; int in = 0, out = 0, bt = 0, n_epochs = 0; void* net = nullptr; void* tnet = nullptr; void* batch = nullptr; float gamma = 0.f; bool use_weight = false; float* d_err = nullptr;
-               std::vector<int32_t> tab; } dqp;
-  void* dqp_buf = nullptr;                                          // device: learner barrier words, flags, tables, exchange areas
+  size_t epoch_first = 0;                  // first op of the epoch recorded last: ops appended behind it (info-row copy, target update) join that epoch's last phase
   // asynchronous runs (crux_dqn_epochs_async): no read-back, no host synchronisation -- the info rows are copied to a caller-owned device array by ops of the list itself.
   // The op list is uploaded from a ring of pinned staging buffers, so the host may record and enqueue up to three chains ahead of the one the device is running.
   bool async = false;
@@ -69,7 +65,7 @@ struct ExecRec {
 };
 bool crux_exec_recording(const crux_ctx* c);
 int32_t crux_exec_begin(crux_ctx* c);                 // start recording on this context (the launch sites below push ops instead of launching)
-int32_t crux_exec_run(crux_ctx* c);                   // upload, run the persistent kernel, fulfil the recorded read-backs; ends the recording
+int32_t crux_exec_run(crux_ctx* c);                   // upload, launch the phases, fulfil the recorded read-backs; ends the recording
 void crux_exec_abort(crux_ctx* c);                    // drop a recording after an error
 ExecOp* crux_exec_new_op(crux_ctx* c, int kid, unsigned nblocks);
 void* crux_exec_small(crux_ctx* c, size_t bytes);     // 256-byte aligned block of the small region (valid until the next crux_exec_begin)
@@ -83,7 +79,7 @@ template <class Op, int KID, class... A> inline void crux_exec_push(crux_ctx* c,
   P p(a...);
   memcpy(op->args, &p, sizeof p); op->abytes = (int32_t)sizeof p;
 }
-// a launch site: record when the context is recording, launch otherwise. NT = threads per block of the stand-alone launch (the executor always runs 256).
+// a launch site: record when the context is recording, launch otherwise. NT = threads per block of the stand-alone launch (the phase kernels always run 256).
 #define CRUX_RUN(c, OpT, KID, kernel, nblocks, NT, stream, ...)                                                            \
   do { if (crux_exec_recording(c)) crux_exec_push<OpT, KID>((c), (unsigned)(nblocks), __VA_ARGS__);                          \
        else hipLaunchKernelGGL(kernel, dim3((unsigned)(nblocks)), dim3(NT), 0, (stream), __VA_ARGS__); } while (0)

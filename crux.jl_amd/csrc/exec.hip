@@ -4,53 +4,9 @@
 #include "ops_small.h"
 #include <algorithm>
 
-#define EXEC_G 64                 // workgroups of the persistent launch, all on one XCD (32 CUs x 2)
 #define EXEC_SMALL_BYTES (256 * 1024)
 
-int32_t crux_x2_placement_ok_c(crux_ctx* c);
-
-// ---- device: the interpreter ------------------------------------------------------------------------------------------------------------
-template <class Op> __device__ __forceinline__ void exec_dispatch(const ExecOp* op, unsigned bid) {
-  // the record sits in LDS (staged one op ahead by k_exec). Its words are moved to SCALAR registers (v_readfirstlane): arguments that arrive in vector
-  // registers turn every pointer computation and every uniform branch of the body into per-lane work (the tile GEMM ran 3x slower that way)
-  constexpr int NW = (int)((sizeof(OpPack<Op>) + 3) / 4);
-  uint32_t w[NW]; const uint32_t* src = (const uint32_t*)op->args;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) w[i] = __builtin_amdgcn_readfirstlane(src[i]);
-  OpPack<Op> p; __builtin_memcpy(&p, w, sizeof p);
-  exec_apply<Op>(bid, __builtin_amdgcn_readfirstlane(op->nblocks), p);
-}
-// Counter barrier between workgroups that sit behind ONE L2 (the learner kernels' exchange, tools/xcu_barrier_bench.hip): stores are write-through
-// to the L2, so s_waitcnt + one relaxed agent-scope atomic is the release; the acquire side drops this CU's L1 and scalar cache.
-// Flag barrier between workgroups that sit behind ONE L2. Workgroup w publishes the phase number in ITS OWN word (plain store: the vector L1 is
-// write-through); one wave then polls all G words with a single coalesced L1-bypassing load per try. No atomics: G arrivals on one address are
-// serialised by the L2 (2.4 us per barrier with 64 workgroups, tools/dbg_nops.py). ctr[0..255] = arrival words, ctr[256] = abort flag.
-__device__ __forceinline__ bool exec_barrier(unsigned* ctr, unsigned wg, unsigned G, unsigned phase, int flags) {
-  __shared__ int ok_s;
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this wave's stores are in the L2
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    if (threadIdx.x == 0) { __hip_atomic_store(ctr + wg, phase, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    unsigned spins = 0; int ok = 1;
-    for (;;) {
-      bool here = true;
-      for (unsigned q = threadIdx.x; q < G; q += 64) here = here && __hip_atomic_load(ctr + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= phase;
-      if (__ballot(!here) == 0ull) break;
-      __builtin_amdgcn_s_sleep(1);
-      if ((++spins & 255u) == 0u && (spins > (1u << 22) || __hip_atomic_load(ctr + 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) { ok = 0; break; }      // never hang the GPU
-    }
-    if (threadIdx.x == 0) { if (!ok) __hip_atomic_store(ctr + 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok_s = ok; }
-  }
-  __syncthreads();
-  // acquire side: drop THIS CU's vector L1 (buffer_inv sc0, workgroup scope in the ISA's terms: the L2 behind it is shared by the whole XCD and needs nothing)
-  // and its scalar cache. The agent-scope form (sc1) also walks the L2 and cost 17 us per barrier with 64 workgroups (tools/dbg_nops.py)
-  // (round 3: the agent-scope form. `buffer_inv sc0` is a workgroup-scope invalidate and leaves the L1 as it is -- a re-read of a line this CU had cached before another
-  //  CU rewrote it returned the OLD data (found with dqn_persist.h's kernels, whose second epoch re-reads the batch rows); flag 1 = the caller reads with L1-bypassing loads)
-  if (!(flags & 1)) asm volatile("buffer_inv sc1" ::: "memory");
-  if (!(flags & 2)) asm volatile("s_dcache_inv" ::: "memory");
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  return ok_s != 0;
-}
+// ---- device: the phase kernels ------------------------------------------------------------------------------------------------------------
 #define EXEC_SWITCH(DISPATCH) \
       switch (kid) { \
         case OP_GEMM: DISPATCH<GemmOp>(op, b); break; \
@@ -115,27 +71,11 @@ __device__ __forceinline__ bool exec_barrier(unsigned* ctr, unsigned wg, unsigne
         default: break; \
       }
 
-
-// the same dispatch with the record read straight from global memory at a uniform address (scalar loads): the one-launch-per-phase form below
+// an op body with its record read straight from global memory at a uniform address (scalar loads): the global-record phase kernel below
 template <class Op> __device__ __forceinline__ void exec_dispatch_g(const ExecOp* op, unsigned bid) {
   const OpPack<Op> p = *(const OpPack<Op>*)op->args;
   exec_apply<Op>(bid, op->nblocks, p);
 }
-// the replay ops alone (dqn_persist.h: k_dqn_replay); the gather's column table is read where it lies
-#define EXEC_SWITCH_REPLAY(DISPATCH) \
-      switch (kid) { \
-        case OP_FILL: DISPATCH<FillOp>(op, b); break; \
-        case OP_PER_SEARCH: DISPATCH<PerSearchOp>(op, b); break; \
-        case OP_UNIFORM_IDS: DISPATCH<UniformIdsOp>(op, b); break; \
-        case OP_GATHER_RING_ALL: { using P_ = OpPack<GatherRingAllOp>; const P_* pp = (const P_*)op->args; \
-          GatherRingAllOp::run_ptr(b, op->nblocks, &pp->head, pp->tail.head, pp->tail.tail.head, pp->tail.tail.tail.head, pp->tail.tail.tail.tail.head); } break; \
-        case OP_RING_IDS: DISPATCH<RingIdsOp>(op, b); break; \
-        case OP_LEAF_REFRESH: DISPATCH<LeafRefreshOp>(op, b); break; \
-        case OP_TREE_TOUCH: DISPATCH<TreeTouchOp>(op, b); break; \
-        case OP_PER_UPDATE: DISPATCH<PerUpdateOp>(op, b); break; \
-        case OP_COPY_F32: DISPATCH<CopyF32Op>(op, b); break; \
-        default: break; \
-      }
 // One PHASE of a recorded sequence as one launch over the whole chip: block x of the grid belongs to the op whose block range contains x. The ops of a
 // phase do not depend on each other, the dependency between phases is the kernel boundary -- no in-kernel barrier, no coherence question, all 256 CUs.
 // A fused epoch then costs (number of phases) launches instead of (number of kernels): 13 instead of 25 for a DQN epoch, 30 instead of ~75 for SAC (10 / 27 per epoch inside a chain).
@@ -219,136 +159,18 @@ static bool phasek_fits(const std::vector<ExecOp>& ops, size_t i0, size_t i1) {
     used += ab; ++n; }
   return n > 0;
 }
-__global__ __launch_bounds__(256) void k_exec(const ExecOp* __restrict__ ops, int nops, unsigned* ctr, int xcd, int32_t* status, int flags) {
-  constexpr int EXEC_HEAVY = 2;
-  if (xcd >= 0 && (int)(blockIdx.x & 7) != xcd) return;
-  const unsigned wg = xcd >= 0 ? blockIdx.x >> 3 : blockIdx.x, G = xcd >= 0 ? gridDim.x >> 3 : gridDim.x;
-  // op records are staged through LDS one op ahead: the 512-byte record of op o+1 is fetched while op o runs and its barrier is waited for, so
-  // dispatch reads its arguments from LDS instead of paying two dependent L2 round trips per op (1.5 us measured, tools/dbg_nops.py)
-  __shared__ ExecOp op_s[2];
-  constexpr int OPW = (int)(sizeof(ExecOp) / 4);
-  if ((int)threadIdx.x < OPW && nops > 0) ((uint32_t*)&op_s[0])[threadIdx.x] = ((const uint32_t*)&ops[0])[threadIdx.x];
-  __syncthreads();
-  unsigned phase = 0, off = 0;
-  for (int o = 0; o < nops; ++o) {
-    const ExecOp* op = &op_s[o & 1];
-    uint32_t nxt = 0;
-    if ((int)threadIdx.x < OPW && o + 1 < nops) nxt = ((const uint32_t*)&ops[o + 1])[threadIdx.x];
-    const int kid = __builtin_amdgcn_readfirstlane(op->kid); const unsigned nb = __builtin_amdgcn_readfirstlane(op->nblocks);
-    unsigned long long* tdbg = (unsigned long long*)(ctr + 1024);          // CRUX_EXEC_FLAGS & 8: per-op timestamps of workgroups 0 and 1 (s_memtime, 100 MHz)
-    if ((flags & 8) && wg < 2 && threadIdx.x == 0 && o < 512) tdbg[(wg * 512 + o) * 3 + 0] = __builtin_amdgcn_s_memtime();
-    // blocks are dealt to the workgroups round-robin over the whole PHASE (ops without a barrier between them), not per op: a phase made of a
-    // one-block op and two GEMMs then keeps 1 + 16 + 32 different workgroups busy instead of giving workgroup 0 a block of each
-    const unsigned b0 = (wg + G - off) % G;
-    for (unsigned b = b0; b < nb; b += G) {
-      EXEC_SWITCH(exec_dispatch)
-      __syncthreads();                                   // the bodies' static LDS is reused by the next block / op of this workgroup
-    }
-    const int bar = __builtin_amdgcn_readfirstlane(op->barrier) & 1;
-    if ((flags & 8) && wg < 2 && threadIdx.x == 0 && o < 512) tdbg[(wg * 512 + o) * 3 + 1] = __builtin_amdgcn_s_memtime();
-    if ((int)threadIdx.x < OPW && o + 1 < nops) ((uint32_t*)&op_s[(o + 1) & 1])[threadIdx.x] = nxt;
-    off = bar ? 0u : (off + nb) % G;
-    if (bar) { phase += 1; if (!exec_barrier(ctr, wg, G, phase, flags)) { if (threadIdx.x == 0 && wg == 0) status[0] = CRUX_EHIP; return; } }
-    else __syncthreads();
-    if ((flags & 8) && wg < 2 && threadIdx.x == 0 && o < 512) tdbg[(wg * 512 + o) * 3 + 2] = __builtin_amdgcn_s_memtime();
-  }
-}
-
-#include "dqn_persist.h"
-
 // ---- host: recording -------------------------------------------------------------------------------------------------------------------
 static ExecRec* rec_of(crux_ctx* c) { return (ExecRec*)c->rec; }
-// CRUX_EXEC_PERSISTENT (development): the one-XCD persistent executor k_exec, for recordings that are run one at a time and waited for. Chained epochs ignore the switch: their
-// op tags assume the phase plan (sequential one-block groups, tile ops), and an asynchronous chain could not read k_exec's status word back.
-static bool exec_persistent_on(crux_ctx* c) { const ExecRec* r = (const ExecRec*)c->rec; return crux_sw().exec_persistent && !(r && r->chain); }
-extern "C" int32_t crux_ensure_aux_stream(crux_ctx* c);      // train.hip: a second stream on its own hardware queue (probed)
-
-// The persistent two-kernel form of a recorded chain of DQN-family epochs (dqn_persist.h). The recording holds every op of every epoch; the learner's ops (tile GEMMs,
-// target, head, norm, info, Adam) are replaced by k_dqn_learn, the replay ops are handed to k_dqn_replay grouped into the stages the two kernels synchronise on.
-#define DQP_BUF_BYTES ((size_t)6 << 20)
-struct DqpBuf { static constexpr size_t oCtrL = 0, oFlags = 2048, oSsq = 2304, oTab = 4096, oPtr = 4096 + 32768, oG = 65536, oZ = oG + 32768, oP = oZ + 262144, oMV = oP + ((size_t)DQP_G * 128 * 256 * 4), oDbg = oMV + (1 << 20), oWT = oDbg + 16384; };      // oWT: 16 x 16 KB      // oMV: 16 x 2 x <= 4360 floats = 558 KB
-template <int IN, int OUT, int BT> static int32_t dqp_launch_learn(crux_ctx* c, const DqpArgs& a, hipStream_t st) {
-  constexpr size_t lds = sizeof(float) * (size_t)DqpL<IN, OUT, BT>::TOTAL;
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];      // (per device: a second device in the process sets the attribute for itself)
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_dqn_learn<IN, OUT, BT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
-  hipLaunchKernelGGL((k_dqn_learn<IN, OUT, BT>), dim3(8 * DQP_G), dim3(256), lds, st, a);
-  return crux_launch_check(c, "k_dqn_learn");
-}
-static bool dqp_shape(int in, int out, int64_t B) { return ((in == 8 && out == 4) || (in == 4 && out == 2)) && (B == 128 || B == 64); }
-static int32_t dqp_build(ExecRec* r) {        // the replay table; CRUX_EUNSUP when the recording holds something the two kernels do not know
-  ExecRec::Dqp& d = r->dqp; const int n = d.n_epochs; if (n < 1 || (int)r->epoch_marks.size() != n || (int)r->readbacks.size() != n) return CRUX_EUNSUP;
-  d.tab.assign(4 * (size_t)n, 0);
-  for (int e = 0; e < n; ++e) {
-    const size_t i0 = r->epoch_marks[e], i1 = e + 1 < n ? r->epoch_marks[e + 1] : r->ops.size();
-    std::vector<std::pair<int, int>> A, Cs; bool head = false;      // (phase, op index)
-    for (size_t i = i0; i < i1; ++i) { const int kid = r->ops[i].kid;
-      switch (kid) {
-        case OP_PER_SEARCH: case OP_UNIFORM_IDS: case OP_PER_SAMPLE: A.push_back({0, (int)i}); break;
-        case OP_GATHER_RING_ALL: case OP_RING_IDS: case OP_COPY_F32: case OP_FILL: if (head) return CRUX_EUNSUP; A.push_back({1, (int)i}); break;
-        case OP_PER_UPDATE: if (head) Cs.push_back({0, (int)i}); else A.push_back({2, (int)i}); break;
-        case OP_LEAF_REFRESH: if (!head) return CRUX_EUNSUP; Cs.push_back({1, (int)i}); break;
-        case OP_TREE_TOUCH: if (!head) return CRUX_EUNSUP; Cs.push_back({2, (int)i}); break;
-        case OP_TD_HEAD: head = true; break;
-        case OP_GEMM: case OP_FWD12: case OP_WGRAD2: case OP_DGRAD2W1: case OP_DQN_TARGET: case OP_SUMSQ2: case OP_TD_INFO: case OP_ADAM_GATED: case OP_ADAM_ADVANCE: case OP_ADAM_SELF: case OP_ADAM_ADVANCE_SELF: break;      // the learner kernel's work
-        default: return CRUX_EUNSUP; } }
-    if (!head || A.empty()) return CRUX_EUNSUP;
-    auto emit = [&](std::vector<std::pair<int, int>>& v, int slot) {
-      std::stable_sort(v.begin(), v.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first < y.first; });
-      const int32_t at = (int32_t)d.tab.size(); d.tab[4 * e + slot] = at; d.tab[4 * e + slot + 1] = (int32_t)v.size();
-      for (size_t k = 0; k < v.size(); ++k) { d.tab.push_back(v[k].second); d.tab.push_back((k + 1 == v.size() || v[k + 1].first != v[k].first) ? 1 : 0); } };
-    emit(A, 0); emit(Cs, 2);
-  }
-  return d.tab.size() * 4 <= 32768 ? CRUX_OK : CRUX_EUNSUP;
-}
-static int32_t dqp_launch(crux_ctx* c, ExecRec* r) {      // inside crux_exec_run: the op list is uploaded, d_ctr is zeroed
-  ExecRec::Dqp& d = r->dqp; crux_mlp* net = (crux_mlp*)d.net; crux_mlp* tn = (crux_mlp*)d.tnet; crux_buffer* b = (crux_buffer*)d.batch;
-  const int n = d.n_epochs; char* buf = (char*)r->dqp_buf;
-  std::vector<void*> ptrs(2 * (size_t)n);
-  for (int e = 0; e < n; ++e) { ptrs[e] = (void*)r->readbacks[e].d_info; ptrs[n + e] = (void*)r->readbacks[e].d_status; }
-  if (ptrs.size() * sizeof(void*) > 16384) return crux_fail(c, CRUX_EINVAL, "dqn epochs: chain of %d epochs", n);
-  HIPCHK(c, hipMemsetAsync(buf, 0, 4096, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf + DqpBuf::oTab, d.tab.data(), d.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf + DqpBuf::oPtr, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, c->stream));
-  DqpArgs a{}; a.p = net->p; a.m = net->m; a.v = net->v; a.bp = net->bp; a.pt = tn->p;
-  for (int l = 0; l < 3; ++l) { a.woff[l] = net->nd.woff[l]; a.boff[l] = net->nd.boff[l]; }
-  a.eta = net->eta; a.b1 = net->b1; a.b2 = net->b2; a.eps = net->eps;
-  a.S = (const float*)b->col[CRUX_COL_S]; a.SP = (const float*)b->col[CRUX_COL_SP]; a.A = (const uint8_t*)b->col[CRUX_COL_A]; a.R = (const float*)b->col[CRUX_COL_R];
-  a.DONE = (const uint8_t*)b->col[CRUX_COL_DONE]; a.W = d.use_weight ? (const float*)b->col[CRUX_COL_WEIGHT] : nullptr;
-  a.gamma = d.gamma; a.n_epochs = n; a.err = d.d_err;
-  a.dinfo = (float* const*)(buf + DqpBuf::oPtr); a.dstatus = (int32_t* const*)(buf + DqpBuf::oPtr + n * sizeof(void*));
-  a.zbuf = (float*)(buf + DqpBuf::oZ); a.pbuf = (float*)(buf + DqpBuf::oP); a.gbuf = (float*)(buf + DqpBuf::oG); a.mv2 = (float*)(buf + DqpBuf::oMV); a.wtg = (float*)(buf + DqpBuf::oWT); a.ssq = (double*)(buf + DqpBuf::oSsq);
-  a.ctrL = (unsigned*)(buf + DqpBuf::oCtrL); a.flags = (unsigned*)(buf + DqpBuf::oFlags); a.status = (int32_t*)(r->d_ctr + 264); a.xcd = 0;
-  a.dbg = crux_sw().dqp_debug ? (unsigned long long*)(buf + DqpBuf::oDbg) : nullptr; if (a.dbg) HIPCHK(c, hipMemsetAsync(a.dbg, 0, 8192, c->stream));
-  // the replay kernel first, on the second stream (its own hardware queue): it samples epoch 0 while the learner loads its parameters
-  HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
-  hipLaunchKernelGGL(k_dqn_replay, dim3(8 * DQP_R), dim3(256), 0, c->aux_stream, (const ExecOp*)r->d_ops, (const int32_t*)(buf + DqpBuf::oTab), n, r->d_ctr, a.flags, a.xcd, a.status, a.dbg);
-  HIPCHK(c, hipEventRecord(c->aux_ev1, c->aux_stream));
-  int32_t rc = CRUX_EUNSUP;
-  if (d.in == 8 && d.out == 4 && d.bt == 8) rc = dqp_launch_learn<8, 4, 8>(c, a, c->stream);
-  else if (d.in == 8 && d.out == 4 && d.bt == 4) rc = dqp_launch_learn<8, 4, 4>(c, a, c->stream);
-  else if (d.in == 4 && d.out == 2 && d.bt == 8) rc = dqp_launch_learn<4, 2, 8>(c, a, c->stream);
-  else if (d.in == 4 && d.out == 2 && d.bt == 4) rc = dqp_launch_learn<4, 2, 4>(c, a, c->stream);
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->aux_ev1, 0));
-  if (crux_sw().dqp_debug) { HIPCHK(c, hipStreamSynchronize(c->stream)); unsigned h[1024]; HIPCHK(c, hipMemcpy(h, buf, 4096, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[dqp] rc %d n %d flags %u %u %u  ctrL", rc, n, h[512], h[513], h[514]); for (int q = 0; q < 16; ++q) fprintf(stderr, " %u", h[q]); fprintf(stderr, " abort %u  ssq", h[256]);
-    const double* sq = (const double*)(h + 576); for (int q = 0; q < 16; ++q) fprintf(stderr, " %.3g", sq[q]); { unsigned hc[300]; (void)hipMemcpy(hc, r->d_ctr, 1200, hipMemcpyDeviceToHost); fprintf(stderr, "  ctrR"); for (int q = 0; q < 32; ++q) fprintf(stderr, " %u", hc[q]); fprintf(stderr, " abortR %u st %d whyL %d whyR %d claims %u %u", hc[256], (int)hc[264], (int)hc[265], (int)hc[266], h[516], h[517]); }
-    fprintf(stderr, "  xcc L"); for (int q = 0; q < 16; ++q) fprintf(stderr, " %u", h[512 + 16 + q]); fprintf(stderr, " R"); for (int q = 0; q < 32; ++q) fprintf(stderr, " %u", h[512 + 32 + q]); fprintf(stderr, "  tab"); for (size_t q = 0; q < d.tab.size() && q < 40; ++q) fprintf(stderr, " %d", d.tab[q]); fprintf(stderr, "\n");
-    static int dumps = 0; if (dumps++ == 2) { unsigned long long t[1024]; HIPCHK(c, hipMemcpy(t, buf + DqpBuf::oDbg, 8192, hipMemcpyDeviceToHost));
-      fprintf(stderr, "[dqp] learner wg 0 (us since its start; ~2.04 GHz ticks; after the start stamp, per epoch: batch ready | forward | barrier b | z loaded | sync | head | stats | acked | sync | dW3 dZ2 P dW2 | barrier c | dH1 dW1 | barrier d | Adam):"); for (int q = 0; q < 512 && t[q]; ++q) fprintf(stderr, " %.1f", (double)(t[q] - t[0]) / 2040.0);
-      fprintf(stderr, "\n[dqp] replay wg 0 (us since the LEARNER's start):"); for (int q = 512; q < 1024 && t[q]; ++q) fprintf(stderr, " %.1f", ((double)t[q] - (double)t[0]) / 2040.0); fprintf(stderr, "\n"); } }
-  return rc;
-}
 bool crux_exec_recording(const crux_ctx* c) { return c && c->rec && ((const ExecRec*)c->rec)->active; }
 int32_t crux_exec_begin(crux_ctx* c) {
   if (!c->rec) c->rec = new ExecRec();
   ExecRec* r = rec_of(c);
   if (r->active) return crux_fail(c, CRUX_EINVAL, "executor: a recording is already open on this context");
   if (!r->small) { if (hipMalloc(&r->small, EXEC_SMALL_BYTES) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "executor: small region"); r->small_cap = EXEC_SMALL_BYTES; }
-  if (!r->d_ctr) { if (hipMalloc(&r->d_ctr, 65536) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "executor: barrier counter"); }
   if (!crux_scratch(c, (size_t)32 << 20)) return crux_fail(c, CRUX_ENOMEM, "executor: scratch");     // pre-sized: the scratch block must not move while pointers into it are recorded
   r->scratch_floor = c->scratch_bytes; r->scratch_off = 0;
   r->ops.clear(); r->readbacks.clear(); r->small_off = 0; r->active = true;
-  r->chain_tags.clear(); r->chain_base = 0; r->chain_ok = true; r->epoch_marks.clear(); r->dqp.on = false;
+  r->chain_tags.clear(); r->chain_base = 0; r->chain_ok = true; r->epoch_first = 0;
   return CRUX_OK;
 }
 // frees everything a context's executor ever allocated (called by crux_ctx_destroy after the stream has drained)
@@ -356,10 +178,8 @@ void crux_exec_destroy(crux_ctx* c) {
   if (!c || !c->rec) return;
   ExecRec* r = rec_of(c);
   if (r->small) (void)hipFree(r->small);
-  if (r->d_ctr) (void)hipFree(r->d_ctr);
   if (r->d_ops) (void)hipFree(r->d_ops);
   if (r->h_stage) (void)hipHostFree(r->h_stage);
-  if (r->dqp_buf) (void)hipFree(r->dqp_buf);
   for (int k = 0; k < 4; ++k) { if (r->h_ring[k]) (void)hipHostFree(r->h_ring[k]); if (r->h_ring_ev[k]) (void)hipEventDestroy((hipEvent_t)r->h_ring_ev[k]); }
   delete r; c->rec = nullptr;
 }
@@ -426,15 +246,15 @@ int32_t crux_exec_run(crux_ctx* c) {
   const size_t nops = r->ops.size();
   int32_t rc = CRUX_OK;
   if (nops) {
-    const size_t ob = nops * sizeof(ExecOp), rb = r->readbacks.size() * (sizeof(float) * CRUX_INFO_N + 16), need_h = ob + rb + 64;
+    const size_t ob = nops * sizeof(ExecOp), rb = r->readbacks.size() * (sizeof(float) * CRUX_INFO_N + 16), need_h = ob + rb;
     if (r->d_ops_cap < ob) { if (r->d_ops) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(r->d_ops); } r->d_ops_cap = ob * 2 + 4096; if (hipMalloc(&r->d_ops, r->d_ops_cap) != hipSuccess) { r->d_ops = nullptr; r->d_ops_cap = 0; return crux_fail(c, CRUX_ENOMEM, "executor: op list"); } }
     const bool async = r->async; r->async = false;
     void* stage = nullptr;
     r->ops.back().barrier &= 2;
-    // an asynchronous chain whose phases all travel in kernel arguments needs neither the device copy of the list nor the zeroed counters (no persistent form, no status
-    // read-back): two stream operations less between chains (they sit IN the stream there, ~15 us per chain)
+    // an asynchronous chain whose phases all travel in kernel arguments needs no device copy of the list: one stream operation less between chains (it sits IN the
+    // stream there)
     bool lean = false;
-    if (async && !r->dqp.on && !crux_sw().exec_no_kernarg) { lean = true;
+    if (async && !crux_sw().exec_no_kernarg) { lean = true;
       size_t i0 = 0;
       while (i0 < nops && lean) { size_t i1 = i0; unsigned blocks = 0; for (;;) { blocks += (r->ops[i1].barrier & 2) ? 0u : r->ops[i1].nblocks; if ((r->ops[i1].barrier & 1) || i1 + 1 == nops) break; ++i1; }
         if (blocks && !phasek_fits(r->ops, i0, i1)) lean = false;
@@ -447,58 +267,31 @@ int32_t crux_exec_run(crux_ctx* c) {
       if (r->h_ring_cap[k] < ob) { if (r->h_ring[k]) (void)hipHostFree(r->h_ring[k]); r->h_ring_cap[k] = ob * 2 + 4096;
         if (hipHostMalloc(&r->h_ring[k], r->h_ring_cap[k], hipHostMallocDefault) != hipSuccess) { r->h_ring[k] = nullptr; r->h_ring_cap[k] = 0; return crux_fail(c, CRUX_ENOMEM, "executor: staging ring"); } }
       stage = r->h_ring[k];
-      r->ops.back().barrier &= 2;
       memcpy(stage, r->ops.data(), ob);
       HIPCHK(c, hipMemcpyAsync(r->d_ops, stage, ob, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipEventRecord((hipEvent_t)r->h_ring_ev[k], c->stream));
     } else {
     if (r->h_stage_cap < need_h) { if (r->h_stage) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(r->h_stage); } r->h_stage_cap = need_h * 2 + 4096; if (hipHostMalloc(&r->h_stage, r->h_stage_cap, hipHostMallocDefault) != hipSuccess) { r->h_stage = nullptr; r->h_stage_cap = 0; return crux_fail(c, CRUX_ENOMEM, "executor: staging"); } }
-    r->ops.back().barrier &= 2;
     memcpy(r->h_stage, r->ops.data(), ob);
     HIPCHK(c, hipMemcpyAsync(r->d_ops, r->h_stage, ob, hipMemcpyHostToDevice, c->stream));
     }
-    if (!lean) HIPCHK(c, hipMemsetAsync(r->d_ctr, 0, 2048, c->stream));
-    // CRUX_EXEC_PERSISTENT (development): the one-XCD persistent executor, for synchronous calls only -- its status word (a workgroup that does not reach a barrier: the grid was
-    // not co-resident, which the register-heavy block kernels of round 4 cause) is read back by the synchronous path; an asynchronous chain would go on with garbage
-    const bool persistent = crux_sw().exec_persistent && !r->async && r->chain_tags.empty();      // (a chained recording carries op tags)
-    if (r->dqp.on) { r->dqp.on = false; rc = dqp_launch(c, r); if (rc) return rc; }
-    else if (!persistent) {
-      // default: one launch per phase over the whole chip (see k_phase). Measured against the persistent one-XCD form (CRUX_EXEC_PERSISTENT=1): the latter
-      // saves the launches but runs every op on 32 CUs behind one L2 and pays ~2 us per barrier; DESIGN 4.3 has the numbers.
-      size_t i0 = 0;
-      while (i0 < nops) { size_t i1 = i0; unsigned blocks = 0; for (;;) { blocks += (r->ops[i1].barrier & 2) ? 0u : r->ops[i1].nblocks; if ((r->ops[i1].barrier & 1) || i1 + 1 == nops) break; ++i1; }
-        if (blocks) {
-          // the phase's records travel in the kernel arguments when they fit (see k_phase_k); zero-block ops are dropped there
-          const bool no_kernarg = crux_sw().exec_no_kernarg;      // tests: every phase through the global-record form
-          if (no_kernarg || (!phasek_launch<384>(r->ops, i0, i1, blocks, c->stream) && !phasek_launch<1024>(r->ops, i0, i1, blocks, c->stream) && !phasek_launch<3840>(r->ops, i0, i1, blocks, c->stream)))
-            hipLaunchKernelGGL(k_phase, dim3(blocks), dim3(256), 0, c->stream, (const ExecOp*)r->d_ops + i0, (int)(i1 - i0 + 1));
-        }
-        i0 = i1 + 1; }
-    } else {
-    // the counter barrier relies on one shared L2: all workgroups on XCD 0 (workgroup i of a grid lands on XCD i mod 8, verified by the placement probe)
-    const int xcd = crux_x2_placement_ok_c(c) ? 0 : -2;
-    if (xcd == -2) return crux_fail(c, CRUX_EUNSUP, "executor: workgroups are not placed round-robin over the XCDs on this device");
-    const int G = EXEC_G;
-    const int xflags = crux_sw().exec_flags;      // 8: per-op timestamps of workgroups 0 and 1, printed below
-    hipLaunchKernelGGL(k_exec, dim3(G * 8), dim3(256), 0, c->stream, (const ExecOp*)r->d_ops, (int)nops, r->d_ctr, xcd, (int32_t*)(r->d_ctr + 264), xflags);
-    if (xflags & 8) { static int dumps = 0;
-      std::vector<unsigned long long> tb(2 * 512 * 3); HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(tb.data(), r->d_ctr + 1024, tb.size() * 8, hipMemcpyDeviceToHost));
-      if (dumps++ == 3) { double tw = 0, tbar = 0; const size_t nn = nops < 512 ? nops : 512;
-        for (size_t o = 0; o < nn; ++o) { const double w0 = (tb[o * 3 + 1] - tb[o * 3]) * 1e-3, b0 = (tb[o * 3 + 2] - tb[o * 3 + 1]) * 1e-3; tw += w0; tbar += b0;      // s_memtime ticks are shader cycles (~2 GHz)
-          fprintf(stderr, "[k_exec] op %3zu kid %2d blocks %4u barrier %d  work %7.2f kcycles  wait %7.2f kcycles\n", o, r->ops[o].kid, r->ops[o].nblocks, r->ops[o].barrier, w0, b0); }
-        fprintf(stderr, "[k_exec] %zu ops: work %.1f kcycles, barrier / wait %.1f kcycles (workgroup 0; shader cycles, ~0.5 ns each)\n", nn, tw, tbar); } }
-    }
-    rc = crux_launch_check(c, "k_exec"); if (rc) return rc;
+    // one launch per phase over the whole chip (see k_phase); the phase's records travel in the kernel arguments when they fit (see k_phase_k; zero-block ops are dropped
+    // there). DESIGN 4.3 has the numbers against the persistent one-XCD form this replaced.
+    size_t i0 = 0;
+    while (i0 < nops) { size_t i1 = i0; unsigned blocks = 0; for (;;) { blocks += (r->ops[i1].barrier & 2) ? 0u : r->ops[i1].nblocks; if ((r->ops[i1].barrier & 1) || i1 + 1 == nops) break; ++i1; }
+      if (blocks) {
+        const bool no_kernarg = crux_sw().exec_no_kernarg;      // tests: every phase through the global-record form
+        if (no_kernarg || (!phasek_launch<384>(r->ops, i0, i1, blocks, c->stream) && !phasek_launch<1024>(r->ops, i0, i1, blocks, c->stream) && !phasek_launch<3840>(r->ops, i0, i1, blocks, c->stream)))
+          hipLaunchKernelGGL(k_phase, dim3(blocks), dim3(256), 0, c->stream, (const ExecOp*)r->d_ops + i0, (int)(i1 - i0 + 1));
+      }
+      i0 = i1 + 1; }
+    rc = crux_launch_check(c, "k_phase"); if (rc) return rc;
     if (async) { r->ops.clear(); r->readbacks.clear(); return CRUX_OK; }      // nothing is read back: the list itself copied the info rows where the caller wants them
     char* hb = (char*)r->h_stage + ob;
     for (size_t k = 0; k < r->readbacks.size(); ++k) { char* h = hb + k * (sizeof(float) * CRUX_INFO_N + 16);
       HIPCHK(c, hipMemcpyAsync(h, r->readbacks[k].d_info, sizeof(float) * CRUX_INFO_N, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipMemcpyAsync(h + sizeof(float) * CRUX_INFO_N, r->readbacks[k].d_status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream)); }
-    int32_t* hst = (int32_t*)(hb + rb);
-    HIPCHK(c, hipMemcpyAsync(hst, r->d_ctr + 264, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (*hst) return crux_fail(c, *hst, "executor: the fused launch reported status %d (a workgroup did not reach a barrier)", *hst);
     for (size_t k = 0; k < r->readbacks.size(); ++k) { const char* h = hb + k * (sizeof(float) * CRUX_INFO_N + 16);
       if (r->readbacks[k].host_info) memcpy(r->readbacks[k].host_info, h, sizeof(float) * CRUX_INFO_N);
       int32_t st; memcpy(&st, h + sizeof(float) * CRUX_INFO_N, sizeof st);
@@ -507,8 +300,6 @@ int32_t crux_exec_run(crux_ctx* c) {
   r->ops.clear(); r->readbacks.clear();
   return rc;
 }
-extern "C" int crux_x2_placement_ok(crux_ctx* c);
-int32_t crux_x2_placement_ok_c(crux_ctx* c) { return crux_x2_placement_ok(c); }
 
 // ---- fused value_training epochs ------------------------------------------------------------------------------------------------------------
 int32_t crux_per_prepare(crux_buffer* source);      // per.hip: any full rebuild of the cumsum tree happens before the recording starts
@@ -544,9 +335,9 @@ int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
 //   update_priorities! per 16-sample tile | 4 the whole pullback ; leaf re-sums | 5 norm ; root paths | 6 info, Adam | 7 beta-power advance
 // In a chain the sampling of epoch e + 1 (phases 0, 1) sits beside the norm and Adam of epoch e -- after the root paths of phase 5 --, its phase 2 beside the advance.
 static bool dqn_tile_case(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, crux_buffer* batch) {
-  const bool on = crux_sw().sac_tile_ops && !exec_persistent_on(net->ctx) && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
-  const int64_t B = batch->capacity; crux_ctx* c = net->ctx;
-  if (!on || c->per_split_sample || !net->has_adam) return false;
+  const bool on = crux_sw().sac_tile_ops && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
+  const int64_t B = batch->capacity;
+  if (!on || !net->has_adam) return false;
   if (source->prioritized && !crux_per_fused_gather()) return false;
   crux_mlp* both[2] = {net, tnet};
   for (crux_mlp* n : both) if (n->nd.L != 3 || !crux_dense_fwd_fused(n) || n->nd.acts[2] != CRUX_ACT_IDENTITY || n->nd.dims[2] != net->nd.dims[2] || n->nd.dims[3] != net->nd.dims[3] || n->nd.dims[0] != batch->obs_dim) return false;
@@ -563,7 +354,7 @@ static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* sourc
   const bool touch_split = per && (B > 256 || source->per_full_dirty);      // (root paths as an op of their own in 5: the search then waits one launch longer)
   const int ov = touch_split ? 2 : 3;
   auto bail = [&](int32_t e) { crux_exec_abort(c); return e; };
-  size_t m = exec_mark(c); const size_t ops0 = m; r->epoch_marks.push_back(ops0);
+  size_t m = exec_mark(c); const size_t ops0 = m; r->epoch_first = ops0;
   auto sect = [&](auto&& rule) { for (size_t i = m; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid); if (p < 0) { plan_ok = false; p = 0; }
       ph.push_back(ph_tag(base > 0 ? base + p - ov : p, 0)); } m = r->ops.size(); };
   auto only = [&](int p) { sect([p](int) { return p; }); };
@@ -648,11 +439,11 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
   // as ov <= nb + 1; without the group the chain is update | leaf | paths at 4 + nf - sq .., and ov <= nb as before.
   const NetPlan pn = net_plan(net, B); const bool ffw = crux_dense_fwd_fused(net);
   const int nf = pn.nf, nb = pn.nb;
-  const int sq0 = (B <= 256 && !exec_persistent_on(c)) ? 1 : 0;
+  const int sq0 = B <= 256 ? 1 : 0;
   const bool tailp = per && sq0 == 1;
   // sph: with the search and the gather in one launch (PerSampleGatherOp) the sampling of an epoch is phase 1 alone, so the search of epoch e + 1 sits one phase later and the
   // overlap may be one deeper
-  const int sph = (per && crux_per_fused_gather() && !c->per_split_sample) ? 1 : 0;
+  const int sph = (per && crux_per_fused_gather()) ? 1 : 0;
   const int ovmax = (tailp ? nb + 1 : nb) + sph;
   const int ov = per ? (ovmax < 1 ? 1 : (ovmax < 3 ? ovmax : 3)) : 3;
   auto tag = [&](size_t from, auto&& rule) { if (!fuse || !crux_exec_recording(c)) return; ExecRec* r = rec_of(c); int g = 0; const int base = r->chain ? r->chain_base : 0;
@@ -660,12 +451,12 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
       const int sub = p >> 12; p &= 4095;
       ph.push_back(ph_tag(base > 0 ? (p < 2 ? base - ov + p : base + p - ov) : p, sub)); } };
   // the target (one block at B <= 256) and the loss head (one block) are a sequential pair: the head runs in the target's block, right after it, and every later
-  // phase moves up by one (sq). Not in the persistent one-XCD form, whose workgroups walk the ops of a phase in lockstep.
+  // phase moves up by one (sq).
   const int sq = sq0;
   if (crux_dense_fwd_fused(target_net) != ffw) plan_ok = false;
   rc = piece(1); if (rc) return bail(rc);
   const size_t ops0 = fuse && crux_exec_recording(c) ? exec_mark(c) : 0;      // first op of THIS epoch (a chained recording already holds the earlier epochs)
-  if (fuse && crux_exec_recording(c) && rec_of(c)->chain) rec_of(c)->epoch_marks.push_back(ops0);
+  if (fuse && crux_exec_recording(c) && rec_of(c)->chain) rec_of(c)->epoch_first = ops0;
   size_t m = ops0;
   rc = per ? crux_per_sample(batch, source, B, nullptr, beta, sample_counter) : crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
   tag(m, [&](int kid, int&) { return (kid == OP_PER_SEARCH || kid == OP_UNIFORM_IDS) ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
@@ -715,36 +506,14 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
   crux_ctx* c = net->ctx;
   const bool fuse = net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && target_net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch &&
                     !crux_sw().no_chained_epochs;
-  // 256-wide networks of the shapes dqn_persist.h instantiates: the whole chain as two persistent kernels. OPT-IN (CRUX_DQN_PERSIST=1): correct (tests/test_gpu_round3.py)
-  // but measured SLOWER than the phase launches in round 3 -- 113-125 us against 73-79 us per C3 epoch (DESIGN 4.3 has the in-kernel timeline) -- so the default stays
-  // with the phases.
-  const int64_t Bc = batch->capacity;
-  const bool persist = fuse && softq_alpha == 0.f && net->nd.L == 3 && target_net->nd.L == 3 && net->nd.dims[1] == 256 && net->nd.dims[2] == 256 && target_net->nd.dims[1] == 256 && target_net->nd.dims[2] == 256 &&
-                       net->nd.dims[0] == target_net->nd.dims[0] && net->nd.dims[3] == target_net->nd.dims[3] && dqp_shape(net->nd.dims[0], net->nd.dims[3], Bc) &&
-                       net->nd.acts[0] == CRUX_ACT_RELU && net->nd.acts[1] == CRUX_ACT_RELU && net->nd.acts[2] == CRUX_ACT_IDENTITY &&
-                       target_net->nd.acts[0] == CRUX_ACT_RELU && target_net->nd.acts[1] == CRUX_ACT_RELU && target_net->nd.acts[2] == CRUX_ACT_IDENTITY &&
-                       net->has_adam && batch->obs_dim == net->nd.dims[0] && batch->act_kind == CRUX_ACTION_DISCRETE && batch->act_dim == net->nd.dims[3] && (!use_weight || has_col(batch, CRUX_COL_WEIGHT)) &&
-                       crux_sw().dqn_persist && !c->dqp_broken && crux_x2_placement_ok_c(c);
   auto flush = [&]() -> int32_t {
     if (!crux_exec_recording(c)) return CRUX_OK;
     ExecRec* r = rec_of(c); r->chain = false;
-    if (persist) {
-      ExecRec::Dqp& d = r->dqp; d.in = net->nd.dims[0]; d.out = net->nd.dims[3]; d.bt = (int)(Bc / 16); d.n_epochs = (int)r->epoch_marks.size(); d.net = net; d.tnet = target_net; d.batch = batch;
-      d.gamma = gamma; d.use_weight = use_weight != 0; d.d_err = source->prioritized ? (float*)((char*)c->epoch_tmp + ((4 * (size_t)Bc + 255) / 256) * 256) : nullptr;
-      int32_t rp = dqp_build(r);
-      if (!rp) rp = crux_ensure_aux_stream(c);
-      if (!rp && !r->dqp_buf && hipMalloc(&r->dqp_buf, DQP_BUF_BYTES) != hipSuccess) { r->dqp_buf = nullptr; rp = CRUX_ENOMEM; }
-      if (!rp) { d.on = true; const int32_t rr = crux_exec_run(c);
-        if (rr == CRUX_EHIP) c->dqp_broken = true;      // a wait timed out (the two kernels did not run side by side): later chains take the phase launches
-        return rr; }
-    }
     if (r->chain_ok && r->chain_tags.size() == r->ops.size()) { const int32_t rs = exec_schedule(c, r->chain_tags); if (rs) { crux_exec_abort(c); return rs; } }
     r->async = d_infos_async != nullptr;
     return crux_exec_run(c);
   };
   int32_t rc = CRUX_OK; int in_chain = 0;
-  struct SplitGuard { crux_ctx* c; bool old; ~SplitGuard() { c->per_split_sample = old; } } split_guard{c, c->per_split_sample};
-  if (persist) c->per_split_sample = true;
   for (int e = 0; e < n_epochs; ++e) {
     float* info_e = infos ? infos + (size_t)e * CRUX_INFO_N : nullptr;
     if (!fuse) { if (d_infos_async) return CRUX_EUNSUP;      // narrow networks run call by call with a read-back per epoch: the caller takes the synchronous entry point
@@ -762,7 +531,7 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
     if (d_infos_async && !tiles) {      // the epoch's info row goes to the caller's device array, copied in the epoch's last phase (one phase after the info op wrote it)
       ExecRec* r = rec_of(c);
       crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_infos_async + (size_t)e * CRUX_INFO_N, (const float*)r->readbacks.back().d_info, (int64_t)CRUX_INFO_N);
-      int tmax = 0; for (size_t k = r->epoch_marks.empty() ? 0 : r->epoch_marks.back(); k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);      // the epoch's last phase (the beta-power advance)
+      int tmax = 0; for (size_t k = r->epoch_first; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);      // the epoch's last phase (the beta-power advance)
       r->chain_tags.push_back(tmax + (tiles ? 4 : 0)); }      // (tile plan: the info op sits IN the epoch's last phase -- the copy joins the launch after it)
     ++in_chain;
   }
@@ -771,7 +540,7 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
   if (fuse && polyak_tau >= 0.f && in_chain > 0) {
     ExecRec* r = rec_of(c); const size_t n0 = r->ops.size();
     rc = crux_polyak(target_net, net, polyak_tau); if (rc) { r->chain = false; crux_exec_abort(c); return rc; }
-    int tmax = 0; for (size_t k = r->epoch_marks.empty() ? 0 : r->epoch_marks.back(); k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);
+    int tmax = 0; for (size_t k = r->epoch_first; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);
     for (size_t k = n0; k < r->ops.size(); ++k) r->chain_tags.push_back(tmax);
   }
   return fuse ? flush() : rc;
@@ -830,7 +599,7 @@ int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* b, float*
 // The order inside every chain is the reference's (temperature, critic and actor each see what the previous step left; sac_target reads log alpha BEFORE the temperature
 // update lands, the actor head after). Same arithmetic as the generic recording below (tools/fused_check.py compares the two bit for bit); false = not this case.
 static bool sac_tile_case(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* q1t, crux_mlp* q2t, crux_buffer* source, crux_buffer* batch, int32_t uc, int32_t ua) {
-  const bool on = crux_sw().sac_tile_ops && !exec_persistent_on(actor->ctx) && !crux_sw().no_fused_epoch;      // (read per call: tests switch forms inside one process)
+  const bool on = crux_sw().sac_tile_ops && !crux_sw().no_fused_epoch;      // (read per call: tests switch forms inside one process)
   if (!on || !uc || !ua || source->prioritized) return false;
   const int64_t B = batch->capacity; crux_mlp* all[5] = {actor, q1, q2, q1t, q2t};
   for (crux_mlp* n : all) { if (n->nd.L != 3 || !crux_dense_fwd_fused(n) || n->nd.acts[2] != CRUX_ACT_IDENTITY || n->nd.dims[2] != actor->nd.dims[2]) return false; }
@@ -974,7 +743,7 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
   // The order inside every chain is the reference's (temperature before critic before actor: each sees the parameters the previous step left).
   // sq: sac_target (one block at B <= 256) and the critic heads (one block each) form a sequential group in ONE block of phase X when the critics train; the critic
   // chain and everything behind it (Y ..) then sit one phase earlier. The temperature chain (X .. X + 3) is independent of it.
-  const int sq = (update_critic && B <= 256 && !exec_persistent_on(c)) ? 1 : 0;
+  const int sq = (update_critic && B <= 256) ? 1 : 0;
   // Round 4: written in launches -- FA / FQ forward launches of the actor / a critic, BQ / BA phases of a pullback with parameter gradients (BQo ops per critic), LQ phases
   // of a critic's input-gradient chain; with the fused block kernels FA = FQ = L - 1 and BQ = BA = L - 1 (net_plan above), otherwise all equal L as in round 3.
   const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);
@@ -1134,7 +903,7 @@ static int32_t dpg_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* 
   //   0 ids | 1 gather, fills | 2.. target actor(sp) forward ; vcat(s, a) ; actor(s) forward of the ACTOR step | 2+LA target action (+ smoothing noise) ; mu(s) -> vcat(s, mu(s))
   //   3+LA.. target Q1 || Q2 forward (and, from 3: Q1 || Q2 forward on (s, a)) | X target | X+1 critic heads | X+2.. critic backward | norm | info, Adam | advance
   //   Y.. Q(s, mu(s)) forward | its input gradient | slice | actor backward | norm | info, Adam | advance, polyak
-  const int sq = (update_critic && B <= 256 && !exec_persistent_on(c)) ? 1 : 0;      // target + critic head(s) as a sequential one-block group (see crux_sac_epoch)
+  const int sq = (update_critic && B <= 256) ? 1 : 0;      // target + critic head(s) as a sequential one-block group (see crux_sac_epoch)
   const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);      // launches per pass (see crux_sac_epoch)
   std::vector<int> ph; bool plan_ok = true; const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
   const int ag = actor->nd.acts[LA - 1] != CRUX_ACT_IDENTITY ? 1 : 0;
@@ -1265,7 +1034,7 @@ int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
 }
 }  // extern "C"
 
-// test hook: value(pi, x) through the executor (the same tile bodies as crux_mlp_forward_cached, run by k_exec) -- tests compare the two bit for bit
+// test hook: value(pi, x) through the executor (the same tile bodies as crux_mlp_forward_cached, run by the phase kernels) -- tests compare the two bit for bit
 extern "C" int32_t crux_debug_exec_forward(crux_mlp* net, const float* d_x, int64_t B, float* d_y, int32_t with_backward, const float* d_dy) {
   if (!net || !d_x || !d_y) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; int32_t rc = crux_exec_begin(c); if (rc) return rc;

@@ -1,4 +1,4 @@
-// offpolicy_unit.hip -- one translation unit for the off-policy dense engine, replay sampling and the fused-step executor: k_exec (exec.hip) calls
+// offpolicy_unit.hip -- one translation unit for the off-policy dense engine, replay sampling and the fused-step executor: its phase kernels (exec.hip) call
 // the op bodies defined in dense.hip, sac.hip and per.hip (cql.hip uses the dense engine's and sac.hip's helpers), and device code is not linked across translation units in this build.
 #include "dense.hip"
 #include "sac.hip"

@@ -463,7 +463,7 @@ int32_t crux_per_sample(crux_buffer* target, crux_buffer* source, int64_t B, con
   double* d_r = nullptr;
   if (rands) { d_r = (double*)crux_scratch(c, 8 * (size_t)B + 256); if (!d_r) return crux_fail(c, CRUX_ENOMEM, "prioritized_sample!: scratch");
     HIPCHK(c, hipMemcpyAsync(d_r, rands, 8 * (size_t)B, hipMemcpyHostToDevice, c->stream)); }
-  const bool fuse_gather = crux_per_fused_gather() && !c->per_split_sample;
+  const bool fuse_gather = crux_per_fused_gather();
   crux_prof_begin(c, CRUX_PROF_PER_SEARCH);
   if (fuse_gather) {
     PerSampleArgs a{}; a.run = source->cumsum; a.total = source->topo_total; a.pr = source->priorities; a.pminmax = source->pminmax; a.N = N; a.B = B; a.nlev = source->topo_levels; a.rands = d_r;

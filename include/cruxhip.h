@@ -504,8 +504,7 @@ int32_t crux_td_step_with_error(crux_mlp* net, crux_buffer* batch, const float* 
  * update_priorities!(source, batch.indices, td_error) -> train!(net, td_loss[, weight]) (:91-93). Results equal the separate calls
  * (crux_per_sample / crux_uniform_sample, crux_dqn_target, crux_td_step[_with_error], crux_per_update_device) in that order, bit for bit. For networks
  * at least 128 wide the ~25 kernel bodies of the epoch are recorded as ops and run by the executor (csrc/exec.hip): ops that do not depend on each
- * other share a launch (13 phase launches over the whole chip instead of ~25, info rows read back once), or -- CRUX_EXEC_PERSISTENT=1 -- by ONE
- * persistent launch on one XCD with L2 counter barriers between dependent ops. info_out: LOSS, GRAD_NORM, [2] = Qavg.                             */
+ * other share a launch (13 phase launches over the whole chip instead of ~25, info rows read back once). info_out: LOSS, GRAD_NORM, [2] = Qavg.  */
 int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
                        uint64_t sample_counter, float* info_out);
 /* The epoch loop of value_training (off_policy.jl:69: `for epoch in 1:c_opt.epochs`; DQN's c_opt.epochs = dN, rl/dqn.jl) as ONE recorded list: n_epochs epochs back to

@@ -1,6 +1,6 @@
 """The CRUX_* switches that select between two forms of the same computation, each against the default form: whatever a run leaves behind must be the same bits.
 (The other switches have tests of their own: CRUX_FS / CRUX_MFMA_X2 / CRUX_FORCE_GENERIC in test_gpu_fs2.py, test_gpu_ppo_parity.py, test_gpu_round3.py;
-CRUX_SPEC_PAIR, CRUX_DENSE_FUSED, CRUX_PER_FUSED_GATHER, CRUX_SAC_TILE_OPS in test_gpu_round4.py; CRUX_PUSH_FUSED in test_gpu_round5.py; CRUX_DQN_PERSIST, CRUX_EXEC_NO_KERNARG,
+CRUX_SPEC_PAIR, CRUX_DENSE_FUSED, CRUX_PER_FUSED_GATHER, CRUX_SAC_TILE_OPS in test_gpu_round4.py; CRUX_PUSH_FUSED in test_gpu_round5.py; CRUX_EXEC_NO_KERNARG,
 CRUX_SMALL_SOLVE_GENERIC in test_gpu_round3.py / test_gpu_round2.py. DESIGN.md section 8.2 has the table.)"""
 import os
 import sys
@@ -48,12 +48,11 @@ def test_on_policy_switch_forms_are_bit_identical(gpu_ctx, monkeypatch, switch, 
     _same(ref[1:], got[1:], ("actor", "critic", "s", "advantage"))
 
 
-@pytest.mark.parametrize("switch,value", [("CRUX_NO_CHAINED_EPOCHS", "1"), ("CRUX_NO_FUSED_EPOCH", "1"), ("CRUX_SYNC_CHAINS", "1"), ("CRUX_EXEC_PERSISTENT", "1")],
-                         ids=["no_chained_epochs", "no_fused_epoch", "sync_chains", "exec_persistent_is_ignored_by_asynchronous_chains"])
+@pytest.mark.parametrize("switch,value", [("CRUX_NO_CHAINED_EPOCHS", "1"), ("CRUX_NO_FUSED_EPOCH", "1"), ("CRUX_SYNC_CHAINS", "1")],
+                         ids=["no_chained_epochs", "no_fused_epoch", "sync_chains"])
 def test_off_policy_switch_forms_are_bit_identical(gpu_ctx, monkeypatch, switch, value):
     """a DQN + prioritized-replay solve on a full ring (8-256-256-4, 24 iterations of 4 steps + 4 epochs): the epochs call by call / one recording per epoch / chains with a
-    read-back after each, against the default chained phase launches. CRUX_EXEC_PERSISTENT (the one-XCD persistent executor, development) applies to synchronous calls only: an
-    asynchronous chain cannot read its status word back, so solve's chains must ignore it."""
+    read-back after each, against the default chained phase launches."""
     monkeypatch.setenv(switch, value); ref = _small_per_solve()
     monkeypatch.delenv(switch); got = _small_per_solve()
     _same(ref, got, ("params", "priorities", "cumsum", "max_priority", "min_priority", "indices", "s"))
