@@ -48,16 +48,16 @@ struct ExecReadback { float* host_info; const float* d_info; const int32_t* d_st
 struct ExecRec {
   std::vector<ExecOp> ops;
   bool active = false;
-  char* small = nullptr; size_t small_cap = 0, small_off = 0;     // device: per-piece info rows / statistics / status words that outlive the piece until the read-back
+  char* small = nullptr; size_t small_cap = 0, small_off = 0;     // device: the recorded steps' info rows / statistics / status words, valid until the read-back
   std::vector<ExecReadback> readbacks;
   void* d_ops = nullptr; size_t d_ops_cap = 0;                     // device copy of the op list
   void* h_stage = nullptr; size_t h_stage_cap = 0;                 // pinned staging of the op list and of the read-backs
   size_t scratch_floor = 0, scratch_off = 0;                       // scratch requests made while recording are carved one after the other from the pre-sized block
-  // chained epochs (crux_dqn_epochs / crux_sac_epochs): several value_training epochs recorded into ONE list, scheduled and run once -- no host round trip between
-  // the epochs of an iteration. While `chain` is set the per-epoch entry points append their phase tags (offset by chain_base) instead of scheduling and running.
+  // chained epochs (run_epoch_chains in exec.hip: crux_dqn_epochs, crux_sac_epochs, crux_dpg_epochs and their asynchronous forms): several value_training epochs recorded
+  // into ONE list, scheduled and run once -- no host round trip between the epochs of an iteration. While `chain` is set the per-epoch recorders append their phase tags
+  // (offset by chain_base, see EpochTags) instead of scheduling and running; chain_ok = false sends the list through unscheduled.
   bool chain = false, chain_ok = true; int chain_base = 0; std::vector<int> chain_tags;
-  size_t epoch_first = 0;                  // first op of the epoch recorded last: ops appended behind it (info-row copy, target update) join that epoch's last phase
-  // asynchronous runs (crux_dqn_epochs_async): no read-back, no host synchronisation -- the info rows are copied to a caller-owned device array by ops of the list itself.
+  // asynchronous runs (crux_*_epochs_async): no read-back, no host synchronisation -- the info rows are copied to a caller-owned device array by ops of the list itself.
   // The op list is uploaded from a ring of pinned staging buffers, so the host may record and enqueue up to three chains ahead of the one the device is running.
   bool async = false;
   float* info_row_override = nullptr;      // asynchronous tile-plan epochs: the epoch's info op writes the caller's device row itself (no copy op, no extra phase behind the chain's last epoch)

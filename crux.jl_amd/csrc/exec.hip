@@ -170,7 +170,7 @@ int32_t crux_exec_begin(crux_ctx* c) {
   if (!crux_scratch(c, (size_t)32 << 20)) return crux_fail(c, CRUX_ENOMEM, "executor: scratch");     // pre-sized: the scratch block must not move while pointers into it are recorded
   r->scratch_floor = c->scratch_bytes; r->scratch_off = 0;
   r->ops.clear(); r->readbacks.clear(); r->small_off = 0; r->active = true;
-  r->chain_tags.clear(); r->chain_base = 0; r->chain_ok = true; r->epoch_first = 0;
+  r->chain_tags.clear(); r->chain_base = 0; r->chain_ok = true;
   return CRUX_OK;
 }
 // frees everything a context's executor ever allocated (called by crux_ctx_destroy after the stream has drained)
@@ -208,7 +208,6 @@ int32_t crux_exec_zero(crux_ctx* c, void* d_ptr, size_t bytes, hipStream_t st) {
 }
 // Phases: ops that do not depend on each other share a barrier. The caller assigns every recorded op a phase number (non-decreasing along every
 // dependency chain); the list is stably sorted by phase and only the last op of a phase keeps its barrier.
-static size_t exec_mark(crux_ctx* c) { return rec_of(c)->ops.size(); }
 // Tags are 4 * phase + sub: sub 0 = an ordinary op of the phase; sub 1 = head of a sequential group, sorted behind the ordinary ops; sub 2 = runs in the block of
 // the op sorted before it, after it (both must be one-block ops: the caller only tags such pairs -- PH_SEQ_HEAD / PH_SEQ_TAIL below).
 static int32_t exec_schedule(crux_ctx* c, const std::vector<int>& phase) {
@@ -303,6 +302,111 @@ int32_t crux_exec_run(crux_ctx* c) {
 
 // ---- fused value_training epochs ------------------------------------------------------------------------------------------------------------
 int32_t crux_per_prepare(crux_buffer* source);      // per.hip: any full rebuild of the cumsum tree happens before the recording starts
+
+// The phase tags of one recorded epoch. tag(rule) tags the ops recorded since the last tag by rule(kid, g) -> phase | PH_SEQ_* (g: a counter the rule may use,
+// zero for every call); a miss (-1) sends the epoch through unscheduled. Inside a chain (ExecRec::chain) every phase moves to the chain's base: phases 0 and 1
+// (the epoch's sampling) back by `lead`, every later phase back by `rest` -- the overlap with the epoch before. finish(len) ends an epoch of `len` phases: inside a
+// chain its tags join the chain's, otherwise the list is scheduled and run. Without a recording (r = NULL: the epoch runs call by call) it does nothing.
+struct EpochTags {
+  crux_ctx* c; ExecRec* r; const char* who; int lead, rest, base = 0; size_t first = 0, m = 0; bool plan_ok = true; std::vector<int> ph;
+  EpochTags(crux_ctx* c_, bool on, const char* who_, int lead_, int rest_) : c(c_), r(on ? rec_of(c_) : nullptr), who(who_), lead(lead_), rest(rest_) {
+    if (r) { base = r->chain ? r->chain_base : 0; first = m = r->ops.size(); } }
+  template <class Rule> void tag(Rule&& rule) {
+    if (!r) return;
+    int g = 0;
+    for (size_t i = m; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid, g);
+      if (p < 0) { if (crux_sw().verbose) fprintf(stderr, "[cruxhip] %s: op kind %d has no phase in the plan\n", who, r->ops[i].kid); plan_ok = false; p = 0; }
+      const int sub = p >> 12; p &= 4095;
+      ph.push_back(ph_tag(base > 0 ? base + p - (p < 2 ? lead : rest) : p, sub)); }
+    m = r->ops.size(); }
+  void only(int p) { tag([p](int, int&) { return p; }); }
+  int32_t finish(int len) {
+    if (!r) return CRUX_OK;
+    if (r->chain) {      // the chain's driver (run_epoch_chains) schedules and runs the whole list
+      if (!(plan_ok && ph.size() == r->ops.size() - first)) r->chain_ok = false;
+      r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += len - (r->chain_base > 0 ? rest : 0);
+      return CRUX_OK; }
+    if (plan_ok && ph.size() == r->ops.size()) { const int32_t rc = exec_schedule(c, ph); if (rc) { crux_exec_abort(c); return rc; } }
+    return crux_exec_run(c); }
+};
+
+// value_training's epoch loop (off_policy.jl:69: `for epoch in 1:c_opt.epochs`) as chains of up to 8 epochs, each ONE recorded list: the epochs are recorded back to back
+// (record(e) records epoch e, its phases following those of epoch e - 1), and the host schedules, uploads and launches once per chain. A prioritized source (per) also
+// ends a chain where its replay tree needs a full rebuild, and is brought up to date before every chain. chain = false: epoch by epoch, each run on its own.
+// d_rows (asynchronous runs): the caller's device array [n_epochs][nrows][CRUX_INFO_N]; rows(e) names the info rows epoch e registers (bit k: row k, in the order the
+// steps ran) and the phase their copies join: `shift` phases after the epoch's last (tile plans: the info op sits IN the last phase), none for shift < 0 (the epoch's
+// info op writes the caller's row itself). tail() records ops that join the last epoch's last phase (the DQN family's target update).
+struct EpochRows { unsigned has; int shift; };
+template <class Record, class Rows, class Tail>
+static int32_t run_epoch_chains(crux_ctx* c, const char* who, bool chain, crux_buffer* per, int32_t n_epochs, int nrows, float* d_rows, Record&& record, Rows&& rows, Tail&& tail) {
+  int32_t rc = CRUX_OK;
+  if (!chain) { if (d_rows) return CRUX_EUNSUP;      // call by call, with a read-back per epoch: the caller takes the synchronous entry point
+    for (int e = 0; e < n_epochs; ++e) { rc = record(e); if (rc) return rc; }
+    return CRUX_OK; }
+  auto fail = [&](int32_t e) { if (c->rec) rec_of(c)->chain = false; crux_exec_abort(c); return e; };
+  auto flush = [&]() -> int32_t {
+    if (!crux_exec_recording(c)) return CRUX_OK;
+    ExecRec* r = rec_of(c); r->chain = false;
+    if (r->chain_ok && r->chain_tags.size() == r->ops.size()) { const int32_t rs = exec_schedule(c, r->chain_tags); if (rs) { crux_exec_abort(c); return rs; } }
+    r->async = d_rows != nullptr;
+    return crux_exec_run(c);
+  };
+  size_t tg0 = 0;      // the first tag of the epoch recorded last
+  auto last_phase = [&]() { const ExecRec* r = rec_of(c); int t = 0; for (size_t k = tg0; k < r->chain_tags.size(); ++k) t = std::max(t, r->chain_tags[k] & ~3); return t; };
+  int in_chain = 0;
+  for (int e = 0; e < n_epochs; ++e) {
+    // a priority tree that needs a plain rebuild (the ring is still filling, or a bulk change) cannot be refreshed inside a recording: run what is recorded first
+    if (in_chain && (in_chain >= 8 || (per && per->per_full_dirty))) { rc = flush(); in_chain = 0; if (rc) return rc; }
+    if (!in_chain) { if (per) { rc = crux_per_prepare(per); if (rc) return rc; }
+      rc = crux_exec_begin(c); if (rc) return rc; }
+    ExecRec* r = rec_of(c); r->chain = true;
+    const size_t rb0 = r->readbacks.size(); tg0 = r->chain_tags.size();
+    rc = record(e); if (rc) return fail(rc);
+    if (d_rows) {      // the epoch's info rows go to the caller's device array, copied in the epoch's last phase (one phase after the info ops wrote them)
+      const EpochRows er = rows(e);
+      if (!crux_exec_recording(c) || r->readbacks.size() != rb0 + (size_t)__builtin_popcount(er.has) || r->chain_tags.size() != r->ops.size())
+        return fail(crux_fail(c, CRUX_EHIP, "%s epochs (async): unexpected recording", who));
+      if (er.shift >= 0) { const int t = last_phase() + er.shift; size_t q = rb0;
+        for (int k = 0; k < nrows; ++k) { if (!(er.has >> k & 1)) continue;
+          crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_rows + ((size_t)e * nrows + k) * CRUX_INFO_N, (const float*)r->readbacks[q++].d_info, (int64_t)CRUX_INFO_N);
+          r->chain_tags.push_back(t); } } }
+    ++in_chain;
+  }
+  ExecRec* r = rec_of(c); const size_t n0 = r->ops.size();
+  rc = tail(); if (rc) return fail(rc);
+  if (r->ops.size() > n0) r->chain_tags.insert(r->chain_tags.end(), r->ops.size() - n0, last_phase());
+  return flush();
+}
+// More than one chain per call (n_epochs > 8): run(d_rows) runs the chains back to back in their asynchronous form, with the info rows in a device block of the
+// context, and the host synchronises ONCE, at the end of the call: the device no longer idles while the host reads back, records and uploads the next chain (C4, 50
+// epochs per call: 180 -> ~155 us per epoch). Same results; a NaN gradient norm is reported from the rows. has(e) and dst[k] (host [n_epochs x CRUX_INFO_N] or NULL):
+// the rows of epoch e (see run_epoch_chains) and where row k goes.
+template <class Run, class Has>
+static int32_t epochs_one_readback(crux_ctx* c, const char* who, const char* family, int32_t n_epochs, int nrows, float* const* dst, Run&& run, Has&& has) {
+  const size_t need = sizeof(float) * nrows * CRUX_INFO_N * (size_t)n_epochs;
+  if (c->epoch_rows_bytes < need) { if (c->epoch_rows) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_rows); c->epoch_rows = nullptr; c->epoch_rows_bytes = 0; }
+    if (hipMalloc(&c->epoch_rows, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "%s epochs: info rows", who); c->epoch_rows_bytes = 2 * need; }
+  HIPCHK(c, hipMemsetAsync(c->epoch_rows, 0, need, c->stream));
+  const int32_t rc = run((float*)c->epoch_rows); if (rc) return rc;
+  std::vector<float> rows((size_t)nrows * CRUX_INFO_N * (size_t)n_epochs);
+  HIPCHK(c, hipMemcpyAsync(rows.data(), c->epoch_rows, need, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
+  bool nan = false;
+  for (int e = 0; e < n_epochs; ++e) { const unsigned h = has(e);
+    for (int k = 0; k < nrows; ++k) { if (!(h >> k & 1)) continue;
+      const float* row = rows.data() + ((size_t)e * nrows + k) * CRUX_INFO_N;
+      if (row[CRUX_INFO_GRAD_NORM] != row[CRUX_INFO_GRAD_NORM]) nan = true;
+      if (dst[k]) memcpy(dst[k] + (size_t)e * CRUX_INFO_N, row, sizeof(float) * CRUX_INFO_N); } }
+  if (nan) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in the %s epochs", family);
+  return CRUX_OK;
+}
+// c->epoch_tmp with at least `bytes` (targets and td errors of the epochs run call by call: a block of the context that no recording carves)
+static int32_t grow_epoch_tmp(crux_ctx* c, size_t bytes, int64_t B, const char* who) {
+  if (c->epoch_tmp_bytes >= bytes) return CRUX_OK;
+  if (c->epoch_tmp) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_tmp); }
+  c->epoch_tmp_bytes = 16 * (size_t)B + 4096;
+  if (hipMalloc(&c->epoch_tmp, c->epoch_tmp_bytes) != hipSuccess) { c->epoch_tmp = nullptr; c->epoch_tmp_bytes = 0; return crux_fail(c, CRUX_ENOMEM, "%s: targets", who); }
+  return CRUX_OK;
+}
 // softq_target(alpha) (rl/softq.jl:4-13). Lives in this translation unit so that the stand-alone kernel and the executor's phase kernel are compiled under the same
 // floating-point contraction setting (exp / log are inlined library code: the two forms must agree bit for bit).
 int32_t crux_mlp_forward_impl(crux_mlp* net, const float* d_x, int64_t B, float* d_y, const float* params_override);
@@ -334,6 +438,10 @@ int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
 //   0 [uniform ids] | 1 prioritized search + gather in one launch (or the gather), zero-fills | 2 layers 0+1 of Q(s) and Q-(s') | 3 both output layers + target + td head +
 //   update_priorities! per 16-sample tile | 4 the whole pullback ; leaf re-sums | 5 norm ; root paths | 6 info, Adam | 7 beta-power advance
 // In a chain the sampling of epoch e + 1 (phases 0, 1) sits beside the norm and Adam of epoch e -- after the root paths of phase 5 --, its phase 2 beside the advance.
+// does the network pair take the recorded chain of crux_dqn_epochs* (wide enough for the dense engine; fused and chained epochs not switched off)?
+static bool dqn_chain_case(const crux_mlp* net, const crux_mlp* tnet) {
+  return net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && tnet->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
+}
 static bool dqn_tile_case(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, crux_buffer* batch) {
   const bool on = crux_sw().sac_tile_ops && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
   const int64_t B = batch->capacity;
@@ -347,53 +455,48 @@ static bool dqn_tile_case(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, cr
 static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
                                uint64_t sample_counter, float* info_out, float* d_y, float* d_err) {
   crux_ctx* c = net->ctx; const int64_t B = batch->capacity; const bool per = source->prioritized; const int nout = net->nd.dims[3], K = net->nd.dims[2];
-  ExecRec* r = rec_of(c); const int base = r->chain_base; std::vector<int> ph; bool plan_ok = true; int32_t rc;
+  int32_t rc;
   // Phases: 0 uniform ids | 1 search + gather / gather | 2 forward (both nets) | 3 td tile (+ update_priorities!) | 4 pullback || leaf re-sum -> root paths (LeafTouchOp) |
   // 5 norm || Adam (AdamSelfOp) | 6 info, beta-power advance. Chained: the sampling of epoch e + 1 runs beside the tail of epoch e -- ids beside 4, search + gather beside 5 (the
   // replay tree is complete after 4; the gather rewrites the batch rows the pullback read: not before 5), forward beside 6 (after Adam): FOUR launches per epoch.
   const bool touch_split = per && (B > 256 || source->per_full_dirty);      // (root paths as an op of their own in 5: the search then waits one launch longer)
   const int ov = touch_split ? 2 : 3;
   auto bail = [&](int32_t e) { crux_exec_abort(c); return e; };
-  size_t m = exec_mark(c); const size_t ops0 = m; r->epoch_first = ops0;
-  auto sect = [&](auto&& rule) { for (size_t i = m; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid); if (p < 0) { plan_ok = false; p = 0; }
-      ph.push_back(ph_tag(base > 0 ? base + p - ov : p, 0)); } m = r->ops.size(); };
-  auto only = [&](int p) { sect([p](int) { return p; }); };
+  EpochTags tg(c, true, "dqn_epoch", ov, ov);
   if (use_weight && !has_col(batch, CRUX_COL_WEIGHT)) return bail(crux_fail(c, CRUX_EINVAL, "td_loss(weight=:weight): batch has no :weight column"));
   rc = per ? crux_per_sample(batch, source, B, nullptr, beta, sample_counter) : crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  sect([](int kid) { return kid == OP_UNIFORM_IDS ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
+  tg.tag([](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
   Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (nout + 2) + 8192), 0}; if (!cv.p) return bail(crux_fail(c, CRUX_ENOMEM, "dqn_epoch: scratch"));
   float* dy = cv.take<float>((size_t)B * nout); float* term = cv.take<float>((size_t)B); float* qsel = cv.take<float>((size_t)B);
   Carve sv{(char*)crux_exec_small(c, 256 * 6), 0}; if (!sv.p) return bail(crux_fail(c, CRUX_ENOMEM, "dqn_epoch: executor region"));
   float* dinfo = sv.take<float>(CRUX_INFO_N); double* ssq = sv.take<double>(2 + SUMSQ_BLOCKS); int32_t* status = sv.take<int32_t>(1); int32_t* nanf = sv.take<int32_t>(2);
   rc = crux_exec_zero(c, dinfo, 256 * 6, c->stream); if (rc) return bail(rc);
-  float* const info_dst = r->info_row_override ? r->info_row_override : dinfo;      // asynchronous chains: the info op writes the caller's device row itself (round 6: one launch less behind the chain's last epoch)
+  ExecRec* r = rec_of(c); float* const info_dst = r->info_row_override ? r->info_row_override : dinfo;      // asynchronous chains: the info op writes the caller's device row itself (round 6: one launch less behind the chain's last epoch)
   if (r->info_row_override) { rc = crux_exec_zero(c, r->info_row_override, sizeof(float) * CRUX_INFO_N, c->stream); if (rc) return bail(rc); }
-  only(1);
+  tg.only(1);
   const float* S = (const float*)batch->col[CRUX_COL_S]; const float* SP = (const float*)batch->col[CRUX_COL_SP];
   rc = crux_dense_forward12(net, S, B, c->stream); if (!rc) rc = crux_dense_forward12(tnet, SP, B, c->stream); if (rc) return bail(rc);
-  only(2);
+  tg.only(2);
   { DqnTdArgs a{}; auto l3 = [&](crux_mlp* n) { const NetDesc& nd = n->nd; return TileSet{n->p + nd.woff[2], n->p + nd.boff[2], crux_dense_act(n, 2), crux_dense_act(n, 3)}; };
     a.qt = l3(tnet); a.q = l3(net); a.r = (const float*)batch->col[CRUX_COL_R]; a.done = (const uint8_t*)batch->col[CRUX_COL_DONE]; a.a = (const uint8_t*)batch->col[CRUX_COL_A];
     a.w = use_weight ? (const float*)batch->col[CRUX_COL_WEIGHT] : nullptr; a.gamma = gamma; a.softq_alpha = softq_alpha; a.nout = nout; a.K = K; a.B = (int32_t)B;
     a.y = d_y; a.dy = dy; a.err = per ? d_err : nullptr; a.term = term; a.qsel = qsel;
     a.per = per ? 1 : 0; a.pr = source->priorities; a.pminmax = source->pminmax; a.ids = batch->d_indices; a.per_alpha = source->alpha;
     crux_exec_push<DqnTdTileOp, OP_DQN_TD_TILE>(c, (unsigned)((B + 15) / 16), a); }
-  only(3);
+  tg.only(3);
   Sumsq2Fix fx{};
   rc = crux_dense_backward(net, S, B, dy, 1.0f, true, nullptr, c->stream, &fx, 0, nanf); if (rc) return bail(rc);
-  only(4);
+  tg.only(4);
   if (per) { rc = crux_per_touched(source, batch->d_indices, B, false, (unsigned*)(nanf + 2)); if (rc) return bail(rc);      // leaves + root paths as one op beside the pullback (LeafTouchOp)
-    sect([](int kid) { return (kid == OP_LEAF_TOUCH || kid == OP_LEAF_REFRESH) ? 4 : kid == OP_TREE_TOUCH ? 5 : -1; }); }
+    tg.tag([](int kid, int&) { return (kid == OP_LEAF_TOUCH || kid == OP_LEAF_REFRESH) ? 4 : kid == OP_TREE_TOUCH ? 5 : -1; }); }
   // 5: the norm (for the info row) and, beside it, Adam gated on the producers' NaN flags (AdamSelfOp, sac.hip) | 6: info, beta-power advance
   CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, net->g, (int64_t)net->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   rc = adam_self(net, nanf, status, fx, 0); if (rc) return bail(rc);
-  sect([](int kid) { return kid == OP_ADAM_ADVANCE_SELF ? 6 : 5; });
+  tg.tag([](int kid, int&) { return kid == OP_ADAM_ADVANCE_SELF ? 6 : 5; });
   crux_exec_push<TdInfo2Op, OP_TD_INFO2>(c, 1u, (const float*)term, (const float*)qsel, (const double*)ssq, B, info_dst);
-  only(6);
+  tg.only(6);
   crux_exec_add_readback(c, info_out, dinfo, status, "td_loss");
-  if (!(plan_ok && ph.size() == r->ops.size() - ops0)) r->chain_ok = false;
-  r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += 7 - (r->chain_base > 0 ? ov : 0);
-  return CRUX_OK;
+  return tg.finish(7);
 }
 
 // One epoch of value_training for the DQN family (src/model_free/off_policy.jl:69-93 with dqn_target, rl/dqn.jl:4-6): rand!(batch, source; i) ->
@@ -407,22 +510,14 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
   const bool fuse = net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && target_net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch;
   int32_t rc;
   if (per) { rc = crux_per_prepare(source); if (rc) return rc; }
-  float* d_y = nullptr; float* d_err = nullptr;
-  { char* sc2 = (char*)c->epoch_tmp;       // targets and td errors: a block of the context that no piece carves
-    if (c->epoch_tmp_bytes < 8 * (size_t)B + 512) { if (sc2) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(sc2); }
-      c->epoch_tmp_bytes = 16 * (size_t)B + 4096; if (hipMalloc(&c->epoch_tmp, c->epoch_tmp_bytes) != hipSuccess) { c->epoch_tmp = nullptr; c->epoch_tmp_bytes = 0; return crux_fail(c, CRUX_ENOMEM, "dqn_epoch: targets"); } sc2 = (char*)c->epoch_tmp; }
-    d_y = (float*)sc2; d_err = (float*)(sc2 + ((4 * (size_t)B + 255) / 256) * 256); }
+  rc = grow_epoch_tmp(c, 8 * (size_t)B + 512, B, "dqn_epoch"); if (rc) return rc;      // targets and td errors
+  float* d_y = (float*)c->epoch_tmp; float* d_err = (float*)((char*)c->epoch_tmp + ((4 * (size_t)B + 255) / 256) * 256);
   if (fuse && c->rec && rec_of(c)->chain && crux_exec_recording(c) && dqn_tile_case(net, target_net, source, batch))      // chained epochs of the C3 family: the tile op (5 launches per epoch)
     return dqn_epoch_tiles(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter, info_out, d_y, d_err);
-  constexpr int eager_mask = 0;
-  auto piece = [&](int bit) -> int32_t { if (!fuse) return CRUX_OK;
-    if (eager_mask & bit) { if (crux_exec_recording(c)) return crux_exec_run(c); return CRUX_OK; }
-    if (!crux_exec_recording(c)) return crux_exec_begin(c); return CRUX_OK; };
   auto bail = [&](int32_t e) { if (fuse) crux_exec_abort(c); return e; };
   // Phase plan of the fused epoch (L = number of Dense layers): the target network's forward chain runs beside the online network's, the replay
   // bookkeeping beside the backward chain.    0 search | 1 gather, ring ids, zero-fill | 2+k forward layer k (both nets; + push! priorities of the batch)
   //   2+L dqn_target | 3+L td head | 4+L+j backward of layer L-1-j (weight + data gradient; + update_priorities!, leaf re-sum, root paths) | then norm, info, Adam
-  std::vector<int> ph; bool plan_ok = true; const int Ld = net->nd.L;
   // chained epochs (crux_dqn_epochs): the sampling of epoch e + 1 (phase 0: search / uniform ids, phase 1: gather, ring ids, fills) touches nothing that the last three
   // phases of epoch e (norm | info + Adam | beta-power advance) read or write -- the batch rows and the sampled ids were last read by the first-layer weight gradient and
   // the tree refresh one phase earlier -- so it runs BESIDE them: phases 0 and 1 of a later epoch are tagged as the previous epoch's last-but-two and last-but-one, and
@@ -446,27 +541,17 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
   const int sph = (per && crux_per_fused_gather()) ? 1 : 0;
   const int ovmax = (tailp ? nb + 1 : nb) + sph;
   const int ov = per ? (ovmax < 1 ? 1 : (ovmax < 3 ? ovmax : 3)) : 3;
-  auto tag = [&](size_t from, auto&& rule) { if (!fuse || !crux_exec_recording(c)) return; ExecRec* r = rec_of(c); int g = 0; const int base = r->chain ? r->chain_base : 0;
-    for (size_t i = from; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid, g); if (p < 0) { plan_ok = false; p = 0; }
-      const int sub = p >> 12; p &= 4095;
-      ph.push_back(ph_tag(base > 0 ? (p < 2 ? base - ov + p : base + p - ov) : p, sub)); } };
   // the target (one block at B <= 256) and the loss head (one block) are a sequential pair: the head runs in the target's block, right after it, and every later
   // phase moves up by one (sq).
   const int sq = sq0;
-  if (crux_dense_fwd_fused(target_net) != ffw) plan_ok = false;
-  rc = piece(1); if (rc) return bail(rc);
-  const size_t ops0 = fuse && crux_exec_recording(c) ? exec_mark(c) : 0;      // first op of THIS epoch (a chained recording already holds the earlier epochs)
-  if (fuse && crux_exec_recording(c) && rec_of(c)->chain) rec_of(c)->epoch_first = ops0;
-  size_t m = ops0;
+  if (fuse && !crux_exec_recording(c)) { rc = crux_exec_begin(c); if (rc) return bail(rc); }      // (a chained recording is already open)
+  EpochTags tg(c, fuse, "dqn_epoch", ov, ov);
+  if (crux_dense_fwd_fused(target_net) != ffw || target_net->nd.L != net->nd.L) tg.plan_ok = false;
   rc = per ? crux_per_sample(batch, source, B, nullptr, beta, sample_counter) : crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  tag(m, [&](int kid, int&) { return (kid == OP_PER_SEARCH || kid == OP_UNIFORM_IDS) ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
-  rc = piece(2); if (rc) return bail(rc);
-  m = fuse && crux_exec_recording(c) ? exec_mark(c) : 0;
+  tg.tag([&](int kid, int&) { return (kid == OP_PER_SEARCH || kid == OP_UNIFORM_IDS) ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
   rc = softq_alpha > 0.f ? crux_softq_target(target_net, batch, gamma, softq_alpha, d_y) : crux_dqn_target(target_net, batch, gamma, d_y); if (rc) return bail(rc);      // softq_target(alpha) (rl/softq.jl:4-13) | dqn_target (rl/dqn.jl:4-6)
-  tag(m, [&](int kid, int& g) { if (kid == OP_FWD12) { g = 1; return 2; }
+  tg.tag([&](int kid, int& g) { if (kid == OP_FWD12) { g = 1; return 2; }
     return kid == OP_GEMM ? (g < nf ? 2 + g++ : -1) : (kid == OP_DQN_TARGET || kid == OP_SOFTQ_TARGET) ? (2 + nf) | (sq ? PH_SEQ_HEAD : 0) : -1; });
-  rc = piece(4); if (rc) return bail(rc);
-  m = fuse && crux_exec_recording(c) ? exec_mark(c) : 0;
   auto td_rule = [&](int kid, int& g) {      // g counts the GEMMs: Ld forward, then (weight, data) pairs from the last layer down, the first layer has no data gradient
     if (kid == OP_FILL) return 1;
     if (kid == OP_FWD12) { g = 1; return 2; }
@@ -476,21 +561,12 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
     if (kid == OP_SUMSQ2) return 4 + nf + nb - sq; if (kid == OP_TD_INFO || kid == OP_ADAM_GATED) return 5 + nf + nb - sq; if (kid == OP_ADAM_ADVANCE) return 6 + nf + nb - sq;
     return -1; };
   if (per) { rc = crux_td_step_with_error(net, batch, d_y, use_weight, d_err, info_out); if (rc) return bail(rc);
-    tag(m, td_rule);
-    rc = piece(8); if (rc) return bail(rc);
-    m = fuse && crux_exec_recording(c) ? exec_mark(c) : 0;
+    tg.tag(td_rule);
     rc = crux_per_update_device(source, batch->d_indices, d_err, B); if (rc) return bail(rc);
-    tag(m, [&](int kid, int&) { if (tailp) return kid == OP_PER_UPDATE ? ((2 + nf) | PH_SEQ_TAIL) : kid == OP_LEAF_REFRESH ? 3 + nf : kid == OP_TREE_TOUCH ? 4 + nf : -1;
+    tg.tag([&](int kid, int&) { if (tailp) return kid == OP_PER_UPDATE ? ((2 + nf) | PH_SEQ_TAIL) : kid == OP_LEAF_REFRESH ? 3 + nf : kid == OP_TREE_TOUCH ? 4 + nf : -1;
       return kid == OP_PER_UPDATE ? 4 + nf - sq : kid == OP_LEAF_REFRESH ? 5 + nf - sq : kid == OP_TREE_TOUCH ? 6 + nf - sq : -1; }); }
-  else { rc = crux_td_step(net, batch, d_y, use_weight, info_out); if (rc) return bail(rc); tag(m, td_rule); }
-  if (fuse && crux_exec_recording(c) && rec_of(c)->chain) {     // chained: the caller (crux_dqn_epochs) schedules and runs the whole list
-    ExecRec* r = rec_of(c);
-    if (!(plan_ok && !eager_mask && target_net->nd.L == Ld && ph.size() == r->ops.size() - ops0)) r->chain_ok = false;
-    r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += (r->chain_base > 0 ? 7 - ov : 7) + nf + nb - sq;
-    return CRUX_OK;
-  }
-  if (fuse && crux_exec_recording(c) && plan_ok && !eager_mask && target_net->nd.L == Ld && ph.size() == rec_of(c)->ops.size()) { rc = exec_schedule(c, ph); if (rc) return bail(rc); }
-  return (fuse && crux_exec_recording(c)) ? crux_exec_run(c) : CRUX_OK;
+  else { rc = crux_td_step(net, batch, d_y, use_weight, info_out); if (rc) return bail(rc); tg.tag(td_rule); }
+  return tg.finish(7 + nf + nb - sq);
 }
 
 int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
@@ -504,46 +580,18 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
                                uint64_t sample_counter0, int32_t n_epochs, float* infos, float* d_infos_async = nullptr, float polyak_tau = -1.f) {
   if (!net || !target_net || !source || !batch || n_epochs < 1) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
-  const bool fuse = net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && target_net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch &&
-                    !crux_sw().no_chained_epochs;
-  auto flush = [&]() -> int32_t {
-    if (!crux_exec_recording(c)) return CRUX_OK;
-    ExecRec* r = rec_of(c); r->chain = false;
-    if (r->chain_ok && r->chain_tags.size() == r->ops.size()) { const int32_t rs = exec_schedule(c, r->chain_tags); if (rs) { crux_exec_abort(c); return rs; } }
-    r->async = d_infos_async != nullptr;
-    return crux_exec_run(c);
+  const bool fuse = dqn_chain_case(net, target_net), tiles = fuse && dqn_tile_case(net, target_net, source, batch);
+  auto record = [&](int e) {      // tile plan, asynchronous: the info op writes the caller's row itself (no copy op)
+    float* row = (d_infos_async && tiles) ? d_infos_async + (size_t)e * CRUX_INFO_N : nullptr;
+    if (row) rec_of(c)->info_row_override = row;
+    const int32_t rc = dqn_epoch_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0 + (uint64_t)e, infos ? infos + (size_t)e * CRUX_INFO_N : nullptr);
+    if (row) rec_of(c)->info_row_override = nullptr;
+    return rc;
   };
-  int32_t rc = CRUX_OK; int in_chain = 0;
-  for (int e = 0; e < n_epochs; ++e) {
-    float* info_e = infos ? infos + (size_t)e * CRUX_INFO_N : nullptr;
-    if (!fuse) { if (d_infos_async) return CRUX_EUNSUP;      // narrow networks run call by call with a read-back per epoch: the caller takes the synchronous entry point
-      rc = dqn_epoch_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0 + (uint64_t)e, info_e); if (rc) return rc; continue; }
-    // a priority tree that needs a plain rebuild (the ring is still filling, or a bulk change) cannot be refreshed inside a recording: run what is recorded first
-    if (in_chain && ((source->prioritized && source->per_full_dirty) || in_chain >= 8)) { rc = flush(); in_chain = 0; if (rc) return rc; }
-    if (!in_chain) { if (source->prioritized) { rc = crux_per_prepare(source); if (rc) return rc; }
-      rc = crux_exec_begin(c); if (rc) return rc; }
-    rec_of(c)->chain = true;
-    const bool tiles = dqn_tile_case(net, target_net, source, batch) && !crux_sw().no_fused_epoch;
-    rec_of(c)->info_row_override = (d_infos_async && tiles) ? d_infos_async + (size_t)e * CRUX_INFO_N : nullptr;      // tile plan: the info op writes the caller's row itself
-    rc = dqn_epoch_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0 + (uint64_t)e, info_e);
-    if (c->rec) rec_of(c)->info_row_override = nullptr;
-    if (rc) { if (c->rec) rec_of(c)->chain = false; crux_exec_abort(c); return rc; }
-    if (d_infos_async && !tiles) {      // the epoch's info row goes to the caller's device array, copied in the epoch's last phase (one phase after the info op wrote it)
-      ExecRec* r = rec_of(c);
-      crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_infos_async + (size_t)e * CRUX_INFO_N, (const float*)r->readbacks.back().d_info, (int64_t)CRUX_INFO_N);
-      int tmax = 0; for (size_t k = r->epoch_first; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);      // the epoch's last phase (the beta-power advance)
-      r->chain_tags.push_back(tmax + (tiles ? 4 : 0)); }      // (tile plan: the info op sits IN the epoch's last phase -- the copy joins the launch after it)
-    ++in_chain;
-  }
   // polyak_average!(pi_minus, pi, tau) after the epoch loop (off_policy.jl:108: the DQN family updates its target once per value_training call) as an op of the chain: it needs
   // the last epoch's Adam (phase 5) and shares the launch of that epoch's info / beta-power phase -- the stand-alone k_polyak launch (~5 us of a 230 us C3 iteration) is gone.
-  if (fuse && polyak_tau >= 0.f && in_chain > 0) {
-    ExecRec* r = rec_of(c); const size_t n0 = r->ops.size();
-    rc = crux_polyak(target_net, net, polyak_tau); if (rc) { r->chain = false; crux_exec_abort(c); return rc; }
-    int tmax = 0; for (size_t k = r->epoch_first; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);
-    for (size_t k = n0; k < r->ops.size(); ++k) r->chain_tags.push_back(tmax);
-  }
-  return fuse ? flush() : rc;
+  return run_epoch_chains(c, "dqn", fuse, source->prioritized ? source : nullptr, n_epochs, 1, d_infos_async, record, [&](int) { return EpochRows{1u, tiles ? -1 : 0}; },
+                          [&]() { return polyak_tau >= 0.f ? crux_polyak(target_net, net, polyak_tau) : CRUX_OK; });
 }
 int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
                         uint64_t sample_counter0, int32_t n_epochs, float* infos) {
@@ -557,7 +605,7 @@ int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source
 int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
                               uint64_t sample_counter0, int32_t n_epochs, float* d_infos) {
   if (!d_infos) return CRUX_EINVAL;
-  if (!net || !target_net || net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || target_net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || crux_sw().no_fused_epoch || crux_sw().no_chained_epochs) return CRUX_EUNSUP;
+  if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   return dqn_epochs_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
 }
 // value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111 with :108), without the host: the chain of crux_dqn_epochs_async (softq_alpha > 0:
@@ -565,14 +613,14 @@ int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
 int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
                                       uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) {
   if (!d_infos || softq_alpha < 0.f || tau > 1.f) return CRUX_EINVAL;
-  if (!net || !target_net || net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || target_net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || crux_sw().no_fused_epoch || crux_sw().no_chained_epochs) return CRUX_EUNSUP;
+  if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   if (tau >= 0.f && net->nd.n_params != target_net->nd.n_params) return crux_fail(net->ctx, CRUX_EINVAL, "value_training: polyak_average! needs equal parameter counts");
   return dqn_epochs_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos, tau);
 }
 int32_t crux_softq_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
                                 uint64_t sample_counter0, int32_t n_epochs, float* d_infos) {      // crux_softq_epochs without the host in the loop (see crux_dqn_epochs_async)
   if (!d_infos || !(alpha > 0.f)) return CRUX_EINVAL;
-  if (!net || !target_net || net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || target_net->nd.maxdim < CRUX_DENSE_MIN_WIDTH || crux_sw().no_fused_epoch || crux_sw().no_chained_epochs) return CRUX_EUNSUP;
+  if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   return dqn_epochs_impl(net, target_net, source, batch, gamma, alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
 }
 int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
@@ -616,11 +664,7 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   if (use_weight && !has_col(batch, CRUX_COL_WEIGHT)) return crux_fail(c, CRUX_EINVAL, "double_Q_loss(weight=:weight): batch has no :weight column");
   if (!crux_exec_recording(c)) { rc = crux_exec_begin(c); if (rc) return rc; }
   auto bail = [&](int32_t e) { crux_exec_abort(c); return e; };
-  ExecRec* r = rec_of(c); const int base = r->chain ? r->chain_base : 0; std::vector<int> ph; bool plan_ok = true;
-  size_t m = exec_mark(c); const size_t ops0 = m;
-  auto sect = [&](auto&& rule) { for (size_t i = m; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid); if (p < 0) { plan_ok = false; p = 0; }
-      ph.push_back(ph_tag(base > 0 ? base + p - 3 : p, 0)); } m = r->ops.size(); };
-  auto only = [&](int p) { sect([p](int) { return p; }); };
+  EpochTags tg(c, true, "sac_epoch", 3, 3);
   // buffers of this epoch (scratch of the recording: live until the list has run)
   float* y = (float*)crux_exec_small(c, 4 * (size_t)B); if (!y) return bail(crux_fail(c, CRUX_EUNSUP, "sac_epoch: batch of %lld rows exceeds the executor's region", (long long)B));
   Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (3 * sd + 3 * ad + 12) + 65536), 0}; if (!cv.p) return bail(crux_fail(c, CRUX_ENOMEM, "sac_epoch: scratch"));
@@ -640,23 +684,23 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   const unsigned nt = (unsigned)((B + 15) / 16);
   // 0, 1: rand!
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  sect([](int kid) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
+  tg.tag([](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
   rc = check_sac(c, actor, q1, q2, la, batch, "sac_epoch"); if (rc) return bail(rc);
   rc = crux_exec_zero(c, it, 256 * 5, c->stream); if (!rc) rc = crux_exec_zero(c, ic, 256 * 6, c->stream); if (!rc) rc = crux_exec_zero(c, ia, 256 * 6, c->stream);
   if (!rc) rc = crux_exec_zero(c, la->g, sizeof(float) * (size_t)la->nd.n_params, c->stream); if (rc) return bail(rc);
-  only(1);
+  tg.only(1);
   // 2
   rc = crux_dense_forward12(actor, SP, B, c->stream); if (rc) return bail(rc);
   CRUX_RUN(c, ConcatSaOp, OP_CONCAT_SA, k_concat_sa, nblk(B * sd), 256, c->stream, S, (const float*)batch->col[CRUX_COL_A], od, ad, B, sa_c);
-  only(2);
+  tg.only(2);
   // 3
   { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = SP; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed; a.cfg[0] = ExploreCfg{noise_counter0, sa_t, lp_t, nullptr};
     crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a); }
   rc = crux_dense_forward12(q1, sa_c, B, c->stream); if (!rc) rc = crux_dense_forward12(q2, sa_c, B, c->stream); if (rc) return bail(rc);
-  only(3);
+  tg.only(3);
   // 4
   rc = crux_dense_forward12(q1t, sa_t, B, c->stream); if (!rc) rc = crux_dense_forward12(q2t, sa_t, B, c->stream); if (!rc) rc = crux_dense_forward12(actor, S, B, c->stream); if (rc) return bail(rc);
-  only(4);
+  tg.only(4);
   // 5
   { SacCriticArgs a{}; a.q1t = l3(q1t, true); a.q2t = l3(q2t, true); a.q1 = l3(q1, true); a.q2 = l3(q2, true); a.r = (const float*)batch->col[CRUX_COL_R]; a.done = (const uint8_t*)batch->col[CRUX_COL_DONE];
     a.lp = lp_t; a.log_alpha = la->p; a.w = w; a.gamma = gamma; a.scale = 0.5f; a.K = K; a.B = (int32_t)B; a.y = y; a.dy1 = dy1; a.dy2 = dy2; a.term1 = t1; a.term2 = t2;
@@ -664,57 +708,51 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = S; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed;      // the two draws side by side (each re-evaluates the output layer: 8 MFMAs)
     a.cfg[0] = ExploreCfg{noise_counter0 + 1, nullptr, lp_temp, nullptr}; crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a);
     a.cfg[0] = ExploreCfg{noise_counter0 + 2, sa_a, lp_a, eps}; crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a); }
-  only(5);
+  tg.only(5);
   // 6
   Sumsq2Fix fxc{}, fxa{};
   rc = crux_dense_backward(q1, sa_c, B, dy1, 1.0f, true, nullptr, c->stream, &fxc, 0, nfc); if (!rc) rc = crux_dense_backward(q2, sa_c, B, dy2, 1.0f, true, nullptr, c->stream, &fxc, 1, nfc); if (rc) return bail(rc);
   CRUX_RUN(c, TempHeadOp, OP_TEMP_HEAD, k_temp_head, 1, 256, c->stream, (const float*)lp_temp, B, H_target, (const float*)la->p, la->g, it, ssq_t);
-  only(6);
+  tg.only(6);
   // 7: the critics' norm (for the info row) and, beside it, their Adam steps gated on the pullback's NaN flags (AdamSelfOp, sac.hip); log alpha's step (+ 8: the advances)
   CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, q1->g, (int64_t)q1->nd.n_params, q2->g, (int64_t)q2->nd.n_params, ssq_c, fxc);
   rc = adam_self(q1, nfc, stc, fxc, 0); if (!rc) rc = adam_self(q2, nfc, stc, fxc, 1); if (!rc) rc = adam_gated(la, ssq_t, stt, false); if (rc) return bail(rc);
-  sect([](int kid) { return (kid == OP_ADAM_ADVANCE || kid == OP_ADAM_ADVANCE_SELF) ? 8 : 7; });
+  tg.tag([](int kid, int&) { return (kid == OP_ADAM_ADVANCE || kid == OP_ADAM_ADVANCE_SELF) ? 8 : 7; });
   // 8: critic info | the updated critics' first two layers on (s, a ~ pi)
   crux_exec_push<CriticInfo2Op, OP_CRITIC_INFO2>(c, 1u, (const float*)t1, (const float*)crux_dense_act(q1, 3), (const float*)t2, (const float*)crux_dense_act(q2, 3), (const double*)ssq_c, B, ic);
   rc = crux_dense_forward12(q1, sa_a, B, c->stream); if (!rc) rc = crux_dense_forward12(q2, sa_a, B, c->stream); if (rc) return bail(rc);
-  only(8);
+  tg.only(8);
   // 9
   { SacActorArgs a{}; a.q1 = l3(q1, true); a.q2 = l3(q2, true); a.lp = lp_a; a.log_alpha = la->p; a.K = K; a.B = (int32_t)B; a.dy1 = da1; a.dy2 = da2; a.term = ta;
     crux_exec_push<SacActorTileOp, OP_SAC_ACTOR_TILE>(c, nt, a); }
-  only(9);
+  tg.only(9);
   // 10
   const float* dz1a = nullptr; const float* dz1b = nullptr;
   rc = crux_dense_dgrad_to_dz1(q1, sa_a, B, da1, &dz1a, c->stream); if (!rc) rc = crux_dense_dgrad_to_dz1(q2, sa_a, B, da2, &dz1b, c->stream); if (rc) return bail(rc);
-  only(10);
+  tg.only(10);
   // 11
   { CriticDxArgs a{}; a.c1 = TileSet{q1->p + q1->nd.woff[0], nullptr, dz1a, nullptr}; a.c2 = TileSet{q2->p + q2->nd.woff[0], nullptr, dz1b, nullptr};
     a.sa = sa_a; a.mu = crux_dense_act(actor, 3); a.eps = eps; a.ls = ls; a.log_alpha = la->p; a.od = od; a.ad = ad; a.K = q1->nd.dims[1]; a.B = (int32_t)B; a.dmu = dmu; a.dls = dls;
     crux_exec_push<CriticDxActorGradTileOp, OP_CRITIC_DX_TILE>(c, nt, a); }
-  only(11);
+  tg.only(11);
   // 12
   rc = crux_dense_backward(actor, S, B, dmu, 1.0f, true, nullptr, c->stream, &fxa, 0, nfa); if (rc) return bail(rc);
   CRUX_RUN(c, RowsumOp, OP_ROWSUM, k_rowsum, ad, 256, c->stream, (const float*)dls, ad, B, actor->g + actor->nd.xoff, nfa);
-  only(12);
+  tg.only(12);
   // 13: the actor's norm | its Adam step (self-gated)
   CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, actor->g, (int64_t)actor->nd.n_params, (float*)nullptr, (int64_t)0, ssq_a, fxa);
   rc = adam_self(actor, nfa, sta, fxa, 0); if (rc) return bail(rc);
-  sect([](int kid) { return kid == OP_ADAM_ADVANCE_SELF ? 14 : 13; });
+  tg.tag([](int kid, int&) { return kid == OP_ADAM_ADVANCE_SELF ? 14 : 13; });
   // 14: actor info, polyak
   crux_exec_push<ActorInfo2Op, OP_ACTOR_INFO2>(c, 1u, (const float*)ta, (const float*)lp_a, (const double*)ssq_a, B, ia);
   if (actor_targ) { rc = crux_polyak(actor_targ, actor, tau); if (rc) return bail(rc); }
   rc = crux_polyak(q1t, q1, tau); if (!rc) rc = crux_polyak(q2t, q2, tau); if (rc) return bail(rc);
-  only(14);
+  tg.only(14);
   // the steps' read-backs in the order they ran (temperature, critics, actor), as the generic recording registers them
   crux_exec_add_readback(c, info_temp, it, stt, "sac_temp_loss"); crux_exec_add_readback(c, info_critic, ic, stc, "double_Q_loss"); crux_exec_add_readback(c, info_actor, ia, sta, "sac_actor_loss");
   // phases 0 / 1 of a chained epoch (ids | gather, fills) overlap the previous epoch's actor pullback (12: the gather rewrites the batch rows it read -- not before 13) and
   // norm + Adam (13), phase 2 (the new actor's forward on s') its info + advance + polyak (14): base + p - 3 for every p. 15 phases, 12 launches per chained epoch.
-  if (r->chain) {
-    if (!(plan_ok && ph.size() == r->ops.size() - ops0)) r->chain_ok = false;
-    r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += 15 - (r->chain_base > 0 ? 3 : 0);
-    return CRUX_OK;
-  }
-  if (plan_ok && ph.size() == r->ops.size()) { rc = exec_schedule(c, ph); if (rc) return bail(rc); }
-  return crux_exec_run(c);
+  return tg.finish(15);
 }
 
 // One epoch of value_training with SAC's pieces (off_policy.jl:69-104, rl/sac.jl): rand! -> sac_target -> train!(log_alpha, sac_temp_loss) ->
@@ -732,9 +770,7 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
   if (fuse) { if (!crux_exec_recording(c)) { rc = crux_exec_begin(c); if (rc) return rc; }       // a chained recording (crux_sac_epochs) is already open
     d_y = (float*)crux_exec_small(c, 4 * (size_t)B);
     if (!d_y) { crux_exec_abort(c); return crux_fail(c, CRUX_EUNSUP, "sac_epoch: batch of %lld rows exceeds the executor's region", (long long)B); } }
-  else { if (c->epoch_tmp_bytes < 4 * (size_t)B + 256) { if (c->epoch_tmp) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_tmp); }
-      c->epoch_tmp_bytes = 16 * (size_t)B + 4096; if (hipMalloc(&c->epoch_tmp, c->epoch_tmp_bytes) != hipSuccess) { c->epoch_tmp = nullptr; c->epoch_tmp_bytes = 0; return crux_fail(c, CRUX_ENOMEM, "sac_epoch: targets"); } }
-    d_y = (float*)c->epoch_tmp; }
+  else { rc = grow_epoch_tmp(c, 4 * (size_t)B + 256, B, "sac_epoch"); if (rc) return rc; d_y = (float*)c->epoch_tmp; }
   auto bail = [&](int32_t e) { if (fuse) crux_exec_abort(c); return e; };
   // Phase plan (LA = layers of the actor, LQ = of a critic; X = 3 + LA + LQ, Y = X + 4 + LQ). Chains that touch different networks run side by side:
   //   0 ids | 1 gather, zero-fills | 2.. actor(sp) forward ; vcat(s, a) ; Q1 || Q2 forward on (s, a) | 2+LA exploration at sp | 3+LA.. target Q1 || Q2 ; actor(s) forward
@@ -747,40 +783,31 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
   // Round 4: written in launches -- FA / FQ forward launches of the actor / a critic, BQ / BA phases of a pullback with parameter gradients (BQo ops per critic), LQ phases
   // of a critic's input-gradient chain; with the fused block kernels FA = FQ = L - 1 and BQ = BA = L - 1 (net_plan above), otherwise all equal L as in round 3.
   const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);
-  std::vector<int> ph; bool plan_ok = true; const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
-  if (LA != LQ || q2->nd.L != LQ || q1_targ->nd.L != LQ || q2_targ->nd.L != LQ) plan_ok = false;       // (the early actor forward needs X + 1 + FA < Y)
-  { const NetPlan p2 = net_plan(q2, B), t1 = net_plan(q1_targ, B), t2 = net_plan(q2_targ, B); if (p2.nf != FQ || p2.nb != BQ || p2.one != pq.one || t1.nf != FQ || t2.nf != FQ || FA != FQ) plan_ok = false; }
+  EpochTags tg(c, fuse, "sac_epoch", 3, 3);
+  const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
+  if (LA != LQ || q2->nd.L != LQ || q1_targ->nd.L != LQ || q2_targ->nd.L != LQ) tg.plan_ok = false;       // (the early actor forward needs X + 1 + FA < Y)
+  { const NetPlan p2 = net_plan(q2, B), t1 = net_plan(q1_targ, B), t2 = net_plan(q2_targ, B); if (p2.nf != FQ || p2.nb != BQ || p2.one != pq.one || t1.nf != FQ || t2.nf != FQ || FA != FQ) tg.plan_ok = false; }
   // chained epochs: phases 0 (ids) and 1 (gather, fills) of a later epoch run beside the previous epoch's actor norm and info + Adam (neither reads the batch), and its
   // phase 2 (actor(sp) forward, vcat(s, a): online networks only) beside the previous epoch's advance + polyak, which writes beta powers and TARGET networks: the rest
   // closes up by three -- see crux_dqn_epoch
-  auto tag = [&](size_t from, auto&& rule) { if (!fuse) return; ExecRec* r = rec_of(c); int g = 0; const int base = r->chain ? r->chain_base : 0;
-    for (size_t i = from; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid, g); if (p < 0) { plan_ok = false; p = 0; }
-      const int sub = p >> 12; p &= 4095;
-      ph.push_back(ph_tag(base > 0 ? (p < 2 ? base - 3 + p : base + p - 3) : p, sub)); } };
-  const size_t ops0 = fuse ? exec_mark(c) : 0;
-  size_t m = ops0;
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  tag(m, [&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
-  m = fuse ? exec_mark(c) : 0;
+  tg.tag([&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
   rc = crux_sac_target(actor, q1_targ, q2_targ, log_alpha, batch, gamma, noise_seed, noise_counter0, d_y); if (rc) return bail(rc);
-  tag(m, [&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
+  tg.tag([&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
     return kid == OP_GAUSS_EXPLORE ? 2 + FA : kid == OP_SAC_TARGET ? X | (sq ? PH_SEQ_HEAD : 0) : -1; });
-  m = fuse ? exec_mark(c) : 0;
   rc = crux_sac_temp_step(actor, log_alpha, batch, H_target, noise_seed, noise_counter0 + 1, info_temp); if (rc) return bail(rc);
-  tag(m, [&](int kid, int& g) { if (kid == OP_FILL) return 1; if (is_mm(kid)) { const int k = g++; return k < FA ? 3 + FA + k : -1; }
+  tg.tag([&](int kid, int& g) { if (kid == OP_FILL) return 1; if (is_mm(kid)) { const int k = g++; return k < FA ? 3 + FA + k : -1; }
     return kid == OP_GAUSS_EXPLORE ? X : kid == OP_TEMP_HEAD ? X + 1 : kid == OP_ADAM_GATED ? X + 2 : kid == OP_ADAM_ADVANCE ? X + 3 : -1; });
   if (update_critic) {
-    m = fuse ? exec_mark(c) : 0;
     rc = crux_double_q_step(q1, q2, batch, d_y, use_weight, info_critic); if (rc) return bail(rc);
-    tag(m, [&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
+    tg.tag([&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
       if (kid == OP_FILL) return 1; if (kid == OP_CONCAT_SA) return 2;
       if (is_mm(kid)) { const int k = (g++) % (FQ + BQo); return k < FQ ? 3 + k : X + 2 - sq + pq.stage(k - FQ); }
       return kid == OP_Q_HEAD ? (sq ? (X | PH_SEQ_TAIL) : X + 1) : kid == OP_SUMSQ2 ? X + 2 - sq + BQ : (kid == OP_CRITIC_INFO || kid == OP_ADAM_GATED) ? X + 3 - sq + BQ : kid == OP_ADAM_ADVANCE ? X + 4 - sq + BQ : -1; });
   }
   if (update_actor) {
-    m = fuse ? exec_mark(c) : 0;
     rc = crux_sac_actor_step(actor, q1, q2, log_alpha, batch, noise_seed, noise_counter0 + 2, info_actor); if (rc) return bail(rc);
-    tag(m, [&](int kid, int& g) {      // GEMMs: LA actor forward, LQ + LQ critic forwards, LQ + LQ critic input gradients, then the actor's (weight, data) pairs
+    tg.tag([&](int kid, int& g) {      // GEMMs: LA actor forward, LQ + LQ critic forwards, LQ + LQ critic input gradients, then the actor's (weight, data) pairs
       if (kid == OP_FILL) return 1;
       // the actor's own forward pass and its exploration draw depend on neither the critic update nor the temperature: they run beside the critic's head / backward
       // phases (X + 1 ..), after the temperature step's last read of the actor's activations (its exploration at X)
@@ -788,20 +815,12 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
         if (k < FA + 2 * FQ + 2 * DQ) return Y + 1 + FQ + (k - FA - 2 * FQ) % DQ; return Y + 2 + FQ + DQ + pa.stage(k - FA - 2 * FQ - 2 * DQ); }
       return kid == OP_GAUSS_EXPLORE ? X + 1 + FA : kid == OP_ACTOR_HEAD ? Y + FQ : kid == OP_ACTOR_GRAD ? Y + 1 + FQ + DQ : kid == OP_ROWSUM ? Y + 2 + FQ + DQ :
              kid == OP_SUMSQ2 ? Y + BA + 2 + FQ + DQ : (kid == OP_ACTOR_INFO || kid == OP_ADAM_GATED) ? Y + BA + 3 + FQ + DQ : kid == OP_ADAM_ADVANCE ? Y + BA + 4 + FQ + DQ : -1; });
-    m = fuse ? exec_mark(c) : 0;
     if (actor_targ) { rc = crux_polyak(actor_targ, actor, tau); if (rc) return bail(rc); }
     rc = crux_polyak(q1_targ, q1, tau); if (rc) return bail(rc);
     rc = crux_polyak(q2_targ, q2, tau); if (rc) return bail(rc);
-    tag(m, [&](int kid, int&) { return kid == OP_POLYAK ? Y + BA + 4 + FQ + DQ : -1; });
+    tg.tag([&](int kid, int&) { return kid == OP_POLYAK ? Y + BA + 4 + FQ + DQ : -1; });
   }
-  if (fuse && rec_of(c)->chain) {      // chained: crux_sac_epochs schedules and runs the whole list
-    ExecRec* r = rec_of(c);
-    if (!(plan_ok && ph.size() == r->ops.size() - ops0)) r->chain_ok = false;
-    r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += Y + BA + 5 + FQ + DQ - (r->chain_base > 0 ? 3 : 0);
-    return CRUX_OK;
-  }
-  if (fuse && plan_ok && ph.size() == rec_of(c)->ops.size()) { rc = exec_schedule(c, ph); if (rc) return bail(rc); }
-  return fuse ? crux_exec_run(c) : CRUX_OK;
+  return tg.finish(Y + BA + 5 + FQ + DQ);
 }
 
 // value_training's epoch loop with SAC's pieces (off_policy.jl:69-104; SAC's c_opt.epochs = dN = 50, rl/sac.jl) in chains of up to 8 epochs per recorded list.
@@ -814,64 +833,26 @@ static int32_t sac_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   if (!actor || n_epochs < 1 || critic_every < 1 || actor_every < 1) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
   const bool fuse = !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
-  if (d_infos_async && !fuse) return CRUX_EUNSUP;
-  auto flush = [&]() -> int32_t {
-    if (!crux_exec_recording(c)) return CRUX_OK;
-    ExecRec* r = rec_of(c); r->chain = false;
-    if (r->chain_ok && r->chain_tags.size() == r->ops.size()) { const int32_t rs = exec_schedule(c, r->chain_tags); if (rs) { crux_exec_abort(c); return rs; } }
-    r->async = d_infos_async != nullptr;
-    return crux_exec_run(c);
-  };
-  int32_t rc = CRUX_OK; int in_chain = 0;
-  for (int e = 0; e < n_epochs; ++e) {
-    const int ge = epoch0 + e; const int32_t uc = ge % critic_every == 0, ua = ge % actor_every == 0;
-    float* it = infos_temp ? infos_temp + (size_t)e * CRUX_INFO_N : nullptr; float* ic = infos_critic ? infos_critic + (size_t)e * CRUX_INFO_N : nullptr; float* ia = infos_actor ? infos_actor + (size_t)e * CRUX_INFO_N : nullptr;
-    if (fuse) {
-      if (in_chain >= 8) { rc = flush(); in_chain = 0; if (rc) return rc; }
-      if (!in_chain) { rc = crux_exec_begin(c); if (rc) return rc; }
-      rec_of(c)->chain = true;
-    }
-    const size_t rb0 = fuse ? rec_of(c)->readbacks.size() : 0, tg0 = fuse ? rec_of(c)->chain_tags.size() : 0;
-    rc = crux_sac_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, uc, ua,
-                        sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + 3ull * (uint64_t)e, it, ic, ia);
-    if (rc) { if (fuse && c->rec) { rec_of(c)->chain = false; crux_exec_abort(c); } return rc; }
-    const bool tiles = fuse && sac_tile_case(actor, q1, q2, q1_targ, q2_targ, source, batch, uc, ua);
-    if (d_infos_async) {      // the epoch's info rows (temperature, [critics], [actor] -- the order the steps ran in) go to rows 3 e .. 3 e + 2 of the caller's device array, copied in the epoch's last phase
-      ExecRec* r = rec_of(c);
-      if (r->readbacks.size() != rb0 + 1 + (uc ? 1 : 0) + (ua ? 1 : 0) || r->chain_tags.size() != r->ops.size()) { r->chain = false; crux_exec_abort(c); return crux_fail(c, CRUX_EHIP, "sac epochs (async): unexpected recording"); }
-      int tmax = 0; for (size_t k = tg0; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);
-      size_t q = rb0; const int slot_of[3] = {0, uc ? 1 : -1, ua ? 2 : -1};
-      for (int sl = 0; sl < 3; ++sl) { if (slot_of[sl] < 0) continue;
-        crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_infos_async + ((size_t)e * 3 + sl) * CRUX_INFO_N, (const float*)r->readbacks[q++].d_info, (int64_t)CRUX_INFO_N);
-        r->chain_tags.push_back(tmax + (tiles ? 4 : 0)); } }      // (tile plans: the actor's info op sits IN the epoch's last phase -- the copy joins the launch after it, the next epoch's third)
-    if (fuse) ++in_chain;
-  }
-  return fuse ? flush() : rc;
+  auto record = [&](int e) { const int ge = epoch0 + e; const size_t o = (size_t)e * CRUX_INFO_N;
+    return crux_sac_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, ge % critic_every == 0, ge % actor_every == 0,
+                          sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + 3ull * (uint64_t)e, infos_temp ? infos_temp + o : nullptr, infos_critic ? infos_critic + o : nullptr,
+                          infos_actor ? infos_actor + o : nullptr); };
+  // rows 3 e .. 3 e + 2: temperature, [critics], [actor]. Tile plans: the actor's info op sits IN the epoch's last phase -- the copies join the launch after it, the next epoch's third
+  auto rows = [&](int e) { const int ge = epoch0 + e; const bool uc = ge % critic_every == 0, ua = ge % actor_every == 0;
+    return EpochRows{1u | (uc ? 2u : 0u) | (ua ? 4u : 0u), sac_tile_case(actor, q1, q2, q1_targ, q2_targ, source, batch, uc, ua) ? 4 : 0}; };
+  return run_epoch_chains(c, "sac", fuse, nullptr, n_epochs, 3, d_infos_async, record, rows, [] { return CRUX_OK; });
 }
 int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                         crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
                         float* infos_temp, float* infos_critic, float* infos_actor) {
-  // More than one chain (n_epochs > 8): the chains run back to back without a read-back between them -- the asynchronous form with the info rows in a device block of the
-  // context -- and the host synchronises ONCE, at the end of the call: the device no longer idles while the host reads back, records and uploads the next chain
-  // (C4, 50 epochs per call: 180 -> ~155 us per epoch). Same results; a NaN gradient norm is reported from the rows.
+  // more than one chain: one read-back at the end of the call (see epochs_one_readback)
   if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
-    crux_ctx* c = actor->ctx; const size_t need = sizeof(float) * 3 * CRUX_INFO_N * (size_t)n_epochs;
-    if (c->epoch_rows_bytes < need) { if (c->epoch_rows) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_rows); c->epoch_rows = nullptr; c->epoch_rows_bytes = 0; }
-      if (hipMalloc(&c->epoch_rows, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "sac epochs: info rows"); c->epoch_rows_bytes = 2 * need; }
-    HIPCHK(c, hipMemsetAsync(c->epoch_rows, 0, need, c->stream));
-    int32_t rc = sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                                 sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, nullptr, (float*)c->epoch_rows);
-    if (rc) return rc;
-    std::vector<float> rows(3 * CRUX_INFO_N * (size_t)n_epochs);
-    HIPCHK(c, hipMemcpyAsync(rows.data(), c->epoch_rows, need, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
-    bool nan = false;
-    for (int e = 0; e < n_epochs; ++e) { const int ge = epoch0 + e; const bool has[3] = {true, ge % critic_every == 0, ge % actor_every == 0}; float* dst[3] = {infos_temp, infos_critic, infos_actor};
-      for (int sl = 0; sl < 3; ++sl) { const float* row = rows.data() + ((size_t)e * 3 + sl) * CRUX_INFO_N;
-        if (has[sl] && row[CRUX_INFO_GRAD_NORM] != row[CRUX_INFO_GRAD_NORM]) nan = true;
-        if (dst[sl] && has[sl]) memcpy(dst[sl] + (size_t)e * CRUX_INFO_N, row, sizeof(float) * CRUX_INFO_N); } }
-    if (nan) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in the SAC epochs");
-    return CRUX_OK;
+    float* const dst[3] = {infos_temp, infos_critic, infos_actor};
+    return epochs_one_readback(actor->ctx, "sac", "SAC", n_epochs, 3, dst,
+      [&](float* d_rows) { return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every,
+                                                  actor_every, sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, nullptr, d_rows); },
+      [&](int e) { const int ge = epoch0 + e; return 1u | (ge % critic_every == 0 ? 2u : 0u) | (ge % actor_every == 0 ? 4u : 0u); });
   }
   return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
                          sample_counter0, noise_seed, noise_counter0, infos_temp, infos_critic, infos_actor, nullptr);
@@ -905,56 +886,40 @@ static int32_t dpg_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* 
   //   Y.. Q(s, mu(s)) forward | its input gradient | slice | actor backward | norm | info, Adam | advance, polyak
   const int sq = (update_critic && B <= 256) ? 1 : 0;      // target + critic head(s) as a sequential one-block group (see crux_sac_epoch)
   const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);      // launches per pass (see crux_sac_epoch)
-  std::vector<int> ph; bool plan_ok = true; const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
-  const int ag = actor->nd.acts[LA - 1] != CRUX_ACT_IDENTITY ? 1 : 0;
-  if (LA != LQ || actor_targ->nd.L != LA || q1_targ->nd.L != LQ || (q2 && q2->nd.L != LQ) || (q2_targ && q2_targ->nd.L != LQ)) plan_ok = false;
-  if (FA != FQ || net_plan(actor_targ, B).nf != FA || net_plan(q1_targ, B).nf != FQ || (q2 && (net_plan(q2, B).nf != FQ || net_plan(q2, B).nb != BQ)) || (q2_targ && net_plan(q2_targ, B).nf != FQ)) plan_ok = false;
   // chained epochs: the sampling of epoch e + 1 beside the actor's norm and info + Adam of epoch e; its phase 2 reads the TARGET actor, which polyak (last phase) writes,
   // so the rest closes up by two only
-  auto tag = [&](size_t from, auto&& rule) { ExecRec* r = rec_of(c); int g = 0; const int base = r->chain ? r->chain_base : 0;
-    for (size_t i = from; i < r->ops.size(); ++i) { int p = rule(r->ops[i].kid, g); if (p < 0) { if (crux_sw().verbose) fprintf(stderr, "[cruxhip] dpg_epoch: op kind %d has no phase in the plan\n", r->ops[i].kid); plan_ok = false; p = 0; }
-      const int sub = p >> 12; p &= 4095;
-      ph.push_back(ph_tag(base > 0 ? (p < 2 ? base - 3 + p : base + p - 2) : p, sub)); } };
-  const size_t ops0 = exec_mark(c);
-  size_t m = ops0;
+  EpochTags tg(c, true, "dpg_epoch", 3, 2);
+  const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
+  const int ag = actor->nd.acts[LA - 1] != CRUX_ACT_IDENTITY ? 1 : 0;
+  if (LA != LQ || actor_targ->nd.L != LA || q1_targ->nd.L != LQ || (q2 && q2->nd.L != LQ) || (q2_targ && q2_targ->nd.L != LQ)) tg.plan_ok = false;
+  if (FA != FQ || net_plan(actor_targ, B).nf != FA || net_plan(q1_targ, B).nf != FQ || (q2 && (net_plan(q2, B).nf != FQ || net_plan(q2, B).nb != BQ)) || (q2_targ && net_plan(q2_targ, B).nf != FQ)) tg.plan_ok = false;
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  tag(m, [&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
-  m = exec_mark(c);
+  tg.tag([&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
   rc = crux_dpg_target(actor_targ, q1_targ, q2_targ, batch, gamma, sigma, eps_min, eps_max, a_min, a_max, noise_seed, noise_counter, d_y); if (rc) return bail(rc);
-  tag(m, [&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
+  tg.tag([&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
     return kid == OP_DPG_ACTION ? 2 + FA : kid == OP_DPG_TARGET ? X | (sq ? PH_SEQ_HEAD : 0) : -1; });
   if (update_critic) {
-    m = exec_mark(c);
     rc = q2 ? crux_double_q_step(q1, q2, batch, d_y, use_weight, info_critic) : crux_q_step(q1, batch, d_y, use_weight, info_critic); if (rc) return bail(rc);
-    tag(m, [&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
+    tg.tag([&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
       if (kid == OP_FILL) return 1; if (kid == OP_CONCAT_SA) return 2;
       if (is_mm(kid)) { const int k = (g++) % (FQ + BQo); return k < FQ ? 3 + k : X + 2 - sq + pq.stage(k - FQ); }
       return kid == OP_Q_HEAD ? (sq ? (X | PH_SEQ_TAIL) : X + 1) : kid == OP_SUMSQ2 ? X + 2 - sq + BQ : (kid == OP_CRITIC_INFO || kid == OP_ADAM_GATED) ? X + 3 - sq + BQ : kid == OP_ADAM_ADVANCE ? X + 4 - sq + BQ : -1; });
   }
   if (update_actor) {
-    m = exec_mark(c);
     rc = crux_dpg_actor_step(actor, q1, batch, info_actor); if (rc) return bail(rc);
-    tag(m, [&](int kid, int& g) {      // GEMMs: LA actor forward, LQ critic forward, LQ critic input gradients, then the actor's (weight, data) pairs
+    tg.tag([&](int kid, int& g) {      // GEMMs: LA actor forward, LQ critic forward, LQ critic input gradients, then the actor's (weight, data) pairs
       if (kid == OP_FILL) return 1;      // the info / status rows and the constant dQ = -1 / B
       if (is_mm(kid)) { const int k = g++; if (k < FA) return 2 + k; if (k < FA + FQ) return Y + (k - FA); if (k < FA + FQ + DQ) return Y + FQ + (k - FA - FQ);
         return Y + FQ + DQ + 1 + ag + pa.stage(k - FA - FQ - DQ); }
       if (kid == OP_ACT_GRAD) return ag ? Y + FQ + DQ + 1 : -1;      // dZ = act'(mu) .* dmu of a bounded (tanh) action head, between the slice and the actor's backward GEMMs
       return kid == OP_DPG_ACTION ? 2 + FA : kid == OP_SLICE_ROWS ? Y + FQ + DQ : kid == OP_SUMSQ2 ? Y + FQ + DQ + 1 + ag + BA : (kid == OP_MEAN_INFO || kid == OP_ADAM_GATED) ? Y + FQ + DQ + 2 + ag + BA :
              kid == OP_ADAM_ADVANCE ? Y + FQ + DQ + 3 + ag + BA : -1; });
-    m = exec_mark(c);
     rc = crux_polyak(actor_targ, actor, tau); if (rc) return bail(rc);
     rc = crux_polyak(q1_targ, q1, tau); if (rc) return bail(rc);
     if (q2 && q2_targ) { rc = crux_polyak(q2_targ, q2, tau); if (rc) return bail(rc); }
-    tag(m, [&](int kid, int&) { return kid == OP_POLYAK ? Y + FQ + DQ + 3 + ag + BA : -1; });
+    tg.tag([&](int kid, int&) { return kid == OP_POLYAK ? Y + FQ + DQ + 3 + ag + BA : -1; });
   }
-  ExecRec* r = rec_of(c);
-  if (r->chain) {
-    if (!(plan_ok && ph.size() == r->ops.size() - ops0)) r->chain_ok = false;
-    r->chain_tags.insert(r->chain_tags.end(), ph.begin(), ph.end()); r->chain_base += Y + FQ + DQ + 4 + ag + BA - (r->chain_base > 0 ? 2 : 0);
-    return CRUX_OK;
-  }
-  if (plan_ok && ph.size() == r->ops.size()) { rc = exec_schedule(c, ph); if (rc) return bail(rc); }
-  return crux_exec_run(c);
+  return tg.finish(Y + FQ + DQ + 4 + ag + BA);
 }
 
 // value_training's epoch loop with DDPG's / TD3's pieces in chains of up to 8 epochs per recorded list (see crux_sac_epochs). sigma < 0: no target-policy smoothing
@@ -964,40 +929,12 @@ static int32_t dpg_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor,
                         float* d_infos_async) {
   if (!actor || !q1 || !actor_targ || !q1_targ || !source || !batch || n_epochs < 1 || critic_every < 1 || actor_every < 1) return CRUX_EINVAL;
-  crux_ctx* c = actor->ctx;
-  const bool chain = !crux_sw().no_chained_epochs;
-  if (d_infos_async && !chain) return CRUX_EUNSUP;
-  auto flush = [&]() -> int32_t {
-    if (!crux_exec_recording(c)) return CRUX_OK;
-    ExecRec* r = rec_of(c); r->chain = false;
-    if (r->chain_ok && r->chain_tags.size() == r->ops.size()) { const int32_t rs = exec_schedule(c, r->chain_tags); if (rs) { crux_exec_abort(c); return rs; } }
-    r->async = d_infos_async != nullptr;
-    return crux_exec_run(c);
-  };
-  int32_t rc = CRUX_OK; int in_chain = 0;
-  for (int e = 0; e < n_epochs; ++e) {
-    const int ge = epoch0 + e; const int32_t uc = ge % critic_every == 0, ua = ge % actor_every == 0;
-    float* ic = infos_critic ? infos_critic + (size_t)e * CRUX_INFO_N : nullptr; float* ia = infos_actor ? infos_actor + (size_t)e * CRUX_INFO_N : nullptr;
-    if (chain) {
-      if (in_chain >= 8) { rc = flush(); in_chain = 0; if (rc) return rc; }
-      if (!in_chain) { rc = crux_exec_begin(c); if (rc) return rc; }
-      rec_of(c)->chain = true;
-    }
-    const size_t rb0 = chain && c->rec ? rec_of(c)->readbacks.size() : 0, tg0 = chain && c->rec ? rec_of(c)->chain_tags.size() : 0;
-    rc = dpg_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, uc, ua,
-                   sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + (uint64_t)e, ic, ia);
-    if (rc) { if (chain && c->rec) { rec_of(c)->chain = false; crux_exec_abort(c); } return rc; }
-    if (d_infos_async) {      // rows 2 e (critic) and 2 e + 1 (actor) of the caller's device array, copied in the epoch's last phase
-      ExecRec* r = rec_of(c);
-      if (!crux_exec_recording(c) || r->readbacks.size() != rb0 + (uc ? 1 : 0) + (ua ? 1 : 0) || r->chain_tags.size() != r->ops.size()) { if (c->rec) { r->chain = false; crux_exec_abort(c); } return crux_fail(c, CRUX_EHIP, "dpg epochs (async): unexpected recording"); }
-      int tmax = 0; for (size_t k = tg0; k < r->chain_tags.size(); ++k) tmax = std::max(tmax, r->chain_tags[k] & ~3);
-      size_t q = rb0; const int has[2] = {uc, ua};
-      for (int sl = 0; sl < 2; ++sl) { if (!has[sl]) continue;
-        crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_infos_async + ((size_t)e * 2 + sl) * CRUX_INFO_N, (const float*)r->readbacks[q++].d_info, (int64_t)CRUX_INFO_N);
-        r->chain_tags.push_back(tmax); } }
-    if (chain) ++in_chain;
-  }
-  return chain ? flush() : rc;
+  auto record = [&](int e) { const int ge = epoch0 + e; const size_t o = (size_t)e * CRUX_INFO_N;
+    return dpg_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, ge % critic_every == 0, ge % actor_every == 0,
+                     sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + (uint64_t)e, infos_critic ? infos_critic + o : nullptr, infos_actor ? infos_actor + o : nullptr); };
+  // rows 2 e (critic) and 2 e + 1 (actor)
+  auto rows = [&](int e) { const int ge = epoch0 + e; return EpochRows{(ge % critic_every == 0 ? 1u : 0u) | (ge % actor_every == 0 ? 2u : 0u), 0}; };
+  return run_epoch_chains(actor->ctx, "dpg", !crux_sw().no_chained_epochs, nullptr, n_epochs, 2, d_infos_async, record, rows, [] { return CRUX_OK; });
 }
 // crux_dpg_epochs without the host in the loop (see crux_dqn_epochs_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows of every epoch
 int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
@@ -1010,24 +947,13 @@ int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_
 int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) {
-  // several chains per call: run back to back, one synchronisation at the end of the call (see crux_sac_epochs)
+  // several chains per call: run back to back, one read-back at the end of the call (see epochs_one_readback)
   if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
-    crux_ctx* c = actor->ctx; const size_t need = sizeof(float) * 2 * CRUX_INFO_N * (size_t)n_epochs;
-    if (c->epoch_rows_bytes < need) { if (c->epoch_rows) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_rows); c->epoch_rows = nullptr; c->epoch_rows_bytes = 0; }
-      if (hipMalloc(&c->epoch_rows, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "dpg epochs: info rows"); c->epoch_rows_bytes = 2 * need; }
-    HIPCHK(c, hipMemsetAsync(c->epoch_rows, 0, need, c->stream));
-    int32_t rc = dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                                 sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, (float*)c->epoch_rows);
-    if (rc) return rc;
-    std::vector<float> rows(2 * CRUX_INFO_N * (size_t)n_epochs);
-    HIPCHK(c, hipMemcpyAsync(rows.data(), c->epoch_rows, need, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
-    bool nan = false;
-    for (int e = 0; e < n_epochs; ++e) { const int ge = epoch0 + e; const bool has[2] = {ge % critic_every == 0, ge % actor_every == 0}; float* dst[2] = {infos_critic, infos_actor};
-      for (int sl = 0; sl < 2; ++sl) { const float* row = rows.data() + ((size_t)e * 2 + sl) * CRUX_INFO_N;
-        if (has[sl] && row[CRUX_INFO_GRAD_NORM] != row[CRUX_INFO_GRAD_NORM]) nan = true;
-        if (dst[sl] && has[sl]) memcpy(dst[sl] + (size_t)e * CRUX_INFO_N, row, sizeof(float) * CRUX_INFO_N); } }
-    if (nan) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in the DDPG / TD3 epochs");
-    return CRUX_OK;
+    float* const dst[2] = {infos_critic, infos_actor};
+    return epochs_one_readback(actor->ctx, "dpg", "DDPG / TD3", n_epochs, 2, dst,
+      [&](float* d_rows) { return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs,
+                                                  critic_every, actor_every, sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, d_rows); },
+      [&](int e) { const int ge = epoch0 + e; return (ge % critic_every == 0 ? 1u : 0u) | (ge % actor_every == 0 ? 2u : 0u); });
   }
   return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
                          sample_counter0, noise_seed, noise_counter0, infos_critic, infos_actor, nullptr);

@@ -138,39 +138,32 @@ def _value_training_sac(solver, D, gamma):
         # same pieces, order and draws as the epoch-by-epoch branch below
         _set_stream_for(buf, solver.sample_seed)
         n = c_opt.epochs; ctr0 = solver.i * n
+        ce, ae, tn, cn, an = int(c_opt.update_every), int(a_opt.update_every), t_opt.name, c_opt.name, a_opt.name
+        def decode(raws):      # raws: [epochs x 3] rows, temperature | critics | actor
+            out, nan = [], False
+            for epoch in range(len(raws) // 3):
+                rt_, rq_, ra_ = raws[3 * epoch], raws[3 * epoch + 1], raws[3 * epoch + 2]
+                info = {tn + "loss": float(rt_[0]), tn + "grad_norm": float(rt_[1]), "SAC alpha": float(rt_[L.INFO["alpha"]])}; nan = nan or bool(np.isnan(rt_[1]))
+                if epoch % ce == 0:
+                    info.update({cn + "loss": float(rq_[0]), cn + "grad_norm": float(rq_[1]), "Q1avg": float(rq_[L.INFO["q1avg"]]), "Q2avg": float(rq_[L.INFO["q2avg"]])}); nan = nan or bool(np.isnan(rq_[1]))
+                if epoch % ae == 0:
+                    info.update({an + "loss": float(ra_[0]), an + "grad_norm": float(ra_[1]), "entropy": float(ra_[L.INFO["entropy"]])}); nan = nan or bool(np.isnan(ra_[1]))
+                out.append(info)
+            return out, nan
+        args = (A.h, Q.N1.h, Q.N2.h, pim.A.h, Qm.N1.h, Qm.N2.h, la.h, buf.h, D.h, float(gamma), float(solver.P["SAC_H_target"]), float(solver.tau),
+                1 if solver.weighted_loss else 0, 0, n, ce, ae, ctr0, solver.noise_seed, 3 * ctr0)
         if getattr(solver, "_async_now", False):
             d_rows, row0 = _info_ring(solver, ctx, 3 * n)
-            rc = lib.crux_sac_epochs_async(A.h, Q.N1.h, Q.N2.h, pim.A.h, Qm.N1.h, Qm.N2.h, la.h, buf.h, D.h, float(gamma), float(solver.P["SAC_H_target"]), float(solver.tau),
-                                           1 if solver.weighted_loss else 0, 0, n, int(c_opt.update_every), int(a_opt.update_every), ctr0, solver.noise_seed, 3 * ctr0, d_rows)
+            rc = lib.crux_sac_epochs_async(*args, d_rows)
             if rc == L.OK:
-                ce, ae, tn, cn, an = int(c_opt.update_every), int(a_opt.update_every), t_opt.name, c_opt.name, a_opt.name
-                def decode(raws):
-                    out, nan = [], False
-                    for epoch in range(len(raws) // 3):
-                        rt_, rq_, ra_ = raws[3 * epoch], raws[3 * epoch + 1], raws[3 * epoch + 2]
-                        info = {tn + "loss": float(rt_[0]), tn + "grad_norm": float(rt_[1]), "SAC alpha": float(rt_[L.INFO["alpha"]])}; nan = nan or bool(np.isnan(rt_[1]))
-                        if epoch % ce == 0:
-                            info.update({cn + "loss": float(rq_[0]), cn + "grad_norm": float(rq_[1]), "Q1avg": float(rq_[L.INFO["q1avg"]]), "Q2avg": float(rq_[L.INFO["q2avg"]])}); nan = nan or bool(np.isnan(rq_[1]))
-                        if epoch % ae == 0:
-                            info.update({an + "loss": float(ra_[0]), an + "grad_norm": float(ra_[1]), "entropy": float(ra_[L.INFO["entropy"]])}); nan = nan or bool(np.isnan(ra_[1]))
-                        out.append(info)
-                    return out, nan
                 solver._dinfos_used += 3 * n
                 return _PendingInfo(row0, 3 * n, decode)
             if rc != L.EUNSUP:
                 ctx.check(rc)
             solver._async_now = False; solver._async_fell_back = True
-        rt, rq, ra = (np.zeros((n, L.INFO_N), np.float32) for _ in range(3))
-        ctx.check(lib.crux_sac_epochs(A.h, Q.N1.h, Q.N2.h, pim.A.h, Qm.N1.h, Qm.N2.h, la.h, buf.h, D.h, float(gamma), float(solver.P["SAC_H_target"]), float(solver.tau),
-                                      1 if solver.weighted_loss else 0, 0, n, int(c_opt.update_every), int(a_opt.update_every), ctr0, solver.noise_seed, 3 * ctr0,
-                                      _vp(rt), _vp(rq), _vp(ra)))
-        for epoch in range(n):
-            info = {t_opt.name + "loss": float(rt[epoch, 0]), t_opt.name + "grad_norm": float(rt[epoch, 1]), "SAC alpha": float(rt[epoch, L.INFO["alpha"]])}
-            if epoch % c_opt.update_every == 0:
-                info.update({c_opt.name + "loss": float(rq[epoch, 0]), c_opt.name + "grad_norm": float(rq[epoch, 1]), "Q1avg": float(rq[epoch, L.INFO["q1avg"]]), "Q2avg": float(rq[epoch, L.INFO["q2avg"]])})
-            if epoch % a_opt.update_every == 0:
-                info.update({a_opt.name + "loss": float(ra[epoch, 0]), a_opt.name + "grad_norm": float(ra[epoch, 1]), "entropy": float(ra[epoch, L.INFO["entropy"]])})
-            infos.append(info)
+        rows = np.zeros((3, n, L.INFO_N), np.float32)
+        ctx.check(lib.crux_sac_epochs(*args, _vp(rows[0]), _vp(rows[1]), _vp(rows[2])))
+        infos = decode(rows.transpose(1, 0, 2).reshape(3 * n, L.INFO_N))[0]
     for epoch in range(0 if fused else c_opt.epochs):
         ctr = solver.i * c_opt.epochs + epoch                                                          # one Philox counter block per epoch
         upd_c, upd_a = epoch % c_opt.update_every == 0, epoch % a_opt.update_every == 0                # :91, :96
@@ -218,43 +211,33 @@ def _value_training_dpg(solver, D, gamma):
         # the whole epoch loop (:69-104) in one C call: chains of up to 8 epochs per recorded list (cruxhip.h: crux_dpg_epochs); same pieces, order and draws as below
         _set_stream_for(buf, solver.sample_seed)
         n = c_opt.epochs; ctr0 = solver.i * n
+        ce, ae, cn, an, tw = int(c_opt.update_every), int(a_opt.update_every), c_opt.name, a_opt.name, twin
+        def decode(raws):      # raws: [epochs x 2] rows, critic | actor
+            out, nan = [], False
+            for epoch in range(len(raws) // 2):
+                rq_, ra_ = raws[2 * epoch], raws[2 * epoch + 1]; info = {}
+                if epoch % ce == 0:
+                    info.update({"Q1avg": float(rq_[L.INFO["q1avg"]]), "Q2avg": float(rq_[L.INFO["q2avg"]])} if tw else {"Qavg": float(rq_[L.INFO["q1avg"]])})
+                    info.update({cn + "loss": float(rq_[0]), cn + "grad_norm": float(rq_[1])}); nan = nan or bool(np.isnan(rq_[1]))
+                if epoch % ae == 0:
+                    info.update({an + "loss": float(ra_[0]), an + "grad_norm": float(ra_[1])}); nan = nan or bool(np.isnan(ra_[1]))
+                out.append(info)
+            return out, nan
+        args = (A.h, (Q.N1 if twin else Q).h, Q.N2.h if twin else None, Am.h, (Qm.N1 if twin else Qm).h, Qm.N2.h if twin else None, buf.h, D.h,
+                float(gamma), float(solver.tau), sm.sigma if sm else -1.0, sm.eps_min if sm else 0.0, sm.eps_max if sm else 0.0, sm.a_min if sm else 0.0,
+                sm.a_max if sm else 0.0, 1 if solver.weighted_loss else 0, 0, n, ce, ae, ctr0, solver.noise_seed, ctr0)
         if getattr(solver, "_async_now", False):
             d_rows, row0 = _info_ring(solver, ctx, 2 * n)
-            rc = lib.crux_dpg_epochs_async(A.h, (Q.N1 if twin else Q).h, Q.N2.h if twin else None, Am.h, (Qm.N1 if twin else Qm).h, Qm.N2.h if twin else None, buf.h, D.h,
-                                           float(gamma), float(solver.tau), sm.sigma if sm else -1.0, sm.eps_min if sm else 0.0, sm.eps_max if sm else 0.0, sm.a_min if sm else 0.0,
-                                           sm.a_max if sm else 0.0, 1 if solver.weighted_loss else 0, 0, n, int(c_opt.update_every), int(a_opt.update_every), ctr0,
-                                           solver.noise_seed, ctr0, d_rows)
+            rc = lib.crux_dpg_epochs_async(*args, d_rows)
             if rc == L.OK:
-                ce, ae, cn, an, tw = int(c_opt.update_every), int(a_opt.update_every), c_opt.name, a_opt.name, twin
-                def decode(raws):
-                    out, nan = [], False
-                    for epoch in range(len(raws) // 2):
-                        rq_, ra_ = raws[2 * epoch], raws[2 * epoch + 1]; info = {}
-                        if epoch % ce == 0:
-                            info.update({"Q1avg": float(rq_[L.INFO["q1avg"]]), "Q2avg": float(rq_[L.INFO["q2avg"]])} if tw else {"Qavg": float(rq_[L.INFO["q1avg"]])})
-                            info.update({cn + "loss": float(rq_[0]), cn + "grad_norm": float(rq_[1])}); nan = nan or bool(np.isnan(rq_[1]))
-                        if epoch % ae == 0:
-                            info.update({an + "loss": float(ra_[0]), an + "grad_norm": float(ra_[1])}); nan = nan or bool(np.isnan(ra_[1]))
-                        out.append(info)
-                    return out, nan
                 solver._dinfos_used += 2 * n
                 return _PendingInfo(row0, 2 * n, decode)
             if rc != L.EUNSUP:
                 ctx.check(rc)
             solver._async_now = False; solver._async_fell_back = True
-        rq, ra = (np.zeros((n, L.INFO_N), np.float32) for _ in range(2))
-        ctx.check(lib.crux_dpg_epochs(A.h, (Q.N1 if twin else Q).h, Q.N2.h if twin else None, Am.h, (Qm.N1 if twin else Qm).h, Qm.N2.h if twin else None, buf.h, D.h,
-                                      float(gamma), float(solver.tau), sm.sigma if sm else -1.0, sm.eps_min if sm else 0.0, sm.eps_max if sm else 0.0, sm.a_min if sm else 0.0,
-                                      sm.a_max if sm else 0.0, 1 if solver.weighted_loss else 0, 0, n, int(c_opt.update_every), int(a_opt.update_every), ctr0,
-                                      solver.noise_seed, ctr0, _vp(rq), _vp(ra)))
-        for epoch in range(n):
-            info = {}
-            if epoch % c_opt.update_every == 0:
-                info.update({"Q1avg": float(rq[epoch, L.INFO["q1avg"]]), "Q2avg": float(rq[epoch, L.INFO["q2avg"]])} if twin else {"Qavg": float(rq[epoch, L.INFO["q1avg"]])})
-                info.update({c_opt.name + "loss": float(rq[epoch, 0]), c_opt.name + "grad_norm": float(rq[epoch, 1])})
-            if epoch % a_opt.update_every == 0:
-                info.update({a_opt.name + "loss": float(ra[epoch, 0]), a_opt.name + "grad_norm": float(ra[epoch, 1])})
-            infos.append(info)
+        rows = np.zeros((2, n, L.INFO_N), np.float32)
+        ctx.check(lib.crux_dpg_epochs(*args, _vp(rows[0]), _vp(rows[1])))
+        infos = decode(rows.transpose(1, 0, 2).reshape(2 * n, L.INFO_N))[0]
     for epoch in range(0 if fused else c_opt.epochs):
         ctr = solver.i * c_opt.epochs + epoch
         solver._rand(D, ctr)                                                                           # :71 rand!(D, buffer, extra_buffers...; fracs, i=S.i)
@@ -315,6 +298,9 @@ def value_training(solver, D, gamma):
         _set_stream_for(buf, solver.sample_seed)
         beta = float(np.float32(buf.beta(solver.i))) if buf.isprioritized() else 0.0                       # rand!(D, buffer, i=S.i): beta(S.i)
         raws = np.zeros((p.epochs, L.INFO_N), np.float32)
+        name = p.name
+        def decode(raws):
+            return [{name + "loss": float(r[0]), name + "grad_norm": float(r[1]), "Qavg": float(r[2])} for r in raws], bool(np.isnan(raws[:, 1]).any())
         if getattr(solver, "_async_now", False):
             # no host in the loop: the chain is enqueued and the info rows stay on the device (OffPolicySolver.history fetches them)
             d_rows, _row0 = _info_ring(solver, ctx, p.epochs)
@@ -323,19 +309,17 @@ def value_training(solver, D, gamma):
             rc = ctx.lib.crux_dqn_value_training_async(pi.h, pim.h, buf.h, D.h, float(gamma), float(solver.P["alpha"]) if solver.target_fn == "softq" else 0.0,
                                                        1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, float(np.float32(solver.tau)), d_rows)
             if rc == L.OK:
-                name = p.name; row0 = _row0
-                def decode(raws):
-                    return [{name + "loss": float(r[0]), name + "grad_norm": float(r[1]), "Qavg": float(r[2])} for r in raws], bool(np.isnan(raws[:, 1]).any())
-                pend = _PendingInfo(row0, p.epochs, decode); solver._dinfos_used += p.epochs
-                return pend                                                                                # (:108 ran inside the chain)
+                solver._dinfos_used += p.epochs
+                return _PendingInfo(_row0, p.epochs, decode)                                               # (:108 ran inside the chain)
             if rc != L.EUNSUP:
                 ctx.check(rc)
             solver._async_now = False; solver._async_fell_back = True      # narrow networks: the synchronous entry point from here on
+        rest = (1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, _vp(raws))
         if solver.target_fn == "softq":      # softq_target(alpha) in place of dqn_target (rl/softq.jl:4-13)
-            ctx.check(ctx.lib.crux_softq_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), float(solver.P["alpha"]), 1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, _vp(raws)))
+            ctx.check(ctx.lib.crux_softq_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), float(solver.P["alpha"]), *rest))
         else:
-            ctx.check(ctx.lib.crux_dqn_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), 1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, _vp(raws)))
-        infos = [{p.name + "loss": float(r[0]), p.name + "grad_norm": float(r[1]), "Qavg": float(r[2])} for r in raws]
+            ctx.check(ctx.lib.crux_dqn_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), *rest))
+        infos = decode(raws)[0]
     for epoch in range(0 if fused else p.epochs):
         raw = np.zeros(L.INFO_N, np.float32); info = {}
         solver._rand(D, solver.i * p.epochs + epoch)                                                   # :71 rand!(D, buffer, extra_buffers...; fracs, i=S.i): beta(S.i); the Philox counter is unique per draw
