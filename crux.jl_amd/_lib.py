@@ -164,6 +164,8 @@ SIGNATURES = {
     "crux_cql_critic_step": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, u64, u64, vp]),
     "crux_cql_alpha_step": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp]),
     "crux_cql_conservative": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp, vp, vp]),
+    "crux_gradient_penalty": (i32, [vp, vp, vp, i64, f32, f32, i32, u64, u64, vp]),
+    "crux_iq_step": (i32, [vp, vp, i64, f32, i32, f32, i32, f32, u64, u64, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

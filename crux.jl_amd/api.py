@@ -38,8 +38,10 @@ from .off_policy import (  # noqa: F401
     _value_training_dpg, _value_training_sac, ddpg_actor_loss, double_Q_loss, sac_actor_loss, sac_temp_loss, td3_actor_loss, td_loss, value_training, value_training_async)
 from .batch import *   # noqa: F401,F403
 from .batch import BatchSAC, CQL, UniformBox, _solve_batch_ac, cql_alpha_loss, cql_critic_loss   # noqa: F401
+from .il_off_policy import *   # noqa: F401,F403
+from .il_off_policy import OnlineIQLearn, SQIL, _value_training_iq, gradient_penalty, iq_loss, sqil_callback   # noqa: F401
 from .on_policy import _solve_on_policy
-from . import core, on_policy, imitation, off_policy, batch   # noqa: F401
+from . import core, on_policy, imitation, off_policy, batch, il_off_policy   # noqa: F401
 
 
 def solve(solver, mdp=None):  # noqa: F811

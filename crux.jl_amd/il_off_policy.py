@@ -1,0 +1,142 @@
+"""il_off_policy.py -- off-policy imitation learning: OnlineIQLearn and SQIL (src/model_free/il/iqlearn.jl, il/sqil.jl) and gradient_penalty
+(src/extras/gradient_penalty.jl).
+
+Both constructors add a normalised copy of the demonstrations to an off-policy solver as an extra buffer drawn at buffer_fractions = [1/2, 1/2]. The staging
+minibatch is then laid out by split_batches as B_p buffer rows followed by B - B_p demo rows, so where the reference marks demo rows with a Bool :expert column
+(iq_callback, required_columns=[:expert]) this module passes B_p to the critic step instead: the reference's column is false on every buffer row and true on every
+demo row. No buffer column is added. iq_loss's critic step, the penalty and its second-order pass are HIP (csrc/iq.hip: crux_iq_step, crux_gradient_penalty)."""
+import numpy as np
+
+from . import _lib as L
+from .core import ContinuousSpace, DiscreteNetwork, DiscreteSpace, _Loss, _ensure_opt, _vp, copy_buffer, normalize_, split_batches
+from .off_policy import SAC, SoftQ
+
+
+class _IqLoss(_Loss):
+    """iq_loss(; gamma=0.9, reg=true, alpha_reg=0.5, gp=true, lambda_gp=10) (iqlearn.jl:49-95): the marker value_training routes to crux_iq_step."""
+
+    def __init__(self, gamma, reg, alpha_reg, gp, lambda_gp):
+        super().__init__("iq")
+        self.gamma, self.reg, self.alpha_reg = float(np.float32(gamma)), bool(reg), float(np.float32(alpha_reg))
+        self.gp, self.lambda_gp = bool(gp), float(np.float32(lambda_gp))
+
+
+def iq_loss(gamma=0.9, reg=True, alpha_reg=0.5, gp=True, lambda_gp=10.0):
+    """iq_loss(; γ=0.9f0, reg=true, α_reg=0.5f0, gp=true, λ_gp=10f0) (iqlearn.jl:49). γ is the loss's own discount, not the MDP's; soft values use alpha = 1."""
+    return _IqLoss(gamma, reg, alpha_reg, gp, lambda_gp)
+
+
+def _dev_cols(ctx, a):
+    a = np.asfortranarray(np.asarray(a, np.float32))
+    if a.ndim != 2:
+        raise ValueError("gradient_penalty: states are (features, batch) arrays")
+    d = ctx.alloc(4 * a.size); ctx.h2d(d, a)
+    return d, a.shape
+
+
+def gradient_penalty(net, x, xtilde=None, target=1.0, seed=0, counter=0):
+    """gradient_penalty(D, x[, xtilde]; target=1f0) (extras/gradient_penalty.jl): mean over columns of (|d sum(D(xhat)) / d xhat| - target)^2 with
+    xhat = eps xtilde + (1 - eps) x, eps_j ~ U(0, 1) per column (include/crux_rng.h, IQ_GP; xtilde=None: xhat = x). Returns the value.
+
+    The draws are a pure function of (seed, counter): calls with the same pair interpolate with the same eps. The reference draws fresh uniforms on every call,
+    so a caller that wants that must pass a counter of its own per call (OnlineIQLearn passes noise_seed and i epochs + epoch)."""
+    ctx = net.ctx
+    d_in = net.network.dims[0]
+    for name, v in (("x", x), ("xtilde", xtilde)):
+        if v is not None and (np.ndim(v) != 2 or np.shape(v)[0] != d_in):
+            raise ValueError("gradient_penalty: %s has shape %s, the network expects (%d, batch)" % (name, np.shape(v), d_in))
+    dx, shp = _dev_cols(ctx, x); dxt = None
+    try:
+        if xtilde is not None:
+            dxt, shp2 = _dev_cols(ctx, xtilde)
+            if shp2 != shp:
+                raise ValueError("gradient_penalty: x and xtilde differ in shape (%s, %s)" % (shp, shp2))
+        out = np.zeros(1, np.float32)
+        ctx.check(ctx.lib.crux_gradient_penalty(net.h, dx, dxt, shp[1], float(np.float32(target)), 1.0, 0, int(seed), int(counter), _vp(out)))
+        return float(out[0])
+    finally:
+        ctx.free(dx)
+        if dxt is not None:
+            ctx.free(dxt)
+
+
+def _demo_buffer(demo, S, A, normalize_demo):
+    """normalize_demo && (D_demo = normalize!(deepcopy(D_demo), S, A)): the caller's buffer is never modified"""
+    d = copy_buffer(demo)
+    if normalize_demo:
+        normalize_(d, S, A)
+    return d
+
+
+def _space(pi, demo):
+    """action_space(pi): a DiscreteNetwork's own; for the continuous policies of SAC a unit ContinuousSpace, which leaves the demo actions unchanged"""
+    return DiscreteSpace(len(pi.outputs), pi.outputs) if isinstance(pi, DiscreteNetwork) else ContinuousSpace(demo.act_dim)
+
+
+def OnlineIQLearn(pi, S, demo, gamma=0.9, normalize_demo=True, solver=SoftQ, reg=True, alpha_reg=0.5, gp=True, lambda_gp=10.0, **kw):
+    """OnlineIQLearn(; π, S, 𝒟_demo, γ=0.9f0, normalize_demo=true, solver=SoftQ, reg=true, α_reg=0.5f0, gp=true, λ_gp=10f0, kwargs...) (iqlearn.jl:98-138):
+    `solver` with the demonstrations as an extra buffer at [1/2, 1/2], c_opt.loss = iq_loss(...) and no target (target_fn returns nothing). Only SoftQ:
+    the reference defines soft_value for a DiscreteNetwork alone. The penalty interpolates between the two halves of the minibatch, so an odd batch size
+    (or any split other than half and half) is refused."""
+    if solver is SAC:
+        raise NotImplementedError("OnlineIQLearn with SAC: iq_loss needs soft_value, which the reference defines for a DiscreteNetwork only (softq.jl:7)")
+    if not isinstance(pi, DiscreteNetwork):
+        raise NotImplementedError("OnlineIQLearn: pi must be a DiscreteNetwork (iq_loss uses soft_value(pi, s), softq.jl:7)")
+    c = dict(kw.pop("c_opt", None) or {})
+    bs = int(c.get("batch_size", 128))
+    if bs % 2:
+        raise ValueError("OnlineIQLearn: batch_size %d is odd; the gradient penalty pairs every demo row with a policy row" % bs)
+    d = _demo_buffer(demo, S, _space(pi, demo), normalize_demo)
+    sv = solver(pi=pi, S=S, c_opt=c, extra_buffers=[d], buffer_fractions=[0.5, 0.5], **kw)
+    sv.c_opt.loss = iq_loss(gamma=gamma, reg=reg, alpha_reg=alpha_reg, gp=gp, lambda_gp=lambda_gp)
+    sv.target_fn = None                  # target_fn = (args...; kwargs...) -> nothing
+    sv.demo = d
+    return sv
+
+
+def _value_training_iq(solver, D, gamma):
+    """value_training(S, D, gamma) (off_policy.jl:66-111) when c_opt.loss is iq_loss: per epoch rand! -> post_batch_callback -> train!(Q, iq_loss) (no target,
+    no priorities); then the final target update (:108). Philox counters: sampling i epochs + epoch (as every value_training), penalty draws noise_seed with the same
+    counter. Info keys as the reference's train! and iq_loss name them."""
+    pi, p, ctx, lo = solver.agent.pi, solver.c_opt, solver.buffer.ctx, solver.c_opt.loss
+    _ensure_opt(pi, p)
+    B = D.capacity
+    fr = [0.0 if len(b) == 0 else f for b, f in zip(solver._sources(), solver.buffer_fractions)]
+    n_policy = split_batches(B, [f / sum(fr) for f in fr])[0]
+    infos = []
+    for epoch in range(p.epochs):
+        ctr = solver.i * p.epochs + epoch
+        info = {}
+        solver._rand(D, ctr)                                                                           # :71
+        if solver.post_batch_callback is not None:
+            solver.post_batch_callback(D, S=solver, info=info)                                         # :77
+        if epoch % p.update_every == 0:                                                                # :91
+            raw, iq = np.zeros(L.INFO_N, np.float32), np.zeros(6, np.float32)
+            ctx.check(ctx.lib.crux_iq_step(pi.h, D.h, n_policy, lo.gamma, 1 if lo.reg else 0, lo.alpha_reg, 1 if lo.gp else 0, lo.lambda_gp,
+                                           solver.noise_seed, ctr, _vp(raw), _vp(iq)))
+            info.update({"softQloss": float(iq[0]), "valueloss": float(iq[1]), "avg_R_expert_IQ": float(iq[2]), "avg_R_demo_IQ": float(iq[3])})
+            if lo.gp:
+                info["grad_pen"] = float(iq[4])
+            if lo.reg:
+                info["reg_loss"] = float(iq[5])
+            info.update({p.name + "loss": float(raw[L.INFO["loss"]]), p.name + "grad_norm": float(raw[L.INFO["grad_norm"]])})
+        infos.append(info)
+    solver._update_target(final=True)                                                                  # :108
+    keys = {k for d in infos for k in d}
+    return {k: float(np.mean([d[k] for d in infos if k in d])) for k in keys}                          # aggregate_info (logging.jl:60-66)
+
+
+def sqil_callback(D, S=None, info=None):
+    """sqil_callback(D; kwargs...) = D[:r] .= 0 (sqil.jl:1-3): the freshly sampled rows get reward 0, the demonstrations keep theirs."""
+    D["r"][...] = 0
+
+
+def SQIL(pi, S, demo, normalize_demo=True, solver=SAC, **kw):
+    """SQIL(; π, S, 𝒟_demo, normalize_demo=true, solver=SAC, kwargs...) (sqil.jl:20-39): `solver` (SAC or SoftQ) with post_sample_callback = sqil_callback and the
+    demonstrations, which must carry :r, as an extra buffer at [1/2, 1/2]."""
+    if not demo.haskey("r"):
+        raise ValueError("SQIL requires a reward value for the demonstrations")
+    d = _demo_buffer(demo, S, _space(pi, demo), normalize_demo)
+    sv = solver(pi=pi, S=S, post_sample_callback=sqil_callback, extra_buffers=[d], buffer_fractions=[0.5, 0.5], **kw)
+    sv.demo = d
+    return sv

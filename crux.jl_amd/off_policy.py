@@ -281,6 +281,9 @@ def _upload_target(solver, D, y):
 def value_training(solver, D, gamma):
     """value_training(S, D, gamma) (src/model_free/off_policy.jl:66-111) for the critic-only (DQN) case: per epoch
     rand! -> post_batch_callback -> target_fn -> [update_priorities!(priority_fn)] -> train!(td_loss); then target_update once (:108)."""
+    if getattr(solver.c_opt.loss, "name", None) == "iq":          # OnlineIQLearn: train!(Q, iq_loss) with no target (il_off_policy.py)
+        from .il_off_policy import _value_training_iq
+        return _value_training_iq(solver, D, gamma)
     if solver.target_fn == "sac" or (callable(solver.target_fn) and solver.a_opt is not None and isinstance(solver.agent.pi.A, GaussianPolicy)):
         return _value_training_sac(solver, D, gamma)
     if solver.target_fn in ("ddpg", "td3"):

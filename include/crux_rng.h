@@ -29,7 +29,9 @@ enum {
   CRUX_RNG_INIT = 7,       /* glorot-uniform parameter init                                  */
   CRUX_RNG_RANDACT = 8,    /* the random action of an eps-greedy draw                        */
   CRUX_RNG_RESERVOIR = 9,  /* push_reservoir!: v[0..1] -> rand() of the weight test, v[2..3] -> rand(1:total_count) */
-  CRUX_RNG_CQL_UNIFORM = 10 /* CQL's importance-sampling actions: Float32.(rand(Product(Uniform(lo, hi)))) (cruxhip.h, CQL paragraph) */
+  CRUX_RNG_CQL_UNIFORM = 10, /* CQL's importance-sampling actions: Float32.(rand(Product(Uniform(lo, hi)))) (cruxhip.h, CQL paragraph) */
+  CRUX_RNG_IQ_GP = 11       /* gradient_penalty's interpolation weights: eps_j = (float)u53(Philox(seed, counter, j, IQ_GP)) for penalty column j,
+                               xhat_j = eps_j xtilde_j + (1 - eps_j) x_j (cruxhip.h, IQ paragraph); OnlineIQLearn: seed = noise_seed, counter = i epochs + epoch */
 };
 
 typedef struct { uint32_t v[4]; } crux_u32x4;

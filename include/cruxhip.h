@@ -628,6 +628,25 @@ int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
 int32_t crux_cql_conservative(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, int32_t n_samples, float is_lo, float is_hi,
                               float thresh, uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs);
 
+/* OnlineIQLearn (src/model_free/il/iqlearn.jl) and gradient_penalty (src/extras/gradient_penalty.jl) on the dense engine -----------------------------------
+ * gradient_penalty(D, x, xtilde; target): per column j of B, xhat_j = eps_j xtilde_j + (1 - eps_j) x_j with eps_j = (float)u53(Philox(seed, counter, j, IQ_GP))
+ * (crux_rng.h; d_xtilde NULL: xhat = x, the one-argument form); g_j = d(sum of the outputs of D(xhat_j)) / d xhat_j; P = mean_j (|g_j| - target)^2.
+ * *penalty_out (host) = P. accumulate != 0: lambda dP/dtheta is ADDED to crux_mlp_grads_ptr(net) (a second-order pass through the network). |g_j| = 0 makes that
+ * gradient NaN, as Zygote's sqrt does. d_x / d_xtilde: device [w x B] with w the network's input width (not checked here: the host binding checks it).
+ * The same (seed, counter) gives the same eps; callers wanting fresh draws per call pass a counter of their own. Identity, relu and tanh layers.            */
+int32_t crux_gradient_penalty(crux_mlp* net, const float* d_x, const float* d_xtilde, int64_t B, float target, float lambda, int32_t accumulate,
+                              uint64_t seed, uint64_t counter, float* penalty_out);
+/* train!(Q, iq_loss(gamma_iq, reg, alpha_reg, gp, lambda_gp)) (iqlearn.jl:49-95) for a DiscreteNetwork Q over the staging minibatch: rows [0, n_policy) are buffer
+ * (policy) rows, the rest demo (expert) rows -- the layout split_batches gives a two-source rand!, standing in for the reference's :expert column. With V = logsumexp
+ * Q(s), V' = logsumexp Q(s') (alpha 1), y = gamma_iq (1 - done) V', R = Q(s, a) - y:
+ *   L = mean_expert(-R) + mean(V - y) [+ lambda_gp gradient_penalty(Q, s_expert, s_policy)] [+ mean(R^2) / (4 alpha_reg)]
+ * then the gradient norm, NaN => CRUX_ENAN with no update ("NaN detected!"), Adam. gp needs as many demo rows as policy rows; the penalty's eps draws are those of
+ * crux_gradient_penalty(seed, counter). A NaN in s, s' or a demo state surfaces as CRUX_ENAN. info_out (host [CRUX_INFO_N]): LOSS, GRAD_NORM; iq_out (host [6]):
+ * softQloss, valueloss, avg_R_expert_IQ, avg_R_demo_IQ, grad_pen (0 without gp), reg_loss (0 without reg). One host synchronisation per call.
+ * One forward pass covers the s, s' and penalty columns: 2B (+ B/2 with gp) must not exceed 2^20.                                                            */
+int32_t crux_iq_step(crux_mlp* q, crux_buffer* batch, int64_t n_policy, float gamma_iq, int32_t reg, float alpha_reg, int32_t gp, float lambda_gp,
+                     uint64_t seed, uint64_t counter, float* info_out, float* iq_out);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer

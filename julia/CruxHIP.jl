@@ -520,6 +520,23 @@ function cql_conservative(A::HipNetwork, Q1::HipNetwork, Q2::HipNetwork, logα::
     out
 end
 
+# OnlineIQLearn (src/model_free/il/iqlearn.jl): the staging minibatch holds n_policy buffer rows, then the demo rows (split_batches of rand! with fracs [1/2, 1/2]);
+# the penalty's interpolation weights are Philox(noise_seed, i epochs + epoch, j, IQ_GP) (include/crux_rng.h)
+function gradient_penalty(D::HipNetwork, d_x::Ptr{Float32}, d_xtilde::Ptr{Float32}, B::Integer; target::Float32=1f0, λ::Float32=1f0, accumulate::Bool=false,
+                          seed::UInt64=UInt64(0), ctr::UInt64=UInt64(0))                                                                 # gradient_penalty(D, x, xtilde) (C_NULL: x alone)
+    out = zeros(Float32, 1)
+    check(D.ctx, ccall((:crux_gradient_penalty, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32, Float32, Int32, UInt64, UInt64, Ptr{Float32}),
+                       D.h, d_x, d_xtilde, B, target, λ, Int32(accumulate), seed, ctr, out))
+    out[1]
+end
+function iq_step!(Q::HipNetwork, mb::HipBuffer, n_policy::Integer, γ::Float32, reg::Bool, α_reg::Float32, gp::Bool, λ_gp::Float32, seed::UInt64, ctr::UInt64,
+                  info=zeros(Float32, INFO_N))                                                                                           # train!(Q, iq_loss(...))
+    iq = zeros(Float32, 6)                                                                                                               # softQloss, valueloss, avg_R_expert_IQ, avg_R_demo_IQ, grad_pen, reg_loss
+    check(Q.ctx, ccall((:crux_iq_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float32, Int32, Float32, Int32, Float32, UInt64, UInt64, Ptr{Float32}, Ptr{Float32}),
+                       Q.h, mb.h, n_policy, γ, Int32(reg), α_reg, Int32(gp), λ_gp, seed, ctr, info, iq))
+    info, iq
+end
+
 # ---------------------------------------------------------------------------------------------------- user-written losses and the regularizer
 # The reference differentiates ANY loss(π, 𝒫, 𝒟) with Zygote (training.jl:16-18). The library's fast paths cover a closed list (loss_id above);
 # everything else composes the explicit pullback: forward with cached activations -> the user's d(loss)/d(output) -> parameter gradients ->
