@@ -111,6 +111,19 @@ void crux_prof_end(crux_ctx* ctx, int slot);
                                             hipGetErrorString(e__), __FILE__, __LINE__);        \
   } while (0)
 
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for kernel K, once per device (a second device in the process sets it for itself)
+template <auto K> static inline int32_t crux_lds_attr_once(crux_ctx* c, size_t bytes) {
+  static bool done[16] = {};
+  if (!done[c->device & 15]) { HIPCHK(c, hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); done[c->device & 15] = true; }
+  return CRUX_OK;
+}
+// scratch carve-up: one crux_scratch block per call, every piece on a 256-byte boundary (span: the bytes a piece of n elements takes)
+struct Carve {
+  char* p; size_t off;
+  template <class T> static size_t span(size_t n) { return ((n * sizeof(T) + 255) / 256) * 256; }
+  template <class T> T* take(size_t n) { T* r = (T*)(p + off); off += span<T>(n); return r; }
+};
+
 // Device-side description of a Chain(Dense...) with the Flux.params flat layout.
 struct NetDesc {
   int32_t L;

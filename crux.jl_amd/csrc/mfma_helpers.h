@@ -11,6 +11,42 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum { MFK_CATEGORICAL = 0, MFK_GAUSSIAN = 1, MFK_VALUE = 2 };
 
+// ---- host side: what the register-resident dispatchers (train_mfma*.hip, train_fs2.hip) share ----
+// The IN -> 64 -> 64 -> OUT family with an identity output layer. fs2 = k_train_fs2's wider test: a 32-wide second layer and a second activation of its own
+// are allowed too (the one- and two-CU forms take one activation for both hidden layers).
+static inline bool mf_family(const NetDesc& nd, bool fs2) {
+  if (nd.L != 3 || nd.dims[1] != MF_HID || nd.acts[2] != CRUX_ACT_IDENTITY) return false;
+  return fs2 ? (nd.dims[2] == 64 || nd.dims[2] == 32) : (nd.dims[2] == MF_HID && nd.acts[0] == nd.acts[1]);
+}
+// (loss, head) -> MFK_*, -1 = no kernel head for it. Which losses a dispatcher accepts is its own filter.
+static inline int mf_kind(int loss, int head) {
+  if (loss == CRUX_LOSS_VALUE_MSE) return MFK_VALUE;
+  return head == CRUX_HEAD_CATEGORICAL ? MFK_CATEGORICAL : head == CRUX_HEAD_GAUSSIAN ? MFK_GAUSSIAN : -1;
+}
+// CRUX_MFMA_TIMING=1 (development): the timing instantiations write per-wave s_memtime totals of 16 phases into TrainArgs.dbg, row r at dbg[16 r].
+#define MF_TIMING_WORDS 512
+// The buffer: one per device (and dispatcher), allocated on first use; NULL = no memory.
+static inline unsigned long long* mf_timing_buf(crux_ctx* c) {
+  static unsigned long long* buf[16] = {};
+  unsigned long long*& b = buf[c->device & 15];
+  if (!b && hipMalloc(&b, MF_TIMING_WORDS * sizeof(unsigned long long)) != hipSuccess) b = nullptr;
+  return b;
+}
+struct MfTimingRow { int row; const char* const* names; char label[96]; };      // names[16]: a phase named "-" is not printed
+// reads the buffer back (synchronising `stream`) and prints each row as "<label> <phase>=<share of the row's total>% ... total=<ticks>"
+static inline int32_t mf_timing_dump(crux_ctx* c, hipStream_t stream, const MfTimingRow* rows, int n) {
+  unsigned long long h[MF_TIMING_WORDS];
+  HIPCHK(c, hipMemcpyAsync(h, mf_timing_buf(c), sizeof h, hipMemcpyDeviceToHost, stream)); HIPCHK(c, hipStreamSynchronize(stream));
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long* t = h + 16 * rows[i].row; unsigned long long tot = 0;
+    for (int k = 0; k < 16; ++k) tot += t[k];
+    fprintf(stderr, "%s", rows[i].label);
+    for (int k = 0; k < 16; ++k) if (rows[i].names[k][0] != '-') fprintf(stderr, " %s=%.1f%%", rows[i].names[k], 100.0 * (double)t[k] / (double)tot);
+    fprintf(stderr, " total=%llu\n", tot);
+  }
+  return CRUX_OK;
+}
+
 __device__ __forceinline__ void wave_sync() {   // order LDS traffic between the lanes of ONE wave (LDS is in-order per wave)
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();

@@ -358,8 +358,6 @@ static int32_t adam_gated(crux_mlp* n, const double* d_ssq, int32_t* d_status, b
   return crux_launch_check(c, "k_adam_gated");
 }
 
-// scratch carve-up: one crux_scratch block per call
-struct Carve { char* p; size_t off; template <class T> T* take(size_t n) { T* r = (T*)(p + off); off += ((n * sizeof(T) + 255) / 256) * 256; return r; } };
 static inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 // info row / statistics / status words of one step: in a recorded (fused) sequence they must survive until the read-back at the end of the launch, so they
 // come from the executor's own region instead of the scratch block the next piece will carve again

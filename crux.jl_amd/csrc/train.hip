@@ -35,12 +35,30 @@ extern "C" const char* crux_peer_why_text(int why);      // comm.hip
 extern "C" int32_t crux_peer_abort_reason(crux_ctx* c, int32_t* out2);
 // status[4] of a learner launch that ended with CRUX_EHIP: 1 a workgroup of the learner is missing, 2 workgroups on different XCDs, 4 a workgroup missed the abort-latch
 // consensus, 16 + b: the replica group ended the launch, b = the bound of peer_wait.h that fired
-static int32_t learner_stopped(crux_ctx* c, int why) {
+static int32_t learner_stopped(crux_ctx* c, int why, const char* sfx) {
   if (why >= 16 || why == 3) { int32_t ab[2] = {0, 0}; if (crux_grouped(c)) (void)crux_peer_abort_reason(c, ab); const int who = ab[0] ? ab[0] : ab[1];
-    return crux_fail(c, CRUX_EHIP, "learner kernel stopped, replica group: %s%s%s. The group is ended: detach and attach again", crux_peer_why_text(why >= 16 ? why - 16 : 0),
+    return crux_fail(c, CRUX_EHIP, "learner kernel stopped%s, replica group: %s%s%s. The group is ended: detach and attach again", sfx, crux_peer_why_text(why >= 16 ? why - 16 : 0),
                      (why - 16 == 3 && who) ? " -- " : "", (why - 16 == 3 && who) ? crux_peer_why_text(who) : ""); }
-  return crux_fail(c, CRUX_EHIP, "learner kernel stopped: %s", why == 2 ? "its workgroups were placed on different XCDs (concurrent dispatches interleaved them)" :
+  return crux_fail(c, CRUX_EHIP, "learner kernel stopped%s: %s", sfx, why == 2 ? "its workgroups were placed on different XCDs (concurrent dispatches interleaved them)" :
                    why == 4 ? "a workgroup never arrived at the abort-latch consensus of a speculatively started learner" : "one of its workgroups never arrived at the exchange (or the replica group's abort word was raised)");
+}
+// the status row of a learner launch (st2: the critic's row of an actor || critic pair as well) -> return code and message; `who` names the learner in the
+// message of any other status, `sfx` ends every message (" in replica 3")
+static int32_t learner_status(crux_ctx* c, const int32_t* st, const int32_t* st2 = nullptr, const char* who = "learner kernel", const char* sfx = "") {
+  const int32_t e1 = st[0], e2 = st2 ? st2[0] : 0;
+  if (e1 == CRUX_ENAN || e2 == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)%s", sfx);
+  if (e1 == CRUX_EHIP || e2 == CRUX_EHIP) return learner_stopped(c, e1 == CRUX_EHIP ? st[4] : st2[4], sfx);
+  if (!e1 && !e2) return CRUX_OK;
+  if (!st2) return crux_fail(c, e1, "%s reported status %d%s", who, e1, sfx);
+  return crux_fail(c, e1 ? e1 : e2, "%s reported status %d/%d%s", who, e1, e2, sfx);
+}
+// aggregate_info(infos) (training.jl:54) over the epochs run: the mean of the per-epoch info rows `ei`, then batches trained and epochs run; epoch_infos gets the rows
+static void reduce_infos(int batches, int epochs, const float* ei, float* info_out, float* epoch_infos) {
+  if (info_out) {
+    for (int q = 0; q < CRUX_INFO_N; ++q) { double s = 0; for (int e = 0; e < epochs; ++e) s += (double)ei[(size_t)e * CRUX_INFO_N + q]; info_out[q] = epochs ? (float)(s / (double)epochs) : 0.f; }
+    info_out[CRUX_INFO_BATCHES_TRAINED] = (float)batches; info_out[CRUX_INFO_EPOCHS_RUN] = (float)epochs;
+  }
+  if (epoch_infos) memcpy(epoch_infos, ei, sizeof(float) * CRUX_INFO_N * (size_t)epochs);
 }
 static int32_t fill_args(TrainArgs& a, crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, int internal_loss) {
   crux_ctx* c = net->ctx;
@@ -174,8 +192,9 @@ static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_
   if (!stream) stream = c->stream;
   const bool prof = stream == c->stream;      // HIP-event timing is kept on the context's main stream
   if (prof) crux_prof_begin(c, prof_slot);
-  // a replica group is attached (comm.hip "peer"): the per-minibatch gradient all-reduce lives in the two-CU kernels only; a learner that would
-  // update its parameters through any other kernel is refused rather than trained un-synchronised (gradient-only / single-step calls stay local)
+  // a replica group is attached (comm.hip "peer"): the per-minibatch gradient all-reduce lives in k_train_fs2's replica-group forms and in the dense-engine learner
+  // (train_dense.hip); a learner that would update its parameters through any other kernel is refused rather than trained un-synchronised (gradient-only /
+  // single-step calls stay local)
   a.need_px = (crux_grouped(c) && a.apply && !a.ids) ? 1 : 0;
   a.px_timeout = c->peer_timeout_ticks;
   a.px_every = 1;
@@ -221,7 +240,7 @@ static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_
 static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_epochs, float* info_out, float* epoch_infos, bool permute_after) {
   crux_ctx* c = net->ctx;
   const size_t eb = sizeof(float) * CRUX_INFO_N * (size_t)(n_epochs > 0 ? n_epochs : 1);
-  char* sc = (char*)crux_scratch(c, eb + 256 + (a.perms ? 0 : 0));
+  char* sc = (char*)crux_scratch(c, eb + 256);
   if (!sc) return crux_fail(c, CRUX_ENOMEM, "train!: scratch");
   a.status = (int32_t*)sc; a.epoch_infos = (float*)(sc + 256);
   HIPCHK(c, hipMemsetAsync(sc, 0, eb + 256, c->stream));
@@ -241,16 +260,9 @@ static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_ep
     const int32_t* fin = a.ord_all ? a.ord_all + (size_t)(st[2] - 1) * (size_t)a.len : (st[3] ? buf->order_b : buf->order_a);
     rc = crux_buffer_apply_order(buf, fin, buf->elements); if (rc) return rc;
   }
-  if (info_out) {
-    for (int q = 0; q < CRUX_INFO_N; ++q) { double s = 0; for (int e = 0; e < st[2]; ++e) s += (double)ei[(size_t)e * CRUX_INFO_N + q]; info_out[q] = st[2] ? (float)(s / (double)st[2]) : 0.f; }
-    info_out[CRUX_INFO_BATCHES_TRAINED] = (float)st[1]; info_out[CRUX_INFO_EPOCHS_RUN] = (float)st[2];
-    if (st[0] == CRUX_ENAN && st[2] == 0) for (int q = 0; q < 2; ++q) info_out[q] = NAN;
-  }
-  if (epoch_infos) memcpy(epoch_infos, ei.data(), sizeof(float) * CRUX_INFO_N * (size_t)st[2]);
-  if (st[0] == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)");
-  if (st[0] == CRUX_EHIP) return learner_stopped(c, st[4]);
-  if (st[0]) return crux_fail(c, st[0], "learner kernel reported status %d", st[0]);
-  return CRUX_OK;
+  reduce_infos(st[1], st[2], ei.data(), info_out, epoch_infos);
+  if (info_out && st[0] == CRUX_ENAN && st[2] == 0) for (int q = 0; q < 2; ++q) info_out[q] = NAN;      // the first epoch failed: no loss / grad norm to report
+  return learner_status(c, st);
 }
 
 static int32_t upload_ids(crux_ctx* c, crux_buffer* buf, const int64_t* ids, int64_t n, int32_t** d_ids) {
@@ -264,6 +276,37 @@ static int32_t upload_ids(crux_ctx* c, crux_buffer* buf, const int64_t* ids, int
 }
 
 
+// perms (the caller's explicit shuffle!(D) of every epoch, epochs x len host indices): range check, then the upload on the main stream into *dst -- scratch the caller
+// carved, or (*dst == NULL) a temporary allocation the caller frees after the launch
+static int32_t upload_perms(crux_ctx* c, const int64_t* perms, int epochs, int64_t len, int64_t** dst, const char* what) {
+  const size_t bytes = 8 * (size_t)epochs * (size_t)len;
+  for (int64_t i = 0; i < (int64_t)epochs * len; ++i) if (perms[i] < 0 || perms[i] >= len) return crux_fail(c, CRUX_EINVAL, "%s[%lld] out of range", what, (long long)i);
+  if (*dst) { HIPCHK(c, hipMemcpyAsync(*dst, perms, bytes, hipMemcpyHostToDevice, c->stream)); return CRUX_OK; }
+  if (hipMalloc(dst, bytes) != hipSuccess) { *dst = nullptr; return crux_fail(c, CRUX_ENOMEM, "batch_train!: perms"); }
+  if (hipMemcpyAsync(*dst, perms, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipFree(*dst); *dst = nullptr; return crux_fail(c, CRUX_EHIP, "batch_train!: perms upload"); }
+  return CRUX_OK;
+}
+
+// batch_train!(net, opt, loss, D) (training.jl:28-55); lag != NULL: lagrange_ppo_loss (rl/ppo.jl:70-131,208), ppo_loss's learner with the PID state riding in the kernel,
+// copied in before the launch and back after it
+static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) {
+  crux_ctx* c = net->ctx;
+  TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, lag ? CRUX_LOSS_PPO : cfg->loss); if (rc) return rc;
+  if (lag) {
+    if (!c->lag_dev) { if (hipMalloc(&c->lag_dev, 256) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "lagrange state"); }
+    HIPCHK(c, hipMemcpyAsync(c->lag_dev, lag, sizeof *lag, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // `lag` is caller memory
+    a.lag = (crux_lagrange*)c->lag_dev; a.COST = (const float*)buf->col[CRUX_COL_COST]; a.CADV = (const float*)buf->col[CRUX_COL_COST_ADVANTAGE]; a.EE = (const uint8_t*)buf->col[CRUX_COL_EPISODE_END];
+  }
+  int64_t* d_perms = nullptr;
+  if (perms) { rc = upload_perms(c, perms, cfg->epochs, buf->elements, &d_perms, "batch_train!: perms"); if (rc) return rc; a.perms = d_perms; }
+  rc = run_batch(net, buf, a, cfg->epochs, info_out, epoch_infos, true);
+  if (lag) (void)hipMemcpyAsync(lag, c->lag_dev, sizeof *lag, hipMemcpyDeviceToHost, c->stream);     // the state advanced by the minibatches that ran (also after CRUX_ENAN, like the reference's P)
+  if (lag || d_perms) (void)hipStreamSynchronize(c->stream);
+  if (d_perms) (void)hipFree(d_perms);
+  return rc;
+}
+
 extern "C" {
 
 int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) {
@@ -271,22 +314,9 @@ int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
   crux_ctx* c = net->ctx;
   if (buf->elements <= 0) return crux_fail(c, CRUX_EINVAL, "batch_train!: empty buffer");
   if (cfg->epochs < 1) return crux_fail(c, CRUX_EINVAL, "batch_train!: epochs %d", cfg->epochs);
-  TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, cfg->loss); if (rc) return rc;
-  int64_t* d_perms = nullptr;
-  if (perms) {
-    const int64_t len = buf->elements;
-    for (int64_t i = 0; i < (int64_t)cfg->epochs * len; ++i) if (perms[i] < 0 || perms[i] >= len) return crux_fail(c, CRUX_EINVAL, "batch_train!: perms[%lld] out of range", (long long)i);
-    if (hipMalloc(&d_perms, 8 * (size_t)cfg->epochs * (size_t)len) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "batch_train!: perms");
-    hipError_t e = hipMemcpyAsync(d_perms, perms, 8 * (size_t)cfg->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { (void)hipFree(d_perms); return crux_fail(c, CRUX_EHIP, "batch_train!: perms upload"); }
-    a.perms = d_perms;
-  }
-  rc = run_batch(net, buf, a, cfg->epochs, info_out, epoch_infos, true);
-  if (d_perms) { (void)hipStreamSynchronize(c->stream); (void)hipFree(d_perms); }
-  return rc;
+  return batch_train_impl(net, buf, cfg, nullptr, perms, info_out, epoch_infos);
 }
 
-// batch_train!(actor, a_opt, P, D) with lagrange_ppo_loss (rl/ppo.jl:70-131,208): ppo_loss's learner with the PID state riding in the kernel
 int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) {
   if (!net || !buf || !cfg || !lag) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
@@ -294,24 +324,7 @@ int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_tr
   if (buf->elements <= 0 || cfg->epochs < 1) return crux_fail(c, CRUX_EINVAL, "batch_train! (lagrange): empty buffer or epochs %d", cfg->epochs);
   if (!has_col(buf, CRUX_COL_COST) || !has_col(buf, CRUX_COL_COST_ADVANTAGE)) return crux_fail(c, CRUX_EINVAL, "lagrange_ppo_loss: buffer needs :cost and :cost_advantage columns (ppo.jl:211)");
   // (a replica group attached: the launch falls through to the dense-engine learner, whose controller step exchanges the cost sums -- train_dense.hip: k_lagrange_pid)
-  TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, CRUX_LOSS_PPO); if (rc) return rc;
-  if (!c->lag_dev) { if (hipMalloc(&c->lag_dev, 256) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "lagrange state"); }
-  HIPCHK(c, hipMemcpyAsync(c->lag_dev, lag, sizeof *lag, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));         // `lag` is caller memory
-  a.lag = (crux_lagrange*)c->lag_dev; a.COST = (const float*)buf->col[CRUX_COL_COST]; a.CADV = (const float*)buf->col[CRUX_COL_COST_ADVANTAGE]; a.EE = (const uint8_t*)buf->col[CRUX_COL_EPISODE_END];
-  int64_t* d_perms = nullptr;
-  if (perms) {
-    const int64_t len = buf->elements;
-    for (int64_t i = 0; i < (int64_t)cfg->epochs * len; ++i) if (perms[i] < 0 || perms[i] >= len) return crux_fail(c, CRUX_EINVAL, "batch_train!: perms[%lld] out of range", (long long)i);
-    if (hipMalloc(&d_perms, 8 * (size_t)cfg->epochs * (size_t)len) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "batch_train!: perms");
-    if (hipMemcpyAsync(d_perms, perms, 8 * (size_t)cfg->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipFree(d_perms); return crux_fail(c, CRUX_EHIP, "batch_train!: perms upload"); }
-    a.perms = d_perms;
-  }
-  rc = run_batch(net, buf, a, cfg->epochs, info_out, epoch_infos, true);
-  (void)hipMemcpyAsync(lag, c->lag_dev, sizeof *lag, hipMemcpyDeviceToHost, c->stream);     // the state advanced by the minibatches that ran (also after CRUX_ENAN, like the reference's P)
-  (void)hipStreamSynchronize(c->stream);
-  if (d_perms) (void)hipFree(d_perms);
-  return rc;
+  return batch_train_impl(net, buf, cfg, lag, perms, info_out, epoch_infos);
 }
 
 static int32_t step_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out, int apply) {
@@ -465,13 +478,51 @@ static int32_t collect(crux_ctx* c, const TrainArgs& a, int n_epochs, float* inf
   HIPCHK(c, hipMemcpyAsync(st, a.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(ei.data(), a.epoch_infos, eb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (info_out) {
-    for (int q = 0; q < CRUX_INFO_N; ++q) { double s = 0; for (int e = 0; e < st[2]; ++e) s += (double)ei[(size_t)e * CRUX_INFO_N + q]; info_out[q] = st[2] ? (float)(s / (double)st[2]) : 0.f; }
-    info_out[CRUX_INFO_BATCHES_TRAINED] = (float)st[1]; info_out[CRUX_INFO_EPOCHS_RUN] = (float)st[2];
-  }
-  if (epoch_infos) memcpy(epoch_infos, ei.data(), sizeof(float) * CRUX_INFO_N * (size_t)st[2]);
+  reduce_infos(st[1], st[2], ei.data(), info_out, epoch_infos);      // (no NaN fill for a first epoch that failed, unlike run_batch)
   memcpy(st_out, st, sizeof st);
   return CRUX_OK;
+}
+// the second learner stream starts after everything queued on the main stream so far
+static int32_t aux_after_main(crux_ctx* c) {
+  HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
+  return CRUX_OK;
+}
+// the device rows of an actor || critic pair in one scratch block: both status rows and epoch infos (zeroed), the uploaded perms (a.perms, k.perms), then
+// `extra` bytes for the caller at *extra_out
+static int32_t pair_scratch(crux_ctx* c, int64_t len, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c, const int64_t* perms_a, const int64_t* perms_c,
+                            TrainArgs& a, TrainArgs& k, size_t extra, char** extra_out) {
+  const size_t na = (size_t)CRUX_INFO_N * (size_t)cfg_a->epochs, nc = (size_t)CRUX_INFO_N * (size_t)cfg_c->epochs;
+  const size_t npa = perms_a ? (size_t)cfg_a->epochs * (size_t)len : 0, npc = perms_c ? (size_t)cfg_c->epochs * (size_t)len : 0;
+  const size_t rows = 2 * Carve::span<int32_t>(64) + Carve::span<float>(na) + Carve::span<float>(nc);
+  Carve cv{(char*)crux_scratch(c, rows + Carve::span<int64_t>(npa) + Carve::span<int64_t>(npc) + extra + 256), 0};
+  if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training: scratch");
+  a.status = cv.take<int32_t>(64); k.status = cv.take<int32_t>(64); a.epoch_infos = cv.take<float>(na); k.epoch_infos = cv.take<float>(nc);
+  HIPCHK(c, hipMemsetAsync(cv.p, 0, rows, c->stream));
+  int64_t* d_pa = perms_a ? cv.take<int64_t>(npa) : nullptr; int64_t* d_pc = perms_c ? cv.take<int64_t>(npc) : nullptr;
+  if (perms_a) { const int32_t rc = upload_perms(c, perms_a, cfg_a->epochs, len, &d_pa, "perms_a"); if (rc) return rc; }
+  if (perms_c) { const int32_t rc = upload_perms(c, perms_c, cfg_c->epochs, len, &d_pc, "perms_c"); if (rc) return rc; }
+  a.perms = d_pa; k.perms = d_pc;
+  if (extra_out) *extra_out = cv.p + cv.off;
+  return CRUX_OK;
+}
+// the epoch orders of both learners ahead of the launches: the critic's chain starts from the actor's last order (the reference shuffles the one buffer on through both
+// batch_train! calls)
+static int32_t pair_orders(crux_ctx* c, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c, TrainArgs& a, TrainArgs& k) {
+  int32_t* oa = nullptr; int32_t* oc = nullptr;
+  int32_t rc = build_orders(c, buf, 0, nullptr, cfg_a->shuffle_seed, cfg_a->shuffle_counter, a.perms, cfg_a->epochs, c->stream, &oa); if (rc) return rc;
+  rc = build_orders(c, buf, 1, oa + (size_t)(cfg_a->epochs - 1) * (size_t)buf->elements, cfg_c->shuffle_seed, cfg_c->shuffle_counter, k.perms, cfg_c->epochs, c->stream, &oc); if (rc) return rc;
+  a.ord_all = oa; k.ord_all = oc;
+  return CRUX_OK;
+}
+// after both learners ran (sta: the actor's status row): the critic's row and infos, both rows -> the return code, then the buffer in the critic's final order -- it already
+// contains the actor's shuffles, so one physical permutation leaves the buffer as the reference would. `who` names the learners in the status message.
+static int32_t pair_tail(crux_ctx* c, crux_buffer* buf, const TrainArgs& k, int epochs_c, float* info_c, float* epoch_infos_c, const int32_t* sta, const char* who) {
+  int32_t stc[8];
+  int32_t rc = collect(c, k, epochs_c, info_c, epoch_infos_c, stc); if (rc) return rc;
+  rc = learner_status(c, sta, stc, who); if (rc) return rc;
+  if (stc[2] < 1) return CRUX_OK;
+  return crux_buffer_apply_order(buf, k.ord_all ? k.ord_all + (size_t)(stc[2] - 1) * (size_t)k.len : (stc[3] ? k.order_b : k.order_a), k.len);
 }
 
 // policy_gradient_training (on_policy.jl:56-78) for two learners of the dense engine: the actor's chain of launches on the main stream from the calling thread, the critic's on the
@@ -488,24 +539,9 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
   if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false) || !crux_train_dense_eligible(k, generic_lds_bytes(k.nd), false)) return CRUX_EUNSUP;
   a.ord_all = nullptr; k.ord_all = nullptr;
   { const int32_t rca = ensure_aux_stream(c); if (rca) return rca; }
-  const size_t ea = sizeof(float) * CRUX_INFO_N * (size_t)cfg_a->epochs, ec = sizeof(float) * CRUX_INFO_N * (size_t)cfg_c->epochs;
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t pa = perms_a ? al(8 * (size_t)cfg_a->epochs * (size_t)len) : 0, pc = perms_c ? al(8 * (size_t)cfg_c->epochs * (size_t)len) : 0;
-  char* sc = (char*)crux_scratch(c, 512 + al(ea) + al(ec) + pa + pc + 256);
-  if (!sc) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training: scratch");
-  a.status = (int32_t*)sc; k.status = (int32_t*)(sc + 256); a.epoch_infos = (float*)(sc + 512); k.epoch_infos = (float*)(sc + 512 + al(ea));
-  HIPCHK(c, hipMemsetAsync(sc, 0, 512 + al(ea) + al(ec), c->stream));
-  int64_t* d_pa = nullptr; int64_t* d_pc = nullptr;
-  if (perms_a) { d_pa = (int64_t*)(sc + 512 + al(ea) + al(ec)); for (int64_t i = 0; i < (int64_t)cfg_a->epochs * len; ++i) if (perms_a[i] < 0 || perms_a[i] >= len) return crux_fail(c, CRUX_EINVAL, "perms_a[%lld] out of range", (long long)i);
-    HIPCHK(c, hipMemcpyAsync(d_pa, perms_a, 8 * (size_t)cfg_a->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream)); }
-  if (perms_c) { d_pc = (int64_t*)(sc + 512 + al(ea) + al(ec) + pa); for (int64_t i = 0; i < (int64_t)cfg_c->epochs * len; ++i) if (perms_c[i] < 0 || perms_c[i] >= len) return crux_fail(c, CRUX_EINVAL, "perms_c[%lld] out of range", (long long)i);
-    HIPCHK(c, hipMemcpyAsync(d_pc, perms_c, 8 * (size_t)cfg_c->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream)); }
-  int32_t* oa = nullptr; int32_t* oc = nullptr;
-  rc = build_orders(c, buf, 0, nullptr, cfg_a->shuffle_seed, cfg_a->shuffle_counter, d_pa, cfg_a->epochs, c->stream, &oa); if (rc) return rc;
-  rc = build_orders(c, buf, 1, oa + (size_t)(cfg_a->epochs - 1) * (size_t)len, cfg_c->shuffle_seed, cfg_c->shuffle_counter, d_pc, cfg_c->epochs, c->stream, &oc); if (rc) return rc;
-  a.ord_all = oa; k.ord_all = oc; a.need_px = 0; k.need_px = 0;
-  HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
+  rc = pair_scratch(c, len, cfg_a, cfg_c, perms_a, perms_c, a, k, 0, nullptr); if (rc) return rc;
+  rc = pair_orders(c, buf, cfg_a, cfg_c, a, k); if (rc) return rc;
+  rc = aux_after_main(c); if (rc) return rc;
   int32_t rck = CRUX_OK; const int dev = c->device;
   std::thread th([&]() { (void)hipSetDevice(dev); rck = crux_train_dense_run(c, k, c->aux_stream, 1); });
   crux_prof_begin(c, CRUX_PROF_TRAIN_ACTOR);
@@ -513,14 +549,9 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
   crux_prof_end(c, CRUX_PROF_TRAIN_ACTOR);
   th.join();
   if (rca) return rca; if (rck) return rck;
-  int32_t sta[8], stc[8];
+  int32_t sta[8];
   rc = collect(c, a, cfg_a->epochs, info_a, epoch_infos_a, sta); if (rc) return rc;
-  rc = collect(c, k, cfg_c->epochs, info_c, epoch_infos_c, stc); if (rc) return rc;
-  if (sta[0] == CRUX_ENAN || stc[0] == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)");
-  if (sta[0] == CRUX_EHIP || stc[0] == CRUX_EHIP) return learner_stopped(c, sta[0] == CRUX_EHIP ? sta[4] : stc[4]);
-  if (sta[0] || stc[0]) return crux_fail(c, sta[0] ? sta[0] : stc[0], "learner reported status %d/%d", sta[0], stc[0]);
-  if (stc[2] < 1) return CRUX_OK;
-  return crux_buffer_apply_order(buf, k.ord_all + (size_t)(stc[2] - 1) * (size_t)len, len);
+  return pair_tail(c, buf, k, cfg_c->epochs, info_c, epoch_infos_c, sta, "learner");
 }
 
 extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
@@ -561,40 +592,23 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
   TrainArgs a, k; int32_t rc = fill_args(a, actor, buf, cfg_a, cfg_a->loss); if (rc) return rc;
   rc = fill_args(k, critic, buf, cfg_c, cfg_c->loss); if (rc) return rc;
   const int64_t len = buf->elements;
-  const size_t ea = sizeof(float) * CRUX_INFO_N * (size_t)cfg_a->epochs, ec = sizeof(float) * CRUX_INFO_N * (size_t)cfg_c->epochs;
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t pa = perms_a ? al(8 * (size_t)cfg_a->epochs * (size_t)len) : 0, pc = perms_c ? al(8 * (size_t)cfg_c->epochs * (size_t)len) : 0;
-  const size_t np_c = (size_t)critic->nd.n_params, snap = spec ? al(3 * 4 * np_c + 64) : 0;      // speculative start: the critic's parameters, Adam moments and beta powers as they are now
-  char* sc = (char*)crux_scratch(c, 512 + al(ea) + al(ec) + pa + pc + snap + 256);
-  if (!sc) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training: scratch");
-  a.status = (int32_t*)sc; k.status = (int32_t*)(sc + 256); a.epoch_infos = (float*)(sc + 512); k.epoch_infos = (float*)(sc + 512 + al(ea));
-  HIPCHK(c, hipMemsetAsync(sc, 0, 512 + al(ea) + al(ec), c->stream));
-  int64_t* d_pa = nullptr; int64_t* d_pc = nullptr;
-  if (perms_a) { d_pa = (int64_t*)(sc + 512 + al(ea) + al(ec)); for (int64_t i = 0; i < (int64_t)cfg_a->epochs * len; ++i) if (perms_a[i] < 0 || perms_a[i] >= len) return crux_fail(c, CRUX_EINVAL, "perms_a[%lld] out of range", (long long)i);
-    HIPCHK(c, hipMemcpyAsync(d_pa, perms_a, 8 * (size_t)cfg_a->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream)); }
-  if (perms_c) { d_pc = (int64_t*)(sc + 512 + al(ea) + al(ec) + pa); for (int64_t i = 0; i < (int64_t)cfg_c->epochs * len; ++i) if (perms_c[i] < 0 || perms_c[i] >= len) return crux_fail(c, CRUX_EINVAL, "perms_c[%lld] out of range", (long long)i);
-    HIPCHK(c, hipMemcpyAsync(d_pc, perms_c, 8 * (size_t)cfg_c->epochs * (size_t)len, hipMemcpyHostToDevice, c->stream)); }
+  const size_t np_c = (size_t)critic->nd.n_params, snap = spec ? Carve::span<char>(3 * 4 * np_c + 64) : 0;      // speculative start: the critic's parameters, Adam moments and beta powers as they are now
+  char* snap_at = nullptr;
+  rc = pair_scratch(c, len, cfg_a, cfg_c, perms_a, perms_c, a, k, snap, &snap_at); if (rc) return rc;
   float* snap_p = nullptr;
   if (spec) {
-    snap_p = (float*)(sc + 512 + al(ea) + al(ec) + pa + pc);
+    snap_p = (float*)snap_at;
     HIPCHK(c, hipMemcpyAsync(snap_p, critic->p, 4 * np_c, hipMemcpyDeviceToDevice, c->stream)); HIPCHK(c, hipMemcpyAsync(snap_p + np_c, critic->m, 4 * np_c, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(snap_p + 2 * np_c, critic->v, 4 * np_c, hipMemcpyDeviceToDevice, c->stream)); HIPCHK(c, hipMemcpyAsync(snap_p + 3 * np_c, critic->bp, 16, hipMemcpyDeviceToDevice, c->stream));
     if (!c->spec_abort) { if (hipHostMalloc((void**)&c->spec_abort, 64, hipHostMallocMapped) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training: pinned abort word"); }
     *(volatile unsigned*)c->spec_abort = 0u;
     void* dptr = nullptr; HIPCHK(c, hipHostGetDevicePointer(&dptr, c->spec_abort, 0)); k.spec_abort = (const unsigned*)dptr;
   }
-  a.perms = d_pa; k.perms = d_pc;
   k.order_a = buf->order_c; k.order_b = buf->order_d;
-  k.pre_epochs = cfg_a->epochs; k.pre_seed = cfg_a->shuffle_seed; k.pre_counter = cfg_a->shuffle_counter; k.pre_perms = d_pa;
-  if (len < ((int64_t)1 << 31)) {   // all epoch orders ahead of time; the critic's chain starts from the actor's last order
-    int32_t* oa = nullptr; int32_t* oc = nullptr;
-    rc = build_orders(c, buf, 0, nullptr, cfg_a->shuffle_seed, cfg_a->shuffle_counter, d_pa, cfg_a->epochs, c->stream, &oa); if (rc) return rc;
-    rc = build_orders(c, buf, 1, oa + (size_t)(cfg_a->epochs - 1) * (size_t)len, cfg_c->shuffle_seed, cfg_c->shuffle_counter, d_pc, cfg_c->epochs, c->stream, &oc); if (rc) return rc;
-    a.ord_all = oa; k.ord_all = oc;
-  }
+  k.pre_epochs = cfg_a->epochs; k.pre_seed = cfg_a->shuffle_seed; k.pre_counter = cfg_a->shuffle_counter; k.pre_perms = a.perms;
+  if (len < ((int64_t)1 << 31)) { rc = pair_orders(c, buf, cfg_a, cfg_c, a, k); if (rc) return rc; }     // all epoch orders ahead of time
   rc = ensure_pack(c, buf, c->stream, a, &k); if (rc) return rc;
-  HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
+  rc = aux_after_main(c); if (rc) return rc;
   rc = launch_train(c, k, CRUX_PROF_TRAIN_CRITIC, c->aux_stream); if (rc) return rc;
   // From here on the critic's kernel runs on aux_stream and reads status / snapshot blocks of the shared scratch: EVERY exit before it has been waited for goes through
   // unwind() -- a speculative critic is told to leave (abort word), the stream is drained, and the critic's parameters / Adam state are put back as they were.
@@ -613,7 +627,7 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
 #define PGT_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (void)hipGetLastError(); return unwind(crux_fail(c, CRUX_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__)); } } while (0)
   PGT_HIP(hipEventRecord(c->aux_ev1, c->aux_stream));
   rc = launch_train(c, a, CRUX_PROF_TRAIN_ACTOR); if (rc) return unwind(rc);
-  int32_t sta[8], stc[8];
+  int32_t sta[8];
   if (spec) {
     rc = collect(c, a, cfg_a->epochs, info_a, epoch_infos_a, sta);      // waits for the ACTOR only
     const bool wrong = !rc && sta[0] == 0 && sta[2] < cfg_a->epochs;      // the actor stopped after sta[2] epochs: the critic was started on the order of cfg_a->epochs shuffles
@@ -622,13 +636,11 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
       if (!restore_critic()) { (void)hipGetLastError(); return unwind(crux_fail(c, CRUX_EHIP, "policy_gradient_training: restoring the critic's snapshot failed")); } }
     if (rc || sta[0]) PGT_HIP(hipStreamSynchronize(c->stream));
     if (rc) return unwind(rc);
-    if (sta[0] == CRUX_ENAN) return unwind(crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)"));
-    if (sta[0] == CRUX_EHIP) return unwind(learner_stopped(c, sta[4]));
-    if (sta[0]) return unwind(crux_fail(c, sta[0], "learner kernel reported status %d", sta[0]));
+    if (sta[0]) return unwind(learner_status(c, sta));
     if (wrong) {
-      PGT_HIP(hipMemsetAsync(k.status, 0, 256, c->stream)); PGT_HIP(hipMemsetAsync(k.epoch_infos, 0, ec, c->stream));
+      PGT_HIP(hipMemsetAsync(k.status, 0, 256, c->stream)); PGT_HIP(hipMemsetAsync(k.epoch_infos, 0, sizeof(float) * CRUX_INFO_N * (size_t)cfg_c->epochs, c->stream));
       int32_t* oc = nullptr;
-      rc = build_orders(c, buf, 1, sta[2] >= 1 ? a.ord_all + (size_t)(sta[2] - 1) * (size_t)len : nullptr, cfg_c->shuffle_seed, cfg_c->shuffle_counter, d_pc, cfg_c->epochs, c->stream, &oc); if (rc) return unwind(rc);
+      rc = build_orders(c, buf, 1, sta[2] >= 1 ? a.ord_all + (size_t)(sta[2] - 1) * (size_t)len : nullptr, cfg_c->shuffle_seed, cfg_c->shuffle_counter, k.perms, cfg_c->epochs, c->stream, &oc); if (rc) return unwind(rc);
       k.ord_all = oc; k.spec_abort = nullptr; k.pre_epochs = sta[2];
       rc = launch_train(c, k, CRUX_PROF_TRAIN_CRITIC); if (rc) return unwind(rc);
     } else PGT_HIP(hipStreamWaitEvent(c->stream, c->aux_ev1, 0));
@@ -638,13 +650,7 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
   }
   critic_in_flight = false;      // (the main stream now waits for the critic: collect() below synchronises it)
 #undef PGT_HIP
-  rc = collect(c, k, cfg_c->epochs, info_c, epoch_infos_c, stc); if (rc) return rc;
-  if (sta[0] == CRUX_ENAN || stc[0] == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)");
-  if (sta[0] == CRUX_EHIP || stc[0] == CRUX_EHIP) return learner_stopped(c, sta[0] == CRUX_EHIP ? sta[4] : stc[4]);
-  if (sta[0] || stc[0]) return crux_fail(c, sta[0] ? sta[0] : stc[0], "learner kernel reported status %d/%d", sta[0], stc[0]);
-  // the critic's final order already contains the actor's shuffles: one physical permutation leaves the buffer as the reference would
-  if (stc[2] < 1) return CRUX_OK;
-  return crux_buffer_apply_order(buf, k.ord_all ? k.ord_all + (size_t)(stc[2] - 1) * (size_t)len : (stc[3] ? buf->order_d : buf->order_c), len);
+  return pair_tail(c, buf, k, cfg_c->epochs, info_c, epoch_infos_c, sta, "learner kernel");
 }
 
 // policy_gradient_training for n independent (actor, critic, buffer) triples in TWO launches (all actors, all critics): multi-seed / population
@@ -656,20 +662,20 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: early stopping / max_batches need the sequential single-learner call");
   if (cfg_a->epochs < 1 || cfg_c->epochs < 1) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_multi: epochs < 1");
   { const int32_t rca = ensure_aux_stream(c); if (rca) return rca; }
-  const size_t ea = sizeof(float) * CRUX_INFO_N * (size_t)cfg_a->epochs, ec = sizeof(float) * CRUX_INFO_N * (size_t)cfg_c->epochs;
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t stride = 512 + al(ea) + al(ec);
+  // per replica: the actor's and the critic's status row and epoch infos
+  const size_t na = (size_t)CRUX_INFO_N * (size_t)cfg_a->epochs, nc = (size_t)CRUX_INFO_N * (size_t)cfg_c->epochs;
+  const size_t stride = 2 * Carve::span<int32_t>(64) + Carve::span<float>(na) + Carve::span<float>(nc);
   char* sc = (char*)crux_scratch(c, stride * (size_t)n + 256); if (!sc) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training_multi: scratch");
   HIPCHK(c, hipMemsetAsync(sc, 0, stride * (size_t)n, c->stream));
-  std::vector<TrainArgs> as((size_t)n), ks((size_t)n);
+  std::vector<TrainArgs> as((size_t)n), ks((size_t)n); int32_t rc;
   for (int i = 0; i < n; ++i) {
     if (!actors[i] || !critics[i] || !bufs[i] || bufs[i]->elements <= 0) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_multi: replica %d is incomplete", i);
     crux_train_cfg ca = *cfg_a, cc = *cfg_c; ca.shuffle_seed += (uint64_t)i; cc.shuffle_seed += (uint64_t)i;     // every replica shuffles with its own stream
-    int32_t rc = fill_args(as[i], actors[i], bufs[i], &ca, ca.loss); if (rc) return rc;
+    rc = fill_args(as[i], actors[i], bufs[i], &ca, ca.loss); if (rc) return rc;
     rc = fill_args(ks[i], critics[i], bufs[i], &cc, cc.loss); if (rc) return rc;
     if (bufs[i]->elements != bufs[0]->elements || as[i].nd.n_params != as[0].nd.n_params || ks[i].nd.n_params != ks[0].nd.n_params) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_multi: replicas must have equal shapes");
-    char* s0 = sc + stride * (size_t)i;
-    as[i].status = (int32_t*)s0; ks[i].status = (int32_t*)(s0 + 256); as[i].epoch_infos = (float*)(s0 + 512); ks[i].epoch_infos = (float*)(s0 + 512 + al(ea));
+    Carve cv{sc + stride * (size_t)i, 0};
+    as[i].status = cv.take<int32_t>(64); ks[i].status = cv.take<int32_t>(64); as[i].epoch_infos = cv.take<float>(na); ks[i].epoch_infos = cv.take<float>(nc);
     ks[i].order_a = bufs[i]->order_c; ks[i].order_b = bufs[i]->order_d;
     // shuffle!(D) per epoch as an index composition INSIDE the learner kernels (every learner composes its own order with its own 512 threads: ~8 us per epoch, all learners at
     // once); the critic first replays the actor's epochs (the reference shuffles the same buffer on through both batch_train! calls). Composed ahead of time -- (Ea + Ec)
@@ -678,8 +684,7 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
     as[i].ord_all = nullptr; ks[i].ord_all = nullptr;
     ks[i].pre_epochs = ca.epochs; ks[i].pre_seed = ca.shuffle_seed; ks[i].pre_counter = ca.shuffle_counter; ks[i].pre_perms = nullptr;
   }
-  HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
+  rc = aux_after_main(c); if (rc) return rc;
   // Two batched forms: two CUs per learner (k_train_mfma<...,4,2>, shortest iteration while 4 n CUs fit the chip) or one CU per learner
   // (k_train_mfma<...,8,1>, 1.1x longer steps but half the CUs: the higher-throughput form once the population exceeds 64 = 256 CUs / 4).
   // more than 64 two-CU learners per launch pair would not be co-resident (2 launches x 2 n workgroups > 256 CUs): a workgroup could then spin on a
@@ -691,7 +696,7 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
     return crux_train_mfma8_launch_multi(c, v, h, st);
   };
   bool handled = false;
-  int32_t rc = launch_many(ks, c->aux_stream, &handled); if (rc) return rc;
+  rc = launch_many(ks, c->aux_stream, &handled); if (rc) return rc;
   if (!handled) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: no batched kernel for this network family / batch size");
   HIPCHK(c, hipEventRecord(c->aux_ev1, c->aux_stream));
   crux_prof_begin(c, CRUX_PROF_TRAIN_ACTOR);
@@ -704,15 +709,12 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
   HIPCHK(c, hipMemcpyAsync(host.data(), sc, host.size(), hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
   std::vector<const int32_t*> fin_ord((size_t)n, nullptr);
   for (int i = 0; i < n; ++i) {
-    const char* s0 = host.data() + stride * (size_t)i;
-    const int32_t* sta = (const int32_t*)s0; const int32_t* stc = (const int32_t*)(s0 + 256);
-    const float* eia = (const float*)(s0 + 512); const float* eic = (const float*)(s0 + 512 + al(ea));
-    for (int w = 0; w < 2; ++w) { const int32_t* st = w ? stc : sta; const float* ei = w ? eic : eia; float* out = w ? info_c : info_a;
-      if (!out) continue; out += (size_t)i * CRUX_INFO_N;
-      for (int q = 0; q < CRUX_INFO_N; ++q) { double sum = 0; for (int e = 0; e < st[2]; ++e) sum += (double)ei[(size_t)e * CRUX_INFO_N + q]; out[q] = st[2] ? (float)(sum / (double)st[2]) : 0.f; }
-      out[CRUX_INFO_BATCHES_TRAINED] = (float)st[1]; out[CRUX_INFO_EPOCHS_RUN] = (float)st[2]; }
-    if (sta[0] == CRUX_ENAN || stc[0] == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in replica %d", i);
-    if (sta[0] || stc[0]) return crux_fail(c, sta[0] ? sta[0] : stc[0], "learner kernel reported status %d/%d in replica %d", sta[0], stc[0], i);
+    Carve hv{host.data() + stride * (size_t)i, 0};      // (the layout above)
+    const int32_t* sta = hv.take<int32_t>(64); const int32_t* stc = hv.take<int32_t>(64); const float* eia = hv.take<float>(na); const float* eic = hv.take<float>(nc);
+    reduce_infos(sta[1], sta[2], eia, info_a ? info_a + (size_t)i * CRUX_INFO_N : nullptr, nullptr);
+    reduce_infos(stc[1], stc[2], eic, info_c ? info_c + (size_t)i * CRUX_INFO_N : nullptr, nullptr);
+    char sfx[32]; snprintf(sfx, sizeof sfx, " in replica %d", i);
+    rc = learner_status(c, sta, stc, "learner kernel", sfx); if (rc) return rc;
     if (stc[2] >= 1) fin_ord[(size_t)i] = stc[3] ? bufs[i]->order_d : bufs[i]->order_c;      // the critic's last epoch order = the buffer's final arrangement
   }
   return crux_buffer_apply_order_multi(n, bufs, fin_ord.data());
@@ -747,23 +749,22 @@ extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_ml
   const int E = cfg_a->epochs, nch = (E + sync_every - 1) / sync_every;
   TrainArgs a, k; int32_t rc = fill_args(a, actor, buf, cfg_a, cfg_a->loss); if (rc) return rc;
   rc = fill_args(k, critic, buf, cfg_c, cfg_c->loss); if (rc) return rc;
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t eb = al(sizeof(float) * CRUX_INFO_N * (size_t)E), stb = 256 * (size_t)nch;
-  char* sc = (char*)crux_scratch(c, 2 * stb + 2 * eb + 256); if (!sc) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training_synced: scratch");
-  HIPCHK(c, hipMemsetAsync(sc, 0, 2 * stb + 2 * eb, c->stream));
-  char* sta_d = sc; char* stc_d = sc + stb; float* eia = (float*)(sc + 2 * stb); float* eic = (float*)(sc + 2 * stb + eb);
-  int32_t* oa = nullptr; int32_t* oc = nullptr;
-  rc = build_orders(c, buf, 0, nullptr, cfg_a->shuffle_seed, cfg_a->shuffle_counter, nullptr, E, c->stream, &oa); if (rc) return rc;
-  rc = build_orders(c, buf, 1, oa + (size_t)(E - 1) * (size_t)len, cfg_c->shuffle_seed, cfg_c->shuffle_counter, nullptr, E, c->stream, &oc); if (rc) return rc;
+  // one status row per chunk and learner, the epoch infos of both learners
+  const size_t stb = Carve::span<int32_t>(64 * (size_t)nch), eb = Carve::span<float>((size_t)CRUX_INFO_N * (size_t)E);
+  Carve cv{(char*)crux_scratch(c, 2 * stb + 2 * eb + 256), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "policy_gradient_training_synced: scratch");
+  HIPCHK(c, hipMemsetAsync(cv.p, 0, 2 * stb + 2 * eb, c->stream));
+  int32_t* sta_d = cv.take<int32_t>(64 * (size_t)nch); int32_t* stc_d = cv.take<int32_t>(64 * (size_t)nch);
+  float* eia = cv.take<float>((size_t)CRUX_INFO_N * (size_t)E); float* eic = cv.take<float>((size_t)CRUX_INFO_N * (size_t)E);
+  rc = pair_orders(c, buf, cfg_a, cfg_c, a, k); if (rc) return rc;      // (no perms: a.perms = k.perms = NULL)
+  const int32_t* oa = a.ord_all; const int32_t* oc = k.ord_all;
   k.order_a = buf->order_c; k.order_b = buf->order_d;
   crux_mlp* nets[2] = {actor, critic};
   for (int ch = 0; ch < nch; ++ch) {
     const int e0 = ch * sync_every, ne = (E - e0 < sync_every) ? E - e0 : sync_every;
     a.epochs = ne; k.epochs = ne; a.ord_all = oa + (size_t)e0 * (size_t)len; k.ord_all = oc + (size_t)e0 * (size_t)len;
-    a.status = (int32_t*)(sta_d + 256 * (size_t)ch); k.status = (int32_t*)(stc_d + 256 * (size_t)ch);
+    a.status = sta_d + 64 * (size_t)ch; k.status = stc_d + 64 * (size_t)ch;
     a.epoch_infos = eia + (size_t)e0 * CRUX_INFO_N; k.epoch_infos = eic + (size_t)e0 * CRUX_INFO_N;
-    HIPCHK(c, hipEventRecord(c->aux_ev0, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_ev0, 0));
+    rc = aux_after_main(c); if (rc) return rc;
     rc = launch_train(c, k, CRUX_PROF_TRAIN_CRITIC, c->aux_stream); if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->aux_ev1, c->aux_stream));
     rc = launch_train(c, a, CRUX_PROF_TRAIN_ACTOR); if (rc) return rc;
@@ -771,19 +772,17 @@ extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_ml
     rc = crux_comm_allreduce_mean_impl(c, nets, 2); if (rc) return rc;
   }
   std::vector<int32_t> hs((size_t)nch * 128); std::vector<float> hi(2 * (size_t)E * CRUX_INFO_N);
-  HIPCHK(c, hipMemcpyAsync(hs.data(), sc, 2 * stb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hs.data(), sta_d, 2 * stb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(hi.data(), eia, sizeof(float) * CRUX_INFO_N * (size_t)E, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(hi.data() + (size_t)E * CRUX_INFO_N, eic, sizeof(float) * CRUX_INFO_N * (size_t)E, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int w = 0; w < 2; ++w) {
     int bt = 0, er = 0;
     for (int ch = 0; ch < nch; ++ch) { const int32_t* st = hs.data() + (size_t)w * (stb / 4) + 64 * (size_t)ch;
-      if (st[0] == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20)");
-      if (st[0]) return crux_fail(c, st[0], "learner kernel reported status %d in chunk %d", st[0], ch);
+      char sfx[32]; snprintf(sfx, sizeof sfx, " in chunk %d", ch);
+      rc = learner_status(c, st, nullptr, "learner kernel", st[0] == CRUX_ENAN ? "" : sfx); if (rc) return rc;      // (the NaN message names no chunk)
       bt += st[1]; er += st[2]; }
-    float* out = w ? info_c : info_a; const float* ei = hi.data() + (size_t)w * (size_t)E * CRUX_INFO_N;
-    if (out) { for (int q = 0; q < CRUX_INFO_N; ++q) { double s = 0; for (int e = 0; e < er; ++e) s += (double)ei[(size_t)e * CRUX_INFO_N + q]; out[q] = er ? (float)(s / (double)er) : 0.f; }
-      out[CRUX_INFO_BATCHES_TRAINED] = (float)bt; out[CRUX_INFO_EPOCHS_RUN] = (float)er; }
+    reduce_infos(bt, er, hi.data() + (size_t)w * (size_t)E * CRUX_INFO_N, w ? info_c : info_a, nullptr);
   }
   return crux_buffer_apply_order(buf, oc + (size_t)(E - 1) * (size_t)len, len);
 }

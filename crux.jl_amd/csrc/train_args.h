@@ -33,7 +33,7 @@ struct TrainArgs {
   float* xbuf; unsigned* xctr;   // two-CU kernel (train_mfma_x2.hip): gradient exchange slots [parity][workgroup] and {arrival counter, abort flag}
   // replica group (comm.hip "peer"): SUM all-reduce of the minibatch gradient over px_n GPUs inside the persistent kernel, between the pullback
   // (training.jl:18) and Flux.update! (:21). px_tab[r] = rank r's slot region for THIS learner stream as mapped in this process.
-  int32_t need_px;           // host-side: a replica group is attached and this launch updates parameters -> only the two-CU kernel may take it
+  int32_t need_px;           // host-side: a replica group is attached and this launch updates parameters -> only a learner with the exchange may take it
   int32_t xcd;               // feature-split kernel: the XCD (blockIdx mod 8) whose compute units this learner takes -- actor and critic (and same-device replicas) sit behind different L2s
   int32_t px_hist;           // 1: lane 0 of each workgroup bins its flag wait of every exchange into the own region's histogram (CRUX_PX_HIST)
   int32_t px_every;          // <= 1: the gradient is exchanged every minibatch; k > 1: local Adam steps, theta / m / v are averaged after every k-th (crux_peer_set_sync_every)

@@ -1,15 +1,14 @@
 // train_fs2.hip -- dispatch of the feature-split, role-specialised learner kernel (train_fs2_kernel.h: k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>): full
 // batch_train! loops (src/training.jl:28-55) of the IN->64->{64,32}->OUT family with minibatches of 65..128 rows, on four compute units of one XCD with four compute + four
 // helper waves each -- the plain policy-gradient / critic losses, lagrange_ppo_loss (LAG) and the replica-group forms (PX / PXK) of every shape in the list below.
-// CRUX_FS=0 switches the kernel off (the sample-split two-CU kernel, or the dense engine for the 32-wide second layer, then run).
+// CRUX_FS=0 switches the kernel off (the sample-split two-CU kernel, or the dense engine for the 32-wide second layer and for replica groups, then run).
 #include "train_fs2_kernel.h"
 
 template <int IN, int OUT, int KIND, int ACT, int H2, int ACT2, bool TIMING, bool PX = false, bool PXK = false, bool LAG = false>
 static int32_t launch_fs2_form(crux_ctx* c, TrainArgs& a, hipStream_t stream) {
   using Lt = Fs2Layout<IN, OUT, H2, LAG>;
   constexpr size_t lds = sizeof(float) * (size_t)(PX && Lt::BK_FITS ? Lt::TOTAL_BK : Lt::TOTAL);
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+  { const int32_t rc = crux_lds_attr_once<k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>>(c, lds); if (rc) return rc; }
   hipLaunchKernelGGL((k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>), dim3(32), dim3(512), lds, stream, a);
   return crux_launch_check(c, PXK ? "k_train_fs2 (replica group, periodic form)" : PX ? "k_train_fs2 (replica group)" : LAG ? "k_train_fs2 (lagrange_ppo_loss)" : "k_train_fs2");
 }
@@ -36,20 +35,17 @@ static int32_t launch_fs2(crux_ctx* c, TrainArgs a, bool timing, hipStream_t str
   }
   constexpr bool HAS_TIMING = H2 == 64 && ACT2 == ACT && ((IN == 4 && (OUT == 2 || OUT == 1)) || (IN == 17 && ACT == CRUX_ACT_TANH));      // the in-kernel phase timers are instantiated for the C2 / C5 learners only
   if constexpr (HAS_TIMING) if (timing) {
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) { if (hipMalloc(&dbg, 512 * 8) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "timing buffer"); }
-    a.dbg = dbg;
+    a.dbg = mf_timing_buf(c);
+    if (!a.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
     int32_t rc = launch_fs2_form<IN, OUT, KIND, ACT, H2, ACT2, true>(c, a, stream); if (rc) return rc;
-    unsigned long long h[512]; HIPCHK(c, hipMemcpyAsync(h, dbg, sizeof h, hipMemcpyDeviceToHost, stream)); HIPCHK(c, hipStreamSynchronize(stream));
-    static const char* nc[16] = {"loop", "wait staged", "fwdL1+T1", "fwdL2", "L3+pair barrier+head", "dW3+dZ2+stats+T2", "wait B_1", "dW2+send+dH1", "dZ1+db+dW1", "B_2+reduce+granules", "wait P1",
-                                 "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+report+exit"};
-    static const char* nh[16] = {"loop", "fetch", "stage next", "wait B_1", "dW2+send+drain", "arrival 1+wait(leader)", "-", "-", "-", "wait B_2+reduce+granules", "wait P1",
-                                 "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+exit"};
-    for (int wg = 0; wg < 4; ++wg) for (int w : {0, 4}) { const char** nm = w == 0 ? nc : nh;
-      fprintf(stderr, "[fs2-timing] %d-%d wg %d %s wave %d:", IN, OUT, wg, w == 0 ? "compute" : "helper", w); unsigned long long tot = 0; for (int k = 0; k < 16; ++k) tot += h[(8 * wg + w) * 16 + k];
-      for (int k = 0; k < 16; ++k) if (nm[k][0] != '-') fprintf(stderr, " %s=%.1f%%", nm[k], 100.0 * (double)h[(8 * wg + w) * 16 + k] / (double)tot);
-      fprintf(stderr, " total=%llu\n", tot); }
-    return CRUX_OK;
+    static const char* const nc[16] = {"loop", "wait staged", "fwdL1+T1", "fwdL2", "L3+pair barrier+head", "dW3+dZ2+stats+T2", "wait B_1", "dW2+send+dH1", "dZ1+db+dW1", "B_2+reduce+granules", "wait P1",
+                                       "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+report+exit"};
+    static const char* const nh[16] = {"loop", "fetch", "stage next", "wait B_1", "dW2+send+drain", "arrival 1+wait(leader)", "-", "-", "-", "wait B_2+reduce+granules", "wait P1",
+                                       "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+exit"};
+    MfTimingRow rows[8];
+    for (int i = 0; i < 8; ++i) { const int wg = i >> 1, w = 4 * (i & 1); rows[i].row = 8 * wg + w; rows[i].names = w == 0 ? nc : nh;
+      snprintf(rows[i].label, sizeof rows[i].label, "[fs2-timing] %d-%d wg %d %s wave %d:", IN, OUT, wg, w == 0 ? "compute" : "helper", w); }
+    return mf_timing_dump(c, stream, rows, 8);
   }
   return launch_fs2_form<IN, OUT, KIND, ACT, H2, ACT2, false>(c, a, stream);
 }
@@ -64,14 +60,10 @@ int32_t crux_train_fs_launch(crux_ctx* c, const TrainArgs& a, bool* handled, hip
   if (crux_sw().fs == 0) return CRUX_OK;            // read per call: tests switch the form inside one process
   if (c->learner_cus != 0 && !a.need_px) return CRUX_OK;      // crux_ctx_set_learner_cus(1 | 2): the caller asked for the one- / two-CU kernels (population runs)
   const NetDesc& nd = a.nd;
-  if (nd.L != 3 || nd.dims[1] != MF_HID || (nd.dims[2] != 64 && nd.dims[2] != 32) || nd.acts[2] != CRUX_ACT_IDENTITY) return CRUX_OK;
+  if (!mf_family(nd, true)) return CRUX_OK;
   if (a.ids || !a.apply || a.bs <= 64 || a.bs > 128 || a.len < a.bs) return CRUX_OK;
-  int kind;
-  if (a.loss == CRUX_LOSS_VALUE_MSE) kind = MFK_VALUE;
-  else if (!CRUX_IS_PG(a.loss)) return CRUX_OK;
-  else if (a.head == CRUX_HEAD_CATEGORICAL) kind = MFK_CATEGORICAL;
-  else if (a.head == CRUX_HEAD_GAUSSIAN) kind = MFK_GAUSSIAN;
-  else return CRUX_OK;
+  const int kind = mf_kind(a.loss, a.head);
+  if (!(a.loss == CRUX_LOSS_VALUE_MSE || CRUX_IS_PG(a.loss)) || kind < 0) return CRUX_OK;
   if (!crux_x2_placement_ok(c)) return CRUX_OK;
   // 32-bit loop control inside the kernel: buffers below 2^30 rows, launches below 2^31 steps (anything larger stays with the two-CU kernel / the dense-engine learner)
   if (a.len >= (1ll << 30) || (long long)a.epochs * ((a.len + a.bs - 1) / a.bs) >= 0x7fffffffll) return CRUX_OK;

@@ -4,14 +4,13 @@
 #include "train_mfma_kernel.h"
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
-template <int IN, int OUT, int KIND, int ACT>
+template <int IN, int OUT, int KIND, int ACT, bool TIMING = false>
 static int32_t launch_one8(crux_ctx* c, const TrainArgs& a, hipStream_t stream) {
   using Lt = MfLayout<IN, OUT, 8>;
   constexpr size_t lds = sizeof(float) * (size_t)Lt::TOTAL;
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];      // (per device: a second device in the process sets the attribute for itself)
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_mfma<IN, OUT, KIND, ACT, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
-  hipLaunchKernelGGL((k_train_mfma<IN, OUT, KIND, ACT, 8, 1>), dim3(1), dim3(512), lds, stream, a, (const TrainArgs*)nullptr);
-  return crux_launch_check(c, "k_train_mfma<8,1>");
+  { const int32_t rc = crux_lds_attr_once<k_train_mfma<IN, OUT, KIND, ACT, 8, 1, TIMING>>(c, lds); if (rc) return rc; }
+  hipLaunchKernelGGL((k_train_mfma<IN, OUT, KIND, ACT, 8, 1, TIMING>), dim3(1), dim3(512), lds, stream, a, (const TrainArgs*)nullptr);
+  return crux_launch_check(c, TIMING ? "k_train_mfma<8,1,timing>" : "k_train_mfma<8,1>");
 }
 
 // n independent learners, one CU each (grid n): argument blocks uploaded to a per-stream device array
@@ -19,8 +18,7 @@ template <int IN, int OUT, int KIND, int ACT>
 static int32_t launch_multi8(crux_ctx* c, std::vector<TrainArgs>& as, hipStream_t stream) {
   using Lt = MfLayout<IN, OUT, 8>;
   constexpr size_t lds = sizeof(float) * (size_t)Lt::TOTAL;
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];      // (per device: a second device in the process sets the attribute for itself)
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_mfma<IN, OUT, KIND, ACT, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+  { const int32_t rc = crux_lds_attr_once<k_train_mfma<IN, OUT, KIND, ACT, 8, 1>>(c, lds); if (rc) return rc; }
   const int which = stream == c->stream ? 0 : 1; const size_t n = as.size(), need = n * sizeof(TrainArgs) + 256;
   if (c->amulti_bytes[which] < need) {
     if (c->amulti[which]) { HIPCHK(c, hipDeviceSynchronize()); (void)hipFree(c->amulti[which]); c->amulti[which] = nullptr; c->amulti_bytes[which] = 0; }
@@ -38,9 +36,9 @@ int32_t crux_train_mfma8_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as, b
   *handled = false;
   if (as.empty()) return CRUX_OK;
   const TrainArgs& a = as[0]; const NetDesc& nd = a.nd;
-  if (nd.L != 3 || nd.dims[1] != MF_HID || nd.dims[2] != MF_HID || nd.acts[2] != CRUX_ACT_IDENTITY || nd.acts[0] != nd.acts[1] || a.ids || !a.apply || a.bs > 128 || a.len < a.bs) return CRUX_OK;
+  if (!mf_family(nd, false) || a.ids || !a.apply || a.bs > 128 || a.len < a.bs) return CRUX_OK;
   const int in = nd.dims[0], out = nd.dims[3], act = nd.acts[0];
-  const int kind = a.loss == CRUX_LOSS_VALUE_MSE ? MFK_VALUE : (a.head == CRUX_HEAD_CATEGORICAL ? MFK_CATEGORICAL : (a.head == CRUX_HEAD_GAUSSIAN ? MFK_GAUSSIAN : -1));
+  const int kind = mf_kind(a.loss, a.head);
   if (!(a.loss == CRUX_LOSS_VALUE_MSE || CRUX_IS_PG(a.loss)) || kind < 0) return CRUX_OK;
 #define MF8M_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_multi8<I, O, K, A_>(c, as, stream); }
   MF8M_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
@@ -56,19 +54,12 @@ int32_t crux_train_mfma8_launch(crux_ctx* c, const TrainArgs& a, int kind, bool*
   *handled = false;
   const int in = a.nd.dims[0], out = a.nd.dims[3], act = a.nd.acts[0];
   if (crux_sw().mfma_timing && in == 4 && out == 2 && kind == MFK_CATEGORICAL && act == CRUX_ACT_RELU) {      // CRUX_MFMA_TIMING=1: per-phase s_memtime totals of the C2 actor (development)
-    using Lt = MfLayout<4, 2, 8>; constexpr size_t lds = sizeof(float) * (size_t)Lt::TOTAL;
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) { if (hipMalloc(&dbg, 128 * 8) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "timing buffer"); }
-    TrainArgs b = a; b.dbg = dbg; *handled = true;
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_train_mfma<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, 8, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_train_mfma<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, 8, 1, true>), dim3(1), dim3(512), lds, stream, b, (const TrainArgs*)nullptr);
-    int32_t rc = crux_launch_check(c, "k_train_mfma<8,1,timing>"); if (rc) return rc;
-    unsigned long long h[128]; HIPCHK(c, hipMemcpyAsync(h, dbg, sizeof h, hipMemcpyDeviceToHost, stream)); HIPCHK(c, hipStreamSynchronize(stream));
-    static const char* nm[16] = {"loop+prefetch", "stage", "fwdL1+T1", "fwdL2", "L3+head", "dW3+dZ2+stats+T2", "dH1", "dZ1+db+dW1", "wait B_a", "dW2", "reduce+store", "exchange wait",
-                                 "load peer+total+ssq", "wait B_or", "info+adam", "wait B_b"};
-    for (int w = 0; w < 8; w += 3) { fprintf(stderr, "[one-cu-timing] wave %d:", w); unsigned long long tot = 0; for (int k = 0; k < 16; ++k) tot += h[w * 16 + k];
-      for (int k = 0; k < 16; ++k) fprintf(stderr, " %s=%.1f%%", nm[k], 100.0 * (double)h[w * 16 + k] / (double)tot); fprintf(stderr, " total=%llu\n", tot); }
-    return CRUX_OK;
+    TrainArgs b = a; b.dbg = mf_timing_buf(c); *handled = true;
+    if (!b.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
+    const int32_t rc = launch_one8<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, true>(c, b, stream); if (rc) return rc;
+    MfTimingRow rows[3];
+    for (int i = 0; i < 3; ++i) { rows[i].row = 3 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[one-cu-timing] wave %d:", 3 * i); }
+    return mf_timing_dump(c, stream, rows, 3);
   }
 #define MF8_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_one8<I, O, K, A_>(c, a, stream); }
   MF8_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)     // C2 actor  (PPO CartPole)

@@ -21,7 +21,6 @@
 #include "train_args.h"
 
 #include "mfma_helpers.h"
-#include "peer_wait.h"
 
 // LDS layouts are chosen against the gfx950 banking rules (ds_read_b128: 64 banks, four non-contiguous 16-lane groups; b32 accesses:
 // 32 banks, two 32-lane halves): master rows are 72 floats, the per-wave exchange tiles are unpadded [64 features][16 samples]
@@ -59,15 +58,16 @@ struct MfLayout {
   static constexpr int TOTAL = oRED + 32;
 };
 
-// PX: the replica-group form (per-minibatch gradient all-reduce over the peer slots). A separate instantiation, so that the single-GPU kernel carries
-// neither the branch nor the live registers of the exchange (with a run-time test the C2 actor step was 3.6 % slower: 8.75 vs 8.44 us).
+// CRUX_MFMA_TIMING: the phases MX_T(0..15) closes, in order (both forms)
+static const char* const MF_PHASES[16] = {"loop+prefetch", "stage", "fwdL1+T1", "fwdL2", "L3+head", "dW3+dZ2+stats+T2", "dH1", "dZ1+db+dW1", "wait B_a", "dW2", "reduce+store",
+                                          "exchange wait", "load peer+total+ssq", "wait B_or", "info+adam", "wait B_b"};
+
 // LAG: lagrange_ppo_loss (ppo.jl:70-131) -- the PID penalty controller advanced once per minibatch inside the kernel and the cost-advantage term of the loss.
 // A separate instantiation (two-CU form only), so that the plain kernels carry none of it.
-template <int IN, int OUT, int KIND, int ACT, int NW, int NWG, bool TIMING = false, bool PX = false, bool LAG = false>
+template <int IN, int OUT, int KIND, int ACT, int NW, int NWG, bool TIMING = false, bool LAG = false>
 __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, const TrainArgs* __restrict__ multi) {
   static_assert((NW == 4 && NWG == 2) || (NW == 8 && NWG == 1), "forms: two workgroups of four waves, or one of eight");
-  static_assert(NWG == 2 || !PX, "the replica-group exchange lives in the two-CU form");
-  static_assert(!LAG || (NWG == 2 && !PX && KIND != MFK_VALUE), "lagrange_ppo_loss: two-CU form, policy heads");
+  static_assert(!LAG || (NWG == 2 && KIND != MFK_VALUE), "lagrange_ppo_loss: two-CU form, policy heads");
   constexpr int MF8_NW = NW;
   constexpr int WT = 16 / NW;                        // 16x16 tiles of W2 (and of its gradient, Adam state) owned by a wave
   // multi != NULL: a batch of independent learners (multi-seed / population training) in one launch. Two-CU form: replica r = blockIdx / 16 uses the
@@ -167,11 +167,6 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
   long long total_batches = 0; int epochs_run = 0, err = 0, why_failed = 0; bool stop = false;
   bool staged = false;                              // the next minibatch is already in this wave's LDS staging tiles
   long long xstep = 0;                              // exchanges done so far (the counter target and the slot parity)
-  // replica group (comm.hip "peer"): exchanges done on this learner stream before this launch -- slot parity and flag values continue across launches
-  float* const px_mine = PX ? a.px_tab[a.px_rank] : nullptr;
-  const unsigned long long px0 = PX ? *(const unsigned long long*)(px_mine + CRUX_PX_COUNT) : 0ull;
-  if (PX && tid == 0) px_launch_begin(px_mine, p);      // the launch's wait budget starts from zero (peer_wait.h, bound 2)
-  const float px_inv = PX ? 1.0f / (float)a.px_n : 1.0f;
   constexpr int XSLOT = 4096 + NSI * NT + 16;
   // the reported minibatch's info (training.jl:22-23) is kept by thread 0 -- its only reader (epoch_infos) -- in free words of the reduction area, not in registers of every
   // thread that would stay live across the whole launch (k_train_fs2 has the measurement: ~30 VGPRs); the KL stays a register: the loop exits read it
@@ -538,8 +533,7 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
           if (ok && xstep == 0) {   // the unfenced exchange is only coherent inside one XCD's L2: refuse to train if the two workgroups were placed on different XCDs
             const unsigned peer_xcc = __hip_atomic_load(a.xctr + 8 + (1 - p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (peer_xcc != my_xcc + 1u) { ok = false; why = 2.f; } }       // 2: the two workgroups of this learner sit on different XCDs
-          if (!ok) { __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (PX) for (int r = 0; r < a.px_n; ++r) __hip_atomic_store((unsigned*)(a.px_tab[r] + CRUX_PX_ABORT), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }   // the replicas stop waiting for this one
+          if (!ok) __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           sm[Lt::oRED + 16] = why;
         }
         __syncthreads();
@@ -558,116 +552,6 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
 #pragma unroll
         for (int k = 0; k < NSI; ++k) gs[k] += pg[k];
         stat_tot = stat_loc + ps;
-        if constexpr (PX) {
-          // ---- SUM all-reduce of the local gradient over the replica group, between the pullback (training.jl:18) and Flux.update! (:21) ----
-          // Both workgroups hold the same local total. They share the writes (peer i of the N-1 goes to workgroup i & 1): the total and the seven
-          // statistics sums go into slot [parity][my rank] of the peer's region, a system-scope release makes them visible, then flag[my rank]
-          // there is raised to the exchange number. Both workgroups then wait for the N-1 flags in the OWN region and add the N contributions in
-          // rank order -- the own one from registers (nothing orders workgroup 1 after a store of workgroup 0, so it is never read back from a
-          // slot), the others from the slots -- so every workgroup of every rank forms the same sum bit for bit.
-          const unsigned long long xg = px0 + (unsigned long long)xstep;       // number of this exchange on this learner stream
-          const int par = (int)(xg & 1ull);
-          { int pi_ = 0;
-            for (int r = 0; r < a.px_n; ++r) {
-              if (r == a.px_rank || (pi_++ & 1) != p) continue;
-              float* dst = a.px_tab[r] + (size_t)(par * CRUX_PX_MAXR + a.px_rank) * CRUX_PX_SLOT;
-#pragma unroll
-              for (int mm = 0; mm < 4; ++mm) *(f32x4*)&dst[tid * 16 + 4 * mm] = gW2[mm];
-#pragma unroll
-              for (int k = 0; k < NSI; ++k) dst[4096 + tid + NT * k] = gs[k];
-              if (tid >= NT - 8 && tid < stat_hi) dst[4096 + NSI * NT + (tid - (NT - 8))] = stat_tot; } }
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // every wave drains its own slot stores; the workgroup meets; ONE lane issues the system-scope
-          __syncthreads();                                                      // release (the L2 write-back covers the lines of all waves) and drains it before the flags go out
-          if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            int pi_ = 0;
-            for (int r = 0; r < a.px_n; ++r) { if (r == a.px_rank) continue;
-              if ((pi_++ & 1) != p) continue;
-              // relaxed: the release above covers the slot stores of every wave (all drained before the barrier)
-              __hip_atomic_store((unsigned long long*)(a.px_tab[r] + CRUX_PX_FLAGS) + 8 * a.px_rank, xg + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-            const long long t0 = wall_clock64();                // 100 MHz; the wait is bounded four ways (peer_wait.h)
-            const unsigned gave_up = px_wait_peers(px_mine, a.px_n, a.px_rank, xg + 1ull, t0, a.px_timeout, p, true); const bool ok = gave_up == 0u;
-            if (!ok) { px_raise_abort(a.px_tab, a.px_n, gave_up);
-              __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-            if (a.px_hist) {      // how long this workgroup waited for the slowest peer's flag (10 ns ticks, log2 bins): the selftest's view of the xGMI hand-off
-              const unsigned long long dtk = (unsigned long long)(wall_clock64() - t0) | 1ull;
-              unsigned* hb = (unsigned*)(px_mine + CRUX_PX_HIST) + 32 * p + (63 - __builtin_clzll(dtk) > 31 ? 31 : 63 - __builtin_clzll(dtk));
-              *hb = *hb + 1u; }
-            sm[Lt::oRED + 16] = ok ? 0.f : (float)(16u + gave_up);      // 16 + bound (peer_wait.h): the replica group ended this launch
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                       // system scope, one lane (the slot loads below are sc0 sc1 and pass the L1 anyway)
-          }
-          __syncthreads();
-          if (sm[Lt::oRED + 16] != 0.f) { err = CRUX_EHIP; why_failed = (int)sm[Lt::oRED + 16]; break; }
-          // the N - 1 slots are read two ranks at a time (all loads of a pair in flight together) and added in rank order
-          f32x4 oW[4]; float oS[NSI]; const float oT = stat_tot;
-#pragma unroll
-          for (int mm = 0; mm < 4; ++mm) oW[mm] = gW2[mm];
-#pragma unroll
-          for (int k = 0; k < NSI; ++k) oS[k] = gs[k];
-          auto px_load = [&](int r, f32x4 (&vW)[4], float (&vS)[NSI], float& vT) {
-            if (r == a.px_rank) {
-#pragma unroll
-              for (int mm = 0; mm < 4; ++mm) vW[mm] = oW[mm];
-#pragma unroll
-              for (int k = 0; k < NSI; ++k) vS[k] = oS[k];
-              vT = oT; return; }
-            const float* src = px_mine + (size_t)(par * CRUX_PX_MAXR + r) * CRUX_PX_SLOT;
-#pragma unroll
-            for (int k = 0; k < NSI; ++k) vS[k] = __hip_atomic_load(src + 4096 + tid + NT * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            vT = 0.f;
-            if (tid >= NT - 8 && tid < stat_hi) vT = __hip_atomic_load(src + 4096 + NSI * NT + (tid - (NT - 8)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            asm volatile("global_load_dwordx4 %0, %4, off sc0 sc1\n\tglobal_load_dwordx4 %1, %4, off offset:16 sc0 sc1\n\tglobal_load_dwordx4 %2, %4, off offset:32 sc0 sc1\n\t"
-                         "global_load_dwordx4 %3, %4, off offset:48 sc0 sc1"
-                         : "=&v"(vW[0]), "=&v"(vW[1]), "=&v"(vW[2]), "=&v"(vW[3]) : "v"(src + tid * 16) : "memory");
-          };
-          // The slots are read PXS ranks at a time -- all loads of a batch in flight together, one round trip to the fine-grained region per batch -- and added in
-          // rank order. Heads of up to four outputs have the registers for four at a time (8 replicas = two round trips); the six-output heads sit at the
-          // 512-register limit and take two (16 + NSI live registers per slot in flight; with four the step loop spills, with two only prologue / epilogue values do).
-          constexpr int PXS = (OUT <= 4) ? 4 : 2;
-          for (int r0 = 0; r0 < a.px_n; r0 += PXS) {
-            f32x4 vW[PXS][4]; float vS[PXS][NSI]; float vT[PXS];
-#pragma unroll
-            for (int q = 0; q < PXS; ++q) {
-              if (r0 + q < a.px_n) px_load(r0 + q, vW[q], vS[q], vT[q]);
-              else { vT[q] = 0.f;
-#pragma unroll
-                for (int mm = 0; mm < 4; ++mm) vW[q][mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < NSI; ++k) vS[q][k] = 0.f; } }
-            if constexpr (PXS == 4) {
-              asm volatile("s_waitcnt vmcnt(0)" : "+v"(vW[0][0]), "+v"(vW[0][1]), "+v"(vW[0][2]), "+v"(vW[0][3]), "+v"(vW[1][0]), "+v"(vW[1][1]), "+v"(vW[1][2]), "+v"(vW[1][3]),
-                                                  "+v"(vW[2][0]), "+v"(vW[2][1]), "+v"(vW[2][2]), "+v"(vW[2][3]), "+v"(vW[3][0]), "+v"(vW[3][1]), "+v"(vW[3][2]), "+v"(vW[3][3]) :: "memory");
-            } else if constexpr (PXS == 2) {
-              asm volatile("s_waitcnt vmcnt(0)" : "+v"(vW[0][0]), "+v"(vW[0][1]), "+v"(vW[0][2]), "+v"(vW[0][3]), "+v"(vW[1][0]), "+v"(vW[1][1]), "+v"(vW[1][2]), "+v"(vW[1][3]) :: "memory");
-            } else {
-              asm volatile("s_waitcnt vmcnt(0)" : "+v"(vW[0][0]), "+v"(vW[0][1]), "+v"(vW[0][2]), "+v"(vW[0][3]) :: "memory");
-            }
-#pragma unroll
-            for (int q = 0; q < PXS; ++q) {
-              if (r0 + q >= a.px_n) break;
-              if (r0 + q == 0) {
-#pragma unroll
-                for (int mm = 0; mm < 4; ++mm) gW2[mm] = vW[q][mm];
-#pragma unroll
-                for (int k = 0; k < NSI; ++k) gs[k] = vS[q][k];
-                stat_tot = vT[q];
-              } else {
-#pragma unroll
-                for (int mm = 0; mm < 4; ++mm) gW2[mm] += vW[q][mm];
-#pragma unroll
-                for (int k = 0; k < NSI; ++k) gs[k] += vS[q][k];
-                stat_tot += vT[q];
-              }
-            }
-          }
-          // mean over the group: global minibatch = px_n x nb samples, every rank's partial was already divided by nb
-#pragma unroll
-          for (int mm = 0; mm < 4; ++mm) gW2[mm] = gW2[mm] * px_inv;
-#pragma unroll
-          for (int k = 0; k < NSI; ++k) gs[k] = gs[k] * px_inv;
-          stat_tot = stat_tot * px_inv;
-        }
         xstep += 1;
       }
       if (tid >= NT - 8 && tid < stat_hi) sm[Lt::oRED + 8 + (tid - (NT - 8))] = stat_tot;
@@ -763,10 +647,9 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
     for (int s = tid; s < ns_valid; s += NT) { const int pc = s_canon(s); a.p[pc] = sm[s_master(s)]; a.m[pc] = sm[Lt::oMS + s]; a.v[pc] = sm[Lt::oVS + s]; }
   }
   if (TIMING && lane == 0 && a.dbg) { for (int k = 0; k < 16; ++k) a.dbg[(4 * p + w) * 16 + k] = tacc[k]; }
-  if (PX && tid == 0 && p == 0) *(unsigned long long*)(px_mine + CRUX_PX_COUNT) = px0 + (unsigned long long)xstep;
   if (tid == 0 && (p == 0 || err)) {
     a.status[0] = err; a.status[1] = (int32_t)total_batches; a.status[2] = epochs_run; a.status[3] = (order_cur == a.order_a) ? 0 : 1;
-    if (err == CRUX_EHIP) a.status[4] = why_failed;      // 1 local workgroup missing, 2 workgroups on different XCDs, 3 replica group timeout / abort
+    if (err == CRUX_EHIP) a.status[4] = why_failed;      // 1 local workgroup missing, 2 workgroups on different XCDs
     a.bp[0] = bp1; a.bp[1] = bp2;
     if constexpr (LAG) { if (p == 0) *a.lag = lg; }
     if (err && a.epoch_infos && epochs_run == 0) { a.epoch_infos[CRUX_INFO_LOSS] = sm[iLOSS]; a.epoch_infos[CRUX_INFO_GRAD_NORM] = NAN; }

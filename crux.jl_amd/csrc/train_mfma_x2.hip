@@ -31,11 +31,10 @@ extern "C" int crux_x2_placement_ok(crux_ctx* c) {
   return cached;
 }
 
-template <int IN, int OUT, int KIND, int ACT, bool TIMING, bool PX, bool LAG = false>
+template <int IN, int OUT, int KIND, int ACT, bool TIMING, bool LAG = false>
 static int32_t launch_x2_form(crux_ctx* c, const TrainArgs& a, size_t lds, hipStream_t stream) {
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];      // (per device: a second device in the process sets the attribute for itself)
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_mfma<IN, OUT, KIND, ACT, 4, 2, TIMING, PX, LAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
-  hipLaunchKernelGGL((k_train_mfma<IN, OUT, KIND, ACT, 4, 2, TIMING, PX, LAG>), dim3(16), dim3(256), lds, stream, a, (const TrainArgs*)nullptr);
+  { const int32_t rc = crux_lds_attr_once<k_train_mfma<IN, OUT, KIND, ACT, 4, 2, TIMING, LAG>>(c, lds); if (rc) return rc; }
+  hipLaunchKernelGGL((k_train_mfma<IN, OUT, KIND, ACT, 4, 2, TIMING, LAG>), dim3(16), dim3(256), lds, stream, a, (const TrainArgs*)nullptr);
   return crux_launch_check(c, "k_train_mfma<4,2>");
 }
 template <int IN, int OUT, int KIND, int ACT, bool TIMING = false>
@@ -49,12 +48,8 @@ static int32_t launch_x2(crux_ctx* c, TrainArgs a, hipStream_t stream) {
   if (!c->xbuf[which]) { if (hipMalloc(&c->xbuf[which], xbytes) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "learner exchange buffer"); }
   a.xbuf = (float*)c->xbuf[which]; a.xctr = (unsigned*)((char*)c->xbuf[which] + sizeof(float) * CRUX_XBUF_FLOATS);
   HIPCHK(c, hipMemsetAsync(a.xctr, 0, 256, stream));
-  if (crux_grouped(c) && a.need_px) {     // local calls (single steps, gradients) never exchange
-    a.px_hist = c->peer_hist ? 1 : 0; a.px_n = c->peer_n; a.px_rank = c->peer_rank; a.px_tab = c->peer_tab + which * CRUX_PX_MAXR;
-    return launch_x2_form<IN, OUT, KIND, ACT, false, true>(c, a, lds, stream);
-  }
-  if constexpr (KIND != MFK_VALUE && !TIMING) { if (a.lag) return launch_x2_form<IN, OUT, KIND, ACT, false, false, true>(c, a, lds, stream); }      // lagrange_ppo_loss (ppo.jl:70-131)
-  return launch_x2_form<IN, OUT, KIND, ACT, TIMING, false>(c, a, lds, stream);
+  if constexpr (KIND != MFK_VALUE && !TIMING) { if (a.lag) return launch_x2_form<IN, OUT, KIND, ACT, false, true>(c, a, lds, stream); }      // lagrange_ppo_loss (ppo.jl:70-131)
+  return launch_x2_form<IN, OUT, KIND, ACT, TIMING>(c, a, lds, stream);
 }
 
 // n independent learners in one launch (grid 16 n): argument blocks uploaded to a per-stream device array, one exchange area each
@@ -62,8 +57,7 @@ template <int IN, int OUT, int KIND, int ACT>
 static int32_t launch_x2_multi(crux_ctx* c, std::vector<TrainArgs>& as, hipStream_t stream) {
   using Lt = MfLayout<IN, OUT, 4>;
   constexpr size_t lds = sizeof(float) * (size_t)Lt::TOTAL;
-  static bool attr_dev[16] = {}; bool& attr = attr_dev[c->device & 15];      // (per device: a second device in the process sets the attribute for itself)
-  if (!attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_mfma<IN, OUT, KIND, ACT, 4, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+  { const int32_t rc = crux_lds_attr_once<k_train_mfma<IN, OUT, KIND, ACT, 4, 2, false>>(c, lds); if (rc) return rc; }
   const int which = stream == c->stream ? 0 : 1; const size_t n = as.size();
   constexpr size_t xbytes = sizeof(float) * 4 * 8192 + 256;
   const size_t need = n * xbytes + n * sizeof(TrainArgs) + 256;
@@ -87,9 +81,9 @@ int32_t crux_train_mfma_x2_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as,
   if (as.empty() || !x2_placement_ok(c)) return CRUX_OK;
   const TrainArgs& a = as[0];
   const NetDesc& nd = a.nd;
-  if (nd.L != 3 || nd.dims[1] != MF_HID || nd.dims[2] != MF_HID || nd.acts[2] != CRUX_ACT_IDENTITY || nd.acts[0] != nd.acts[1] || a.ids || !a.apply || a.bs <= 64 || a.bs > 128 || a.len < a.bs) return CRUX_OK;
+  if (!mf_family(nd, false) || a.ids || !a.apply || a.bs <= 64 || a.bs > 128 || a.len < a.bs) return CRUX_OK;
   const int in = nd.dims[0], out = nd.dims[3], act = nd.acts[0];
-  const int kind = a.loss == CRUX_LOSS_VALUE_MSE ? MFK_VALUE : (a.head == CRUX_HEAD_CATEGORICAL ? MFK_CATEGORICAL : (a.head == CRUX_HEAD_GAUSSIAN ? MFK_GAUSSIAN : -1));
+  const int kind = mf_kind(a.loss, a.head);
   if (!(a.loss == CRUX_LOSS_VALUE_MSE || CRUX_IS_PG(a.loss)) || kind < 0) return CRUX_OK;
 #define MFXM_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2_multi<I, O, K, A_>(c, as, stream); }
   MFXM_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
@@ -105,13 +99,12 @@ int32_t crux_train_mfma_x2_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as,
 // (workgroup 1 then idles on empty tiles) -- used for the shapes that have no one-CU instantiation.
 int32_t crux_train_mfma_x2_launch(crux_ctx* c, const TrainArgs& a, int kind, bool* handled, hipStream_t stream, bool any_mode) {
   *handled = false;
-  const bool off = !crux_sw().mfma_x2;
-  if (off) return CRUX_OK;
+  if (!crux_sw().mfma_x2) return CRUX_OK;
+  if (crux_grouped(c) && a.need_px) return CRUX_OK;      // no replica-group form: grouped updates run on k_train_fs2 or the dense-engine learner
   if (!any_mode && (a.ids || !a.apply || a.bs <= 64 || a.len < a.bs)) return CRUX_OK;     // single steps and small batches stay on one CU when it has the shape
   if (!x2_placement_ok(c)) return CRUX_OK;
   const int in = a.nd.dims[0], out = a.nd.dims[3], act = a.nd.acts[0];
-  if (a.lag) {     // lagrange_ppo_loss: its own instantiations, for the shapes below; replica groups and every other shape stay on the dense-engine learner
-    if (crux_grouped(c) && a.need_px) return CRUX_OK;
+  if (a.lag) {     // lagrange_ppo_loss: its own instantiations, for the shapes below; every other shape stays on the dense-engine learner
 #define MFXL_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2<I, O, K, A_>(c, a, stream); }
     MFXL_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
     MFXL_CASE(8, 4, MFK_CATEGORICAL, CRUX_ACT_RELU)
@@ -121,16 +114,12 @@ int32_t crux_train_mfma_x2_launch(crux_ctx* c, const TrainArgs& a, int kind, boo
     return CRUX_OK;
   }
   if (crux_sw().mfma_timing && ((in == 4 && out == 2 && kind == MFK_CATEGORICAL && act == CRUX_ACT_RELU) || (in == 17 && out == 6 && kind == MFK_GAUSSIAN && act == CRUX_ACT_TANH))) {
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) { if (hipMalloc(&dbg, 128 * 8) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "timing buffer"); }
-    TrainArgs b = a; b.dbg = dbg; *handled = true;
-    int32_t rc = in == 4 ? launch_x2<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, true>(c, b, stream) : launch_x2<17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH, true>(c, b, stream); if (rc) return rc;
-    unsigned long long h[128]; HIPCHK(c, hipMemcpyAsync(h, dbg, sizeof h, hipMemcpyDeviceToHost, stream)); HIPCHK(c, hipStreamSynchronize(stream));
-    static const char* nm[16] = {"loop+prefetch", "stage", "fwdL1+T1", "fwdL2", "L3+head", "dW3+dZ2+stats+T2", "dH1", "dZ1+db+dW1", "wait B_a", "dW2", "reduce+store", "exchange wait",
-                                 "load peer+total+ssq", "wait B_or", "info+adam", "wait B_b"};
-    for (int w = 0; w < 8; w += 4) { fprintf(stderr, "[x2-timing] %d-%d wg %d wave %d:", in, out, w >> 2, w & 3); unsigned long long tot = 0; for (int k = 0; k < 16; ++k) tot += h[w * 16 + k];
-      for (int k = 0; k < 16; ++k) fprintf(stderr, " %s=%.1f%%", nm[k], 100.0 * (double)h[w * 16 + k] / (double)tot); fprintf(stderr, " total=%llu\n", tot); }
-    return CRUX_OK;
+    TrainArgs b = a; b.dbg = mf_timing_buf(c); *handled = true;
+    if (!b.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
+    const int32_t rc = in == 4 ? launch_x2<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, true>(c, b, stream) : launch_x2<17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH, true>(c, b, stream); if (rc) return rc;
+    MfTimingRow rows[2];
+    for (int i = 0; i < 2; ++i) { rows[i].row = 4 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[x2-timing] %d-%d wg %d wave 0:", in, out, i); }
+    return mf_timing_dump(c, stream, rows, 2);
   }
 #define MFX_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2<I, O, K, A_>(c, a, stream); }
   MFX_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)     // C2 actor  (PPO CartPole)

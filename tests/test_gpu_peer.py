@@ -404,7 +404,7 @@ def test_policy_gradient_training_of_two_replicas_in_the_periodic_form(two_conte
 
 
 def test_unsupported_shape_with_a_group_attached_is_refused(two_contexts):
-    """the exchange lives in the two-CU kernels: a learner they do not cover must fail loudly instead of training un-synchronised."""
+    """the exchange lives in k_train_fs2's replica-group forms and the dense-engine learner: a learner neither covers must fail loudly instead of training un-synchronised."""
     ctx = two_contexts[0]
     g = crux.ContinuousNetwork(parity.chain([4, 32, 1], ["relu", "identity"]), ctx=ctx)
     d = _shard(400, E=2, T=64)
@@ -526,22 +526,35 @@ def test_dense_engine_learner_under_a_replica_group_equals_the_concatenated_batc
     launches per minibatch, train_dense.hip) under a group of two: the flat gradient (18 180 floats = three slot-sized chunks) and the head's statistics are SUM-all-reduced
     by k_px_allreduce_flat between the pullback and the gated Adam. Two replicas with minibatches of 128 must take the steps of ONE oracle learner on minibatches of 256 and
     stay bit-identical to each other."""
-    ctxs = two_contexts; bs, epochs, N = 128, 2, 512
-    rng = np.random.default_rng(31); extras = ["return", "logprob", "advantage"]
+    _group_vs_concatenated_oracle(two_contexts, which, 8, 128, 4, 31, "dense-engine learner")
+
+
+@pytest.mark.parametrize("which", ["actor", "critic"])
+def test_c2_learner_under_a_replica_group_without_the_feature_split_kernel_takes_the_dense_engine(two_contexts, monkeypatch, which):
+    """CRUX_FS=0 switches k_train_fs2 off; the one- and two-CU kernels have no replica-group exchange, so a grouped 4->64->64->2 PPO actor / 4->64->64->1 critic with minibatches
+    of 128 is the dense-engine learner's (train_dense.hip, k_px_allreduce_flat). Same checks as above: bit-identical replicas, the concatenated-batch oracle within the same bounds.
+    (The monkeypatch fixture re-reads the process-wide switches after the setenv and again after the test.)"""
+    monkeypatch.setenv("CRUX_FS", "0")
+    _group_vs_concatenated_oracle(two_contexts, which, 4, 64, 2, 37, "C2 learner under CRUX_FS=0")
+
+
+def _group_vs_concatenated_oracle(ctxs, which, od, width, na, seed, what):
+    bs, epochs, N = 128, 2, 512
+    rng = np.random.default_rng(seed); extras = ["return", "logprob", "advantage"]
     def shard():
-        ai = rng.integers(0, 4, N)
-        return {"s": rng.normal(0, 1, (8, N)).astype(np.float32), "a": np.eye(4, dtype=bool)[:, ai], "sp": rng.normal(0, 1, (8, N)).astype(np.float32), "r": np.ones((1, N), np.float32),
+        ai = rng.integers(0, na, N)
+        return {"s": rng.normal(0, 1, (od, N)).astype(np.float32), "a": np.eye(na, dtype=bool)[:, ai], "sp": rng.normal(0, 1, (od, N)).astype(np.float32), "r": np.ones((1, N), np.float32),
                 "done": np.zeros((1, N), bool), "episode_end": np.zeros((1, N), bool), "return": rng.normal(0, 1, (1, N)).astype(np.float32),
                 "logprob": rng.normal(-1.4, 0.05, (1, N)).astype(np.float32), "advantage": rng.normal(0, 1, (1, N)).astype(np.float32)}
     shards = [shard(), shard()]
-    dims = [8, 128, 128, 4] if which == "actor" else [8, 128, 128, 1]
+    dims = [od, width, width, na] if which == "actor" else [od, width, width, 1]
     loss, head = ("ppo", "categorical") if which == "actor" else ("value_mse", "deterministic")
     perms = [np.stack([rng.permutation(N) for _ in range(epochs)]) for _ in range(2)]
     nets, bufs = [], []
     for r, ctx in enumerate(ctxs):
         ch = parity.chain(dims, parity.ACTS)
-        g = crux.DiscreteNetwork(ch, [1, 2, 3, 4], ctx=ctx, seed=78, stream=3) if which == "actor" else crux.ContinuousNetwork(ch, ctx=ctx, seed=78, stream=3)
-        b = crux.ExperienceBuffer(crux.ContinuousSpace(8), crux.DiscreteSpace(4), N, extras, ctx=ctx); b.push_(shards[r])
+        g = crux.DiscreteNetwork(ch, list(range(1, na + 1)), ctx=ctx, seed=78, stream=3) if which == "actor" else crux.ContinuousNetwork(ch, ctx=ctx, seed=78, stream=3)
+        b = crux.ExperienceBuffer(crux.ContinuousSpace(od), crux.DiscreteSpace(na), N, extras, ctx=ctx); b.push_(shards[r])
         nets.append(g); bufs.append(b)
     P = {"eps": 0.2, "lambda_p": 1.0, "lambda_e": 0.1}
     infos = [None, None]
@@ -557,7 +570,7 @@ def test_dense_engine_learner_under_a_replica_group_equals_the_concatenated_batc
     assert np.array_equal(m0, m1) and np.array_equal(v0, v1) and np.array_equal(bp0, bp1)
     assert infos[0]["n_loss"] == infos[1]["n_loss"] and infos[0]["n_grad_norm"] == infos[1]["n_grad_norm"]
     glob, pos = _interleave(shards, bs)
-    ob = O.OBuffer(8, 4, L.ACTION_DISCRETE, 2 * N, extras); ob.push(glob)
+    ob = O.OBuffer(od, na, L.ACTION_DISCRETE, 2 * N, extras); ob.push(glob)
     o = O.OMlp(dims, parity.ACTS).init_glorot(78, 3).adam_init(float(np.float32(3e-4)))
     gperm = np.empty((epochs, 2 * N), np.int64)
     for e in range(epochs):
@@ -567,8 +580,8 @@ def test_dense_engine_learner_under_a_replica_group_equals_the_concatenated_batc
     oi = np.zeros(L.INFO_N, np.float32)
     O.chk(O.lib().orc_batch_train(o.h, ob.h, C.byref(cfg), O.vpz(gperm), O.vpz(oi), None))
     d = float(np.abs(p0 - o.params).max())
-    print(which, "dense-engine learner, two replicas vs concatenated-batch oracle after %d steps: max |dtheta| = %.3g" % (epochs * (N // bs), d), "loss", infos[0]["n_loss"], float(oi[0]))
-    assert d < 2e-6            # measured 4.5e-8 (actor) / 1.5e-8 (critic) after 8 steps
+    print(which, what + ", two replicas vs concatenated-batch oracle after %d steps: max |dtheta| = %.3g" % (epochs * (N // bs), d), "loss", infos[0]["n_loss"], float(oi[0]))
+    assert d < 2e-6            # measured 4.5e-8 (actor) / 1.5e-8 (critic) after 8 steps on the 128-wide shapes
     assert abs(infos[0]["n_loss"] - float(oi[0])) < 2e-5 * max(1.0, abs(float(oi[0])))
 
 
