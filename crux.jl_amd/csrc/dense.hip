@@ -123,11 +123,11 @@ struct Gemm16 { static __device__ __forceinline__ void run(const unsigned bid_, 
     q.C[ci] = v; }
 } };
 template <bool AV, bool BV, bool SPLITK>
-__global__ __launch_bounds__(256) void k_gemm16(GemmArgs q) { __shared__ float part[SPLITK ? GEMM16_PART : 1]; Gemm16<AV, BV, SPLITK>::run(blockIdx.x, q, part); }
+__global__ __launch_bounds__(256) void k_gemm16(GemmArgs q, int quart) { __shared__ float part[SPLITK ? GEMM16_PART : 1]; Gemm16<AV, BV, SPLITK>::run(blockIdx.x, q, part, quart); }
 // the executor's form (exec.hip): the variant is data
 struct GemmOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, GemmArgs q, int variant) {
   __shared__ float part[GEMM16_PART];         // one combine buffer for all variants (a static array per template instantiation cost the phase kernel 15 KB of LDS)
-  const int quart = (variant >> 3) & 1;       // bit 0 AV, bit 1 BV, bit 2 split-K over the workgroup's waves, bit 3 the four K quarters walked by one wave (no launch site sets it now)
+  const int quart = (variant >> 3) & 1;       // bit 0 AV, bit 1 BV, bit 2 split-K over the workgroup's waves, bit 3 the four K quarters walked by one wave (launch_gemm: K >= 128 past the split-K tile limit)
   switch (variant & 7) {
     case 0: Gemm16<false, false, false>::run(bid_, q, part, quart); break; case 1: Gemm16<true, false, false>::run(bid_, q, part, quart); break;
     case 2: Gemm16<false, true, false>::run(bid_, q, part, quart); break;  case 3: Gemm16<true, true, false>::run(bid_, q, part, quart); break;
@@ -157,25 +157,29 @@ static int32_t launch_gemm(crux_ctx* c, const GemmArgs& q, hipStream_t st) {
   const dim3 block(256);
   const bool av = vec_ok(q.A, q.sAk, q.sAi, q.K), bv = vec_ok(q.B, q.sBk, q.sBj, q.K);
   constexpr bool no_split = false;
+  // K >= 128 is reduced in four quarters WHATEVER the launch form (Gemm16): past the tile limit of the split-K form one wave walks the four quarters of its tile. (Until the
+  // shape grid of tests/test_gpu_dense_grid.py these launches took ONE chain over K: a 256-wide layer at B >= 4112 then differed in the last bits from Fwd12Op, which always
+  // quarters, and from the same layer at B = 4096.)
+  const int quart = (q.K >= 128 && tiles > 4096 && !no_split) ? 1 : 0;
   if (crux_exec_recording(c)) {                       // fused sequence (exec.hip): the same tile bodies, run by the phase launches
     // the phase launches run over the whole chip like the stand-alone launches and split K over the four waves of a workgroup whenever those do
     const bool split = q.K >= 128 && tiles <= 4096 && !no_split;
-    crux_exec_push<GemmOp, OP_GEMM>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0)));
+    crux_exec_push<GemmOp, OP_GEMM>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0) | (quart ? 8 : 0)));
     return CRUX_OK;
   }
   if (q.K >= 128 && tiles <= 4096 && !no_split) {     // deep reductions: split K over the workgroup's four waves
     const dim3 grid((unsigned)tiles);
-    if (av && bv) hipLaunchKernelGGL((k_gemm16<true, true, true>), grid, block, 0, st, q);
-    else if (av) hipLaunchKernelGGL((k_gemm16<true, false, true>), grid, block, 0, st, q);
-    else if (bv) hipLaunchKernelGGL((k_gemm16<false, true, true>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((k_gemm16<false, false, true>), grid, block, 0, st, q);
+    if (av && bv) hipLaunchKernelGGL((k_gemm16<true, true, true>), grid, block, 0, st, q, 0);
+    else if (av) hipLaunchKernelGGL((k_gemm16<true, false, true>), grid, block, 0, st, q, 0);
+    else if (bv) hipLaunchKernelGGL((k_gemm16<false, true, true>), grid, block, 0, st, q, 0);
+    else hipLaunchKernelGGL((k_gemm16<false, false, true>), grid, block, 0, st, q, 0);
     return crux_launch_check(c, "k_gemm16");
   }
   const dim3 grid((unsigned)((tiles + 3) / 4));
-  if (av && bv) hipLaunchKernelGGL((k_gemm16<true, true, false>), grid, block, 0, st, q);
-  else if (av) hipLaunchKernelGGL((k_gemm16<true, false, false>), grid, block, 0, st, q);
-  else if (bv) hipLaunchKernelGGL((k_gemm16<false, true, false>), grid, block, 0, st, q);
-  else hipLaunchKernelGGL((k_gemm16<false, false, false>), grid, block, 0, st, q);
+  if (av && bv) hipLaunchKernelGGL((k_gemm16<true, true, false>), grid, block, 0, st, q, quart);
+  else if (av) hipLaunchKernelGGL((k_gemm16<true, false, false>), grid, block, 0, st, q, quart);
+  else if (bv) hipLaunchKernelGGL((k_gemm16<false, true, false>), grid, block, 0, st, q, quart);
+  else hipLaunchKernelGGL((k_gemm16<false, false, false>), grid, block, 0, st, q, quart);
   return crux_launch_check(c, "k_gemm16");
 }
 

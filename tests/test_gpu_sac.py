@@ -11,37 +11,10 @@ import numpy as np
 import pytest
 
 import parity
+from dense_reference import _np_backward, _np_mlp
 from parity import crux, L, O
 
 pytestmark = pytest.mark.gpu
-
-
-def _np_mlp(params, dims, acts, x):
-    """float64 forward of Chain(Dense...) returning all activations."""
-    hs, off = [x.astype(np.float64)], 0
-    for l, act in enumerate(acts):
-        i, o = dims[l], dims[l + 1]
-        W = params[off:off + i * o].reshape((o, i), order="F").astype(np.float64); off += i * o
-        b = params[off:off + o].astype(np.float64); off += o
-        z = W @ hs[-1] + b[:, None]
-        hs.append(np.maximum(z, 0) if act == "relu" else np.tanh(z) if act == "tanh" else z)
-    return hs
-
-
-def _np_backward(params, dims, acts, hs, dy):
-    g, d = np.zeros_like(params, dtype=np.float64), dy.astype(np.float64)
-    offs, off = [], 0
-    for l in range(len(acts)):
-        offs.append(off); off += dims[l] * dims[l + 1] + dims[l + 1]
-    for l in reversed(range(len(acts))):
-        i, o = dims[l], dims[l + 1]
-        y = hs[l + 1]
-        d = d * (y > 0) if acts[l] == "relu" else d * (1 - y * y) if acts[l] == "tanh" else d
-        W = params[offs[l]:offs[l] + i * o].reshape((o, i), order="F").astype(np.float64)
-        g[offs[l]:offs[l] + i * o] = (d @ hs[l].T).reshape(-1, order="F")
-        g[offs[l] + i * o:offs[l] + i * o + o] = d.sum(axis=1)
-        d = W.T @ d
-    return g, d
 
 
 @pytest.mark.parametrize("dims,acts,B", [([3, 32, 1], ["tanh", "identity"], 37), ([2, 32, 1], ["relu", "tanh"], 256), ([4, 256, 256, 1], ["relu", "relu", "identity"], 256),
