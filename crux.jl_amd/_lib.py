@@ -166,6 +166,11 @@ SIGNATURES = {
     "crux_cql_conservative": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp, vp, vp]),
     "crux_gradient_penalty": (i32, [vp, vp, vp, i64, f32, f32, i32, u64, u64, vp]),
     "crux_iq_step": (i32, [vp, vp, i64, f32, i32, f32, i32, f32, u64, u64, vp, vp]),
+    "crux_offgail_d_step": (i32, [vp, P(vp), i32, i64, u64, u64, vp]),
+    "crux_offgail_round": (i32, [vp, P(vp), i32, i64, i32, vp, u64, u64, vp]),
+    "crux_offgail_reward": (i32, [vp, vp, i32, vp]),
+    "crux_offgail_gather": (i32, [P(vp), i32, i64, u64, u64, vp]),
+    "crux_adril_relabel": (i32, [vp, i64, i64, i64, P(i64), P(i64)]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

@@ -39,7 +39,9 @@ from .off_policy import (  # noqa: F401
 from .batch import *   # noqa: F401,F403
 from .batch import BatchSAC, CQL, UniformBox, _solve_batch_ac, cql_alpha_loss, cql_critic_loss   # noqa: F401
 from .il_off_policy import *   # noqa: F401,F403
-from .il_off_policy import OnlineIQLearn, SQIL, _value_training_iq, gradient_penalty, iq_loss, sqil_callback   # noqa: F401
+from .il_off_policy import (  # noqa: F401
+    AdRIL, OffPolicyGAIL, OnlineIQLearn, SQIL, _value_training_iq, adril_relabel_, gradient_penalty, iq_loss, offgail_d_step_, offgail_gather, offgail_reward_, offgail_round_,
+    sqil_callback)
 from .on_policy import _solve_on_policy
 from . import core, on_policy, imitation, off_policy, batch, il_off_policy   # noqa: F401
 

@@ -1,14 +1,20 @@
-"""il_off_policy.py -- off-policy imitation learning: OnlineIQLearn and SQIL (src/model_free/il/iqlearn.jl, il/sqil.jl) and gradient_penalty
-(src/extras/gradient_penalty.jl).
+"""il_off_policy.py -- off-policy imitation learning: OnlineIQLearn and SQIL (src/model_free/il/iqlearn.jl, il/sqil.jl), gradient_penalty
+(src/extras/gradient_penalty.jl), OffPolicyGAIL (il/off_policy_gail.jl) and AdRIL (il/AdRIL.jl).
 
 Both constructors add a normalised copy of the demonstrations to an off-policy solver as an extra buffer drawn at buffer_fractions = [1/2, 1/2]. The staging
 minibatch is then laid out by split_batches as B_p buffer rows followed by B - B_p demo rows, so where the reference marks demo rows with a Bool :expert column
 (iq_callback, required_columns=[:expert]) this module passes B_p to the critic step instead: the reference's column is false on every buffer row and true on every
-demo row. No buffer column is added. iq_loss's critic step, the penalty and its second-order pass are HIP (csrc/iq.hip: crux_iq_step, crux_gradient_penalty)."""
+demo row. No buffer column is added. iq_loss's critic step, the penalty and its second-order pass are HIP (csrc/iq.hip: crux_iq_step, crux_gradient_penalty).
+
+OffPolicyGAIL's callback (discriminator epochs on freshly drawn rows of every source, then the reward rewrite of the staging batch) is one C call,
+crux_offgail_round; AdRIL's rewrite of the ring's rewards is crux_adril_relabel, run on the device through OffPolicySolver.post_sample_device (csrc/gail_off.hip)."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib as L
-from .core import ContinuousSpace, DiscreteNetwork, DiscreteSpace, _Loss, _ensure_opt, _vp, copy_buffer, normalize_, split_batches
+from .core import (ContinuousNetwork, ContinuousSpace, DiscreteNetwork, DiscreteSpace, ExperienceBuffer, TrainingParams, _Loss, _ensure_opt, _vp, copy_buffer, normalize_,
+                   split_batches)
 from .off_policy import SAC, SoftQ
 
 
@@ -138,5 +144,109 @@ def SQIL(pi, S, demo, normalize_demo=True, solver=SAC, **kw):
         raise ValueError("SQIL requires a reward value for the demonstrations")
     d = _demo_buffer(demo, S, _space(pi, demo), normalize_demo)
     sv = solver(pi=pi, S=S, post_sample_callback=sqil_callback, extra_buffers=[d], buffer_fractions=[0.5, 0.5], **kw)
+    sv.demo = d
+    return sv
+
+
+def _handles(bufs):
+    return (C.c_void_p * len(bufs))(*[b.h for b in bufs])
+
+
+def offgail_d_step_(D, sources, Bd, seed, counter):
+    """One discriminator step of OffPolicyGAIL (off_policy_gail.jl:65-98) over `sources` = [demo, buffer, ndas...]: returns the raw info row (crux_offgail_d_step)."""
+    raw = np.zeros(L.INFO_N, np.float32)
+    D.ctx.check(D.ctx.lib.crux_offgail_d_step(D.h, _handles(sources), len(sources), int(Bd), int(seed), int(counter), _vp(raw)))
+    return raw
+
+
+def offgail_round_(D, sources, Bd, d_epochs, batch, seed, counter0):
+    """GAIL_callback (off_policy_gail.jl:64-125) as one call: d_epochs discriminator steps, then batch[:r] rewritten; returns the last step's raw info row."""
+    raw = np.zeros(L.INFO_N, np.float32)
+    D.ctx.check(D.ctx.lib.crux_offgail_round(D.h, _handles(sources), len(sources), int(Bd), int(d_epochs), batch.h, int(seed), int(counter0), _vp(raw)))
+    return raw
+
+
+def offgail_reward_(D, batch, K):
+    """batch[:r] .= sum((log.(softmax(D(s, a)) .+ 1f-5) .- log.(1f0 .- softmax(D(s, a)) .+ 1f-5)) .* w, dims=1) (off_policy_gail.jl:121-124); returns mean(r)."""
+    out = np.zeros(1, np.float32)
+    D.ctx.check(D.ctx.lib.crux_offgail_reward(D.h, batch.h, int(K), _vp(out)))
+    return float(out[0])
+
+
+def offgail_gather(sources, Bd, seed, counter):
+    """The columns X = vcat(s, a) one discriminator step with (seed, counter) forms, source k in columns [k Bd, (k + 1) Bd) (crux_offgail_gather)."""
+    ctx, K = sources[0].ctx, len(sources)
+    sd = sources[0].obs_dim + sources[0].act_dim
+    X = np.empty((sd, K * int(Bd)), np.float32, order="F")
+    d = ctx.alloc(4 * X.size)
+    try:
+        ctx.check(ctx.lib.crux_offgail_gather(_handles(sources), K, int(Bd), int(seed), int(counter), d))
+        ctx.d2h(d, X)
+    finally:
+        ctx.free(d)
+    return X
+
+
+def adril_relabel_(buf, n_new, buffer_init, dN):
+    """AdRIL_callback (AdRIL.jl:39-50) on the ring after the push of its n_new newest rows (crux_adril_relabel); returns (max_i, k)."""
+    mx, k = C.c_int64(), C.c_int64()
+    buf.ctx.check(buf.ctx.lib.crux_adril_relabel(buf.h, int(n_new), int(buffer_init), int(dN), C.byref(mx), C.byref(k)))
+    return mx.value, k.value
+
+
+def OffPolicyGAIL(pi, S, demo, D, ndas=(), normalize_demo=True, solver=SAC, d_opt=None, **kw):
+    """OffPolicyGAIL(; π, S, 𝒟_demo, 𝒟_ndas=[], normalize_demo=true, D::ContinuousNetwork, solver=SAC, d_opt=(epochs=5,), kwargs...) (off_policy_gail.jl:18-129):
+    `solver` with post_batch_callback = GAIL_callback. After every rand! of value_training the callback runs d_opt.epochs discriminator steps, each over
+    d_opt.batch_size freshly drawn rows of the demonstrations, the solver's buffer and every NDA buffer (logitcrossentropy over 2 + N_nda classes), and then
+    replaces the staging batch's rewards by the discriminator's: one crux_offgail_round. Draws: key solver.sample_seed, counters round * epochs + epoch with a
+    round counter kept on the solver (`gail_rounds`, continued across solve calls), streams 16 + k (include/crux_rng.h).
+
+    Works with every solver whose value_training honours post_batch_callback (SAC, DDPG / TD3, DQN / SoftQ). Deviation: normalize_demo=False with NDA buffers
+    is allowed and leaves them as they are; the reference assigns `false` to 𝒟_ndas[i] in that case (:44), which fails at the first rand!."""
+    d = dict(d_opt or {}); d.setdefault("epochs", 5); d.setdefault("name", "discriminator_")
+    dp = TrainingParams(loss=None, **d)                                                                  # loss = () -> nothing (:31)
+    ndas = list(ndas)
+    K = 2 + len(ndas)
+    if not isinstance(D, ContinuousNetwork):
+        raise TypeError("OffPolicyGAIL: D must be a ContinuousNetwork")
+    sd = demo.obs_dim + demo.act_dim
+    if D.network.dims[0] != sd or D.network.dims[-1] != K:
+        raise ValueError("OffPolicyGAIL: D must map vcat(s, a) (%d) to 2 + length(ndas) = %d outputs, not %d -> %d" % (sd, K, D.network.dims[0], D.network.dims[-1]))
+    A = _space(pi.A if hasattr(pi, "A") else pi, demo)
+    dm = _demo_buffer(demo, S, A, normalize_demo)
+    nd = [_demo_buffer(b, S, A, normalize_demo) for b in ndas]
+    sv = solver(pi=pi, S=S, **kw)
+    if sv.buffer.isprioritized():
+        raise NotImplementedError("OffPolicyGAIL with a prioritized buffer: the discriminator's rand! would go through prioritized_sample! and rewrite :weight")
+    sv.gail_rounds = 0
+
+    def GAIL_callback(batch, S=None, info=None):
+        _ensure_opt(D, dp)
+        raw = offgail_round_(D, [dm, sv.buffer] + nd, dp.batch_size, dp.epochs, batch, sv.sample_seed, sv.gail_rounds * dp.epochs)
+        sv.gail_rounds += 1
+        if info is not None:
+            info[dp.name + "loss"] = float(raw[L.INFO["loss"]]); info[dp.name + "grad_norm"] = float(raw[L.INFO["grad_norm"]])
+    sv.post_batch_callback = GAIL_callback
+    sv.discriminator, sv.d_opt, sv.demo, sv.ndas = D, dp, dm, nd
+    return sv
+
+
+def AdRIL(pi, S, demo, dN=50, solver=SAC, normalize_demo=True, expert_frac=0.5, buffer_size=1000, buffer_init=0, buffer=None, **kw):
+    """AdRIL(; π, S, ΔN=50, solver=SAC, 𝒟_demo, normalize_demo=true, expert_frac=0.5, buffer_size=1000, buffer_init=0, buffer=ExperienceBuffer(S, A, buffer_size, [:i]),
+    kwargs...) (AdRIL.jl:20-64): `solver` with the demonstrations, which must carry :r, as an extra buffer at [1 - expert_frac, expert_frac] and AdRIL_callback after every
+    steps!: fresh rows get reward 0, rows at least ΔN iterations old -1/k. The rewrite covers the whole ring, so it runs on the device (post_sample_device ->
+    crux_adril_relabel) instead of through post_sample_callback's host copies."""
+    if not demo.haskey("r"):
+        raise ValueError("AdRIL requires a reward value for the demonstrations")
+    A = _space(pi.A if hasattr(pi, "A") else pi, demo)
+    d = _demo_buffer(demo, S, A, normalize_demo)
+    if buffer is None:
+        buffer = ExperienceBuffer(S, A, buffer_size, ["i"], ctx=demo.ctx)
+    sv = solver(pi=pi, S=S, dN=dN, extra_buffers=[d], buffer_fractions=[1 - expert_frac, expert_frac], buffer_size=buffer_size, buffer_init=buffer_init, buffer=buffer, **kw)
+    b0 = int(buffer_init)
+
+    def AdRIL_callback(solver_, n_new, info):
+        adril_relabel_(solver_.buffer, n_new, b0, dN)
+    sv.post_sample_device = AdRIL_callback
     sv.demo = d
     return sv

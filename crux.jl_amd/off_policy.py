@@ -53,6 +53,7 @@ class OffPolicySolver:
         self.tau, self.weighted_loss, self.sample_seed = float(tau), bool(weighted_loss), int(sample_seed)
         self.target_update, self.priority_fn = target_update, priority_fn
         self.post_sample_callback, self.post_batch_callback, self.pre_train_callback = post_sample_callback, post_batch_callback, pre_train_callback
+        self.post_sample_device = None        # (S, n_new, info) after every steps!, on the ring as the rollout left it: relabels that stay on the device (AdRIL); None = nothing
         self.extra_buffers = list(extra_buffers)
         self.buffer_fractions = list(buffer_fractions) if buffer_fractions is not None else ([1.0] if not self.extra_buffers else None)
         if self.extra_buffers and (self.buffer_fractions is None or len(self.buffer_fractions) != 1 + len(self.extra_buffers)):
@@ -394,7 +395,7 @@ def _solve_small_dqn(solver, D, s, gamma, i, stop):
     """The iterations i, i + dN, ..., stop of solve(::OffPolicySolver) for a small DQN as a few launches of the one-workgroup solve kernel (cruxhip.h:
     crux_dqn_small_solve); returns the first iteration index it did NOT run (== i when the configuration needs the call-by-call loop)."""
     pe, pi, buf = solver.agent.pi_explore, solver.agent.pi, solver.buffer
-    if not (s.h is not None and solver.fused_epochs and solver.target_fn == "dqn" and not solver.custom_seams() and solver.post_sample_callback is None and solver.pre_train_callback is None
+    if not (s.h is not None and solver.fused_epochs and solver.target_fn == "dqn" and not solver.custom_seams() and solver.post_sample_callback is None and solver.post_sample_device is None and solver.pre_train_callback is None
             and solver.log is None and solver.interaction_storage is None and isinstance(pe, EpsGreedyPolicy) and isinstance(pi, DiscreteNetwork)
             and not buf.isprioritized() and not solver.weighted_loss and max(pi.network.dims) < 128 and D.capacity <= 256 and s.n_envs <= 4 and solver.dN % s.n_envs == 0 and i <= stop):
         return i
@@ -420,6 +421,8 @@ def _solve_small_dqn(solver, D, s, gamma, i, stop):
 def _post_sample(solver, n, info):
     """steps!(...; cb = D -> S.post_sample_callback(D, S=S, info=info)) (off_policy.jl:125,138; sampler.jl:151): the callback sees the n rows this steps!
     produced (host copies of the ring's newest rows, oldest first) and whatever it changes in them is written back into the ring."""
+    if solver.post_sample_device is not None:
+        solver.post_sample_device(solver, n, info)
     if solver.post_sample_callback is None:
         return
     buf = solver.buffer
@@ -466,8 +469,8 @@ def _solve_off_policy(solver, mdp):
         steps_(s, solver.buffer, Nsteps=solver.dN, explore=True, i=i, want_info=False)                # :138 (its info is not used by this loop)
         it_info = {}
         # asynchronous chains when nothing on the host looks at an iteration's result before the next one starts: no logger, no callbacks, built-in seams
-        solver._async_now = (solver.async_training and solver.log is None and solver.post_sample_callback is None and solver.pre_train_callback is None
-                             and not solver.custom_seams() and solver.fused_epochs and not getattr(solver, "_async_unsupported", False) and solver.interaction_storage is None)
+        solver._async_now = (solver.async_training and solver.log is None and solver.post_sample_callback is None and solver.post_sample_device is None
+                             and solver.pre_train_callback is None and not solver.custom_seams() and solver.fused_epochs and not getattr(solver, "_async_unsupported", False) and solver.interaction_storage is None)
         _post_sample(solver, solver.dN, it_info)                                                      # :138 cb = D -> S.post_sample_callback(D, S=S, info=info)
         if solver.interaction_storage is not None:                                                    # :138 store=S.interaction_storage (after the callback, sampler.jl:150-151)
             solver.interaction_storage.append(solver.buffer.minibatch((first_ + np.arange(solver.dN)) % solver.buffer.capacity + 1))

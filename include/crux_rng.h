@@ -34,6 +34,11 @@ enum {
                                xhat_j = eps_j xtilde_j + (1 - eps_j) x_j (cruxhip.h, IQ paragraph); OnlineIQLearn: seed = noise_seed, counter = i epochs + epoch */
 };
 
+/* Streams of CRUX_RNG_SAMPLE. A value_training epoch with Philox counter c draws its staging minibatch with rand!: source k of the solver (the buffer, then the
+ * extra buffers) uses stream k and counter c B + j for row j. OffPolicyGAIL's discriminator draws (cruxhip.h, crux_offgail_d_step) use the same purpose with stream
+ * 16 + k for source k (demo, the solver's buffer, NDA 1..) and counter (c0 + e) Bd + j for row j of discriminator epoch e, c0 = the solver's round counter times
+ * d_epochs: streams 16.. are never used by rand! (at most 16 sources), so no discriminator draw coincides with a staging draw of the same key. */
+
 typedef struct { uint32_t v[4]; } crux_u32x4;
 
 CRUX_HD uint32_t crux_mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }

@@ -647,6 +647,36 @@ int32_t crux_gradient_penalty(crux_mlp* net, const float* d_x, const float* d_xt
 int32_t crux_iq_step(crux_mlp* q, crux_buffer* batch, int64_t n_policy, float gamma_iq, int32_t reg, float alpha_reg, int32_t gp, float lambda_gp,
                      uint64_t seed, uint64_t counter, float* info_out, float* iq_out);
 
+/* OffPolicyGAIL (src/model_free/il/off_policy_gail.jl) and AdRIL (src/model_free/il/AdRIL.jl) on the dense engine ---------------------------------------------
+ * sources: K = 2 + N_nda buffers -- the demonstrations, the solver's buffer, then the NDA buffers (hcat(D_demo_batch, D_batch, D_ndas_batch...), :78). D maps
+ * vcat(s, a) (obs_dim + act_dim; one-hot actions enter as 0/1) to K classes. One discriminator step (:65-98): Bd rows of every source, drawn on the device with
+ * crux_uniform_sample's draw over the source's length -- id = (Philox(seed, counter Bd + j, 16 + k, SAMPLE).v[0] len_k) >> 32 (crux_rng.h) -- form NC = K Bd
+ * columns, source k in [k Bd, (k + 1) Bd); L = Flux.Losses.logitcrossentropy(D(x), y) = mean_j (logsumexp z_j - z_j[label_j]) with the label of a column = its
+ * source; then train! (training.jl:13-25): gradient, norm, NaN => CRUX_ENAN with no update ("NaN detected!"), Adam. Only the s and a columns of the sources are
+ * read. A NaN in a gathered value surfaces as CRUX_ENAN. info_out (host [CRUX_INFO_N]): LOSS, GRAD_NORM. No float atomics: identical calls give identical bits.
+ * CRUX_EINVAL: K < 2; D's widths; sources that differ in obs_dim, act_dim or action kind from each other or from batch; an empty source; Bd < 1.
+ * CRUX_EUNSUP: a prioritized source (prioritized_sample! and its :weight rewrite); K Bd > 2^20; K > 16.                                                        */
+int32_t crux_offgail_d_step(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64_t Bd, uint64_t seed, uint64_t counter, float* info_out);
+/* The whole GAIL_callback (:64-125): d_epochs steps at counters counter0 .. counter0 + d_epochs - 1, then the reward rewrite of batch, enqueued back to back with one
+ * host synchronisation at the end. Bit-identical to d_epochs calls of crux_offgail_d_step followed by crux_offgail_reward. info_out: the LAST step's row (the
+ * reference passes one info Dict to every train!, :98, training.jl:22-24). A NaN norm in step e stops the round there: that step and the later ones update
+ * nothing, batch[:r] is not rewritten, info_out is step e's row, CRUX_ENAN.                                                                                     */
+int32_t crux_offgail_round(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64_t Bd, int32_t d_epochs, crux_buffer* batch, uint64_t seed, uint64_t counter0,
+                           float* info_out);
+/* The reward rewrite (:121-124) over the B rows of batch: p = softmax(D(vcat(s, a))), r = sum_k w_k (log(p_k + 1f-5) - log(1f0 - p_k + 1f-5)) with
+ * w = [1, 0, -1/N_nda, ...] (N_nda = K - 2), operand order as written, every operation rounded on its own; batch[:r] = r. *mean_r (host, may be NULL) = mean(r). */
+int32_t crux_offgail_reward(crux_mlp* D, crux_buffer* batch, int32_t K, float* mean_r);
+/* The gather of one discriminator step alone (tests, debugging): d_X (device [(obs_dim + act_dim) x K Bd]) = the columns crux_offgail_d_step(seed, counter) forms. */
+int32_t crux_offgail_gather(crux_buffer* const* sources, int32_t K, int64_t Bd, uint64_t seed, uint64_t counter, float* d_X);
+/* AdRIL_callback (AdRIL.jl:39-50). The reference runs it BEFORE push! (sampler.jl:150-152); a rollout of this library has already written its n_new rows into the
+ * ring, so the call is defined on the ring after the push and leaves what the reference has after its push: the n_new newest rows get r = 0 (D[:r] .= 0, :40); with
+ * max_i = maximum(ring[:i]) over the len rows and k = Int((max_i - buffer_init) / dN) - 1 every other row gets r = -1/k when i <= max_i - dN and 0 otherwise (the
+ * Float64 quotient rounded into the Float32 column). len <= n_new (the reference's buffer was empty, :42): only the zeroing, *k_out = 0. k == 0 gives -Inf, as in the
+ * reference (reachable with buffer_init > 0, depending on the :i values the pre-fill wrote; AdRIL's default buffer_init is 0). (max_i - buffer_init) % dN != 0 is the
+ * reference's InexactError: CRUX_EINVAL, ring untouched. A ring without :i: CRUX_EINVAL. The maximum is taken over the rows still in the ring: rows a wrapping push
+ * has overwritten do not count (they would in the reference, where the callback still sees them). One launch pair, no host copy of a column.                    */
+int32_t crux_adril_relabel(crux_buffer* ring, int64_t n_new, int64_t buffer_init, int64_t dN, int64_t* max_i_out, int64_t* k_out);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer

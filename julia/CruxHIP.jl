@@ -537,6 +537,41 @@ function iq_step!(Q::HipNetwork, mb::HipBuffer, n_policy::Integer, γ::Float32, 
     info, iq
 end
 
+# OffPolicyGAIL (src/model_free/il/off_policy_gail.jl): sources = [𝒟_demo, 𝒮.buffer, 𝒟_ndas...]; D maps vcat(s, a) to 2 + N_nda classes. The draws of discriminator
+# epoch e of round n are Philox(sample_seed, (n d_epochs + e) B + j, 16 + k, SAMPLE) for row j of source k (include/crux_rng.h)
+source_handles(sources::Vector{HipBuffer}) = Ptr{Cvoid}[b.h for b in sources]
+function offgail_d_step!(D::HipNetwork, sources::Vector{HipBuffer}, B::Integer, seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N))      # train!(D, logitcrossentropy(D(x), y)) (:98)
+    hs = source_handles(sources)
+    GC.@preserve hs check(D.ctx, ccall((:crux_offgail_d_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Int32, Int64, UInt64, UInt64, Ptr{Float32}),
+                                       D.h, hs, Int32(length(hs)), B, seed, ctr, info))
+    info
+end
+function offgail_reward!(D::HipNetwork, mb::HipBuffer, K::Integer)                                                                           # 𝒟[:r] .= sum((log.(...) .- log.(...)) .* w, dims=1) (:121-124)
+    out = zeros(Float32, 1)
+    check(D.ctx, ccall((:crux_offgail_reward, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float32}), D.h, mb.h, Int32(K), out))
+    out[1]
+end
+function offgail_gather(sources::Vector{HipBuffer}, B::Integer, seed::UInt64, ctr::UInt64, d_X::Ptr{Float32})                                # the columns x of one step (:78-81), for inspection
+    hs = source_handles(sources)
+    GC.@preserve hs check(sources[1].ctx, ccall((:crux_offgail_gather, LIB), Int32, (Ptr{Ptr{Cvoid}}, Int32, Int64, UInt64, UInt64, Ptr{Float32}), hs, Int32(length(hs)), B, seed, ctr, d_X))
+    d_X
+end
+"""GAIL_callback of OffPolicyGAIL (:64-125) as one call: `d_epochs` discriminator steps and the reward rewrite of the staging minibatch `mb`. `round` is the
+number of callbacks this solver has run so far. Set as `𝒮.post_batch_callback = (𝒟; info, kw...) -> OffPolicyGAIL_callback!(D, sources, B, epochs, 𝒟, seed, round; info)`."""
+function OffPolicyGAIL_callback!(D::HipNetwork, sources::Vector{HipBuffer}, B::Integer, d_epochs::Integer, mb::HipBuffer, seed::UInt64, round::Integer; info=Dict(), name="discriminator_")
+    raw = zeros(Float32, INFO_N); hs = source_handles(sources)
+    GC.@preserve hs check(D.ctx, ccall((:crux_offgail_round, LIB), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Ptr{Cvoid}, UInt64, UInt64, Ptr{Float32}),
+                                       D.h, hs, Int32(length(hs)), B, Int32(d_epochs), mb.h, seed, UInt64(round * d_epochs), raw))
+    info[string(name, "loss")] = raw[1]; info[string(name, "grad_norm")] = raw[2]
+    info
+end
+"""AdRIL_callback of AdRIL (src/model_free/il/AdRIL.jl:39-50) on the ring AFTER the push of its `n_new` newest rows; returns (max_i, k)."""
+function AdRIL_relabel!(ring::HipBuffer, n_new::Integer, buffer_init::Integer, ΔN::Integer)
+    mx = Ref{Int64}(0); k = Ref{Int64}(0)
+    check(ring.ctx, ccall((:crux_adril_relabel, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Int64, Ref{Int64}, Ref{Int64}), ring.h, n_new, buffer_init, ΔN, mx, k))
+    mx[], k[]
+end
+
 # ---------------------------------------------------------------------------------------------------- user-written losses and the regularizer
 # The reference differentiates ANY loss(π, 𝒫, 𝒟) with Zygote (training.jl:16-18). The library's fast paths cover a closed list (loss_id above);
 # everything else composes the explicit pullback: forward with cached activations -> the user's d(loss)/d(output) -> parameter gradients ->
