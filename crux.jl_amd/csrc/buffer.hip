@@ -436,14 +436,31 @@ int32_t crux_per_update(crux_buffer* b, const int64_t* I, const void* v, int32_t
   if (!b->prioritized) return crux_fail(c, CRUX_EINVAL, "update_priorities!: buffer is not prioritized");
   if (n == 0) return CRUX_OK;
   for (int64_t j = 0; j < n; ++j) if (I[j] < 0 || I[j] >= b->capacity) return crux_fail(c, CRUX_EINVAL, "update_priorities!: index %lld out of range", (long long)I[j]);
-  const size_t ib = ((8 * (size_t)n + 255) / 256) * 256, vb = (v_is_f64 ? 8 : 4) * (size_t)n;
-  char* sc = (char*)crux_scratch(c, ib + vb + 256);
+  // duplicate indices: the reference loop is sequential, the last write of a repeated row wins. PerUpdateOp resolves that itself for n <= 512 (the sampled minibatch); a larger
+  // call is walked here: when a row repeats, the last occurrence of every row is sent once more, alone, as a second pass behind the first (distinct rows: nothing races), and
+  // overwrites whatever the first pass's writers left there. The first pass still sees every value: max / min track them all (:297-298).
+  const size_t esz = v_is_f64 ? 8 : 4;
+  std::vector<int64_t> wI; std::vector<char> wv;
+  if (n > 512) {
+    std::vector<uint64_t> seen(((size_t)b->capacity + 63) / 64, 0); bool dup = false;
+    for (int64_t j = 0; j < n && !dup; ++j) { uint64_t& w = seen[(size_t)I[j] >> 6]; const uint64_t m = 1ull << (I[j] & 63); dup = (w & m) != 0; w |= m; }
+    if (dup) { std::fill(seen.begin(), seen.end(), 0); wI.reserve((size_t)n); wv.reserve(esz * (size_t)n);
+      for (int64_t j = n - 1; j >= 0; --j) { uint64_t& w = seen[(size_t)I[j] >> 6]; const uint64_t m = 1ull << (I[j] & 63); if (w & m) continue; w |= m;
+        wI.push_back(I[j]); const char* src = (const char*)v + esz * (size_t)j; wv.insert(wv.end(), src, src + esz); } }
+  }
+  const int64_t nw = (int64_t)wI.size();
+  const size_t ib = ((8 * (size_t)n + 255) / 256) * 256, vb = ((esz * (size_t)n + 255) / 256) * 256, wib = ((8 * (size_t)nw + 255) / 256) * 256;
+  char* sc = (char*)crux_scratch(c, ib + vb + wib + esz * (size_t)nw + 256);
   if (!sc) return crux_fail(c, CRUX_ENOMEM, "update_priorities!: scratch");
   HIPCHK(c, hipMemcpyAsync(sc, I, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(sc + ib, v, vb, hipMemcpyHostToDevice, c->stream));
-  // duplicate indices: the reference loop lets the last write win; values for duplicated rows are equal in every call site
+  HIPCHK(c, hipMemcpyAsync(sc + ib, v, esz * (size_t)n, hipMemcpyHostToDevice, c->stream));
   CRUX_RUN(c, PerUpdateOp, OP_PER_UPDATE, k_per_update, grid_for(n), 256, c->stream, b->priorities, b->pminmax, (const int64_t*)sc, v_is_f64 ? (const double*)(sc + ib) : (const double*)nullptr, v_is_f64 ? (const float*)nullptr : (const float*)(sc + ib), (const float*)nullptr, b->alpha, n);
   int32_t rc = crux_launch_check(c, "k_per_update"); if (rc) return rc;
+  if (nw > 0) { char* ws = sc + ib + vb;
+    HIPCHK(c, hipMemcpyAsync(ws, wI.data(), 8 * (size_t)nw, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ws + wib, wv.data(), esz * (size_t)nw, hipMemcpyHostToDevice, c->stream));
+    CRUX_RUN(c, PerUpdateOp, OP_PER_UPDATE, k_per_update, grid_for(nw), 256, c->stream, b->priorities, b->pminmax, (const int64_t*)ws, v_is_f64 ? (const double*)(ws + wib) : (const double*)nullptr, v_is_f64 ? (const float*)nullptr : (const float*)(ws + wib), (const float*)nullptr, b->alpha, nw);
+    rc = crux_launch_check(c, "k_per_update(last occurrences)"); if (rc) return rc; }
   { bool in_tree = true; for (int64_t j = 0; j < n; ++j) in_tree = in_tree && I[j] < b->elements;      // rows beyond length(b) are outside the current tree
     if (!in_tree) { b->per_full_dirty = true; b->cumsum_valid = false; } else { rc = crux_per_touched(b, (const int64_t*)sc, n, false); if (rc) return rc; } }                     // :299 cumsum_valid = false; only the touched leaves are re-summed
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -173,11 +173,13 @@ int64_t* crux_buffer_indices_ptr(crux_buffer* b);
 int32_t crux_buffer_indices(const crux_buffer* b, int64_t* out, int64_t n);
 
 /* prioritized replay (src/experience_buffer.jl:38-50,290-301,324-349) ---------------------------- */
-/* update_priorities!(b, I, v): v Float64 (v_is_f64=1) or Float32.                                 */
+/* update_priorities!(b, I, v): v Float64 (v_is_f64=1) or Float32. Exact at any n: where a row repeats in I, the value of its LAST occurrence is stored, like the
+ * reference's sequential loop (:290-301), and max / min see every value. */
 int32_t crux_per_update(crux_buffer* b, const int64_t* I, const void* v, int32_t v_is_f64, int64_t n);
 /* same with device-resident ids (int64) and Float32 values (the td-error path, off_policy.jl:83). Duplicate ids: the reference's scalar loop lets the LAST
  * occurrence win (:296-298); that order is reproduced exactly for n <= 512. For 512 < n the winner among duplicates is unspecified -- harmless when duplicated
- * ids carry equal values, which holds for td_error of the same row (the only caller inside the library); pass unique ids or equal values otherwise. */
+ * ids carry equal values, which holds for td_error of the same row (the only caller inside the library); pass unique ids or equal values otherwise, or
+ * take the host entry above, which is exact at any n. */
 int32_t crux_per_update_device(crux_buffer* b, const int64_t* d_ids, const float* d_v, int64_t n);
 /* prioritized_sample!(target, source; i, B): `rands` = B Float64 uniforms (NULL => Philox draw with
  * counter `i`). Writes ids into target.indices, IS weights into source[:weight], gathers rows.     */
