@@ -171,6 +171,9 @@ SIGNATURES = {
     "crux_offgail_reward": (i32, [vp, vp, i32, vp]),
     "crux_offgail_gather": (i32, [P(vp), i32, i64, u64, u64, vp]),
     "crux_adril_relabel": (i32, [vp, i64, i64, i64, P(i64), P(i64)]),
+    "crux_orthogonal_reg": (i32, [vp, f32, i32, vp]),
+    "crux_advil_d_step": (i32, [vp, vp, vp, f32, f32, u64, u64, vp, vp]),
+    "crux_advil_actor_step": (i32, [vp, vp, vp, f32, f32, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

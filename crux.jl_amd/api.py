@@ -42,8 +42,11 @@ from .il_off_policy import *   # noqa: F401,F403
 from .il_off_policy import (  # noqa: F401
     AdRIL, OffPolicyGAIL, OnlineIQLearn, SQIL, _value_training_iq, adril_relabel_, gradient_penalty, iq_loss, offgail_d_step_, offgail_gather, offgail_reward_, offgail_round_,
     sqil_callback)
+from .il_batch import *   # noqa: F401,F403
+from .il_batch import AdVIL, advil_actor_step_, advil_d_loss, advil_d_step_, advil_pi_loss   # noqa: F401
+from .core import OrthogonalRegularizer, orthogonal_regularizer   # noqa: F401
 from .on_policy import _solve_on_policy
-from . import core, on_policy, imitation, off_policy, batch, il_off_policy   # noqa: F401
+from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch   # noqa: F401
 
 
 def solve(solver, mdp=None):  # noqa: F811

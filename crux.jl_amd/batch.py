@@ -5,13 +5,17 @@ Every train! is one C call on a minibatch gathered into a staging buffer on the 
 
 Randomness (include/crux_rng.h, include/cruxhip.h CQL paragraph): the epoch shuffle is crux_buffer_shuffle(a_opt.shuffle_seed, epoch); minibatch g
 (S.grad_steps, which continues across solve calls) takes the noise counters 8g + 0 (CQL alpha samples), + 1 (SAC temperature), + 2 (sac_target),
-+ 3 (CQL critic samples), + 4 (actor) of solver.noise_seed. The reference iterates param_optimizers in Dict order, which is unspecified; here the
-order is fixed as CQL alpha first, then the SAC temperature (both updates are independent once the draws are counter-based)."""
++ 3 (CQL critic samples), + 4 (actor), + 5 (AdVIL's gradient-penalty draws) of solver.noise_seed. The reference iterates param_optimizers in Dict order, which is unspecified; here the
+order is fixed as CQL alpha first, then the SAC temperature (both updates are independent once the draws are counter-based).
+
+AdVIL (il_batch.py) is the loop's other shape: a single ContinuousNetwork critic trained without a target (advil_d_loss) and a deterministic actor (advil_pi_loss
+with an OrthogonalRegularizer), in the reference's order -- critic step first, then the actor step on the same minibatch with the updated critic (batch.jl:66-78)."""
 import numpy as np
 
 from . import _lib as L
-from .core import (ActorCritic, ContinuousNetwork, DoubleNetwork, GaussianPolicy, ParamVector, PolicyParams, TrainingParams, _Loss,
+from .core import (ActorCritic, ContinuousNetwork, DoubleNetwork, GaussianPolicy, OrthogonalRegularizer, ParamVector, PolicyParams, TrainingParams, _Loss,
                    _ensure_opt, _vp, buffer_like, clone_policy, copy_buffer, discount, normalize_, polyak_average_, shuffle_device_)
+from .il_batch import advil_actor_step_, advil_d_loss, advil_d_step_, advil_pi_loss
 from .imitation import BatchSolver
 from .logging import aggregate_info
 from .off_policy import double_Q_loss, sac_actor_loss, sac_temp_loss
@@ -19,7 +23,7 @@ from .off_policy import double_Q_loss, sac_actor_loss, sac_temp_loss
 cql_alpha_loss, cql_critic_loss = _Loss("cql_alpha"), _Loss("cql_critic")     # batch/cql.jl: cql_alpha_loss, cql_critic_loss() = double_Q_loss + conservative_loss
 
 # noise counter offsets inside the block of 8 of one minibatch
-CTR_CQL_ALPHA, CTR_SAC_TEMP, CTR_TARGET, CTR_CQL_CRITIC, CTR_ACTOR, CTR_BLOCK = 0, 1, 2, 3, 4, 8
+CTR_CQL_ALPHA, CTR_SAC_TEMP, CTR_TARGET, CTR_CQL_CRITIC, CTR_ACTOR, CTR_ADVIL_GP, CTR_BLOCK = 0, 1, 2, 3, 4, 5, 8
 
 
 class UniformBox:
@@ -37,6 +41,22 @@ def _check_actor_critic(pi, who):
             and isinstance(pi.C.N1, ContinuousNetwork) and isinstance(pi.C.N2, ContinuousNetwork)):
         raise TypeError("%s: pi must be ActorCritic(GaussianPolicy, DoubleNetwork(ContinuousNetwork, ContinuousNetwork))" % who)
     # (a SquashedGaussianPolicy actor passes this test and is refused by the library -- CRUX_EUNSUP -- at the first step, as in SAC)
+
+
+def _check_advil(solver):
+    """The shape AdVIL builds (AdVIL.jl:46-53): c_opt without a target_fn, a deterministic actor and a single critic."""
+    pi, a_opt, c_opt = solver.agent.pi, solver.a_opt, solver.c_opt
+    if not (isinstance(pi, ActorCritic) and isinstance(pi.A, ContinuousNetwork) and isinstance(pi.C, ContinuousNetwork)):
+        raise TypeError("BatchSolver: advil_pi_loss / advil_d_loss need pi = ActorCritic(ContinuousNetwork, ContinuousNetwork)")
+    if a_opt.loss is not advil_pi_loss or c_opt is None or c_opt.loss is not advil_d_loss:
+        raise NotImplementedError("BatchSolver: advil_pi_loss and advil_d_loss are implemented as a pair (a_opt.loss, c_opt.loss)")
+    if solver.target_fn is not None:
+        raise NotImplementedError("BatchSolver: advil_d_loss takes no target (target_fn must be None)")
+    if a_opt.regularizer is not None and not isinstance(a_opt.regularizer, OrthogonalRegularizer):
+        raise NotImplementedError("BatchSolver: with advil_pi_loss the regularizer must be None or an OrthogonalRegularizer (it is evaluated on the device)")
+    for k in ("lambda_GP", "lambda_BC"):
+        if k not in solver.P:
+            raise KeyError("BatchSolver: P[%r] is missing (AdVIL's λ_GP, λ_BC)" % k)
 
 
 def _param_step(solver, theta, p, mb, base, info):
@@ -72,7 +92,11 @@ def _solve_batch_ac(solver, mdp=None):
     a_opt, c_opt = solver.a_opt, solver.c_opt
     gamma = float(np.float32(discount(mdp))) if mdp is not None else float(np.float32(solver.gamma))
     _ensure_opt(A, a_opt)
-    if c_opt is not None:
+    advil = a_opt.loss is advil_pi_loss or (c_opt is not None and c_opt.loss is advil_d_loss)
+    if advil:
+        _check_advil(solver)
+        _ensure_opt(Q, c_opt)
+    elif c_opt is not None:
         _ensure_opt(Q.N1, c_opt); _ensure_opt(Q.N2, c_opt)
     n, B = len(D), int(a_opt.batch_size)
     if n < 1:
@@ -104,9 +128,12 @@ def _solve_batch_ac(solver, mdp=None):
                 raise NotImplementedError("BatchSolver: target_fn %r" % (solver.target_fn,))
             if c_opt is not None:                                                                   # :66-71
                 raw = np.zeros(L.INFO_N, np.float32)
-                if y is None:
+                if c_opt.loss is advil_d_loss:                                                      # no target: y stays None
+                    raw, adv = advil_d_step_(A, Q, mb, P["lambda_GP"], solver.noise_seed, base + CTR_ADVIL_GP)
+                    info.update({"D_expert": float(adv[0]), "D_policy": float(adv[1]), "grad_pen": float(adv[2])})
+                elif y is None:
                     raise NotImplementedError("BatchSolver: a critic without a target_fn has no device implementation")
-                if c_opt.loss is cql_critic_loss:
+                elif c_opt.loss is cql_critic_loss:
                     ctx.check(lib.crux_cql_critic_step(A.h, Q.N1.h, Q.N2.h, P["CQL_log_alpha"].h, mb.h, y, int(P["CQL_n_action_samples"]), P["CQL_is_distribution"].lo,
                                                        P["CQL_is_distribution"].hi, float(P["CQL_alpha_thresh"]), 1 if solver.weighted_loss else 0, solver.noise_seed,
                                                        base + CTR_CQL_CRITIC, _vp(raw)))
@@ -114,8 +141,9 @@ def _solve_batch_ac(solver, mdp=None):
                     ctx.check(lib.crux_double_q_step(Q.N1.h, Q.N2.h, mb.h, y, 1 if solver.weighted_loss else 0, _vp(raw)))
                 else:
                     raise NotImplementedError("BatchSolver: critic loss %r has no device implementation" % getattr(c_opt.loss, "name", c_opt.loss))
-                info.update({c_opt.name + "loss": float(raw[0]), c_opt.name + "grad_norm": float(raw[1]), "Q1avg": float(raw[L.INFO["q1avg"]]),
-                             "Q2avg": float(raw[L.INFO["q2avg"]])})
+                info.update({c_opt.name + "loss": float(raw[0]), c_opt.name + "grad_norm": float(raw[1])})
+                if c_opt.loss is not advil_d_loss:
+                    info.update({"Q1avg": float(raw[L.INFO["q1avg"]]), "Q2avg": float(raw[L.INFO["q2avg"]])})
                 if solver.target_fn is not None:
                     if solver.target_update is None:
                         polyak_average_(pim, pi, np.float32(0.005))                                 # the default target_update (batch.jl:30)
@@ -125,6 +153,9 @@ def _solve_batch_ac(solver, mdp=None):
                 raw = np.zeros(L.INFO_N, np.float32)
                 ctx.check(lib.crux_sac_actor_step(A.h, Q.N1.h, Q.N2.h, la.h, mb.h, solver.noise_seed, base + CTR_ACTOR, _vp(raw)))
                 info.update({a_opt.name + "loss": float(raw[0]), a_opt.name + "grad_norm": float(raw[1]), "entropy": float(raw[L.INFO["entropy"]])})
+            elif a_opt.loss is advil_pi_loss:                                                       # with the critic this minibatch has just updated
+                raw, adv = advil_actor_step_(A, Q, mb, P["lambda_BC"], a_opt.regularizer.beta if a_opt.regularizer is not None else 0.0)
+                info.update({a_opt.name + "loss": float(raw[0]), a_opt.name + "grad_norm": float(raw[1]), "bc_mse": float(adv[1]), "orth_reg": float(adv[2])})
             else:
                 raise NotImplementedError("BatchSolver: actor loss %r has no device implementation with a critic" % getattr(a_opt.loss, "name", a_opt.loss))
             solver.grad_steps += 1

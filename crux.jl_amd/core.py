@@ -1222,7 +1222,8 @@ class TrainingParams:
     """TrainingParams(; loss, optimizer=Adam(3f-4), regularizer, batch_size=128, epochs=80, early_stopping, name, max_batches)
     (src/training.jl:1-11). PPO's early_stopping (`infos[end][:kl] > target_kl`, ppo.jl:59) is expressed as target_kl and runs inside the
     persistent learner kernel. The function-valued seams of the reference take the host-driven path of _train_seam / _batch_train_seam:
-    regularizer(theta) -> (value, gradient) over the flat parameter vector (training.jl:4,13: loss + regularizer(pi)); early_stopping(infos) ->
+    regularizer(theta) -> (value, gradient) over the flat parameter vector (training.jl:4,13: loss + regularizer(pi)), or an OrthogonalRegularizer, which
+    stays on the device; early_stopping(infos) ->
     Bool over the per-epoch info dicts (:8,46,49); loss = CustomLoss(fn)."""
 
     def __init__(self, loss, optimizer=None, batch_size=128, epochs=80, target_kl=None, name="", max_batches=math.inf,
@@ -1233,6 +1234,21 @@ class TrainingParams:
         self.optimizer = optimizer or Adam(np.float32(3e-4))
         self.batch_size, self.epochs, self.target_kl, self.name, self.max_batches = int(batch_size), int(epochs), target_kl, name, max_batches
         self.shuffle_seed, self.shuffle_counter = int(shuffle_seed), 0
+
+
+class OrthogonalRegularizer:
+    """OrthogonalRegularizer(; beta=1f-4) (src/extras/orthogonal_regularization.jl): beta sum_l |offdiag(W_l' W_l)|^2 over the Dense layers of a network. As the
+    `regularizer` of a TrainingParams it is evaluated on the device (crux_orthogonal_reg) instead of being called with the flat parameter vector."""
+
+    def __init__(self, beta=1e-4):
+        self.beta = float(np.float32(beta))
+
+
+def orthogonal_regularizer(net, beta=1e-4, accumulate=False):
+    """OrthogonalRegularizer(beta)(net): returns the value. accumulate: its gradient 4 beta W_l R_l is added to the weight slots of the network's gradient buffer."""
+    out = np.zeros(1, np.float32)
+    net.ctx.check(net.ctx.lib.crux_orthogonal_reg(net.h, float(np.float32(beta)), 1 if accumulate else 0, _vp(out)))
+    return float(out[0])
 
 
 def _uses_seam(p):
@@ -1276,8 +1292,11 @@ def _train_seam(pi, p, P, D, ids0, info):
         raw = np.zeros(L.INFO_N, np.float32); cfg = _train_cfg(pi, p, P)
         ctx.check(lib.crux_loss_grad(pi.h, D.h, C.byref(cfg), _vp(ids0), ids0.size, _vp(raw)))
         l = float(raw[L.INFO["loss"]])
+    dev_reg = isinstance(p.regularizer, OrthogonalRegularizer)
+    if dev_reg:                                                            # on the device, before the gradient is read back
+        l = float(np.float32(l) + np.float32(orthogonal_regularizer(pi, p.regularizer.beta, accumulate=True)))
     g = np.empty(n, np.float32); ctx.d2h(lib.crux_mlp_grads_ptr(pi.h), g)
-    if p.regularizer is not None:
+    if p.regularizer is not None and not dev_reg:
         rv, rg = p.regularizer(pi.get_params())
         l = float(np.float32(l) + np.float32(rv)); g = (g + np.asarray(rg, np.float32).reshape(-1)).astype(np.float32)
         ctx.h2d(lib.crux_mlp_grads_ptr(pi.h), g)

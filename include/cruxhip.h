@@ -617,7 +617,7 @@ int32_t crux_sac_actor_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
  * draw, logprob as GaussianPolicy's); uniform samples x = Philox(seed, counter, stream, CQL_UNIFORM), a = (float)(lo + (hi - lo) u53(x0, x1)), logprob =
  * (float)(-act_dim log(hi - lo)) in Float64. No gradient reaches the actor (ignore_derivatives).
  * Batch loop counters (src/model_free/batch.jl:38-85, one block of 8 per global minibatch index g, which continues across solve calls): 8g + 0 CQL alpha samples,
- * + 1 SAC temperature, + 2 sac_target, + 3 CQL critic samples, + 4 actor; the epoch shuffle is crux_buffer_shuffle(seed, epoch).
+ * + 1 SAC temperature, + 2 sac_target, + 3 CQL critic samples, + 4 actor, + 5 AdVIL's penalty draws (crux_advil_d_step); the epoch shuffle is crux_buffer_shuffle(seed, epoch).
  * train!(critic, double_Q_loss + conservative_loss): LOSS, GRAD_NORM (one norm over both nets), Q1AVG, Q2AVG.                                                      */
 int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, const float* d_y, int32_t n_samples,
                              float is_lo, float is_hi, float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out);
@@ -678,6 +678,31 @@ int32_t crux_offgail_gather(crux_buffer* const* sources, int32_t K, int64_t Bd, 
  * reference's InexactError: CRUX_EINVAL, ring untouched. A ring without :i: CRUX_EINVAL. The maximum is taken over the rows still in the ring: rows a wrapping push
  * has overwritten do not count (they would in the reference, where the callback still sees them). One launch pair, no host copy of a column.                    */
 int32_t crux_adril_relabel(crux_buffer* ring, int64_t n_new, int64_t buffer_init, int64_t dN, int64_t* max_i_out, int64_t* k_out);
+
+/* AdVIL (src/model_free/il/AdVIL.jl) and OrthogonalRegularizer (src/extras/orthogonal_regularization.jl) on the dense engine -----------------------------------
+ * OrthogonalRegularizer(beta)(pi) (orthogonal_regularization.jl:5-15): over every Dense layer l of the handle (weight W_l, out x in; biases and the trailing
+ * extras do not count -- GaussianPolicy's logSigma layer has no `weight`), P_l = W_l^T W_l (in x in), R_l = P_l with its diagonal zeroed, value = beta sum_l
+ * sum_ij R_l[i, j]^2. *value_out (host) = the value. accumulate != 0: 4 beta W_l R_l (R is symmetric: d|R|^2 / dW = 2 W (R + R^T)) is ADDED to the weight slots of
+ * crux_mlp_grads_ptr(net); bias and extra slots are not touched. Two Gemm16 launches and one masked fixed-order reduction per layer, no float atomics: identical
+ * calls give identical bits. beta = 0: value 0, gradient untouched. CRUX_EUNSUP while a fused sequence is recorded.                                            */
+int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float* value_out);
+/* train!(critic(pi), advil_d_loss) (AdVIL.jl:6-10) over the staging minibatch of B demonstration rows with continuous actions; actor: a ContinuousNetwork handle
+ * obs_dim -> act_dim, D: obs_dim + act_dim -> 1. With expert_sa = vcat(s, a) and pi_sa = vcat(s, pi(s)) (no gradient reaches the actor):
+ *   L = mean D(expert_sa) - mean D(pi_sa) + lambda_gp gradient_penalty(D, expert_sa, pi_sa; target = gp_target)        (the reference passes target = 0.4f0)
+ * the penalty as crux_gradient_penalty(seed, counter): xhat_j = eps_j pi_sa_j + (1 - eps_j) expert_sa_j, eps_j = (float)u53(Philox(seed, counter, j, IQ_GP)); one
+ * forward pass of D covers the 3B columns [expert_sa | pi_sa | xhat]. Then train! (training.jl:13-25): gradient, norm, NaN => CRUX_ENAN with no update ("NaN
+ * detected!"), Adam. Only D is updated; the actor's parameters and gradient buffer are untouched. info_out (host [CRUX_INFO_N]): LOSS, GRAD_NORM; adv_out (host [4]):
+ * mean D(expert_sa), mean D(pi_sa), P, lambda_gp P. One host synchronisation. Batch loop counter (batch.jl:38-85, the block of 8 of the CQL paragraph): 8g + 5.
+ * Both AdVIL steps: a NaN in s or a surfaces as CRUX_ENAN with no parameter changed. CRUX_EINVAL: a discrete action column; widths that do not fit; B < 1;
+ * 3B > 2^20. CRUX_EUNSUP: an activation of D other than identity, relu or tanh; an actor handle with trailing extras; recording into a fused sequence.           */
+int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, float lambda_gp, float gp_target, uint64_t seed, uint64_t counter,
+                          float* info_out, float* adv_out);
+/* train!(actor(pi), advil_pi_loss + OrthogonalRegularizer(beta_orth)) (AdVIL.jl:1-4, :50; train! adds the regularizer to the loss, training.jl:13):
+ *   L = mean D(s, pi(s)) + lambda_bc Flux.mse(pi(s), a) + beta_orth reg(actor)        (mse: the mean over all act_dim B elements)
+ * the gradient reaches the actor through D's input gradient (D's parameters are not trained here) and the BC term, da = dsa[obs_dim:, :] + lambda_bc 2 (pi(s) - a) /
+ * (act_dim B); the regularizer's gradient is added as crux_orthogonal_reg(accumulate) adds it, before the norm. Only the actor is updated. info_out: LOSS,
+ * GRAD_NORM; adv_out (host [3]): mean D(s, pi(s)), mse, beta_orth reg. beta_orth = 0: no regularizer. One host synchronisation.                                 */
+int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, float lambda_bc, float beta_orth, float* info_out, float* adv_out);
 
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */

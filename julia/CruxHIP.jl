@@ -572,6 +572,25 @@ function AdRIL_relabel!(ring::HipBuffer, n_new::Integer, buffer_init::Integer, Î
     mx[], k[]
 end
 
+# AdVIL (src/model_free/il/AdVIL.jl) on the staging minibatch of a BatchSolver; the penalty's draws of minibatch g are Philox(noise_seed, 8g + 5, j, IQ_GP) (include/cruxhip.h)
+function orthogonal_reg!(Ï€::HipNetwork, Î²::Float32; accumulate::Bool=false)                                                                  # OrthogonalRegularizer(Î²)(Ï€); accumulate: âˆ‡ += 4Î² W R
+    out = zeros(Float32, 1)
+    check(Ï€.ctx, ccall((:crux_orthogonal_reg, LIB), Int32, (Ptr{Cvoid}, Float32, Int32, Ptr{Float32}), Ï€.h, Î², Int32(accumulate), out))
+    out[1]
+end
+function advil_d_step!(A::HipNetwork, D::HipNetwork, mb::HipBuffer, Î»_GP::Float32, seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N); target::Float32=0.4f0)   # train!(critic(Ï€), advil_d_loss)
+    adv = zeros(Float32, 4)                                                                                                                  # mean D(expert), mean D(Ï€), P, Î»_GP P
+    check(D.ctx, ccall((:crux_advil_d_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, UInt64, UInt64, Ptr{Float32}, Ptr{Float32}),
+                       A.h, D.h, mb.h, Î»_GP, target, seed, ctr, info, adv))
+    info, adv
+end
+function advil_actor_step!(A::HipNetwork, D::HipNetwork, mb::HipBuffer, Î»_BC::Float32, Î²_orth::Float32, info=zeros(Float32, INFO_N))         # train!(actor(Ï€), advil_Ï€_loss + OrthogonalRegularizer(Î²))
+    adv = zeros(Float32, 3)                                                                                                                  # mean D(s, Ï€(s)), mse, Î² reg
+    check(D.ctx, ccall((:crux_advil_actor_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Ptr{Float32}, Ptr{Float32}),
+                       A.h, D.h, mb.h, Î»_BC, Î²_orth, info, adv))
+    info, adv
+end
+
 # ---------------------------------------------------------------------------------------------------- user-written losses and the regularizer
 # The reference differentiates ANY loss(Ï€, ð’«, ð’Ÿ) with Zygote (training.jl:16-18). The library's fast paths cover a closed list (loss_id above);
 # everything else composes the explicit pullback: forward with cached activations -> the user's d(loss)/d(output) -> parameter gradients ->
