@@ -174,6 +174,9 @@ SIGNATURES = {
     "crux_orthogonal_reg": (i32, [vp, f32, i32, vp]),
     "crux_advil_d_step": (i32, [vp, vp, vp, f32, f32, u64, u64, vp, vp]),
     "crux_advil_actor_step": (i32, [vp, vp, vp, f32, f32, vp, vp]),
+    "crux_asaf_freeze": (i32, [vp, vp, i64, i64, vp]),
+    "crux_asaf_actor_step": (i32, [vp, vp, i64, i64, vp, vp, vp, f32, vp, vp]),
+    "crux_asaf_batch_train": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, u64, f32, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

@@ -1,10 +1,11 @@
 // offpolicy_unit.hip -- one translation unit for the off-policy dense engine, replay sampling and the fused-step executor: its phase kernels (exec.hip) call
-// the op bodies defined in dense.hip, sac.hip and per.hip (cql.hip, iq.hip, advil.hip and gail_off.hip use the dense engine's and sac.hip's helpers), and device code is not linked across translation units in this build.
+// the op bodies defined in dense.hip, sac.hip and per.hip (cql.hip, iq.hip, advil.hip, asaf.hip and gail_off.hip use the dense engine's and sac.hip's helpers), and device code is not linked across translation units in this build.
 #include "dense.hip"
 #include "sac.hip"
 #include "cql.hip"
 #include "iq.hip"
 #include "advil.hip"
+#include "asaf.hip"
 #include "gail_off.hip"
 #include "train_dense.hip"
 #include "per.hip"

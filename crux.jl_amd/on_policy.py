@@ -45,6 +45,9 @@ def policy_gradient_training(solver, D, perms_a=None, perms_c=None):
         pi_ = batch_train_(theta, p_opt, solver.P, D, info={})
         info.update({k: v for k, v in pi_.items() if not k.startswith("_")})
     A, Cn, pa, pc = actor(solver.agent.pi), critic(solver.agent.pi), solver.a_opt, solver.c_opt
+    if pa.loss.name == "asaf":                                                                         # ASAF (il/asaf.jl): no critic; the loss reads the rollout minibatch and all demonstrations
+        from .il_on_policy import batch_train_asaf_
+        return batch_train_asaf_(solver, D, info=info)
     if pc is None:
         return batch_train_(A, pa, solver.P, D, info=info, perms=perms_a)
     if pa.loss.name == "lagrange_ppo" or getattr(solver, "cost_opt", None) is not None or _uses_seam(pa) or _uses_seam(pc):

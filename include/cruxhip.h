@@ -704,6 +704,42 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, floa
  * GRAD_NORM; adv_out (host [3]): mean D(s, pi(s)), mse, beta_orth reg. beta_orth = 0: no regularizer. One host synchronisation.                                 */
 int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, float lambda_bc, float beta_orth, float* info_out, float* adv_out);
 
+/* ASAF (src/model_free/il/asaf.jl) on the dense engine ------------------------------------------------------------------------------------------------------------
+ * The policy is its own discriminator against a frozen copy piG of itself (deepcopy in post_batch_callback, asaf.jl:57: once per iteration, after sampling and
+ * before batch_train!). piG is constant for the whole batch_train!, so logpdf(piG, ., .) over the rollout rows (gG) and over the demonstrations (gE) are iteration
+ * constants: crux_asaf_freeze forms them once and no step forwards a second network.
+ * d_out[i] = logpdf(pi, s_i, a_i) for rows [first_row, first_row + n_rows) of buf (device, n_rows floats; it may be a column of buf itself). pi: a GaussianPolicy handle
+ * (trailing act_dim extras = logSigma; gaussian_logpdf, policies.jl:333-336, summed over the action) or a SquashedGaussianPolicy handle (crux_mlp_get_squash != 0;
+ * squashed_gaussian_logprob, :383-396, of atanh(clamp(a / ascale, -1 + 1f-5, 1 - 1f-5)) with sigma = exp(clamp(logSigma, -5, 2)) and the unclamped - logSigma term).
+ * One forward pass and one head kernel; no parameter and no gradient buffer changes. A NaN in s_i or a_i gives d_out[i] = NaN. One host synchronisation.
+ * CRUX_EINVAL / CRUX_EUNSUP as crux_asaf_actor_step (policy, buffer, row range; n_rows <= 2^20).                                                                  */
+int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int64_t n_rows, float* d_out);
+/* train!(actor(pi), asaf_actor_loss(piG, D_demo)) (asaf.jl:1-21) on rollout rows [off, off + n) of buf plus ALL N_E rows of demo (the demonstrations are never
+ * minibatched or shuffled). d_gG (device): aligned with buf's rows, entry off + i = logpdf(piG, s, a) of row off + i; d_gE (device [N_E]) the same over demo. With
+ * l_i = logpdf(pi, s_i, a_i), l_E,j = logpdf(pi, s_E,j, a_E,j) (one forward pass over the n + N_E columns [s | s_E]) and entropy = 1.4189385 + sum logSigma:
+ *   L = mean_j softplus(gE_j - l_E,j) + mean_i softplus(l_i - gG_i) - 0.1 entropy            (0.1f0 is the reference's literal)
+ *   dL/dl_i = sigmoid(l_i - gG_i) / n, dL/dl_E,j = -sigmoid(gE_j - l_E,j) / N_E, dl/dmu = (a - mu) / sigma^2, dl/dlogSigma = (a - mu)^2 / sigma^2 - 1 (squashed: a is
+ *   the atanh value and the first term exists only where -5 <= logSigma <= 2, the clamp's own derivative); the entropy adds -0.1 to every logSigma slot.
+ * Then train! (training.jl:13-25): the norm over the raw gradient, NaN => CRUX_ENAN with nothing changed ("NaN detected!"), Adam. clip_value > 0 and finite: the
+ * gradient is clamped element-wise to +-clip_value after the norm and before Adam (Optimiser(ClipValue(c), Adam), examples/il/pendulum.jl); otherwise off.
+ * info_out (host [CRUX_INFO_N]): LOSS, GRAD_NORM, ENTROPY; asaf_out (host [3]): entropy, the expert term, the policy term. A NaN in s or a of either buffer surfaces as
+ * CRUX_ENAN. Float64 partial sums in a fixed block order, no float atomics: identical calls give identical bits. One host synchronisation.
+ * CRUX_EINVAL: a discrete action column in either buffer; widths that do not fit (pi must map obs_dim -> act_dim with act_dim <= 64 logSigma entries; demo must have
+ * buf's obs_dim and act_dim); n < 1 or rows outside buf; an empty demonstration buffer; n + N_E > 2^20; no crux_adam_init. CRUX_EUNSUP: a handle without the logSigma
+ * extras (a deterministic ContinuousNetwork; the categorical head is not implemented); an activation other than identity, relu or tanh; recording into a fused sequence. */
+int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_t n, const float* d_gG, crux_buffer* demo, const float* d_gE, float clip_value,
+                             float* info_out, float* asaf_out);
+/* batch_train!(actor(pi), a_opt, P, D) (training.jl:28-55) with the loss above, enqueued whole with one host synchronisation at the end: per epoch e
+ * crux_buffer_shuffle(buf, shuffle_seed, shuffle_counter + e), then one step per partition of batch_size rows (the last may be short); max_batches > 0 ends the call
+ * after that many steps (:45, :50). gG is buf's :logprob column (crux_asaf_freeze writes it before the call; the shuffles permute it with the rows -- the reference's
+ * buffer has no such column, it evaluates piG in every step instead). Bit-identical to the loop of crux_buffer_shuffle and crux_asaf_actor_step.
+ * epoch_rows (host [epochs x 20] or NULL): per epoch run, the info row of its last minibatch ([CRUX_INFO_N]) followed by entropy, the expert term, the policy term and
+ * one spare; filled on the device. info_out (host [CRUX_INFO_N]): the last epoch's row with BATCHES_TRAINED and EPOCHS_RUN. After a NaN norm no later step of the chain
+ * updates anything or writes a row: the call returns CRUX_ENAN, info_out is the row of the step that stopped, the row order of buf is unspecified.
+ * CRUX_EINVAL additionally: batch_size < 1, epochs < 1, a buffer without :logprob.                                                                                 */
+int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo, const float* d_gE, int32_t batch_size, int32_t epochs, int32_t max_batches,
+                              uint64_t shuffle_seed, uint64_t shuffle_counter, float clip_value, float* info_out, float* epoch_rows);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer

@@ -591,6 +591,23 @@ function advil_actor_step!(A::HipNetwork, D::HipNetwork, mb::HipBuffer, λ_BC::F
     info, adv
 end
 
+# ASAF (src/model_free/il/asaf.jl): πG is constant for a whole batch_train!, so logpdf(πG, ·, ·) is formed once per iteration (asaf_freeze!) and the steps forward π only.
+# d_out / d_gG / d_gE are device pointers (device_vec, or a buffer column); gG is aligned with the buffer's rows, off is 0-based (include/cruxhip.h)
+asaf_freeze!(π::HipNetwork, b::HipBuffer, d_out::Ptr{Cvoid}; first_row::Int64=0, n_rows::Int64=length(b) - first_row) =                   # d_out[i] = logpdf(π, s_i, a_i)
+    check(π.ctx, ccall((:crux_asaf_freeze, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}), π.h, b.h, first_row, n_rows, d_out))
+function asaf_actor_step!(π::HipNetwork, b::HipBuffer, off::Int64, n::Int64, d_gG::Ptr{Cvoid}, demo::HipBuffer, d_gE::Ptr{Cvoid}, info=zeros(Float32, INFO_N); clip_value::Float32=0f0)   # train!(π, asaf_actor_loss(πG, 𝒟_demo))
+    out = zeros(Float32, 3)                                                                                                                  # entropy, the expert term, the policy term
+    check(π.ctx, ccall((:crux_asaf_actor_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Ptr{Float32}, Ptr{Float32}),
+                       π.h, b.h, off, n, d_gG, demo.h, d_gE, clip_value, info, out))
+    info, out
+end
+function asaf_batch_train!(π::HipNetwork, b::HipBuffer, demo::HipBuffer, d_gE::Ptr{Cvoid}, p::Crux.TrainingParams, seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N); clip_value::Float32=0f0)   # batch_train!; gG = b[:logprob]
+    rows = zeros(Float32, INFO_N + 4, p.epochs)                                                                                              # per epoch: the info row, entropy, expert term, policy term, spare
+    check(π.ctx, ccall((:crux_asaf_batch_train, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, UInt64, UInt64, Float32, Ptr{Float32}, Ptr{Float32}),
+                       π.h, b.h, demo.h, d_gE, Int32(p.batch_size), Int32(p.epochs), isfinite(p.max_batches) ? Int32(p.max_batches) : Int32(0), seed, ctr, clip_value, info, rows))
+    info, rows
+end
+
 # ---------------------------------------------------------------------------------------------------- user-written losses and the regularizer
 # The reference differentiates ANY loss(π, 𝒫, 𝒟) with Zygote (training.jl:16-18). The library's fast paths cover a closed list (loss_id above);
 # everything else composes the explicit pullback: forward with cached activations -> the user's d(loss)/d(output) -> parameter gradients ->
