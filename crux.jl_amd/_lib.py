@@ -177,6 +177,10 @@ SIGNATURES = {
     "crux_asaf_freeze": (i32, [vp, vp, i64, i64, vp]),
     "crux_asaf_actor_step": (i32, [vp, vp, i64, i64, vp, vp, vp, f32, vp, vp]),
     "crux_asaf_batch_train": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, u64, f32, vp, vp]),
+    "crux_gail_d_batch_train": (i32, [vp, vp, vp, i32, i32, i32, u64, u64, vp, vp]),
+    "crux_nda_reward_cost": (i32, [vp, vp, vp, f32, vp]),
+    "crux_nda_advantages": (i32, [vp, vp, vp, f32, f32]),
+    "crux_nda_gail_round": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, u64, i32, i32, i32, u64, u64, f32, f32, f32, vp, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

@@ -9,7 +9,7 @@ Array convention: like the Julia arrays, columns are (features, batch) with the 
 are Fortran-ordered so their memory is identical to the Julia array's (and to what crosses the C ABI).
 
 Round 4: the definitions live in four modules by solver family -- core.py (contexts, networks, buffers, sampling, steps!, losses, train! / batch_train!), on_policy.py
-(OnPolicySolver, PPO, LagrangePPO, A2C, REINFORCE), imitation.py (OnPolicyGAIL, BC), off_policy.py (OffPolicySolver, DQN, SoftQ, SAC, DDPG, TD3); this module re-exports all of
+(OnPolicySolver, PPO, LagrangePPO, A2C, REINFORCE), imitation.py (OnPolicyGAIL, NDA_GAIL_JS, BC), off_policy.py (OffPolicySolver, DQN, SoftQ, SAC, DDPG, TD3); this module re-exports all of
 them (private helpers included) and holds the `solve` dispatcher, so `crux.X` and `crux.api.X` resolve as before.
 """
 import ctypes as C   # noqa: F401
@@ -31,7 +31,7 @@ from .on_policy import (  # noqa: F401
     A2C, LagrangePPO, OnPolicySolver, PPO, REINFORCE, allreduce_mean_, policy_gradient_training, policy_gradient_training_multi, policy_gradient_training_synced, solve)
 from .imitation import *   # noqa: F401,F403
 from .imitation import (  # noqa: F401
-    BC, BatchSolver, OnPolicyGAIL, _solve_batch, batch_train_gail_d_, gail_d_loss, gail_reward_, logpdf_bc_loss, loss_value, mse_action_loss, stop_on_validation_increase)
+    BC, BatchSolver, NDA_GAIL_JS, OnPolicyGAIL, _solve_batch, batch_train_gail_d_, batch_train_gail_d_chain_, nda_advantages_, nda_gail_round_, nda_reward_cost_, gail_d_loss, gail_reward_, logpdf_bc_loss, loss_value, mse_action_loss, stop_on_validation_increase)
 from .off_policy import *   # noqa: F401,F403
 from .off_policy import (  # noqa: F401
     DDPG, DQN, OffPolicySolver, SAC, SoftQ, TD3, _PendingInfo, _dpg_solver, _info_ring, _post_sample, _set_stream_for, _solve_off_policy, _solve_small_dqn, _upload_target,

@@ -118,6 +118,19 @@ __device__ __forceinline__ void whiten_block(float* __restrict__ v, int64_t n) {
 }
 __global__ __launch_bounds__(1024) void k_whiten(float* __restrict__ v, int64_t n) { whiten_block(v, n); }
 __global__ __launch_bounds__(1024) void k_whiten_multi(float* const* __restrict__ vs, int64_t n) { whiten_block(vs[blockIdx.x], n); }
+// NDA-GAIL's advantage tail (nda_gail_js.jl:51-61): the reward scan and the cost scan as one launch (grid.y = channel), GAE and returns of a channel in one pass, then
+// both whitens as one launch (one block each). gate (may be NULL): nothing is written once the round's discriminator chains stopped with CRUX_ENAN.
+__global__ void k_nda_gae2(const float* __restrict__ r, const float* __restrict__ cost, const uint8_t* __restrict__ done, const uint8_t* __restrict__ ee, const float* __restrict__ Vs,
+                           const float* __restrict__ Vsp, const float* __restrict__ Cs, const float* __restrict__ Csp, float lambda, float gamma, int64_t n, float* __restrict__ adv,
+                           float* __restrict__ ret, float* __restrict__ cadv, float* __restrict__ cret, int32_t* __restrict__ flags, const int32_t* __restrict__ gate) {
+  if (gate && gate[0] == CRUX_ENAN) return;
+  if (blockIdx.y == 0) gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, n, adv, ret, flags);
+  else gae_returns_body(cost, done, ee, Cs, Csp, lambda, gamma, n, cadv, cret, flags + 1);
+}
+__global__ __launch_bounds__(1024) void k_nda_whiten2(float* __restrict__ v0, float* __restrict__ v1, int64_t n, const int32_t* __restrict__ gate) {
+  if (gate && gate[0] == CRUX_ENAN) return;
+  whiten_block(blockIdx.x == 0 ? v0 : v1, n);
+}
 
 static int32_t values(crux_mlp* critic, const float* d_x, int64_t n, float* d_y) {
   return crux_mlp_forward_impl(critic, d_x, n, d_y, nullptr);   // 2 x 65536 critic evaluations = 0.14 ms per iteration with the generic forward kernel
@@ -343,6 +356,60 @@ int32_t crux_whiten(crux_buffer* b, int32_t key) {
 }
 
 }  // extern "C"
+
+// ---- NDA-GAIL's advantage tail --------------------------------------------------------------------------------------------------------------------------------
+// scratch of the enqueue-only form: V(s), V(sp), Vc(s), Vc(sp) and the two NaN flags
+size_t crux_nda_adv_bytes(int64_t n) { return 4 * Carve::span<float>((size_t)n) + 256; }
+int32_t crux_nda_adv_check(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, const char* who) {
+  crux_ctx* c = b->ctx;
+  for (int k : {CRUX_COL_ADVANTAGE, CRUX_COL_RETURN, CRUX_COL_COST, CRUX_COL_COST_ADVANTAGE, CRUX_COL_COST_RETURN})
+    if (!f32_scalar_col(b, k)) return crux_fail(c, CRUX_EINVAL, "%s: the buffer lacks column %d (:advantage, :return, :cost, :cost_advantage and :cost_return are needed)", who, k);
+  if (V->ctx != c || Vc->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: the critics and the buffer belong to different contexts", who);
+  for (crux_mlp* q : {V, Vc}) if (q->nd.L < 1 || q->nd.dims[q->nd.L] != 1 || q->nd.dims[0] != b->obs_dim)
+    return crux_fail(c, CRUX_EINVAL, "%s: both critics must map obs(%d) -> 1 (@assert length(Vs) == 1)", who, b->obs_dim);
+  const int64_t n = b->elements;
+  if (n < 2) return crux_fail(c, CRUX_EINVAL, "%s: whiten needs at least 2 elements", who);
+  if (n > (int64_t)JLW_MAXLEAF * 512) return crux_fail(c, CRUX_EUNSUP, "%s: %lld elements (the pairwise reduction is laid out for at most %d leaves)", who, (long long)n, JLW_MAXLEAF);
+  return CRUX_OK;
+}
+// everything enqueued, nothing read: flags_out[0] / [1] are raised by a NaN reward / cost advantage (@assert !isnan(A), sampler.jl:270)
+int32_t crux_nda_adv_enqueue(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float lambda, float gamma, char* sc, const int32_t* gate, int32_t** flags_out) {
+  crux_ctx* c = b->ctx; const int64_t n = b->elements;
+  Carve cv{sc, 0}; float* Vs = cv.take<float>((size_t)n); float* Vsp = cv.take<float>((size_t)n); float* Cs = cv.take<float>((size_t)n); float* Csp = cv.take<float>((size_t)n);
+  int32_t* flags = cv.take<int32_t>(2);
+  HIPCHK(c, hipMemsetAsync(flags, 0, 256, c->stream));
+  const float* S = (const float*)b->col[CRUX_COL_S]; const float* SP = (const float*)b->col[CRUX_COL_SP];
+  crux_prof_begin(c, CRUX_PROF_VALUES);
+  int32_t rc = values(V, S, n, Vs); if (rc) return rc;
+  rc = values(V, SP, n, Vsp); if (rc) return rc;
+  rc = values(Vc, S, n, Cs); if (rc) return rc;
+  rc = values(Vc, SP, n, Csp); if (rc) return rc;
+  crux_prof_end(c, CRUX_PROF_VALUES);
+  crux_prof_begin(c, CRUX_PROF_GAE);
+  hipLaunchKernelGGL(k_nda_gae2, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_R], (const float*)b->col[CRUX_COL_COST], (const uint8_t*)b->col[CRUX_COL_DONE],
+                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], (const float*)Vs, (const float*)Vsp, (const float*)Cs, (const float*)Csp, lambda, gamma, n, (float*)b->col[CRUX_COL_ADVANTAGE],
+                     (float*)b->col[CRUX_COL_RETURN], (float*)b->col[CRUX_COL_COST_ADVANTAGE], (float*)b->col[CRUX_COL_COST_RETURN], flags, gate);
+  crux_prof_end(c, CRUX_PROF_GAE);
+  crux_prof_begin(c, CRUX_PROF_WHITEN);
+  hipLaunchKernelGGL(k_nda_whiten2, dim3(2), dim3(1024), 0, c->stream, (float*)b->col[CRUX_COL_ADVANTAGE], (float*)b->col[CRUX_COL_COST_ADVANTAGE], n, gate);
+  crux_prof_end(c, CRUX_PROF_WHITEN);
+  *flags_out = flags;
+  return crux_launch_check(c, "k_nda_gae2 / k_nda_whiten2");
+}
+extern "C" int32_t crux_nda_advantages(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float lambda, float gamma) {
+  if (!b || !V || !Vc) return CRUX_EINVAL;
+  crux_ctx* c = b->ctx; const char* who = "nda_advantages";
+  int32_t rc = crux_nda_adv_check(b, V, Vc, who); if (rc) return rc;
+  char* sc = (char*)crux_scratch(c, crux_nda_adv_bytes(b->elements)); if (!sc) return crux_fail(c, CRUX_ENOMEM, "%s: scratch", who);
+  int32_t* flags = nullptr;
+  rc = crux_nda_adv_enqueue(b, V, Vc, lambda, gamma, sc, nullptr, &flags); if (rc) return rc;
+  int32_t* h = (int32_t*)crux_pinned(c, 8); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
+  HIPCHK(c, hipMemcpyAsync(h, flags, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h[0]) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
+  if (h[1]) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN cost advantage (@assert !isnan(A))");
+  return CRUX_OK;
+}
 
 // ---- importance-weight columns (src/sampler.jl:58-62,108-111,283-308) ------------------------------------------------------------------------
 // exp.(logpdf(pa, s, a) .- logprob): z = the nominal policy's outputs of the rows [nout x n]

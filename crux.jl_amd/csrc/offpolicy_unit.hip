@@ -1,5 +1,5 @@
 // offpolicy_unit.hip -- one translation unit for the off-policy dense engine, replay sampling and the fused-step executor: its phase kernels (exec.hip) call
-// the op bodies defined in dense.hip, sac.hip and per.hip (cql.hip, iq.hip, advil.hip, asaf.hip and gail_off.hip use the dense engine's and sac.hip's helpers), and device code is not linked across translation units in this build.
+// the op bodies defined in dense.hip, sac.hip and per.hip (cql.hip, iq.hip, advil.hip, asaf.hip, gail_off.hip and nda_gail.hip use the dense engine's and sac.hip's helpers), and device code is not linked across translation units in this build.
 #include "dense.hip"
 #include "sac.hip"
 #include "cql.hip"
@@ -7,6 +7,7 @@
 #include "advil.hip"
 #include "asaf.hip"
 #include "gail_off.hip"
+#include "nda_gail.hip"
 #include "train_dense.hip"
 #include "per.hip"
 #include "exec.hip"

@@ -333,6 +333,12 @@ struct GailInfoOp { static __device__ __forceinline__ void run(const unsigned bi
   dinfo[CRUX_INFO_LOSS] = (float)(st[0] / (double)n_ex) + (float)(st[1] / (double)n_pi); dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
 } };
 __global__ void k_gail_info(const double* __restrict__ st, const double* __restrict__ ssq, int64_t n_ex, int64_t n_pi, float* __restrict__ dinfo) { GailInfoOp::run(blockIdx.x, gridDim.x, st, ssq, n_ex, n_pi, dinfo); }
+// the same row inside a chain (nda_gail.hip): the norm is finalised for the gate as always, but no row is written once an earlier step stopped with CRUX_ENAN
+__global__ void k_gail_info_chain(const double* __restrict__ st, const double* __restrict__ ssq, int64_t n_ex, int64_t n_pi, const int32_t* __restrict__ status, float* __restrict__ dinfo) {
+  if (threadIdx.x != 0) return;
+  if (status[0] == CRUX_ENAN) { ssq_finalize(ssq); return; }
+  GailInfoOp::run(blockIdx.x, gridDim.x, st, ssq, n_ex, n_pi, dinfo);
+}
 struct GailRewardOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, int64_t n, float alpha_r, float rscale, float* __restrict__ r, double* __restrict__ partial) {
   __shared__ double red[4];
   double s = 0;
@@ -476,26 +482,46 @@ int32_t crux_q_step(crux_mlp* q, crux_buffer* b, const float* d_y, int32_t use_w
   return q_step_impl(q, nullptr, b, d_y, use_weight, info_out, "td_loss");
 }
 
+}  // extern "C"
+
+// One discriminator step of gail_d_loss(GAN_BCELoss()), enqueued only: the gather of both halves, the dense forward pass, the two BCE heads, the dense backward pass, the
+// norm, the info row and the gated Adam. crux_gail_d_step is this plus the read-back; the chain of nda_gail.hip enqueues it once per minibatch pair with chained = true
+// (all steps share `status`, and no row is written once it holds CRUX_ENAN). The caller has zeroed dinfo and status.
+struct GailStepBufs { float* x; float* dz; double* st2; double* ssq; };
+static int32_t gail_check(crux_ctx* c, const crux_mlp* D, const crux_buffer* ex, const crux_buffer* pi) {
+  const int sd = ex->obs_dim + ex->act_dim;
+  if (pi->obs_dim != ex->obs_dim || pi->act_dim != ex->act_dim || pi->act_kind != ex->act_kind) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: expert and policy buffers differ in shape");
+  if (D->nd.L < 1 || D->nd.dims[0] != sd || D->nd.dims[D->nd.L] != 1) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: discriminator must map vcat(a, s) (%d) -> 1", sd);
+  return CRUX_OK;
+}
+static int32_t gail_enqueue_step(crux_mlp* D, const crux_buffer* ex, int64_t off_ex, int64_t n_ex, const crux_buffer* pi, int64_t off_pi, int64_t n_pi, const GailStepBufs& gb, float* dinfo,
+                                 int32_t* status, bool chained) {
+  crux_ctx* c = D->ctx; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad; const int64_t B = n_ex + n_pi;
+  const int u8 = ex->act_kind == CRUX_ACTION_DISCRETE ? 1 : 0;
+  hipLaunchKernelGGL(k_concat_as, dim3(nblk(n_ex * sd)), dim3(256), 0, c->stream, (const void*)ex->col[CRUX_COL_A], u8, (const float*)ex->col[CRUX_COL_S], od, ad, off_ex, n_ex, gb.x);
+  hipLaunchKernelGGL(k_concat_as, dim3(nblk(n_pi * sd)), dim3(256), 0, c->stream, (const void*)pi->col[CRUX_COL_A], u8, (const float*)pi->col[CRUX_COL_S], od, ad, off_pi, n_pi, gb.x + (size_t)n_ex * sd);
+  int32_t rc = crux_dense_forward(D, gb.x, B, c->stream); if (rc) return rc;
+  hipLaunchKernelGGL(k_gail_head, dim3(1), dim3(256), 0, c->stream, crux_dense_act(D, D->nd.L), n_ex, n_pi, gb.dz, gb.st2);
+  rc = crux_dense_backward(D, gb.x, B, gb.dz, 1.0f, true, nullptr, c->stream); if (rc) return rc;
+  CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, gb.ssq, Sumsq2Fix{});
+  if (chained) hipLaunchKernelGGL(k_gail_info_chain, dim3(1), dim3(1), 0, c->stream, (const double*)gb.st2, (const double*)gb.ssq, n_ex, n_pi, (const int32_t*)status, dinfo);
+  else hipLaunchKernelGGL(k_gail_info, dim3(1), dim3(1), 0, c->stream, gb.st2, gb.ssq, n_ex, n_pi, dinfo);
+  return adam_gated(D, gb.ssq, status);
+}
+
+extern "C" {
+
 int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, float* info_out) {
   if (!D || !ex || !pi) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad;
   if (n_ex <= 0 || n_pi <= 0 || off_ex < 0 || off_pi < 0 || off_ex + n_ex > ex->elements || off_pi + n_pi > pi->elements) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: row ranges outside the buffers");
-  if (pi->obs_dim != od || pi->act_dim != ad || pi->act_kind != ex->act_kind) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: expert and policy buffers differ in shape");
-  if (D->nd.L < 1 || D->nd.dims[0] != sd || D->nd.dims[D->nd.L] != 1) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: discriminator must map vcat(a, s) (%d) -> 1", sd);
+  int32_t rc = gail_check(c, D, ex, pi); if (rc) return rc;
   const int64_t B = n_ex + n_pi;
   Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (sd + 1) + 8192), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "gail_d_loss: scratch");
-  float* x = cv.take<float>((size_t)B * sd); float* dz = cv.take<float>((size_t)B); float* dinfo = cv.take<float>(CRUX_INFO_N);
-  double* st2 = cv.take<double>(2); double* ssq = cv.take<double>(2 + SUMSQ_BLOCKS); int32_t* st = cv.take<int32_t>(1);
-  HIPCHK(c, hipMemsetAsync(dinfo, 0, 256 * 5, c->stream));
-  const int u8 = ex->act_kind == CRUX_ACTION_DISCRETE ? 1 : 0;
-  hipLaunchKernelGGL(k_concat_as, dim3(nblk(n_ex * sd)), dim3(256), 0, c->stream, (const void*)ex->col[CRUX_COL_A], u8, (const float*)ex->col[CRUX_COL_S], od, ad, off_ex, n_ex, x);
-  hipLaunchKernelGGL(k_concat_as, dim3(nblk(n_pi * sd)), dim3(256), 0, c->stream, (const void*)pi->col[CRUX_COL_A], u8, (const float*)pi->col[CRUX_COL_S], od, ad, off_pi, n_pi, x + (size_t)n_ex * sd);
-  int32_t rc = crux_dense_forward(D, x, B, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_gail_head, dim3(1), dim3(256), 0, c->stream, crux_dense_act(D, D->nd.L), n_ex, n_pi, dz, st2);
-  rc = crux_dense_backward(D, x, B, dz, 1.0f, true, nullptr, c->stream); if (rc) return rc;
-  CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, ssq, Sumsq2Fix{});
-  hipLaunchKernelGGL(k_gail_info, dim3(1), dim3(1), 0, c->stream, st2, ssq, n_ex, n_pi, dinfo);
-  rc = adam_gated(D, ssq, st); if (rc) return rc;
+  GailStepBufs gb; gb.x = cv.take<float>((size_t)B * sd); gb.dz = cv.take<float>((size_t)B); float* dinfo = cv.take<float>(CRUX_INFO_N);
+  gb.st2 = cv.take<double>(2); gb.ssq = cv.take<double>(2 + SUMSQ_BLOCKS); int32_t* st = cv.take<int32_t>(1);
+  HIPCHK(c, hipMemsetAsync(dinfo, 0, 256 * 6, c->stream));
+  rc = gail_enqueue_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, gb, dinfo, st, false); if (rc) return rc;
   return finish_step(c, dinfo, st, info_out, "gail_d_loss");
 }
 

@@ -1,4 +1,4 @@
-"""imitation.py -- OnPolicyGAIL and the BatchSolver family (BC) (src/model_free/il/on_policy_gail.jl, il/bc.jl, src/model_free/batch.jl).
+"""imitation.py -- OnPolicyGAIL, NDA_GAIL_JS and the BatchSolver family (BC) (src/model_free/il/on_policy_gail.jl, il/nda_gail_js.jl, il/bc.jl, src/model_free/batch.jl).
 
 Split out of api.py in round 4; `crux_jl_amd.api` re-exports everything, so `crux.X` and `crux.api.X` resolve as before."""
 import ctypes as C
@@ -78,6 +78,92 @@ def OnPolicyGAIL(pi, S, gamma, D, demo, lambda_gae=0.95, alpha_r=0.5, normalize_
         whiten_(buf, "advantage")                                                       # :64
     sv.post_batch_callback = GAIL_callback
     sv.discriminator, sv.d_opt, sv.demo = D, dp, demo
+    return sv
+
+
+# --------------------------------------------------------------------------------------------------------------
+# NDA_GAIL_JS (src/model_free/il/nda_gail_js.jl) -- LagrangePPO whose post_batch_callback trains two discriminators and rewrites :r and :cost
+# --------------------------------------------------------------------------------------------------------------
+def _max_batches(p):
+    return 0 if p.max_batches in (None, math.inf) else int(p.max_batches)
+
+
+def _d_info(p, rows, raw):
+    """aggregate_info over the epoch rows of a discriminator chain: epoch info = its last pair, result = mean over epochs"""
+    e = int(raw[L.INFO["epochs_run"]]); rows = rows[:e]
+    return {p.name + "loss": float(np.mean(rows[:, L.INFO["loss"]])), p.name + "grad_norm": float(np.mean(rows[:, L.INFO["grad_norm"]])),
+            p.name + "batches_trained": int(raw[L.INFO["batches_trained"]])}
+
+
+def batch_train_gail_d_chain_(Dnet, p, D_expert, D_policy, info=None):
+    """batch_train_gail_d_ as one C call (crux_gail_d_batch_train): the same shuffles, pairs and steps, bit for bit, with one host synchronisation."""
+    _ensure_opt(Dnet, p)
+    raw, rows = np.zeros(L.INFO_N, np.float32), np.zeros((p.epochs, L.INFO_N), np.float32)
+    try:
+        Dnet.ctx.check(Dnet.ctx.lib.crux_gail_d_batch_train(Dnet.h, D_expert.h, D_policy.h, p.batch_size, p.epochs, _max_batches(p), p.shuffle_seed, p.shuffle_counter, _vp(raw), _vp(rows)))
+    finally:
+        p.shuffle_counter += int(raw[L.INFO["epochs_run"]]) if raw[L.INFO["epochs_run"]] > 0 else 0
+    out = _d_info(p, rows, raw)
+    if info is not None:
+        info.update(out)
+    out["_epoch_infos"] = rows[:int(raw[L.INFO["epochs_run"]])]
+    return out
+
+
+def nda_reward_cost_(Dnet, Dnda, buf, alpha_r=0.5):
+    """buf[:r] and buf[:cost] from the two discriminators (nda_gail_js.jl:33-49, crux_nda_reward_cost); returns (mean(r), sum(c) / sum(episode_end), sum(episode_end))."""
+    out = np.zeros(3, np.float32)
+    Dnet.ctx.check(Dnet.ctx.lib.crux_nda_reward_cost(Dnet.h, Dnda.h, buf.h, float(alpha_r), _vp(out)))
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+def nda_advantages_(buf, V, Vc, lambda_gae, gamma):
+    """fill_gae! / fill_returns! of :r and :cost with V and Vc and both whitens (nda_gail_js.jl:51-61) as one C call (crux_nda_advantages)."""
+    buf.ctx.check(buf.ctx.lib.crux_nda_advantages(buf.h, V.h, Vc.h, float(lambda_gae), float(gamma)))
+
+
+def nda_gail_round_(Dnet, Dnda, dp, dpn, demo, nda, buf, copyD, copyN, V, Vc, alpha_r, lambda_gae, gamma, info=None):
+    """The whole GAIL_callback (nda_gail_js.jl:28-63) as one C call (crux_nda_gail_round); both shuffle counters advance by the epochs run."""
+    _ensure_opt(Dnet, dp); _ensure_opt(Dnda, dpn)
+    rD, rN, out3 = np.zeros(L.INFO_N, np.float32), np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
+    try:
+        Dnet.ctx.check(Dnet.ctx.lib.crux_nda_gail_round(Dnet.h, Dnda.h, demo.h, nda.h, buf.h, copyD.h, copyN.h, V.h, Vc.h,
+                                                        dp.batch_size, dp.epochs, _max_batches(dp), dp.shuffle_seed, dp.shuffle_counter,
+                                                        dpn.batch_size, dpn.epochs, _max_batches(dpn), dpn.shuffle_seed, dpn.shuffle_counter,
+                                                        float(alpha_r), float(lambda_gae), float(gamma), _vp(rD), _vp(rN), _vp(out3)))
+    finally:
+        for p, raw in ((dp, rD), (dpn, rN)):
+            p.shuffle_counter += int(raw[L.INFO["epochs_run"]]) if raw[L.INFO["epochs_run"]] > 0 else 0
+    info = info if info is not None else {}
+    for p, raw in ((dp, rD), (dpn, rN)):      # the round hands back each chain's last epoch row (its last pair), not the mean over epochs batch_train_gail_d_chain_ forms
+        info[p.name + "loss"], info[p.name + "grad_norm"] = float(raw[L.INFO["loss"]]), float(raw[L.INFO["grad_norm"]])
+        info[p.name + "batches_trained"] = int(raw[L.INFO["batches_trained"]])
+    info["disc_reward"], info["disc_nda_cost"] = float(out3[0]), float(out3[1])
+    return info
+
+
+def NDA_GAIL_JS(pi, S, D_demo, D_nda, Vc, gamma, D, Dnda, lambda_gae=0.95, alpha_r=0.5, normalize_demo=True, solver=None, d_opt=None, d_opt_nda=None, **kw):
+    """NDA_GAIL_JS(; π, S, 𝒟_demo, 𝒟_nda, Vc, γ, λ_gae=0.95, αr=0.5, normalize_demo=true, D, Dnda, solver=LagrangePPO, gan_loss=GAN_BCELoss(), d_opt, d_opt_nda)
+    (src/model_free/il/nda_gail_js.jl:1-65): the solver (LagrangePPO: cost critic Vc, :cost columns, PID penalty) with a post_batch_callback that trains D on
+    (demonstrations, copy of the fresh batch) and Dnda on (negative demonstrations, another copy), sets :r from D, :cost = max(0, r_nda - r), and refills GAE, returns
+    and both whitened advantages with the actor-critic's critic and Vc. The callback replaces the solver's own (the later keyword wins in the reference, :64) and is one
+    C call (crux_nda_gail_round). Both demonstration buffers are copied, and normalised when asked; the caller's stay as they were."""
+    d = dict(d_opt or {}); d.setdefault("name", "discriminator_")
+    dn = dict(d_opt_nda or {}); dn.setdefault("name", "nda_discriminator_")
+    dp, dpn = TrainingParams(loss=gail_d_loss, **d), TrainingParams(loss=gail_d_loss, **dn)
+    A = pi.space if hasattr(pi, "space") else ContinuousSpace(actor(pi).network.dims[-1])
+    demo, nda = copy_buffer(D_demo), copy_buffer(D_nda)
+    if normalize_demo:
+        normalize_(demo, S, A); normalize_(nda, S, A)
+    sv = (solver or LagrangePPO)(pi=pi, S=S, Vc=Vc, lambda_gae=lambda_gae, **kw)
+    copies = []
+
+    def GAIL_callback(buf, info):
+        if not copies or copies[0].capacity < len(buf):
+            copies[:] = [buffer_like(buf, capacity=buf.capacity), buffer_like(buf, capacity=buf.capacity)]      # the two deepcopy(𝒟) (:29, :30), refilled on the device every round
+        nda_gail_round_(D, Dnda, dp, dpn, demo, nda, buf, copies[0], copies[1], critic(sv.agent.pi), Vc, alpha_r, lambda_gae, gamma, info=info)
+    sv.post_batch_callback = GAIL_callback
+    sv.discriminator, sv.nda_discriminator, sv.d_opt, sv.d_opt_nda, sv.demo, sv.nda = D, Dnda, dp, dpn, demo, nda
     return sv
 
 

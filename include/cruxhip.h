@@ -740,6 +740,46 @@ int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_
 int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo, const float* d_gE, int32_t batch_size, int32_t epochs, int32_t max_batches,
                               uint64_t shuffle_seed, uint64_t shuffle_counter, float clip_value, float* info_out, float* epoch_rows);
 
+/* NDA-GAIL-JS (src/model_free/il/nda_gail_js.jl) on the dense engine ---------------------------------------------------------------------------------------------
+ * batch_train!(D, d_opt, (;), D_expert, D_policy) (src/training.jl:28-55) with gail_d_loss(GAN_BCELoss()) (on_policy_gail.jl:1-5), enqueued whole with one host
+ * synchronisation at the end. Shuffle k = shuffle_counter + epoch: crux_buffer_shuffle(expert, shuffle_seed, 2k) and crux_buffer_shuffle(policy, shuffle_seed, 2k + 1)
+ * (:36), then one step of crux_gail_d_step's arithmetic per zipped pair of partitions of batch_size rows (:40): the shorter buffer ends the epoch, the last pair may be
+ * short on either side; max_batches > 0 ends the call after that many steps (:45, :50). Bit-identical to the loop of crux_buffer_shuffle and crux_gail_d_step:
+ * parameters, Adam moments and info rows. epoch_rows (host [epochs x CRUX_INFO_N] or NULL): per epoch run, the row of its last pair (LOSS, GRAD_NORM), written on the
+ * device. info_out (host [CRUX_INFO_N]): the last epoch's row with BATCHES_TRAINED and EPOCHS_RUN. After a NaN norm no later step updates anything or writes a row: the
+ * call returns CRUX_ENAN, info_out is the row of the step that stopped, the row order of both buffers is unspecified.
+ * CRUX_EINVAL: batch_size < 1, epochs < 1; buffers that differ in shape, are empty, are one handle or belong to another context; a discriminator that does not map
+ * act_dim + obs_dim -> 1; no crux_adam_init. CRUX_EUNSUP: recording into a fused sequence.                                                                         */
+int32_t crux_gail_d_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed,
+                                uint64_t shuffle_counter, float* info_out, float* epoch_rows);
+/* The reward and the hinge cost of GAIL_callback (nda_gail_js.jl:33-49) over all rows of buf: one gather of vcat(a, s) (one-hot actions as 0/1) feeds both networks;
+ * r = ar logsigmoid(D_out) - (1 - ar) logcompsigmoid(D_out) (:34, the Float32 operation order of crux_gail_reward: buf[:r] is bit-identical to
+ * crux_gail_reward(D, buf, ar, 1)), r_nda the same from Dnda (:43), c = max(0, r_nda - r) (:44); buf[:r] = r, buf[:cost] = c. out3 (host [3]): mean(r)
+ * (info["disc_reward"], :37), sum(c) / sum(episode_end) (info["disc_nda_cost"], :47; the Float32 quotient, Inf or NaN when no row closes an episode) and
+ * sum(episode_end). Float64 block partials added in a fixed order, no float atomics. A NaN in a gathered value makes r and c of that row NaN; it is not an error.
+ * One host synchronisation. Dnda may be D. CRUX_EINVAL: discriminator widths other than act_dim + obs_dim -> 1; D, Dnda or buf on different contexts; a buffer
+ * without :cost; an empty buffer (or more than 2^20 rows).                                                                                                          */
+int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, float alpha_r, float* out3);
+/* The advantage tail of GAIL_callback (nda_gail_js.jl:51-61) over the episodes of buf: V and Vc evaluated on :s and :sp, fill_gae! / fill_returns! of :r into
+ * :advantage / :return and of :cost into :cost_advantage / :cost_return (src/sampler.jl:255-281), both advantages whitened (src/utils.jl:41-42). Everything is
+ * enqueued; one host synchronisation reads both NaN flags (@assert !isnan(A), sampler.jl:270 => CRUX_ENAN). The four columns are bit-identical to crux_fill_gae,
+ * crux_fill_returns, crux_fill_gae_keys and crux_fill_returns_keys with the cost keys, and crux_whiten twice.
+ * CRUX_EINVAL: a missing column; critics that do not map obs_dim -> 1 or live on another context; fewer than 2 rows.                                              */
+int32_t crux_nda_advantages(crux_buffer* buf, crux_mlp* V, crux_mlp* Vc, float lambda, float gamma);
+/* The whole GAIL_callback (nda_gail_js.jl:28-63), enqueued back to back on one stream with one host synchronisation at the end: copyD and copyN (caller-owned plain
+ * buffers shaped like batch, capacity >= length(batch)) are refilled from batch on the device -- the two deepcopy(D) (:29, :30) --, then
+ * crux_gail_d_batch_train(D, demo, copyD, <d_opt>), crux_gail_d_batch_train(Dnda, nda, copyN, <d_opt_nda>), crux_nda_reward_cost(D, Dnda, batch, alpha_r) and
+ * crux_nda_advantages(batch, V, Vc, lambda, gamma). Bit-identical to those four calls in turn. info_D / info_Dnda (host [CRUX_INFO_N] each): as info_out of the
+ * chains; out3 as crux_nda_reward_cost. Both chains share one status word: after a NaN norm in either, no later step of either network updates anything, batch is not
+ * rewritten (neither :r, :cost nor the four advantage columns) and the call returns CRUX_ENAN; the info row of the chain that stopped is the row of that step.
+ * The two networks' steps are independent of each other; they are NOT run side by side here.
+ * CRUX_EINVAL: as the four calls; D == Dnda; copies that are not buffers of their own, differ from batch in shape, are prioritized or too small. Nothing is launched
+ * and no buffer is touched when a check fails.                                                                                                                     */
+int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
+                            int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                            int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
+                            float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer
