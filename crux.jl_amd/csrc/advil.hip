@@ -107,16 +107,12 @@ __global__ void k_advil_pi_info(const double* __restrict__ st, const double* __r
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------------------------
 struct OrthBufs { float* P; float* T; double* part; };
-static size_t orth_bytes(const NetDesc& nd) {
+struct OrthPlan {      // the largest P_l and T_l over the layers: both are reused from layer to layer
   size_t mp = 0, mt = 0;
-  for (int l = 0; l < nd.L; ++l) { const size_t in = (size_t)nd.dims[l], out = (size_t)nd.dims[l + 1]; if (in * in > mp) mp = in * in; if (out * in > mt) mt = out * in; }
-  return Carve::span<float>(mp) + Carve::span<float>(mt) + Carve::span<double>((size_t)CRUX_MAXL * ORTH_BLOCKS);
-}
-static OrthBufs orth_carve(const NetDesc& nd, Carve& cv) {
-  size_t mp = 0, mt = 0;
-  for (int l = 0; l < nd.L; ++l) { const size_t in = (size_t)nd.dims[l], out = (size_t)nd.dims[l + 1]; if (in * in > mp) mp = in * in; if (out * in > mt) mt = out * in; }
-  OrthBufs ob; ob.P = cv.take<float>(mp); ob.T = cv.take<float>(mt); ob.part = cv.take<double>((size_t)CRUX_MAXL * ORTH_BLOCKS); return ob;
-}
+  explicit OrthPlan(const NetDesc& nd) { for (int l = 0; l < nd.L; ++l) { const size_t in = (size_t)nd.dims[l], out = (size_t)nd.dims[l + 1]; if (in * in > mp) mp = in * in; if (out * in > mt) mt = out * in; } }
+  size_t bytes() const { return Carve::span<float>(mp) + Carve::span<float>(mt) + Carve::span<double>((size_t)CRUX_MAXL * ORTH_BLOCKS); }
+  OrthBufs carve(Carve& cv) const { OrthBufs ob; ob.P = cv.take<float>(mp); ob.T = cv.take<float>(mt); ob.part = cv.take<double>((size_t)CRUX_MAXL * ORTH_BLOCKS); return ob; }
+};
 // the regularizer of every Dense layer, enqueued only: ob.part[l ORTH_BLOCKS + b] = the partial sums of layer l; accumulate: g_W += 4 beta W R. P and T are reused from
 // layer to layer (stream order)
 static int32_t orth_enqueue(crux_mlp* n, float beta, bool accumulate, const OrthBufs& ob) {
@@ -145,19 +141,6 @@ static int32_t advil_check(crux_ctx* c, const crux_mlp* actor, const crux_mlp* D
   if (B < 1 || 3 * B > (1 << 20)) return crux_fail(c, CRUX_EINVAL, "%s: batch %lld out of range (three columns per row, at most 2^20 in one forward pass)", who, (long long)B);
   return CRUX_OK;
 }
-// the one host synchronisation of a step: info row, the step's values and the status word together
-static int32_t advil_finish(crux_ctx* c, const float* dinfo, const float* adv, int n_adv, const int32_t* status, float* info_out, float* adv_out, const char* who) {
-  float* h = (float*)crux_pinned(c, sizeof(float) * (CRUX_INFO_N + 8) + 16); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
-  HIPCHK(c, hipMemcpyAsync(h, dinfo, sizeof(float) * CRUX_INFO_N, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N, adv, sizeof(float) * (size_t)n_adv, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N + 6, status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (info_out) memcpy(info_out, h, sizeof(float) * CRUX_INFO_N);
-  if (adv_out) memcpy(adv_out, h + CRUX_INFO_N, sizeof(float) * (size_t)n_adv);
-  int32_t st; memcpy(&st, h + CRUX_INFO_N + 6, sizeof st);
-  if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s", who);
-  return CRUX_OK;
-}
 
 extern "C" {
 
@@ -167,9 +150,9 @@ int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
   *value_out = 0.f;
   if (beta == 0.f || nd.L < 1) return CRUX_OK;      // nothing to add; a bare parameter vector has no layer with a weight
-  const size_t bytes = orth_bytes(nd) + 256;
+  const OrthPlan op(nd); const size_t bytes = op.bytes() + 256;
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
-  const OrthBufs ob = orth_carve(nd, cv); double* tot = cv.take<double>(1);
+  const OrthBufs ob = op.carve(cv); double* tot = cv.take<double>(1);
   int32_t rc = orth_enqueue(net, beta, accumulate != 0, ob); if (rc) return rc;
   hipLaunchKernelGGL(k_orth_value, dim3(1), dim3(1), 0, c->stream, (const double*)ob.part, nd.L, tot);
   rc = crux_launch_check(c, "k_orth_value"); if (rc) return rc;
@@ -187,7 +170,7 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float la
   const int64_t B = b->elements, NC = 3 * B; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad;
   const size_t half = (((size_t)sd * (size_t)B + 63) / 64) * 64;      // expert_sa and pi_sa, each on a 256-byte boundary
   IqBufs ib{}; rc = iq_prepare(D, B, B, true, ib, who, 2 * half); if (rc) return rc;
-  float* esa = ib.extra; float* psa = ib.extra + half;
+  float* esa = ib.own; float* psa = ib.own + half;
   const float* S = (const float*)b->col[CRUX_COL_S];
   rc = crux_dense_forward(actor, S, B, c->stream); if (rc) return rc;
   hipLaunchKernelGGL(k_advil_sa, dim3(nblk(B * sd)), dim3(256), 0, c->stream, S, (const float*)b->col[CRUX_COL_A], (const float*)crux_dense_act(actor, actor->nd.L), od, ad, B, esa, psa, ib.nanflag);
@@ -207,10 +190,10 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float la
   rc = iq_penalty_sweeps(D, B, B, ib); if (rc) return rc;
   rc = iq_add_penalty(D, ib); if (rc) return rc;
   hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, D->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
-  hipLaunchKernelGGL(k_advil_d_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, lambda_gp, ib.dinfo, ib.iq);
+  hipLaunchKernelGGL(k_advil_d_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, lambda_gp, ib.dinfo, ib.extra);
   rc = crux_launch_check(c, "k_advil_d_info"); if (rc) return rc;
   rc = adam_gated(D, ib.ssq, ib.status); if (rc) return rc;
-  return advil_finish(c, ib.dinfo, ib.iq, 4, ib.status, info_out, adv_out, who);
+  return finish_step(c, ib.dinfo, ib.extra, 4, ib.status, info_out, adv_out, who);
 }
 
 int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_bc, float beta_orth, float* info_out, float* adv_out) {
@@ -219,33 +202,31 @@ int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, floa
   int32_t rc = advil_check(c, actor, D, b, who); if (rc) return rc;
   if (!actor->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad; const bool orth = beta_orth != 0.f;
-  const size_t bytes = 2 * Carve::span<float>((size_t)sd * B) + Carve::span<float>((size_t)ad * B) + Carve::span<float>((size_t)B) + orth_bytes(an) + Carve::span<double>(ORTH_BLOCKS) + IQ_SMALL;
+  const OrthPlan op(an);
+  const size_t bytes = 2 * Carve::span<float>((size_t)sd * B) + Carve::span<float>((size_t)ad * B) + Carve::span<float>((size_t)B) + op.bytes() + Carve::span<double>(ORTH_BLOCKS) + STEP_SMALL;
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
   float* sa = cv.take<float>((size_t)sd * B); float* dsa = cv.take<float>((size_t)sd * B); float* da = cv.take<float>((size_t)ad * B); float* dy = cv.take<float>((size_t)B);
-  const OrthBufs ob = orth_carve(an, cv); double* mpart = cv.take<double>(ORTH_BLOCKS);
-  char* small = cv.take<char>(IQ_SMALL);      // info row | the step's values | stats | sum-of-squares partials | status | NaN flag, all zeroed
-  Carve sv{small, 0}; float* dinfo = sv.take<float>(CRUX_INFO_N); float* adv = sv.take<float>(6); double* stats = sv.take<double>(8); double* ssq = sv.take<double>(2 + SUMSQ_BLOCKS);
-  int32_t* status = sv.take<int32_t>(1); int32_t* nanflag = sv.take<int32_t>(1);
-  HIPCHK(c, hipMemsetAsync(small, 0, IQ_SMALL, c->stream));
+  const OrthBufs ob = op.carve(cv); double* mpart = cv.take<double>(ORTH_BLOCKS);
+  StepSmall sm; rc = step_small(c, cv, sm); if (rc) return rc;
   const float* S = (const float*)b->col[CRUX_COL_S]; const float* A = (const float*)b->col[CRUX_COL_A];
   rc = crux_dense_forward(actor, S, B, c->stream); if (rc) return rc;
   const float* mu = crux_dense_act(actor, an.L);
-  hipLaunchKernelGGL(k_advil_sa, dim3(nblk(B * sd)), dim3(256), 0, c->stream, S, A, mu, od, ad, B, (float*)nullptr, sa, nanflag);
+  hipLaunchKernelGGL(k_advil_sa, dim3(nblk(B * sd)), dim3(256), 0, c->stream, S, A, mu, od, ad, B, (float*)nullptr, sa, sm.nanflag);
   rc = crux_launch_check(c, "k_advil_sa"); if (rc) return rc;
   rc = crux_dense_forward(D, sa, B, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_advil_pi_head, dim3(1), dim3(256), 0, c->stream, (const float*)crux_dense_act(D, D->nd.L), B, (const int32_t*)nanflag, dy, stats);
+  hipLaunchKernelGGL(k_advil_pi_head, dim3(1), dim3(256), 0, c->stream, (const float*)crux_dense_act(D, D->nd.L), B, (const int32_t*)sm.nanflag, dy, sm.stats);
   rc = crux_launch_check(c, "k_advil_pi_head"); if (rc) return rc;
   rc = crux_dense_backward(D, sa, B, dy, 1.0f, false, dsa, c->stream); if (rc) return rc;                 // the discriminator's parameters are not trained here
   hipLaunchKernelGGL(k_advil_da, dim3(ORTH_BLOCKS), dim3(256), 0, c->stream, (const float*)dsa, mu, A, od, ad, B, lambda_bc, da, mpart);
   rc = crux_launch_check(c, "k_advil_da"); if (rc) return rc;
   rc = crux_dense_backward(actor, S, B, da, 1.0f, true, nullptr, c->stream); if (rc) return rc;          // nothing deferred: the regularizer adds to a complete gradient
   if (orth) { rc = orth_enqueue(actor, beta_orth, true, ob); if (rc) return rc; }
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, actor->g, (int64_t)an.n_params, (float*)nullptr, (int64_t)0, ssq, Sumsq2Fix{});
-  hipLaunchKernelGGL(k_advil_pi_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)mpart, orth ? (const double*)ob.part : (const double*)nullptr, an.L,
-                     (const double*)ssq, B, ad, lambda_bc, beta_orth, dinfo, adv);
+  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, actor->g, (int64_t)an.n_params, (float*)nullptr, (int64_t)0, sm.ssq, Sumsq2Fix{});
+  hipLaunchKernelGGL(k_advil_pi_info, dim3(1), dim3(1), 0, c->stream, (const double*)sm.stats, (const double*)mpart, orth ? (const double*)ob.part : (const double*)nullptr, an.L,
+                     (const double*)sm.ssq, B, ad, lambda_bc, beta_orth, sm.dinfo, sm.extra);
   rc = crux_launch_check(c, "k_advil_pi_info"); if (rc) return rc;
-  rc = adam_gated(actor, ssq, status); if (rc) return rc;
-  return advil_finish(c, dinfo, adv, 3, status, info_out, adv_out, who);
+  rc = adam_gated(actor, sm.ssq, sm.status); if (rc) return rc;
+  return finish_step(c, sm.dinfo, sm.extra, 3, sm.status, info_out, adv_out, who);
 }
 
 }  // extern "C"

@@ -15,9 +15,9 @@
 //   dense backward, k_sumsq2 (norm over the raw gradient), k_asaf_info, k_asaf_clip (optional: clamp to +-clip_value after the norm, ClipValue before Adam), gated Adam
 // No float atomics anywhere: two identical calls give identical bits. The engine's relu maps NaN to 0 where NNlib's propagates it, so NaN inputs are flagged and the head
 // poisons what it forms (the idiom of k_iq_expand / k_iq_head).
-// The chain (crux_asaf_batch_train) enqueues epochs x (crux_buffer_shuffle, every minibatch step) with one host synchronisation at the end. All steps share one status
-// word: k_adam_gated leaves it at CRUX_ENAN from the first NaN norm on and updates nothing after that (sac.hip), and k_asaf_info writes no row once it is set, so the
-// row of the step that stopped stays.
+// The chain (crux_asaf_batch_train) enqueues epochs x (crux_buffer_shuffle, every minibatch step) with one host synchronisation at the end: chain.h holds the loop, the
+// scratch layout behind the shuffles' staging, the read-back and the report. All steps share one status word, and k_asaf_info writes no row once it is set, so the row of
+// the step that stopped stays.
 #include "common.h"
 #include "exec.h"
 
@@ -186,7 +186,7 @@ int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_
   const AsafBufs ab = asaf_carve(cv, od, ad, NC); float* row = cv.take<float>(ASAF_ROW); int32_t* status = cv.take<int32_t>(1);
   HIPCHK(c, hipMemsetAsync(row, 0, 512, c->stream));
   rc = asaf_enqueue_step(pi, buf, off, n, d_gG, demo, d_gE, clip_value, ab, row, status); if (rc) return rc;
-  return advil_finish(c, row, row + CRUX_INFO_N, ASAF_NOUT, status, info_out, asaf_out, who);
+  return finish_step(c, row, row + CRUX_INFO_N, ASAF_NOUT, status, info_out, asaf_out, who);
 }
 
 int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo, const float* d_gE, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed,
@@ -200,37 +200,20 @@ int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo,
   const float* d_gG = (const float*)buf->col[CRUX_COL_LOGPROB];
   const int od = buf->obs_dim, ad = buf->act_dim; const int64_t NC = bmax + demo->elements;
   rc = ensure_ws(pi, NC); if (rc) return rc;      // the workspace must not be re-allocated between the steps
-  // one scratch block for the whole chain: crux_buffer_shuffle's staging (buffer.hip: crux_buffer_apply_order carves the widest column from the start of the block) stays in
-  // front of the chain's own pieces, so the later, smaller requests of the shuffles return the same block and leave the rows and the status word alone
-  size_t maxst = 0; for (int k = 0; k < CRUX_NCOLS; ++k) if (has_col(buf, k) && col_stride(buf, k) > maxst) maxst = col_stride(buf, k);
-  const size_t front = Carve::span<char>(maxst * (size_t)len + 256), rows_b = Carve::span<float>((size_t)ASAF_ROW * (size_t)epochs);
-  const size_t bytes = front + asaf_bytes(od, ad, NC) + 256 + rows_b;
+  // one scratch block for the whole chain, its own pieces behind the shuffles' staging (chain.h)
+  ChainHead hd{ASAF_ROW}; const size_t front = shuffle_front(buf);
+  const size_t bytes = front + asaf_bytes(od, ad, NC) + hd.bytes(epochs);
   char* base = (char*)crux_scratch(c, bytes); if (!base) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
-  Carve cv{base + front, 0}; const AsafBufs ab = asaf_carve(cv, od, ad, NC); int32_t* status = cv.take<int32_t>(1); float* rows = cv.take<float>((size_t)ASAF_ROW * (size_t)epochs);
-  HIPCHK(c, hipMemsetAsync(status, 0, 256 + rows_b, c->stream));
+  Carve cv{base + front, 0}; const AsafBufs ab = asaf_carve(cv, od, ad, NC); hd.carve(cv, epochs);
+  rc = hd.zero(c); if (rc) return rc;
   int64_t total = 0; int epochs_run = 0;
-  for (int ep = 0; ep < epochs; ++ep) {
-    rc = crux_buffer_shuffle(buf, shuffle_seed, shuffle_counter + (uint64_t)ep); if (rc) return rc;                      // shuffle!(D) (training.jl:36)
-    for (int64_t s0 = 0; s0 < len; s0 += batch_size) {                                                                  // partition(1:length(D), batch_size) (:40)
-      const int64_t nb = (len - s0) < batch_size ? (len - s0) : batch_size;
-      rc = asaf_enqueue_step(pi, buf, s0, nb, d_gG, demo, d_gE, clip_value, ab, rows + (size_t)ep * ASAF_ROW, status); if (rc) return rc;
-      total += 1;
-      if (max_batches > 0 && total >= max_batches) break;                                                               // :45
-    }
-    epochs_run += 1;
-    if (max_batches > 0 && total >= max_batches) break;                                                                 // :50
-  }
-  // the one host synchronisation: the status word and every epoch's row (the status word sits right in front of the rows)
-  const size_t rb = 256 + sizeof(float) * (size_t)ASAF_ROW * (size_t)epochs_run;
-  char* h = (char*)crux_pinned(c, rb); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
-  HIPCHK(c, hipMemcpyAsync(h, status, rb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int32_t st; memcpy(&st, h, sizeof st);
-  const float* hr = (const float*)(h + 256);
-  int last = epochs_run - 1;
-  if (st == CRUX_ENAN) for (int e = 0; e < epochs_run; ++e) { const float gn = hr[(size_t)e * ASAF_ROW + CRUX_INFO_GRAD_NORM]; if (gn != gn) { last = e; break; } }
-  if (epoch_rows) memcpy(epoch_rows, hr, sizeof(float) * (size_t)ASAF_ROW * (size_t)epochs_run);
-  if (info_out) { memcpy(info_out, hr + (size_t)last * ASAF_ROW, sizeof(float) * CRUX_INFO_N); info_out[CRUX_INFO_BATCHES_TRAINED] = (float)total; info_out[CRUX_INFO_EPOCHS_RUN] = (float)epochs_run; }
+  rc = chain_epochs(epochs, (len + batch_size - 1) / batch_size, max_batches,
+                    [&](int ep) { return crux_buffer_shuffle(buf, shuffle_seed, shuffle_counter + (uint64_t)ep); },
+                    [&](int ep, int64_t q) { const int64_t s0 = q * batch_size, nb = (len - s0) < batch_size ? (len - s0) : batch_size;
+                      return asaf_enqueue_step(pi, buf, s0, nb, d_gG, demo, d_gE, clip_value, ab, hd.rows + (size_t)ep * ASAF_ROW, hd.status); },
+                    &total, &epochs_run); if (rc) return rc;
+  int32_t st; const char* h; rc = hd.fetch(c, hd.run_bytes(epochs_run), who, &st, &h); if (rc) return rc;
+  const int last = chain_report(st, (const float*)(h + 256), ASAF_ROW, epochs_run, total, true, info_out, epoch_rows);
   if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s, epoch %d", who, last + 1);
   return CRUX_OK;
 }

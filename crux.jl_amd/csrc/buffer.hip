@@ -88,7 +88,8 @@ int32_t crux_buffer_per_on_push(crux_buffer* b, const int64_t* d_I, int64_t N) {
   { const int32_t rc = crux_launch_check(b->ctx, "k_per_update(push)"); if (rc) return rc; }
   return crux_per_touched(b, d_I, N, true);
 }
-// physical permutation of every column by a device int32 order: new[:,j] = old[:,order[j]]
+// physical permutation of every column by a device int32 order: new[:,j] = old[:,order[j]]. The staging is the START of the scratch block, maxst * n + 256 bytes: the chained
+// entry points keep their own pieces behind it across the shuffles (chain.h: shuffle_front restates this size and must follow it)
 int32_t crux_buffer_apply_order(crux_buffer* b, const int32_t* d_order, int64_t n) {
   crux_ctx* c = b->ctx;
   size_t maxst = 0; for (int k = 0; k < CRUX_NCOLS; ++k) if (has_col(b, k) && col_stride(b, k) > maxst) maxst = col_stride(b, k);

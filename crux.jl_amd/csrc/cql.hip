@@ -185,8 +185,7 @@ static int32_t cql_backward(crux_mlp* n, const float* sa, int64_t NB, const floa
 }
 
 // expand + forward of both nets + head: shared by the three entry points. dy1 / dy2 / y NULL: no seeds (alpha step, conservative value)
-#define CQL_SMALL 2048
-struct CqlBufs { float* sa; float* lp; float* dy1; float* dy2; float* part; double* stats; double* ssq; float* dinfo; int32_t* status; int32_t* nanflag; };
+struct CqlBufs : StepSmall { float* sa; float* lp; float* dy1; float* dy2; float* part; };
 static int32_t cql_check(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
   int32_t rc = check_sac(c, actor, q1, q2, la, b, who); if (rc) return rc;
@@ -201,14 +200,11 @@ static int32_t cql_prepare(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_buf
   size_t pf = 0;
   if (seeds) { const crux_mlp* qs[2] = {q1, q2};
     for (int t = 0; t < 2; ++t) for (int l = 0; l < qs[t]->nd.L; ++l) { const size_t f = cql_wgrad_floats(qs[t]->nd.dims[l + 1], qs[t]->nd.dims[l], NB); if (f > pf) pf = f; } }
-  const size_t bytes = 4 * ((size_t)NB * sd + (size_t)2 * N * B + (seeds ? 2 * (size_t)NB : 0) + pf) + 6 * 256 + CQL_SMALL;     // + the rounding of six takes
+  const size_t bytes = 4 * ((size_t)NB * sd + (size_t)2 * N * B + (seeds ? 2 * (size_t)NB : 0) + pf) + 6 * 256 + STEP_SMALL;     // + the rounding of six takes
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
   cb.sa = cv.take<float>((size_t)NB * sd); cb.lp = cv.take<float>((size_t)2 * N * B);
   cb.dy1 = seeds ? cv.take<float>((size_t)NB) : nullptr; cb.dy2 = seeds ? cv.take<float>((size_t)NB) : nullptr; cb.part = seeds ? cv.take<float>(pf) : nullptr;
-  char* small = cv.take<char>(CQL_SMALL);      // info row 256 B | stats 256 B | sum-of-squares partials 768 B | status 256 B | NaN flag 256 B, all zeroed
-  Carve sv{small, 0}; cb.dinfo = sv.take<float>(CRUX_INFO_N); cb.stats = sv.take<double>(8); cb.ssq = sv.take<double>(2 + SUMSQ_BLOCKS); cb.status = sv.take<int32_t>(1); cb.nanflag = sv.take<int32_t>(1);
-  HIPCHK(c, hipMemsetAsync(small, 0, CQL_SMALL, c->stream));
-  return CRUX_OK;
+  return step_small(c, cv, cb);
 }
 static int32_t cql_forward_head(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int N, float lo, float hi, float thresh, const float* d_y, int32_t use_weight,
                                 uint64_t seed, uint64_t counter, const CqlBufs& cb, float* d_samples, float* d_lp_out) {

@@ -11,8 +11,8 @@
 // The reward rewrite (:121-124): p = softmax(D(vcat(s, a))) over the staging batch, r = sum_k w_k (log(p_k + 1f-5) - log(1f0 - p_k + 1f-5)), w = [1, 0, -1/N_nda, ...].
 // No float atomics anywhere: two identical calls give identical bits. The engine's relu maps NaN to 0 where NNlib's propagates it, so the gather flags NaN inputs and the head
 // poisons what it forms (the idiom of k_iq_expand / k_iq_head).
-// A round enqueues d_epochs steps and the reward rewrite back to back. All steps share one status word: k_adam_gated leaves it at CRUX_ENAN from the first NaN norm on and
-// updates nothing after that (sac.hip), and k_offgail_reward writes nothing once it is set -- the round stops at that step without the host looking.
+// A round enqueues d_epochs steps and the reward rewrite back to back. All steps share one status word (chain.h: ChainHead, with each step's small region as its row), and
+// k_offgail_reward writes nothing once it is set -- the round stops at that step without the host looking. The read-back and the report are chain.h's.
 #include "common.h"
 #include "exec.h"
 
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_adril_relabel(const int64_t* __restrict
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------------------------
 #define OG_STEP_SMALL 1792      // per step: info row 256 B | stats 256 B | sum-of-squares partials 768 B | NaN flag 256 B | spare 256 B
-struct OgBufs { float* X; float* dz; float* xr; OgSrc* tab; double* rpart; int32_t* status; char* steps; };
+struct OgBufs { float* X; float* dz; float* xr; OgSrc* tab; double* rpart; ChainHead hd{OG_STEP_SMALL / 4}; };      // hd: a row is the first 256 B of a step's small region
 static int32_t og_check(crux_ctx* c, crux_mlp* D, crux_buffer* const* srcs, int32_t K, int64_t Bd, crux_buffer* batch, const char* who) {
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
   if (K < 2) return crux_fail(c, CRUX_EINVAL, "%s: %d sources; the demonstrations and the solver's buffer are the first two", who, K);
@@ -143,11 +143,11 @@ static int32_t og_check(crux_ctx* c, crux_mlp* D, crux_buffer* const* srcs, int3
 // one scratch block for E steps over NC columns and a reward rewrite over B columns (0: none); the shared status word and the small regions are zeroed
 static int32_t og_prepare(crux_ctx* c, int sd, int K, int64_t NC, int64_t B, int E, OgBufs& ob, const char* who) {
   const size_t bytes = Carve::span<float>((size_t)sd * NC) + Carve::span<float>((size_t)K * NC) + Carve::span<float>((size_t)sd * B) + Carve::span<OgSrc>(OFFGAIL_MAXK) +
-                       Carve::span<double>(OFFGAIL_RBLOCKS) + 256 + (size_t)E * OG_STEP_SMALL + 256;
+                       Carve::span<double>(OFFGAIL_RBLOCKS) + ob.hd.bytes(E) + 256;
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
   ob.X = cv.take<float>((size_t)sd * NC); ob.dz = cv.take<float>((size_t)K * NC); ob.xr = cv.take<float>((size_t)sd * B); ob.tab = cv.take<OgSrc>(OFFGAIL_MAXK);
-  ob.rpart = cv.take<double>(OFFGAIL_RBLOCKS); ob.status = cv.take<int32_t>(1); ob.steps = cv.take<char>((size_t)E * OG_STEP_SMALL);
-  HIPCHK(c, hipMemsetAsync(ob.rpart, 0, Carve::span<double>(OFFGAIL_RBLOCKS) + 256 + (size_t)E * OG_STEP_SMALL, c->stream));
+  ob.rpart = cv.take<double>(OFFGAIL_RBLOCKS); ob.hd.carve(cv, E);
+  HIPCHK(c, hipMemsetAsync(ob.rpart, 0, Carve::span<double>(OFFGAIL_RBLOCKS) + ob.hd.extent, c->stream));      // the reward's partials sit right in front of the head
   return CRUX_OK;
 }
 static int32_t og_upload_sources(crux_ctx* c, crux_buffer* const* srcs, int K, OgSrc* h_tab, const OgBufs& ob) {
@@ -157,7 +157,7 @@ static int32_t og_upload_sources(crux_ctx* c, crux_buffer* const* srcs, int K, O
 }
 struct OgStep { float* dinfo; double* stats; double* ssq; int32_t* nanflag; };
 static OgStep og_step(const OgBufs& ob, int e) {
-  Carve sv{ob.steps + (size_t)e * OG_STEP_SMALL, 0}; OgStep t;
+  Carve sv{(char*)ob.hd.rows + (size_t)e * OG_STEP_SMALL, 0}; OgStep t;
   t.dinfo = sv.take<float>(CRUX_INFO_N); t.stats = sv.take<double>(8); t.ssq = sv.take<double>(2 + SUMSQ_BLOCKS); t.nanflag = sv.take<int32_t>(1); return t;
 }
 // step e of a call, enqueued only
@@ -174,7 +174,7 @@ static int32_t og_enqueue_step(crux_mlp* D, const crux_buffer* f, int K, int64_t
   hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   hipLaunchKernelGGL(k_offgail_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, NC, dinfo);
   rc = crux_launch_check(c, "k_offgail_info"); if (rc) return rc;
-  return adam_gated(D, ssq, ob.status);
+  return adam_gated(D, ssq, ob.hd.status);
 }
 static int32_t og_enqueue_reward(crux_mlp* D, crux_buffer* b, int K, const OgBufs& ob, const int32_t* status) {
   crux_ctx* c = D->ctx; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad; const int64_t B = b->elements;
@@ -209,18 +209,14 @@ static int32_t og_run(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64
   if (!D->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
   int32_t rc = ensure_ws(D, NC > B ? NC : B); if (rc) return rc;      // the workspace must not be re-allocated between the steps and the reward's forward pass
   OgBufs ob{}; rc = og_prepare(c, sd, K, NC, B, E, ob, who); if (rc) return rc;
-  const size_t hb = sizeof(OgSrc) * OFFGAIL_MAXK, rb = (size_t)E * OG_STEP_SMALL + 256;
+  const size_t hb = sizeof(OgSrc) * OFFGAIL_MAXK, rb = ob.hd.run_bytes(E);
   char* h = (char*)crux_pinned(c, hb + rb); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
   rc = og_upload_sources(c, sources, K, (OgSrc*)h, ob); if (rc) return rc;
   for (int e = 0; e < E; ++e) { rc = og_enqueue_step(D, f, K, Bd, seed, counter0 + (uint64_t)e, ob, e); if (rc) return rc; }
-  if (batch) { rc = og_enqueue_reward(D, batch, K, ob, ob.status); if (rc) return rc; }
-  // the one host synchronisation: the status word and every step's info row (status sits right in front of the steps' regions)
-  HIPCHK(c, hipMemcpyAsync(h + hb, ob.status, rb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int32_t st; memcpy(&st, h + hb, sizeof st);
-  int last = E - 1;
-  if (st == CRUX_ENAN) for (int e = 0; e < E; ++e) { float gn; memcpy(&gn, h + hb + 256 + (size_t)e * OG_STEP_SMALL + sizeof(float) * CRUX_INFO_GRAD_NORM, sizeof gn); if (gn != gn) { last = e; break; } }
-  if (info_out) memcpy(info_out, h + hb + 256 + (size_t)last * OG_STEP_SMALL, sizeof(float) * CRUX_INFO_N);      // the same info Dict goes to every train!: the last one's entries stay (training.jl:22-24)
+  if (batch) { rc = og_enqueue_reward(D, batch, K, ob, ob.hd.status); if (rc) return rc; }
+  // the one host synchronisation, behind the source table in the same pinned block. The same info Dict goes to every train!: the last one's entries stay (training.jl:22-24)
+  int32_t st; const char* hh; rc = ob.hd.fetch(c, rb, who, &st, &hh, hb); if (rc) return rc;
+  const int last = chain_report(st, (const float*)(hh + 256), ob.hd.stride, E, E, false, info_out, nullptr);
   if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s, discriminator epoch %d", who, last + 1);
   return CRUX_OK;
 }

@@ -124,11 +124,9 @@ __global__ void k_iq_info(const double* __restrict__ st, const double* __restric
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------------------------
-#define IQ_SMALL 2048
-struct IqBufs {
+struct IqBufs : StepSmall {      // extra: the six iq_loss values (advil.hip: the step's four)
   float* X; float* dy; float* Z[CRUX_MAXL + 1]; float* G[CRUX_MAXL + 1]; float* gb[2]; float* dbar; float* t1; float* t2;
-  double* stats; double* ssq; float* dinfo; float* iq; int32_t* status; int32_t* nanflag;
-  float* extra;      // extra_floats of the caller's own behind everything else (advil.hip: expert_sa and pi_sa)
+  float* own;      // own_floats of the caller's behind everything else (advil.hip: expert_sa and pi_sa)
 };
 static bool iq_has_tanh(const NetDesc& nd) { for (int l = 0; l < nd.L; ++l) if (nd.acts[l] == CRUX_ACT_TANH) return true; return false; }
 static int32_t iq_check_net(crux_ctx* c, const crux_mlp* n, const char* who) {
@@ -139,25 +137,22 @@ static int32_t iq_check_net(crux_ctx* c, const crux_mlp* n, const char* who) {
     return crux_fail(c, CRUX_EUNSUP, "%s: activation %d of layer %d", who, nd.acts[l], l + 1);
   return CRUX_OK;
 }
-// scratch for nl loss columns (0 or B) and H penalty columns; second-order buffers only when want_pg; extra_floats: a piece for the caller in the same block
-static int32_t iq_prepare(crux_mlp* n, int64_t nl, int64_t H, bool want_pg, IqBufs& ib, const char* who, size_t extra_floats = 0) {
+// scratch for nl loss columns (0 or B) and H penalty columns; second-order buffers only when want_pg; own_floats: a piece for the caller in the same block
+static int32_t iq_prepare(crux_mlp* n, int64_t nl, int64_t H, bool want_pg, IqBufs& ib, const char* who, size_t own_floats = 0) {
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd; const int64_t NC = 2 * nl + H; const size_t np = (size_t)nd.n_params;
   size_t fl = (size_t)nd.dims[0] * NC + (size_t)nd.dims[nd.L] * NC;
   for (int l = 1; l <= nd.L; ++l) fl += (size_t)nd.dims[l] * NC;        // Z_l
   for (int l = 0; l < nd.L; ++l) fl += (size_t)nd.dims[l] * NC;         // G_l
   if (want_pg) fl += 3 * (size_t)nd.maxdim * H + 2 * np;
-  const size_t bytes = 4 * fl + 256 * (2 * CRUX_MAXL + 10) + IQ_SMALL + (extra_floats ? Carve::span<float>(extra_floats) : 0);
+  const size_t bytes = 4 * fl + 256 * (2 * CRUX_MAXL + 10) + STEP_SMALL + (own_floats ? Carve::span<float>(own_floats) : 0);
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
   ib.X = cv.take<float>((size_t)nd.dims[0] * NC); ib.dy = cv.take<float>((size_t)nd.dims[nd.L] * NC);
   for (int l = 1; l <= nd.L; ++l) ib.Z[l] = cv.take<float>((size_t)nd.dims[l] * NC);
   for (int l = 0; l < nd.L; ++l) ib.G[l] = cv.take<float>((size_t)nd.dims[l] * NC);
   if (want_pg) { ib.gb[0] = cv.take<float>((size_t)nd.maxdim * H); ib.gb[1] = cv.take<float>((size_t)nd.maxdim * H); ib.dbar = cv.take<float>((size_t)nd.maxdim * H);
                  ib.t1 = cv.take<float>(np); ib.t2 = cv.take<float>(np); }
-  char* small = cv.take<char>(IQ_SMALL);      // info row 256 B | iq row 256 B | stats 256 B | sum-of-squares partials 768 B | status 256 B | NaN flag 256 B, all zeroed
-  Carve sv{small, 0}; ib.dinfo = sv.take<float>(CRUX_INFO_N); ib.iq = sv.take<float>(6); ib.stats = sv.take<double>(8); ib.ssq = sv.take<double>(2 + SUMSQ_BLOCKS);
-  ib.status = sv.take<int32_t>(1); ib.nanflag = sv.take<int32_t>(1);
-  ib.extra = extra_floats ? cv.take<float>(extra_floats) : nullptr;
-  HIPCHK(c, hipMemsetAsync(small, 0, IQ_SMALL, c->stream));
+  { const int32_t rc = step_small(c, cv, ib); if (rc) return rc; }
+  ib.own = own_floats ? cv.take<float>(own_floats) : nullptr;
   if (want_pg) HIPCHK(c, hipMemsetAsync(ib.t1, 0, 4 * np, c->stream));       // T1's bias entries stay zero; t2 is zeroed below when there is no second-order sweep
   if (want_pg) HIPCHK(c, hipMemsetAsync(ib.t2, 0, 4 * np, c->stream));
   return CRUX_OK;
@@ -299,20 +294,10 @@ int32_t crux_iq_step(crux_mlp* q, crux_buffer* b, int64_t n_policy, float gamma_
     rc = iq_add_penalty(q, ib); if (rc) return rc;
   }
   hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, q->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
-  hipLaunchKernelGGL(k_iq_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, Bp, H, gp, lambda_gp, reg, alpha_reg, ib.dinfo, ib.iq);
+  hipLaunchKernelGGL(k_iq_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, Bp, H, gp, lambda_gp, reg, alpha_reg, ib.dinfo, ib.extra);
   rc = crux_launch_check(c, "k_iq_info"); if (rc) return rc;
   rc = adam_gated(q, ib.ssq, ib.status); if (rc) return rc;
-  // the one host synchronisation: info row, iq values and status together
-  float* h = (float*)crux_pinned(c, sizeof(float) * (CRUX_INFO_N + 8) + 16); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
-  HIPCHK(c, hipMemcpyAsync(h, ib.dinfo, sizeof(float) * CRUX_INFO_N, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N, ib.iq, sizeof(float) * 6, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N + 6, ib.status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (info_out) memcpy(info_out, h, sizeof(float) * CRUX_INFO_N);
-  if (iq_out) memcpy(iq_out, h + CRUX_INFO_N, sizeof(float) * 6);
-  int32_t st; memcpy(&st, h + CRUX_INFO_N + 6, sizeof st);
-  if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s", who);
-  return CRUX_OK;
+  return finish_step(c, ib.dinfo, ib.extra, 6, ib.status, info_out, iq_out, who);
 }
 
 }  // extern "C"

@@ -385,17 +385,22 @@ static int32_t check_sac(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q
   if (la && la->nd.n_params < 1) return crux_fail(c, CRUX_EINVAL, "%s: log_alpha handle has no parameters", who);
   return CRUX_OK;
 }
-static int32_t finish_step(crux_ctx* c, const float* d_info, const int32_t* d_status, float* info_out, const char* who) {
+// the one host synchronisation of a step: the info row, (d_extra != NULL) the n_extra <= 6 values of its own the step leaves, and the status word together. The entry points
+// with values of their own refuse a recorded sequence before anything is enqueued (iq_check_net), so the recording branch is reached with d_extra == NULL only
+static int32_t finish_step(crux_ctx* c, const float* d_info, const float* d_extra, int n_extra, const int32_t* d_status, float* info_out, float* extra_out, const char* who) {
   if (crux_exec_recording(c)) { crux_exec_add_readback(c, info_out, d_info, d_status, who); return CRUX_OK; }   // fulfilled by crux_exec_run after the fused launch
-  float* h = (float*)crux_pinned(c, sizeof(float) * CRUX_INFO_N + 16); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
+  float* h = (float*)crux_pinned(c, sizeof(float) * (CRUX_INFO_N + 8) + 16); if (!h) return crux_fail(c, CRUX_ENOMEM, "%s: pinned staging", who);
   HIPCHK(c, hipMemcpyAsync(h, d_info, sizeof(float) * CRUX_INFO_N, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (d_extra) HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N, d_extra, sizeof(float) * (size_t)n_extra, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h + CRUX_INFO_N + 6, d_status, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (info_out) memcpy(info_out, h, sizeof(float) * CRUX_INFO_N);
-  int32_t st; memcpy(&st, h + CRUX_INFO_N, sizeof st);
+  if (d_extra && extra_out) memcpy(extra_out, h + CRUX_INFO_N, sizeof(float) * (size_t)n_extra);
+  int32_t st; memcpy(&st, h + CRUX_INFO_N + 6, sizeof st);
   if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s", who);
   return CRUX_OK;
 }
+static int32_t finish_step(crux_ctx* c, const float* d_info, const int32_t* d_status, float* info_out, const char* who) { return finish_step(c, d_info, nullptr, 0, d_status, info_out, nullptr, who); }
 
 // train!(critic, td_loss) for wide DiscreteNetwork critics (C3: 8-256-256-4) on the dense engine; crux_td_step (train.hip) routes here.
 int32_t crux_td_step_dense(crux_mlp* net, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out, float* d_err) {

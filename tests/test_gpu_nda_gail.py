@@ -309,6 +309,23 @@ def test_nan_in_the_demonstrations_stops_the_round(gpu_ctx):
     assert rc == L.ENAN and np.isnan(raw[L.INFO["grad_norm"]]) and _same(a2.D.get_params(), b.D.get_params()) and _same(raw[:2], rD[:2])
 
 
+def test_nan_in_the_negative_demonstrations_names_the_second_chain(gpu_ctx):
+    """the other branch of the round's report: D's chain is clean, Dnda's meets the NaN. Ten rows of the negative demonstrations' :s hold one; an epoch's three pairs read
+    192 of the 201 rows, so at most nine of them sit behind what the first epoch reads. D ends where the host loop over all of its epochs ends, its row is that loop's
+    last, and the message names nda_discriminator."""
+    c = case(SHAPES[0]); B = c["B"]; c["nda"]["s"][1, 40:50] = np.nan
+    a, b = Setup(gpu_ctx, c), Setup(gpu_ctx, c)
+    r0 = a.batch["r"].copy()
+    rc, rD, rN, out3 = _round(a, B, 3, 2, 0, 0)
+    msg = (gpu_ctx.lib.crux_last_error(gpu_ctx.h) or b"").decode()
+    assert rc == L.ENAN and "NaN detected" in msg and "nda_discriminator epoch 1" in msg and "the batch is not rewritten" in msg, msg
+    rows, total = _host_loop(b.D, b.demo, b.copyD, B, 3, 0)
+    assert total == 9 and _same(a.D.get_params(), b.D.get_params()) and _same(rD[:2], rows[-1][:2]) and np.isfinite(rD[L.INFO["grad_norm"]])
+    assert rD[L.INFO["batches_trained"]] == 9 and rD[L.INFO["epochs_run"]] == 3
+    assert np.isnan(rN[L.INFO["grad_norm"]]) and rN[L.INFO["epochs_run"]] == 2
+    assert _same(a.batch["r"], r0)
+
+
 # ---- 7. refusals ------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_invalid_arguments_are_refused_without_a_launch(gpu_ctx):
     c = case(SHAPES[0]); st = Setup(gpu_ctx, c); lib = gpu_ctx.lib; out = np.zeros(3, np.float32)
