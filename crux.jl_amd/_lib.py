@@ -61,6 +61,9 @@ SIGNATURES = {
     "crux_mlp_forward": (i32, [vp, vp, i64, vp]),
     "crux_mlp_forward_host": (i32, [vp, vp, i64, vp]),
     "crux_mlp_copy": (i32, [vp, vp]),
+    "crux_mlp_set_spectral": (i32, [vp, vp, vp, u64, u32]),
+    "crux_mlp_get_spectral": (i32, [vp, vp, vp, vp]),
+    "crux_mlp_spectral_layers": (i32, [vp, vp]),
     "crux_polyak": (i32, [vp, vp, f32]),
     "crux_adam_init": (i32, [vp, f64, f64, f64, f64]),
     "crux_adam_get_state": (i32, [vp, vp, vp, vp]),

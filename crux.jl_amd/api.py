@@ -18,7 +18,7 @@ import numpy as np   # noqa: F401
 from . import _lib as L   # noqa: F401
 from .core import *   # noqa: F401,F403
 from .core import (  # noqa: F401
-    ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
+    ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DenseSN, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, HostMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
     PolicyParams, SAMPLE_SEED, Sampler, SimpleGridWorld, SquashedGaussianPolicy, SynthMDP, TrainingParams, _F32_KEYS, _Loss, _batch_train_seam, _ensure_opt, _fill_block,
     _fill_importance_weights, _info_dict, _leaves, _np_dtype, _rollout_cfg, _train_cfg, _train_seam, _uses_seam, _vp, a2c_loss, actor, batch_train_, buffer_like, capacity,

@@ -209,8 +209,23 @@ class Dense:
         self.inp, self.out, self.act = int(inp), int(out), act if isinstance(act, str) else getattr(act, "__name__", "identity")
 
 
+class DenseSN(Dense):
+    """DenseSN(in, out, act; n_iterations=1) (src/extras/spectral_normalization.jl:22-42): a Dense layer whose weight is divided by its largest singular value,
+    estimated by `n_iterations` rounds of power iteration on the persistent, non-trainable `u` in EVERY forward call. Trainable: (weight, bias) only.
+    u: the initial vector (out values), or None for randn(Float32, out, 1) drawn from the policy's seed."""
+
+    def __init__(self, inp, out, act="identity", n_iterations=1, u=None):
+        super().__init__(inp, out, act)
+        self.n_iterations = int(n_iterations)
+        if not 1 <= self.n_iterations <= 8:
+            raise ValueError("DenseSN: n_iterations = %d, must be 1..8" % self.n_iterations)
+        self.u = None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1)
+        if self.u is not None and self.u.size != self.out:
+            raise ValueError("DenseSN: u has %d values, the layer has %d outputs" % (self.u.size, self.out))
+
+
 class Chain:
-    """Flux.Chain(Dense...)."""
+    """Flux.Chain(Dense | DenseSN ...)."""
 
     def __init__(self, *layers):
         self.layers = list(layers)
@@ -225,6 +240,11 @@ class Chain:
     @property
     def acts(self):
         return [L.ACT[l.act] for l in self.layers]
+
+    @property
+    def sn_iterations(self):
+        """n_iterations per layer, 0 for a plain Dense."""
+        return [l.n_iterations if isinstance(l, DenseSN) else 0 for l in self.layers]
 
 
 class NetworkPolicy:
@@ -241,6 +261,40 @@ class NetworkPolicy:
         self.h = h
         self.ctx.check(self.ctx.lib.crux_mlp_init_glorot(self.h, int(seed), int(stream), float(extra_init)))
         self.optimizer = None
+        if any(network.sn_iterations):
+            self.set_spectral([l.u for l in network.layers if isinstance(l, DenseSN)], seed=seed, stream=stream)
+
+    def set_spectral(self, us=None, seed=0, stream=0):
+        """Switch the DenseSN layers of the chain on (crux_mlp_set_spectral). us: one u per SN layer; a missing one (or us=None) is drawn as standard normals."""
+        sn = [l for l in self.network.layers if isinstance(l, DenseSN)]
+        it = (C.c_int32 * len(self.network.layers))(*self.network.sn_iterations)
+        us = list(us) if us is not None else [None] * len(sn)
+        if all(u is None for u in us):
+            self.ctx.check(self.ctx.lib.crux_mlp_set_spectral(self.h, it, None, int(seed), int(stream)))
+            return
+        if any(u is None for u in us):      # some given: draw the device's normals first, then overwrite the given ones
+            self.ctx.check(self.ctx.lib.crux_mlp_set_spectral(self.h, it, None, int(seed), int(stream)))
+            us = [d if u is None else u for u, (d, _, _) in zip(us, self.spectral_state())]
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(u, np.float32).reshape(-1) for u in us]), np.float32)
+        if flat.size != sum(l.out for l in sn):
+            raise ValueError("set_spectral: %d values of u for SN layers with %d outputs in all" % (flat.size, sum(l.out for l in sn)))
+        self.ctx.check(self.ctx.lib.crux_mlp_set_spectral(self.h, it, _vp(flat), int(seed), int(stream)))
+
+    @property
+    def is_spectral(self):
+        return self.network is not None and any(self.network.sn_iterations)
+
+    def spectral_state(self):
+        """[(u, v, sigma)] of the DenseSN layers after the last forward call (crux_mlp_get_spectral; v and sigma are zero before the first one)."""
+        sn = [l for l in self.network.layers if isinstance(l, DenseSN)]
+        if not sn:
+            return []
+        u, v, s = np.empty(sum(l.out for l in sn), np.float32), np.empty(sum(l.inp for l in sn), np.float32), np.empty(len(sn), np.float32)
+        self.ctx.check(self.ctx.lib.crux_mlp_get_spectral(self.h, _vp(u), _vp(v), _vp(s)))
+        out, uo, vo = [], 0, 0
+        for k, l in enumerate(sn):
+            out.append((u[uo:uo + l.out].copy(), v[vo:vo + l.inp].copy(), float(s[k]))); uo += l.out; vo += l.inp
+        return out
 
     # Flux.params(pi) as one flat Float32 vector in Flux order (W1,b1,W2,b2,...,extras)
     @property
@@ -401,6 +455,16 @@ def _leaves(pi):
     return [pi]
 
 
+def refuse_spectral(pi, who):
+    """DenseSN is implemented for discriminators only: the rollout and every policy / critic learner read the raw weights (cruxhip.h, DenseSN paragraph)."""
+    if pi is None:
+        return
+    for q in _leaves(pi):
+        if isinstance(q, NetworkPolicy) and q.is_spectral:
+            raise ValueError("%s: a policy or critic network contains a DenseSN layer; spectral normalisation is implemented for discriminators "
+                             "(OnPolicyGAIL, OffPolicyGAIL, NDA_GAIL_JS) only" % who)
+
+
 def polyak_average_(to, frm, tau=1.0):
     """polyak_average!(to, from, tau) (src/policies.jl:48-59) over every layer of the (possibly composite) policy."""
     for t, f in zip(_leaves(to), _leaves(frm)):
@@ -428,6 +492,8 @@ def clone_policy(pi):
     else:
         new = ContinuousNetwork(pi.network, ctx=pi.ctx)
     copyto_(new, pi)
+    if new.is_spectral:      # deepcopy carries u along (copyto! does not)
+        new.set_spectral([u for u, _, _ in pi.spectral_state()])
     return new
 
 
@@ -436,6 +502,8 @@ class PolicyParams:
 
     def __init__(self, pi, space=None, pi_explore=None, pi_minus=None, pa=None):
         self.pi, self.pi_explore, self.pi_minus = pi, pi_explore if pi_explore is not None else pi, pi_minus
+        for q in (pi, pi_explore, pi_minus, pa):
+            refuse_spectral(q, "PolicyParams")
         self.pa = pa                                   # nominal action policy (policies.jl:17): the reference distribution of :importance_weight (sampler.jl:108-111)
         a = actor(pi)
         self.space = space or (DiscreteSpace(len(a.outputs), a.outputs) if isinstance(a, DiscreteNetwork) else ContinuousSpace(a.network.dims[-1]))

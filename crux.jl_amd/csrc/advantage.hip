@@ -174,7 +174,7 @@ int32_t crux_first_episode_metrics(crux_buffer* b, int32_t n_envs, int64_t T, fl
   return CRUX_OK;
 }
 
-int32_t crux_fill_gae_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int32_t source, int32_t target) {
+int32_t crux_fill_gae_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int32_t source, int32_t target) { CRUX_PLAIN_ONLY("crux_fill_gae_keys", critic);
   if (!b || !critic) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
   if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_gae!: buffer lacks the source / target column (%d -> %d)", source, target);
@@ -200,11 +200,12 @@ int32_t crux_fill_gae_keys(crux_buffer* b, crux_mlp* critic, float lambda, float
   if (h) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
   return CRUX_OK;
 }
-int32_t crux_fill_gae(crux_buffer* b, crux_mlp* critic, float lambda, float gamma) { return crux_fill_gae_keys(b, critic, lambda, gamma, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
+int32_t crux_fill_gae(crux_buffer* b, crux_mlp* critic, float lambda, float gamma) { CRUX_PLAIN_ONLY("crux_fill_gae", critic); return crux_fill_gae_keys(b, critic, lambda, gamma, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
 
 // fill_gae! + fill_returns! for n buffers (the tail of a batched rollout): everything is enqueued, ONE host synchronisation reads the n NaN flags
 int32_t crux_fill_gae_multi(int32_t n, crux_buffer* const* bufs, crux_mlp* const* critics, float lambda, float gamma, int32_t with_returns) {
   if (n < 1 || !bufs || !critics) return CRUX_EINVAL;
+  for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_fill_gae_multi", critics[i]);
   crux_ctx* c = bufs[0]->ctx; size_t vb = 0;
   for (int i = 0; i < n; ++i) {
     crux_buffer* b = bufs[i]; crux_mlp* critic = critics[i]; if (!b || !critic) return CRUX_EINVAL;
@@ -276,7 +277,7 @@ int32_t crux_whiten_multi(int32_t n, crux_buffer* const* bufs, int32_t key) {
 
 // fill_gae!(data, ep, V, lambda, gamma) / fill_returns!(data, ep, gamma) as terminate_episode! applies them to the block a steps! call just
 // produced (sampler.jl:53-57,140-148), on the ring rows [first_row, first_row + n_rows) mod capacity that the block was pushed to.
-int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) {
+int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) { CRUX_PLAIN_ONLY("crux_fill_gae_rows_keys", critic);
   if (!b || !critic) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
   if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_gae!: buffer lacks the source / target column (%d -> %d)", source, target);
@@ -308,7 +309,7 @@ int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, 
   if (h) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
   return CRUX_OK;
 }
-int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { return crux_fill_gae_rows_keys(b, critic, lambda, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
+int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { CRUX_PLAIN_ONLY("crux_fill_gae_rows", critic); return crux_fill_gae_rows_keys(b, critic, lambda, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
 int32_t crux_fill_returns_rows_keys(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) {
   if (!b) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
@@ -396,7 +397,7 @@ int32_t crux_nda_adv_enqueue(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float la
   *flags_out = flags;
   return crux_launch_check(c, "k_nda_gae2 / k_nda_whiten2");
 }
-extern "C" int32_t crux_nda_advantages(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float lambda, float gamma) {
+extern "C" int32_t crux_nda_advantages(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float lambda, float gamma) { CRUX_PLAIN_ONLY("crux_nda_advantages", V, Vc);
   if (!b || !V || !Vc) return CRUX_EINVAL;
   crux_ctx* c = b->ctx; const char* who = "nda_advantages";
   int32_t rc = crux_nda_adv_check(b, V, Vc, who); if (rc) return rc;
@@ -451,7 +452,7 @@ __global__ void k_importance_fills(const float* __restrict__ iw, const uint8_t* 
     if (cum) for (int64_t k = start; k <= i; ++k) cum[phys(k)] = w;                                                          // :292-299
   }
 }
-extern "C" int32_t crux_importance_weight_rows(crux_buffer* b, crux_mlp* nominal, int32_t head, int64_t first_row, int64_t n_rows) {
+extern "C" int32_t crux_importance_weight_rows(crux_buffer* b, crux_mlp* nominal, int32_t head, int64_t first_row, int64_t n_rows) { CRUX_PLAIN_ONLY("crux_importance_weight_rows", nominal);
   if (!b || !nominal) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
   if (!has_col(b, CRUX_COL_IMPORTANCE_WEIGHT) || !has_col(b, CRUX_COL_LOGPROB)) return crux_fail(c, CRUX_EINVAL, "importance_weight: the buffer needs :importance_weight and :logprob columns");

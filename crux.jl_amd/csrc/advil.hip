@@ -144,7 +144,7 @@ static int32_t advil_check(crux_ctx* c, const crux_mlp* actor, const crux_mlp* D
 
 extern "C" {
 
-int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float* value_out) {
+int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float* value_out) { CRUX_PLAIN_ONLY("crux_orthogonal_reg", net);
   if (!net || !value_out) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const char* who = "OrthogonalRegularizer"; const NetDesc& nd = net->nd;
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
@@ -162,7 +162,7 @@ int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float
   return CRUX_OK;
 }
 
-int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_gp, float gp_target, uint64_t seed, uint64_t counter, float* info_out, float* adv_out) {
+int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_gp, float gp_target, uint64_t seed, uint64_t counter, float* info_out, float* adv_out) { CRUX_PLAIN_ONLY("crux_advil_d_step", actor, D);
   if (!actor || !D || !b) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "advil_d_loss"; const NetDesc& nd = D->nd;
   int32_t rc = advil_check(c, actor, D, b, who); if (rc) return rc;
@@ -196,7 +196,7 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float la
   return finish_step(c, ib.dinfo, ib.extra, 4, ib.status, info_out, adv_out, who);
 }
 
-int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_bc, float beta_orth, float* info_out, float* adv_out) {
+int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_bc, float beta_orth, float* info_out, float* adv_out) { CRUX_PLAIN_ONLY("crux_advil_actor_step", actor, D);
   if (!actor || !D || !b) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "advil_pi_loss"; const NetDesc& an = actor->nd;
   int32_t rc = advil_check(c, actor, D, b, who); if (rc) return rc;

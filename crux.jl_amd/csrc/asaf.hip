@@ -160,7 +160,7 @@ static int32_t asaf_enqueue_step(crux_mlp* pi, const crux_buffer* b, int64_t off
 
 extern "C" {
 
-int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int64_t n_rows, float* d_out) {
+int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int64_t n_rows, float* d_out) { CRUX_PLAIN_ONLY("crux_asaf_freeze", pi);
   if (!pi || !buf || !d_out) return CRUX_EINVAL;
   crux_ctx* c = pi->ctx; const char* who = "asaf_freeze";
   int32_t rc = asaf_check_pi(c, pi, buf, who); if (rc) return rc;
@@ -176,7 +176,7 @@ int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int6
   return CRUX_OK;
 }
 
-int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_t n, const float* d_gG, crux_buffer* demo, const float* d_gE, float clip_value, float* info_out, float* asaf_out) {
+int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_t n, const float* d_gG, crux_buffer* demo, const float* d_gE, float clip_value, float* info_out, float* asaf_out) { CRUX_PLAIN_ONLY("crux_asaf_actor_step", pi);
   if (!pi || !buf || !demo || !d_gG || !d_gE) return CRUX_EINVAL;
   crux_ctx* c = pi->ctx; const char* who = "asaf_actor_loss";
   int32_t rc = asaf_check_step(c, pi, buf, off, n, demo, who); if (rc) return rc;
@@ -190,7 +190,7 @@ int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_
 }
 
 int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo, const float* d_gE, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed,
-                              uint64_t shuffle_counter, float clip_value, float* info_out, float* epoch_rows) {
+                              uint64_t shuffle_counter, float clip_value, float* info_out, float* epoch_rows) { CRUX_PLAIN_ONLY("crux_asaf_batch_train", pi);
   if (!pi || !buf || !demo || !d_gE) return CRUX_EINVAL;
   crux_ctx* c = pi->ctx; const char* who = "batch_train! (asaf_actor_loss)";
   if (batch_size < 1 || epochs < 1 || epochs > 65536) return crux_fail(c, CRUX_EINVAL, "%s: batch_size = %d, epochs = %d out of range", who, batch_size, epochs);

@@ -87,7 +87,7 @@ int32_t crux_comm_destroy(crux_ctx* c) {
 int32_t crux_comm_size(const crux_ctx* c) { return c && c->comm ? c->comm_n : 1; }
 // exact data-parallel step (k = 1): crux_loss_grad on the local minibatch -> crux_allreduce_grads (SUM over ranks, stream-ordered) ->
 // crux_adam_apply(net, 1/nranks): every rank applies the same update, parameters and Adam state stay replicated
-int32_t crux_allreduce_grads(crux_mlp* net) {
+int32_t crux_allreduce_grads(crux_mlp* net) { CRUX_PLAIN_ONLY("crux_allreduce_grads", net);
   if (!net) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; if (!c->comm) return CRUX_OK;
   RcclApi* api = rccl(c); if (!api) return CRUX_ERCCL;
@@ -326,7 +326,7 @@ int32_t crux_peer_probe(crux_ctx* c, int32_t rounds, int32_t first_bound_ms, int
 int32_t crux_peer_size(const crux_ctx* c) { return c && c->peer_n > 1 ? c->peer_n : 1; }
 int32_t crux_peer_rank(const crux_ctx* c) { return c && c->peer_n > 1 ? c->peer_rank : 0; }
 
-int32_t crux_allreduce_mean(crux_mlp* net) {
+int32_t crux_allreduce_mean(crux_mlp* net) { CRUX_PLAIN_ONLY("crux_allreduce_mean", net);
   if (!net) return CRUX_EINVAL;
   crux_mlp* one[1] = {net}; return crux_comm_allreduce_mean_impl(net->ctx, one, 1);
 }

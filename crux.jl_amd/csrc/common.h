@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include <initializer_list>
 #include <cstring>
 #include "switches.h"
 #include <cstdio>
@@ -137,6 +138,16 @@ struct NetDesc {
   int32_t maxdim;
 };
 
+// DenseSN state of a handle (spectral.hip; src/extras/spectral_normalization.jl): allocated by crux_mlp_set_spectral, never inside a chain. One device block:
+// weff (the effective weights W / sigma at the offsets of the flat parameters, written by every forward pass), u, v and sigma of the SN layers, the layer table.
+struct crux_sn_layer { int32_t in, out, woff, uoff, voff, iters, idx, pad; };
+struct crux_sn {
+  int32_t iters[CRUX_MAXL] = {0};      // n_iterations per layer; 0 = plain Dense
+  int32_t n_sn = 0, n_u = 0, n_v = 0;
+  void* block = nullptr;
+  float* weff = nullptr; float* u = nullptr; float* v = nullptr; float* sigma = nullptr; crux_sn_layer* tab = nullptr;
+};
+
 struct crux_mlp {
   crux_ctx* ctx = nullptr;
   NetDesc nd{};
@@ -150,6 +161,7 @@ struct crux_mlp {
   float squash = 0.f;   // > 0: SquashedGaussianPolicy with this ascale (policies.jl:353-400) wherever the Gaussian head is used
   float* ws = nullptr;  // dense-engine workspace (dense.hip): cached activations 1..L + two delta buffers, capacity ws_B samples
   int64_t ws_B = 0;
+  crux_sn* sn = nullptr;   // NULL: a plain Chain(Dense...), every path as without DenseSN
 };
 
 struct crux_buffer {
@@ -255,4 +267,11 @@ struct Sumsq2Fix { const float* part[2]; int32_t out1[2], in0[2], woff[2], boff[
 int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const float* d_dy, float gscale, bool want_g, float* d_dx, hipStream_t st, Sumsq2Fix* defer = nullptr, int defer_slot = 0, int32_t* nanflags = nullptr);
 float* crux_dense_act(crux_mlp* n, int l);
 int32_t crux_td_step_dense(crux_mlp* net, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out, float* d_err);   // sac.hip
+// spectral.hip: the power iteration + effective weights of one forward pass, the conversion of the weight gradient after one backward pass (enqueued only)
+int32_t crux_sn_power(crux_mlp* n, hipStream_t st);
+int32_t crux_sn_grad(crux_mlp* n, hipStream_t st);
+void crux_sn_free(crux_mlp* n);
+// Entries whose kernels read n->p directly refuse a handle with DenseSN layers (CRUX_EUNSUP, the message names the entry): they would silently use un-normalised weights.
+int32_t crux_plain_only(const char* entry, std::initializer_list<const crux_mlp*> nets);
+#define CRUX_PLAIN_ONLY(entry, ...) do { const int32_t rc_sn__ = crux_plain_only(entry, {__VA_ARGS__}); if (rc_sn__) return rc_sn__; } while (0)
 #define CRUX_DENSE_MIN_WIDTH 128   // networks at least this wide go through the multi-CU dense engine

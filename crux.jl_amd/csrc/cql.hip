@@ -226,7 +226,7 @@ static int32_t cql_forward_head(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, cru
 extern "C" {
 
 int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const float* d_y, int32_t n_samples, float is_lo, float is_hi,
-                             float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) {
+                             float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_cql_critic_step", actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b || !d_y) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "cql_critic_loss";
   int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
@@ -244,7 +244,7 @@ int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_m
 }
 
 int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
-                            uint64_t seed, uint64_t counter, float* info_out) {
+                            uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_cql_alpha_step", actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "cql_alpha_loss";
   int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
@@ -258,7 +258,7 @@ int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
 }
 
 int32_t crux_cql_conservative(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
-                              uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) {
+                              uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) { CRUX_PLAIN_ONLY("crux_cql_conservative", actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b || !out4) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "conservative_loss";
   int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;

@@ -208,14 +208,24 @@ static float* ws_delta(crux_mlp* n, int which) {
   return n->ws + off + (size_t)which * (size_t)n->nd.maxdim * (size_t)n->ws_B;
 }
 
+// the weights of layer l the passes multiply with: W / sigma of the last forward pass for a DenseSN layer (spectral.hip), the parameters themselves otherwise
+static inline const float* dense_w(const crux_mlp* n, int l) { return (n->sn && n->sn->iters[l] ? n->sn->weff : n->p) + n->nd.woff[l]; }
+// DenseSN: every forward call advances u and renews sigma and W / sigma first (spectral_normalization.jl:40-41), on the same stream
+static int32_t dense_sn_power(crux_mlp* n, hipStream_t st) {
+  if (!n->sn) return CRUX_OK;
+  if (crux_exec_recording(n->ctx)) return crux_fail(n->ctx, CRUX_EUNSUP, "forward: a handle with spectrally normalised layers is not recordable into a fused sequence");
+  return crux_sn_power(n, st);
+}
+
 int32_t crux_dense_forward(crux_mlp* n, const float* d_x, int64_t B, hipStream_t st) {
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd;
   if (nd.L < 1) return crux_fail(c, CRUX_EINVAL, "forward: the handle has no layers");
   if (B < 1 || B > (1 << 20)) return crux_fail(c, CRUX_EINVAL, "forward: batch %lld out of range", (long long)B);
   int32_t rc = ensure_ws(n, B); if (rc) return rc;
+  rc = dense_sn_power(n, st); if (rc) return rc;
   const float* x = d_x; int l0 = 0;
   if (crux_dense_fwd_fused(n)) {      // layers 0 and 1 as one launch (dense_fused.h)
-    Fwd12Args a{}; a.W1 = n->p + nd.woff[0]; a.b1 = n->p + nd.boff[0]; a.W2 = n->p + nd.woff[1]; a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
+    Fwd12Args a{}; a.W1 = dense_w(n, 0); a.b1 = n->p + nd.boff[0]; a.W2 = dense_w(n, 1); a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
     a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act1 = nd.acts[0]; a.act2 = nd.acts[1];
     CRUX_RUN(c, Fwd12Op, OP_FWD12, k_fwd12, df_fwd12_blocks(nd, B), 256, st, a);
     rc = crux_launch_check(c, "k_fwd12"); if (rc) return rc;
@@ -223,7 +233,7 @@ int32_t crux_dense_forward(crux_mlp* n, const float* d_x, int64_t B, hipStream_t
   }
   for (int l = l0; l < nd.L; ++l) {
     const int in = nd.dims[l], out = nd.dims[l + 1];
-    GemmArgs q{}; q.A = n->p + nd.woff[l]; q.sAi = 1; q.sAk = out; q.B = x; q.sBk = 1; q.sBj = in; q.M = out; q.N = (int)B; q.K = in;
+    GemmArgs q{}; q.A = dense_w(n, l); q.sAi = 1; q.sAk = out; q.B = x; q.sBk = 1; q.sBj = in; q.M = out; q.N = (int)B; q.K = in;
     q.C = crux_dense_act(n, l + 1); q.sCj = out; q.epi = EPI_FWD; q.bias = n->p + nd.boff[l]; q.act = nd.acts[l];
     rc = launch_gemm(c, q, st); if (rc) return rc;
     x = q.C;
@@ -237,7 +247,8 @@ int32_t crux_dense_forward12(crux_mlp* n, const float* d_x, int64_t B, hipStream
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd;
   if (!crux_dense_fwd_fused(n) || nd.L != 3) return crux_fail(c, CRUX_EUNSUP, "forward12: not a fused three-layer shape");
   int32_t rc = ensure_ws(n, B); if (rc) return rc;
-  Fwd12Args a{}; a.W1 = n->p + nd.woff[0]; a.b1 = n->p + nd.boff[0]; a.W2 = n->p + nd.woff[1]; a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
+  rc = dense_sn_power(n, st); if (rc) return rc;
+  Fwd12Args a{}; a.W1 = dense_w(n, 0); a.b1 = n->p + nd.boff[0]; a.W2 = dense_w(n, 1); a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
   a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act1 = nd.acts[0]; a.act2 = nd.acts[1];
   CRUX_RUN(c, Fwd12Op, OP_FWD12, k_fwd12, df_fwd12_blocks(nd, B), 256, st, a);
   return crux_launch_check(c, "k_fwd12");
@@ -246,8 +257,8 @@ int32_t crux_dense_forward12(crux_mlp* n, const float* d_x, int64_t B, hipStream
 int32_t crux_dense_dgrad_to_dz1(crux_mlp* n, const float* d_x, int64_t B, const float* d_dy, const float** d_dz1, hipStream_t st) {
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd;
   if (!crux_dense_bwd_fused3(n, B) || !n->ws || n->ws_B < B) return crux_fail(c, CRUX_EUNSUP, "dgrad_to_dz1: not a fused three-layer shape with a cached forward pass");
-  DzSrc z{}; z.W3 = n->p + nd.woff[2]; z.dZ3 = d_dy; z.out3 = nd.dims[3]; z.act = nd.acts[1];
-  Dgrad2Args a{}; a.z = z; a.W2 = n->p + nd.woff[1]; a.dZ2 = crux_dense_act(n, 2); a.H1 = crux_dense_act(n, 1); a.x = d_x; a.part = ws_part(n); a.dZ1 = ws_delta(n, 0);
+  DzSrc z{}; z.W3 = dense_w(n, 2); z.dZ3 = d_dy; z.out3 = nd.dims[3]; z.act = nd.acts[1];
+  Dgrad2Args a{}; a.z = z; a.W2 = dense_w(n, 1); a.dZ2 = crux_dense_act(n, 2); a.H1 = crux_dense_act(n, 1); a.x = d_x; a.part = ws_part(n); a.dZ1 = ws_delta(n, 0);
   a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act0 = nd.acts[0]; a.want_g = 0;
   CRUX_RUN(c, Dgrad2W1Op, OP_DGRAD2W1, k_dgrad2w1, (unsigned)((nd.dims[1] >> 4) * 4), 256, st, a);
   *d_dz1 = a.dZ1;
@@ -258,6 +269,8 @@ int32_t crux_dense_dgrad_to_dz1(crux_mlp* n, const float* d_x, int64_t B, const 
 int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const float* d_dy, float gscale, bool want_g, float* d_dx, hipStream_t st, Sumsq2Fix* defer, int defer_slot, int32_t* nanflags) {
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd;
   if (nd.L < 1 || !n->ws || n->ws_B < B) return crux_fail(c, CRUX_EINVAL, "backward: no cached forward pass for this batch");
+  // DenseSN: the norm that follows must be taken of the CONVERTED gradient, so layer 0's gradient is finished here (the un-deferred route; the caller's Sumsq2Fix slot stays empty)
+  if (n->sn) { defer = nullptr; if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "backward: a handle with spectrally normalised layers is not recordable into a fused sequence"); }
   const float* dcur = d_dy; float* dnxt = ws_delta(n, 0); float* dspare = ws_delta(n, 1);
   if (nd.acts[nd.L - 1] != CRUX_ACT_IDENTITY) {   // dZ_L = act'(Y_L) .* dY; an identity output layer (the usual critic / mean head) uses dY as it is
     const int64_t cnt = (int64_t)nd.dims[nd.L] * B;
@@ -279,15 +292,15 @@ int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const floa
     }
     if (fused && l == 1) {      // layers 1 and 0 together (dense_fused.h): dW1' = dcur X1' | dX1 = act0'(X1) .* (W1'' dcur) -> layer 0's dW, db inside the same workgroups
       DzSrc z{}; const float* dz1 = dcur;
-      if (fused3) { z.W3 = n->p + nd.woff[2]; z.dZ3 = dcur; z.out3 = nd.dims[3]; z.act = nd.acts[1]; dz1 = crux_dense_act(n, 2); }      // dcur is still dZ of the output layer; the operand pointer becomes H2
+      if (fused3) { z.W3 = dense_w(n, 2); z.dZ3 = dcur; z.out3 = nd.dims[3]; z.act = nd.acts[1]; dz1 = crux_dense_act(n, 2); }      // dcur is still dZ of the output layer; the operand pointer becomes H2
       if (want_g) { Wgrad2Args w{}; w.z = z; w.dZ = dz1; w.X = x; w.dW = n->g + nd.woff[1]; w.db = n->g + nd.boff[1]; w.scale = gscale; w.out = out; w.in = in; w.B = (int32_t)B; w.nf = nanflags;
         CRUX_RUN(c, Wgrad2Op, OP_WGRAD2, k_wgrad2, (unsigned)((out >> 5) * (in >> 5)), 256, st, w); }
-      Dgrad2Args a{}; a.z = z; a.W2 = n->p + nd.woff[1]; a.dZ2 = dz1; a.H1 = x; a.x = d_x; a.part = ws_part(n); a.dZ1 = d_dx ? dnxt : nullptr;
+      Dgrad2Args a{}; a.z = z; a.W2 = dense_w(n, 1); a.dZ2 = dz1; a.H1 = x; a.x = d_x; a.part = ws_part(n); a.dZ1 = d_dx ? dnxt : nullptr;
       a.in0 = nd.dims[0]; a.out1 = in; a.out2 = out; a.B = (int32_t)B; a.act0 = nd.acts[0]; a.want_g = want_g ? 1 : 0; a.nf = nanflags;
       CRUX_RUN(c, Dgrad2W1Op, OP_DGRAD2W1, k_dgrad2w1, (unsigned)((in >> 4) * 4), 256, st, a);
       if (want_g) { defer->part[defer_slot] = a.part; defer->out1[defer_slot] = in; defer->in0[defer_slot] = nd.dims[0]; defer->woff[defer_slot] = nd.woff[0]; defer->boff[defer_slot] = nd.boff[0]; defer->scale[defer_slot] = gscale; }
       if (d_dx) {                // the input gradient of layer 0 from the dZ of layer 0 the fused op left in the workspace
-        GemmArgs q{}; q.A = n->p + nd.woff[0]; q.sAi = in; q.sAk = 1; q.B = dnxt; q.sBk = 1; q.sBj = in; q.M = nd.dims[0]; q.N = (int)B; q.K = in;
+        GemmArgs q{}; q.A = dense_w(n, 0); q.sAi = in; q.sAk = 1; q.B = dnxt; q.sBk = 1; q.sBj = in; q.M = nd.dims[0]; q.N = (int)B; q.K = in;
         q.C = d_dx; q.sCj = nd.dims[0]; q.epi = EPI_BWD_DATA; q.ysrc = nullptr; q.act = CRUX_ACT_IDENTITY;
         int32_t rc = launch_gemm(c, q, st); if (rc) return rc; }
       break;
@@ -298,12 +311,13 @@ int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const floa
       int32_t rc = launch_gemm(c, q, st); if (rc) return rc;
     }
     if (l > 0 || d_dx) {
-      GemmArgs q{}; q.A = n->p + nd.woff[l]; q.sAi = out; q.sAk = 1; q.B = dcur; q.sBk = 1; q.sBj = out; q.M = in; q.N = (int)B; q.K = out;
+      GemmArgs q{}; q.A = dense_w(n, l); q.sAi = out; q.sAk = 1; q.B = dcur; q.sBk = 1; q.sBj = out; q.M = in; q.N = (int)B; q.K = out;
       q.C = l > 0 ? dnxt : d_dx; q.sCj = in; q.epi = EPI_BWD_DATA; q.ysrc = l > 0 ? x : nullptr; q.act = l > 0 ? nd.acts[l - 1] : CRUX_ACT_IDENTITY;
       int32_t rc = launch_gemm(c, q, st); if (rc) return rc;
       dcur = dnxt; float* t = dnxt; dnxt = dspare; dspare = t;      // ping-pong between the two workspace buffers; d_dy itself is never written
     }
   }
+  if (n->sn && want_g) return crux_sn_grad(n, st);      // G -> G / sigma - (<G, W> / sigma^2) u v' for the DenseSN layers, gscale included (the conversion is linear in G)
   return crux_launch_check(c, "dense backward");
 }
 

@@ -1022,7 +1022,7 @@ int32_t crux_env_get_state(crux_env* e, double* state, int64_t* ep_len, int64_t*
   return CRUX_OK;
 }
 
-int32_t crux_rollout(crux_env* e, crux_mlp* policy, const crux_rollout_cfg* cfg, crux_buffer* buf, int64_t T, double* sum_r, int64_t* n_episode_end) {
+int32_t crux_rollout(crux_env* e, crux_mlp* policy, const crux_rollout_cfg* cfg, crux_buffer* buf, int64_t T, double* sum_r, int64_t* n_episode_end) { CRUX_PLAIN_ONLY("crux_rollout", policy);
   if (!e || !policy || !cfg || !buf || T < 1) return CRUX_EINVAL;
   crux_ctx* c = e->ctx;
   const int64_t N = (int64_t)e->n_envs * T;
@@ -1083,7 +1083,7 @@ int32_t crux_rollout(crux_env* e, crux_mlp* policy, const crux_rollout_cfg* cfg,
 // steps! for n independent samplers of equal shape in ONE launch (multi-seed runs): problem r rolls out its own policy on its own environments into its own buffer
 // exploration(pi_explore, svec; pi_on, i) / action(pi, svec) of step! (sampler.jl:73) for n_envs caller-stepped samplers at once: see k_explore_* above.
 int32_t crux_policy_explore(crux_mlp* policy, const crux_rollout_cfg* cfg, int32_t n_envs, const float* obs, uint64_t seed, const int64_t* steps_taken,
-                            void* actions_out, float* logprob_out) {
+                            void* actions_out, float* logprob_out) { CRUX_PLAIN_ONLY("crux_policy_explore", policy);
   if (!policy || !cfg || !obs || !actions_out || n_envs < 1) return CRUX_EINVAL;
   crux_ctx* c = policy->ctx; const NetDesc& pn = policy->nd;
   if (pn.L < 1) return crux_fail(c, CRUX_EINVAL, "policy_explore: the policy has no layers");
@@ -1128,7 +1128,7 @@ int32_t crux_policy_explore(crux_mlp* policy, const crux_rollout_cfg* cfg, int32
 // just written, what terminate_episode! ran on the reference's `data` before the push (sampler.jl:53-66): fill_gae! / fill_returns!, the importance-weight products, the cost
 // advantage / return -- for whichever of those columns the buffer has. cols[CRUX_COL_EPISODE_END] carries the caller's episode cuts (done, max_steps, the reset at the end).
 int32_t crux_steps_push(crux_buffer* buf, int64_t n, const void* const* cols, int64_t rows_per_env, int32_t close_last, crux_mlp* critic, float lambda, float gamma,
-                        crux_mlp* cost_critic, crux_mlp* nominal, int32_t nominal_head, int64_t* first_row_out) {
+                        crux_mlp* cost_critic, crux_mlp* nominal, int32_t nominal_head, int64_t* first_row_out) { CRUX_PLAIN_ONLY("crux_steps_push", critic, cost_critic, nominal);
   if (!buf || !cols || n < 0) return CRUX_EINVAL;
   crux_ctx* c = buf->ctx;
   if (n > buf->capacity && (has_col(buf, CRUX_COL_ADVANTAGE) || has_col(buf, CRUX_COL_RETURN) || has_col(buf, CRUX_COL_COST_ADVANTAGE) || has_col(buf, CRUX_COL_COST_RETURN) ||
@@ -1159,6 +1159,7 @@ int32_t crux_steps_push(crux_buffer* buf, int64_t n, const void* const* cols, in
 
 int32_t crux_rollout_multi(int32_t n, crux_env* const* envs, crux_mlp* const* policies, const crux_rollout_cfg* cfg, crux_buffer* const* bufs, int64_t T, double* sum_r, int64_t* n_episode_end) {
   if (n < 1 || !envs || !policies || !cfg || !bufs || T < 1) return CRUX_EINVAL;
+  for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_rollout_multi", policies[i]);
   crux_ctx* c = envs[0]->ctx; crux_env* e0 = envs[0]; const NetDesc& pn = policies[0]->nd; const int nout = pn.dims[pn.L];
   const bool h64 = pn.L == 3 && pn.dims[1] == 64 && pn.dims[2] == 64 && pn.acts[0] == pn.acts[1] && pn.acts[2] == CRUX_ACT_IDENTITY;
   if (!h64) return crux_fail(c, CRUX_EUNSUP, "steps! (multi): only the 64-wide register-resident rollout kernel is batched");
@@ -1229,7 +1230,7 @@ int32_t crux_env_step_host(crux_ctx* c, int32_t kind, int64_t n, const double* s
 // batch capacity == B <= 256, at most 4 environments, dN a multiple of them, both networks narrower than the dense engine's threshold, a rollout that the
 // generic kernel would run. infos: host [iters x epochs x CRUX_INFO_N] (loss, grad norm, [2] = Qavg per epoch).
 extern "C" int32_t crux_dqn_small_solve(crux_mlp* net, crux_mlp* target_net, crux_env* e, const crux_rollout_cfg* cfg, crux_buffer* source, crux_buffer* batch,
-                                        int32_t iters, int32_t dN, int32_t epochs, float gamma, float tau, int32_t use_weight, uint64_t i0, float* infos, double* sum_r, int64_t* n_episode_end) {
+                                        int32_t iters, int32_t dN, int32_t epochs, float gamma, float tau, int32_t use_weight, uint64_t i0, float* infos, double* sum_r, int64_t* n_episode_end) { CRUX_PLAIN_ONLY("crux_dqn_small_solve", net, target_net);
   if (!net || !target_net || !e || !cfg || !source || !batch || iters < 1 || dN < 1 || epochs < 1) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const int64_t B = batch->capacity; const int E = e->n_envs;
   const NetDesc& pn = net->nd;

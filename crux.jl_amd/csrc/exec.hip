@@ -411,7 +411,7 @@ static int32_t grow_epoch_tmp(crux_ctx* c, size_t bytes, int64_t B, const char* 
 // floating-point contraction setting (exp / log are inlined library code: the two forms must agree bit for bit).
 int32_t crux_mlp_forward_impl(crux_mlp* net, const float* d_x, int64_t B, float* d_y, const float* params_override);
 __global__ void k_softq_target(const float* __restrict__ q, int nout, const float* __restrict__ r, const uint8_t* __restrict__ done, float gamma, float alpha, int64_t n, float* __restrict__ y) { SoftqTargetOp::run(blockIdx.x, gridDim.x, q, nout, r, done, gamma, alpha, n, y); }
-extern "C" int32_t crux_softq_target(crux_mlp* tn, crux_buffer* batch, float gamma, float alpha, float* d_y) {
+extern "C" int32_t crux_softq_target(crux_mlp* tn, crux_buffer* batch, float gamma, float alpha, float* d_y) { CRUX_PLAIN_ONLY("crux_softq_target", tn);
   if (!tn || !batch || !d_y) return CRUX_EINVAL;
   crux_ctx* c = tn->ctx; const int64_t n = batch->elements; if (n == 0) return CRUX_OK;
   if (!(alpha > 0.f)) return crux_fail(c, CRUX_EINVAL, "softq_target: alpha must be positive");
@@ -570,7 +570,7 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
 }
 
 int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                       uint64_t sample_counter, float* info_out) { return dqn_epoch_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter, info_out); }
+                       uint64_t sample_counter, float* info_out) { CRUX_PLAIN_ONLY("crux_dqn_epoch", net, target_net); return dqn_epoch_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter, info_out); }
 
 // value_training's epoch loop (off_policy.jl:69: `for epoch in 1:c_opt.epochs`) for the DQN family as ONE recorded list: the n epochs are recorded back to back, the
 // phases of epoch e follow those of epoch e - 1, and the host uploads, launches and reads back once. Epoch e draws with sample counter sample_counter0 + e; beta is
@@ -594,7 +594,7 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
                           [&]() { return polyak_tau >= 0.f ? crux_polyak(target_net, net, polyak_tau) : CRUX_OK; });
 }
 int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                        uint64_t sample_counter0, int32_t n_epochs, float* infos) {
+                        uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs", net, target_net);
   return dqn_epochs_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter0, n_epochs, infos);
 }
 // the same loop with softq_target(alpha) (rl/softq.jl:4-13) in place of dqn_target: SoftQ's value_training
@@ -603,7 +603,7 @@ int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source
 // value_training while the device runs this one. A NaN gradient norm shows as a NaN in the info row (the update is skipped on the device as always, training.jl:20);
 // CRUX_EUNSUP for networks that do not take the recorded form (the caller uses crux_dqn_epochs).
 int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                              uint64_t sample_counter0, int32_t n_epochs, float* d_infos) {
+                              uint64_t sample_counter0, int32_t n_epochs, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs_async", net, target_net);
   if (!d_infos) return CRUX_EINVAL;
   if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   return dqn_epochs_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
@@ -611,20 +611,20 @@ int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
 // value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111 with :108), without the host: the chain of crux_dqn_epochs_async (softq_alpha > 0:
 // crux_softq_epochs_async) with polyak_average!(target_net, net, tau) riding in the last epoch's final phase. tau < 0: no target update (== the plain async entries).
 int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) {
+                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_value_training_async", net, target_net);
   if (!d_infos || softq_alpha < 0.f || tau > 1.f) return CRUX_EINVAL;
   if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   if (tau >= 0.f && net->nd.n_params != target_net->nd.n_params) return crux_fail(net->ctx, CRUX_EINVAL, "value_training: polyak_average! needs equal parameter counts");
   return dqn_epochs_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos, tau);
 }
 int32_t crux_softq_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                                uint64_t sample_counter0, int32_t n_epochs, float* d_infos) {      // crux_softq_epochs without the host in the loop (see crux_dqn_epochs_async)
+                                uint64_t sample_counter0, int32_t n_epochs, float* d_infos) { CRUX_PLAIN_ONLY("crux_softq_epochs_async", net, target_net);      // crux_softq_epochs without the host in the loop (see crux_dqn_epochs_async)
   if (!d_infos || !(alpha > 0.f)) return CRUX_EINVAL;
   if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   return dqn_epochs_impl(net, target_net, source, batch, gamma, alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
 }
 int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                          uint64_t sample_counter0, int32_t n_epochs, float* infos) {
+                          uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_softq_epochs", net, target_net);
   if (!(alpha > 0.f)) return CRUX_EINVAL;
   return dqn_epochs_impl(net, target_net, source, batch, gamma, alpha, use_weight, beta, sample_counter0, n_epochs, infos);
 }
@@ -759,7 +759,7 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
 // [train!(critic, double_Q_loss)] -> [train!(actor, sac_actor_loss) -> polyak_average!(pi_minus, pi, tau)] as ONE fused launch.
 int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                        crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t update_critic, int32_t update_actor,
-                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) {
+                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) { CRUX_PLAIN_ONLY("crux_sac_epoch", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
   if (!actor || !q1 || !q2 || !q1_targ || !q2_targ || !log_alpha || !source || !batch) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const int64_t B = batch->capacity;
   if (source->prioritized) return crux_fail(c, CRUX_EUNSUP, "sac_epoch: prioritized replay over a DoubleNetwork critic is not defined (td_error, src/utils.jl:112)");
@@ -845,7 +845,7 @@ static int32_t sac_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
 int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                         crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
-                        float* infos_temp, float* infos_critic, float* infos_actor) {
+                        float* infos_temp, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_sac_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
   // more than one chain: one read-back at the end of the call (see epochs_one_readback)
   if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
     float* const dst[3] = {infos_temp, infos_critic, infos_actor};
@@ -861,7 +861,7 @@ int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
 // epoch (rows of steps an epoch skipped -- critic_every / actor_every -- are left as they were).
 int32_t crux_sac_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                               crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) {
+                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_sac_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
   if (!d_infos) return CRUX_EINVAL;
   return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
                          sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, nullptr, d_infos);
@@ -939,14 +939,14 @@ static int32_t dpg_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
 // crux_dpg_epochs without the host in the loop (see crux_dqn_epochs_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows of every epoch
 int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                               float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) {
+                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_dpg_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ);
   if (!d_infos) return CRUX_EINVAL;
   return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
                          sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, d_infos);
 }
 int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) {
+                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_dpg_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ);
   // several chains per call: run back to back, one read-back at the end of the call (see epochs_one_readback)
   if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
     float* const dst[2] = {infos_critic, infos_actor};
@@ -961,7 +961,7 @@ int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
 }  // extern "C"
 
 // test hook: value(pi, x) through the executor (the same tile bodies as crux_mlp_forward_cached, run by the phase kernels) -- tests compare the two bit for bit
-extern "C" int32_t crux_debug_exec_forward(crux_mlp* net, const float* d_x, int64_t B, float* d_y, int32_t with_backward, const float* d_dy) {
+extern "C" int32_t crux_debug_exec_forward(crux_mlp* net, const float* d_x, int64_t B, float* d_y, int32_t with_backward, const float* d_dy) { CRUX_PLAIN_ONLY("crux_debug_exec_forward", net);
   if (!net || !d_x || !d_y) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; int32_t rc = crux_exec_begin(c); if (rc) return rc;
   rc = crux_dense_forward(net, d_x, B, c->stream); if (rc) { crux_exec_abort(c); return rc; }
@@ -980,7 +980,7 @@ extern "C" int32_t crux_debug_exec_nops(crux_ctx* c, int32_t n, int32_t blocks) 
   return crux_exec_run(c);
 }
 // test hook: the forward pass of `net` recorded `reps` times (dependent ops): per-op cost of the tile GEMM inside the executor
-extern "C" int32_t crux_debug_exec_forward_reps(crux_mlp* net, const float* d_x, int64_t B, int32_t reps) {
+extern "C" int32_t crux_debug_exec_forward_reps(crux_mlp* net, const float* d_x, int64_t B, int32_t reps) { CRUX_PLAIN_ONLY("crux_debug_exec_forward_reps", net);
   crux_ctx* c = net->ctx; int32_t rc = crux_exec_begin(c); if (rc) return rc;
   for (int k = 0; k < reps; ++k) { rc = crux_dense_forward(net, d_x, B, c->stream); if (rc) { crux_exec_abort(c); return rc; } }
   return crux_exec_run(c);

@@ -232,7 +232,7 @@ static int32_t iq_add_penalty(crux_mlp* n, const IqBufs& ib) {
 extern "C" {
 
 int32_t crux_gradient_penalty(crux_mlp* net, const float* d_x, const float* d_xtilde, int64_t B, float target, float lambda, int32_t accumulate,
-                              uint64_t seed, uint64_t counter, float* penalty_out) {
+                              uint64_t seed, uint64_t counter, float* penalty_out) { CRUX_PLAIN_ONLY("crux_gradient_penalty", net);
   if (!net || !d_x || !penalty_out) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const char* who = "gradient_penalty"; const NetDesc& nd = net->nd;
   int32_t rc = iq_check_net(c, net, who); if (rc) return rc;
@@ -259,7 +259,7 @@ int32_t crux_gradient_penalty(crux_mlp* net, const float* d_x, const float* d_xt
 }
 
 int32_t crux_iq_step(crux_mlp* q, crux_buffer* b, int64_t n_policy, float gamma_iq, int32_t reg, float alpha_reg, int32_t gp, float lambda_gp,
-                     uint64_t seed, uint64_t counter, float* info_out, float* iq_out) {
+                     uint64_t seed, uint64_t counter, float* info_out, float* iq_out) { CRUX_PLAIN_ONLY("crux_iq_step", q);
   if (!q || !b) return CRUX_EINVAL;
   crux_ctx* c = q->ctx; const char* who = "iq_loss"; const NetDesc& nd = q->nd;
   int32_t rc = iq_check_net(c, q, who); if (rc) return rc;

@@ -177,6 +177,7 @@ int32_t crux_mlp_destroy(crux_mlp* n) {
   if (!n) return CRUX_OK;
   crux_sync_before_free(n->ctx);
   (void)hipFree(n->p); (void)hipFree(n->g); (void)hipFree(n->m); (void)hipFree(n->v); (void)hipFree(n->bp); if (n->ws) (void)hipFree(n->ws);
+  crux_sn_free(n);
   delete n; return CRUX_OK;
 }
 
@@ -229,12 +230,16 @@ int32_t crux_mlp_forward_host(crux_mlp* n, const float* x, int64_t B, float* y) 
 int32_t crux_mlp_copy(crux_mlp* to, const crux_mlp* from) {
   if (!to || !from) return CRUX_EINVAL;
   if (to->nd.n_params != from->nd.n_params) return crux_fail(to->ctx, CRUX_EINVAL, "copyto!: parameter counts differ");
+  // DenseSN: trainable is (weight, bias) (spectral_normalization.jl:36), so copyto! moves W and b and leaves u alone; the layers must be of the same kind
+  for (int l = 0; l < to->nd.L && l < from->nd.L; ++l) if (((to->sn && to->sn->iters[l]) != 0) != ((from->sn && from->sn->iters[l]) != 0))
+    return crux_fail(to->ctx, CRUX_EINVAL, "copyto!: layer %d is spectrally normalised in one handle only", l);
   HIPCHK(to->ctx, hipMemcpyAsync(to->p, from->p, sizeof(float) * (size_t)to->nd.n_params, hipMemcpyDeviceToDevice, to->ctx->stream));
   return CRUX_OK;
 }
 
 int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau) {
   if (!to || !from) return CRUX_EINVAL;
+  CRUX_PLAIN_ONLY("crux_polyak", to, from);
   if (to->nd.n_params != from->nd.n_params) return crux_fail(to->ctx, CRUX_EINVAL, "polyak_average!: parameter counts differ");
   const int64_t n = to->nd.n_params;
   // inside a recorded chain the three polyak updates of an epoch share a phase with other ops: 64 grid-striding blocks each instead of n / 256 (a phase of > 768 blocks takes
@@ -275,6 +280,7 @@ int32_t crux_adam_set_state(crux_mlp* n, const float* m, const float* v, const d
 
 int32_t crux_mlp_set_squash(crux_mlp* n, float ascale) {
   if (!n) return CRUX_EINVAL;
+  CRUX_PLAIN_ONLY("crux_mlp_set_squash", n);
   if (!(ascale >= 0.f)) return crux_fail(n->ctx, CRUX_EINVAL, "SquashedGaussianPolicy: ascale must be >= 0 (0 = plain GaussianPolicy)");
   n->squash = ascale; return CRUX_OK;
 }
@@ -298,6 +304,12 @@ int32_t crux_mlp_forward_impl(crux_mlp* n, const float* d_x, int64_t B, float* d
   if (B == 0) return CRUX_OK;
   crux_ctx* c = n->ctx;
   if (n->nd.L < 1) return crux_fail(c, CRUX_EINVAL, "mlp_forward: the handle is a bare parameter vector (n_layers = 0)");
+  if (n->sn) {      // DenseSN: one forward call of the dense engine (u advances, spectral.hip), its output copied out
+    if (params_override) return crux_fail(c, CRUX_EUNSUP, "mlp_forward: parameter override on a handle with spectrally normalised layers");
+    const int32_t rc = crux_dense_forward(n, d_x, B, c->stream); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(d_y, crux_dense_act(n, n->nd.L), sizeof(float) * (size_t)n->nd.dims[n->nd.L] * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+    return CRUX_OK;
+  }
   if (fwd_h64_ok(n->nd, B)) {      // the 64-wide family at large batches (fill_gae!'s critic evaluations): the matrix pipes, same bits (above)
     hipLaunchKernelGGL(k_mlp_forward_h64, dim3(fwd_h64_blocks(B, 1)), dim3(256), 0, c->stream, n->nd, params_override ? params_override : n->p, d_x, B, d_y);
     return crux_launch_check(c, "k_mlp_forward_h64"); }

@@ -164,7 +164,7 @@ int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, floa
 int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
                             int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
                             int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
-                            float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3) {
+                            float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3) { CRUX_PLAIN_ONLY("crux_nda_gail_round", V, Vc);
   if (!D || !Dnda || !demo || !nda || !batch || !copyD || !copyN || !V || !Vc) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "GAIL_callback (NDA-GAIL)";
   // every check first: nothing is launched and no buffer is touched when one fails

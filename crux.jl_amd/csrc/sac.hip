@@ -422,7 +422,7 @@ int32_t crux_td_step_dense(crux_mlp* net, crux_buffer* b, const float* d_y, int3
 
 extern "C" {
 
-int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1t, crux_mlp* q2t, crux_mlp* la, crux_buffer* b, float gamma, uint64_t seed, uint64_t counter, float* d_y) {
+int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1t, crux_mlp* q2t, crux_mlp* la, crux_buffer* b, float gamma, uint64_t seed, uint64_t counter, float* d_y) { CRUX_PLAIN_ONLY("crux_sac_target", actor, q1t, q2t, la);
   if (!actor || !q1t || !q2t || !la || !b || !d_y) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; int32_t rc = check_sac(c, actor, q1t, q2t, la, b, "sac_target"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim;
@@ -437,7 +437,7 @@ int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1t, crux_mlp* q2t, crux_mlp*
   return crux_launch_check(c, "sac_target");
 }
 
-int32_t crux_sac_temp_step(crux_mlp* actor, crux_mlp* la, crux_buffer* b, float H_target, uint64_t seed, uint64_t counter, float* info_out) {
+int32_t crux_sac_temp_step(crux_mlp* actor, crux_mlp* la, crux_buffer* b, float H_target, uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_sac_temp_step", actor, la);
   if (!actor || !la || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; int32_t rc = check_sac(c, actor, nullptr, nullptr, la, b, "sac_temp_loss"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim;
@@ -478,11 +478,11 @@ static int32_t q_step_impl(crux_mlp* q1, crux_mlp* q2, crux_buffer* b, const flo
   if (q2) { rc = adam_gated(q2, ssq, st); if (rc) return rc; }
   return finish_step(c, dinfo, st, info_out, who);
 }
-int32_t crux_double_q_step(crux_mlp* q1, crux_mlp* q2, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) {
+int32_t crux_double_q_step(crux_mlp* q1, crux_mlp* q2, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) { CRUX_PLAIN_ONLY("crux_double_q_step", q1, q2);
   if (!q1 || !q2 || !b || !d_y) return CRUX_EINVAL;
   return q_step_impl(q1, q2, b, d_y, use_weight, info_out, "double_Q_loss");
 }
-int32_t crux_q_step(crux_mlp* q, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) {
+int32_t crux_q_step(crux_mlp* q, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) { CRUX_PLAIN_ONLY("crux_q_step", q);
   if (!q || !b || !d_y) return CRUX_EINVAL;
   return q_step_impl(q, nullptr, b, d_y, use_weight, info_out, "td_loss");
 }
@@ -550,7 +550,7 @@ int32_t crux_gail_reward(crux_mlp* D, crux_buffer* b, float alpha_r, float rscal
 }
 
 int32_t crux_dpg_target(crux_mlp* actor_t, crux_mlp* q1t, crux_mlp* q2t, crux_buffer* b, float gamma, float sigma, float eps_min, float eps_max, float a_min, float a_max,
-                        uint64_t seed, uint64_t counter, float* d_y) {
+                        uint64_t seed, uint64_t counter, float* d_y) { CRUX_PLAIN_ONLY("crux_dpg_target", actor_t, q1t, q2t);
   if (!actor_t || !q1t || !b || !d_y) return CRUX_EINVAL;
   crux_ctx* c = actor_t->ctx; int32_t rc = check_sac(c, nullptr, q1t, q2t, nullptr, b, "ddpg_target"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim;
@@ -566,7 +566,7 @@ int32_t crux_dpg_target(crux_mlp* actor_t, crux_mlp* q1t, crux_mlp* q2t, crux_bu
   return crux_launch_check(c, "ddpg_target");
 }
 
-int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* b, float* info_out) {
+int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* b, float* info_out) { CRUX_PLAIN_ONLY("crux_dpg_actor_step", actor, q);
   if (!actor || !q || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; int32_t rc = check_sac(c, nullptr, q, nullptr, nullptr, b, "ddpg_actor_loss"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad;
@@ -591,7 +591,7 @@ int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* b, float*
   return finish_step(c, dinfo, st, info_out, "ddpg_actor_loss");
 }
 
-int32_t crux_sac_actor_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, uint64_t seed, uint64_t counter, float* info_out) {
+int32_t crux_sac_actor_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_sac_actor_step", actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; int32_t rc = check_sac(c, actor, q1, q2, la, b, "sac_actor_loss"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad;

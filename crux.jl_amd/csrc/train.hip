@@ -309,7 +309,7 @@ static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_trai
 
 extern "C" {
 
-int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) {
+int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train", net);
   if (!net || !buf || !cfg) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
   if (buf->elements <= 0) return crux_fail(c, CRUX_EINVAL, "batch_train!: empty buffer");
@@ -317,7 +317,7 @@ int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
   return batch_train_impl(net, buf, cfg, nullptr, perms, info_out, epoch_infos);
 }
 
-int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) {
+int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_lagrange", net);
   if (!net || !buf || !cfg || !lag) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
   if (cfg->loss != CRUX_LOSS_LAGRANGE_PPO) return crux_fail(c, CRUX_EINVAL, "batch_train! (lagrange): cfg.loss must be CRUX_LOSS_LAGRANGE_PPO");
@@ -336,13 +336,13 @@ static int32_t step_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
   return run_batch(net, buf, a, 1, info_out, nullptr, false);
 }
 
-int32_t crux_train_step(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) {
+int32_t crux_train_step(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) { CRUX_PLAIN_ONLY("crux_train_step", net);
   return step_impl(net, buf, cfg, ids, n, info_out, 1);
 }
-int32_t crux_loss_grad(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) {
+int32_t crux_loss_grad(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) { CRUX_PLAIN_ONLY("crux_loss_grad", net);
   return step_impl(net, buf, cfg, ids, n, info_out, 0);
 }
-int32_t crux_loss_grad_device_ids(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int32_t* d_ids, int64_t n, float* d_info) {
+int32_t crux_loss_grad_device_ids(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int32_t* d_ids, int64_t n, float* d_info) { CRUX_PLAIN_ONLY("crux_loss_grad_device_ids", net);
   if (!net || !buf || !cfg || !d_ids || n < 1) return CRUX_EINVAL;
   TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, cfg->loss); if (rc) return rc;
   a.ids = d_ids; a.n_ids = n; a.bs = (int32_t)n; a.epochs = 1; a.max_batches = 0; a.target_kl = -1.f; a.apply = 0;
@@ -555,7 +555,7 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
 }
 
 extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
-                                                 const int64_t* perms_a, const int64_t* perms_c, float* info_a, float* info_c, float* epoch_infos_a, float* epoch_infos_c) {
+                                                 const int64_t* perms_a, const int64_t* perms_c, float* info_a, float* info_c, float* epoch_infos_a, float* epoch_infos_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
   bool exact = cfg_a->target_kl < 0.f && cfg_a->max_batches <= 0;
@@ -658,6 +658,7 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
 extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* const* actors, crux_mlp* const* critics, crux_buffer* const* bufs, const crux_train_cfg* cfg_a,
                                                        const crux_train_cfg* cfg_c, float* info_a, float* info_c) {
   if (n < 1 || !actors || !critics || !bufs || !cfg_a || !cfg_c) return CRUX_EINVAL;
+  for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_policy_gradient_training_multi", actors[i], critics[i]);
   crux_ctx* c = actors[0]->ctx;
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: early stopping / max_batches need the sequential single-learner call");
   if (cfg_a->epochs < 1 || cfg_c->epochs < 1) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_multi: epochs < 1");
@@ -739,7 +740,7 @@ extern "C" int32_t crux_buffer_shuffle(crux_buffer* b, uint64_t seed, uint64_t c
 // group of 1) the all-reduce is skipped and the result is bit-identical to crux_policy_gradient_training (the epoch orders are precomposed,
 // the learner state persists in device memory between launches).
 extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
-                                                        int32_t sync_every, float* info_a, float* info_c) {
+                                                        int32_t sync_every, float* info_a, float* info_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training_synced", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c || sync_every < 1) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_synced: early stopping / max_batches would let replicas diverge in epoch count");
@@ -790,9 +791,9 @@ extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_ml
 // ---- off-policy pieces ------------------------------------------------------------------------------
 int32_t crux_td_error(crux_mlp* net, crux_buffer* batch, const float* d_y, float* d_err);
 static int32_t td_step_impl(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out, float* d_err);
-int32_t crux_td_step(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out) { return td_step_impl(net, batch, d_y, use_weight, info_out, nullptr); }
+int32_t crux_td_step(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out) { CRUX_PLAIN_ONLY("crux_td_step", net); return td_step_impl(net, batch, d_y, use_weight, info_out, nullptr); }
 // td_error(pi, D, y) (utils.jl:112) and train!(pi, td_loss) (utils.jl:76-87) evaluate the same Q(s, a) with the same parameters: one forward pass serves both
-int32_t crux_td_step_with_error(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* d_err, float* info_out) {
+int32_t crux_td_step_with_error(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* d_err, float* info_out) { CRUX_PLAIN_ONLY("crux_td_step_with_error", net);
   if (!d_err) return CRUX_EINVAL;
   return td_step_impl(net, batch, d_y, use_weight, info_out, d_err);
 }
@@ -826,7 +827,7 @@ __global__ void k_td_error(const float* __restrict__ q, int nout, const uint8_t*
 
 extern "C" {
 
-int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_y) {
+int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_y) { CRUX_PLAIN_ONLY("crux_dqn_target", tn);
   if (!tn || !batch || !d_y) return CRUX_EINVAL;
   crux_ctx* c = tn->ctx; const int64_t n = batch->elements; if (n == 0) return CRUX_OK;
   const int nout = tn->nd.dims[tn->nd.L];
@@ -838,7 +839,7 @@ int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_
   return crux_launch_check(c, "k_dqn_target");
 }
 
-int32_t crux_td_error(crux_mlp* net, crux_buffer* batch, const float* d_y, float* d_err) {
+int32_t crux_td_error(crux_mlp* net, crux_buffer* batch, const float* d_y, float* d_err) { CRUX_PLAIN_ONLY("crux_td_error", net);
   if (!net || !batch || !d_y || !d_err) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const int64_t n = batch->elements; if (n == 0) return CRUX_OK;
   const int nout = net->nd.dims[net->nd.L];

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Off-policy imitation on Pendulum -- the pattern of the reference's examples/il/pendulum.jl: an expert (a short SAC run), its transitions as demonstrations,
 then OffPolicyGAIL and AdRIL from the same initialisation. Prints the learning curve of each learner: the undiscounted return of the greedy policy (fixed
-evaluation seed) after every `--chunk` environment steps. The discriminator is a plain ContinuousNetwork with two outputs (the reference's example uses a
-spectrally normalised one, which this library does not have)."""
+evaluation seed) after every `--chunk` environment steps. The discriminator is a plain ContinuousNetwork with two outputs; `--sn` builds it from three
+DenseSN layers instead, like the reference example's spectrally normalised D_SN."""
 import argparse
 import os
 import sys
@@ -36,6 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--expert_steps", type=int, default=10000); ap.add_argument("--steps", type=int, default=10000); ap.add_argument("--chunk", type=int, default=2000)
     ap.add_argument("--n_demo", type=int, default=2000); ap.add_argument("--width", type=int, default=256)
+    ap.add_argument("--sn", action="store_true", help="spectrally normalised discriminator (DenseSN, DenseSN, DenseSN)")
     a = ap.parse_args()
     mdp = crux.PendulumMDP(n_envs=1, seed=0)
     S, A = mdp.state_space(), crux.ContinuousSpace(1)
@@ -50,7 +51,8 @@ def main():
     print("demonstrations: %d transitions, mean reward %.3f" % (len(demo), float(demo["r"].mean())))
 
     pi = nets(a.width)
-    D = crux.ContinuousNetwork(crux.Chain(crux.Dense(4, a.width, "relu"), crux.Dense(a.width, a.width, "relu"), crux.Dense(a.width, 2)), seed=7)
+    lay = crux.DenseSN if a.sn else crux.Dense
+    D = crux.ContinuousNetwork(crux.Chain(lay(4, a.width, "relu"), lay(a.width, a.width, "relu"), lay(a.width, 2)), seed=7)
     gail = crux.OffPolicyGAIL(pi, S, demo, D, N=a.chunk, buffer_init=1000, d_opt={"epochs": 5, "batch_size": 128, "optimizer": crux.Adam(np.float32(3e-4))}, **kw())
     curve("OffPolicyGAIL", gail, mdp, pi, a.steps, a.chunk)
 

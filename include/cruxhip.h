@@ -106,6 +106,26 @@ float crux_mlp_get_squash(const crux_mlp* net);
 int32_t crux_mlp_copy(crux_mlp* to, const crux_mlp* from);
 int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
 
+/* DenseSN (src/extras/spectral_normalization.jl): spectrally normalised layers inside a Chain, what the reference builds its GAIL discriminators from
+ * (test/gym/solver_tests.jl:94-97, examples/il/pendulum.jl:27,33). Layer l with n_iter[l] >= 1 holds a persistent non-trainable u (out x 1, initially
+ * randn(Float32, out, 1), :31) and EVERY forward call runs n_iter[l] rounds of t = W'u, v = t / (|t| + eps), s = W v, u <- s / (|s| + eps) with
+ * eps = eps(Float32) (:2-11), forms sigma = u'W v (:14) and evaluates act.((W ./ sigma) x .+ b) (:41). u and v are constants of the pullback (:40), sigma is
+ * differentiated through W: with G = dL/d(W / sigma), dL/dW = G / sigma - (<G, W> / sigma^2) u v'. The trainables are (weight, bias) only (:36): parameters,
+ * gradient, Adam state, crux_mlp_n_params and crux_mlp_copy (which leaves u alone, like copyto!) are those of the plain Dense chain.
+ * crux_mlp_set_spectral: n_iter [n_layers], 0 = plain Dense, 1..8 = DenseSN with that n_iterations; all 0 makes the handle plain again. host_u: the u of the
+ * SN layers one after the other (out_l values each), or NULL: standard normals, element i = Box-Muller's first output of Philox(seed, i, stream, CRUX_RNG_NOISE)
+ * (include/crux_rng.h). Allocates; call it outside any chain. crux_mlp_get_spectral (synchronises; tests, checkpoints): u, v (in_l values per SN layer) and sigma
+ * (one per SN layer) of the last forward call; any pointer may be NULL. crux_mlp_spectral_layers: the n_iter the handle carries, returns the number of SN layers.
+ * An SN handle is accepted by crux_mlp_forward*, crux_mlp_forward_cached / crux_mlp_backward, crux_gail_d_step, crux_gail_d_batch_train, crux_gail_reward,
+ * crux_nda_reward_cost, crux_nda_gail_round (D and Dnda), crux_offgail_d_step / _round / _reward, get / set params, the Adam entries and crux_mlp_copy (equal SN
+ * layers in both handles). Every other entry that takes a crux_mlp reads the raw weights and returns CRUX_EUNSUP naming itself.
+ * Deviation: L_D(GAN_BCELoss) calls D on the expert half and then on the policy half (src/extras/gans.jl:9), so the reference advances u twice per
+ * on-policy discriminator step and the halves see slightly different sigma; the device forms ONE pass over both halves, u advances once. The two coincide at the
+ * fixed point of the iteration. OffPolicyGAIL calls D once on the concatenation (off_policy_gail.jl:98): exact. */
+int32_t crux_mlp_set_spectral(crux_mlp* net, const int32_t* n_iter /*n_layers; 0 = plain Dense*/, const float* host_u /*or NULL*/, uint64_t seed, uint32_t stream);
+int32_t crux_mlp_get_spectral(crux_mlp* net, float* host_u, float* host_v, float* host_sigma);
+int32_t crux_mlp_spectral_layers(const crux_mlp* net, int32_t* n_iter /*n_layers or NULL*/);
+
 /* optimiser: Flux.Optimise.Adam(eta, (b1,b2), eps) attached to one network
  * (TrainingParams.optimizer, src/training.jl:3; Flux.update! at :21). State = (m, v, beta powers). */
 int32_t crux_adam_init(crux_mlp* net, double eta, double beta1, double beta2, double eps);

@@ -75,6 +75,14 @@ function POMDPs.value(π::HipNetwork, s::AbstractMatrix{Float32})               
 end
 Crux.polyak_average!(to::HipNetwork, from::HipNetwork, τ=1f0) = check(to.ctx, ccall((:crux_polyak, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float32), to.h, from.h, τ))   # src/policies.jl:48-59
 Base.copyto!(to::HipNetwork, from::HipNetwork) = check(to.ctx, ccall((:crux_mlp_copy, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), to.h, from.h))                          # :61-65
+# DenseSN (src/extras/spectral_normalization.jl): n_iter[l] = n_iterations of layer l, 0 for a plain Dense; u = the SN layers' u one after the other, or nothing for randn
+function set_spectral!(π::HipNetwork, n_iter::Vector{Int32}, u::Union{Nothing,Vector{Float32}}=nothing; seed::Integer=0, stream::Integer=0)
+    check(π.ctx, ccall((:crux_mlp_set_spectral, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float32}, UInt64, UInt32), π.h, n_iter, u === nothing ? C_NULL : u, UInt64(seed), UInt32(stream)))
+end
+function spectral_state(π::HipNetwork, n_u::Integer, n_v::Integer, n_sn::Integer)      # (u, v, σ) of the last forward call, concatenated over the SN layers
+    u = Vector{Float32}(undef, n_u); v = Vector{Float32}(undef, n_v); σ = Vector{Float32}(undef, n_sn)
+    check(π.ctx, ccall((:crux_mlp_get_spectral, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), π.h, u, v, σ)); (u, v, σ)
+end
 attach!(π::HipNetwork, o::Flux.Optimise.Adam) = check(π.ctx, ccall((:crux_adam_init, LIB), Int32, (Ptr{Cvoid}, Float64, Float64, Float64, Float64), π.h, o.eta, o.beta[1], o.beta[2], o.epsilon))
 
 # ---------------------------------------------------------------------------------------------------- buffer
