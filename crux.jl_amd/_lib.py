@@ -184,6 +184,12 @@ SIGNATURES = {
     "crux_nda_reward_cost": (i32, [vp, vp, vp, f32, vp]),
     "crux_nda_advantages": (i32, [vp, vp, vp, f32, f32]),
     "crux_nda_gail_round": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, u64, i32, i32, i32, u64, u64, f32, f32, f32, vp, vp, vp]),
+    "crux_ensemble_forward": (i32, [P(vp), i32, i32, vp, i64, vp, vp, vp, vp]),
+    "crux_ensemble_logpdf": (i32, [P(vp), i32, i32, vp, vp, i64, vp]),
+    "crux_ensemble_step": (i32, [P(vp), i32, i32, vp, vp, vp, i64, vp]),
+    "crux_ensemble_train": (i32, [P(vp), i32, i32, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
+    "crux_ensemble_passes": (i32, [P(vp), i32, vp, i64, P(vp), P(vp)]),
+    "crux_ensemble_forward_recording": (i32, [P(vp), i32, i32, vp, i64, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),
@@ -227,6 +233,7 @@ LOSS = {"ppo": 0, "value_mse": 1, "a2c": 3, "reinforce": 4, "logpdf_bc": 5, "mse
 INFO = {"loss": 0, "grad_norm": 1, "entropy": 2, "kl": 3, "clip_fraction": 4, "avg_advantage": 5, "avg_return": 6,
         "batches_trained": 7, "epochs_run": 8, "q1avg": 9, "q2avg": 10, "alpha": 11, "penalty": 12, "cur_cost": 13, "cost_loss": 14, "p_loss": 15}
 INFO_N = 16
+ENS = {"gauss": 0, "class": 1}      # crux_ensemble_*: kind
 PROF = {"rollout": 0, "values": 1, "gae": 2, "whiten": 3, "train_actor": 4, "train_critic": 5, "per_scan": 6,
         "per_search": 7, "gather": 8, "td_step": 9, "tiny_solve": 10}
 

@@ -266,6 +266,10 @@ struct Sumsq2Fix { const float* part[2]; int32_t out1[2], in0[2], woff[2], boff[
 // AdamSelfOp (sac.hip) gates on, so that Adam shares the phase of the norm instead of following it
 int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const float* d_dy, float gscale, bool want_g, float* d_dx, hipStream_t st, Sumsq2Fix* defer = nullptr, int defer_slot = 0, int32_t* nanflags = nullptr);
 float* crux_dense_act(crux_mlp* n, int l);
+// the member-grouped form of the two passes (dense.hip): one launch per layer over M <= CRUX_GROUP_MAX handles of one shape that read ONE input matrix; bit-identical per member
+#define CRUX_GROUP_MAX 16
+int32_t crux_dense_forward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, hipStream_t st);
+int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags);
 int32_t crux_td_step_dense(crux_mlp* net, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out, float* d_err);   // sac.hip
 // spectral.hip: the power iteration + effective weights of one forward pass, the conversion of the weight gradient after one backward pass (enqueued only)
 int32_t crux_sn_power(crux_mlp* n, hipStream_t st);

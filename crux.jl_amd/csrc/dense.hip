@@ -321,6 +321,117 @@ int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const floa
   return crux_launch_check(c, "dense backward");
 }
 
+// ---- member-grouped passes: one launch per layer over M networks of identical NetDesc (the ensembles of ensemble.hip) ------------------------------------------------
+// The grid is M x (the blocks one member's launch has); block b works for member b / blocks_per_member on tile block b % blocks_per_member with the SAME Gemm16 body
+// and the same split-K / quarter choice launch_gemm makes for that member alone -- a function of one member's M, N, K and tile count, never of the grouped grid -- so a
+// member's results are bit-identical to its own launches. What differs between members is six pointers; they travel by value in the kernel arguments (16 x 48 bytes), picked
+// with the block-uniform member index: no pointer chasing on the device, no atomics. The vector-load forms (AV / BV) are taken when every member's operand allows them; they
+// change how an operand is fetched, not which k meets which (Gemm16), so the bits do not depend on them. Plain per-layer tiles only: the pair ops of dense_fused.h are not
+// grouped (tests/test_gpu_dense_grid.py pins that they give the bits of the plain tiles), and nothing here is recordable into the fused executor.
+struct GemmGroup { const float* A[CRUX_GROUP_MAX]; const float* B[CRUX_GROUP_MAX]; float* C[CRUX_GROUP_MAX]; const float* bias[CRUX_GROUP_MAX]; const float* ysrc[CRUX_GROUP_MAX]; float* gbias[CRUX_GROUP_MAX]; };
+template <bool AV, bool BV, bool SPLITK>
+__global__ __launch_bounds__(256) void k_gemm16_group(GemmArgs q, const GemmGroup t, const unsigned bpm, const int quart) {
+  __shared__ float part[SPLITK ? GEMM16_PART : 1];
+  const unsigned m = blockIdx.x / bpm;
+  q.A = t.A[m]; q.B = t.B[m]; q.C = t.C[m]; q.bias = t.bias[m]; q.ysrc = t.ysrc[m]; q.gbias = t.gbias[m];
+  Gemm16<AV, BV, SPLITK>::run(blockIdx.x - m * bpm, q, part, quart);
+}
+// q: the fields all members share (its six pointers are ignored); t: the members' pointers
+static int32_t launch_gemm_group(crux_ctx* c, const GemmArgs& q, const GemmGroup& t, int M, hipStream_t st) {
+  const int tiles = ((q.M + 15) >> 4) * ((q.N + 15) >> 4);
+  bool av = true, bv = true;
+  for (int m = 0; m < M; ++m) { av = av && vec_ok(t.A[m], q.sAk, q.sAi, q.K); bv = bv && vec_ok(t.B[m], q.sBk, q.sBj, q.K); }
+  const bool split = q.K >= 128 && tiles <= 4096;                       // launch_gemm's choices for one member
+  const int quart = (q.K >= 128 && tiles > 4096) ? 1 : 0;
+  const unsigned bpm = (unsigned)(split ? tiles : (tiles + 3) / 4);
+  const dim3 grid(bpm * (unsigned)M), block(256);
+  if (split) {
+    if (av && bv) hipLaunchKernelGGL((k_gemm16_group<true, true, true>), grid, block, 0, st, q, t, bpm, 0);
+    else if (av) hipLaunchKernelGGL((k_gemm16_group<true, false, true>), grid, block, 0, st, q, t, bpm, 0);
+    else if (bv) hipLaunchKernelGGL((k_gemm16_group<false, true, true>), grid, block, 0, st, q, t, bpm, 0);
+    else hipLaunchKernelGGL((k_gemm16_group<false, false, true>), grid, block, 0, st, q, t, bpm, 0);
+  } else {
+    if (av && bv) hipLaunchKernelGGL((k_gemm16_group<true, true, false>), grid, block, 0, st, q, t, bpm, quart);
+    else if (av) hipLaunchKernelGGL((k_gemm16_group<true, false, false>), grid, block, 0, st, q, t, bpm, quart);
+    else if (bv) hipLaunchKernelGGL((k_gemm16_group<false, true, false>), grid, block, 0, st, q, t, bpm, quart);
+    else hipLaunchKernelGGL((k_gemm16_group<false, false, false>), grid, block, 0, st, q, t, bpm, quart);
+  }
+  return crux_launch_check(c, "k_gemm16_group");
+}
+struct ActGradGroup { const float* dy[CRUX_GROUP_MAX]; const float* y[CRUX_GROUP_MAX]; float* dz[CRUX_GROUP_MAX]; };
+__global__ void k_act_grad_group(const ActGradGroup t, const unsigned bpm, int act, int64_t n) {
+  const unsigned m = blockIdx.x / bpm;
+  ActGradOp::run(blockIdx.x - m * bpm, bpm, t.dy[m], t.y[m], act, n, t.dz[m]);
+}
+// what every grouped pass asks of its handles: 1..CRUX_GROUP_MAX distinct plain handles of one context and one shape, outside a recording
+static int32_t dense_group_check(crux_mlp* const* nets, int M, int64_t B, const char* who) {
+  if (!nets || M < 1 || !nets[0]) return CRUX_EINVAL;
+  crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
+  if (M > CRUX_GROUP_MAX) return crux_fail(c, CRUX_EINVAL, "%s: %d members, at most %d", who, M, CRUX_GROUP_MAX);
+  for (int m = 0; m < M; ++m) {
+    if (!nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d is NULL", who, m);
+    if (nets[m]->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: member %d belongs to another context", who, m);
+    for (int k = 0; k < m; ++k) if (nets[k] == nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: members %d and %d are one handle", who, k, m);
+    const NetDesc& md = nets[m]->nd;
+    if (md.L != nd.L || md.n_extra != nd.n_extra || memcmp(md.dims, nd.dims, sizeof(int32_t) * (size_t)(nd.L + 1)) || memcmp(md.acts, nd.acts, sizeof(int32_t) * (size_t)nd.L))
+      return crux_fail(c, CRUX_EINVAL, "%s: member %d differs from member 0 in its widths or activations", who, m);
+    if (nets[m]->sn) return crux_fail(c, CRUX_EUNSUP, "%s: member %d has spectrally normalised layers (the grouped passes read the raw weights)", who, m);
+  }
+  if (nd.L < 1) return crux_fail(c, CRUX_EINVAL, "%s: the handles have no layers", who);
+  if (B < 1 || B > (1 << 20)) return crux_fail(c, CRUX_EINVAL, "%s: batch %lld out of range", who, (long long)B);
+  if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
+  return CRUX_OK;
+}
+// crux_dense_forward for every member over ONE input matrix d_x [dims[0] x B]: L launches. Each member keeps its own workspace and cached activations.
+int32_t crux_dense_forward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, hipStream_t st) {
+  int32_t rc = dense_group_check(nets, M, B, "crux_dense_forward_group"); if (rc) return rc;
+  crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
+  for (int m = 0; m < M; ++m) { rc = ensure_ws(nets[m], B); if (rc) return rc; }
+  for (int l = 0; l < nd.L; ++l) {
+    const int in = nd.dims[l], out = nd.dims[l + 1];
+    GemmArgs q{}; q.sAi = 1; q.sAk = out; q.sBk = 1; q.sBj = in; q.M = out; q.N = (int)B; q.K = in; q.sCj = out; q.epi = EPI_FWD; q.act = nd.acts[l];
+    GemmGroup t{};
+    for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = l == 0 ? d_x : crux_dense_act(n, l); t.C[m] = crux_dense_act(n, l + 1); t.bias[m] = n->p + nd.boff[l]; }
+    rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc;
+  }
+  return CRUX_OK;
+}
+// crux_dense_backward(want_g, no input gradient) for every member after crux_dense_forward_group with the same d_x: member m's parameter gradient of d_dy[m] [out_L x B]
+// (not modified) lands in its own gradient vector. 2 L - 1 launches (+ 1 for an output activation).
+int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags) {
+  int32_t rc = dense_group_check(nets, M, B, "crux_dense_backward_group"); if (rc) return rc;
+  crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
+  const float* dcur[CRUX_GROUP_MAX]; float* dnxt[CRUX_GROUP_MAX]; float* dspare[CRUX_GROUP_MAX];
+  for (int m = 0; m < M; ++m) {
+    if (!nets[m]->ws || nets[m]->ws_B < B) return crux_fail(c, CRUX_EINVAL, "crux_dense_backward_group: member %d has no cached forward pass for this batch", m);
+    if (!d_dy[m]) return crux_fail(c, CRUX_EINVAL, "crux_dense_backward_group: member %d has no output gradient", m);
+    dcur[m] = d_dy[m]; dnxt[m] = ws_delta(nets[m], 0); dspare[m] = ws_delta(nets[m], 1);
+  }
+  if (nd.acts[nd.L - 1] != CRUX_ACT_IDENTITY) {
+    const int64_t cnt = (int64_t)nd.dims[nd.L] * B; const unsigned bpm = (unsigned)((cnt + 255) / 256);
+    ActGradGroup t{};
+    for (int m = 0; m < M; ++m) { t.dy[m] = dcur[m]; t.y[m] = crux_dense_act(nets[m], nd.L); t.dz[m] = dnxt[m]; }
+    hipLaunchKernelGGL(k_act_grad_group, dim3(bpm * (unsigned)M), dim3(256), 0, st, t, bpm, nd.acts[nd.L - 1], cnt);
+    rc = crux_launch_check(c, "k_act_grad_group"); if (rc) return rc;
+    for (int m = 0; m < M; ++m) { dcur[m] = dnxt[m]; dnxt[m] = dspare[m]; dspare[m] = const_cast<float*>(dcur[m]); }
+  }
+  for (int l = nd.L - 1; l >= 0; --l) {
+    const int in = nd.dims[l], out = nd.dims[l + 1];
+    { GemmArgs q{}; q.sAi = 1; q.sAk = out; q.sBk = in; q.sBj = 1; q.M = out; q.N = in; q.K = (int)B; q.sCj = out; q.epi = EPI_WGRAD; q.scale = gscale; q.nf = nanflags;
+      GemmGroup t{};
+      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = dcur[m]; t.B[m] = l == 0 ? d_x : crux_dense_act(n, l); t.C[m] = n->g + nd.woff[l]; t.gbias[m] = n->g + nd.boff[l]; }
+      rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc; }
+    if (l > 0) {
+      GemmArgs q{}; q.sAi = out; q.sAk = 1; q.sBk = 1; q.sBj = out; q.M = in; q.N = (int)B; q.K = out; q.sCj = in; q.epi = EPI_BWD_DATA; q.act = nd.acts[l - 1];
+      GemmGroup t{};
+      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = dcur[m]; t.C[m] = dnxt[m]; t.ysrc[m] = crux_dense_act(n, l); }
+      rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc;
+      for (int m = 0; m < M; ++m) { dcur[m] = dnxt[m]; float* x = dnxt[m]; dnxt[m] = dspare[m]; dspare[m] = x; }
+    }
+  }
+  return CRUX_OK;
+}
+
 extern "C" {
 
 int32_t crux_mlp_forward_cached(crux_mlp* net, const float* d_x, int64_t B, float* d_y) {

@@ -222,18 +222,9 @@ struct ActorInfoOp { static __device__ __forceinline__ void run(const unsigned b
   dinfo[CRUX_INFO_LOSS] = (float)(st[0] / (double)B); dinfo[CRUX_INFO_ENTROPY] = (float)(-(st[1] / (double)B)); dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
 } };
 __global__ void k_actor_info(const double* __restrict__ st, const double* __restrict__ ssq, int64_t B, float* __restrict__ dinfo) { ActorInfoOp::run(blockIdx.x, gridDim.x, st, ssq, B, dinfo); }
-// Flux.update!(Adam) gated on the gradient norm: NaN => parameters untouched, status set (training.jl:20)
-struct AdamGatedOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, double* __restrict__ bp,
-                                                    double eta, double b1, double b2, double eps, int64_t n, const double* __restrict__ ssq, int32_t* __restrict__ status, int advance, int from_partials) {
-  // from_partials (fused executor): the 64 partials of k_sumsq2 are added here, in the order ssq_finalize adds them, so that the info op -- which writes ssq[0] --
-  // can share this op's phase instead of preceding it by a barrier
-  // The gate only asks whether the norm is NaN. The partials are sums of squares (no cancellation), so their sum is NaN exactly when one of them is: each lane
-  // looks at its own partials and the wave votes -- instead of every thread adding all 64 in ssq_finalize's order (64 loads + 64 dependent Float64 adds per thread)
-  bool bad;
-  if (!from_partials) bad = isnan(ssq[0]);
-  else { bool b_ = false; for (int k = (int)(threadIdx.x & 63); k < SUMSQ_BLOCKS; k += 64) b_ = b_ || isnan(ssq[1 + k]); bad = __ballot(b_) != 0ull; }
-  if (status[0] == CRUX_ENAN) return;      // an earlier step of this launch sequence already stopped with "NaN detected!": no further updates (training.jl:20)
-  if (bad) { if (bid_ == 0 && threadIdx.x == 0) status[0] = CRUX_ENAN; return; }
+// the update of an open gate, shared by k_adam_gated and the ensembles' grouped form (ensemble.hip: k_ens_adam); nb_ blocks work on this parameter vector
+__device__ __forceinline__ void adam_update(const unsigned bid_, const unsigned nb_, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, double* __restrict__ bp,
+                                            double eta, double b1, double b2, double eps, int64_t n, int advance) {
   const double c1 = 1.0 - bp[0], c2 = 1.0 - bp[1];
   for (int64_t i = (int64_t)bid_ * blockDim.x + threadIdx.x; i < n; i += (int64_t)nb_ * blockDim.x) {     // element-wise: any grid gives the same result
     const double gd = (double)g[i];
@@ -247,6 +238,20 @@ struct AdamGatedOp { static __device__ __forceinline__ void run(const unsigned b
   __syncthreads();
   if (threadIdx.x == 0) { __threadfence(); unsigned* ticket = (unsigned*)(bp + 2);
     if (atomicAdd(ticket, 1u) == nb_ - 1) { bp[0] *= b1; bp[1] *= b2; *ticket = 0u; } }
+}
+// Flux.update!(Adam) gated on the gradient norm: NaN => parameters untouched, status set (training.jl:20)
+struct AdamGatedOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, double* __restrict__ bp,
+                                                    double eta, double b1, double b2, double eps, int64_t n, const double* __restrict__ ssq, int32_t* __restrict__ status, int advance, int from_partials) {
+  // from_partials (fused executor): the 64 partials of k_sumsq2 are added here, in the order ssq_finalize adds them, so that the info op -- which writes ssq[0] --
+  // can share this op's phase instead of preceding it by a barrier
+  // The gate only asks whether the norm is NaN. The partials are sums of squares (no cancellation), so their sum is NaN exactly when one of them is: each lane
+  // looks at its own partials and the wave votes -- instead of every thread adding all 64 in ssq_finalize's order (64 loads + 64 dependent Float64 adds per thread)
+  bool bad;
+  if (!from_partials) bad = isnan(ssq[0]);
+  else { bool b_ = false; for (int k = (int)(threadIdx.x & 63); k < SUMSQ_BLOCKS; k += 64) b_ = b_ || isnan(ssq[1 + k]); bad = __ballot(b_) != 0ull; }
+  if (status[0] == CRUX_ENAN) return;      // an earlier step of this launch sequence already stopped with "NaN detected!": no further updates (training.jl:20)
+  if (bad) { if (bid_ == 0 && threadIdx.x == 0) status[0] = CRUX_ENAN; return; }
+  adam_update(bid_, nb_, p, g, m, v, bp, eta, b1, b2, eps, n, advance);
 } };
 __global__ __launch_bounds__(256) void k_adam_gated(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, double* __restrict__ bp,
                                                     double eta, double b1, double b2, double eps, int64_t n, const double* __restrict__ ssq, int32_t* __restrict__ status, int advance, int from_partials) { AdamGatedOp::run(blockIdx.x, gridDim.x, p, g, m, v, bp, eta, b1, b2, eps, n, ssq, status, advance, from_partials); }

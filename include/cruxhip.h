@@ -800,6 +800,47 @@ int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux
                             int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
                             float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3);
 
+/* DeepEnsemble / DeepClassificationEnsemble (src/extras/deep_ensembles.jl) on the member-grouped passes of the dense engine ---------------------------------------
+ * nets: M in 1..16 distinct ContinuousNetwork handles of ONE context with equal widths and activations (the members, :3, :41). All members read the same input
+ * matrix; every dense layer of all members is ONE launch (a member's tiles are the tiles of its own launch: outputs and gradients are bit-identical to
+ * crux_mlp_forward_cached / crux_mlp_backward per handle). Arrays are (features, batch), device memory unless noted.
+ * kind CRUX_ENS_GAUSS: a member's output has 2 nd rows, mu = o[1:nd, :], var = softplus.(o[nd+1:end, :]) .+ 1f-3 (:11-17); the mixture is mu* = mean_m mu_m,
+ * var* = mean_m (var_m + mu_m^2) - mu*^2 (:20-24, Float32, members added in ascending order); de_gaussian_logpdf = -log(var) / 2 - (y - mu)^2 / (2 var) (:27, no
+ * 2 pi term); training_loss = mean_m [ -mean(w .* logpdf_m) ] over all nd B elements (:33-36), y and w [nd x B].
+ * kind CRUX_ENS_CLASS: p_m = softmax(o_m) (:50), the mixture mean_m p_m (:56), logpdf = log.(sum(p* .* y, dims=1) .+ 1f-10) (:61), training_loss =
+ * mean_m Flux.Losses.crossentropy(p_m, y) (:67: the batch mean of -sum_c xlogy(y_c, p_c + eps(Float32))), y [C x B]; the weights are accepted and IGNORED (:65-67).
+ * CRUX_EINVAL (nothing enqueued): M outside 1..16, a NULL or repeated handle, members of different widths, activations or contexts, handles with trailing extras,
+ * an odd output width for the Gaussian kind, B outside 1..2^20, and for step / train a member without crux_adam_init or with other Adam hyper-parameters than
+ * member 0 (one optimiser covers the ensemble; Adam is element-wise, so it is one Adam per member). CRUX_EUNSUP: a member with DenseSN layers; a call while the
+ * fused executor records.                                                                                                                                          */
+#define CRUX_ENS_GAUSS 0
+#define CRUX_ENS_CLASS 1
+/* individual_forward (:11-17, :49-51) and the ensemble call (:20-24, :54-57): the grouped forward pass and one combine launch, enqueued on the context's stream.
+ * GAUSS: d_mu, d_var [M][nd x B] (either may be NULL), d_mean, d_evar [nd x B]. CLASS: d_mu [M][C x B] holds p_m (may be NULL), d_mean [C x B]; d_var, d_evar unused. */
+int32_t crux_ensemble_forward(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_x, int64_t B, float* d_mu, float* d_var, float* d_mean, float* d_evar);
+/* logpdf(ens, x, y) (:30, :60-62): d_out [nd x B] (GAUSS) or [1 x B] (CLASS). Enqueued only.                                                                       */
+int32_t crux_ensemble_logpdf(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_x, const float* d_y, int64_t B, float* d_out);
+/* train! (src/training.jl:13-25) with training_loss: grouped forward, one head launch (seeds and Float64 loss partials of all members), grouped pullback, one
+ * sum-of-squares launch, one gated Adam launch. d_w: [nd x B] or NULL = ones (GAUSS); ignored for CLASS. info_out (host [CRUX_INFO_N + 2 M]): LOSS = the ensemble
+ * loss, GRAD_NORM = the norm over all members' gradients, then at [CRUX_INFO_N + m] member m's loss and at [CRUX_INFO_N + M + m] its gradient norm. If ANY member's
+ * gradient norm is NaN, or o, y or w hold a NaN, no member is updated and the call returns CRUX_ENAN ("NaN detected!", :20). One host synchronisation. No float
+ * atomics: two identical calls give identical bits.                                                                                                                */
+int32_t crux_ensemble_step(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_x, const float* d_y, const float* d_w, int64_t B, float* info_out);
+/* batch_train! (src/training.jl:28-55) for the ensemble over a data set d_X [in x N], d_Y, d_W (or NULL) of N columns, enqueued whole with one host
+ * synchronisation at the end. perms (HOST, [epochs][N] int64, 0-based): the row order of every epoch (shuffle!, :36) -- the entry draws nothing. Per partition of
+ * batch_size columns (a short last one runs, :40) one gather launch fills the staging all members read, then crux_ensemble_step's launches follow; max_batches > 0
+ * ends the call after that many steps (:45, :50). Bit-identical to crux_ensemble_step on the same minibatches. epoch_rows (host [epochs x (CRUX_INFO_N + 2 M)] or
+ * NULL): per epoch run, the row of its last step. info_out (host [CRUX_INFO_N + 2 M]): the last epoch's row with BATCHES_TRAINED and EPOCHS_RUN. After a NaN norm
+ * no later step updates anything or writes a row; the call returns CRUX_ENAN and info_out is the row of the step that stopped. CRUX_EINVAL also for batch_size < 1,
+ * epochs outside 1..4096, N < 1 and a permutation entry outside 0..N-1.                                                                                            */
+int32_t crux_ensemble_train(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_X, const float* d_Y, const float* d_W, int64_t N, int32_t batch_size, int32_t epochs,
+                            int32_t max_batches, const int64_t* perms, float* info_out, float* epoch_rows);
+/* Test entries. passes: the grouped forward over d_x, member m's output copied to d_out[m] [out x B], then the grouped pullback of d_dy[m] (grad_scale 1) into
+ * member m's gradient vector; d_dy and d_out are HOST arrays of M device pointers. forward_recording: crux_ensemble_forward called while the fused executor records on
+ * the members' context; the recording is dropped, nothing is launched, the refusal's code is returned.                                                             */
+int32_t crux_ensemble_passes(crux_mlp* const* nets, int32_t M, const float* d_x, int64_t B, const float* const* d_dy, float* const* d_out);
+int32_t crux_ensemble_forward_recording(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_x, int64_t B, float* d_mean, float* d_evar);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer
