@@ -307,16 +307,17 @@ def test_phase_records_in_global_memory_give_the_same_epochs(gpu_ctx, monkeypatc
         assert np.array_equal(x, y), np.abs(x - y).max()
 
 
-@pytest.mark.parametrize("dims", [[8, 256, 256, 4], [8, 256, 4], [128, 4]], ids=["L3", "L2", "L1"])
-def test_chained_dqn_epochs_equal_single_epoch_calls(gpu_ctx, dims):
+@pytest.mark.parametrize("dims,B", [([8, 256, 256, 4], 128), ([8, 256, 4], 128), ([128, 4], 128), ([8, 256, 256, 4], 320)], ids=["L3", "L2", "L1", "L3-B320"])
+def test_chained_dqn_epochs_equal_single_epoch_calls(gpu_ctx, dims, B):
     """crux_dqn_epochs (the c_opt.epochs epochs of one value_training recorded into one list, no host round trip between them) == the same epochs as
     separate crux_dqn_epoch calls: sampled rows, priorities, networks and infos, bit for bit -- with prioritized replay on a FULL ring (incremental tree
     refresh inside the chain) and on a ring that is still filling (the chain is cut where the tree needs a plain rebuild). Networks of two and of one Dense layer
     have a backward chain shorter than the replay-tree refresh: the overlap of neighbouring epochs shrinks there (exec.hip `ov`; ADVICE r2: with the full overlap the
-    search of epoch e + 1 raced the root-path refresh of epoch e)."""
+    search of epoch e + 1 raced the root-path refresh of epoch e). B = 320: the plans past the 256-row seam -- no sequential target + head group (exec.hip sq0 = 0 / sq = 0),
+    root paths as an op of their own (touch_split)."""
     no = dims[0]
     def run(chained, fill):
-        rng = np.random.default_rng(3); N, B = 20_000, 128
+        rng = np.random.default_rng(3); N = 20_000
         S, A = crux.ContinuousSpace(no), crux.DiscreteSpace(4)
         buf = crux.ExperienceBuffer(S, A, N, prioritized=True); D = crux.buffer_like(buf, capacity=B)
         n0 = N if fill else N // 2
@@ -339,11 +340,13 @@ def test_chained_dqn_epochs_equal_single_epoch_calls(gpu_ctx, dims):
             assert np.array_equal(x, y), fill
 
 
-def test_chained_sac_epochs_equal_single_epoch_calls(gpu_ctx):
+@pytest.mark.parametrize("B", [256, 320])
+def test_chained_sac_epochs_equal_single_epoch_calls(gpu_ctx, B):
     """crux_sac_epochs (chains of up to 8 epochs per recorded list, update_every handled per epoch) == crux_sac_epoch called epoch by epoch, bit for bit;
-    11 epochs = one full chain + a partial one, critic every epoch, actor + target update every second epoch."""
+    11 epochs = one full chain + a partial one, critic every epoch, actor + target update every second epoch. B = 320: the plan without the sequential
+    target + critic-head group (exec.hip sq = 0)."""
     def run(chained):
-        rng = np.random.default_rng(4); B, n = 256, 5000
+        rng = np.random.default_rng(4); n = 5000
         S, A = crux.ContinuousSpace(3), crux.ContinuousSpace(1)
         buf = crux.ExperienceBuffer(S, A, n); D = crux.buffer_like(buf, capacity=B)
         buf.push_({"s": rng.normal(0, 1, (3, n)).astype(np.float32), "a": rng.uniform(-2, 2, (1, n)).astype(np.float32), "sp": rng.normal(0, 1, (3, n)).astype(np.float32),
