@@ -189,7 +189,7 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float la
   rc = crux_launch_check(c, "k_iq_gp_head"); if (rc) return rc;
   rc = iq_penalty_sweeps(D, B, B, ib); if (rc) return rc;
   rc = iq_add_penalty(D, ib); if (rc) return rc;
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, D->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
   hipLaunchKernelGGL(k_advil_d_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, lambda_gp, ib.dinfo, ib.extra);
   rc = crux_launch_check(c, "k_advil_d_info"); if (rc) return rc;
   rc = adam_gated(D, ib.ssq, ib.status); if (rc) return rc;
@@ -221,7 +221,7 @@ int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, floa
   rc = crux_launch_check(c, "k_advil_da"); if (rc) return rc;
   rc = crux_dense_backward(actor, S, B, da, 1.0f, true, nullptr, c->stream); if (rc) return rc;          // nothing deferred: the regularizer adds to a complete gradient
   if (orth) { rc = orth_enqueue(actor, beta_orth, true, ob); if (rc) return rc; }
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, actor->g, (int64_t)an.n_params, (float*)nullptr, (int64_t)0, sm.ssq, Sumsq2Fix{});
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, actor->g, (int64_t)an.n_params, (float*)nullptr, (int64_t)0, sm.ssq, Sumsq2Fix{});
   hipLaunchKernelGGL(k_advil_pi_info, dim3(1), dim3(1), 0, c->stream, (const double*)sm.stats, (const double*)mpart, orth ? (const double*)ob.part : (const double*)nullptr, an.L,
                      (const double*)sm.ssq, B, ad, lambda_bc, beta_orth, sm.dinfo, sm.extra);
   rc = crux_launch_check(c, "k_advil_pi_info"); if (rc) return rc;

@@ -12,7 +12,7 @@
 //                 dmu = w (u - mu) / sigma^2 (u = a, or atanh(clamp(a / ascale)) when squashed), and per block the Float64 sums of both softplus terms and of
 //                 w ((u - mu)^2 / sigma^2 [logSigma inside the clamp] - 1) per logSigma slot -- wave sums added into LDS in a fixed order, no per-thread arrays
 //   k_asaf_gx     the block partials added in block order: g[logSigma] = sum - 0.1 (the entropy's share), the two softplus sums; poisoned when the NaN flag is set
-//   dense backward, k_sumsq2 (norm over the raw gradient), k_asaf_info, k_asaf_clip (optional: clamp to +-clip_value after the norm, ClipValue before Adam), gated Adam
+//   dense backward, Sumsq2Op (norm over the raw gradient), k_asaf_info, k_asaf_clip (optional: clamp to +-clip_value after the norm, ClipValue before Adam), gated Adam
 // No float atomics anywhere: two identical calls give identical bits. The engine's relu maps NaN to 0 where NNlib's propagates it, so NaN inputs are flagged and the head
 // poisons what it forms (the idiom of k_iq_expand / k_iq_head).
 // The chain (crux_asaf_batch_train) enqueues epochs x (crux_buffer_shuffle, every minibatch step) with one host synchronisation at the end: chain.h holds the loop, the
@@ -151,7 +151,7 @@ static int32_t asaf_enqueue_step(crux_mlp* pi, const crux_buffer* b, int64_t off
   rc = crux_launch_check(c, "k_asaf_head"); if (rc) return rc;
   Sumsq2Fix fx{};
   rc = crux_dense_backward(pi, ab.X, NC, ab.dy, 1.0f, true, nullptr, c->stream, &fx, 0); if (rc) return rc;
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, pi->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, pi->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   hipLaunchKernelGGL(k_asaf_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, n, NE, ls, ad, (const int32_t*)status, row, row + CRUX_INFO_N);
   if (clip > 0.f && clip < INFINITY) hipLaunchKernelGGL(k_asaf_clip, dim3(nblk(nd.n_params)), dim3(256), 0, c->stream, pi->g, clip, (int64_t)nd.n_params);
   rc = crux_launch_check(c, "k_asaf_info"); if (rc) return rc;

@@ -1,7 +1,7 @@
 // chain.h -- host-side scaffolding shared by the imitation-learning and offline entry points of the off-policy unity build (cql.hip, iq.hip, advil.hip, asaf.hip,
 // gail_off.hip, nda_gail.hip): the small region of one step, and for a chain of steps the scratch layout behind the shuffles' staging, the epoch loop, the read-back and
 // the report. The read-back of ONE step is finish_step (sac.hip). Included from offpolicy_unit.hip behind sac.hip: it uses Carve and crux_pinned (common.h) and the status
-// convention of adam_gated (sac.hip: k_adam_gated leaves the word at CRUX_ENAN from the first NaN norm on and updates nothing after that). Host code only; no kernel lives here.
+// convention of adam_gated (sac.hip: AdamGatedOp leaves the word at CRUX_ENAN from the first NaN norm on and updates nothing after that). Host code only; no kernel lives here.
 #pragma once
 
 template <class F> struct ScopeGuard { F f; bool armed = true; ~ScopeGuard() { if (armed) f(); } void dismiss() { armed = false; } };      // runs f when the scope is left, unless dismissed

@@ -186,7 +186,7 @@ struct crux_buffer {
   int32_t* topo_left = nullptr; int32_t* topo_right = nullptr; int32_t* topo_level_off = nullptr;   // heap-numbered nodes (root 1, children 2k / 2k + 1); level l = [2^l, 2^(l+1))
   float* topo_total = nullptr; float* topo_prefix = nullptr;
   // incremental maintenance (per.hip): `cumsum` holds the leaf-LOCAL running sums; c[i] = prefix[leaf(i)] + cumsum[i]. After update_priorities! only the
-  // touched leaves are re-summed (k_leaf_refresh); the node totals / prefixes are re-derived by the LDS tree pass at the next sample.
+  // touched leaves are re-summed (LeafRefreshOp); the node totals / prefixes are re-derived by the LDS tree pass at the next sample.
   int64_t per_run_n = -1; bool per_full_dirty = true;
   int32_t* order_a = nullptr;    // device [capacity] logical->physical order scratch for batch_train
   int32_t* order_b = nullptr;

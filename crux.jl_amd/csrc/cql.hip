@@ -167,7 +167,7 @@ static int32_t cql_backward(crux_mlp* n, const float* sa, int64_t NB, const floa
   const float* dcur = d_dy; float* dnxt = ws_delta(n, 0); float* dspare = ws_delta(n, 1);
   if (nd.acts[nd.L - 1] != CRUX_ACT_IDENTITY) {
     const int64_t cnt = (int64_t)nd.dims[nd.L] * NB;
-    hipLaunchKernelGGL(k_act_grad, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, d_dy, (const float*)crux_dense_act(n, nd.L), nd.acts[nd.L - 1], cnt, dnxt);
+    crux_launch<ActGradOp>((unsigned)((cnt + 255) / 256), 256, st, d_dy, (const float*)crux_dense_act(n, nd.L), nd.acts[nd.L - 1], cnt, dnxt);
     dcur = dnxt; dnxt = dspare; dspare = const_cast<float*>(dcur);
   }
   for (int l = nd.L - 1; l >= 0; --l) {
@@ -236,7 +236,7 @@ int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_m
   const int64_t NB = (int64_t)(1 + 2 * n_samples) * b->elements;
   rc = cql_backward(q1, cb.sa, NB, cb.dy1, cb.part, c->stream); if (rc) return rc;
   rc = cql_backward(q2, cb.sa, NB, cb.dy2, cb.part, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, q1->g, (int64_t)q1->nd.n_params, q2->g, (int64_t)q2->nd.n_params, cb.ssq, Sumsq2Fix{});
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, q1->g, (int64_t)q1->nd.n_params, q2->g, (int64_t)q2->nd.n_params, cb.ssq, Sumsq2Fix{});
   hipLaunchKernelGGL(k_cql_critic_info, dim3(1), dim3(1), 0, c->stream, (const double*)cb.stats, (const double*)cb.ssq, cb.dinfo);
   rc = adam_gated(q1, cb.ssq, cb.status); if (rc) return rc;
   rc = adam_gated(q2, cb.ssq, cb.status); if (rc) return rc;

@@ -148,7 +148,6 @@ struct ActGradOp { static __device__ __forceinline__ void run(const unsigned bid
   const int64_t i = (int64_t)bid_ * blockDim.x + threadIdx.x; if (i >= n) return;
   dz[i] = crux_act_grad(act, y[i], dy[i]);
 } };
-__global__ void k_act_grad(const float* __restrict__ dy, const float* __restrict__ y, int act, int64_t n, float* __restrict__ dz) { ActGradOp::run(blockIdx.x, gridDim.x, dy, y, act, n, dz); }
 static inline bool vec_ok(const float* p, int64_t s_k, int64_t s_outer, int K) {
   return s_k == 1 && (K & 3) == 0 && (s_outer & 3) == 0 && (((uintptr_t)p) & 15) == 0;
 }
@@ -164,7 +163,7 @@ static int32_t launch_gemm(crux_ctx* c, const GemmArgs& q, hipStream_t st) {
   if (crux_exec_recording(c)) {                       // fused sequence (exec.hip): the same tile bodies, run by the phase launches
     // the phase launches run over the whole chip like the stand-alone launches and split K over the four waves of a workgroup whenever those do
     const bool split = q.K >= 128 && tiles <= 4096 && !no_split;
-    crux_exec_push<GemmOp, OP_GEMM>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0) | (quart ? 8 : 0)));
+    crux_exec_push<GemmOp>(c, (unsigned)(split ? tiles : (tiles + 3) / 4), q, (int)((av ? 1 : 0) | (bv ? 2 : 0) | (split ? 4 : 0) | (quart ? 8 : 0)));
     return CRUX_OK;
   }
   if (q.K >= 128 && tiles <= 4096 && !no_split) {     // deep reductions: split K over the workgroup's four waves
@@ -227,7 +226,7 @@ int32_t crux_dense_forward(crux_mlp* n, const float* d_x, int64_t B, hipStream_t
   if (crux_dense_fwd_fused(n)) {      // layers 0 and 1 as one launch (dense_fused.h)
     Fwd12Args a{}; a.W1 = dense_w(n, 0); a.b1 = n->p + nd.boff[0]; a.W2 = dense_w(n, 1); a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
     a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act1 = nd.acts[0]; a.act2 = nd.acts[1];
-    CRUX_RUN(c, Fwd12Op, OP_FWD12, k_fwd12, df_fwd12_blocks(nd, B), 256, st, a);
+    CRUX_RUN(c, Fwd12Op, df_fwd12_blocks(nd, B), 256, st, a);
     rc = crux_launch_check(c, "k_fwd12"); if (rc) return rc;
     x = a.H2; l0 = 2;
   }
@@ -250,7 +249,7 @@ int32_t crux_dense_forward12(crux_mlp* n, const float* d_x, int64_t B, hipStream
   rc = dense_sn_power(n, st); if (rc) return rc;
   Fwd12Args a{}; a.W1 = dense_w(n, 0); a.b1 = n->p + nd.boff[0]; a.W2 = dense_w(n, 1); a.b2 = n->p + nd.boff[1]; a.x = d_x; a.H1 = crux_dense_act(n, 1); a.H2 = crux_dense_act(n, 2);
   a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act1 = nd.acts[0]; a.act2 = nd.acts[1];
-  CRUX_RUN(c, Fwd12Op, OP_FWD12, k_fwd12, df_fwd12_blocks(nd, B), 256, st, a);
+  CRUX_RUN(c, Fwd12Op, df_fwd12_blocks(nd, B), 256, st, a);
   return crux_launch_check(c, "k_fwd12");
 }
 // the input-gradient chain down to layer 0's dZ (the caller's op applies layer 0's weights): returns the buffer [dims[1] x B] Dgrad2W1Op fills
@@ -260,7 +259,7 @@ int32_t crux_dense_dgrad_to_dz1(crux_mlp* n, const float* d_x, int64_t B, const 
   DzSrc z{}; z.W3 = dense_w(n, 2); z.dZ3 = d_dy; z.out3 = nd.dims[3]; z.act = nd.acts[1];
   Dgrad2Args a{}; a.z = z; a.W2 = dense_w(n, 1); a.dZ2 = crux_dense_act(n, 2); a.H1 = crux_dense_act(n, 1); a.x = d_x; a.part = ws_part(n); a.dZ1 = ws_delta(n, 0);
   a.in0 = nd.dims[0]; a.out1 = nd.dims[1]; a.out2 = nd.dims[2]; a.B = (int32_t)B; a.act0 = nd.acts[0]; a.want_g = 0;
-  CRUX_RUN(c, Dgrad2W1Op, OP_DGRAD2W1, k_dgrad2w1, (unsigned)((nd.dims[1] >> 4) * 4), 256, st, a);
+  CRUX_RUN(c, Dgrad2W1Op, (unsigned)((nd.dims[1] >> 4) * 4), 256, st, a);
   *d_dz1 = a.dZ1;
   return crux_launch_check(c, "k_dgrad2w1");
 }
@@ -274,7 +273,7 @@ int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const floa
   const float* dcur = d_dy; float* dnxt = ws_delta(n, 0); float* dspare = ws_delta(n, 1);
   if (nd.acts[nd.L - 1] != CRUX_ACT_IDENTITY) {   // dZ_L = act'(Y_L) .* dY; an identity output layer (the usual critic / mean head) uses dY as it is
     const int64_t cnt = (int64_t)nd.dims[nd.L] * B;
-    CRUX_RUN(c, ActGradOp, OP_ACT_GRAD, k_act_grad, (unsigned)((cnt + 255) / 256), 256, st, d_dy, crux_dense_act(n, nd.L), nd.acts[nd.L - 1], cnt, dnxt);
+    CRUX_RUN(c, ActGradOp, (unsigned)((cnt + 255) / 256), 256, st, d_dy, crux_dense_act(n, nd.L), nd.acts[nd.L - 1], cnt, dnxt);
     dcur = dnxt; dnxt = dspare; dspare = const_cast<float*>(dcur);
   }
   // with parameter gradients the fused pair leaves layer 0's gradient as quarter partials: only where the caller runs Sumsq2Op next (defer); input-gradient chains need no such reader
@@ -294,10 +293,10 @@ int32_t crux_dense_backward(crux_mlp* n, const float* d_x, int64_t B, const floa
       DzSrc z{}; const float* dz1 = dcur;
       if (fused3) { z.W3 = dense_w(n, 2); z.dZ3 = dcur; z.out3 = nd.dims[3]; z.act = nd.acts[1]; dz1 = crux_dense_act(n, 2); }      // dcur is still dZ of the output layer; the operand pointer becomes H2
       if (want_g) { Wgrad2Args w{}; w.z = z; w.dZ = dz1; w.X = x; w.dW = n->g + nd.woff[1]; w.db = n->g + nd.boff[1]; w.scale = gscale; w.out = out; w.in = in; w.B = (int32_t)B; w.nf = nanflags;
-        CRUX_RUN(c, Wgrad2Op, OP_WGRAD2, k_wgrad2, (unsigned)((out >> 5) * (in >> 5)), 256, st, w); }
+        CRUX_RUN(c, Wgrad2Op, (unsigned)((out >> 5) * (in >> 5)), 256, st, w); }
       Dgrad2Args a{}; a.z = z; a.W2 = dense_w(n, 1); a.dZ2 = dz1; a.H1 = x; a.x = d_x; a.part = ws_part(n); a.dZ1 = d_dx ? dnxt : nullptr;
       a.in0 = nd.dims[0]; a.out1 = in; a.out2 = out; a.B = (int32_t)B; a.act0 = nd.acts[0]; a.want_g = want_g ? 1 : 0; a.nf = nanflags;
-      CRUX_RUN(c, Dgrad2W1Op, OP_DGRAD2W1, k_dgrad2w1, (unsigned)((in >> 4) * 4), 256, st, a);
+      CRUX_RUN(c, Dgrad2W1Op, (unsigned)((in >> 4) * 4), 256, st, a);
       if (want_g) { defer->part[defer_slot] = a.part; defer->out1[defer_slot] = in; defer->in0[defer_slot] = nd.dims[0]; defer->woff[defer_slot] = nd.woff[0]; defer->boff[defer_slot] = nd.boff[0]; defer->scale[defer_slot] = gscale; }
       if (d_dx) {                // the input gradient of layer 0 from the dZ of layer 0 the fused op left in the workspace
         GemmArgs q{}; q.A = dense_w(n, 0); q.sAi = in; q.sAk = 1; q.B = dnxt; q.sBk = 1; q.sBj = in; q.M = nd.dims[0]; q.N = (int)B; q.K = in;

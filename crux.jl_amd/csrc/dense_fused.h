@@ -22,7 +22,7 @@ __device__ __forceinline__ int df_kper(int K) { return K >= 128 ? ((((K + 3) >> 
 
 // ---- layers 0 + 1 forward -------------------------------------------------------------------------------------------------------------------
 struct Fwd12Args { const float* W1; const float* b1; const float* W2; const float* b2; const float* x; float* H1; float* H2; int32_t in0, out1, out2, B, act1, act2; };
-struct Fwd12Op { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Fwd12Args q) {
+struct Fwd12Op { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Fwd12Args q) {
   // One 16 x 16 tile of layer 1's output per workgroup, Gemm16's split-K form: wave w walks quarter w of K = out1 and wave 0 adds the quarters in wave order. The
   // layer-0 values a wave needs are the out1 / 4 features of ITS quarter for the tile's 16 samples: it evaluates them itself (K = in0 <= 32: 4-8 MFMAs per 16 features),
   // and the D-layout result [feature 4 g + r][sample c] IS the B operand of the layer-1 MFMA for that 16-group -- no LDS panel, no workgroup barrier before the combine.
@@ -76,7 +76,6 @@ struct Fwd12Op { static __device__ __forceinline__ void run(const unsigned bid_,
     for (int r = 0; r < 4; ++r) o[r] = crux_act(q.act2, pa[r] + b2v[r]);
     *(f32x4*)(q.H2 + i0 + 4 * g + (int64_t)q.out2 * s) = o; }
 } };
-__global__ __launch_bounds__(256) void k_fwd12(Fwd12Args q) { Fwd12Op::run(blockIdx.x, gridDim.x, q); }
 static inline bool df_fwd12_ok(const NetDesc& nd) {
   return nd.L >= 2 && nd.dims[0] <= 32 && (nd.dims[1] == 128 || nd.dims[1] == 192 || nd.dims[1] == 256) && nd.dims[2] >= 16 && (nd.dims[2] & 15) == 0;
 }
@@ -93,7 +92,7 @@ template <int O3> __device__ __forceinline__ float df_dz(const DzSrc& z, float h
   return crux_act_grad(z.act, h, v);
 }
 struct Wgrad2Args { const float* dZ; const float* X; float* dW; float* db; float scale; int32_t out, in, B; DzSrc z; int32_t* nf; };      // z.W3 != nullptr: dZ points at H (the layer's own output) and the gradient is formed on the fly
-struct Wgrad2Op { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Wgrad2Args q) {
+struct Wgrad2Op { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Wgrad2Args q) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int tI = q.out >> 5; const int bi = (int)bid_ % tI, bk = (int)bid_ / tI; const int I0 = bi << 5, K0 = bk << 5;
   const int K = q.B; const bool quartered = K >= 128; const int kper = df_kper(K);
@@ -177,7 +176,6 @@ struct Wgrad2Op { static __device__ __forceinline__ void run(const unsigned bid_
   *(f32x4*)(q.dW + i + (int64_t)q.out * kc) = o;
   if (q.nf && bad) atomicOr((int*)q.nf, 1);
 } };
-__global__ __launch_bounds__(256) void k_wgrad2(Wgrad2Args q) { Wgrad2Op::run(blockIdx.x, gridDim.x, q); }
 
 // ---- data gradient through layer 1, then layer 0's weight gradient, for 16 layer-0 features x ONE QUARTER of the samples -----------------------------------------
 //   dH[f, s] = sum_o W2[o, f] dZ2[o, s]   (K = out2)      dZ1 = act0'(H1) .* dH      dW1[f, q] = scale * sum_s dZ1[f, s] x[q, s], db1[f] = scale * sum_s dZ1[f, s]   (K = B)
@@ -304,8 +302,7 @@ template <int O3> struct Dgrad2W1OpT { static __device__ __forceinline__ void ru
     if (tq == 0) prow_out[(int64_t)(F0 + c) * DF_PART_STRIDE(q.in0) + q.in0 + g] = prow;      // lane (c, g): the partial row sum of feature F0 + c over this quarter's k = 16 u + 4 g + r
   } }
 } };
-struct Dgrad2W1Op { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Dgrad2Args q) { if (q.z.W3 && q.z.out3 > 1) Dgrad2W1OpT<4>::run(bid_, nb_, q); else Dgrad2W1OpT<1>::run(bid_, nb_, q); } };      // (the op type the recorder packs; stand-alone launches)
-__global__ __launch_bounds__(256) void k_dgrad2w1(Dgrad2Args q) { Dgrad2W1Op::run(blockIdx.x, gridDim.x, q); }
+struct Dgrad2W1Op { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, Dgrad2Args q) { if (q.z.W3 && q.z.out3 > 1) Dgrad2W1OpT<4>::run(bid_, nb_, q); else Dgrad2W1OpT<1>::run(bid_, nb_, q); } };      // (the op type the recorder packs; stand-alone launches)
 // the pair (Wgrad2Op on layer 1, Dgrad2W1Op through layer 1 into layer 0) applies to: a narrow input, layer widths in whole 32-blocks, K = out2 in {128, 192, 256}, 128 <= B <= 256
 static inline bool df_bwd_ok(const NetDesc& nd, int64_t B) {
   return nd.L >= 2 && nd.dims[0] <= 16 && nd.dims[1] >= 32 && (nd.dims[1] & 31) == 0 && (nd.dims[2] == 128 || nd.dims[2] == 192 || nd.dims[2] == 256) && B >= 128 && B <= 256;

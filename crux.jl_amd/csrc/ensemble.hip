@@ -15,14 +15,14 @@
 //                                partials; a NaN in o, y or w raises the NaN flag and poisons the column's seeds (the engine's relu maps NaN to 0 where NNlib's does not)
 //   crux_dense_backward_group    2 L - 1 launches (+ 1 for an output activation)
 //   k_ens_sumsq                  Sumsq2Op per member: 64 Float64 partials each
-//   k_ens_adam                   the info row (block 0) and k_adam_gated's update for every member, gated on ALL members: one NaN partial anywhere (or the NaN flag) and
+//   k_ens_adam                   the info row (block 0) and AdamGatedOp's update for every member, gated on ALL members: one NaN partial anywhere (or the NaN flag) and
 //                                no member is updated, the status word goes to CRUX_ENAN and stays there
 // No float atomics anywhere: two identical calls give identical bits.
 #include "common.h"
 #include "exec.h"
 
 #define ENS_HEAD_BLOCKS 16                      // loss partials per member
-#define ENS_SSQ_STRIDE (2 + SUMSQ_BLOCKS)       // doubles per member: [0] the sum (ssq_finalize), [1..64] k_sumsq2's partials
+#define ENS_SSQ_STRIDE (2 + SUMSQ_BLOCKS)       // doubles per member: [0] the sum (ssq_finalize), [1..64] Sumsq2Op's partials
 #define ENS_EPS32 1.1920929e-07f                // eps(Float32)
 
 struct EnsOut { const float* o[CRUX_GROUP_MAX]; };      // the members' output activations [nout x B], each in its own workspace
@@ -134,7 +134,7 @@ struct EnsAdam { float* p[CRUX_GROUP_MAX]; const float* g[CRUX_GROUP_MAX]; float
 __global__ __launch_bounds__(256) void k_ens_adam(const EnsAdam t, int M, const unsigned bpm, double eta, double b1, double b2, double eps, int64_t n, double* __restrict__ ssq,
                                                   const double* __restrict__ hpart, double denom, const int32_t* __restrict__ nanflag, int32_t* __restrict__ status, float* __restrict__ row) {
   const unsigned mem = blockIdx.x / bpm, bid = blockIdx.x - mem * bpm;
-  bool b_ = nanflag[0] != 0;      // the gate asks whether ANY member's squared norm is NaN: exactly when one of its partials is (k_adam_gated)
+  bool b_ = nanflag[0] != 0;      // the gate asks whether ANY member's squared norm is NaN: exactly when one of its partials is (AdamGatedOp)
   for (int k = (int)(threadIdx.x & 63); k < M * SUMSQ_BLOCKS; k += 64) b_ = b_ || isnan(ssq[(size_t)(k / SUMSQ_BLOCKS) * ENS_SSQ_STRIDE + 1 + (k % SUMSQ_BLOCKS)]);
   const bool bad = __ballot(b_) != 0ull;
   if (status[0] == CRUX_ENAN) return;

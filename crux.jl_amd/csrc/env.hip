@@ -685,7 +685,7 @@ __global__ __launch_bounds__(256) void k_dqn_small_solve(SmallSolveArgs q) {
     // ---- value_training (:66-111)
     for (int ep = 0; ep < q.epochs; ++ep) {
       const uint64_t ictr = si * (uint64_t)q.epochs + (uint64_t)ep;
-      // rand!(D, buffer): uniform_sample! (experience_buffer.jl:317-321) with the library's Philox draw (per.hip k_uniform_ids), then the row gather
+      // rand!(D, buffer): uniform_sample! (experience_buffer.jl:317-321) with the library's Philox draw (per.hip UniformIdsOp), then the row gather
       for (int j = tid; j < B; j += 256) { const crux_u32x4 x = crux_philox(q.sample_seed, ictr * (uint64_t)B + (uint64_t)j, q.sample_stream, CRUX_RNG_SAMPLE);
         q.bidx[j] = (int64_t)(((uint64_t)x.v[0] * (uint64_t)elements) >> 32); }
       __threadfence_block(); __syncthreads(); SS_T(1);
@@ -816,7 +816,7 @@ __global__ __launch_bounds__(64) void k_dqn_tiny_solve(SmallSolveArgs q) {
       for (int half = 0; half < 2; ++half) {
         const int j = lane + 64 * half;
         if (j < B) {
-          // rand!(D, buffer): uniform_sample! with the library's Philox draw (per.hip k_uniform_ids)
+          // rand!(D, buffer): uniform_sample! with the library's Philox draw (per.hip UniformIdsOp)
           const crux_u32x4 xr = crux_philox(q.sample_seed, ictr * (uint64_t)B + (uint64_t)j, q.sample_stream, CRUX_RNG_SAMPLE);
           const int64_t row = (int64_t)(((uint64_t)xr.v[0] * (uint64_t)elements) >> 32);
           q.bidx[j] = row;

@@ -7,75 +7,38 @@
 #define EXEC_SMALL_BYTES (256 * 1024)
 
 // ---- device: the phase kernels ------------------------------------------------------------------------------------------------------------
-#define EXEC_SWITCH(DISPATCH) \
-      switch (kid) { \
-        case OP_GEMM: DISPATCH<GemmOp>(op, b); break; \
-        case OP_ACT_GRAD: DISPATCH<ActGradOp>(op, b); break; \
-        case OP_GAUSS_EXPLORE: DISPATCH<GaussExploreOp>(op, b); break; \
-        case OP_CONCAT_SA: DISPATCH<ConcatSaOp>(op, b); break; \
-        case OP_SAC_TARGET: DISPATCH<SacTargetOp>(op, b); break; \
-        case OP_DPG_ACTION: DISPATCH<DpgActionOp>(op, b); break; \
-        case OP_DPG_TARGET: DISPATCH<DpgTargetOp>(op, b); break; \
-        case OP_FILL: DISPATCH<FillOp>(op, b); break; \
-        case OP_SLICE_ROWS: DISPATCH<SliceRowsOp>(op, b); break; \
-        case OP_MEAN_INFO: DISPATCH<MeanInfoOp>(op, b); break; \
-        case OP_TEMP_HEAD: DISPATCH<TempHeadOp>(op, b); break; \
-        case OP_Q_HEAD: DISPATCH<QHeadOp>(op, b); break; \
-        case OP_TD_HEAD: DISPATCH<TdHeadOp>(op, b); break; \
-        case OP_TD_INFO: DISPATCH<TdInfoOp>(op, b); break; \
-        case OP_SUMSQ2: DISPATCH<Sumsq2Op>(op, b); break; \
-        case OP_CRITIC_INFO: DISPATCH<CriticInfoOp>(op, b); break; \
-        case OP_ACTOR_HEAD: DISPATCH<ActorHeadOp>(op, b); break; \
-        case OP_ACTOR_GRAD: DISPATCH<ActorGradOp>(op, b); break; \
-        case OP_ROWSUM: DISPATCH<RowsumOp>(op, b); break; \
-        case OP_ACTOR_INFO: DISPATCH<ActorInfoOp>(op, b); break; \
-        case OP_ADAM_GATED: DISPATCH<AdamGatedOp>(op, b); break; \
-        case OP_PER_SEARCH: DISPATCH<PerSearchOp>(op, b); break; \
-        case OP_UNIFORM_IDS: DISPATCH<UniformIdsOp>(op, b); break; \
-        case OP_GATHER_RING_ALL: DISPATCH<GatherRingAllOp>(op, b); break; \
-        case OP_RING_IDS: DISPATCH<RingIdsOp>(op, b); break; \
-        case OP_LEAF_REFRESH: DISPATCH<LeafRefreshOp>(op, b); break; \
-        case OP_TREE_TOUCH: DISPATCH<TreeTouchOp>(op, b); break; \
-        case OP_LEAF_TOUCH: DISPATCH<LeafTouchOp>(op, b); break; \
-        case OP_PER_UPDATE: DISPATCH<PerUpdateOp>(op, b); break; \
-        case OP_DQN_TARGET: DISPATCH<DqnTargetOp>(op, b); break; \
-        case OP_TD_ERROR: DISPATCH<TdErrorOp>(op, b); break; \
-        case OP_POLYAK: DISPATCH<PolyakOp>(op, b); break; \
-        case OP_COPY_F32: DISPATCH<CopyF32Op>(op, b); break; \
-        case OP_ADAM_ADVANCE: DISPATCH<AdamAdvanceOp>(op, b); break; \
-        case OP_ADAM_SELF: DISPATCH<AdamSelfOp>(op, b); break; \
-        case OP_ADAM_ADVANCE_SELF: DISPATCH<AdamAdvanceSelfOp>(op, b); break; \
-        case OP_SOFTQ_TARGET: DISPATCH<SoftqTargetOp>(op, b); break; \
-        case OP_PER_SAMPLE: PerSampleGatherOp::run_ptr(b, op->nblocks, (const PerSampleArgs*)op->args); break; \
-        case OP_ACTOR_EXPLORE_TILE: DISPATCH<ActorExploreTileOp>(op, b); break; \
-        case OP_SAC_CRITIC_TILE: DISPATCH<SacCriticTileOp>(op, b); break; \
-        case OP_CRITIC_INFO2: DISPATCH<CriticInfo2Op>(op, b); break; \
-        case OP_SAC_ACTOR_TILE: DISPATCH<SacActorTileOp>(op, b); break; \
-        case OP_ACTOR_INFO2: DISPATCH<ActorInfo2Op>(op, b); break; \
-        case OP_CRITIC_DX_TILE: DISPATCH<CriticDxActorGradTileOp>(op, b); break; \
-        case OP_DQN_TD_TILE: DISPATCH<DqnTdTileOp>(op, b); break; \
-        case OP_TD_INFO2: DISPATCH<TdInfo2Op>(op, b); break; \
-        case OP_FWD12: DISPATCH<Fwd12Op>(op, b); break; \
-        case OP_WGRAD2: DISPATCH<Wgrad2Op>(op, b); break; \
-        case OP_DGRAD2W1: if constexpr (EXEC_HEAVY == 1) { DISPATCH<Dgrad2W1OpT<1>>(op, b); } else if constexpr (EXEC_HEAVY == 2) { DISPATCH<Dgrad2W1Op>(op, b); } break; \
-        default: break; \
-      }
-
-// the ops that may run as the sequential tail of a one-block op (the loss heads that consume a target): a small switch of its own, so that the main dispatch stays
-// straight-line (with the full switch inside a loop every phase ran ~1 us longer)
-#define EXEC_SWITCH_TAIL(DISPATCH) \
-      switch (kid) { \
-        case OP_TD_HEAD: DISPATCH<TdHeadOp>(op, b); break; \
-        case OP_Q_HEAD: DISPATCH<QHeadOp>(op, b); break; \
-        case OP_PER_UPDATE: DISPATCH<PerUpdateOp>(op, b); break; \
-        default: break; \
-      }
-
-// an op body with its record read straight from global memory at a uniform address (scalar loads): the global-record phase kernel below
-template <class Op> __device__ __forceinline__ void exec_dispatch_g(const ExecOp* op, unsigned bid) {
+// an op body with its record read where it lies, at a uniform address (scalar loads). Rec: an ExecOp of the list in global memory (k_phase), or a KOp naming a
+// record inside the kernel arguments (k_phase_k)
+template <class Op, class Rec> __device__ __forceinline__ void exec_dispatch(const Rec* op, unsigned bid) {
   const OpPack<Op> p = *(const OpPack<Op>*)op->args;
   exec_apply<Op>(bid, op->nblocks, p);
 }
+// The dispatch of a phase kernel, generated from the op table (exec.h): `kid`, `op` and `b` are the caller's. Two entries are written by hand:
+//   OP_PER_SAMPLE reads its arguments through a pointer (PerSampleGatherOp::run_ptr: a by-value copy of the column table would live in scratch);
+//   OP_DGRAD2W1 is compiled into the EXEC_HEAVY instantiations only (~300 VGPRs: see k_phase), in the form the phase needs.
+#define EXEC_CASE(id, Op, tail) case id: exec_dispatch<Op>(op, b); break;
+#define EXEC_SWITCH \
+      switch (kid) { \
+        CRUX_EXEC_OPS(EXEC_CASE, EXEC_OP_SKIP) \
+        case OP_PER_SAMPLE: PerSampleGatherOp::run_ptr(b, op->nblocks, (const PerSampleArgs*)op->args); break; \
+        case OP_DGRAD2W1: if constexpr (EXEC_HEAVY == 1) { exec_dispatch<Dgrad2W1OpT<1>>(op, b); } else if constexpr (EXEC_HEAVY == 2) { exec_dispatch<Dgrad2W1Op>(op, b); } break; \
+        default: break; \
+      }
+// the ops that may run as the sequential tail of a one-block op (the table's tail column; exec_schedule refuses any other with exec_op_tail): a small switch of its
+// own, so that the main dispatch stays straight-line (with the full switch inside a loop every phase ran ~1 us longer)
+#define EXEC_CASE_TAIL_0(id, Op)
+#define EXEC_CASE_TAIL_1(id, Op) case id: exec_dispatch<Op>(op, b); break;
+#define EXEC_CASE_TAIL(id, Op, tail) EXEC_CASE_TAIL_##tail(id, Op)
+#define EXEC_SWITCH_TAIL \
+      switch (kid) { \
+        CRUX_EXEC_OPS(EXEC_CASE_TAIL, EXEC_OP_SKIP) \
+        default: break; \
+      }
+// every op of the table has a body, and its arguments fit an ExecOp as plain data
+#define EXEC_OP_CHECK(id, Op, ...) static_assert(sizeof(OpPack<Op>) <= CRUX_EXEC_ARG_BYTES, #Op ": arguments exceed the ExecOp slot"); \
+                                   static_assert(std::is_trivially_copyable<OpPack<Op>>::value, #Op ": arguments must be plain data");
+CRUX_EXEC_OPS(EXEC_OP_CHECK, EXEC_OP_CHECK)
+
 // One PHASE of a recorded sequence as one launch over the whole chip: block x of the grid belongs to the op whose block range contains x. The ops of a
 // phase do not depend on each other, the dependency between phases is the kernel boundary -- no in-kernel barrier, no coherence question, all 256 CUs.
 // A fused epoch then costs (number of phases) launches instead of (number of kernels): 13 instead of 25 for a DQN epoch, 30 instead of ~75 for SAC (10 / 27 per epoch inside a chain).
@@ -87,10 +50,10 @@ __global__ __launch_bounds__(256) void k_phase(const ExecOp* __restrict__ ops, i
   unsigned b = blockIdx.x; int o = 0;
   for (;;) { const unsigned nb = (ops[o].barrier & 2) ? 0u : ops[o].nblocks; if (o + 1 < n && b >= nb) { b -= nb; ++o; } else break; }
   { const ExecOp* op = ops + o; const int kid = op->kid;
-    EXEC_SWITCH(exec_dispatch_g) }
+    EXEC_SWITCH }
   while (o + 1 < n && (ops[o + 1].barrier & 2)) { __threadfence(); __syncthreads(); ++o; b = 0;
     const ExecOp* op = ops + o; const int kid = op->kid;
-    EXEC_SWITCH_TAIL(exec_dispatch_g) }
+    EXEC_SWITCH_TAIL }
 }
 // The same phase with its op records INSIDE the kernel arguments (<= 8 ops, <= 3.8 KB of packed arguments: every phase of the DQN / SAC epochs). With the records in
 // global memory a workgroup walks block counts -> body id -> arguments -> the op's own data: three dependent scalar loads from memory the host copy has just written
@@ -102,18 +65,14 @@ __global__ __launch_bounds__(256) void k_phase(const ExecOp* __restrict__ ops, i
 template <int BYTES> struct PhaseK { int32_t n; int32_t pad; int32_t kid[PHASEK_MAXOPS]; uint32_t nblocks[PHASEK_MAXOPS]; uint32_t off[PHASEK_MAXOPS]; alignas(16) unsigned char args[BYTES]; };
 static_assert(sizeof(PhaseK<3840>) <= 4096, "HIP kernel arguments are limited to 4 KB");
 struct KOp { const unsigned char* args; unsigned nblocks; };
-template <class Op> __device__ __forceinline__ void exec_dispatch_k(const KOp* op, unsigned bid) {
-  const OpPack<Op> p = *(const OpPack<Op>*)op->args;
-  exec_apply<Op>(bid, op->nblocks, p);
-}
 // the gather's column table (456 bytes) is read where it lies in the kernel arguments instead of travelling by value (see GatherRingAllOp::run_ptr)
-template <> __device__ __forceinline__ void exec_dispatch_k<GatherRingAllOp>(const KOp* op, unsigned bid) {
+template <> __device__ __forceinline__ void exec_dispatch<GatherRingAllOp, KOp>(const KOp* op, unsigned bid) {
   using P = OpPack<GatherRingAllOp>; const P* pp = (const P*)op->args;
   GatherRingAllOp::run_ptr(bid, op->nblocks, &pp->head, pp->tail.head, pp->tail.tail.head, pp->tail.tail.tail.head, pp->tail.tail.tail.tail.head);
 }
 // the same for the fused prioritized search + gather (its arguments carry the same table: taking the address of a by-value copy put 176 bytes of every thread into scratch,
 // on the one phase of a C3 epoch that is a chain of dependent memory round trips; round 6)
-template <> __device__ __forceinline__ void exec_dispatch_k<PerSampleGatherOp>(const KOp* op, unsigned bid) {
+template <> __device__ __forceinline__ void exec_dispatch<PerSampleGatherOp, KOp>(const KOp* op, unsigned bid) {
   PerSampleGatherOp::run_ptr(bid, op->nblocks, &((const OpPack<PerSampleGatherOp>*)op->args)->head);
 }
 template <int BYTES, int EXEC_HEAVY>
@@ -128,10 +87,10 @@ __global__ __launch_bounds__(256) void k_phase_k(PhaseK<BYTES> by_value) {
   // op whose only consumer is another one-block op (target -> loss head) shares its launch instead of paying a kernel boundary (~5 us) for a 128-float hand-over.
   // Same compute unit, write-through L1: the fence + workgroup barrier make the first op's global stores visible to the second.
   { const int kid = pk->kid[o]; const KOp kop{pk->args + pk->off[o], pk->nblocks[o]}; const KOp* op = &kop;
-    EXEC_SWITCH(exec_dispatch_k) }
+    EXEC_SWITCH }
   while (o + 1 < n && (pk->kid[o + 1] & PHASEK_SEQ)) { __threadfence(); __syncthreads(); ++o; b = 0;
     const int kid = pk->kid[o] & (PHASEK_SEQ - 1); const KOp kop{pk->args + pk->off[o], 1u}; const KOp* op = &kop;
-    EXEC_SWITCH_TAIL(exec_dispatch_k) }
+    EXEC_SWITCH_TAIL }
 }
 // host: pack ops [i0, i1] of a recording into a PhaseK<BYTES>; false when they do not fit
 template <int BYTES> static bool phasek_launch(const std::vector<ExecOp>& ops, size_t i0, size_t i1, unsigned blocks, hipStream_t st) {
@@ -203,7 +162,7 @@ int32_t crux_exec_zero(crux_ctx* c, void* d_ptr, size_t bytes, hipStream_t st) {
   if (!crux_exec_recording(c)) { HIPCHK(c, hipMemsetAsync(d_ptr, 0, bytes, st)); return CRUX_OK; }
   if (bytes % 4) return crux_fail(c, CRUX_EINVAL, "executor: zero-fill of %zu bytes", bytes);
   const int64_t n = (int64_t)(bytes / 4);
-  crux_exec_push<FillOp, OP_FILL>(c, (unsigned)((n + 255) / 256), (float*)d_ptr, 0.f, n);
+  crux_exec_push<FillOp>(c, (unsigned)((n + 255) / 256), (float*)d_ptr, 0.f, n);
   return CRUX_OK;
 }
 // Phases: ops that do not depend on each other share a barrier. The caller assigns every recorded op a phase number (non-decreasing along every
@@ -218,8 +177,8 @@ static int32_t exec_schedule(crux_ctx* c, const std::vector<int>& phase) {
   std::vector<ExecOp> out(n);
   for (size_t k = 0; k < n; ++k) { out[k] = r->ops[idx[k]]; out[k].barrier = (k + 1 == n || (phase[idx[k + 1]] >> 2) != (phase[idx[k]] >> 2)) ? 1 : 0;
     if ((phase[idx[k]] & 3) == 2) {
-      // the in-block tail switch (EXEC_SWITCH_TAIL) knows these bodies only: anything else would be skipped silently
-      if (out[k].kid != OP_TD_HEAD && out[k].kid != OP_Q_HEAD && out[k].kid != OP_PER_UPDATE) return crux_fail(c, CRUX_EHIP, "executor: op %d cannot run as a sequential tail", out[k].kid);
+      // the in-block tail switch (EXEC_SWITCH_TAIL) knows the table's tail ops only: anything else would be skipped silently
+      if (!exec_op_tail(out[k].kid)) return crux_fail(c, CRUX_EHIP, "executor: op %d cannot run as a sequential tail", out[k].kid);
       if (k == 0 || (phase[idx[k - 1]] >> 2) != (phase[idx[k]] >> 2) || out[k].nblocks != 1 || out[k - 1].nblocks != 1) return crux_fail(c, CRUX_EHIP, "executor: a sequential op without a one-block predecessor in its phase");
       out[k].barrier |= 2; } }
   r->ops.swap(out); return CRUX_OK;
@@ -368,7 +327,7 @@ static int32_t run_epoch_chains(crux_ctx* c, const char* who, bool chain, crux_b
         return fail(crux_fail(c, CRUX_EHIP, "%s epochs (async): unexpected recording", who));
       if (er.shift >= 0) { const int t = last_phase() + er.shift; size_t q = rb0;
         for (int k = 0; k < nrows; ++k) { if (!(er.has >> k & 1)) continue;
-          crux_exec_push<CopyF32Op, OP_COPY_F32>(c, 1u, d_rows + ((size_t)e * nrows + k) * CRUX_INFO_N, (const float*)r->readbacks[q++].d_info, (int64_t)CRUX_INFO_N);
+          crux_exec_push<CopyF32Op>(c, 1u, d_rows + ((size_t)e * nrows + k) * CRUX_INFO_N, (const float*)r->readbacks[q++].d_info, (int64_t)CRUX_INFO_N);
           r->chain_tags.push_back(t); } } }
     ++in_chain;
   }
@@ -410,7 +369,6 @@ static int32_t grow_epoch_tmp(crux_ctx* c, size_t bytes, int64_t B, const char* 
 // softq_target(alpha) (rl/softq.jl:4-13). Lives in this translation unit so that the stand-alone kernel and the executor's phase kernel are compiled under the same
 // floating-point contraction setting (exp / log are inlined library code: the two forms must agree bit for bit).
 int32_t crux_mlp_forward_impl(crux_mlp* net, const float* d_x, int64_t B, float* d_y, const float* params_override);
-__global__ void k_softq_target(const float* __restrict__ q, int nout, const float* __restrict__ r, const uint8_t* __restrict__ done, float gamma, float alpha, int64_t n, float* __restrict__ y) { SoftqTargetOp::run(blockIdx.x, gridDim.x, q, nout, r, done, gamma, alpha, n, y); }
 extern "C" int32_t crux_softq_target(crux_mlp* tn, crux_buffer* batch, float gamma, float alpha, float* d_y) { CRUX_PLAIN_ONLY("crux_softq_target", tn);
   if (!tn || !batch || !d_y) return CRUX_EINVAL;
   crux_ctx* c = tn->ctx; const int64_t n = batch->elements; if (n == 0) return CRUX_OK;
@@ -420,7 +378,7 @@ extern "C" int32_t crux_softq_target(crux_mlp* tn, crux_buffer* batch, float gam
   int32_t rc;
   if (tn->nd.maxdim >= CRUX_DENSE_MIN_WIDTH) { rc = crux_dense_forward(tn, (const float*)batch->col[CRUX_COL_SP], n, c->stream); if (rc) return rc; q = crux_dense_act(tn, tn->nd.L); }
   else { rc = crux_mlp_forward_impl(tn, (const float*)batch->col[CRUX_COL_SP], n, q, nullptr); if (rc) return rc; }
-  CRUX_RUN(c, SoftqTargetOp, OP_SOFTQ_TARGET, k_softq_target, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const float*)batch->col[CRUX_COL_R], (const uint8_t*)batch->col[CRUX_COL_DONE], gamma, alpha, n, d_y);
+  CRUX_RUN(c, SoftqTargetOp, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const float*)batch->col[CRUX_COL_R], (const uint8_t*)batch->col[CRUX_COL_DONE], gamma, alpha, n, d_y);
   return crux_launch_check(c, "k_softq_target");
 }
 
@@ -482,7 +440,7 @@ static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* sourc
     a.w = use_weight ? (const float*)batch->col[CRUX_COL_WEIGHT] : nullptr; a.gamma = gamma; a.softq_alpha = softq_alpha; a.nout = nout; a.K = K; a.B = (int32_t)B;
     a.y = d_y; a.dy = dy; a.err = per ? d_err : nullptr; a.term = term; a.qsel = qsel;
     a.per = per ? 1 : 0; a.pr = source->priorities; a.pminmax = source->pminmax; a.ids = batch->d_indices; a.per_alpha = source->alpha;
-    crux_exec_push<DqnTdTileOp, OP_DQN_TD_TILE>(c, (unsigned)((B + 15) / 16), a); }
+    crux_exec_push<DqnTdTileOp>(c, (unsigned)((B + 15) / 16), a); }
   tg.only(3);
   Sumsq2Fix fx{};
   rc = crux_dense_backward(net, S, B, dy, 1.0f, true, nullptr, c->stream, &fx, 0, nanf); if (rc) return bail(rc);
@@ -490,10 +448,10 @@ static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* sourc
   if (per) { rc = crux_per_touched(source, batch->d_indices, B, false, (unsigned*)(nanf + 2)); if (rc) return bail(rc);      // leaves + root paths as one op beside the pullback (LeafTouchOp)
     tg.tag([](int kid, int&) { return (kid == OP_LEAF_TOUCH || kid == OP_LEAF_REFRESH) ? 4 : kid == OP_TREE_TOUCH ? 5 : -1; }); }
   // 5: the norm (for the info row) and, beside it, Adam gated on the producers' NaN flags (AdamSelfOp, sac.hip) | 6: info, beta-power advance
-  CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, net->g, (int64_t)net->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
+  CRUX_RUN(c, Sumsq2Op, SUMSQ_BLOCKS, 256, c->stream, net->g, (int64_t)net->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   rc = adam_self(net, nanf, status, fx, 0); if (rc) return bail(rc);
   tg.tag([](int kid, int&) { return kid == OP_ADAM_ADVANCE_SELF ? 6 : 5; });
-  crux_exec_push<TdInfo2Op, OP_TD_INFO2>(c, 1u, (const float*)term, (const float*)qsel, (const double*)ssq, B, info_dst);
+  crux_exec_push<TdInfo2Op>(c, 1u, (const float*)term, (const float*)qsel, (const double*)ssq, B, info_dst);
   tg.only(6);
   crux_exec_add_readback(c, info_out, dinfo, status, "td_loss");
   return tg.finish(7);
@@ -589,7 +547,7 @@ static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer*
     return rc;
   };
   // polyak_average!(pi_minus, pi, tau) after the epoch loop (off_policy.jl:108: the DQN family updates its target once per value_training call) as an op of the chain: it needs
-  // the last epoch's Adam (phase 5) and shares the launch of that epoch's info / beta-power phase -- the stand-alone k_polyak launch (~5 us of a 230 us C3 iteration) is gone.
+  // the last epoch's Adam (phase 5) and shares the launch of that epoch's info / beta-power phase -- the stand-alone PolyakOp launch (~5 us of a 230 us C3 iteration) is gone.
   return run_epoch_chains(c, "dqn", fuse, source->prioritized ? source : nullptr, n_epochs, 1, d_infos_async, record, [&](int) { return EpochRows{1u, tiles ? -1 : 0}; },
                           [&]() { return polyak_tau >= 0.f ? crux_polyak(target_net, net, polyak_tau) : CRUX_OK; });
 }
@@ -691,11 +649,11 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   tg.only(1);
   // 2
   rc = crux_dense_forward12(actor, SP, B, c->stream); if (rc) return bail(rc);
-  CRUX_RUN(c, ConcatSaOp, OP_CONCAT_SA, k_concat_sa, nblk(B * sd), 256, c->stream, S, (const float*)batch->col[CRUX_COL_A], od, ad, B, sa_c);
+  CRUX_RUN(c, ConcatSaOp, nblk(B * sd), 256, c->stream, S, (const float*)batch->col[CRUX_COL_A], od, ad, B, sa_c);
   tg.only(2);
   // 3
   { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = SP; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed; a.cfg[0] = ExploreCfg{noise_counter0, sa_t, lp_t, nullptr};
-    crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a); }
+    crux_exec_push<ActorExploreTileOp>(c, nt, a); }
   rc = crux_dense_forward12(q1, sa_c, B, c->stream); if (!rc) rc = crux_dense_forward12(q2, sa_c, B, c->stream); if (rc) return bail(rc);
   tg.only(3);
   // 4
@@ -704,27 +662,27 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   // 5
   { SacCriticArgs a{}; a.q1t = l3(q1t, true); a.q2t = l3(q2t, true); a.q1 = l3(q1, true); a.q2 = l3(q2, true); a.r = (const float*)batch->col[CRUX_COL_R]; a.done = (const uint8_t*)batch->col[CRUX_COL_DONE];
     a.lp = lp_t; a.log_alpha = la->p; a.w = w; a.gamma = gamma; a.scale = 0.5f; a.K = K; a.B = (int32_t)B; a.y = y; a.dy1 = dy1; a.dy2 = dy2; a.term1 = t1; a.term2 = t2;
-    crux_exec_push<SacCriticTileOp, OP_SAC_CRITIC_TILE>(c, nt, a); }
+    crux_exec_push<SacCriticTileOp>(c, nt, a); }
   { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = S; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed;      // the two draws side by side (each re-evaluates the output layer: 8 MFMAs)
-    a.cfg[0] = ExploreCfg{noise_counter0 + 1, nullptr, lp_temp, nullptr}; crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a);
-    a.cfg[0] = ExploreCfg{noise_counter0 + 2, sa_a, lp_a, eps}; crux_exec_push<ActorExploreTileOp, OP_ACTOR_EXPLORE_TILE>(c, nt, a); }
+    a.cfg[0] = ExploreCfg{noise_counter0 + 1, nullptr, lp_temp, nullptr}; crux_exec_push<ActorExploreTileOp>(c, nt, a);
+    a.cfg[0] = ExploreCfg{noise_counter0 + 2, sa_a, lp_a, eps}; crux_exec_push<ActorExploreTileOp>(c, nt, a); }
   tg.only(5);
   // 6
   Sumsq2Fix fxc{}, fxa{};
   rc = crux_dense_backward(q1, sa_c, B, dy1, 1.0f, true, nullptr, c->stream, &fxc, 0, nfc); if (!rc) rc = crux_dense_backward(q2, sa_c, B, dy2, 1.0f, true, nullptr, c->stream, &fxc, 1, nfc); if (rc) return bail(rc);
-  CRUX_RUN(c, TempHeadOp, OP_TEMP_HEAD, k_temp_head, 1, 256, c->stream, (const float*)lp_temp, B, H_target, (const float*)la->p, la->g, it, ssq_t);
+  CRUX_RUN(c, TempHeadOp, 1, 256, c->stream, (const float*)lp_temp, B, H_target, (const float*)la->p, la->g, it, ssq_t);
   tg.only(6);
   // 7: the critics' norm (for the info row) and, beside it, their Adam steps gated on the pullback's NaN flags (AdamSelfOp, sac.hip); log alpha's step (+ 8: the advances)
-  CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, q1->g, (int64_t)q1->nd.n_params, q2->g, (int64_t)q2->nd.n_params, ssq_c, fxc);
+  CRUX_RUN(c, Sumsq2Op, SUMSQ_BLOCKS, 256, c->stream, q1->g, (int64_t)q1->nd.n_params, q2->g, (int64_t)q2->nd.n_params, ssq_c, fxc);
   rc = adam_self(q1, nfc, stc, fxc, 0); if (!rc) rc = adam_self(q2, nfc, stc, fxc, 1); if (!rc) rc = adam_gated(la, ssq_t, stt, false); if (rc) return bail(rc);
   tg.tag([](int kid, int&) { return (kid == OP_ADAM_ADVANCE || kid == OP_ADAM_ADVANCE_SELF) ? 8 : 7; });
   // 8: critic info | the updated critics' first two layers on (s, a ~ pi)
-  crux_exec_push<CriticInfo2Op, OP_CRITIC_INFO2>(c, 1u, (const float*)t1, (const float*)crux_dense_act(q1, 3), (const float*)t2, (const float*)crux_dense_act(q2, 3), (const double*)ssq_c, B, ic);
+  crux_exec_push<CriticInfo2Op>(c, 1u, (const float*)t1, (const float*)crux_dense_act(q1, 3), (const float*)t2, (const float*)crux_dense_act(q2, 3), (const double*)ssq_c, B, ic);
   rc = crux_dense_forward12(q1, sa_a, B, c->stream); if (!rc) rc = crux_dense_forward12(q2, sa_a, B, c->stream); if (rc) return bail(rc);
   tg.only(8);
   // 9
   { SacActorArgs a{}; a.q1 = l3(q1, true); a.q2 = l3(q2, true); a.lp = lp_a; a.log_alpha = la->p; a.K = K; a.B = (int32_t)B; a.dy1 = da1; a.dy2 = da2; a.term = ta;
-    crux_exec_push<SacActorTileOp, OP_SAC_ACTOR_TILE>(c, nt, a); }
+    crux_exec_push<SacActorTileOp>(c, nt, a); }
   tg.only(9);
   // 10
   const float* dz1a = nullptr; const float* dz1b = nullptr;
@@ -733,18 +691,18 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   // 11
   { CriticDxArgs a{}; a.c1 = TileSet{q1->p + q1->nd.woff[0], nullptr, dz1a, nullptr}; a.c2 = TileSet{q2->p + q2->nd.woff[0], nullptr, dz1b, nullptr};
     a.sa = sa_a; a.mu = crux_dense_act(actor, 3); a.eps = eps; a.ls = ls; a.log_alpha = la->p; a.od = od; a.ad = ad; a.K = q1->nd.dims[1]; a.B = (int32_t)B; a.dmu = dmu; a.dls = dls;
-    crux_exec_push<CriticDxActorGradTileOp, OP_CRITIC_DX_TILE>(c, nt, a); }
+    crux_exec_push<CriticDxActorGradTileOp>(c, nt, a); }
   tg.only(11);
   // 12
   rc = crux_dense_backward(actor, S, B, dmu, 1.0f, true, nullptr, c->stream, &fxa, 0, nfa); if (rc) return bail(rc);
-  CRUX_RUN(c, RowsumOp, OP_ROWSUM, k_rowsum, ad, 256, c->stream, (const float*)dls, ad, B, actor->g + actor->nd.xoff, nfa);
+  CRUX_RUN(c, RowsumOp, ad, 256, c->stream, (const float*)dls, ad, B, actor->g + actor->nd.xoff, nfa);
   tg.only(12);
   // 13: the actor's norm | its Adam step (self-gated)
-  CRUX_RUN(c, Sumsq2Op, OP_SUMSQ2, k_sumsq2, SUMSQ_BLOCKS, 256, c->stream, actor->g, (int64_t)actor->nd.n_params, (float*)nullptr, (int64_t)0, ssq_a, fxa);
+  CRUX_RUN(c, Sumsq2Op, SUMSQ_BLOCKS, 256, c->stream, actor->g, (int64_t)actor->nd.n_params, (float*)nullptr, (int64_t)0, ssq_a, fxa);
   rc = adam_self(actor, nfa, sta, fxa, 0); if (rc) return bail(rc);
   tg.tag([](int kid, int&) { return kid == OP_ADAM_ADVANCE_SELF ? 14 : 13; });
   // 14: actor info, polyak
-  crux_exec_push<ActorInfo2Op, OP_ACTOR_INFO2>(c, 1u, (const float*)ta, (const float*)lp_a, (const double*)ssq_a, B, ia);
+  crux_exec_push<ActorInfo2Op>(c, 1u, (const float*)ta, (const float*)lp_a, (const double*)ssq_a, B, ia);
   if (actor_targ) { rc = crux_polyak(actor_targ, actor, tau); if (rc) return bail(rc); }
   rc = crux_polyak(q1t, q1, tau); if (!rc) rc = crux_polyak(q2t, q2, tau); if (rc) return bail(rc);
   tg.only(14);
@@ -976,7 +934,7 @@ extern "C" int32_t crux_debug_exec_forward(crux_mlp* net, const float* d_x, int6
 extern "C" int32_t crux_debug_exec_nops(crux_ctx* c, int32_t n, int32_t blocks) {
   int32_t rc = crux_exec_begin(c); if (rc) return rc;
   float* p = (float*)crux_exec_small(c, 4 * 256 * (size_t)(blocks > 0 ? blocks : 1));
-  for (int k = 0; k < n; ++k) crux_exec_push<FillOp, OP_FILL>(c, (unsigned)(blocks > 0 ? blocks : 1), p, (float)k, (int64_t)256 * (blocks > 0 ? blocks : 1));
+  for (int k = 0; k < n; ++k) crux_exec_push<FillOp>(c, (unsigned)(blocks > 0 ? blocks : 1), p, (float)k, (int64_t)256 * (blocks > 0 ? blocks : 1));
   return crux_exec_run(c);
 }
 // test hook: the forward pass of `net` recorded `reps` times (dependent ops): per-op cost of the tile GEMM inside the executor

@@ -171,7 +171,7 @@ static int32_t og_enqueue_step(crux_mlp* D, const crux_buffer* f, int K, int64_t
   rc = crux_launch_check(c, "k_offgail_ce_head"); if (rc) return rc;
   Sumsq2Fix fx{};
   rc = crux_dense_backward(D, ob.X, NC, ob.dz, 1.0f, true, nullptr, c->stream, &fx, 0); if (rc) return rc;
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   hipLaunchKernelGGL(k_offgail_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, NC, dinfo);
   rc = crux_launch_check(c, "k_offgail_info"); if (rc) return rc;
   return adam_gated(D, ssq, ob.hd.status);

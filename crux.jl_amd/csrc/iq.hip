@@ -173,7 +173,7 @@ static int32_t iq_wgrad(crux_ctx* c, const float* dZ, const float* X, int out, i
 static int32_t iq_dgrad(crux_mlp* n, int64_t nl, int64_t H, const IqBufs& ib) {
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd; const int64_t NC = 2 * nl + H; const int L = nd.L;
   const int64_t cnt = (int64_t)nd.dims[L] * NC;
-  hipLaunchKernelGGL(k_act_grad, dim3(nblk(cnt)), dim3(256), 0, c->stream, (const float*)ib.dy, (const float*)crux_dense_act(n, L), nd.acts[L - 1], cnt, ib.Z[L]);
+  crux_launch<ActGradOp>(nblk(cnt), 256, c->stream, (const float*)ib.dy, (const float*)crux_dense_act(n, L), nd.acts[L - 1], cnt, ib.Z[L]);
   int32_t rc = crux_launch_check(c, "k_act_grad"); if (rc) return rc;
   for (int l = L; l >= 1; --l) {
     const int in = nd.dims[l - 1], out = nd.dims[l];
@@ -184,7 +184,7 @@ static int32_t iq_dgrad(crux_mlp* n, int64_t nl, int64_t H, const IqBufs& ib) {
     }
     rc = iq_gemm(c, n->p + nd.woff[l - 1], out, 1, ib.Z[l], 1, out, in, (int)NC, out, ib.G[l - 1], in); if (rc) return rc;
     const int64_t m = (int64_t)in * NC;
-    hipLaunchKernelGGL(k_act_grad, dim3(nblk(m)), dim3(256), 0, c->stream, (const float*)ib.G[l - 1], (const float*)crux_dense_act(n, l - 1), nd.acts[l - 2], m, ib.Z[l - 1]);
+    crux_launch<ActGradOp>(nblk(m), 256, c->stream, (const float*)ib.G[l - 1], (const float*)crux_dense_act(n, l - 1), nd.acts[l - 2], m, ib.Z[l - 1]);
     rc = crux_launch_check(c, "k_act_grad"); if (rc) return rc;
   }
   return CRUX_OK;
@@ -243,7 +243,7 @@ int32_t crux_gradient_penalty(crux_mlp* net, const float* d_x, const float* d_xt
   rc = crux_launch_check(c, "k_iq_expand"); if (rc) return rc;
   rc = crux_dense_forward(net, ib.X, B, c->stream); if (rc) return rc;
   const int64_t ny = (int64_t)nd.dims[nd.L] * B;
-  hipLaunchKernelGGL(k_fill, dim3(nblk(ny)), dim3(256), 0, c->stream, ib.dy, 1.0f, ny);
+  crux_launch<FillOp>(nblk(ny), 256, c->stream, ib.dy, 1.0f, ny);
   rc = iq_dgrad(net, 0, B, ib); if (rc) return rc;
   hipLaunchKernelGGL(k_iq_gp_head, dim3(1), dim3(256), 0, c->stream, (const float*)ib.G[0], nd.dims[0], B, target, lambda, (const int32_t*)ib.nanflag,
                      accumulate ? ib.gb[0] : nullptr, ib.stats);
@@ -278,7 +278,7 @@ int32_t crux_iq_step(crux_mlp* q, crux_buffer* b, int64_t n_policy, float gamma_
   hipLaunchKernelGGL(k_iq_expand, dim3(nblk(NC)), dim3(256), 0, c->stream, S, (const float*)b->col[CRUX_COL_SP], B, S + Bp * od, S, H, od, seed, counter, ib.X, ib.nanflag);
   rc = crux_launch_check(c, "k_iq_expand"); if (rc) return rc;
   rc = crux_dense_forward(q, ib.X, NC, c->stream); if (rc) return rc;
-  if (H) { const int64_t ny = (int64_t)A * H; hipLaunchKernelGGL(k_fill, dim3(nblk(ny)), dim3(256), 0, c->stream, ib.dy + 2 * B * A, 1.0f, ny); }
+  if (H) { const int64_t ny = (int64_t)A * H; crux_launch<FillOp>(nblk(ny), 256, c->stream, ib.dy + 2 * B * A, 1.0f, ny); }
   hipLaunchKernelGGL(k_iq_head, dim3(1), dim3(256), 0, c->stream, (const float*)crux_dense_act(q, nd.L), (const uint8_t*)b->col[CRUX_COL_A], (const uint8_t*)b->col[CRUX_COL_DONE],
                      A, B, Bp, gamma_iq, reg, alpha_reg, (const int32_t*)ib.nanflag, ib.dy, ib.stats);
   rc = crux_launch_check(c, "k_iq_head"); if (rc) return rc;
@@ -293,7 +293,7 @@ int32_t crux_iq_step(crux_mlp* q, crux_buffer* b, int64_t n_policy, float gamma_
     rc = iq_penalty_sweeps(q, B, H, ib); if (rc) return rc;
     rc = iq_add_penalty(q, ib); if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_sumsq2, dim3(SUMSQ_BLOCKS), dim3(256), 0, c->stream, q->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, q->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
   hipLaunchKernelGGL(k_iq_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, Bp, H, gp, lambda_gp, reg, alpha_reg, ib.dinfo, ib.extra);
   rc = crux_launch_check(c, "k_iq_info"); if (rc) return rc;
   rc = adam_gated(q, ib.ssq, ib.status); if (rc) return rc;

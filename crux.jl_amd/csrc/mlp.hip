@@ -137,8 +137,6 @@ __global__ void k_glorot(NetDesc nd, float* p, uint64_t seed, uint32_t stream, f
   }
 }
 
-__global__ void k_polyak(float* __restrict__ to, const float* __restrict__ from, float tau, int64_t n) { PolyakOp::run(blockIdx.x, gridDim.x, to, from, tau, n); }
-
 // Flux.Optimise.Adam apply! with Float64 scalar fields: each broadcast evaluated in Float64 per element,
 // rounded to Float32 on store.
 __global__ void k_adam_apply(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -166,7 +164,7 @@ int32_t crux_mlp_create(crux_ctx* ctx, int32_t L, const int32_t* dims, const int
   fill_desc(n->nd, L, L > 0 ? dims : dim0, acts, n_extra);
   const size_t bytes = sizeof(float) * (size_t)n->nd.n_params;
   if (hipMalloc(&n->p, bytes) != hipSuccess || hipMalloc(&n->g, bytes) != hipSuccess || hipMalloc(&n->m, bytes) != hipSuccess ||
-      hipMalloc(&n->v, bytes) != hipSuccess || hipMalloc(&n->bp, 4 * sizeof(double)) != hipSuccess)   /* [beta1^t, beta2^t, ticket of k_adam_gated, pad] */ { delete n; return crux_fail(ctx, CRUX_ENOMEM, "mlp: hipMalloc failed"); }
+      hipMalloc(&n->v, bytes) != hipSuccess || hipMalloc(&n->bp, 4 * sizeof(double)) != hipSuccess)   /* [beta1^t, beta2^t, ticket of AdamGatedOp, pad] */ { delete n; return crux_fail(ctx, CRUX_ENOMEM, "mlp: hipMalloc failed"); }
   HIPCHK(ctx, hipMemsetAsync(n->p, 0, bytes, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(n->g, 0, bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(n->m, 0, bytes, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(n->v, 0, bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(n->bp, 0, 4 * sizeof(double), ctx->stream));
@@ -245,7 +243,7 @@ int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau) {
   // inside a recorded chain the three polyak updates of an epoch share a phase with other ops: 64 grid-striding blocks each instead of n / 256 (a phase of > 768 blocks takes
   // two rounds over the chip)
   const unsigned nbk = (unsigned)((n + 255) / 256);
-  CRUX_RUN(to->ctx, PolyakOp, OP_POLYAK, k_polyak, crux_exec_recording(to->ctx) ? (nbk < 64u ? nbk : 64u) : nbk, 256, to->ctx->stream, to->p, from->p, tau, n);
+  CRUX_RUN(to->ctx, PolyakOp, crux_exec_recording(to->ctx) ? (nbk < 64u ? nbk : 64u) : nbk, 256, to->ctx->stream, to->p, from->p, tau, n);
   return crux_launch_check(to->ctx, "k_polyak");
 }
 

@@ -8,13 +8,13 @@
 //   k_leaf_totals   one thread per leaf: sequential Float32 sum of the leaf            (streams N floats)
 //   k_tree          one block: child totals bottom-up, then prefixes top-down          (2 x leaves nodes)
 //   k_leaf_scan     one thread per leaf: c[i] = prefix + running leaf sum              (streams N floats in, N out)
-// followed by k_per_search (Float64 key against the Float32 cumsum, :335-340), the IS weights (:343-347) and the row gather.
+// followed by PerSearchOp (Float64 key against the Float32 cumsum, :335-340), the IS weights (:343-347) and the row gather.
 // The tree shape depends only on N and is built on the host once per buffer length.
 //
 // Incremental form (the reference rescans all N priorities per gradient step, :329-332; its abandoned sum-tree is at :48,:334-336): the cumsum is
 // never materialised. `cumsum[i]` holds the running sum INSIDE i's leaf and c[i] = prefix(leaf(i)) + cumsum[i] is formed when the search probes
 // it -- the same Float32 additions in the same order as accumulate_pairwise! performs (c[i] = op(s, s_)). update_priorities! re-sums only the
-// leaves it touched (k_leaf_refresh: <= 127 elements each) and the node totals on their root paths (k_tree_touch); prefix(leaf) = v[1] + the totals of the
+// leaves it touched (LeafRefreshOp: <= 127 elements each) and the node totals on their root paths (TreeTouchOp); prefix(leaf) = v[1] + the totals of the
 // left siblings passed on the way down, added top-down, is formed per probe from those totals. searchsortedfirst probes exactly the elements the reference's
 // binary search would. Per sampled step at N = 1 M: <= 128 x 127 x 8 B of leaf traffic + a few KB of node totals and probes instead of 8 MB.
 #include "common.h"
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(1024) void k_tree_lds(const int32_t* __restrict__ l
     for (int i = 0; i < NPT; ++i) { const int k = t + 1024 * i; if (k >= lo && k < hi && lft[i] >= 0) { const float s = pre[k]; pre[lft[i]] = s; pre[rgt[i]] = s + tot[lft[i]]; } }
     __syncthreads();
   }
-  for (int k = t; k < nn; k += 1024) { prefix[k] = pre[k]; total[k] = tot[k]; }     // internal totals stay resident: k_tree_touch updates them along touched paths
+  for (int k = t; k < nn; k += 1024) { prefix[k] = pre[k]; total[k] = tot[k]; }     // internal totals stay resident: TreeTouchOp updates them along touched paths
 }
 __global__ __launch_bounds__(LEAF_BLK) void k_leaf_scan(const float* __restrict__ v, const int32_t* __restrict__ lstart, const int32_t* __restrict__ llen,
                                                         const int32_t* __restrict__ lnode, int nl, const float* __restrict__ prefix, float* __restrict__ c) {
@@ -148,11 +148,10 @@ __global__ __launch_bounds__(LEAF_BLK) void k_leaf_scan(const float* __restrict_
   for (int i = t; i < cnt; i += LEAF_BLK) c[base + i] = sm[i];
   if (blockIdx.x == 0 && t == 0) c[0] = v[0];
 }
-__global__ __launch_bounds__(256) void k_leaf_refresh(const float* __restrict__ v, const int64_t* __restrict__ ids, int64_t n, int64_t N, int nlev, float* __restrict__ run, float* __restrict__ total) { LeafRefreshOp::run(blockIdx.x, gridDim.x, v, ids, n, N, nlev, run, total); }
 // LeafRefreshOp and TreeTouchOp in ONE launch (the chained C3 epochs, exec.hip dqn_epoch_tiles): every workgroup re-sums its leaves, publishes them (device-scope release) and takes
 // a ticket; the workgroup that draws the last ticket -- all leaves are then visible to it -- walks the root paths. The root paths so leave the launch of the pullback they sit
 // beside, and the next epoch's search can follow one launch earlier. `ticket` is a zeroed word; n <= 256 touched elements.
-struct LeafTouchOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ v, const int64_t* __restrict__ ids, int64_t n, int64_t N, int nlev,
+struct LeafTouchOp { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ v, const int64_t* __restrict__ ids, int64_t n, int64_t N, int nlev,
                                                     float* __restrict__ run, float* __restrict__ total, unsigned* __restrict__ ticket) {
   __shared__ int last_;
   LeafRefreshOp::run(bid_, nb_, v, ids, n, N, nlev, run, total);
@@ -163,8 +162,6 @@ struct LeafTouchOp { static __device__ __forceinline__ void run(const unsigned b
   __threadfence();
   TreeTouchOp::run(0u, 1u, ids, n, N, nlev, total);
 } };
-__global__ __launch_bounds__(256) void k_leaf_touch(const float* __restrict__ v, const int64_t* __restrict__ ids, int64_t n, int64_t N, int nlev, float* __restrict__ run, float* __restrict__ total, unsigned* __restrict__ ticket) { LeafTouchOp::run(blockIdx.x, gridDim.x, v, ids, n, N, nlev, run, total, ticket); }
-__global__ __launch_bounds__(1024) void k_tree_touch(const int64_t* __restrict__ ids, int64_t n, int64_t N, int nlev, float* __restrict__ total) { TreeTouchOp::run(blockIdx.x, gridDim.x, ids, n, N, nlev, total); }
 __global__ __launch_bounds__(1024) void k_push_touch(int64_t* __restrict__ ids, int64_t n, int64_t base, int64_t C, float* pr, float* pminmax, float alpha, int64_t N, int nlev,
                                                      float* run, float* total, int touch) { push_touch_block(ids, n, base, C, pr, pminmax, alpha, N, nlev, run, total, touch); }
 // host side of push_touch_block. crux_per_push_plan: is this push of that shape, and is the tree in its incremental state (the conditions of crux_per_touched(from_push = true),
@@ -284,22 +281,19 @@ __device__ __forceinline__ int per_search_wave(const int64_t j, const float* __r
   *w_out = ptot;      // (the total the stratum width came from: the caller forms the importance weight, per_weight_lane0 below)
   return lo;
 }
-struct PerSearchOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ run, const float* __restrict__ total, const float* __restrict__ pr, const float* __restrict__ pminmax, int64_t N, int64_t B, int nlev,
+struct PerSearchOp { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ run, const float* __restrict__ total, const float* __restrict__ pr, const float* __restrict__ pminmax, int64_t N, int64_t B, int nlev,
                              const double* __restrict__ rands, uint64_t seed, uint32_t stream, uint64_t ictr, float beta, int64_t* __restrict__ ids, float* __restrict__ weight) {
   const int64_t j = (int64_t)bid_ * 4 + (threadIdx.x >> 6);
   if (j >= B) return;
   float ptot; const int lo = per_search_wave(j, run, total, pr, pminmax, N, B, nlev, rands, seed, stream, ictr, beta, ids, weight, &ptot);
   if ((threadIdx.x & 63) == 0) (void)per_weight_lane0(j, lo, ptot, pr, pminmax, N, beta, ids, weight);
 } };
-__global__ __launch_bounds__(256) void k_per_search(const float* __restrict__ run, const float* __restrict__ total, const float* __restrict__ pr, const float* __restrict__ pminmax, int64_t N, int64_t B, int nlev,
-                             const double* __restrict__ rands, uint64_t seed, uint32_t stream, uint64_t ictr, float beta, int64_t* __restrict__ ids, float* __restrict__ weight) { PerSearchOp::run(blockIdx.x, gridDim.x, run, total, pr, pminmax, N, B, nlev, rands, seed, stream, ictr, beta, ids, weight); }
 struct UniformIdsOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, int64_t N, int64_t B, uint64_t seed, uint32_t stream, uint64_t ictr, int64_t* ids) {
   const int64_t j = (int64_t)bid_ * blockDim.x + threadIdx.x;
   if (j >= B) return;
   const crux_u32x4 x = crux_philox(seed, ictr * (uint64_t)B + (uint64_t)j, stream, CRUX_RNG_SAMPLE);
   ids[j] = (int64_t)(((uint64_t)x.v[0] * (uint64_t)N) >> 32);
 } };
-__global__ void k_uniform_ids(int64_t N, int64_t B, uint64_t seed, uint32_t stream, uint64_t ictr, int64_t* ids) { UniformIdsOp::run(blockIdx.x, gridDim.x, N, B, seed, stream, ictr, ids); }
 // gather rows src[ids[j]] into the ring of dst at (base + j) % C
 template <typename T>
 __global__ void k_gather_ring(T* __restrict__ dst, const T* __restrict__ src, const int64_t* __restrict__ ids, int64_t n, int32_t row_elems, int64_t base, int64_t C) {
@@ -330,13 +324,13 @@ struct GatherRingAllOp {
   }
   static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, GatherCols g, const int64_t* __restrict__ ids, int64_t n, int64_t base, int64_t C) { run_ptr(bid_, nb_, &g, ids, n, base, C); }
 };
-__global__ void k_gather_ring_all(GatherCols g, const int64_t* __restrict__ ids, int64_t n, int64_t base, int64_t C) { GatherRingAllOp::run(blockIdx.x, gridDim.x, g, ids, n, base, C); }
 // prioritized_sample! of one row per WAVE, search and gather in ONE launch (round 4): the wave that found stratum j's index copies that row into the batch ring right away --
 // the sampled ids no longer cross a kernel boundary between `searchsortedfirst` and `push!(target, source, ids)` (experience_buffer.jl:340,348). The row's :weight entry is
 // the value the wave has just computed (the source column is written too, as before; the copy takes it from the register instead of reading it back).
 struct PerSampleArgs { const float* run; const float* total; const float* pr; const float* pminmax; int64_t N, B; const double* rands; uint64_t seed, ictr; int64_t* ids; float* weight; int64_t base, C;
                        int32_t nlev; uint32_t stream; float beta; int32_t pad; GatherCols g; };
 struct PerSampleGatherOp {
+  static constexpr int max_threads = 256;
   static __device__ __forceinline__ void run_ptr(const unsigned bid_, const unsigned nb_, const PerSampleArgs* a) {
     __shared__ GatherCols gs2;
     // the column table (456 bytes of the kernel arguments) is only needed by the gather: its loads are issued now, the LDS copy and the barrier come AFTER the search, so the
@@ -367,14 +361,14 @@ struct PerSampleGatherOp {
   }
   static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, PerSampleArgs a) { run_ptr(bid_, nb_, &a); }
 };
-__global__ __launch_bounds__(256) void k_per_sample_gather(PerSampleArgs a) { PerSampleGatherOp::run_ptr(blockIdx.x, gridDim.x, (const PerSampleArgs*)__builtin_amdgcn_kernarg_segment_ptr()); }      // (the table is read where it lies: no private copy)
+// its stand-alone kernel is written out (a specialisation of k_op): the table is read where it lies in the kernel arguments, no private copy
+template <> __global__ __launch_bounds__(256) void k_op<PerSampleGatherOp, 256, PerSampleArgs>(PerSampleArgs a) { PerSampleGatherOp::run_ptr(blockIdx.x, gridDim.x, (const PerSampleArgs*)__builtin_amdgcn_kernarg_segment_ptr()); }
 struct RingIdsOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, int64_t* out, int64_t n, int64_t base, int64_t C) { const int64_t j = (int64_t)bid_ * blockDim.x + threadIdx.x; if (j < n) out[j] = (base + j) % C; } };
-__global__ void k_ring_ids(int64_t* out, int64_t n, int64_t base, int64_t C) { RingIdsOp::run(blockIdx.x, gridDim.x, out, n, base, C); }
 
 // the ring rows of the next N pushed transitions, mod1.(next_ind : next_ind + N - 1, C) (experience_buffer.jl:236), written on the device: no host vector, no copy to wait for
 int32_t crux_buffer_ring_ids_device(crux_buffer* b, int64_t N, int64_t* d_out) {
   if (N <= 0) return CRUX_OK;
-  hipLaunchKernelGGL(k_ring_ids, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->ctx->stream, d_out, N, b->next_ind, b->capacity);
+  crux_launch<RingIdsOp>((unsigned)((N + 255) / 256), 256, b->ctx->stream, d_out, N, b->next_ind, b->capacity);
   return crux_launch_check(b->ctx, "k_ring_ids");
 }
 static unsigned gridn(int64_t total) { int64_t nb = (total + 255) / 256; if (nb < 1) nb = 1; if (nb > 8192) nb = 8192; return (unsigned)nb; }
@@ -415,9 +409,9 @@ int32_t crux_per_touched(crux_buffer* b, const int64_t* d_ids, int64_t n, bool f
   if (from_push && b->elements < b->capacity) { b->per_full_dirty = true; return CRUX_OK; }   // the ring is still growing: the rows may lie beyond the current tree
   if (b->per_full_dirty || b->topo_n < 2 || b->per_run_n != b->topo_n || b->topo_n != b->elements || n > 4096 || !d_ids) { b->per_full_dirty = true; return CRUX_OK; }
   if (b->topo_levels > CRUX_PER_PMAX) { b->per_full_dirty = true; return CRUX_OK; }
-  if (ticket && n <= 256 && crux_exec_recording(b->ctx)) { crux_exec_push<LeafTouchOp, OP_LEAF_TOUCH>(b->ctx, (unsigned)((n + 3) / 4), (const float*)b->priorities, d_ids, n, (int64_t)b->topo_n, (int)b->topo_levels, b->cumsum, b->topo_total, ticket); return CRUX_OK; }
-  CRUX_RUN(b->ctx, LeafRefreshOp, OP_LEAF_REFRESH, k_leaf_refresh, (unsigned)((n + 3) / 4), 256, b->ctx->stream, b->priorities, d_ids, n, b->topo_n, b->topo_levels, b->cumsum, b->topo_total);
-  CRUX_RUN(b->ctx, TreeTouchOp, OP_TREE_TOUCH, k_tree_touch, 1, 1024, b->ctx->stream, d_ids, n, b->topo_n, b->topo_levels, b->topo_total);
+  if (ticket && n <= 256 && crux_exec_recording(b->ctx)) { crux_exec_push<LeafTouchOp>(b->ctx, (unsigned)((n + 3) / 4), (const float*)b->priorities, d_ids, n, (int64_t)b->topo_n, (int)b->topo_levels, b->cumsum, b->topo_total, ticket); return CRUX_OK; }
+  CRUX_RUN(b->ctx, LeafRefreshOp, (unsigned)((n + 3) / 4), 256, b->ctx->stream, b->priorities, d_ids, n, b->topo_n, b->topo_levels, b->cumsum, b->topo_total);
+  CRUX_RUN(b->ctx, TreeTouchOp, 1, 1024, b->ctx->stream, d_ids, n, b->topo_n, b->topo_levels, b->topo_total);
   return crux_launch_check(b->ctx, "k_leaf_refresh");
 }
 
@@ -436,12 +430,12 @@ static int32_t gather_into(crux_buffer* target, crux_buffer* source, int64_t B, 
   const int64_t base = target->next_ind, C = target->capacity;
   crux_prof_begin(c, CRUX_PROF_GATHER);
   GatherCols g; gather_table(target, source, g);
-  if (g.n > 0 && !rows_done) CRUX_RUN(c, GatherRingAllOp, OP_GATHER_RING_ALL, k_gather_ring_all, gridn(B * g.pre[g.n]), 256, c->stream, g, (const int64_t*)target->d_indices, B, base, C);
+  if (g.n > 0 && !rows_done) CRUX_RUN(c, GatherRingAllOp, gridn(B * g.pre[g.n]), 256, c->stream, g, (const int64_t*)target->d_indices, B, base, C);
   crux_prof_end(c, CRUX_PROF_GATHER);
   int32_t rc = crux_launch_check(c, "k_gather_ring"); if (rc) return rc;
   if (target->prioritized) {       // buffer_like of a prioritized buffer is prioritized too (:84): push! runs update_priorities! on it
     int64_t* ring = (int64_t*)crux_scratch(c, 8 * (size_t)B + 256); if (!ring) return crux_fail(c, CRUX_ENOMEM, "sample: scratch");
-    CRUX_RUN(c, RingIdsOp, OP_RING_IDS, k_ring_ids, gridn(B), 256, c->stream, ring, B, base, C);
+    CRUX_RUN(c, RingIdsOp, gridn(B), 256, c->stream, ring, B, base, C);
     rc = crux_buffer_per_on_push(target, ring, B); if (rc) return rc;
   }
   if (fetch_indices) { target->indices_n = B; target->indices_stale = true; }   // crux_buffer_indices copies them out when (if) the host asks: no synchronisation per sample
@@ -468,12 +462,12 @@ int32_t crux_per_sample(crux_buffer* target, crux_buffer* source, int64_t B, con
     PerSampleArgs a{}; a.run = source->cumsum; a.total = source->topo_total; a.pr = source->priorities; a.pminmax = source->pminmax; a.N = N; a.B = B; a.nlev = source->topo_levels; a.rands = d_r;
     a.seed = source->sample_seed; a.stream = source->sample_stream; a.ictr = i; a.beta = beta; a.ids = target->d_indices; a.weight = (float*)source->col[CRUX_COL_WEIGHT]; a.base = target->next_ind; a.C = target->capacity;
     gather_table(target, source, a.g);
-    CRUX_RUN(c, PerSampleGatherOp, OP_PER_SAMPLE, k_per_sample_gather, (unsigned)((B + 3) / 4), 256, c->stream, a);
+    CRUX_RUN(c, PerSampleGatherOp, (unsigned)((B + 3) / 4), 256, c->stream, a);
     crux_prof_end(c, CRUX_PROF_PER_SEARCH);
     rc = crux_launch_check(c, "k_per_sample_gather"); if (rc) return rc;
     return gather_into(target, source, B, true, /*rows_done=*/true);
   }
-  CRUX_RUN(c, PerSearchOp, OP_PER_SEARCH, k_per_search, (unsigned)((B + 3) / 4), 256, c->stream, source->cumsum, source->topo_total, source->priorities, source->pminmax, N, B, source->topo_levels, (const double*)d_r, source->sample_seed, source->sample_stream, i, beta, target->d_indices, (float*)source->col[CRUX_COL_WEIGHT]);
+  CRUX_RUN(c, PerSearchOp, (unsigned)((B + 3) / 4), 256, c->stream, source->cumsum, source->topo_total, source->priorities, source->pminmax, N, B, source->topo_levels, (const double*)d_r, source->sample_seed, source->sample_stream, i, beta, target->d_indices, (float*)source->col[CRUX_COL_WEIGHT]);
   crux_prof_end(c, CRUX_PROF_PER_SEARCH);
   rc = crux_launch_check(c, "k_per_search"); if (rc) return rc;
   return gather_into(target, source, B, true);
@@ -487,7 +481,7 @@ int32_t crux_uniform_sample(crux_buffer* target, crux_buffer* source, int64_t B,
   if (target->obs_dim != source->obs_dim || target->act_dim != source->act_dim || target->act_kind != source->act_kind) return crux_fail(c, CRUX_EINVAL, "uniform_sample!: column shapes differ");
   if (ids) { for (int64_t j = 0; j < B; ++j) if (ids[j] < 0 || ids[j] >= N) return crux_fail(c, CRUX_EINVAL, "uniform_sample!: id %lld out of range", (long long)ids[j]);
     HIPCHK(c, hipMemcpyAsync(target->d_indices, ids, 8 * (size_t)B, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
-  else CRUX_RUN(c, UniformIdsOp, OP_UNIFORM_IDS, k_uniform_ids, gridn(B), 256, c->stream, N, B, source->sample_seed, source->sample_stream, i, target->d_indices);
+  else CRUX_RUN(c, UniformIdsOp, gridn(B), 256, c->stream, N, B, source->sample_seed, source->sample_stream, i, target->d_indices);
   return gather_into(target, source, B, true);
 }
 

@@ -822,9 +822,6 @@ static int32_t td_step_impl(crux_mlp* net, crux_buffer* batch, const float* d_y,
 // ---- dqn_target / td_error -----------------------------------------------------------------------------
 int32_t crux_mlp_forward_impl(crux_mlp* net, const float* d_x, int64_t B, float* d_y, const float* params_override);
 
-__global__ void k_dqn_target(const float* __restrict__ q, int nout, const float* __restrict__ r, const uint8_t* __restrict__ done, float gamma, int64_t n, float* __restrict__ y) { DqnTargetOp::run(blockIdx.x, gridDim.x, q, nout, r, done, gamma, n, y); }
-__global__ void k_td_error(const float* __restrict__ q, int nout, const uint8_t* __restrict__ a, const float* __restrict__ y, int64_t n, float* __restrict__ err) { TdErrorOp::run(blockIdx.x, gridDim.x, q, nout, a, y, n, err); }
-
 extern "C" {
 
 int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_y) { CRUX_PLAIN_ONLY("crux_dqn_target", tn);
@@ -835,7 +832,7 @@ int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_
   int32_t rc;
   if (tn->nd.maxdim >= CRUX_DENSE_MIN_WIDTH) { rc = crux_dense_forward(tn, (const float*)batch->col[CRUX_COL_SP], n, c->stream); if (rc) return rc; q = crux_dense_act(tn, tn->nd.L); }
   else { rc = crux_mlp_forward_impl(tn, (const float*)batch->col[CRUX_COL_SP], n, q, nullptr); if (rc) return rc; }
-  CRUX_RUN(c, DqnTargetOp, OP_DQN_TARGET, k_dqn_target, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const float*)batch->col[CRUX_COL_R], (const uint8_t*)batch->col[CRUX_COL_DONE], gamma, n, d_y);
+  CRUX_RUN(c, DqnTargetOp, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const float*)batch->col[CRUX_COL_R], (const uint8_t*)batch->col[CRUX_COL_DONE], gamma, n, d_y);
   return crux_launch_check(c, "k_dqn_target");
 }
 
@@ -848,7 +845,7 @@ int32_t crux_td_error(crux_mlp* net, crux_buffer* batch, const float* d_y, float
   int32_t rc;
   if (net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH) { rc = crux_dense_forward(net, (const float*)batch->col[CRUX_COL_S], n, c->stream); if (rc) return rc; q = crux_dense_act(net, net->nd.L); }
   else { rc = crux_mlp_forward_impl(net, (const float*)batch->col[CRUX_COL_S], n, q, nullptr); if (rc) return rc; }
-  CRUX_RUN(c, TdErrorOp, OP_TD_ERROR, k_td_error, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const uint8_t*)batch->col[CRUX_COL_A], d_y, n, d_err);
+  CRUX_RUN(c, TdErrorOp, (unsigned)((n + 255) / 256), 256, c->stream, q, nout, (const uint8_t*)batch->col[CRUX_COL_A], d_y, n, d_err);
   return crux_launch_check(c, "k_td_error");
 }
 
