@@ -10,9 +10,7 @@
 // Compiled inside offpolicy_unit.hip (uses the heads' helpers of sac.hip).
 #include "train_args.h"
 #include "peer_wait.h"
-#ifndef EPS32F
-#define EPS32F 1.1920928955078125e-07f
-#endif
+#include "mfma_helpers.h"      // EPS32F
 #define CRUX_MAXEXTRA 64      // logSigma entries a Gaussian head may carry here (act_dim <= 64, as in check_sac)
 
 __global__ void k_gather_obs(const float* __restrict__ S, int od, const int32_t* __restrict__ rows, int64_t nb, float* __restrict__ x) {

@@ -46,6 +46,7 @@
 #include "train_args.h"
 
 #include "mfma_helpers.h"
+#include "learner_shared.h"
 #include "peer_wait.h"
 
 #define FS_LD 72
@@ -170,30 +171,9 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   // dW2 / W2 ownership: tile (mp, m) = rows [16mp, 16mp+16) x columns [16m, 16m+16), numbered 4 mp + m; wave w owns the WT tiles from number w WT on (same mp)
   const int mp0 = (w * WT) >> 2, m0 = (w * WT) & 3;
 
-  auto s_master = [&](int s) -> int {
-    if (s < Lt::sB1) { const int o = s & 63, i = s >> 6; return Lt::oW1R + o * Lt::W1LD + i; }
-    if (s < Lt::sB2) return Lt::oB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::oB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) { const int q = s - Lt::sW3; const int o = q % OUT, i = q / OUT; return Lt::oW3R + o * H2 + i; }
-    if (s < Lt::sEX) return Lt::oB3 + (s - Lt::sB3);
-    return Lt::oEX + (s - Lt::sEX);
-  };
-  auto s_canon = [&](int s) -> int {
-    if (s < Lt::sB1) return Lt::cW1 + s;
-    if (s < Lt::sB2) return Lt::cB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::cB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) return Lt::cW3 + (s - Lt::sW3);
-    if (s < Lt::sEX) return Lt::cB3 + (s - Lt::sB3);
-    return Lt::cEX + (s - Lt::sEX);
-  };
-  auto s_part = [&](int s) -> int {
-    if (s < Lt::sB1) { const int o = s & 63, i = s >> 6; return Lt::pW1 + i * FS_LD + o; }
-    if (s < Lt::sB2) return Lt::pB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::pB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) { const int q = s - Lt::sW3; const int o = q % OUT, i = q / OUT; return Lt::pW3 + o * H2 + i; }
-    if (s < Lt::sEX) return Lt::pB3 + (s - Lt::sB3);
-    return Lt::pEX + (s - Lt::sEX);
-  };
+  auto s_master = [](int s) { return slot_master<Lt, OUT, H2>(s); };
+  auto s_canon = [](int s) { return slot_canon<Lt>(s); };
+  auto s_part = [](int s) { return slot_part<Lt, OUT, H2, FS_LD>(s); };
   const int ns_valid = Lt::sEX + n_extra;
 
   // ---- load parameters and Adam state (all 512 threads) ------------------------------------------------------------
@@ -304,11 +284,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     return true;
   };
   auto epoch_epilogue = [&](int ep) {
-    if (tid == 0 && p == 0 && a.epoch_infos) { float* e = a.epoch_infos + (size_t)ep * CRUX_INFO_N;   // aggregate_info(minibatch_infos) == last minibatch (Q3)
-      for (int k = 0; k < CRUX_INFO_N; ++k) e[k] = 0.f;
-      e[CRUX_INFO_LOSS] = sm[Lt::iLOSS]; e[CRUX_INFO_GRAD_NORM] = sm[Lt::iGN];
-      if (KIND != MFK_VALUE) { e[CRUX_INFO_ENTROPY] = sm[Lt::iENT]; e[CRUX_INFO_KL] = inf_kl; e[CRUX_INFO_CLIP_FRACTION] = sm[Lt::iCLIP]; e[CRUX_INFO_AVG_ADVANTAGE] = sm[Lt::iADV]; e[CRUX_INFO_AVG_RETURN] = sm[Lt::iRET]; }
-      if constexpr (LAG) { e[CRUX_INFO_PENALTY] = sm[Lt::iPEN]; e[CRUX_INFO_CUR_COST] = sm[Lt::iCUR]; e[CRUX_INFO_COST_LOSS] = sm[Lt::iCLOSS]; e[CRUX_INFO_P_LOSS] = sm[Lt::iPLOSS]; } }
+    if (tid == 0 && p == 0 && a.epoch_infos) epoch_info_row<Lt, KIND, LAG>(a.epoch_infos + (size_t)ep * CRUX_INFO_N, sm, inf_kl);
     epochs_run += 1;
     if (target_kl >= 0.f && KIND != MFK_VALUE && inf_kl > target_kl) stop = true;   // training.jl:49
     if (max_batches > 0 && total_batches >= max_batches) stop = true;               // :50

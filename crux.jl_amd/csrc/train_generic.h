@@ -1,11 +1,9 @@
 // train_generic.h -- the shape-generic persistent learner body (train! / batch_train!, src/training.jl:13-55) shared by train.hip and env.hip.
 #pragma once
 #include "train_args.h"
+#include "mfma_helpers.h"      // EPS32F
 
 #define TR_CH 32
-#ifndef EPS32F
-#define EPS32F 1.1920928955078125e-07f
-#endif
 
 __device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
   // 256 threads = 4 waves. Deterministic: wave butterfly then fixed-order sum of 4 partials.

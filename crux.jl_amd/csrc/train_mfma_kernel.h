@@ -21,6 +21,7 @@
 #include "train_args.h"
 
 #include "mfma_helpers.h"
+#include "learner_shared.h"
 
 // LDS layouts are chosen against the gfx950 banking rules (ds_read_b128: 64 banks, four non-contiguous 16-lane groups; b32 accesses:
 // 32 banks, two 32-lane halves): master rows are 72 floats, the per-wave exchange tiles are unpadded [64 features][16 samples]
@@ -56,6 +57,10 @@ struct MfLayout {
   static constexpr int oSC = oXS + MF8_NW * 16 * XP;
   static constexpr int oRED = oSC + MF8_NW * 16 * SCW;        // [0,8): per-wave sum of squares; [8,15): reduced stat sums; [16]: abort flag
   static constexpr int TOTAL = oRED + 32;
+  // the reported minibatch's info (training.jl:22-23) is kept by thread 0 -- its only reader (epoch_infos) -- in free words of the reduction area, not in registers of every
+  // thread that would stay live across the whole launch (k_train_fs2 has the measurement: ~30 VGPRs); the KL stays a register: the loop exits read it
+  static constexpr int iLOSS = oRED + 18, iGN = oRED + 19, iENT = oRED + 20, iCLIP = oRED + 21, iADV = oRED + 22, iRET = oRED + 23,
+                       iPEN = oRED + 24, iCUR = oRED + 25, iCLOSS = oRED + 26, iPLOSS = oRED + 27;
 };
 
 // CRUX_MFMA_TIMING: the phases MX_T(0..15) closes, in order (both forms)
@@ -101,30 +106,9 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
   const int mp0 = NW == 4 ? w : (w >> 1), m0 = NW == 4 ? 0 : 2 * (w & 1);
   const int p = NWG == 2 ? (int)((blockIdx.x >> 3) & 1) : 0;   // workgroup 0 or 1 of this learner (blockIdx 16r / 16r + 8)
 
-  auto s_master = [&](int s) -> int {
-    if (s < Lt::sB1) { const int o = s & 63, i = s >> 6; return Lt::oW1R + o * Lt::W1LD + i; }
-    if (s < Lt::sB2) return Lt::oB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::oB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) { const int t = s - Lt::sW3; const int o = t % OUT, i = t / OUT; return Lt::oW3R + o * MF_HID + i; }
-    if (s < Lt::sEX) return Lt::oB3 + (s - Lt::sB3);
-    return Lt::oEX + (s - Lt::sEX);
-  };
-  auto s_canon = [&](int s) -> int {
-    if (s < Lt::sB1) return Lt::cW1 + s;
-    if (s < Lt::sB2) return Lt::cB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::cB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) return Lt::cW3 + (s - Lt::sW3);
-    if (s < Lt::sEX) return Lt::cB3 + (s - Lt::sB3);
-    return Lt::cEX + (s - Lt::sEX);
-  };
-  auto s_part = [&](int s) -> int {
-    if (s < Lt::sB1) { const int o = s & 63, i = s >> 6; return Lt::pW1 + i * MF8_LD + o; }
-    if (s < Lt::sB2) return Lt::pB1 + (s - Lt::sB1);
-    if (s < Lt::sW3) return Lt::pB2 + (s - Lt::sB2);
-    if (s < Lt::sB3) { const int t = s - Lt::sW3; const int o = t % OUT, i = t / OUT; return Lt::pW3 + o * MF_HID + i; }
-    if (s < Lt::sEX) return Lt::pB3 + (s - Lt::sB3);
-    return Lt::pEX + (s - Lt::sEX);
-  };
+  auto s_master = [](int s) { return slot_master<Lt, OUT, MF_HID>(s); };
+  auto s_canon = [](int s) { return slot_canon<Lt>(s); };
+  auto s_part = [](int s) { return slot_part<Lt, OUT, MF_HID, MF8_LD>(s); };
   const int ns_valid = Lt::sEX + n_extra;
   constexpr int NSI = (NS + NT - 1) / NT;
   int so_part[NSI], so_master[NSI]; bool so_ok[NSI], so_ex[NSI];
@@ -168,10 +152,6 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
   bool staged = false;                              // the next minibatch is already in this wave's LDS staging tiles
   long long xstep = 0;                              // exchanges done so far (the counter target and the slot parity)
   constexpr int XSLOT = 4096 + NSI * NT + 16;
-  // the reported minibatch's info (training.jl:22-23) is kept by thread 0 -- its only reader (epoch_infos) -- in free words of the reduction area, not in registers of every
-  // thread that would stay live across the whole launch (k_train_fs2 has the measurement: ~30 VGPRs); the KL stays a register: the loop exits read it
-  constexpr int iLOSS = Lt::oRED + 18, iGN = Lt::oRED + 19, iENT = Lt::oRED + 20, iCLIP = Lt::oRED + 21, iADV = Lt::oRED + 22, iRET = Lt::oRED + 23,
-                iPEN = Lt::oRED + 24, iCUR = Lt::oRED + 25, iCLOSS = Lt::oRED + 26, iPLOSS = Lt::oRED + 27;
   if (threadIdx.x == 0) { for (int k = 18; k < 28; ++k) sm[Lt::oRED + k] = 0.f; }
   float inf_kl = 0.f;
   const int n_epochs = a.ids ? 1 : a.epochs;
@@ -582,21 +562,21 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
           for (int q = 1; q < MF8_NW; ++q) ss += sm[Lt::oRED + q];
           if (KIND != MFK_VALUE) inf_kl = t[2] * invB;
           if (tid == 0) {
-          sm[iGN] = sqrtf(ss);
-          if (KIND == MFK_VALUE) { sm[iLOSS] = t[6] * invB; sm[iRET] = t[4] * invB; }
+          sm[Lt::iGN] = sqrtf(ss);
+          if (KIND == MFK_VALUE) { sm[Lt::iLOSS] = t[6] * invB; sm[Lt::iRET] = t[4] * invB; }
           else { const float p_loss = -(t[0] * invB); float entropy;
             if (KIND == MFK_CATEGORICAL) entropy = t[1] * invB;
             else { entropy = 1.4189385332046727f;
 #pragma unroll
               for (int k = 0; k < OUT; ++k) entropy += sm[Lt::oEX + k]; }
-            sm[iENT] = entropy; sm[iLOSS] = a.lambda_p * p_loss + a.lambda_e * (-entropy); sm[iADV] = t[3] * invB; sm[iRET] = t[4] * invB; sm[iCLIP] = t[5] * invB;
+            sm[Lt::iENT] = entropy; sm[Lt::iLOSS] = a.lambda_p * p_loss + a.lambda_e * (-entropy); sm[Lt::iADV] = t[3] * invB; sm[Lt::iRET] = t[4] * invB; sm[Lt::iCLIP] = t[5] * invB;
             if constexpr (LAG) { const float cost_loss = pen * (t[7] * invB);                                        // ppo.jl:119
-              sm[iLOSS] = ((a.lambda_p * p_loss + a.lambda_e * (-entropy)) + cost_loss) / (1.f + pen);                  // :131
-              sm[iPEN] = pen; sm[iCUR] = lg.cur_cost; sm[iCLOSS] = cost_loss; sm[iPLOSS] = a.lambda_p * p_loss; } }
+              sm[Lt::iLOSS] = ((a.lambda_p * p_loss + a.lambda_e * (-entropy)) + cost_loss) / (1.f + pen);                  // :131
+              sm[Lt::iPEN] = pen; sm[Lt::iCUR] = lg.cur_cost; sm[Lt::iCLOSS] = cost_loss; sm[Lt::iPLOSS] = a.lambda_p * p_loss; } }
           }
         }
       }
-      if (any_bad) { if (tid == 0) sm[iGN] = NAN; err = CRUX_ENAN; break; }      // training.jl:20: no update
+      if (any_bad) { if (tid == 0) sm[Lt::iGN] = NAN; err = CRUX_ENAN; break; }      // training.jl:20: no update
       // ======================= Adam (Flux.update!, training.jl:21) =======================
       if (a.apply) {
 #pragma unroll
@@ -627,11 +607,7 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
       if (a.target_kl >= 0.f && KIND != MFK_VALUE && inf_kl > a.target_kl) break;   // :46
     }
     if (err) break;
-    if (tid == 0 && p == 0 && a.epoch_infos) { float* e = a.epoch_infos + (size_t)ep * CRUX_INFO_N;   // aggregate_info(minibatch_infos) == last minibatch (Q3)
-      for (int k = 0; k < CRUX_INFO_N; ++k) e[k] = 0.f;
-      e[CRUX_INFO_LOSS] = sm[iLOSS]; e[CRUX_INFO_GRAD_NORM] = sm[iGN];
-      if (KIND != MFK_VALUE) { e[CRUX_INFO_ENTROPY] = sm[iENT]; e[CRUX_INFO_KL] = inf_kl; e[CRUX_INFO_CLIP_FRACTION] = sm[iCLIP]; e[CRUX_INFO_AVG_ADVANTAGE] = sm[iADV]; e[CRUX_INFO_AVG_RETURN] = sm[iRET]; }
-      if constexpr (LAG) { e[CRUX_INFO_PENALTY] = sm[iPEN]; e[CRUX_INFO_CUR_COST] = sm[iCUR]; e[CRUX_INFO_COST_LOSS] = sm[iCLOSS]; e[CRUX_INFO_P_LOSS] = sm[iPLOSS]; } }
+    if (tid == 0 && p == 0 && a.epoch_infos) epoch_info_row<Lt, KIND, LAG>(a.epoch_infos + (size_t)ep * CRUX_INFO_N, sm, inf_kl);
     epochs_run += 1;
     if (a.target_kl >= 0.f && KIND != MFK_VALUE && inf_kl > a.target_kl) stop = true;   // :49
     if (a.max_batches > 0 && total_batches >= a.max_batches) stop = true;               // :50
@@ -652,7 +628,7 @@ __global__ __launch_bounds__(64 * NW) void k_train_mfma(TrainArgs a_single, cons
     if (err == CRUX_EHIP) a.status[4] = why_failed;      // 1 local workgroup missing, 2 workgroups on different XCDs
     a.bp[0] = bp1; a.bp[1] = bp2;
     if constexpr (LAG) { if (p == 0) *a.lag = lg; }
-    if (err && a.epoch_infos && epochs_run == 0) { a.epoch_infos[CRUX_INFO_LOSS] = sm[iLOSS]; a.epoch_infos[CRUX_INFO_GRAD_NORM] = NAN; }
+    if (err && a.epoch_infos && epochs_run == 0) { a.epoch_infos[CRUX_INFO_LOSS] = sm[Lt::iLOSS]; a.epoch_infos[CRUX_INFO_GRAD_NORM] = NAN; }
   }
 }
 
