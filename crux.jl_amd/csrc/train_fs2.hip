@@ -6,7 +6,7 @@
 
 template <int IN, int OUT, int KIND, int ACT, int H2, int ACT2, bool TIMING, bool PX = false, bool PXK = false, bool LAG = false>
 static int32_t launch_fs2_form(crux_ctx* c, TrainArgs& a, hipStream_t stream) {
-  using Lt = Fs2Layout<IN, OUT, H2, LAG>;
+  using Lt = Fs2LayoutFor<IN, OUT, H2, LAG, PX>;
   constexpr size_t lds = sizeof(float) * (size_t)(PX && Lt::BK_FITS ? Lt::TOTAL_BK : Lt::TOTAL);
   { const int32_t rc = crux_lds_attr_once<k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>>(c, lds); if (rc) return rc; }
   hipLaunchKernelGGL((k_train_fs2<IN, OUT, KIND, ACT, H2, ACT2, TIMING, PX, PXK, LAG>), dim3(32), dim3(512), lds, stream, a);
@@ -42,10 +42,10 @@ static int32_t launch_fs2(crux_ctx* c, TrainArgs a, bool timing, hipStream_t str
                                        "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+report+exit"};
     static const char* const nh[16] = {"loop", "fetch", "stage next", "wait B_1", "dW2+send+drain", "arrival 1+wait(leader)", "-", "-", "-", "wait B_2+reduce+granules", "wait P1",
                                        "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+exit"};
-    MfTimingRow rows[8];
-    for (int i = 0; i < 8; ++i) { const int wg = i >> 1, w = 4 * (i & 1); rows[i].row = 8 * wg + w; rows[i].names = w == 0 ? nc : nh;
+    MfTimingRow rows[12];      // per workgroup: compute wave 0, the helper leader, the last helper wave
+    for (int i = 0; i < 12; ++i) { const int wg = i / 3, w = i % 3 == 0 ? 0 : i % 3 == 1 ? 4 : 7; rows[i].row = 8 * wg + w; rows[i].names = w == 0 ? nc : nh;
       snprintf(rows[i].label, sizeof rows[i].label, "[fs2-timing] %d-%d wg %d %s wave %d:", IN, OUT, wg, w == 0 ? "compute" : "helper", w); }
-    return mf_timing_dump(c, stream, rows, 8);
+    return mf_timing_dump(c, stream, rows, 12);
   }
   return launch_fs2_form<IN, OUT, KIND, ACT, H2, ACT2, false>(c, a, stream);
 }

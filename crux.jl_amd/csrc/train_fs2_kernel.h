@@ -34,6 +34,9 @@
 //       compute waves are in dH1 / dZ1 / dW1: when the small partials are ready, the peers' W2 partials are known to be in the L2 already;
 //   (2) the small partials, the last bytes of the step, travel as data-tagged granules -- store, then poll the peers' granules until the tag is the step's: one L2 round trip
 //       where the flag protocol needs three (drain, arrival + wait, load);
+//       The small parameters are dealt to the 512 threads in rounds (s = tid + 512 k); the loss head's own sums -- 7 statistics, the gradients of b3 and log-sigma, the lagrange
+//       cost term -- lie in one vector behind them. Where b3 and log-sigma alone would open another round (4-64-64-2: 512 + 2 parameters, 11-64-64-3: 1024 + 6) they are not
+//       dealt: the "misc lanes" that carry that vector's words through the exchange own them (Fs2Layout, MISC), and every thread sums, stores, polls and updates one round less;
 //   (3) each role is its own code path: the register allocation is the maximum of the two roles, not their union -- no plain or lagrange instantiation spills;
 //   (4) two workgroup barriers per step instead of five; pairs and roles meet through LDS counters.
 // NaN semantics (training.jl:20: a NaN gradient norm is an error BEFORE the update): every thread forms the totals of its own elements in every workgroup; one that finds a
@@ -92,13 +95,26 @@ struct FsLayout {
   static_assert(XSLOT <= 8192, "exchange slot");
 };
 
-template <int IN, int OUT, int H2, bool LAG = false>
+// MISC: b3 and log-sigma are not dealt in rounds. The loss head leaves one vector per tile in the partial block's pMISC words -- 7 statistics sums, the OUT gradients of b3, the
+// OUT of log-sigma (Gaussian heads), the cost term (lagrange) -- and NV "misc lanes" carry it through the exchange, one word each: lane k_ sums word pMISC + k_ over the tiles,
+// publishes a granule and polls the peers' copies. A lane whose word is a gradient also OWNS that parameter (NaN test, norm share, Adam, undo). The rounds then cover W1, b1, b2
+// and W3 only: one round fewer for every shape within OUT + extras + 16 of a multiple of 512 (the C2 actor: 512 + 2). Lane k_ is thread (sB3 - 7 + k_) mod 512, so b3[o] and
+// logsigma[o] stay with the thread the dealing gave them to, as its last element: the wave's share of the gradient norm adds the same terms in the same order (same bits).
+// MISC = false is the dealt map: b3 and log-sigma in the rounds, the 7 statistics lanes (an eighth: the lagrange cost term) at the end of the last wave. It stays where the
+// misc lanes save no round (FS2_MISC_PAYS below: there they only add the owners' code to waves that still run every round -- C5 measured 7.53 -> 7.62 us per step) and in the
+// replica-group forms, whose exchange sections carry the rounds' registers.
+// (name the layout of an instantiation through Fs2LayoutFor below, which derives MISC in one place)
+template <int IN, int OUT, int H2, bool LAG = false, bool MISC = false>
 struct Fs2Layout : FsLayout<IN, OUT, 4, true, H2, LAG> {
   using B = FsLayout<IN, OUT, 4, true, H2, LAG>;
   static constexpr int NTC = 256;                                   // compute threads = helper threads
-  static constexpr int NSC = (B::NS + 511) / 512;                   // small parameters per thread (all 512 threads share them)
+  static constexpr bool MISC_MAP = MISC;
+  static constexpr int NSD = MISC ? B::sB3 : B::NS;                 // small-parameter slots dealt to the threads in rounds of 512 (s = tid + 512 k)
+  static constexpr int NSC = (NSD + 511) / 512;                     // rounds: dealt small parameters per thread (all 512 threads share them)
+  static constexpr int LB = MISC ? ((B::sB3 - 7) & 511) : 512 - 8;  // thread of misc lane 0
   static constexpr int WT2 = (B::NT2 * 4) / 8;                      // W2 tiles per wave (all eight waves own tiles)
-  static constexpr int NGR = NSC * 512 + 8;                         // granules of a slot: the small partials, then the 7 statistics sums
+  static constexpr int gST = NSC * 512;                             // granule numbers: the dealt small partials, then the misc lanes' words (at most 7 + 8 + 8 + 1)
+  static constexpr int NGR = gST + (MISC ? 24 : 8);                 // (24 reserved whatever the head's NV is: the slot stride then depends on the shape's rounds only)
   static constexpr int xW2 = 0, xGR = B::W2N;                       // exchange slot: W2 partials [thread][WT2][4] | granules {value, step} of the small partials and statistics
   static constexpr int XSLOT2 = ((xGR + 2 * NGR + 3) / 4) * 4;
   static_assert(2 * 4 * XSLOT2 <= CRUX_XBUF_FLOATS, "exchange area");
@@ -117,6 +133,11 @@ struct Fs2Layout : FsLayout<IN, OUT, 4, true, H2, LAG> {
   // of wave 0's and wave 1's copies
   static constexpr int iPEN = B::oLGS + 5, iCUR = B::oLGS + 6, iCLOSS = B::oLGS + 7, iPLOSS = B::oLGS + 15;
 };
+
+// the misc-lane map is used where it saves a round of the dealt small parameters: the shapes with OUT + extras + 16 slots or fewer past a multiple of 512 (4-64-64-2, 11-64-64-3)
+template <int IN, int OUT, int H2, bool LAG> constexpr bool FS2_MISC_PAYS = Fs2Layout<IN, OUT, H2, LAG, true>::NSC < Fs2Layout<IN, OUT, H2, LAG, false>::NSC;
+// the layout of instantiation <IN, OUT, H2, LAG, PX> -- kernel and host name it through this alias: misc lanes where they save a round, never in the replica-group forms
+template <int IN, int OUT, int H2, bool LAG, bool PX> using Fs2LayoutFor = Fs2Layout<IN, OUT, H2, LAG, !PX && FS2_MISC_PAYS<IN, OUT, H2, LAG>>;
 
 // meeting point of a subset of the workgroup's waves: one LDS counter, monotonic over the launch (target = members x number of uses so far). A wave's LDS operations execute in
 // order, so everything it wrote before the add is in the LDS before the add is.
@@ -140,8 +161,9 @@ template <int IN, int OUT, int KIND, int ACT, int H2 = 64, int ACT2 = ACT, bool 
 __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   static_assert(!PXK || PX, "PXK: the periodic form of the replica group");
   static_assert(!LAG || (!PX && KIND != MFK_VALUE), "lagrange_ppo_loss: policy heads, one replica");
-  static_assert(!PX || FsLayout<IN, OUT, 4, true, H2, false>::W2N + Fs2Layout<IN, OUT, H2>::NSC * 512 + 8 <= CRUX_PX_SEC, "a payload section must fit CRUX_PX_SEC");
-  using Lt = Fs2Layout<IN, OUT, H2, LAG>;
+  static_assert(!PX || FsLayout<IN, OUT, 4, true, H2, false>::W2N + Fs2Layout<IN, OUT, H2, false, false>::NSC * 512 + 8 <= CRUX_PX_SEC, "a payload section must fit CRUX_PX_SEC");
+  using Lt = Fs2LayoutFor<IN, OUT, H2, LAG, PX>;
+  constexpr bool MISC = Lt::MISC_MAP;               // b3 / log-sigma owned by misc lanes where that saves a round; the replica-group forms keep the dealt map
   constexpr int NWG = 4, NWC = 4, TILES = 2, NT = 512, NTC = 256, MH = Lt::MH, HH = Lt::HH, W2N = Lt::W2N, NW = 8;
   constexpr int WT = Lt::WT2;                       // 16x16 tiles of W2 owned by a wave (all eight waves own tiles)
   constexpr int KS0 = Lt::KS0, IP = Lt::IP, JT = Lt::JT, XP = Lt::XP, NS = Lt::NS, NSC = Lt::NSC, XSLOT = Lt::XSLOT2;
@@ -162,7 +184,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   int xcur = 0;
   float* T1 = sm + Lt::oT1 + t * Lt::TILE;
   float* T2 = sm + Lt::oT2 + t * Lt::TILE2;
-  const int n_extra = (KIND == MFK_GAUSSIAN) ? OUT : 0;
+  constexpr int n_extra = (KIND == MFK_GAUSSIAN) ? OUT : 0;
   unsigned long long tacc[16]; unsigned long long tlast = 0;
   if (TIMING) { for (int k = 0; k < 16; ++k) tacc[k] = 0; tlast = __builtin_amdgcn_s_memtime(); }
 #define FS2_T(ph) do { if (TIMING) { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tacc[ph] += tn - tlast; tlast = tn; } } while (0)
@@ -174,7 +196,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   auto s_master = [](int s) { return slot_master<Lt, OUT, H2>(s); };
   auto s_canon = [](int s) { return slot_canon<Lt>(s); };
   auto s_part = [](int s) { return slot_part<Lt, OUT, H2, FS_LD>(s); };
-  const int ns_valid = Lt::sEX + n_extra;
+  constexpr int ns_valid = Lt::sEX + n_extra, ns_dealt = MISC ? Lt::sB3 : ns_valid;
 
   // ---- load parameters and Adam state (all 512 threads) ------------------------------------------------------------
   for (int q = tid; q < W2N; q += NT) { const int o = q % H2, i = q / H2; const float v = a.p[Lt::cW2 + q];
@@ -353,9 +375,15 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   // the small parameters (everything but W2), shared by all 512 threads
   int so_part[NSC], so_master[NSC]; bool so_ok[NSC], so_ex[NSC];
 #pragma unroll
-  for (int k = 0; k < NSC; ++k) { const int s = tid + NT * k; so_ok[k] = s < ns_valid; so_ex[k] = s >= Lt::sEX;
+  for (int k = 0; k < NSC; ++k) { const int s = tid + NT * k; so_ok[k] = s < ns_dealt; so_ex[k] = s >= Lt::sEX;
     so_part[k] = so_ok[k] ? s_part(s) : 0; so_master[k] = so_ok[k] ? s_master(s) : 0; }
-  const bool stat_lane = tid >= NT - 8 && tid < (LAG ? NT : NT - 1);      // stat sums, by 7 lanes of the last wave (an eighth: the cost term of lagrange_ppo_loss)
+  // the misc lanes (Fs2Layout): lane k_ carries word pMISC + k_ of the tiles' partial blocks. k_ < 7: a statistics sum; 7 <= k_ < 7 + NOWN: the gradient of b3 | log-sigma
+  // element k_ - 7 (slot s = sB3 + k_ - 7; sEX == sB3 + OUT and pEX == pB3 + OUT: one block in both spaces), owned by this lane; k_ == 7 + NOWN: the lagrange cost term.
+  // (the dealt map: the 7 statistics lanes at the end of the last wave, the lagrange cost term -- the word behind b3 | log-sigma -- as the eighth)
+  constexpr int NOWN = MISC ? OUT + n_extra : 0, NV = 7 + NOWN + (LAG ? 1 : 0);
+  auto misc_k = [&]() -> int { if constexpr (MISC) return (tid - Lt::LB) & (NT - 1); else return tid - (NT - 8); };      // (formed where it is used: no register across the launch)
+  const bool stat_lane = MISC ? misc_k() < NV : (tid >= NT - 8 && tid < (LAG ? NT : NT - 1));
+  const bool own_lane = MISC && misc_k() >= 7 && misc_k() < 7 + NOWN;
   // ---- replica group (comm.hip "peer"): mean over the group of NSEC payload sections (the W2-tile registers + the small parameters'
   // registers of every thread) and one statistics word, the same bits on every workgroup of every rank. Per-step form: ONE section, the minibatch gradient and its statistics;
   // periodic form (PXK): THREE sections -- theta, m, v after every k-th Adam step -- in one exchange. All four workgroups hold the same local values and share the writes (peer i
@@ -486,7 +514,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         for (int q = 1; q < TILES; ++q) gsum += sm[po + q * Lt::PART]; }
       gs[k] = gsum; }
     float stat_loc = 0.f;
-    if (stat_lane) { const int k_ = tid - (NT - 8); const int ko = (LAG && k_ == 7) ? Lt::pMISC + 7 + OUT + (KIND == MFK_GAUSSIAN ? OUT : 0) : Lt::pST + k_; stat_loc = sm[Lt::oPART + ko];
+    if (stat_lane) { const int ko = (!MISC && LAG && misc_k() == 7) ? Lt::pMISC + 7 + OUT + n_extra : Lt::pMISC + misc_k(); stat_loc = sm[Lt::oPART + ko];
 #pragma unroll
       for (int q = 1; q < TILES; ++q) stat_loc += sm[Lt::oPART + q * Lt::PART + ko]; }
     // the small partials travel as granules: {value, step} in ONE naturally aligned 8-byte store -- the tag is the flag
@@ -496,7 +524,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
       *(u32x2*)(mine + Lt::xGR + 2 * gi) = gq; };
 #pragma unroll
     for (int k = 0; k < NSC; ++k) gran_put(tid + NT * k, gs[k]);
-    if (stat_lane) gran_put(NSC * NT + (tid - (NT - 8)), stat_loc);
+    if (stat_lane) gran_put(Lt::gST + misc_k(), stat_loc);
     FS2_T(9);
     fs2_flag_wait(sm + Lt::fP1, tag);           // phase 1 is complete (or has failed): every workgroup's W2 partials are in the L2
     FS2_T(10);
@@ -536,7 +564,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
 #pragma unroll
           for (int k = 0; k < NSC; ++k) gv[j][k] = __hip_atomic_load((const unsigned long long*)(peer + 2 * (tid + NT * k)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           gst[j] = ((unsigned long long)tag << 32);
-          if (stat_lane) gst[j] = __hip_atomic_load((const unsigned long long*)(peer + 2 * (NSC * NT + (tid - (NT - 8)))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+          if (stat_lane) gst[j] = __hip_atomic_load((const unsigned long long*)(peer + 2 * (Lt::gST + misc_k())), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         bool all_in = true;
 #pragma unroll
         for (int j = 0; j < NLD; ++j) { all_in = all_in && (unsigned)(gst[j] >> 32) == tag; ps[j] = __builtin_bit_cast(float, (unsigned)gst[j]);
@@ -550,7 +578,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     FS2_T(11);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FS2_T(12);
-    float th_o[NSC], m_o[NSC], v_o[NSC];
+    float th_o[NSC], m_o[NSC], v_o[NSC]; float th_mo = 0.f, m_mo = 0.f, v_mo = 0.f;
     float stat_tot = stat_loc;
     if constexpr (PX && !PXK) {
       if (!failed) {
@@ -574,14 +602,24 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         adam_w2(gW2); }                          // (every compute wave is past B_2: nobody reads the W2 masters any more)
 #pragma unroll
       for (int k = 0; k < NSC; ++k) { gs[k] = (gs[k] + pg[0][k]) + (pg[1][k] + pg[2][k]); bad_tot = bad_tot || (so_ok[k] && isnan(gs[k])); }
-      if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
-      stat_tot = (stat_loc + ps[0]) + (ps[1] + ps[2]);
+      if constexpr (MISC) {
+        stat_tot = (stat_loc + ps[0]) + (ps[1] + ps[2]);
+        bad_tot = bad_tot || (own_lane && isnan(stat_tot));      // a lane that owns its word: the total is a gradient
+        if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
+      } else {      // (the dealt map keeps its statement order and with it the parent's instruction stream: with the two statements swapped C5 measured 7.54 -> 7.65 us
+                    //  per step, profiles/fs2_misc_lanes_ab.txt)
+        if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
+        stat_tot = (stat_loc + ps[0]) + (ps[1] + ps[2]);
+      }
     }
-    if (stat_lane) sm[Lt::oRED + 8 + (tid - (NT - 8))] = stat_tot;
+    if (stat_lane && !own_lane) sm[Lt::oRED + 8 + (MISC && misc_k() > 7 ? 7 : misc_k())] = stat_tot;      // the statistics of the report (word 7: the lagrange cost term)
 #pragma unroll
     for (int k = 0; k < NSC; ++k) if (so_ok[k]) {
-      if (KIND == MFK_GAUSSIAN && so_ex[k]) gs[k] += LAG ? -lambda_e / (1.f + pen) : -lambda_e;       // d(-lambda_e H)/dlogSigma, H = const + sum(logSigma); lagrange: the whole loss is divided by 1 + penalty
+      if (!MISC && KIND == MFK_GAUSSIAN && so_ex[k]) gs[k] += LAG ? -lambda_e / (1.f + pen) : -lambda_e;       // d(-lambda_e H)/dlogSigma, H = const + sum(logSigma); lagrange: the whole loss is divided by 1 + penalty
       if (want_ssq) ssq += gs[k] * gs[k]; }
+    if constexpr (MISC) { if (own_lane) {      // the owned element comes last, where the dealing had it
+      if (KIND == MFK_GAUSSIAN && misc_k() >= 7 + OUT) stat_tot += LAG ? -lambda_e / (1.f + pen) : -lambda_e;
+      if (want_ssq) ssq += stat_tot * stat_tot; } }
     if (want_ssq) { ssq = wave_sum(ssq);
       if (lane == 0) sm[Lt::oRED + w] = ssq; }      // this wave's share of the gradient norm (the report is formed after B_b)
     FS2_T(13);
@@ -592,7 +630,12 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         if (so_ok[k]) { float m_ = sm[Lt::oMS + s], v_ = sm[Lt::oVS + s]; const int mo = so_master[k]; const float th = sm[mo];
           m_o[k] = m_; v_o[k] = v_; th_o[k] = th;
           const float d = adam1(gs[k], m_, v_, ak);
-          sm[Lt::oMS + s] = m_; sm[Lt::oVS + s] = v_; sm[mo] = th - d; } } };
+          sm[Lt::oMS + s] = m_; sm[Lt::oVS + s] = v_; sm[mo] = th - d; } }
+      if constexpr (MISC) { if (own_lane) { const int mi_s = Lt::sB3 + (misc_k() - 7), mi_master = s_master(mi_s);
+          float m_ = sm[Lt::oMS + mi_s], v_ = sm[Lt::oVS + mi_s]; const float th = sm[mi_master];
+          m_mo = m_; v_mo = v_; th_mo = th;
+          const float d = adam1(stat_tot, m_, v_, ak);
+          sm[Lt::oMS + mi_s] = m_; sm[Lt::oVS + mi_s] = v_; sm[mi_master] = th - d; } } };
     if (!failed) adam_small();
     if constexpr (PX && PXK) {
       // ---- periodic form (crux_peer_set_sync_every(k > 1)): between exchanges every replica takes LOCAL Adam steps on its own shard; after every k-th step the group averages
@@ -625,6 +668,8 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
 #pragma unroll
       for (int k = 0; k < NSC; ++k) { const int s = tid + NT * k;
         if (so_ok[k]) { sm[Lt::oMS + s] = m_o[k]; sm[Lt::oVS + s] = v_o[k]; sm[so_master[k]] = th_o[k]; } }
+      if constexpr (MISC) { if (own_lane) { const int mi_s = Lt::sB3 + (misc_k() - 7), mi_master = s_master(mi_s);
+          sm[Lt::oMS + mi_s] = m_mo; sm[Lt::oVS + mi_s] = v_mo; sm[mi_master] = th_mo; } }
 #pragma unroll
       for (int mm = 0; mm < WT; ++mm) {
         if constexpr (BK_LDS) { tW2[mm] = *(const f32x4*)&bk[4 * NT * mm]; mW2[mm] = *(const f32x4*)&bk[4 * NT * (WT + mm)]; vW2[mm] = *(const f32x4*)&bk[4 * NT * (2 * WT + mm)]; }
