@@ -175,6 +175,9 @@ SIGNATURES = {
     "crux_offgail_gather": (i32, [P(vp), i32, i64, u64, u64, vp]),
     "crux_adril_relabel": (i32, [vp, i64, i64, i64, P(i64), P(i64)]),
     "crux_orthogonal_reg": (i32, [vp, f32, i32, vp]),
+    "crux_fisher_create": (i32, [vp, f32, P(vp)]), "crux_fisher_destroy": (i32, [vp]), "crux_fisher_get": (i32, [vp, vp, vp, P(i64)]), "crux_fisher_set": (i32, [vp, vp, vp, i64, f32]),
+    "crux_fisher_add": (i32, [vp, i32]), "crux_fisher_snapshot": (i32, [vp]), "crux_fisher_reg": (i32, [vp, i32, vp]),
+    "crux_batch_train_fisher": (i32, [vp, vp, vp, P(TrainCfg), vp, vp, vp]),
     "crux_advil_d_step": (i32, [vp, vp, vp, f32, f32, u64, u64, vp, vp]),
     "crux_advil_actor_step": (i32, [vp, vp, vp, f32, f32, vp, vp]),
     "crux_asaf_freeze": (i32, [vp, vp, i64, i64, vp]),

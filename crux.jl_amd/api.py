@@ -47,10 +47,13 @@ from .il_batch import AdVIL, advil_actor_step_, advil_d_loss, advil_d_step_, adv
 from .il_on_policy import *   # noqa: F401,F403
 from .il_on_policy import ASAF, asaf_actor_step_, asaf_freeze_, asaf_loss, batch_train_asaf_   # noqa: F401
 from .core import OrthogonalRegularizer, orthogonal_regularizer   # noqa: F401
+from .continual import *   # noqa: F401,F403
+from .continual import (  # noqa: F401
+    DiagonalFisherRegularizer, add_fisher_information_diagonal_, continual_learning, log_multitask_performances_, update_fisher_)
 from .ensembles import *   # noqa: F401,F403
 from .ensembles import DeepClassificationEnsemble, DeepEnsemble, individual_forward, logpdf, training_loss   # noqa: F401
 from .on_policy import _solve_on_policy
-from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles   # noqa: F401
+from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles, continual   # noqa: F401
 
 
 def solve(solver, mdp=None):  # noqa: F811

@@ -1291,7 +1291,7 @@ class TrainingParams:
     (src/training.jl:1-11). PPO's early_stopping (`infos[end][:kl] > target_kl`, ppo.jl:59) is expressed as target_kl and runs inside the
     persistent learner kernel. The function-valued seams of the reference take the host-driven path of _train_seam / _batch_train_seam:
     regularizer(theta) -> (value, gradient) over the flat parameter vector (training.jl:4,13: loss + regularizer(pi)), or an OrthogonalRegularizer, which
-    stays on the device; early_stopping(infos) ->
+    stays on the device, or a DiagonalFisherRegularizer (continual.py), which rides in the dense-engine learner's chain; early_stopping(infos) ->
     Bool over the per-epoch info dicts (:8,46,49); loss = CustomLoss(fn)."""
 
     def __init__(self, loss, optimizer=None, batch_size=128, epochs=80, target_kl=None, name="", max_batches=math.inf,
@@ -1317,6 +1317,15 @@ def orthogonal_regularizer(net, beta=1e-4, accumulate=False):
     out = np.zeros(1, np.float32)
     net.ctx.check(net.ctx.lib.crux_orthogonal_reg(net.h, float(np.float32(beta)), 1 if accumulate else 0, _vp(out)))
     return float(out[0])
+
+
+def _fisher_reg(p):
+    """p.regularizer when it is a DiagonalFisherRegularizer (continual.py: evaluated on the device), else None"""
+    r = getattr(p, "regularizer", None)
+    if r is None:
+        return None
+    from .continual import DiagonalFisherRegularizer
+    return r if isinstance(r, DiagonalFisherRegularizer) else None
 
 
 def _uses_seam(p):
@@ -1360,8 +1369,13 @@ def _train_seam(pi, p, P, D, ids0, info):
         raw = np.zeros(L.INFO_N, np.float32); cfg = _train_cfg(pi, p, P)
         ctx.check(lib.crux_loss_grad(pi.h, D.h, C.byref(cfg), _vp(ids0), ids0.size, _vp(raw)))
         l = float(raw[L.INFO["loss"]])
-    dev_reg = isinstance(p.regularizer, OrthogonalRegularizer)
-    if dev_reg:                                                            # on the device, before the gradient is read back
+    fisher = _fisher_reg(p)
+    dev_reg = isinstance(p.regularizer, OrthogonalRegularizer) or fisher is not None
+    if fisher is not None:                                                 # on the device (crux_fisher_reg), before the gradient is read back
+        if fisher.net is not pi:
+            raise ValueError("train!: the DiagonalFisherRegularizer belongs to another network")
+        l = float(np.float32(l) + np.float32(fisher(accumulate=True)))
+    elif dev_reg:                                                          # on the device, before the gradient is read back
         l = float(np.float32(l) + np.float32(orthogonal_regularizer(pi, p.regularizer.beta, accumulate=True)))
     g = np.empty(n, np.float32); ctx.d2h(lib.crux_mlp_grads_ptr(pi.h), g)
     if p.regularizer is not None and not dev_reg:
@@ -1463,6 +1477,11 @@ def batch_train_(pi, p, P, D, info=None, perms=None):
     """batch_train!(pi, p, P, D; info) (src/training.jl:28-55): epochs x (shuffle!, partition, train!) with max_batches and
     early stopping, as ONE persistent kernel. perms: optional (epochs, len) 1-based permutations (else Philox)."""
     _ensure_opt(pi, p)
+    if _fisher_reg(p) is not None:                     # a DiagonalFisherRegularizer of this network: the dense-engine learner's chain (crux_batch_train_fisher) where it applies
+        from .continual import _batch_train_fisher
+        out = _batch_train_fisher(pi, p, P, D, info, perms)
+        if out is not None:
+            return out
     if _uses_seam(p):
         return _batch_train_seam(pi, p, P, D, info, perms)
     cfg = _train_cfg(pi, p, P)

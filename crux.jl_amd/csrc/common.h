@@ -164,6 +164,21 @@ struct crux_mlp {
   crux_sn* sn = nullptr;   // NULL: a plain Chain(Dense...), every path as without DenseSN
 };
 
+// DiagonalFisherRegularizer of one handle (fisher.hip; src/extras/fisher_information.jl): the running mean F of squared loss gradients, the anchor theta_prev, the table of
+// the handle's parameter arrays (W_0, b_0, ..., then the trailing extras as one array) and the value pass's block partials ([0] the value, [1..] one per block).
+#define CRUX_FISHER_MAXA (2 * CRUX_MAXL + 1)
+#define CRUX_FISHER_BLOCKS 64
+struct crux_fisher {
+  crux_ctx* ctx = nullptr;       // the owning handle's context (destroy must not look at `net`: a host language's finaliser may have freed the handle first)
+  crux_mlp* net = nullptr;
+  float* F = nullptr;            // device [n_params]
+  float* theta_prev = nullptr;   // device [n_params]
+  int64_t N = 0;
+  float lambda = 1.f;
+  int32_t A = 0, off[CRUX_FISHER_MAXA] = {0}, len[CRUX_FISHER_MAXA] = {0};
+  double* part = nullptr;        // device [2 + CRUX_FISHER_BLOCKS]
+};
+
 struct crux_buffer {
   crux_ctx* ctx = nullptr;
   int32_t obs_dim = 0, act_dim = 0, act_kind = 0;

@@ -141,7 +141,7 @@ static int32_t build_orders(crux_ctx* c, crux_buffer* buf, int slot, const int32
   return crux_launch_check(c, "k_compose_order");
 }
 
-bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic);     // train_dense.hip
+bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic, bool any_size = false);     // train_dense.hip
 // ---- packed learner rows --------------------------------------------------------------------------------------------------------------------
 // One line per transition with everything a policy-gradient / critic minibatch step reads of it: [s | action | logprob | advantage | return], padded to a power of two of
 // floats (C2: 8 floats = 32 B, C5: 32 floats = 128 B). Written once per batch_train! call (the columns do not change while the learners run; :advantage was whitened before);
@@ -185,11 +185,22 @@ static int32_t ensure_pack(crux_ctx* c, crux_buffer* buf, hipStream_t st, TrainA
     t->PACK = buf->pack; t->pack_stride = stride; t->pack_act = od; t->pack_lp = od + na; }
   return crux_launch_check(c, "k_pack_rows");
 }
-int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm = nullptr, int which = 0);
+int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm = nullptr, int which = 0, const crux_fisher* reg = nullptr);
 int32_t crux_train_fs_launch(crux_ctx* c, const TrainArgs& a, bool* handled, hipStream_t stream, bool probe);      // train_fs2.hip
-static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_t stream = nullptr) {
+// reg (crux_batch_train_fisher): the regulariser rides in the dense-engine learner's chain only -- the register-resident family is skipped, every shape whose loss the dense
+// learner has takes that route, anything else is CRUX_EUNSUP (the host falls back to its seam)
+static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_t stream = nullptr, const crux_fisher* reg = nullptr) {
   bool handled = false;
   if (!stream) stream = c->stream;
+  if (reg) {
+    a.need_px = 0; a.px_timeout = c->peer_timeout_ticks; a.px_every = 1;
+    if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false, true)) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a DiagonalFisherRegularizer: the dense-engine learner has no loss %d / head %d for this handle", a.loss, a.head);
+    const bool prof_r = stream == c->stream;
+    if (prof_r) crux_prof_begin(c, prof_slot);
+    const int32_t rcr = crux_train_dense_run(c, a, stream, stream == c->stream ? 0 : 1, reg);
+    if (prof_r) crux_prof_end(c, prof_slot);
+    return rcr;
+  }
   const bool prof = stream == c->stream;      // HIP-event timing is kept on the context's main stream
   if (prof) crux_prof_begin(c, prof_slot);
   // a replica group is attached (comm.hip "peer"): the per-minibatch gradient all-reduce lives in k_train_fs2's replica-group forms and in the dense-engine learner
@@ -237,7 +248,7 @@ static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_
 }
 
 // runs the kernel and interprets status; info_out = aggregate over epochs (aggregate_info(infos), training.jl:54)
-static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_epochs, float* info_out, float* epoch_infos, bool permute_after) {
+static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_epochs, float* info_out, float* epoch_infos, bool permute_after, const crux_fisher* reg = nullptr) {
   crux_ctx* c = net->ctx;
   const size_t eb = sizeof(float) * CRUX_INFO_N * (size_t)(n_epochs > 0 ? n_epochs : 1);
   char* sc = (char*)crux_scratch(c, eb + 256);
@@ -250,8 +261,8 @@ static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_ep
     int32_t* oa = nullptr; rc = build_orders(c, buf, 0, nullptr, a.shuffle_seed, a.shuffle_counter, a.perms, n_epochs, c->stream, &oa); if (rc) return rc;
     a.ord_all = oa;
   }
-  if (!a.ids) { rc = ensure_pack(c, buf, c->stream, a, nullptr); if (rc) return rc; }
-  rc = launch_train(c, a, slot); if (rc) return rc;
+  if (!a.ids && !reg) { rc = ensure_pack(c, buf, c->stream, a, nullptr); if (rc) return rc; }      // (the dense chain gathers through the order, not from packed rows)
+  rc = launch_train(c, a, slot, nullptr, reg); if (rc) return rc;
   int32_t st[8]; std::vector<float> ei((size_t)CRUX_INFO_N * (size_t)(n_epochs > 0 ? n_epochs : 1));
   HIPCHK(c, hipMemcpyAsync(st, a.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(ei.data(), a.epoch_infos, eb, hipMemcpyDeviceToHost, c->stream));
@@ -289,7 +300,7 @@ static int32_t upload_perms(crux_ctx* c, const int64_t* perms, int epochs, int64
 
 // batch_train!(net, opt, loss, D) (training.jl:28-55); lag != NULL: lagrange_ppo_loss (rl/ppo.jl:70-131,208), ppo_loss's learner with the PID state riding in the kernel,
 // copied in before the launch and back after it
-static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) {
+static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos, const crux_fisher* reg = nullptr) {
   crux_ctx* c = net->ctx;
   TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, lag ? CRUX_LOSS_PPO : cfg->loss); if (rc) return rc;
   if (lag) {
@@ -300,7 +311,7 @@ static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_trai
   }
   int64_t* d_perms = nullptr;
   if (perms) { rc = upload_perms(c, perms, cfg->epochs, buf->elements, &d_perms, "batch_train!: perms"); if (rc) return rc; a.perms = d_perms; }
-  rc = run_batch(net, buf, a, cfg->epochs, info_out, epoch_infos, true);
+  rc = run_batch(net, buf, a, cfg->epochs, info_out, epoch_infos, true, reg);
   if (lag) (void)hipMemcpyAsync(lag, c->lag_dev, sizeof *lag, hipMemcpyDeviceToHost, c->stream);     // the state advanced by the minibatches that ran (also after CRUX_ENAN, like the reference's P)
   if (lag || d_perms) (void)hipStreamSynchronize(c->stream);
   if (d_perms) (void)hipFree(d_perms);
@@ -325,6 +336,21 @@ int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_tr
   if (!has_col(buf, CRUX_COL_COST) || !has_col(buf, CRUX_COL_COST_ADVANTAGE)) return crux_fail(c, CRUX_EINVAL, "lagrange_ppo_loss: buffer needs :cost and :cost_advantage columns (ppo.jl:211)");
   // (a replica group attached: the launch falls through to the dense-engine learner, whose controller step exchanges the cost sums -- train_dense.hip: k_lagrange_pid)
   return batch_train_impl(net, buf, cfg, lag, perms, info_out, epoch_infos);
+}
+
+// batch_train!(net, opt, loss + R, D) (training.jl:13,28-55) with R a DiagonalFisherRegularizer (src/extras/fisher_information.jl): crux_batch_train with the regulariser
+// carried to the dense-engine learner's chain (train_dense.hip)
+int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_fisher", net);
+  if (!net || !R || !buf || !cfg) return CRUX_EINVAL;
+  crux_ctx* c = net->ctx; const char* who = "batch_train! with a DiagonalFisherRegularizer";
+  if (R->net != net) return crux_fail(c, CRUX_EUNSUP, "%s: the regulariser belongs to another handle", who);
+  if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
+  if (crux_grouped(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not in a replica group", who);
+  if (!(cfg->loss == CRUX_LOSS_PPO || cfg->loss == CRUX_LOSS_A2C || cfg->loss == CRUX_LOSS_VALUE_MSE || cfg->loss == CRUX_LOSS_MSE_ACTION))
+    return crux_fail(c, CRUX_EUNSUP, "%s: loss %d is not one of the dense-engine learner's (ppo, a2c, value mse, mse_action)", who, cfg->loss);
+  if (buf->elements <= 0) return crux_fail(c, CRUX_EINVAL, "batch_train!: empty buffer");
+  if (cfg->epochs < 1) return crux_fail(c, CRUX_EINVAL, "batch_train!: epochs %d", cfg->epochs);
+  return batch_train_impl(net, buf, cfg, nullptr, perms, info_out, epoch_infos, R);
 }
 
 static int32_t step_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out, int apply) {

@@ -198,18 +198,23 @@ __global__ __launch_bounds__(1024) void k_px_allreduce_flat(float* __restrict__ 
 __global__ void k_nan_status(const double* __restrict__ ssq, int32_t* __restrict__ status) { if (isnan(ssq[0])) status[0] = CRUX_ENAN; }   // gradient-only calls: the NaN check of training.jl:20 without the update
 
 // which learners take this path (called by launch_train after the MFMA family declined)
-bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic) {
+// any_size: a regularised chain (crux_batch_train_fisher) -- no other learner carries the regulariser, so the size thresholds do not apply
+bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic, bool any_size) {
   if (!a.host_net || !(a.ids || a.ord_all)) return false;
   if (!(CRUX_IS_PG(a.loss) || a.loss == CRUX_LOSS_VALUE_MSE || (a.loss == CRUX_LOSS_MSE_ACTION && a.squash == 0.f))) return false;
   if (CRUX_IS_PG(a.loss) && a.head != CRUX_HEAD_CATEGORICAL && a.head != CRUX_HEAD_GAUSSIAN) return false;
   if (a.nd.L < 1 || a.nd.n_extra > CRUX_MAXEXTRA) return false;
+  if (any_size) return true;
   if (generic_lds > 160 * 1024 - 64) return true;                                   // the generic learner cannot hold it at all
   return !force_generic && a.nd.n_params >= 512 && a.bs >= 32 && !a.ids;            // single steps and tiny networks (the README's 2-8-4) stay on the one-launch generic learner
 }
 
 // `strm` / `which`: the stream the chain runs on and the resource set it uses (0: the context's main stream; 1: the second learner stream -- policy_gradient_training runs the
 // critic's chain there, from a second host thread, beside the actor's: both chains are launch-bound, two queues interleave them on the device).
-int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int which) {
+// reg (or NULL): the DiagonalFisherRegularizer of this network (fisher.hip) -- per minibatch its gradient joins the pullback's before the norm and its value the info row's loss
+// (training.jl:13,19-20). The regulariser adds to every slot of the gradient, layer 0's included, so the pullback completes layer 0 itself (defer = nullptr, the replica
+// group's route): quarter partials that Sumsq2Op forms only afterwards would overwrite the regulariser's share of W_0, b_0.
+int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int which, const crux_fisher* reg) {
   if (!strm) strm = c->stream;
   void*& dtmp = which ? c->dense_tmp2 : c->dense_tmp; size_t& dtmp_bytes = which ? c->dense_tmp2_bytes : c->dense_tmp_bytes;
   crux_mlp* net = (crux_mlp*)a.host_net; const NetDesc& nd = net->nd; const int nout = nd.dims[nd.L], od = nd.dims[0];
@@ -251,11 +256,13 @@ int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int wh
       // (round 4) the fused pullback of layers 1 / 0 where it applies (dense_fused.h: three launches instead of five); it leaves layer 0's gradient as quarter partials that
       // Sumsq2Op completes -- not in a replica group, whose flat all-reduce reads the whole gradient before the norm
       const bool group = a.need_px && c->peer_n > 1; Sumsq2Fix fx{};
-      rc = crux_dense_backward(net, x, nb, dy, 1.0f, true, nullptr, strm, group ? nullptr : &fx, 0); if (rc) return rc;
+      rc = crux_dense_backward(net, x, nb, dy, 1.0f, true, nullptr, strm, (group || reg) ? nullptr : &fx, 0); if (rc) return rc;
       if (group)      // replica group: the gradient (and the statistics) of the GLOBAL minibatch, the same bits on every rank
         hipLaunchKernelGGL(k_px_allreduce_flat, dim3(1), dim3(1024), 0, strm, net->g, (int64_t)nd.n_params, st, (float* const*)(c->peer_tab + which * CRUX_PX_MAXR), c->peer_rank, c->peer_n, status, c->peer_timeout_ticks);
+      if (fisher_active(reg)) fisher_enqueue_reg(reg, true, strm);
       crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, strm, (float*)net->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
       hipLaunchKernelGGL(k_pg_info, dim3(1), dim3(1), 0, strm, (const double*)st, (const double*)ssq, nb, a.loss, a.head, a.lambda_p, a.lambda_e, (const float*)(net->p + nd.xoff), a.ad, dinfo, (const crux_lagrange*)a.lag);
+      if (fisher_active(reg)) fisher_enqueue_finish(reg, dinfo, strm);
       if (a.apply) { rc = adam_gated(net, ssq, status, true, strm); if (rc) return rc; }
       else hipLaunchKernelGGL(k_nan_status, dim3(1), dim3(1), 0, strm, (const double*)ssq, status);
       total_batches += 1; fresh = false;

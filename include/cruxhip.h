@@ -37,6 +37,7 @@ typedef struct crux_ctx crux_ctx;
 typedef struct crux_mlp crux_mlp;
 typedef struct crux_buffer crux_buffer;
 typedef struct crux_env crux_env;
+typedef struct crux_fisher crux_fisher;
 
 /* lifecycle --------------------------------------------------------------------------------- */
 /* stream: a hipStream_t to run on (e.g. torch's current stream) or NULL to create a private one. */
@@ -723,6 +724,32 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, floa
  * (act_dim B); the regularizer's gradient is added as crux_orthogonal_reg(accumulate) adds it, before the norm. Only the actor is updated. info_out: LOSS,
  * GRAD_NORM; adv_out (host [3]): mean D(s, pi(s)), mse, beta_orth reg. beta_orth = 0: no regularizer. One host synchronisation.                                 */
 int32_t crux_advil_actor_step(crux_mlp* actor, crux_mlp* D, crux_buffer* batch, float lambda_bc, float beta_orth, float* info_out, float* adv_out);
+
+/* DiagonalFisherRegularizer -- elastic weight consolidation (src/extras/fisher_information.jl), the driver's device half (src/extras/multitask_learning.jl) --------
+ * One regulariser belongs to one handle. Its parameter arrays are those of Flux.params in the handle's flat layout: W_0, b_0, ..., W_{L-1}, b_{L-1}, then the trailing
+ * extras (GaussianPolicy's logSigma) as ONE array when there are any; A = their number, numel_a the size of array a. All Float32.
+ * create = DiagonalFisherRegularizer(theta, lambda) (:8): F = 0, N = 0, theta_prev = copy(theta). get / set: host copies of F and theta_prev (n_params floats each) and
+ * of N (get synchronises and skips NULLs; set: NULL = keep, N < 0 = keep, lambda always taken: checkpoints, tests).
+ * add = add_fisher_information_diagonal! (:20-28) with g = the handle's gradient buffer as it stands (the gradient of the batch loss, squared -- not a per-sample
+ * square): `times` times in one launch, N += 1; F = F + (g g - F) / Float32(N), every operation rounded to nearest -- bit for bit numpy's Float32 expression.
+ * update_fisher! (:30-38) evaluates the loss of the whole buffer in every partition, so one gradient is added n_partitions times; snapshot = its last line,
+ * theta_prev = copy(theta). add and snapshot only enqueue.
+ * reg = R(pi) (:10-18) = lambda / A sum_a mean_a(F (theta - theta_prev)^2): every array's mean with its own divisor, Float32 terms, Float64 sums combined in a fixed
+ * order (identical calls give identical bits, no float atomics). *value_out (host) = the value; accumulate != 0: 2 lambda / (A numel_a) F_i (theta_i - theta_prev_i)
+ * is ADDED to every slot of the handle's gradient buffer (as the orthogonal regulariser above adds its own). lambda = 0: value 0, gradient untouched. One synchronisation.
+ * batch_train_fisher = batch_train!(pi, loss + R) (src/training.jl:13,28-55): crux_batch_train with R evaluated inside the dense-engine learner's chain of
+ * every minibatch -- R's gradient joins the pullback's before the norm and the NaN check (:19-20), R's value the reported loss (:13); two more launches per
+ * minibatch, no host round trip. Losses: CRUX_LOSS_PPO, _A2C, _VALUE_MSE, _MSE_ACTION (no squash), on every network shape and minibatch size.
+ * CRUX_EUNSUP: a handle with DenseSN layers; while a fused sequence is recorded; (batch_train_fisher) a replica group is attached, R belongs to another handle, any
+ * other loss -- the caller falls back to evaluating reg(accumulate) between its own gradient and update calls.                                                   */
+int32_t crux_fisher_create(crux_mlp* net, float lambda, crux_fisher** out);
+int32_t crux_fisher_destroy(crux_fisher* R);
+int32_t crux_fisher_get(crux_fisher* R, float* host_F, float* host_theta_prev, int64_t* N_out);
+int32_t crux_fisher_set(crux_fisher* R, const float* host_F, const float* host_theta_prev, int64_t N, float lambda);
+int32_t crux_fisher_add(crux_fisher* R, int32_t times);
+int32_t crux_fisher_snapshot(crux_fisher* R);
+int32_t crux_fisher_reg(crux_fisher* R, int32_t accumulate, float* value_out);
+int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos);
 
 /* ASAF (src/model_free/il/asaf.jl) on the dense engine ------------------------------------------------------------------------------------------------------------
  * The policy is its own discriminator against a frozen copy piG of itself (deepcopy in post_batch_callback, asaf.jl:57: once per iteration, after sampling and

@@ -586,6 +586,36 @@ function orthogonal_reg!(π::HipNetwork, β::Float32; accumulate::Bool=false)   
     check(π.ctx, ccall((:crux_orthogonal_reg, LIB), Int32, (Ptr{Cvoid}, Float32, Int32, Ptr{Float32}), π.h, β, Int32(accumulate), out))
     out[1]
 end
+# DiagonalFisherRegularizer (src/extras/fisher_information.jl) on the device: F, θ⁻ and N live beside the handle; as the regulariser of batch_train! it rides in the dense-engine learner's chain
+mutable struct HipFisher
+    h::Ptr{Cvoid}; π::HipNetwork
+end
+function HipFisher(π::HipNetwork, λ::Float32=1f0)                                                                                            # DiagonalFisherRegularizer(θ, λ): F = 0, N = 0, θ⁻ = copy(θ)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(π.ctx, ccall((:crux_fisher_create, LIB), Int32, (Ptr{Cvoid}, Float32, Ref{Ptr{Cvoid}}), π.h, λ, h))
+    R = HipFisher(h[], π)
+    finalizer(r -> ccall((:crux_fisher_destroy, LIB), Int32, (Ptr{Cvoid},), r.h), R)
+end
+function fisher_state(R::HipFisher, n::Integer)                                                                                              # (F, θ⁻, N) as host copies; n = length of the flat parameter vector
+    F = zeros(Float32, n); θ⁻ = zeros(Float32, n); N = Ref{Int64}(0)
+    check(R.π.ctx, ccall((:crux_fisher_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Int64}), R.h, F, θ⁻, N))
+    F, θ⁻, N[]
+end
+fisher_set!(R::HipFisher, F::Vector{Float32}, θ⁻::Vector{Float32}, N::Integer, λ::Float32) =
+    check(R.π.ctx, ccall((:crux_fisher_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int64, Float32), R.h, F, θ⁻, Int64(N), λ))
+fisher_add!(R::HipFisher; times::Integer=1) = check(R.π.ctx, ccall((:crux_fisher_add, LIB), Int32, (Ptr{Cvoid}, Int32), R.h, Int32(times)))       # add_fisher_information_diagonal! with the handle's gradient buffer
+fisher_snapshot!(R::HipFisher) = check(R.π.ctx, ccall((:crux_fisher_snapshot, LIB), Int32, (Ptr{Cvoid},), R.h))                                # θ⁻ = copy(θ)
+function fisher_reg!(R::HipFisher; accumulate::Bool=false)                                                                                   # R(π); accumulate: ∇ += 2λ/(A numel_a) F (θ - θ⁻)
+    out = zeros(Float32, 1)
+    check(R.π.ctx, ccall((:crux_fisher_reg, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}), R.h, Int32(accumulate), out))
+    out[1]
+end
+function batch_train_fisher!(π::HipNetwork, R::HipFisher, cfg::TrainCfg, 𝒟::HipBuffer, info=zeros(Float32, INFO_N))                            # batch_train!(π, loss + R); EUNSUP: fall back to fisher_reg!(accumulate=true) per step
+    rc = ccall((:crux_batch_train_fisher, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{TrainCfg}, Ptr{Int64}, Ptr{Float32}, Ptr{Float32}), π.h, R.h, 𝒟.h, cfg, C_NULL, info, C_NULL)
+    rc == EUNSUP && return nothing
+    check(π.ctx, rc)
+    info
+end
 function advil_d_step!(A::HipNetwork, D::HipNetwork, mb::HipBuffer, λ_GP::Float32, seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N); target::Float32=0.4f0)   # train!(critic(π), advil_d_loss)
     adv = zeros(Float32, 4)                                                                                                                  # mean D(expert), mean D(π), P, λ_GP P
     check(D.ctx, ccall((:crux_advil_d_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, UInt64, UInt64, Ptr{Float32}, Ptr{Float32}),
