@@ -65,7 +65,7 @@ def c3(crux, ctx, cpu=True, steps=300):
         k[0] += EP
         ctx.check(ctx.lib.crux_dqn_epochs(q.h, qm.h, buf.h, D.h, 0.99, 1, 0.5, k[0], EP, raw.ctypes.data_as(L.vp)))
     t = _timed(ctx, iteration, max(1, steps // EP)) / EP
-    # the same chains through the entry point solve() uses (crux_dqn_epochs_async: no read-back, no synchronisation between the calls -- the host records chain k + 1
+    # the same chains through the entry point solve() uses (crux_dqn_value_training_async: no read-back, no synchronisation between the calls -- the host records chain k + 1
     # while the device runs chain k): what an epoch costs when the host is out of the loop
     d_rows = ctx.alloc(4 * L.INFO_N * EP)
     def iteration_async():
@@ -119,7 +119,7 @@ def c3(crux, ctx, cpu=True, steps=300):
 
 def c3_solve(crux, ctx, iters=600, ring=1_000_000):
     """Whole solve(DQN + prioritized replay) iterations at the C3 shapes and at the ring size BASELINE names (1 M transitions, full): steps! of dN = 4 environment steps with
-    eps-greedy exploration, push! with max priority, four value_training epochs, polyak. The iteration loop enqueues every chain without waiting for it (crux_dqn_epochs_async) --
+    eps-greedy exploration, push! with max priority, four value_training epochs, polyak. The iteration loop enqueues every chain without waiting for it (crux_dqn_value_training_async) --
     wall time per iteration. The ring is filled once with synthetic transitions and a non-trivial priority landscape (a 1 M-step rollout of one environment would only add
     seconds to the run; the iterations timed afterwards are the same)."""
     mdp = crux.SynthMDP(8, 4, discrete=True, n_envs=1, seed=3)

@@ -195,6 +195,31 @@ static inline NetPlan net_plan(const crux_mlp* n, int64_t B) { const int L = n->
 #define PH_SEQ_HEAD (1 << 12)
 #define PH_SEQ_TAIL (2 << 12)
 static inline int ph_tag(int p_mapped, int sub) { return 4 * p_mapped + sub; }
+// What the generic SAC and DDPG / TD3 epoch plans share (SacRun::one, DpgRun::one draw the phase tables). Written in launches: FA / FQ forward launches of the actor / a
+// critic, BQ / BA phases of a pullback with parameter gradients (BQo ops per critic), DQ phases of a critic's input-gradient chain; with the fused block kernels FA = FQ = L - 1
+// and BQ = BA = L - 1 (net_plan above), otherwise all equal L. X = the target's phase, Y = the first phase of the actor step's critic passes. sq: the target (one block at
+// B <= 256) and the critic heads (one block each) form a sequential group in ONE block of phase X when the critics train; the critic chain and all behind it (Y ..) sit one earlier.
+struct ActorCriticPlan {
+  NetPlan pa, pq; int64_t B; int LA, LQ, FA, FQ, BQ, BQo, BA, DQ, sq, X, Y;
+  ActorCriticPlan(const crux_mlp* actor, const crux_mlp* q1, int64_t B_, bool update_critic) : pa(net_plan(actor, B_)), pq(net_plan(q1, B_)), B(B_), LA(actor->nd.L), LQ(q1->nd.L),
+    FA(pa.nf), FQ(pq.nf), BQ(pq.nb), BQo(pq.nbops), BA(pa.nb), DQ(pq.dq), sq((update_critic && B_ <= 256) ? 1 : 0), X(3 + FA + FQ), Y(X + 4 + BQ - sq) {}
+  // the plan holds for networks of one depth and one launch count: the second critic (NULL: none) like the first, the target critics' forward passes like a critic's
+  bool ok(const crux_mlp* q2, const crux_mlp* q1t, const crux_mlp* q2t) const {
+    if (LA != LQ || FA != FQ || q1t->nd.L != LQ || net_plan(q1t, B).nf != FQ) return false;
+    if (q2 && (q2->nd.L != LQ || net_plan(q2, B).nf != FQ || net_plan(q2, B).nb != BQ)) return false;
+    return !(q2t && (q2t->nd.L != LQ || net_plan(q2t, B).nf != FQ)); }
+  // rand!: 0 ids | 1 gather
+  static int sampling(int kid) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; }
+  // the target: 2.. actor(sp) forward | 2+FA the next action (action_op) | 3+FA.. target Q1 || Q2 forward | X the target itself (target_op), head of the sequential group
+  int target(int kid, int& g, int action_op, int target_op) const {
+    if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
+    return kid == action_op ? 2 + FA : kid == target_op ? X | (sq ? PH_SEQ_HEAD : 0) : -1; }
+  // the critic step, per critic: FQ forward launches, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
+  int critic(int kid, int& g) const {
+    if (kid == OP_FILL) return 1; if (kid == OP_CONCAT_SA) return 2;
+    if (is_mm(kid)) { const int k = (g++) % (FQ + BQo); return k < FQ ? 3 + k : X + 2 - sq + pq.stage(k - FQ); }
+    return kid == OP_Q_HEAD ? (sq ? (X | PH_SEQ_TAIL) : X + 1) : kid == OP_SUMSQ2 ? X + 2 - sq + BQ : (kid == OP_CRITIC_INFO || kid == OP_ADAM_GATED) ? X + 3 - sq + BQ : kid == OP_ADAM_ADVANCE ? X + 4 - sq + BQ : -1; }
+};
 
 int32_t crux_exec_run(crux_ctx* c) {
   ExecRec* r = rec_of(c);
@@ -336,28 +361,44 @@ static int32_t run_epoch_chains(crux_ctx* c, const char* who, bool chain, crux_b
   if (r->ops.size() > n0) r->chain_tags.insert(r->chain_tags.end(), r->ops.size() - n0, last_phase());
   return flush();
 }
-// More than one chain per call (n_epochs > 8): run(d_rows) runs the chains back to back in their asynchronous form, with the info rows in a device block of the
+// One value_training call of a family. Run (DqnRun, SacRun, DpgRun below) holds the call's networks, buffers, hyper-parameters, counters and epoch range, and offers valid()
+// (the argument check: CRUX_EINVAL), chain(), per(), tail(), rows(e), shift(e) (what run_epoch_chains asks for) and epoch(e, host_rows), which records epoch e (call by call:
+// runs it) with info row k going to host_rows[k] + e * CRUX_INFO_N. d_rows: the asynchronous form; otherwise host_rows[k]: host [n_epochs x CRUX_INFO_N] or NULL.
+// More than one chain per call (n_epochs > 8, Run::ONE_READBACK): the chains run back to back in their asynchronous form, with the info rows in a device block of the
 // context, and the host synchronises ONCE, at the end of the call: the device no longer idles while the host reads back, records and uploads the next chain (C4, 50
-// epochs per call: 180 -> ~155 us per epoch). Same results; a NaN gradient norm is reported from the rows. has(e) and dst[k] (host [n_epochs x CRUX_INFO_N] or NULL):
-// the rows of epoch e (see run_epoch_chains) and where row k goes.
-template <class Run, class Has>
-static int32_t epochs_one_readback(crux_ctx* c, const char* who, const char* family, int32_t n_epochs, int nrows, float* const* dst, Run&& run, Has&& has) {
-  const size_t need = sizeof(float) * nrows * CRUX_INFO_N * (size_t)n_epochs;
+// epochs per call: 180 -> ~155 us per epoch). Same results; a NaN gradient norm is reported from the rows.
+template <class Run> static int32_t run_family(const Run& run, float* const* host_rows, float* d_rows) {
+  if (!run.valid()) return CRUX_EINVAL;
+  crux_ctx* c = run.ctx(); constexpr int NR = Run::NROWS; const int32_t n_epochs = run.n_epochs;
+  auto chains = [&](float* const* hr, float* dr) {
+    return run_epoch_chains(c, Run::who, run.chain(), run.per(), n_epochs, NR, dr,
+      [&](int e) {      // shift < 0, asynchronous: the epoch's info op writes the caller's row itself (no copy op)
+        float* row = (dr && run.shift(e) < 0) ? dr + (size_t)e * NR * CRUX_INFO_N : nullptr;
+        if (row) rec_of(c)->info_row_override = row;
+        const int32_t rc = run.epoch(e, hr);
+        if (row) rec_of(c)->info_row_override = nullptr;
+        return rc; },
+      [&](int e) { return EpochRows{run.rows(e), run.shift(e)}; }, [&] { return run.tail(); }); };
+  static float* const none[NR] = {};
+  if (d_rows) return chains(none, d_rows);
+  if (!(Run::ONE_READBACK && n_epochs > 8 && run.chain() && !crux_sw().sync_chains)) return chains(host_rows, nullptr);
+  const size_t need = sizeof(float) * NR * CRUX_INFO_N * (size_t)n_epochs;
   if (c->epoch_rows_bytes < need) { if (c->epoch_rows) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->epoch_rows); c->epoch_rows = nullptr; c->epoch_rows_bytes = 0; }
-    if (hipMalloc(&c->epoch_rows, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "%s epochs: info rows", who); c->epoch_rows_bytes = 2 * need; }
+    if (hipMalloc(&c->epoch_rows, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "%s epochs: info rows", Run::who); c->epoch_rows_bytes = 2 * need; }
   HIPCHK(c, hipMemsetAsync(c->epoch_rows, 0, need, c->stream));
-  const int32_t rc = run((float*)c->epoch_rows); if (rc) return rc;
-  std::vector<float> rows((size_t)nrows * CRUX_INFO_N * (size_t)n_epochs);
+  const int32_t rc = chains(none, (float*)c->epoch_rows); if (rc) return rc;
+  std::vector<float> rows((size_t)NR * CRUX_INFO_N * (size_t)n_epochs);
   HIPCHK(c, hipMemcpyAsync(rows.data(), c->epoch_rows, need, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
   bool nan = false;
-  for (int e = 0; e < n_epochs; ++e) { const unsigned h = has(e);
-    for (int k = 0; k < nrows; ++k) { if (!(h >> k & 1)) continue;
-      const float* row = rows.data() + ((size_t)e * nrows + k) * CRUX_INFO_N;
+  for (int e = 0; e < n_epochs; ++e) { const unsigned h = run.rows(e);
+    for (int k = 0; k < NR; ++k) { if (!(h >> k & 1)) continue;
+      const float* row = rows.data() + ((size_t)e * NR + k) * CRUX_INFO_N;
       if (row[CRUX_INFO_GRAD_NORM] != row[CRUX_INFO_GRAD_NORM]) nan = true;
-      if (dst[k]) memcpy(dst[k] + (size_t)e * CRUX_INFO_N, row, sizeof(float) * CRUX_INFO_N); } }
-  if (nan) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in the %s epochs", family);
+      if (host_rows[k]) memcpy(host_rows[k] + (size_t)e * CRUX_INFO_N, row, sizeof(float) * CRUX_INFO_N); } }
+  if (nan) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in the %s epochs", Run::family);
   return CRUX_OK;
 }
+static inline float* info_row(float* const* host_rows, int k, int e) { return host_rows[k] ? host_rows[k] + (size_t)e * CRUX_INFO_N : nullptr; }
 // c->epoch_tmp with at least `bytes` (targets and td errors of the epochs run call by call: a block of the context that no recording carves)
 static int32_t grow_epoch_tmp(crux_ctx* c, size_t bytes, int64_t B, const char* who) {
   if (c->epoch_tmp_bytes >= bytes) return CRUX_OK;
@@ -386,7 +427,6 @@ extern "C" {
 int32_t crux_per_sample(crux_buffer* target, crux_buffer* source, int64_t B, const double* rands, float beta, uint64_t i);
 int32_t crux_uniform_sample(crux_buffer* target, crux_buffer* source, int64_t B, const int64_t* ids, uint64_t i);
 int32_t crux_dqn_target(crux_mlp* tn, crux_buffer* batch, float gamma, float* d_y);
-int32_t crux_softq_target(crux_mlp* tn, crux_buffer* batch, float gamma, float alpha, float* d_y);
 int32_t crux_td_step(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out);
 int32_t crux_td_step_with_error(crux_mlp* net, crux_buffer* batch, const float* d_y, int32_t use_weight, float* d_err, float* info_out);
 int32_t crux_per_update_device(crux_buffer* b, const int64_t* d_ids, const float* d_v, int64_t n);
@@ -397,9 +437,7 @@ int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
 //   update_priorities! per 16-sample tile | 4 the whole pullback ; leaf re-sums | 5 norm ; root paths | 6 info, Adam | 7 beta-power advance
 // In a chain the sampling of epoch e + 1 (phases 0, 1) sits beside the norm and Adam of epoch e -- after the root paths of phase 5 --, its phase 2 beside the advance.
 // does the network pair take the recorded chain of crux_dqn_epochs* (wide enough for the dense engine; fused and chained epochs not switched off)?
-static bool dqn_chain_case(const crux_mlp* net, const crux_mlp* tnet) {
-  return net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && tnet->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
-}
+static bool dqn_chain_case(const crux_mlp* net, const crux_mlp* tnet) { return net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && tnet->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs; }
 static bool dqn_tile_case(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, crux_buffer* batch) {
   const bool on = crux_sw().sac_tile_ops && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
   const int64_t B = batch->capacity;
@@ -410,8 +448,26 @@ static bool dqn_tile_case(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, cr
   if (!crux_dense_bwd_fused3(net, B)) return false;
   return batch->act_kind == CRUX_ACTION_DISCRETE && batch->act_dim == net->nd.dims[3] && net->nd.dims[3] <= 4;
 }
-static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                               uint64_t sample_counter, float* info_out, float* d_y, float* d_err) {
+// One value_training call of the DQN family (see run_family). The target function is named, not inferred from alpha; DqnTdArgs::softq_alpha keeps its convention on the
+// device (0 = dqn_target): device_alpha().
+struct DqnRun {
+  enum Target { TARGET_DQN, TARGET_SOFTQ };
+  crux_mlp *net, *target_net; crux_buffer *source, *batch; float gamma; Target target; float alpha; int32_t use_weight; float beta; uint64_t sample_counter0; int32_t n_epochs;
+  float polyak_tau;      // >= 0: polyak_average!(target_net, net, tau) behind the last epoch (tail)
+  static constexpr int NROWS = 1; static constexpr bool ONE_READBACK = false; static constexpr const char *who = "dqn", *family = "DQN";
+  float device_alpha() const { return target == TARGET_SOFTQ ? alpha : 0.f; }
+  bool valid() const { return net && target_net && source && batch && n_epochs >= 1; }
+  crux_ctx* ctx() const { return net->ctx; }      bool chain() const { return dqn_chain_case(net, target_net); }
+  crux_buffer* per() const { return source->prioritized ? source : nullptr; }      unsigned rows(int) const { return 1u; }
+  int shift(int) const { return chain() && dqn_tile_case(net, target_net, source, batch) ? -1 : 0; }      // tile plan: the info op writes the caller's row itself
+  // polyak_average!(pi_minus, pi, tau) after the epoch loop (off_policy.jl:108: the DQN family updates its target once per value_training call) as an op of the chain: it needs
+  // the last epoch's Adam (phase 5) and shares the launch of that epoch's info / beta-power phase -- the stand-alone PolyakOp launch (~5 us of a 230 us C3 iteration) is gone.
+  int32_t tail() const { return polyak_tau >= 0.f ? crux_polyak(target_net, net, polyak_tau) : CRUX_OK; }
+  int32_t epoch(int e, float* const* host_rows) const;
+  int32_t epoch_tiles(uint64_t sample_counter, float* info_out, float* d_y, float* d_err) const;      // the chained C3 family
+};
+int32_t DqnRun::epoch_tiles(uint64_t sample_counter, float* info_out, float* d_y, float* d_err) const {      // (the tile plan other files call dqn_epoch_tiles)
+  crux_mlp* const tnet = target_net; const float softq_alpha = device_alpha();
   crux_ctx* c = net->ctx; const int64_t B = batch->capacity; const bool per = source->prioritized; const int nout = net->nd.dims[3], K = net->nd.dims[2];
   int32_t rc;
   // Phases: 0 uniform ids | 1 search + gather / gather | 2 forward (both nets) | 3 td tile (+ update_priorities!) | 4 pullback || leaf re-sum -> root paths (LeafTouchOp) |
@@ -460,9 +516,9 @@ static int32_t dqn_epoch_tiles(crux_mlp* net, crux_mlp* tnet, crux_buffer* sourc
 // One epoch of value_training for the DQN family (src/model_free/off_policy.jl:69-93 with dqn_target, rl/dqn.jl:4-6): rand!(batch, source; i) ->
 // y = target(pi_minus, batch) -> [td_error -> update_priorities!(source, batch.indices, .)] -> train!(pi, td_loss). Networks at least
 // CRUX_DENSE_MIN_WIDTH wide run the whole epoch as ONE fused launch; narrower ones take the same steps one call at a time.
-static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                       uint64_t sample_counter, float* info_out) {
+int32_t DqnRun::epoch(int e, float* const* host_rows) const {
   if (!net || !target_net || !source || !batch) return CRUX_EINVAL;
+  const uint64_t sample_counter = sample_counter0 + (uint64_t)e; float* info_out = info_row(host_rows, 0, e);
   crux_ctx* c = net->ctx; const int64_t B = batch->capacity;
   const bool per = source->prioritized;
   const bool fuse = net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && target_net->nd.maxdim >= CRUX_DENSE_MIN_WIDTH && !crux_sw().no_fused_epoch;
@@ -471,7 +527,7 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
   rc = grow_epoch_tmp(c, 8 * (size_t)B + 512, B, "dqn_epoch"); if (rc) return rc;      // targets and td errors
   float* d_y = (float*)c->epoch_tmp; float* d_err = (float*)((char*)c->epoch_tmp + ((4 * (size_t)B + 255) / 256) * 256);
   if (fuse && c->rec && rec_of(c)->chain && crux_exec_recording(c) && dqn_tile_case(net, target_net, source, batch))      // chained epochs of the C3 family: the tile op (5 launches per epoch)
-    return dqn_epoch_tiles(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter, info_out, d_y, d_err);
+    return epoch_tiles(sample_counter, info_out, d_y, d_err);
   auto bail = [&](int32_t e) { if (fuse) crux_exec_abort(c); return e; };
   // Phase plan of the fused epoch (L = number of Dense layers): the target network's forward chain runs beside the online network's, the replay
   // bookkeeping beside the backward chain.    0 search | 1 gather, ring ids, zero-fill | 2+k forward layer k (both nets; + push! priorities of the batch)
@@ -507,7 +563,7 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
   if (crux_dense_fwd_fused(target_net) != ffw || target_net->nd.L != net->nd.L) tg.plan_ok = false;
   rc = per ? crux_per_sample(batch, source, B, nullptr, beta, sample_counter) : crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
   tg.tag([&](int kid, int&) { return (kid == OP_PER_SEARCH || kid == OP_UNIFORM_IDS) ? 0 : (kid == OP_PER_SAMPLE || kid == OP_GATHER_RING_ALL || kid == OP_RING_IDS || kid == OP_COPY_F32) ? 1 : kid == OP_PER_UPDATE ? 2 : -1; });
-  rc = softq_alpha > 0.f ? crux_softq_target(target_net, batch, gamma, softq_alpha, d_y) : crux_dqn_target(target_net, batch, gamma, d_y); if (rc) return bail(rc);      // softq_target(alpha) (rl/softq.jl:4-13) | dqn_target (rl/dqn.jl:4-6)
+  rc = target == TARGET_SOFTQ ? crux_softq_target(target_net, batch, gamma, alpha, d_y) : crux_dqn_target(target_net, batch, gamma, d_y); if (rc) return bail(rc);      // softq_target(alpha) (rl/softq.jl:4-13) | dqn_target (rl/dqn.jl:4-6)
   tg.tag([&](int kid, int& g) { if (kid == OP_FWD12) { g = 1; return 2; }
     return kid == OP_GEMM ? (g < nf ? 2 + g++ : -1) : (kid == OP_DQN_TARGET || kid == OP_SOFTQ_TARGET) ? (2 + nf) | (sq ? PH_SEQ_HEAD : 0) : -1; });
   auto td_rule = [&](int kid, int& g) {      // g counts the GEMMs: Ld forward, then (weight, data) pairs from the last layer down, the first layer has no data gradient
@@ -528,63 +584,34 @@ static int32_t dqn_epoch_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* 
 }
 
 int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                       uint64_t sample_counter, float* info_out) { CRUX_PLAIN_ONLY("crux_dqn_epoch", net, target_net); return dqn_epoch_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter, info_out); }
-
+                       uint64_t sample_counter, float* info_out) { CRUX_PLAIN_ONLY("crux_dqn_epoch", net, target_net);
+  return DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_DQN, 0.f, use_weight, beta, sample_counter, 1, -1.f}.epoch(0, &info_out);
+}
 // value_training's epoch loop (off_policy.jl:69: `for epoch in 1:c_opt.epochs`) for the DQN family as ONE recorded list: the n epochs are recorded back to back, the
 // phases of epoch e follow those of epoch e - 1, and the host uploads, launches and reads back once. Epoch e draws with sample counter sample_counter0 + e; beta is
 // the iteration's (rand!(…, i = S.i)). infos: host [n x CRUX_INFO_N]. Falls back to n single-epoch calls wherever an epoch cannot be chained (narrow networks, a
 // priority tree that needs a full rebuild between epochs).
-static int32_t dqn_epochs_impl(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                               uint64_t sample_counter0, int32_t n_epochs, float* infos, float* d_infos_async = nullptr, float polyak_tau = -1.f) {
-  if (!net || !target_net || !source || !batch || n_epochs < 1) return CRUX_EINVAL;
-  crux_ctx* c = net->ctx;
-  const bool fuse = dqn_chain_case(net, target_net), tiles = fuse && dqn_tile_case(net, target_net, source, batch);
-  auto record = [&](int e) {      // tile plan, asynchronous: the info op writes the caller's row itself (no copy op)
-    float* row = (d_infos_async && tiles) ? d_infos_async + (size_t)e * CRUX_INFO_N : nullptr;
-    if (row) rec_of(c)->info_row_override = row;
-    const int32_t rc = dqn_epoch_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0 + (uint64_t)e, infos ? infos + (size_t)e * CRUX_INFO_N : nullptr);
-    if (row) rec_of(c)->info_row_override = nullptr;
-    return rc;
-  };
-  // polyak_average!(pi_minus, pi, tau) after the epoch loop (off_policy.jl:108: the DQN family updates its target once per value_training call) as an op of the chain: it needs
-  // the last epoch's Adam (phase 5) and shares the launch of that epoch's info / beta-power phase -- the stand-alone PolyakOp launch (~5 us of a 230 us C3 iteration) is gone.
-  return run_epoch_chains(c, "dqn", fuse, source->prioritized ? source : nullptr, n_epochs, 1, d_infos_async, record, [&](int) { return EpochRows{1u, tiles ? -1 : 0}; },
-                          [&]() { return polyak_tau >= 0.f ? crux_polyak(target_net, net, polyak_tau) : CRUX_OK; });
-}
 int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
                         uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs", net, target_net);
-  return dqn_epochs_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter0, n_epochs, infos);
+  return run_family(DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_DQN, 0.f, use_weight, beta, sample_counter0, n_epochs, -1.f}, &infos, nullptr);
 }
 // the same loop with softq_target(alpha) (rl/softq.jl:4-13) in place of dqn_target: SoftQ's value_training
-// The same chain WITHOUT the host: nothing is read back and nothing is waited for; the info row of epoch e lands in d_infos[e] (device, [n_epochs x CRUX_INFO_N]) when
-// the device gets there. For the iteration loop of solve(::OffPolicySolver) (off_policy.jl:133-147): the host records and enqueues the next iteration's steps! and
-// value_training while the device runs this one. A NaN gradient norm shows as a NaN in the info row (the update is skipped on the device as always, training.jl:20);
-// CRUX_EUNSUP for networks that do not take the recorded form (the caller uses crux_dqn_epochs).
-int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                              uint64_t sample_counter0, int32_t n_epochs, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs_async", net, target_net);
-  if (!d_infos) return CRUX_EINVAL;
-  if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
-  return dqn_epochs_impl(net, target_net, source, batch, gamma, 0.f, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
+int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
+                          uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_softq_epochs", net, target_net);
+  if (!(alpha > 0.f)) return CRUX_EINVAL;
+  return run_family(DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_SOFTQ, alpha, use_weight, beta, sample_counter0, n_epochs, -1.f}, &infos, nullptr);
 }
-// value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111 with :108), without the host: the chain of crux_dqn_epochs_async (softq_alpha > 0:
-// crux_softq_epochs_async) with polyak_average!(target_net, net, tau) riding in the last epoch's final phase. tau < 0: no target update (== the plain async entries).
+// value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111 with :108) WITHOUT the host, for the iteration loop of solve(::OffPolicySolver): nothing
+// is read back or waited for; the info row of epoch e lands in d_infos[e] (device, [n_epochs x CRUX_INFO_N]) when the device gets there (a NaN gradient norm shows there), and
+// polyak_average!(target_net, net, tau) rides in the last epoch's final phase (tau < 0: none). softq_alpha == 0 selects dqn_target, > 0 softq_target(alpha): a SoftQ caller
+// must pass alpha > 0. CRUX_EUNSUP for networks that do not take the recorded form (the caller uses crux_dqn_epochs / crux_softq_epochs).
 int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
                                       uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_value_training_async", net, target_net);
   if (!d_infos || softq_alpha < 0.f || tau > 1.f) return CRUX_EINVAL;
   if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   if (tau >= 0.f && net->nd.n_params != target_net->nd.n_params) return crux_fail(net->ctx, CRUX_EINVAL, "value_training: polyak_average! needs equal parameter counts");
-  return dqn_epochs_impl(net, target_net, source, batch, gamma, softq_alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos, tau);
-}
-int32_t crux_softq_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                                uint64_t sample_counter0, int32_t n_epochs, float* d_infos) { CRUX_PLAIN_ONLY("crux_softq_epochs_async", net, target_net);      // crux_softq_epochs without the host in the loop (see crux_dqn_epochs_async)
-  if (!d_infos || !(alpha > 0.f)) return CRUX_EINVAL;
-  if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
-  return dqn_epochs_impl(net, target_net, source, batch, gamma, alpha, use_weight, beta, sample_counter0, n_epochs, nullptr, d_infos);
-}
-int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                          uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_softq_epochs", net, target_net);
-  if (!(alpha > 0.f)) return CRUX_EINVAL;
-  return dqn_epochs_impl(net, target_net, source, batch, gamma, alpha, use_weight, beta, sample_counter0, n_epochs, infos);
+  const DqnRun run{net, target_net, source, batch, gamma, softq_alpha > 0.f ? DqnRun::TARGET_SOFTQ : DqnRun::TARGET_DQN, softq_alpha, use_weight, beta, sample_counter0, n_epochs, tau};
+  return run_family(run, nullptr, d_infos);
 }
 
 int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1t, crux_mlp* q2t, crux_mlp* la, crux_buffer* b, float gamma, uint64_t seed, uint64_t counter, float* d_y);
@@ -604,7 +631,25 @@ int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* b, float*
 //   11 critic input gradients down to layer 0's dZ | 12 layer 0's W' dZ + reverse of exploration | 13 actor pullback ; logSigma row sums | 14 norm | 15 info, Adam | 16 advance, polyak
 // The order inside every chain is the reference's (temperature, critic and actor each see what the previous step left; sac_target reads log alpha BEFORE the temperature
 // update lands, the actor head after). Same arithmetic as the generic recording below (tools/fused_check.py compares the two bit for bit); false = not this case.
-static bool sac_tile_case(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* q1t, crux_mlp* q2t, crux_buffer* source, crux_buffer* batch, int32_t uc, int32_t ua) {
+struct SacRun {      // one value_training call with SAC's pieces (crux_sac_epoch, crux_sac_epochs[_async]): see run_family
+  crux_mlp *actor, *q1, *q2, *actor_targ, *q1_targ, *q2_targ, *log_alpha; crux_buffer *source, *batch; float gamma, H_target, tau; int32_t use_weight, epoch0, n_epochs, critic_every, actor_every;
+  uint64_t sample_counter0, noise_seed, noise_counter0;
+  static constexpr int NROWS = 3; static constexpr bool ONE_READBACK = true; static constexpr const char *who = "sac", *family = "SAC";
+  bool valid() const { return actor && q1 && q2 && q1_targ && q2_targ && log_alpha && source && batch && n_epochs >= 1 && critic_every >= 1 && actor_every >= 1; }
+  crux_ctx* ctx() const { return actor->ctx; }      crux_buffer* per() const { return nullptr; }      int32_t tail() const { return CRUX_OK; }
+  bool chain() const { return !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs; }
+  bool uc(int e) const { return (epoch0 + e) % critic_every == 0; }      bool ua(int e) const { return (epoch0 + e) % actor_every == 0; }
+  // rows 3 e .. 3 e + 2: temperature, [critics], [actor]. Tile plans: the actor's info op sits IN the epoch's last phase -- the copies join the launch after it, the next epoch's third
+  unsigned rows(int e) const { return 1u | (uc(e) ? 2u : 0u) | (ua(e) ? 4u : 0u); }
+  int shift(int e) const { return tile_case(uc(e), ua(e)) ? 4 : 0; }
+  int32_t epoch(int e, float* const* host_rows) const {
+    return one(uc(e), ua(e), sample_counter0 + (uint64_t)e, noise_counter0 + 3ull * (uint64_t)e, info_row(host_rows, 0, e), info_row(host_rows, 1, e), info_row(host_rows, 2, e)); }
+  int32_t one(int32_t update_critic, int32_t update_actor, uint64_t sample_counter, uint64_t noise_counter, float* info_temp, float* info_critic, float* info_actor) const;
+  bool tile_case(int32_t uc, int32_t ua) const;
+  int32_t epoch_tiles(uint64_t sample_counter, uint64_t noise_counter, float* info_temp, float* info_critic, float* info_actor) const;
+};
+bool SacRun::tile_case(int32_t uc, int32_t ua) const {
+  crux_mlp* const q1t = q1_targ, * const q2t = q2_targ;
   const bool on = crux_sw().sac_tile_ops && !crux_sw().no_fused_epoch;      // (read per call: tests switch forms inside one process)
   if (!on || !uc || !ua || source->prioritized) return false;
   const int64_t B = batch->capacity; crux_mlp* all[5] = {actor, q1, q2, q1t, q2t};
@@ -614,9 +659,8 @@ static bool sac_tile_case(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp*
   if (q1t->nd.dims[3] != 1 || q2t->nd.dims[3] != 1 || q1->nd.dims[0] != batch->obs_dim + batch->act_dim) return false;
   return true;
 }
-static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1t, crux_mlp* q2t, crux_mlp* la, crux_buffer* source, crux_buffer* batch,
-                               float gamma, float H_target, float tau, int32_t use_weight, uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0,
-                               float* info_temp, float* info_critic, float* info_actor) {
+int32_t SacRun::epoch_tiles(uint64_t sample_counter, uint64_t noise_counter, float* info_temp, float* info_critic, float* info_actor) const {      // (the tile plan other files call sac_epoch_tiles)
+  crux_mlp* const q1t = q1_targ, * const q2t = q2_targ, * const la = log_alpha;
   crux_ctx* c = actor->ctx; const int64_t B = batch->capacity; const int od = batch->obs_dim, ad = batch->act_dim, sd = od + ad, K = actor->nd.dims[2];
   int32_t rc = CRUX_OK;
   if (use_weight && !has_col(batch, CRUX_COL_WEIGHT)) return crux_fail(c, CRUX_EINVAL, "double_Q_loss(weight=:weight): batch has no :weight column");
@@ -652,7 +696,7 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
   CRUX_RUN(c, ConcatSaOp, nblk(B * sd), 256, c->stream, S, (const float*)batch->col[CRUX_COL_A], od, ad, B, sa_c);
   tg.only(2);
   // 3
-  { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = SP; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed; a.cfg[0] = ExploreCfg{noise_counter0, sa_t, lp_t, nullptr};
+  { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = SP; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed; a.cfg[0] = ExploreCfg{noise_counter, sa_t, lp_t, nullptr};
     crux_exec_push<ActorExploreTileOp>(c, nt, a); }
   rc = crux_dense_forward12(q1, sa_c, B, c->stream); if (!rc) rc = crux_dense_forward12(q2, sa_c, B, c->stream); if (rc) return bail(rc);
   tg.only(3);
@@ -664,8 +708,8 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
     a.lp = lp_t; a.log_alpha = la->p; a.w = w; a.gamma = gamma; a.scale = 0.5f; a.K = K; a.B = (int32_t)B; a.y = y; a.dy1 = dy1; a.dy2 = dy2; a.term1 = t1; a.term2 = t2;
     crux_exec_push<SacCriticTileOp>(c, nt, a); }
   { ActorExploreArgs a{}; a.mu = l3(actor, true); a.ls = ls; a.s = S; a.od = od; a.ad = ad; a.K = K; a.B = (int32_t)B; a.n_cfg = 1; a.seed = noise_seed;      // the two draws side by side (each re-evaluates the output layer: 8 MFMAs)
-    a.cfg[0] = ExploreCfg{noise_counter0 + 1, nullptr, lp_temp, nullptr}; crux_exec_push<ActorExploreTileOp>(c, nt, a);
-    a.cfg[0] = ExploreCfg{noise_counter0 + 2, sa_a, lp_a, eps}; crux_exec_push<ActorExploreTileOp>(c, nt, a); }
+    a.cfg[0] = ExploreCfg{noise_counter + 1, nullptr, lp_temp, nullptr}; crux_exec_push<ActorExploreTileOp>(c, nt, a);
+    a.cfg[0] = ExploreCfg{noise_counter + 2, sa_a, lp_a, eps}; crux_exec_push<ActorExploreTileOp>(c, nt, a); }
   tg.only(5);
   // 6
   Sumsq2Fix fxc{}, fxa{};
@@ -715,14 +759,12 @@ static int32_t sac_epoch_tiles(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux
 
 // One epoch of value_training with SAC's pieces (off_policy.jl:69-104, rl/sac.jl): rand! -> sac_target -> train!(log_alpha, sac_temp_loss) ->
 // [train!(critic, double_Q_loss)] -> [train!(actor, sac_actor_loss) -> polyak_average!(pi_minus, pi, tau)] as ONE fused launch.
-int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
-                       crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t update_critic, int32_t update_actor,
-                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) { CRUX_PLAIN_ONLY("crux_sac_epoch", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
+int32_t SacRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample_counter, uint64_t noise_counter, float* info_temp, float* info_critic, float* info_actor) const {
   if (!actor || !q1 || !q2 || !q1_targ || !q2_targ || !log_alpha || !source || !batch) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const int64_t B = batch->capacity;
   if (source->prioritized) return crux_fail(c, CRUX_EUNSUP, "sac_epoch: prioritized replay over a DoubleNetwork critic is not defined (td_error, src/utils.jl:112)");
-  if (c->rec && rec_of(c)->chain && sac_tile_case(actor, q1, q2, q1_targ, q2_targ, source, batch, update_critic, update_actor))      // chained epochs of the C4 family: the tile ops (14 launches per epoch)
-    return sac_epoch_tiles(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, sample_counter, noise_seed, noise_counter0, info_temp, info_critic, info_actor);
+  if (c->rec && rec_of(c)->chain && tile_case(update_critic, update_actor))      // chained epochs of the C4 family: the tile ops (14 launches per epoch)
+    return epoch_tiles(sample_counter, noise_counter, info_temp, info_critic, info_actor);
   const bool fuse = !crux_sw().no_fused_epoch;
   int32_t rc; float* d_y = nullptr;
   if (fuse) { if (!crux_exec_recording(c)) { rc = crux_exec_begin(c); if (rc) return rc; }       // a chained recording (crux_sac_epochs) is already open
@@ -735,36 +777,26 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
   //   X sac_target ; exploration at s | X+1 critic heads ; temperature head | X+2.. critic backward (weight || data gradient, both critics) ; Adam(log_alpha) | .. norm | info, Adam(Q1), Adam(Q2)
   //   X+1.. actor(s) forward of the ACTOR step, exploration (beside the critic's backward) | Y.. Q1 || Q2 forward | actor head | Q1 || Q2 input gradients | reverse of exploration | actor backward ; logSigma row sums | norm | info, Adam | polyak
   // The order inside every chain is the reference's (temperature before critic before actor: each sees the parameters the previous step left).
-  // sq: sac_target (one block at B <= 256) and the critic heads (one block each) form a sequential group in ONE block of phase X when the critics train; the critic
-  // chain and everything behind it (Y ..) then sit one phase earlier. The temperature chain (X .. X + 3) is independent of it.
-  const int sq = (update_critic && B <= 256) ? 1 : 0;
-  // Round 4: written in launches -- FA / FQ forward launches of the actor / a critic, BQ / BA phases of a pullback with parameter gradients (BQo ops per critic), LQ phases
-  // of a critic's input-gradient chain; with the fused block kernels FA = FQ = L - 1 and BQ = BA = L - 1 (net_plan above), otherwise all equal L as in round 3.
-  const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);
+  // The temperature chain (X .. X + 3) is independent of the sequential group at X (ActorCriticPlan: the constants and the rules shared with DDPG / TD3).
+  const ActorCriticPlan P(actor, q1, B, update_critic); const NetPlan& pa = P.pa; const int FA = P.FA, FQ = P.FQ, BA = P.BA, DQ = P.DQ, X = P.X, Y = P.Y;
   EpochTags tg(c, fuse, "sac_epoch", 3, 3);
-  const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
-  if (LA != LQ || q2->nd.L != LQ || q1_targ->nd.L != LQ || q2_targ->nd.L != LQ) tg.plan_ok = false;       // (the early actor forward needs X + 1 + FA < Y)
-  { const NetPlan p2 = net_plan(q2, B), t1 = net_plan(q1_targ, B), t2 = net_plan(q2_targ, B); if (p2.nf != FQ || p2.nb != BQ || p2.one != pq.one || t1.nf != FQ || t2.nf != FQ || FA != FQ) tg.plan_ok = false; }
+  if (!P.ok(q2, q1_targ, q2_targ) || net_plan(q2, B).one != P.pq.one) tg.plan_ok = false;       // (the early actor forward needs X + 1 + FA < Y)
   // chained epochs: phases 0 (ids) and 1 (gather, fills) of a later epoch run beside the previous epoch's actor norm and info + Adam (neither reads the batch), and its
   // phase 2 (actor(sp) forward, vcat(s, a): online networks only) beside the previous epoch's advance + polyak, which writes beta powers and TARGET networks: the rest
   // closes up by three -- see crux_dqn_epoch
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  tg.tag([&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
-  rc = crux_sac_target(actor, q1_targ, q2_targ, log_alpha, batch, gamma, noise_seed, noise_counter0, d_y); if (rc) return bail(rc);
-  tg.tag([&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
-    return kid == OP_GAUSS_EXPLORE ? 2 + FA : kid == OP_SAC_TARGET ? X | (sq ? PH_SEQ_HEAD : 0) : -1; });
-  rc = crux_sac_temp_step(actor, log_alpha, batch, H_target, noise_seed, noise_counter0 + 1, info_temp); if (rc) return bail(rc);
+  tg.tag([&](int kid, int&) { return P.sampling(kid); });
+  rc = crux_sac_target(actor, q1_targ, q2_targ, log_alpha, batch, gamma, noise_seed, noise_counter, d_y); if (rc) return bail(rc);
+  tg.tag([&](int kid, int& g) { return P.target(kid, g, OP_GAUSS_EXPLORE, OP_SAC_TARGET); });
+  rc = crux_sac_temp_step(actor, log_alpha, batch, H_target, noise_seed, noise_counter + 1, info_temp); if (rc) return bail(rc);
   tg.tag([&](int kid, int& g) { if (kid == OP_FILL) return 1; if (is_mm(kid)) { const int k = g++; return k < FA ? 3 + FA + k : -1; }
     return kid == OP_GAUSS_EXPLORE ? X : kid == OP_TEMP_HEAD ? X + 1 : kid == OP_ADAM_GATED ? X + 2 : kid == OP_ADAM_ADVANCE ? X + 3 : -1; });
   if (update_critic) {
     rc = crux_double_q_step(q1, q2, batch, d_y, use_weight, info_critic); if (rc) return bail(rc);
-    tg.tag([&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
-      if (kid == OP_FILL) return 1; if (kid == OP_CONCAT_SA) return 2;
-      if (is_mm(kid)) { const int k = (g++) % (FQ + BQo); return k < FQ ? 3 + k : X + 2 - sq + pq.stage(k - FQ); }
-      return kid == OP_Q_HEAD ? (sq ? (X | PH_SEQ_TAIL) : X + 1) : kid == OP_SUMSQ2 ? X + 2 - sq + BQ : (kid == OP_CRITIC_INFO || kid == OP_ADAM_GATED) ? X + 3 - sq + BQ : kid == OP_ADAM_ADVANCE ? X + 4 - sq + BQ : -1; });
+    tg.tag([&](int kid, int& g) { return P.critic(kid, g); });
   }
   if (update_actor) {
-    rc = crux_sac_actor_step(actor, q1, q2, log_alpha, batch, noise_seed, noise_counter0 + 2, info_actor); if (rc) return bail(rc);
+    rc = crux_sac_actor_step(actor, q1, q2, log_alpha, batch, noise_seed, noise_counter + 2, info_actor); if (rc) return bail(rc);
     tg.tag([&](int kid, int& g) {      // GEMMs: LA actor forward, LQ + LQ critic forwards, LQ + LQ critic input gradients, then the actor's (weight, data) pairs
       if (kid == OP_FILL) return 1;
       // the actor's own forward pass and its exploration draw depend on neither the critic update nor the temperature: they run beside the critic's head / backward
@@ -781,56 +813,49 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
   return tg.finish(Y + BA + 5 + FQ + DQ);
 }
 
+int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
+                       crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t update_critic, int32_t update_actor,
+                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) { CRUX_PLAIN_ONLY("crux_sac_epoch", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
+  const SacRun run{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, 0, 1, 1, 1, sample_counter, noise_seed, noise_counter0};
+  return run.one(update_critic, update_actor, sample_counter, noise_counter0, info_temp, info_critic, info_actor);
+}
 // value_training's epoch loop with SAC's pieces (off_policy.jl:69-104; SAC's c_opt.epochs = dN = 50, rl/sac.jl) in chains of up to 8 epochs per recorded list.
 // Epoch e (global index epoch0 + e within the iteration) trains the critic when (epoch0 + e) % critic_every == 0 and the actor (then the target update) when
 // (epoch0 + e) % actor_every == 0 (:91,96); it draws with sample counter sample_counter0 + e and noise counters noise_counter0 + 3 e .. + 2. infos_*: host [n x CRUX_INFO_N].
-static int32_t sac_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
-                        crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
-                        float* infos_temp, float* infos_critic, float* infos_actor, float* d_infos_async) {
-  if (!actor || n_epochs < 1 || critic_every < 1 || actor_every < 1) return CRUX_EINVAL;
-  crux_ctx* c = actor->ctx;
-  const bool fuse = !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs;
-  auto record = [&](int e) { const int ge = epoch0 + e; const size_t o = (size_t)e * CRUX_INFO_N;
-    return crux_sac_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, ge % critic_every == 0, ge % actor_every == 0,
-                          sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + 3ull * (uint64_t)e, infos_temp ? infos_temp + o : nullptr, infos_critic ? infos_critic + o : nullptr,
-                          infos_actor ? infos_actor + o : nullptr); };
-  // rows 3 e .. 3 e + 2: temperature, [critics], [actor]. Tile plans: the actor's info op sits IN the epoch's last phase -- the copies join the launch after it, the next epoch's third
-  auto rows = [&](int e) { const int ge = epoch0 + e; const bool uc = ge % critic_every == 0, ua = ge % actor_every == 0;
-    return EpochRows{1u | (uc ? 2u : 0u) | (ua ? 4u : 0u), sac_tile_case(actor, q1, q2, q1_targ, q2_targ, source, batch, uc, ua) ? 4 : 0}; };
-  return run_epoch_chains(c, "sac", fuse, nullptr, n_epochs, 3, d_infos_async, record, rows, [] { return CRUX_OK; });
-}
 int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                         crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
                         float* infos_temp, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_sac_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
-  // more than one chain: one read-back at the end of the call (see epochs_one_readback)
-  if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_fused_epoch && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
-    float* const dst[3] = {infos_temp, infos_critic, infos_actor};
-    return epochs_one_readback(actor->ctx, "sac", "SAC", n_epochs, 3, dst,
-      [&](float* d_rows) { return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every,
-                                                  actor_every, sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, nullptr, d_rows); },
-      [&](int e) { const int ge = epoch0 + e; return 1u | (ge % critic_every == 0 ? 2u : 0u) | (ge % actor_every == 0 ? 4u : 0u); });
-  }
-  return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                         sample_counter0, noise_seed, noise_counter0, infos_temp, infos_critic, infos_actor, nullptr);
+  float* const host_rows[3] = {infos_temp, infos_critic, infos_actor};
+  return run_family(SacRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
+                           sample_counter0, noise_seed, noise_counter0}, host_rows, nullptr);
 }
-// crux_sac_epochs without the host in the loop (see crux_dqn_epochs_async): d_infos is DEVICE memory, [n_epochs][3][CRUX_INFO_N] = temperature | critics | actor rows of every
+// crux_sac_epochs without the host in the loop (see crux_dqn_value_training_async): d_infos is DEVICE memory, [n_epochs][3][CRUX_INFO_N] = temperature | critics | actor rows of every
 // epoch (rows of steps an epoch skipped -- critic_every / actor_every -- are left as they were).
 int32_t crux_sac_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                               crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                               int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_sac_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
   if (!d_infos) return CRUX_EINVAL;
-  return sac_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                         sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, nullptr, d_infos);
+  return run_family(SacRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
+                           sample_counter0, noise_seed, noise_counter0}, nullptr, d_infos);
 }
 
 // One epoch of value_training with DDPG's / TD3's pieces (off_policy.jl:69-104; rl/ddpg.jl, rl/td3.jl): rand! -> ddpg_target | td3_target -> [train!(critic, td_loss |
 // double_Q_loss)] -> [train!(actor, -mean(Q(s, mu(s)))) -> polyak_average!] recorded as one list. q2 / q2_targ = NULL: single critic (DDPG); q2 with q2_targ = NULL:
 // twin critics trained against a single-target (not used by the reference's solvers).
-static int32_t dpg_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
-                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t update_critic, int32_t update_actor,
-                         uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter, float* info_critic, float* info_actor) {
+struct DpgRun {      // one value_training call with DDPG's / TD3's pieces (crux_dpg_epochs[_async]): see run_family
+  crux_mlp *actor, *q1, *q2, *actor_targ, *q1_targ, *q2_targ; crux_buffer *source, *batch; float gamma, tau, sigma, eps_min, eps_max, a_min, a_max; int32_t use_weight, epoch0, n_epochs, critic_every, actor_every;
+  uint64_t sample_counter0, noise_seed, noise_counter0;
+  static constexpr int NROWS = 2; static constexpr bool ONE_READBACK = true; static constexpr const char *who = "dpg", *family = "DDPG / TD3";
+  bool valid() const { return actor && q1 && actor_targ && q1_targ && source && batch && n_epochs >= 1 && critic_every >= 1 && actor_every >= 1; }
+  crux_ctx* ctx() const { return actor->ctx; }      crux_buffer* per() const { return nullptr; }      int32_t tail() const { return CRUX_OK; }
+  bool chain() const { return !crux_sw().no_chained_epochs; }
+  bool uc(int e) const { return (epoch0 + e) % critic_every == 0; }      bool ua(int e) const { return (epoch0 + e) % actor_every == 0; }
+  unsigned rows(int e) const { return (uc(e) ? 1u : 0u) | (ua(e) ? 2u : 0u); }      int shift(int) const { return 0; }      // rows 2 e (critic) and 2 e + 1 (actor)
+  int32_t epoch(int e, float* const* host_rows) const { return one(uc(e), ua(e), sample_counter0 + (uint64_t)e, noise_counter0 + (uint64_t)e, info_row(host_rows, 0, e), info_row(host_rows, 1, e)); }
+  int32_t one(int32_t update_critic, int32_t update_actor, uint64_t sample_counter, uint64_t noise_counter, float* info_critic, float* info_actor) const;
+};
+int32_t DpgRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample_counter, uint64_t noise_counter, float* info_critic, float* info_actor) const {
   crux_ctx* c = actor->ctx; const int64_t B = batch->capacity;
   if (source->prioritized) return crux_fail(c, CRUX_EUNSUP, "dpg_epoch: DDPG / TD3 with a prioritized buffer is not wired up");
   int32_t rc;
@@ -842,26 +867,19 @@ static int32_t dpg_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* 
   //   0 ids | 1 gather, fills | 2.. target actor(sp) forward ; vcat(s, a) ; actor(s) forward of the ACTOR step | 2+LA target action (+ smoothing noise) ; mu(s) -> vcat(s, mu(s))
   //   3+LA.. target Q1 || Q2 forward (and, from 3: Q1 || Q2 forward on (s, a)) | X target | X+1 critic heads | X+2.. critic backward | norm | info, Adam | advance
   //   Y.. Q(s, mu(s)) forward | its input gradient | slice | actor backward | norm | info, Adam | advance, polyak
-  const int sq = (update_critic && B <= 256) ? 1 : 0;      // target + critic head(s) as a sequential one-block group (see crux_sac_epoch)
-  const NetPlan pa = net_plan(actor, B), pq = net_plan(q1, B);      // launches per pass (see crux_sac_epoch)
+  const ActorCriticPlan P(actor, q1, B, update_critic); const NetPlan& pa = P.pa; const int LA = P.LA, FA = P.FA, FQ = P.FQ, BA = P.BA, DQ = P.DQ, Y = P.Y;
   // chained epochs: the sampling of epoch e + 1 beside the actor's norm and info + Adam of epoch e; its phase 2 reads the TARGET actor, which polyak (last phase) writes,
   // so the rest closes up by two only
   EpochTags tg(c, true, "dpg_epoch", 3, 2);
-  const int LA = actor->nd.L, LQ = q1->nd.L, FA = pa.nf, FQ = pq.nf, BQ = pq.nb, BQo = pq.nbops, BA = pa.nb, DQ = pq.dq, X = 3 + FA + FQ, Y = X + 4 + BQ - sq;
   const int ag = actor->nd.acts[LA - 1] != CRUX_ACT_IDENTITY ? 1 : 0;
-  if (LA != LQ || actor_targ->nd.L != LA || q1_targ->nd.L != LQ || (q2 && q2->nd.L != LQ) || (q2_targ && q2_targ->nd.L != LQ)) tg.plan_ok = false;
-  if (FA != FQ || net_plan(actor_targ, B).nf != FA || net_plan(q1_targ, B).nf != FQ || (q2 && (net_plan(q2, B).nf != FQ || net_plan(q2, B).nb != BQ)) || (q2_targ && net_plan(q2_targ, B).nf != FQ)) tg.plan_ok = false;
+  if (!P.ok(q2, q1_targ, q2_targ) || actor_targ->nd.L != LA || net_plan(actor_targ, B).nf != FA) tg.plan_ok = false;
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
-  tg.tag([&](int kid, int&) { return kid == OP_UNIFORM_IDS ? 0 : kid == OP_GATHER_RING_ALL ? 1 : -1; });
+  tg.tag([&](int kid, int&) { return P.sampling(kid); });
   rc = crux_dpg_target(actor_targ, q1_targ, q2_targ, batch, gamma, sigma, eps_min, eps_max, a_min, a_max, noise_seed, noise_counter, d_y); if (rc) return bail(rc);
-  tg.tag([&](int kid, int& g) { if (is_mm(kid)) { const int k = g++; return k < FA ? 2 + k : 3 + FA + (k - FA) % FQ; }
-    return kid == OP_DPG_ACTION ? 2 + FA : kid == OP_DPG_TARGET ? X | (sq ? PH_SEQ_HEAD : 0) : -1; });
+  tg.tag([&](int kid, int& g) { return P.target(kid, g, OP_DPG_ACTION, OP_DPG_TARGET); });
   if (update_critic) {
     rc = q2 ? crux_double_q_step(q1, q2, batch, d_y, use_weight, info_critic) : crux_q_step(q1, batch, d_y, use_weight, info_critic); if (rc) return bail(rc);
-    tg.tag([&](int kid, int& g) {      // per critic: LQ forward GEMMs, head, then (weight, data) pairs from the last layer down (the first layer has no data gradient)
-      if (kid == OP_FILL) return 1; if (kid == OP_CONCAT_SA) return 2;
-      if (is_mm(kid)) { const int k = (g++) % (FQ + BQo); return k < FQ ? 3 + k : X + 2 - sq + pq.stage(k - FQ); }
-      return kid == OP_Q_HEAD ? (sq ? (X | PH_SEQ_TAIL) : X + 1) : kid == OP_SUMSQ2 ? X + 2 - sq + BQ : (kid == OP_CRITIC_INFO || kid == OP_ADAM_GATED) ? X + 3 - sq + BQ : kid == OP_ADAM_ADVANCE ? X + 4 - sq + BQ : -1; });
+    tg.tag([&](int kid, int& g) { return P.critic(kid, g); });
   }
   if (update_actor) {
     rc = crux_dpg_actor_step(actor, q1, batch, info_actor); if (rc) return bail(rc);
@@ -882,39 +900,20 @@ static int32_t dpg_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* 
 
 // value_training's epoch loop with DDPG's / TD3's pieces in chains of up to 8 epochs per recorded list (see crux_sac_epochs). sigma < 0: no target-policy smoothing
 // (DDPG); otherwise TD3's clamp(a' + clamp(sigma randn, eps_min, eps_max), a_min, a_max) with noise counters noise_counter0 + e. infos_*: host [n x CRUX_INFO_N].
-static int32_t dpg_epochs_impl(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
+int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor,
-                        float* d_infos_async) {
-  if (!actor || !q1 || !actor_targ || !q1_targ || !source || !batch || n_epochs < 1 || critic_every < 1 || actor_every < 1) return CRUX_EINVAL;
-  auto record = [&](int e) { const int ge = epoch0 + e; const size_t o = (size_t)e * CRUX_INFO_N;
-    return dpg_epoch(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, ge % critic_every == 0, ge % actor_every == 0,
-                     sample_counter0 + (uint64_t)e, noise_seed, noise_counter0 + (uint64_t)e, infos_critic ? infos_critic + o : nullptr, infos_actor ? infos_actor + o : nullptr); };
-  // rows 2 e (critic) and 2 e + 1 (actor)
-  auto rows = [&](int e) { const int ge = epoch0 + e; return EpochRows{(ge % critic_every == 0 ? 1u : 0u) | (ge % actor_every == 0 ? 2u : 0u), 0}; };
-  return run_epoch_chains(actor->ctx, "dpg", !crux_sw().no_chained_epochs, nullptr, n_epochs, 2, d_infos_async, record, rows, [] { return CRUX_OK; });
+                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_dpg_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ);
+  float* const host_rows[2] = {infos_critic, infos_actor};
+  return run_family(DpgRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
+                           sample_counter0, noise_seed, noise_counter0}, host_rows, nullptr);
 }
-// crux_dpg_epochs without the host in the loop (see crux_dqn_epochs_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows of every epoch
+// crux_dpg_epochs without the host in the loop (see crux_dqn_value_training_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows of every epoch
 int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                               float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                               int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_dpg_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ);
   if (!d_infos) return CRUX_EINVAL;
-  return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                         sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, d_infos);
-}
-int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
-                        float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_dpg_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ);
-  // several chains per call: run back to back, one read-back at the end of the call (see epochs_one_readback)
-  if (actor && n_epochs > 8 && critic_every >= 1 && actor_every >= 1 && !crux_sw().no_chained_epochs && !crux_sw().sync_chains) {
-    float* const dst[2] = {infos_critic, infos_actor};
-    return epochs_one_readback(actor->ctx, "dpg", "DDPG / TD3", n_epochs, 2, dst,
-      [&](float* d_rows) { return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs,
-                                                  critic_every, actor_every, sample_counter0, noise_seed, noise_counter0, nullptr, nullptr, d_rows); },
-      [&](int e) { const int ge = epoch0 + e; return (ge % critic_every == 0 ? 1u : 0u) | (ge % actor_every == 0 ? 2u : 0u); });
-  }
-  return dpg_epochs_impl(actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
-                         sample_counter0, noise_seed, noise_counter0, infos_critic, infos_actor, nullptr);
+  return run_family(DpgRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
+                           sample_counter0, noise_seed, noise_counter0}, nullptr, d_infos);
 }
 }  // extern "C"
 

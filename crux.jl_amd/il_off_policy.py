@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .logging import aggregate_info
 from .core import (ContinuousNetwork, ContinuousSpace, DiscreteNetwork, DiscreteSpace, ExperienceBuffer, TrainingParams, _Loss, _ensure_opt, _vp, copy_buffer, normalize_,
                    split_batches)
 from .off_policy import SAC, SoftQ
@@ -128,8 +129,7 @@ def _value_training_iq(solver, D, gamma):
             info.update({p.name + "loss": float(raw[L.INFO["loss"]]), p.name + "grad_norm": float(raw[L.INFO["grad_norm"]])})
         infos.append(info)
     solver._update_target(final=True)                                                                  # :108
-    keys = {k for d in infos for k in d}
-    return {k: float(np.mean([d[k] for d in infos if k in d])) for k in keys}                          # aggregate_info (logging.jl:60-66)
+    return aggregate_info(infos)
 
 
 def sqil_callback(D, S=None, info=None):

@@ -5,6 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
+from .logging import aggregate_info
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -61,7 +62,7 @@ class OffPolicySolver:
         self.fused_epochs = True              # value_training's epoch loop through crux_dqn_epochs / crux_sac_epochs (recorded op lists run by the executor for wide networks)
         self.sampler, self.batch, self._history = None, None, []
         self._dy = self._derr = None
-        # solve() without the host in the loop (cruxhip.h: crux_dqn_epochs_async): the epochs' info rows stay on the device until somebody looks at `history`
+        # solve() without the host in the loop (cruxhip.h: crux_dqn_value_training_async): the epochs' info rows stay on the device until somebody looks at `history`
         self.async_training = True
         self._async_now = self._async_unsupported = self._async_fell_back = False
         self._dinfos, self._dinfos_rows, self._dinfos_used, self._pending = None, 0, 0, []      # device ring of info rows; (history index, first row, epochs, name) not yet fetched
@@ -88,8 +89,7 @@ class OffPolicySolver:
         for hi, r0, n, decode, extra in pend:
             raws = rows[r0:r0 + n]
             infos, nan = decode(raws)
-            keys = {k for x in infos for k in x}
-            d = {k: float(np.mean([x[k] for x in infos if k in x])) for k in keys}                       # aggregate_info: mean over the dicts that have the key (logging.jl:60-66)
+            d = aggregate_info(infos)
             d.update({k: v for k, v in extra.items() if k not in d})
             self._history[hi] = d
             if bad is None and nan:
@@ -153,18 +153,10 @@ def _value_training_sac(solver, D, gamma):
             return out, nan
         args = (A.h, Q.N1.h, Q.N2.h, pim.A.h, Qm.N1.h, Qm.N2.h, la.h, buf.h, D.h, float(gamma), float(solver.P["SAC_H_target"]), float(solver.tau),
                 1 if solver.weighted_loss else 0, 0, n, ce, ae, ctr0, solver.noise_seed, 3 * ctr0)
-        if getattr(solver, "_async_now", False):
-            d_rows, row0 = _info_ring(solver, ctx, 3 * n)
-            rc = lib.crux_sac_epochs_async(*args, d_rows)
-            if rc == L.OK:
-                solver._dinfos_used += 3 * n
-                return _PendingInfo(row0, 3 * n, decode)
-            if rc != L.EUNSUP:
-                ctx.check(rc)
-            solver._async_now = False; solver._async_fell_back = True
-        rows = np.zeros((3, n, L.INFO_N), np.float32)
-        ctx.check(lib.crux_sac_epochs(*args, _vp(rows[0]), _vp(rows[1]), _vp(rows[2])))
-        infos = decode(rows.transpose(1, 0, 2).reshape(3 * n, L.INFO_N))[0]
+        infos = _fused_epochs(solver, ctx, 3, n, decode, lambda d_rows: lib.crux_sac_epochs_async(*args, d_rows),
+                              lambda rows: lib.crux_sac_epochs(*args, _vp(rows[0]), _vp(rows[1]), _vp(rows[2])))
+        if isinstance(infos, _PendingInfo):
+            return infos
     for epoch in range(0 if fused else c_opt.epochs):
         ctr = solver.i * c_opt.epochs + epoch                                                          # one Philox counter block per epoch
         upd_c, upd_a = epoch % c_opt.update_every == 0, epoch % a_opt.update_every == 0                # :91, :96
@@ -186,8 +178,7 @@ def _value_training_sac(solver, D, gamma):
             info.update({a_opt.name + "loss": float(raw[0]), a_opt.name + "grad_norm": float(raw[1]), "entropy": float(raw[L.INFO["entropy"]])})
             solver._update_target()                                                                    # :100 (target update only when the actor trains)
         infos.append(info)
-    keys = {k for d in infos for k in d}
-    return {k: float(np.mean([d[k] for d in infos if k in d])) for k in keys}      # aggregate_info: mean over the dicts that have the key (logging.jl:60-66)
+    return aggregate_info(infos)
 
 
 def _value_training_dpg(solver, D, gamma):
@@ -227,18 +218,10 @@ def _value_training_dpg(solver, D, gamma):
         args = (A.h, (Q.N1 if twin else Q).h, Q.N2.h if twin else None, Am.h, (Qm.N1 if twin else Qm).h, Qm.N2.h if twin else None, buf.h, D.h,
                 float(gamma), float(solver.tau), sm.sigma if sm else -1.0, sm.eps_min if sm else 0.0, sm.eps_max if sm else 0.0, sm.a_min if sm else 0.0,
                 sm.a_max if sm else 0.0, 1 if solver.weighted_loss else 0, 0, n, ce, ae, ctr0, solver.noise_seed, ctr0)
-        if getattr(solver, "_async_now", False):
-            d_rows, row0 = _info_ring(solver, ctx, 2 * n)
-            rc = lib.crux_dpg_epochs_async(*args, d_rows)
-            if rc == L.OK:
-                solver._dinfos_used += 2 * n
-                return _PendingInfo(row0, 2 * n, decode)
-            if rc != L.EUNSUP:
-                ctx.check(rc)
-            solver._async_now = False; solver._async_fell_back = True
-        rows = np.zeros((2, n, L.INFO_N), np.float32)
-        ctx.check(lib.crux_dpg_epochs(*args, _vp(rows[0]), _vp(rows[1])))
-        infos = decode(rows.transpose(1, 0, 2).reshape(2 * n, L.INFO_N))[0]
+        infos = _fused_epochs(solver, ctx, 2, n, decode, lambda d_rows: lib.crux_dpg_epochs_async(*args, d_rows),
+                              lambda rows: lib.crux_dpg_epochs(*args, _vp(rows[0]), _vp(rows[1])))
+        if isinstance(infos, _PendingInfo):
+            return infos
     for epoch in range(0 if fused else c_opt.epochs):
         ctr = solver.i * c_opt.epochs + epoch
         solver._rand(D, ctr)                                                                           # :71 rand!(D, buffer, extra_buffers...; fracs, i=S.i)
@@ -261,8 +244,7 @@ def _value_training_dpg(solver, D, gamma):
             info.update({a_opt.name + "loss": float(raw[0]), a_opt.name + "grad_norm": float(raw[1])})
             solver._update_target()                                                                    # :100
         infos.append(info)
-    keys = {k for d in infos for k in d}
-    return {k: float(np.mean([d[k] for d in infos if k in d])) for k in keys}                          # aggregate_info: mean over the dicts that have the key (logging.jl:60-66)
+    return aggregate_info(infos)
 
 
 def _set_stream_for(buf, seed):
@@ -290,6 +272,7 @@ def value_training(solver, D, gamma):
     if solver.target_fn in ("ddpg", "td3"):
         return _value_training_dpg(solver, D, gamma)
     pi, pim, buf, p, ctx = solver.agent.pi, solver.agent.pi_minus, solver.buffer, solver.c_opt, solver.buffer.ctx
+    alpha = _softq_alpha(solver.P["alpha"]) if solver.target_fn == "softq" else 0.0                      # before any device call: nothing is drawn for a solver it refuses
     _ensure_opt(pi, p)
     B = D.capacity
     if solver._dy is None:
@@ -301,29 +284,17 @@ def value_training(solver, D, gamma):
         # between them (cruxhip.h: crux_dqn_epochs); same steps, same order, same draws as the separate calls below
         _set_stream_for(buf, solver.sample_seed)
         beta = float(np.float32(buf.beta(solver.i))) if buf.isprioritized() else 0.0                       # rand!(D, buffer, i=S.i): beta(S.i)
-        raws = np.zeros((p.epochs, L.INFO_N), np.float32)
-        name = p.name
+        name, lib = p.name, ctx.lib
         def decode(raws):
             return [{name + "loss": float(r[0]), name + "grad_norm": float(r[1]), "Qavg": float(r[2])} for r in raws], bool(np.isnan(raws[:, 1]).any())
-        if getattr(solver, "_async_now", False):
-            # no host in the loop: the chain is enqueued and the info rows stay on the device (OffPolicySolver.history fetches them)
-            d_rows, _row0 = _info_ring(solver, ctx, p.epochs)
-            # the epoch loop AND the target update of :108 (polyak_average!(pi_minus, pi, tau): the built-in target_update of this fused path) in ONE chain: the polyak
-            # update rides in the last epoch's final phase instead of a launch of its own (cruxhip.h: crux_dqn_value_training_async)
-            rc = ctx.lib.crux_dqn_value_training_async(pi.h, pim.h, buf.h, D.h, float(gamma), float(solver.P["alpha"]) if solver.target_fn == "softq" else 0.0,
-                                                       1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, float(np.float32(solver.tau)), d_rows)
-            if rc == L.OK:
-                solver._dinfos_used += p.epochs
-                return _PendingInfo(_row0, p.epochs, decode)                                               # (:108 ran inside the chain)
-            if rc != L.EUNSUP:
-                ctx.check(rc)
-            solver._async_now = False; solver._async_fell_back = True      # narrow networks: the synchronous entry point from here on
-        rest = (1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs, _vp(raws))
-        if solver.target_fn == "softq":      # softq_target(alpha) in place of dqn_target (rl/softq.jl:4-13)
-            ctx.check(ctx.lib.crux_softq_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), float(solver.P["alpha"]), *rest))
-        else:
-            ctx.check(ctx.lib.crux_dqn_epochs(pi.h, pim.h, buf.h, D.h, float(gamma), *rest))
-        infos = decode(raws)[0]
+        nets, rest = (pi.h, pim.h, buf.h, D.h, float(gamma)), (1 if solver.weighted_loss else 0, beta, solver.i * p.epochs, p.epochs)
+        # asynchronous: the epoch loop AND the target update of :108 (polyak_average!(pi_minus, pi, tau): the built-in target_update of this fused path) in ONE chain, the
+        # polyak update riding in the last epoch's final phase (cruxhip.h: crux_dqn_value_training_async; alpha = 0 there means dqn_target). Narrow networks: CRUX_EUNSUP
+        def call_sync(rows):      # softq_target(alpha) in place of dqn_target (rl/softq.jl:4-13)
+            return lib.crux_softq_epochs(*nets, alpha, *rest, _vp(rows[0])) if solver.target_fn == "softq" else lib.crux_dqn_epochs(*nets, *rest, _vp(rows[0]))
+        infos = _fused_epochs(solver, ctx, 1, p.epochs, decode, lambda d_rows: lib.crux_dqn_value_training_async(*nets, alpha, *rest, float(np.float32(solver.tau)), d_rows), call_sync)
+        if isinstance(infos, _PendingInfo):
+            return infos                                                                               # (:108 ran inside the chain)
     for epoch in range(0 if fused else p.epochs):
         raw = np.zeros(L.INFO_N, np.float32); info = {}
         solver._rand(D, solver.i * p.epochs + epoch)                                                   # :71 rand!(D, buffer, extra_buffers...; fracs, i=S.i): beta(S.i); the Philox counter is unique per draw
@@ -333,7 +304,7 @@ def value_training(solver, D, gamma):
         if callable(solver.target_fn):
             y_host = _upload_target(solver, D, solver.target_fn(pim, solver.P, D, gamma, i=solver.i))  # :80 with the caller's target
         elif solver.target_fn == "softq":
-            ctx.check(ctx.lib.crux_softq_target(pim.h, D.h, float(gamma), float(solver.P["alpha"]), solver._dy))   # :80  softq.jl:4-13
+            ctx.check(ctx.lib.crux_softq_target(pim.h, D.h, float(gamma), alpha, solver._dy))            # :80  softq.jl:4-13
         else:
             ctx.check(ctx.lib.crux_dqn_target(pim.h, D.h, float(gamma), solver._dy))                    # :80  dqn.jl:4-6
         if buf.isprioritized() and solver.priority_fn is not None:                                     # :83 with the caller's priority function
@@ -350,8 +321,7 @@ def value_training(solver, D, gamma):
         info.update({p.name + "loss": float(raw[0]), p.name + "grad_norm": float(raw[1]), "Qavg": float(raw[2])})
         infos.append(info)
     solver._update_target(final=True)                                                                  # :108
-    keys = {k for d in infos for k in d}
-    return {k: float(np.mean([d[k] for d in infos if k in d])) for k in keys}                          # aggregate_info: mean over the dicts that have the key (logging.jl:60-66)
+    return aggregate_info(infos)
 
 
 def value_training_async(solver, D, gamma):
@@ -371,6 +341,25 @@ def value_training_async(solver, D, gamma):
     return tinfo
 
 
+def _fused_epochs(solver, ctx, rows_per_epoch, n, decode, call_async, call_sync):
+    """The epoch loop of one value_training call (n epochs, rows_per_epoch info rows each) through a family's fused entry points. When the call is to run without the host
+    (solver._async_now), call_async(d_rows) enqueues the chains with their rows in the solver's device ring and the result is a _PendingInfo; CRUX_EUNSUP there marks the
+    fallback (_async_fell_back: the synchronous entry point from here on). call_sync(rows) fills host rows [rows_per_epoch][n][INFO_N]; the result is decode's info dicts."""
+    nrows = rows_per_epoch * n
+    if getattr(solver, "_async_now", False):
+        d_rows, row0 = _info_ring(solver, ctx, nrows)
+        rc = call_async(d_rows)
+        if rc == L.OK:
+            solver._dinfos_used += nrows
+            return _PendingInfo(row0, nrows, decode)
+        if rc != L.EUNSUP:
+            ctx.check(rc)
+        solver._async_now = False; solver._async_fell_back = True
+    rows = np.zeros((rows_per_epoch, n, L.INFO_N), np.float32)
+    ctx.check(call_sync(rows))
+    return decode(rows.transpose(1, 0, 2).reshape(nrows, L.INFO_N))[0]
+
+
 def _info_ring(solver, ctx, nrows):
     """nrows rows of the solver's device info ring (fetching what is pending when it is full); returns the device address of the first one and its row index"""
     if solver._dinfos is None or solver._dinfos_used + nrows > solver._dinfos_rows:
@@ -386,7 +375,7 @@ def _info_ring(solver, ctx, nrows):
 
 
 class _PendingInfo:
-    """value_training's info of an iteration whose chain is still on its way (crux_dqn_epochs_async): rows [row0, row0 + n) of the solver's device info ring."""
+    """value_training's info of an iteration whose chain is still on its way (crux_dqn_value_training_async and its kin): rows [row0, row0 + n) of the solver's device info ring."""
     def __init__(self, row0, n, decode):
         self.row0, self.n, self.decode = row0, n, decode      # decode(rows) -> (list of per-epoch info dicts, any NaN norm)
 
@@ -525,10 +514,18 @@ def SAC(pi, S, N, dN=50, SAC_alpha=1.0, SAC_H_target=None, pi_explore=None, SAC_
                            a_opt=TrainingParams(loss=sac_actor_loss, **a), c_opt=TrainingParams(loss=double_Q_loss, **c), target_fn="sac", **kw)
 
 
+def _softq_alpha(alpha):
+    """softq_target(alpha) and softmax(Q ./ alpha) need alpha > 0; with alpha = 0 the asynchronous entry point would train the solver as a DQN (cruxhip.h)"""
+    a = float(np.float32(alpha))
+    if not a > 0.0:
+        raise ValueError("SoftQ: alpha must be positive, got %r" % (alpha,))
+    return a
+
+
 def SoftQ(pi, S, N, dN=4, c_opt=None, alpha=1.0, **kw):
     """SoftQ(; pi::DiscreteNetwork, N, dN=4, c_opt=(epochs=4,), alpha=1f0) (src/model_free/rl/softq.jl:31-58): the policy samples from
-    softmax(Q ./ alpha) (always_stochastic, :52-53), target = softq_target(alpha)."""
-    pi.always_stochastic, pi.logit_div = True, float(np.float32(alpha))
+    softmax(Q ./ alpha) (always_stochastic, :52-53), target = softq_target(alpha). ValueError unless alpha > 0."""
+    pi.always_stochastic, pi.logit_div = True, _softq_alpha(alpha)
     pim = DiscreteNetwork(pi.network, pi.outputs, ctx=pi.ctx); copyto_(pim, pi)
     c = dict(c_opt or {}); c.setdefault("name", "critic_"); c.setdefault("epochs", 4)
     return OffPolicySolver(agent=PolicyParams(pi, pi_minus=pim), S=S, N=N, dN=dN, c_opt=TrainingParams(loss=td_loss, **c), target_fn="softq", P={"alpha": np.float32(alpha)}, **kw)

@@ -540,24 +540,21 @@ int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source,
  * step; a caller that needs that state should use the per-epoch entry points.                                                                                       */
 int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
                         uint64_t sample_counter0, int32_t n_epochs, float* infos);
-/* The same epoch loop with softq_target(alpha) (rl/softq.jl:4-13) in place of dqn_target: value_training of the SoftQ solver (rl/softq.jl:31-58).             */
-/* crux_dqn_epochs without the host in the loop: nothing is read back, nothing is waited for. The info row of epoch e (LOSS, GRAD_NORM, [2] = Qavg) is copied
- * to d_infos[e * CRUX_INFO_N] (DEVICE memory, n_epochs rows) by the recorded list itself; the caller fetches the rows when it wants them (crux_ctx_sync +
- * crux_memcpy_d2h). Meant for the iteration loop of solve(::OffPolicySolver) (off_policy.jl:133-147): the host records and enqueues iteration k + 1 (steps!,
- * value_training, target update) while the device runs iteration k -- up to three chains ahead. A NaN gradient norm skips the update on the device as always
- * (training.jl:20) and shows as NaN in the row; the "NaN detected!" error is the caller's to raise when it reads the rows. CRUX_EUNSUP: the networks do not take
- * the recorded form (narrower than the dense engine's minimum width) -- use crux_dqn_epochs.                                                               */
-int32_t crux_dqn_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                              uint64_t sample_counter0, int32_t n_epochs, float* d_infos);
-/* value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111: the epoch loop, then `target_update(pi_minus, pi)` once, :108), without the host:
- * the chain of crux_dqn_epochs_async (softq_alpha > 0: of crux_softq_epochs_async) with polyak_average!(target_net, net, tau) (src/utils.jl polyak_average!) as an op of the
- * chain's last phase instead of a launch of its own. tau < 0: no target update. Same results, bit for bit, as the async entry followed by crux_polyak.                   */
-int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos);
+/* The same epoch loop with softq_target(alpha) (rl/softq.jl:4-13) in place of dqn_target: value_training of the SoftQ solver (rl/softq.jl:31-58). CRUX_EINVAL unless alpha > 0. */
 int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
                           uint64_t sample_counter0, int32_t n_epochs, float* infos);
-int32_t crux_softq_epochs_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                          uint64_t sample_counter0, int32_t n_epochs, float* d_infos);      /* the same without the host in the loop (see crux_dqn_epochs_async) */
+/* value_training of the DQN family INCLUDING its target update (off_policy.jl:66-111: the epoch loop, then `target_update(pi_minus, pi)` once, :108) without the host in the
+ * loop: nothing is read back, nothing is waited for. The info row of epoch e (LOSS, GRAD_NORM, [2] = Qavg) is written to d_infos[e * CRUX_INFO_N] (DEVICE memory, n_epochs
+ * rows) by the recorded list itself; the caller fetches the rows when it wants them (crux_ctx_sync + crux_memcpy_d2h). polyak_average!(target_net, net, tau) (src/utils.jl) is
+ * an op of the chain's last phase instead of a launch of its own; tau < 0: no target update. Same results, bit for bit, as crux_dqn_epochs / crux_softq_epochs followed by
+ * crux_polyak. Meant for the iteration loop of solve(::OffPolicySolver) (off_policy.jl:133-147): the host records and enqueues iteration k + 1 (steps!, value_training, target
+ * update) while the device runs iteration k -- up to three chains ahead. A NaN gradient norm skips the update on the device as always (training.jl:20) and shows as NaN in the
+ * row; the "NaN detected!" error is the caller's to raise when it reads the rows.
+ * softq_alpha selects the target: == 0 means dqn_target, > 0 softq_target(softq_alpha); < 0 is CRUX_EINVAL. A SoftQ caller must pass alpha > 0 -- with 0 this entry would train
+ * its solver as a DQN without a word (crux_softq_epochs and crux_softq_target refuse alpha <= 0; this entry cannot, 0 being its way to say DQN).
+ * CRUX_EUNSUP: the networks do not take the recorded form (narrower than the dense engine's minimum width) -- use crux_dqn_epochs / crux_softq_epochs.                  */
+int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
+                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos);
 /* One epoch of value_training with SAC's pieces (off_policy.jl:69-104, rl/sac.jl:4-52,94-104) as one recorded op list (30 phases, see crux_dqn_epoch): rand! -> sac_target ->
  * train!(log_alpha, sac_temp_loss) -> [update_critic: train!(critic, double_Q_loss)] -> [update_actor: train!(actor, sac_actor_loss), then
  * polyak_average!(target, online, tau) for the actor (when actor_targ != NULL) and both critics (:100)]. The three exploration draws use noise counters
@@ -574,7 +571,7 @@ int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
                         crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
                         float* infos_temp, float* infos_critic, float* infos_actor);
-/* The same chains without the host in the loop (see crux_dqn_epochs_async): nothing is read back or waited for; d_infos is DEVICE memory, [n_epochs][3][CRUX_INFO_N] =
+/* The same chains without the host in the loop (see crux_dqn_value_training_async): nothing is read back or waited for; d_infos is DEVICE memory, [n_epochs][3][CRUX_INFO_N] =
  * the temperature | critic | actor info rows of every epoch, copied there by the recorded lists themselves (rows of steps an epoch skips stay untouched).          */
 int32_t crux_sac_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                               crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
@@ -589,7 +586,7 @@ int32_t crux_sac_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_
 int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor);
-/* The same chains without the host in the loop (see crux_dqn_epochs_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows.      */
+/* The same chains without the host in the loop (see crux_dqn_value_training_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows.      */
 int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos);

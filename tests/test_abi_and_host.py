@@ -32,6 +32,16 @@ def test_binding_table_covers_the_header():
     assert sorted(L.SIGNATURES) == header_symbols()
 
 
+def test_retired_dqn_async_entries_are_gone_from_library_and_header():
+    # crux_dqn_value_training_async (tau < 0: no target update) is the one asynchronous entry of the DQN family
+    lib = C.CDLL(crux.LIB_PATH)
+    txt = open(os.path.join(ROOT, "include", "cruxhip.h")).read()
+    for name in ("crux_dqn_epochs_async", "crux_softq_epochs_async"):
+        assert not hasattr(lib, name), "still exported: " + name
+        assert name not in txt and name not in L.SIGNATURES
+    assert hasattr(lib, "crux_dqn_value_training_async")
+
+
 def test_struct_layouts_match_the_header_sizes():
     # crux_rollout_cfg / crux_train_cfg are passed by pointer: sizes must match the C definitions (natural alignment)
     assert C.sizeof(L.RolloutCfg) == 72 and C.sizeof(L.TrainCfg) == 64

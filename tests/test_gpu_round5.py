@@ -115,7 +115,7 @@ def test_c3_solve_on_the_one_million_row_prioritized_ring(gpu_ctx, forced):
         if forced:      # the oracle's state of this moment into the GPU twins
             g.set_params(o.params.copy()); g.set_adam_state(*o.adam_state()); sv.agent.pi_minus.set_params(ot.params.copy())
         crux.solve(sv, mdp)                                               # one iteration (sv.N = dN): steps!, four chained epochs, polyak
-        assert getattr(sv, "_async_unsupported", False) is False          # through the asynchronous chains (crux_dqn_epochs_async)
+        assert getattr(sv, "_async_unsupported", False) is False          # through the asynchronous chains (crux_dqn_value_training_async)
         cfg.i0 = i; oe.rollout(o, cfg, ob, dN)
         written = []
         for ep in range(dN):
