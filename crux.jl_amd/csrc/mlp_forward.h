@@ -1,5 +1,5 @@
 // mlp_forward.h -- value(pi, x) for narrow Chain(Dense...) networks (src/policies.jl:94,120): one workgroup = tiles of FWD_TS samples, activations ping-pong in LDS.
-// Shared by mlp.hip (k_mlp_forward) and env.hip (the small-network solve kernel).
+// Shared by mlp.hip (k_mlp_forward) and small_solve.hip (the small-network solve kernel).
 #pragma once
 #include "common.h"
 

@@ -8,7 +8,7 @@
 #include "common.h"
 #include "exec.h"
 
-// Box-Muller standard normal, first output; identical to the rollout's definition (env.hip, oracle randn_f32).
+// Box-Muller standard normal, first output; identical to the rollout's definition (rollout.h, oracle randn_f32).
 __device__ __forceinline__ float sac_randn(uint64_t seed, uint64_t ctr, uint32_t stream) {
   const crux_u32x4 x = crux_philox(seed, ctr, stream, CRUX_RNG_NOISE);
   const double u1 = crux_u32x2_to_f64(x.v[0], x.v[1]), u2 = crux_u32x2_to_f64(x.v[2], x.v[3]);

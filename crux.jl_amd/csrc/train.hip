@@ -25,12 +25,6 @@ __global__ __launch_bounds__(256) void k_train_generic(TrainArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
-static size_t generic_lds_bytes(const NetDesc& nd) {
-  size_t fl = 0; for (int l = 0; l <= nd.L; ++l) fl += (size_t)nd.dims[l] * TR_CH;
-  fl += 2 * (size_t)nd.maxdim * TR_CH + (size_t)TR_CH * (nd.n_extra > 0 ? nd.n_extra : 1);
-  return fl * sizeof(float);
-}
-
 extern "C" const char* crux_peer_why_text(int why);      // comm.hip
 extern "C" int32_t crux_peer_abort_reason(crux_ctx* c, int32_t* out2);
 // status[4] of a learner launch that ended with CRUX_EHIP: 1 a workgroup of the learner is missing, 2 workgroups on different XCDs, 4 a workgroup missed the abort-latch
@@ -66,7 +60,7 @@ static int32_t fill_args(TrainArgs& a, crux_mlp* net, crux_buffer* buf, const cr
   if (net->nd.dims[0] != buf->obs_dim) return crux_fail(c, CRUX_EINVAL, "train!: network input %d != obs dim %d", net->nd.dims[0], buf->obs_dim);
   memset(&a, 0, sizeof a);
   a.px_timeout = net->ctx->peer_timeout_ticks;
-  a.nd = net->nd; a.p = net->p; a.g = net->g; a.m = net->m; a.v = net->v; a.bp = net->bp; a.eta = net->eta; a.b1 = net->b1; a.b2 = net->b2; a.eps = net->eps;
+  train_args_net(a, net);
   a.S = (const float*)buf->col[CRUX_COL_S]; a.A = buf->col[CRUX_COL_A];
   a.LP = has_col(buf, CRUX_COL_LOGPROB) ? (const float*)buf->col[CRUX_COL_LOGPROB] : nullptr;
   a.ADV = has_col(buf, CRUX_COL_ADVANTAGE) ? (const float*)buf->col[CRUX_COL_ADVANTAGE] : nullptr;

@@ -50,6 +50,10 @@ struct TrainArgs {
   const unsigned* spec_abort;
   void* host_net;            // host-side: the crux_mlp this block was filled from (the dense-engine learner drives its GEMM workspace); never read on the device
 };
+// the network / optimiser fields of the block: theta, its gradient, the Adam moments and beta powers, Adam's hyper-parameters
+inline void train_args_net(TrainArgs& a, const crux_mlp* net) {
+  a.nd = net->nd; a.p = net->p; a.g = net->g; a.m = net->m; a.v = net->v; a.bp = net->bp; a.eta = net->eta; a.b1 = net->b1; a.b2 = net->b2; a.eps = net->eps;
+}
 
 // The minibatch rows are device global memory. Typing the per-step loads as address_space(1) makes them global_load instead of the flat_load a
 // generic pointer compiles to: flat accesses also count on lgkmcnt, so every LDS wait after the prefetch of the next minibatch was issued

@@ -1,9 +1,15 @@
-// train_generic.h -- the shape-generic persistent learner body (train! / batch_train!, src/training.jl:13-55) shared by train.hip and env.hip.
+// train_generic.h -- the shape-generic persistent learner body (train! / batch_train!, src/training.jl:13-55) shared by train.hip and small_solve.hip.
 #pragma once
 #include "train_args.h"
 #include "mfma_helpers.h"      // EPS32F
 
 #define TR_CH 32
+// dynamic LDS of train_generic_run for a network: the carve at the top of its body, in bytes
+static size_t generic_lds_bytes(const NetDesc& nd) {
+  size_t fl = 0; for (int l = 0; l <= nd.L; ++l) fl += (size_t)nd.dims[l] * TR_CH;
+  fl += 2 * (size_t)nd.maxdim * TR_CH + (size_t)TR_CH * (nd.n_extra > 0 ? nd.n_extra : 1);
+  return fl * sizeof(float);
+}
 
 __device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
   // 256 threads = 4 waves. Deterministic: wave butterfly then fixed-order sum of 4 partials.
@@ -15,10 +21,10 @@ __device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
   return t;
 }
 
-// the whole learner as a device function: k_train_generic (train.hip) is this body launched as one workgroup; the small-network solve kernel (env.hip) calls it
+// the whole learner as a device function: k_train_generic (train.hip) is this body launched as one workgroup; the small-network solve kernel (small_solve.hip) calls it
 // once per value_training epoch. 256 threads; sm = dynamic LDS of generic_lds_bytes(nd), red = 4 doubles of LDS.
 __device__ __forceinline__ void train_generic_run(const TrainArgs& a, float* sm, double* red) {
-#pragma clang fp contract(fast)      // train.hip's own mode: the same bits when this body is compiled inside env.hip (built with -ffp-contract=off for the dynamics)
+#pragma clang fp contract(fast)      // train.hip's own mode: the same bits when this body is compiled inside small_solve.hip (built with -ffp-contract=off for the dynamics)
   const NetDesc& nd = a.nd;
   const int tid = threadIdx.x;
   const int L = nd.L, nout = nd.dims[L], od = nd.dims[0];

@@ -1,6 +1,6 @@
 """The restated CartPole as a HOST environment (test helper, not a test module): the four functions a crux.HostMDP needs, stepping with a supplied dynamics function --
 the oracle's (orc_env_step_host, CPU) or the library's test hook (crux_env_step_host, the rollout kernel's own device functions) -- and drawing initial states exactly as
-the device samplers do (csrc/env.hip: env_draw_initial = -0.05 + 0.1 u, u = the four Float64 uniforms of crux_philox(seed, 2 n_resets (+1), env, CRUX_RNG_RESET))."""
+the device samplers do (csrc/rollout.h: env_draw_initial = -0.05 + 0.1 u, u = the four Float64 uniforms of crux_philox(seed, 2 n_resets (+1), env, CRUX_RNG_RESET))."""
 import ctypes as C
 
 import numpy as np

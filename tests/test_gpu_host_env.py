@@ -75,6 +75,37 @@ def test_policy_explore_equals_the_oracle_twin(gpu_ctx, case):
         assert not np.array_equal(ga, ga3)
 
 
+H64_ROWS = [      # the rows of the register-resident shape table (H64_SHAPES, csrc/rollout.h): mdp kind, obs, act, hidden activation
+    ("cartpole_relu", "cartpole", 4, 2, "relu"), ("cartpole_tanh", "cartpole", 4, 2, "tanh"),
+    ("pendulum_relu", "pendulum", 3, 1, "relu"), ("pendulum_tanh", "pendulum", 3, 1, "tanh"),
+    ("synth_17_6_tanh", "synth", 17, 6, "tanh"), ("synth_17_6_relu", "synth", 17, 6, "relu"),
+]
+
+
+@pytest.mark.parametrize("row", H64_ROWS, ids=[r[0] for r in H64_ROWS])
+def test_policy_explore_reproduces_the_rollouts_action_and_logprob_columns(gpu_ctx, row):
+    """The seam the host-stepped environments rest on, on every row of the shape table: crux_policy_explore on the observations a device rollout saw (its :s column), with the
+    rollout's own draw counters, gives the rollout's :a column exactly and its :logprob column bit for bit -- k_explore_h64 and k_rollout_h64 are dispatched from one table."""
+    _, kind, od, ad, act = row
+    E, T, seed, i0 = 3, 4, 515, 40
+    ch = parity.chain([od, 64, 64, ad], [act, act, "identity"])
+    if kind == "cartpole":
+        pi, mdp, head = crux.DiscreteNetwork(ch, [1, 2], seed=13, stream=0), crux.CartPoleMDP(n_envs=E, seed=seed), "categorical"
+    else:
+        pi, head = crux.GaussianPolicy(ch, np.full(ad, -0.4, np.float32), seed=13, stream=0), "gaussian"
+        mdp = crux.PendulumMDP(n_envs=E, seed=seed) if kind == "pendulum" else crux.SynthMDP(od, ad, n_envs=E, seed=seed)
+    buf = crux.ExperienceBuffer(mdp.state_space(), mdp.action_space(), E * T, ["logprob"])
+    smp = crux.Sampler(mdp, pi, max_steps=100, required_columns=["logprob"])      # fresh: every environment has taken 0 steps
+    crux.steps_(smp, buf, Nsteps=E * T, explore=True, i=i0)
+    S, A, LP = buf["s"], buf["a"], buf["logprob"]
+    assert np.isfinite(LP).all()
+    for t in range(T):
+        rows = np.arange(E) * T + t                                              # env-major block: row e*T + t
+        a, lp = crux.policy_explore(pi, _cfg(head, i0=i0 + t * E), S[:, rows], seed, np.full(E, t, np.int64))
+        assert np.array_equal(a, A[:, rows]), "step %d: actions differ" % t
+        assert np.array_equal(np.isnan(lp), np.isnan(LP[0, rows])) and np.array_equal(lp.view(np.uint32), np.ascontiguousarray(LP[0, rows]).view(np.uint32)), "step %d: logprob differs" % t
+
+
 def _host_cartpole(ctx, E, seed):
     return crux.HostMDP(H.cartpole_initialstate(seed), H.cartpole_gen(H.device_step(ctx)), H.cartpole_isterminal, H.cartpole_observation, 4, 2, True, n_envs=E, seed=seed, discount=0.99)
 

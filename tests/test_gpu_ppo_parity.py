@@ -148,6 +148,33 @@ def test_batched_rollouts_match_single_rollouts(gpu_ctx):
 
 
 @pytest.mark.gpu
+def test_batched_rollouts_match_single_rollouts_on_the_pendulum_row(gpu_ctx):
+    """The same on a second row of the rollout kernels' shape table: two Pendulum problems with a 3-64-64-1 tanh GaussianPolicy."""
+    import os
+    from parity import crux
+    if os.environ.get("CRUX_FORCE_GENERIC"):
+        pytest.skip("the debug switch routes the single rollouts to the generic kernel, the batched launch exists for the register-resident one only")
+    n, E, T = 2, 2, 5
+    def build():
+        out = []
+        for r in range(n):
+            pi = crux.GaussianPolicy(parity.chain([3, 64, 64, 1], ["tanh", "tanh", "identity"]), np.full(1, -0.3, np.float32), seed=80 + r, stream=0)
+            mdp = crux.PendulumMDP(n_envs=E, seed=400 + r)
+            buf = crux.ExperienceBuffer(mdp.state_space(), mdp.action_space(), E * T, ["return", "logprob"])
+            out.append((buf, crux.Sampler(mdp, pi, max_steps=3, required_columns=["return", "logprob"])))
+        return out
+    pa, pb = build(), build()
+    ia = crux.steps_multi_([q[1] for q in pa], [q[0] for q in pa], Nsteps=E * T, explore=True, i=0, reset=True)
+    ib = [crux.steps_(q[1], q[0], Nsteps=E * T, explore=True, i=0, reset=True) for q in pb]
+    for r in range(n):
+        for k in pa[r][0].keys():
+            ca, cb = pa[r][0][k], pb[r][0][k]
+            assert np.array_equal(ca.view(np.uint32), cb.view(np.uint32)) if ca.dtype == np.float32 else np.array_equal(ca, cb), (r, k)
+        assert ia[r]["n_episode_end"] == ib[r]["n_episode_end"] > 0 and ia[r]["sum_r"] == ib[r]["sum_r"]
+    assert not np.array_equal(pa[0][0]["s"], pa[1][0]["s"])
+
+
+@pytest.mark.gpu
 def test_synced_training_equals_plain_call_without_and_with_a_group_of_one(gpu_ctx):
     """crux_policy_gradient_training_synced: the learner launched per chunk of `sync_every` epochs (+ the stream-ordered RCCL all-reduce of
     parameters and Adam moments) must equal the single-launch call bit for bit when there is nothing to average: (1) no communicator,
