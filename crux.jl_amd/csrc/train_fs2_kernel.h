@@ -170,8 +170,25 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   constexpr int NACT = (OUT > 4 ? OUT : 4);
   constexpr bool BK_LDS = PX && Lt::BK_FITS;
   if ((int)(blockIdx.x & 7) != a.xcd) return;        // the four workgroups of the learner: blocks x, x + 8, x + 16, x + 24 -> one XCD
+  // Arguments that are read once per launch or once per epoch are read WHERE THEY ARE USED, from the kernarg segment (TrainArgs is the kernel's only argument: offset 0) through
+  // a pointer the compiler cannot see through: every `a.field` is loaded at the kernel's entry, and a field with a use behind the minibatch loop (p, m, v, bp, status, the shuffle
+  // arguments, the column pointers of the un-packed rows ...) then stays live across it -- the scalar file has 102 registers, and what does not fit is spilled into VGPR lanes and
+  // read back with v_readlane inside the step (no scratch, so the resource tables never showed it). `a.field` remains for what is read before the loops only, and
+  // for what a step itself reads (xbuf, xctr, PACK and its offsets, lag).
+  // PT: a form that keeps the parent's text at every one of these sites (the rule of DESIGN 4.1: a form that gains a VGPR spill keeps it) -- the periodic replica-group form of the
+  // 27-input Gaussian head, at 256 vector registers with 61 spilled either way. There ka() is the plain kernarg pointer (the compiler hoists its loads to the entry, as it does
+  // a.field), smr is sm, and the predicates, the KL test, the carried order_nxt and the packed rows' scalars are written as before.
+  constexpr bool PT = PXK && IN >= 27 && KIND == MFK_GAUSSIAN;
+  auto ka = [&]() { auto* q = (const __attribute__((address_space(4))) TrainArgs*)__builtin_amdgcn_kernarg_segment_ptr(); if constexpr (!PT) asm volatile("" : "+s"(q)); return q; };
   const int p = (int)(blockIdx.x >> 3);
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  // smr: sm again, for the words of the reduction area (statistics, group-barrier counters, step flags, thread 0's report). Their addresses are constants; written through sm the
+  // compiler hoists each one out of the loops into a scalar register of its own (some twenty), and copies it to a vector register for every LDS instruction. Formed from ONE
+  // register it cannot see through, they are immediate offsets of the instructions. (A scalar register: from a vector one the compiler takes every word read this way, and
+  // every branch on it, for divergent.)
+  typedef __attribute__((address_space(3))) float lds_f32;
+  lds_f32* red3 = (lds_f32*)(sm + Lt::oRED); if constexpr (!PT) asm volatile("" : "+s"(red3));
+  float* const smr = (float*)red3 - Lt::oRED;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
   const bool cw = w < NWC;                           // compute wave
   const int wt = w & (NWC - 1);                      // (tile, half) role: of the tile work for a compute wave, of the staging work for a helper
@@ -186,7 +203,9 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   float* T2 = sm + Lt::oT2 + t * Lt::TILE2;
   constexpr int n_extra = (KIND == MFK_GAUSSIAN) ? OUT : 0;
   unsigned long long tacc[16]; unsigned long long tlast = 0;
-  if (TIMING) { for (int k = 0; k < 16; ++k) tacc[k] = 0; tlast = __builtin_amdgcn_s_memtime(); }
+  // (the sixteen accumulators live in vector registers: as uniform 64-bit values they were 32 scalar registers, the largest single spill source of the timing forms, whose
+  //  instruction stream is meant to be the plain kernels' plus the clock reads)
+  if (TIMING) { for (int k = 0; k < 16; ++k) { tacc[k] = 0; asm volatile("" : "+v"(tacc[k])); } tlast = __builtin_amdgcn_s_memtime(); }
 #define FS2_T(ph) do { if (TIMING) { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tacc[ph] += tn - tlast; tlast = tn; } } while (0)
   const int t_wr = (4 * g) * 16 + 4 * ((c >> 2) ^ fs_tx(g)) + (c & 3);
   const int t_rd = c * 16 + 4 * (g ^ fs_tx(c >> 2));
@@ -203,7 +222,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     sm[Lt::oW2R + o * FS_LD + i] = v; sm[Lt::oW2C + i * FS_LD + o] = v; }
   for (int q = tid; q < MF_HID * Lt::W1LD; q += NT) sm[Lt::oW1R + q] = 0.f;
   if (tid < 16) { sm[Lt::oB3 + tid] = 0.f; sm[Lt::oEX + tid] = 0.f; }
-  if (tid < 32) sm[Lt::oRED + tid] = 0.f;            // statistics, group-barrier counters and step flags start from zero
+  if (tid < 32) smr[Lt::oRED + tid] = 0.f;            // statistics, group-barrier counters and step flags start from zero
   for (int q = tid; q < TILES * Lt::PART; q += NT) sm[Lt::oPART + q] = 0.f;
   uint32_t my_xcc = 0;
   if (tid == 0) { asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc)); my_xcc &= 0xf;
@@ -219,6 +238,14 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   AdamK ak; ak.b1 = (float)a.b1; ak.b2 = (float)a.b2; ak.omb1 = (float)(1.0 - a.b1); ak.omb2 = (float)(1.0 - a.b2); ak.eps = (float)a.eps; ak.eta = (float)a.eta;
   const double db1 = a.b1, db2 = a.b2;
   const float lambda_p = a.lambda_p, lambda_e = a.lambda_e, target_kl = a.target_kl, squash = a.squash;
+  // KL early stopping is on: one scalar word. (As the comparison target_kl >= 0 -- a vector compare, there is no scalar one -- it is a 64-bit lane mask that every use reads back.)
+  int kl_word = 0; if constexpr (!PT) { kl_word = __builtin_amdgcn_readfirstlane((KIND != MFK_VALUE && target_kl >= 0.f) ? 1 : 0); asm volatile("" : "+s"(kl_word)); }
+  auto kl_on = [&]() -> bool { if constexpr (KIND == MFK_VALUE) return false; else if constexpr (PT) return target_kl >= 0.f; else return kl_word != 0; };
+  // ... and the bound the KL statistic is held against: target_kl, or +inf where early stopping is off (x > kl_thr == early stopping on && x > target_kl for every x, NaN included)
+  const float kl_thr = PT ? 0.f : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (KIND != MFK_VALUE && target_kl >= 0.f) ? target_kl : INFINITY)));
+  auto kl_over = [&](float x) -> bool { if constexpr (KIND == MFK_VALUE) return false; else if constexpr (PT) return target_kl >= 0.f && x > target_kl; else return x > kl_thr; };
+  // thread 0's work (the report, the status words) sits on cold paths: its predicate is formed there, not kept as a lane mask across the step
+  auto is_t0 = [&]() -> bool { int t_ = tid; if constexpr (!PT) asm volatile("" : "+v"(t_)); return t_ == 0; };
   float pen = 0.f;                                     // lagrange_ppo_loss: the penalty of the current minibatch; the controller's state sits in LDS, one copy per wave
   float* lgs = sm + Lt::oLGS + 8 * w;                  // [I, smooth_delta, smooth_Jc, Jc_prev, deriv_term, penalty, cur_cost, -]
   if constexpr (LAG) { if (lane == 0) { lgs[0] = a.lag->I; lgs[1] = a.lag->smooth_delta; lgs[2] = a.lag->smooth_Jc; lgs[3] = a.lag->Jc_prev; lgs[4] = a.lag->deriv_term; lgs[5] = a.lag->penalty; lgs[6] = a.lag->cur_cost; lgs[7] = 0.f; } }
@@ -244,7 +271,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   const int max_batches = a.max_batches > 0 && a.max_batches < 0x7fffffffll ? (int)a.max_batches : 0;
   const int bs = a.bs;
 
-  int32_t* order_cur = a.order_a; int32_t* order_nxt = a.order_b;
+  int32_t* order_cur = a.order_a; int32_t* order_nxt_pt = a.order_b;      // (order_nxt_pt: carried across the launch in the PT forms only)
   int total_batches = 0; int epochs_run = 0, err = 0, why_failed = 0; bool stop = false;
   bool staged = false;
   unsigned xstep = 0;                                // exchanges of this launch: every group-barrier target and both arrival counters are multiples of xstep + 1
@@ -253,6 +280,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   if (!a.ord_all) { for (int64_t j = tid; j < a.len; j += NT) order_cur[j] = (int32_t)j; }
   if (!a.ord_all && a.pre_epochs > 0) {
     __syncthreads();
+    int32_t* order_nxt = a.order_b;
     for (int pe = 0; pe < a.pre_epochs; ++pe) {
       if (a.pre_perms) { for (int64_t j = tid; j < a.len; j += NT) order_nxt[j] = order_cur[a.pre_perms[(int64_t)pe * a.len + j]]; }
       else { const crux_perm pp = crux_perm_make(a.pre_seed, a.pre_counter + (uint64_t)pe, 0, (uint32_t)a.len);
@@ -260,6 +288,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
       __syncthreads();
       int32_t* tq = order_cur; order_cur = order_nxt; order_nxt = tq;
     }
+    order_nxt_pt = order_nxt;
   }
   __syncthreads();
   const int total_rows = (int)a.len;
@@ -269,46 +298,81 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   // the end of a minibatch step after B_b, identical in every thread of the workgroup (its inputs are LDS words published before the barrier): the KL statistic and the loop exits.
   // false = the minibatch loop ends here.
   auto step_exit = [&](float invB, bool any_bad) -> bool {
-    if (KIND != MFK_VALUE && target_kl >= 0.f) inf_kl = sm[Lt::oRED + 8 + 2] * invB;
-    if (any_bad) { if (tid == 0) sm[Lt::iGN] = NAN; err = CRUX_ENAN; return false; }      // training.jl:20: no update
+    if (kl_on()) inf_kl = smr[Lt::oRED + 8 + 2] * invB;
+    if (any_bad) { if (is_t0()) smr[Lt::iGN] = NAN; err = CRUX_ENAN; return false; }      // training.jl:20: no update
     total_batches += 1;
     if (max_batches > 0 && total_batches >= max_batches) return false;                // training.jl:45
-    if (target_kl >= 0.f && KIND != MFK_VALUE && inf_kl > target_kl) return false;    // :46
+    if (kl_over(inf_kl)) return false;    // :46
     return true;
   };
   // both roles run the same epoch prologue (same barriers): the speculative-run consensus and the epoch's shuffle order. false = leave the epoch loop.
   auto epoch_prologue = [&](int ep) -> bool {
-    if (a.spec_abort) {
-      if (tid == 0) {
-        const unsigned r = __hip_atomic_load(a.spec_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        (void)__hip_atomic_fetch_or(a.xctr + 16, r ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        (void)__hip_atomic_fetch_add(a.xctr + 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned want = (unsigned)NWG * (unsigned)(ep + 1); unsigned spins = 0; bool late = false;
-        while (__hip_atomic_load(a.xctr + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) { __builtin_amdgcn_s_sleep(2); if (++spins > (1u << 24)) { late = true; break; } }
-        if (late) { (void)__hip_atomic_fetch_or(a.xctr + 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        sm[Lt::oRED + 17] = late ? 2.f : (__hip_atomic_load(a.xctr + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1.f : 0.f); }
-      __syncthreads();
-      if (sm[Lt::oRED + 17] == 2.f) { err = CRUX_EHIP; why_failed = 4; return false; }
-      if (sm[Lt::oRED + 17] != 0.f) { err = CRUX_TRAIN_ABORTED; return false; }
+    if constexpr (PT) {      // the text from before the arguments were read at their use, word for word (reading `a`, two exits, the carried order_nxt)
+      if (a.spec_abort) {
+        if (tid == 0) {
+          const unsigned r = __hip_atomic_load(a.spec_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          (void)__hip_atomic_fetch_or(a.xctr + 16, r ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          (void)__hip_atomic_fetch_add(a.xctr + 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned want = (unsigned)NWG * (unsigned)(ep + 1); unsigned spins = 0; bool late = false;
+          while (__hip_atomic_load(a.xctr + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) { __builtin_amdgcn_s_sleep(2); if (++spins > (1u << 24)) { late = true; break; } }
+          if (late) { (void)__hip_atomic_fetch_or(a.xctr + 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+          smr[Lt::oRED + 17] = late ? 2.f : (__hip_atomic_load(a.xctr + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1.f : 0.f); }
+        __syncthreads();
+        if (smr[Lt::oRED + 17] == 2.f) { err = CRUX_EHIP; why_failed = 4; return false; }
+        if (smr[Lt::oRED + 17] != 0.f) { err = CRUX_TRAIN_ABORTED; return false; }
+      }
+      if (a.ord_all) order_cur = const_cast<int32_t*>(a.ord_all) + (size_t)ep * (size_t)a.len;   // shuffle orders composed ahead of time by k_compose_order
+      else {   // shuffle!(D) as an index composition (experience_buffer.jl:118-124)
+        // (the thread index is laundered: from the plain `tid` the compiler hoists the 64-bit element addresses of this once-per-epoch loop out of the epoch loop and keeps them
+        //  alive across the whole launch -- in scratch, in the forms that sit at the 256-register limit: the two spilled dwords of the C5 periodic form, round 6)
+        int tidl = tid; asm volatile("" : "+v"(tidl));
+        if (a.perms) { for (int64_t j = tidl; j < a.len; j += NT) order_nxt_pt[j] = order_cur[a.perms[(int64_t)ep * a.len + j]]; }
+        else { const crux_perm pp = crux_perm_make(a.shuffle_seed, a.shuffle_counter + (uint64_t)ep, 0, (uint32_t)a.len);
+          for (int64_t j = tidl; j < a.len; j += NT) order_nxt_pt[j] = order_cur[crux_perm_at(&pp, (uint32_t)j)]; }
+        __syncthreads();
+        int32_t* tq = order_cur; order_cur = order_nxt_pt; order_nxt_pt = tq;
+      }
+      return true;
+    } else {
+      const auto* k = ka();
+      if (const unsigned* const spec_abort = k->spec_abort) {
+        if (is_t0()) { unsigned* const xctr = k->xctr;
+          const unsigned r = __hip_atomic_load(spec_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          (void)__hip_atomic_fetch_or(xctr + 16, r ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          (void)__hip_atomic_fetch_add(xctr + 17, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned want = (unsigned)NWG * (unsigned)(ep + 1); unsigned spins = 0; bool late = false;
+          while (__hip_atomic_load(xctr + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) { __builtin_amdgcn_s_sleep(2); if (++spins > (1u << 24)) { late = true; break; } }
+          if (late) { (void)__hip_atomic_fetch_or(xctr + 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+          smr[Lt::oRED + 17] = late ? 2.f : (__hip_atomic_load(xctr + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1.f : 0.f); }
+        __syncthreads();
+        // (one exit that writes both words: two exits, one of which writes err alone, were merged into a store through a selected address, and err / why_failed then live in scratch)
+        if (const float verdict = smr[Lt::oRED + 17]; verdict != 0.f) { const bool late = verdict == 2.f; err = late ? CRUX_EHIP : CRUX_TRAIN_ABORTED; why_failed = late ? 4 : 0; return false; }
+      }
+      if (const int32_t* const ord_all = k->ord_all) order_cur = const_cast<int32_t*>(ord_all) + (size_t)ep * (size_t)k->len;   // shuffle orders composed ahead of time by k_compose_order
+      else {   // shuffle!(D) as an index composition (experience_buffer.jl:118-124)
+        // (the thread index is laundered: from the plain `tid` the compiler hoists the 64-bit element addresses of this once-per-epoch loop out of the epoch loop and keeps them
+        //  alive across the whole launch -- in scratch, in the forms that sit at the 256-register limit: the two spilled dwords of the C5 periodic form, round 6)
+        int tidl = tid; asm volatile("" : "+v"(tidl));
+        // (the order that is not the current one: named from the arguments here, not carried across the minibatch loop)
+        const int epl = __builtin_amdgcn_readfirstlane(ep);      // (from the plain `ep` the row offset ep * len * 8 becomes a 64-bit induction variable carried across the minibatch loop)
+        const int64_t len = k->len; const int64_t* const perms = k->perms; int32_t* const order_nxt = order_cur == k->order_a ? k->order_b : k->order_a;
+        if (perms) { for (int64_t j = tidl; j < len; j += NT) order_nxt[j] = order_cur[perms[(int64_t)epl * len + j]]; }
+        else { const crux_perm pp = crux_perm_make(k->shuffle_seed, k->shuffle_counter + (uint64_t)epl, 0, (uint32_t)len);
+          for (int64_t j = tidl; j < len; j += NT) order_nxt[j] = order_cur[crux_perm_at(&pp, (uint32_t)j)]; }
+        __syncthreads();
+        order_cur = order_nxt;
+      }
+      return true;
     }
-    if (a.ord_all) order_cur = const_cast<int32_t*>(a.ord_all) + (size_t)ep * (size_t)a.len;   // shuffle orders composed ahead of time by k_compose_order
-    else {   // shuffle!(D) as an index composition (experience_buffer.jl:118-124)
-      // (the thread index is laundered: from the plain `tid` the compiler hoists the 64-bit element addresses of this once-per-epoch loop out of the epoch loop and keeps them
-      //  alive across the whole launch -- in scratch, in the forms that sit at the 256-register limit: the two spilled dwords of the C5 periodic form, round 6)
-      int tidl = tid; asm volatile("" : "+v"(tidl));
-      if (a.perms) { for (int64_t j = tidl; j < a.len; j += NT) order_nxt[j] = order_cur[a.perms[(int64_t)ep * a.len + j]]; }
-      else { const crux_perm pp = crux_perm_make(a.shuffle_seed, a.shuffle_counter + (uint64_t)ep, 0, (uint32_t)a.len);
-        for (int64_t j = tidl; j < a.len; j += NT) order_nxt[j] = order_cur[crux_perm_at(&pp, (uint32_t)j)]; }
-      __syncthreads();
-      int32_t* tq = order_cur; order_cur = order_nxt; order_nxt = tq;
-    }
-    return true;
   };
   auto epoch_epilogue = [&](int ep) {
-    if (tid == 0 && p == 0 && a.epoch_infos) epoch_info_row<Lt, KIND, LAG>(a.epoch_infos + (size_t)ep * CRUX_INFO_N, sm, inf_kl);
+    int p_ = p; if constexpr (!PT) asm volatile("" : "+s"(p_));      // (a scalar compare here; from the plain `p` the compiler keeps p == 0 as a lane mask across the step for the write-back's sake)
+    if constexpr (PT) { if (tid == 0 && p == 0 && ka()->epoch_infos) epoch_info_row<Lt, KIND, LAG>(ka()->epoch_infos + (size_t)ep * CRUX_INFO_N, smr, inf_kl); } else
+    if (p_ == 0) { if (is_t0()) if (float* const infos = ka()->epoch_infos) epoch_info_row<Lt, KIND, LAG>(infos + (size_t)ep * CRUX_INFO_N, smr, inf_kl); }
     epochs_run += 1;
-    if (target_kl >= 0.f && KIND != MFK_VALUE && inf_kl > target_kl) stop = true;   // training.jl:49
+    if (kl_over(inf_kl)) stop = true;   // training.jl:49
     if (max_batches > 0 && total_batches >= max_batches) stop = true;               // :50
   };
 
@@ -415,7 +479,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
-      const bool dead = fs2_flag_get(sm + Lt::fERR) != 0u, sus = check_suspect && fs2_flag_get(sm + Lt::fSUS) == tag;
+      const bool dead = fs2_flag_get(smr + Lt::fERR) != 0u, sus = check_suspect && fs2_flag_get(smr + Lt::fSUS) == tag;
       bool ok = !dead && !sus;
       if (ok) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
@@ -426,19 +490,19 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
           __hip_atomic_store((unsigned long long*)(a.px_tab[r] + CRUX_PX_FLAGS) + 8 * a.px_rank, xg + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
         const long long t0 = wall_clock64();                // 100 MHz; the wait is bounded four ways (peer_wait.h): a peer that is absent, slow, gone, or a host that calls the launch off
         const unsigned gave_up = px_wait_peers(px_mine, a.px_n, a.px_rank, xg + 1ull, t0, a.px_timeout, p, true);
-        if (gave_up) { ok = false; fs2_flag_set(sm + Lt::fERR, 16u + gave_up); }      // 16 + bound: the replica group ended this launch (train.hip names the bound)
+        if (gave_up) { ok = false; fs2_flag_set(smr + Lt::fERR, 16u + gave_up); }      // 16 + bound: the replica group ended this launch (train.hip names the bound)
         if (a.px_hist) {      // how long this workgroup waited for the slowest peer's flag (10 ns ticks, log2 bins; workgroups 0 and 1 report)
           const unsigned long long dtk = (unsigned long long)(wall_clock64() - t0) | 1ull;
           if (p < 2) { unsigned* hb = (unsigned*)(px_mine + CRUX_PX_HIST) + 32 * p + (63 - __builtin_clzll(dtk) > 31 ? 31 : 63 - __builtin_clzll(dtk)); *hb = *hb + 1u; } }
       }
       if (!ok) {      // this learner leaves the group (failure, or a NaN step): the peers must not wait for it
-        { const unsigned e = fs2_flag_get(sm + Lt::fERR); px_raise_abort(a.px_tab, a.px_n, sus && !dead ? 5u : (e >= 16u ? e - 16u : 1u)); }      // the bound that fired (5: left on a NaN step)
+        { const unsigned e = fs2_flag_get(smr + Lt::fERR); px_raise_abort(a.px_tab, a.px_n, sus && !dead ? 5u : (e >= 16u ? e - 16u : 1u)); }      // the bound that fired (5: left on a NaN step)
         if (!sus || dead) __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                       // system scope, one lane: drops this compute unit's L1 (the slot loads below bypass it anyway: sc0 sc1)
     }
     __syncthreads();
-    if (fs2_flag_get(sm + Lt::fERR) != 0u) return 1;
-    if (check_suspect && fs2_flag_get(sm + Lt::fSUS) == tag) return 2;
+    if (fs2_flag_get(smr + Lt::fERR) != 0u) return 1;
+    if (check_suspect && fs2_flag_get(smr + Lt::fSUS) == tag) return 2;
     // the slots are read one rank at a time (all loads of a rank in flight together) and added in rank order; the own contribution comes from the registers
     f32x4 oW[NSEC][WT]; float oS[NSEC][NSC]; const float oT = xT;
 #pragma unroll
@@ -526,13 +590,13 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     for (int k = 0; k < NSC; ++k) gran_put(tid + NT * k, gs[k]);
     if (stat_lane) gran_put(Lt::gST + misc_k(), stat_loc);
     FS2_T(9);
-    fs2_flag_wait(sm + Lt::fP1, tag);           // phase 1 is complete (or has failed): every workgroup's W2 partials are in the L2
+    fs2_flag_wait(smr + Lt::fP1, tag);           // phase 1 is complete (or has failed): every workgroup's W2 partials are in the L2
     FS2_T(10);
-    bool failed = fs2_flag_get(sm + Lt::fERR) != 0u;
+    bool failed = fs2_flag_get(smr + Lt::fERR) != 0u;
     f32x4 pw[NWG - 1][WT];
     if (!failed) w2_loads(pw);
     float ssq = 0.f; bool bad_tot = false;
-    const bool want_ssq = static_report(st_now) || (KIND != MFK_VALUE && target_kl >= 0.f);      // only a step that may report needs the gradient norm
+    const bool want_ssq = static_report(st_now) || kl_on();      // only a step that may report needs the gradient norm
     f32x4 tW2o[BK_LDS ? 1 : WT], mW2o[BK_LDS ? 1 : WT], vW2o[BK_LDS ? 1 : WT];      // the state before this step's update: a suspect step (known after B_b) is undone first
     float* const bk = sm + Lt::oBK + 4 * tid;      // (LDS form: [theta | m | v][tile][thread] x 16 B)
 #pragma unroll
@@ -572,7 +636,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
           for (int k = 0; k < NSC; ++k) { all_in = all_in && (unsigned)(gv[j][k] >> 32) == tag; pg[j][k] = __builtin_bit_cast(float, (unsigned)gv[j][k]); } }
         if (__all(all_in ? 1 : 0)) break;
         if ((++spins & 255u) == 0u && (spins > (1u << 22) || __hip_atomic_load(a.xctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {      // never hang the GPU
-          __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (fs2_flag_get(sm + Lt::fERR) == 0u) fs2_flag_set(sm + Lt::fERR, 1u); failed = true; break; }
+          __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (fs2_flag_get(smr + Lt::fERR) == 0u) fs2_flag_set(smr + Lt::fERR, 1u); failed = true; break; }
       }
     }
     FS2_T(11);
@@ -595,7 +659,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         adam_w2(gW2);                            // (every compute wave is past B_2: nobody reads the W2 masters any more)
 #pragma unroll
         for (int k = 0; k < NSC; ++k) bad_tot = bad_tot || (so_ok[k] && isnan(gs[k]));
-        if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
+        if (bad_tot) fs2_flag_set(smr + Lt::fSUS, tag);
       }
     } else if (!failed) {
       if constexpr (!W2_FIRST) { w2_total(gW2, pw); w2_check(gW2, want_ssq, ssq, bad_tot);
@@ -605,14 +669,14 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
       if constexpr (MISC) {
         stat_tot = (stat_loc + ps[0]) + (ps[1] + ps[2]);
         bad_tot = bad_tot || (own_lane && isnan(stat_tot));      // a lane that owns its word: the total is a gradient
-        if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
+        if (bad_tot) fs2_flag_set(smr + Lt::fSUS, tag);
       } else {      // (the dealt map keeps its statement order and with it the parent's instruction stream: with the two statements swapped C5 measured 7.54 -> 7.65 us
                     //  per step, profiles/fs2_misc_lanes_ab.txt)
-        if (bad_tot) fs2_flag_set(sm + Lt::fSUS, tag);
+        if (bad_tot) fs2_flag_set(smr + Lt::fSUS, tag);
         stat_tot = (stat_loc + ps[0]) + (ps[1] + ps[2]);
       }
     }
-    if (stat_lane && !own_lane) sm[Lt::oRED + 8 + (MISC && misc_k() > 7 ? 7 : misc_k())] = stat_tot;      // the statistics of the report (word 7: the lagrange cost term)
+    if (stat_lane && !own_lane) smr[Lt::oRED + 8 + (MISC && misc_k() > 7 ? 7 : misc_k())] = stat_tot;      // the statistics of the report (word 7: the lagrange cost term)
 #pragma unroll
     for (int k = 0; k < NSC; ++k) if (so_ok[k]) {
       if (!MISC && KIND == MFK_GAUSSIAN && so_ex[k]) gs[k] += LAG ? -lambda_e / (1.f + pen) : -lambda_e;       // d(-lambda_e H)/dlogSigma, H = const + sum(logSigma); lagrange: the whole loss is divided by 1 + penalty
@@ -621,7 +685,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
       if (KIND == MFK_GAUSSIAN && misc_k() >= 7 + OUT) stat_tot += LAG ? -lambda_e / (1.f + pen) : -lambda_e;
       if (want_ssq) ssq += stat_tot * stat_tot; } }
     if (want_ssq) { ssq = wave_sum(ssq);
-      if (lane == 0) sm[Lt::oRED + w] = ssq; }      // this wave's share of the gradient norm (the report is formed after B_b)
+      if (lane == 0) smr[Lt::oRED + w] = ssq; }      // this wave's share of the gradient norm (the report is formed after B_b)
     FS2_T(13);
     // Adam on the small parameters (Flux.update!, training.jl:21); the values read here are what a suspect step is put back to
     auto adam_small = [&]() {
@@ -661,7 +725,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     }
     FS2_T(14);
     __syncthreads();   // ---- B_b: masters updated; tiles and partials may be overwritten
-    const unsigned why = fs2_flag_get(sm + Lt::fERR), sus = fs2_flag_get(sm + Lt::fSUS);      // (both reads in flight together: one LDS round trip)
+    const unsigned why = fs2_flag_get(smr + Lt::fERR), sus = fs2_flag_get(smr + Lt::fSUS);      // (both reads in flight together: one LDS round trip)
     if (why != 0u) { err = CRUX_EHIP; why_failed = (int)why; return false; }
     any_bad = 0;
     if (sus == tag) {      // a thread of this workgroup found a NaN total: every thread back to its pre-step state (training.jl:20: error, no update)
@@ -750,7 +814,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
 #pragma unroll
             for (int o = 0; o < OUT; ++o) zq[o] = zp[o]; }
         }
-        fs2_group_barrier(sm + Lt::cPAIR + t, 2u * (xstep + 1u), lane);      // ---- B_z: the pair's partial logits are visible (the two waves of the tile only)
+        fs2_group_barrier(smr + Lt::cPAIR + t, 2u * (xstep + 1u), lane);      // ---- B_z: the pair's partial logits are visible (the two waves of the tile only)
         float dz[OUT], dex[OUT];
         float s_lossp = 0.f, s_H = 0.f, s_kl = 0.f, s_adv = 0.f, s_ret = 0.f, s_clip = 0.f, s_sq = 0.f, s_cost = 0.f;
         float ent_pre = 1.4189385332046727f;
@@ -885,7 +949,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
               acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][r], wv1[r], acc1, 0, 0, 0); } }
           dz1r[0] = acc0; dz1r[1] = acc1; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the dW2 stores left before dH1: acknowledged by now -- tell the helper leader (phase 1)
-        if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(sm + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FS2_T(7);
         float gb1[2], gb2[MH];
 #pragma unroll
@@ -917,26 +981,26 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
             if (16 * jt + c < Lt::W1ROWS) *(f32x4*)&part[Lt::pW1 + (16 * jt + c) * FS_LD + 32 * h + 16 * mm + 4 * g] = acc; }
         }
         FS2_T(8);
-        fs2_group_barrier(sm + Lt::cCOMP, (unsigned)NWC * (xstep + 1u), lane);   // ---- B_2: the small partial gradients of both tiles are visible (compute waves only)
+        fs2_group_barrier(smr + Lt::cCOMP, (unsigned)NWC * (xstep + 1u), lane);   // ---- B_2: the small partial gradients of both tiles are visible (compute waves only)
         const unsigned tag = xstep + 1u;
         int any_bad = 0; st_now = st;
         if (!step_tail(tag, gW2, any_bad)) break;
         // minibatch info (training.jl:22-23, ppo.jl:13-19): identical in every compute thread; only the epoch's last minibatch (or the one that stops the loop) is ever reported
-        if (any_bad || static_report(st) || (KIND != MFK_VALUE && target_kl >= 0.f)) {
-          const float* tq = sm + Lt::oRED + 8;
-          const bool report = any_bad || static_report(st) || (KIND != MFK_VALUE && target_kl >= 0.f && tq[2] * invB > target_kl);
+        if (any_bad || static_report(st) || kl_on()) {
+          const float* tq = smr + Lt::oRED + 8;
+          const bool report = any_bad || static_report(st) || kl_over(tq[2] * invB);
           if (report) {
-            float ss = sm[Lt::oRED];
+            float ss = smr[Lt::oRED];
 #pragma unroll
-            for (int q = 1; q < NW; ++q) ss += sm[Lt::oRED + q];
+            for (int q = 1; q < NW; ++q) ss += smr[Lt::oRED + q];
             if (KIND != MFK_VALUE) inf_kl = tq[2] * invB;
-            if (tid == 0) { sm[Lt::iGN] = sqrtf(ss);
-              if (KIND == MFK_VALUE) { sm[Lt::iLOSS] = tq[6] * invB; sm[Lt::iRET] = tq[4] * invB; }
+            if (is_t0()) { smr[Lt::iGN] = sqrtf(ss);
+              if (KIND == MFK_VALUE) { smr[Lt::iLOSS] = tq[6] * invB; smr[Lt::iRET] = tq[4] * invB; }
               else { const float p_loss = -(tq[0] * invB); const float entropy = KIND == MFK_CATEGORICAL ? tq[1] * invB : ent_pre;
-                sm[Lt::iENT] = entropy; sm[Lt::iLOSS] = fmaf(lambda_p, p_loss, lambda_e * (-entropy)); sm[Lt::iADV] = tq[3] * invB; sm[Lt::iRET] = tq[4] * invB; sm[Lt::iCLIP] = tq[5] * invB;
+                smr[Lt::iENT] = entropy; smr[Lt::iLOSS] = fmaf(lambda_p, p_loss, lambda_e * (-entropy)); smr[Lt::iADV] = tq[3] * invB; smr[Lt::iRET] = tq[4] * invB; smr[Lt::iCLIP] = tq[5] * invB;
                 if constexpr (LAG) { const float cost_loss = pen * (tq[7] * invB);                                        // ppo.jl:119
-                  sm[Lt::iLOSS] = ((lambda_p * p_loss + lambda_e * (-entropy)) + cost_loss) / (1.f + pen);                  // :131   (iPEN / iCUR are wave 0's controller words: current)
-                  sm[Lt::iCLOSS] = cost_loss; sm[Lt::iPLOSS] = lambda_p * p_loss; } } } } }
+                  smr[Lt::iLOSS] = ((lambda_p * p_loss + lambda_e * (-entropy)) + cost_loss) / (1.f + pen);                  // :131   (iPEN / iCUR are wave 0's controller words: current)
+                  smr[Lt::iCLOSS] = cost_loss; smr[Lt::iPLOSS] = lambda_p * p_loss; } } } } }
         const bool go = step_exit(invB, any_bad != 0);
         if (!any_bad) { bp1 *= db1; bp2 *= db2; }
         xcur ^= 1; xstep += 1u; staged = st + bs < total_rows;
@@ -962,6 +1026,13 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     for (int e = 0; e < NXL; ++e) px[e] = 0.f;
     int n_row = 0, n_valid = 0;
     int n_row2 = -1; float p_cost2 = 0.f, p_ee2 = 0.f, p_cadv = 0.f;      // LAG: helper thread ct < 128 carries row ct of the WHOLE minibatch (its :cost and :episode_end); :cost_advantage of the own sample
+    // The packed rows' base and offsets are read by the address arithmetic of the row loads alone (vector instructions): they live in vector registers of this role, which has
+    // them to spare, and not in nine scalar ones (the 64-bit forms of the offsets included) across the step. Whether the rows are packed is one scalar word.
+    constexpr bool PK_V = !PT && !(PXK && IN >= 24 && KIND == MFK_GAUSSIAN);      // (the periodic replica-group forms of the 24- / 27-input Gaussian heads spill vector registers as it is: scalar there)
+    const float* pk_base = a.PACK; int pk_stride = a.pack_stride, pk_lp = a.pack_lp, pk_act = a.pack_act;
+    if constexpr (PK_V) asm volatile("" : "+v"(pk_base), "+v"(pk_stride), "+v"(pk_lp), "+v"(pk_act));
+    int pk_word = 0; if constexpr (!PT) { pk_word = __builtin_amdgcn_readfirstlane(a.PACK ? 1 : 0); asm volatile("" : "+s"(pk_word)); }
+    auto packed = [&]() -> bool { if constexpr (PT) return a.PACK != nullptr; else return pk_word != 0; };
     auto fetch_index = [&](const int32_t* ord, int st, int nb) {
       const int sidx = 8 * NWC * p + 16 * t + c;
       n_valid = sidx < nb ? 1 : 0;
@@ -969,36 +1040,39 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
       if constexpr (LAG) n_row2 = ct < nb ? CRUX_GLOBAL_PTR(int32_t, ord)[st + ct] : -1;
     };
     auto fetch_data = [&]() {
+      // (this call's lane predicates are formed here, from copies the compiler cannot see through: hoisted out of the step they were lane masks that did not fit the scalar file)
+      int h = wt & 1, lane = tid & 63; if constexpr (!PT) asm volatile("" : "+v"(h), "+v"(lane));
       const int rowlo = n_row; p_valid = n_valid; const int64_t row = rowlo;
-      if constexpr (LAG) { p_cost2 = n_row2 >= 0 ? CRUX_GLOBAL_PTR(float, a.COST)[n_row2] : 0.f; p_ee2 = (n_row2 >= 0 && CRUX_GLOBAL_PTR(uint8_t, a.EE)[n_row2]) ? 1.f : 0.f; }
+      if constexpr (LAG) { const auto* k = ka(); p_cost2 = n_row2 >= 0 ? CRUX_GLOBAL_PTR(float, k->COST)[n_row2] : 0.f; p_ee2 = (n_row2 >= 0 && CRUX_GLOBAL_PTR(uint8_t, k->EE)[n_row2]) ? 1.f : 0.f; }
       if (h == 0) {
         const int rs = __shfl(rowlo, lane >> 2, 64), vs = __shfl(p_valid, lane >> 2, 64);
-        const float* xrow = a.PACK ? CRUX_GLOBAL_PTR(float, a.PACK) + (int64_t)rs * a.pack_stride + (lane & 3) * NXL : CRUX_GLOBAL_PTR(float, a.S) + (int64_t)rs * IN + (lane & 3) * NXL;
+        // (the column pointers of the un-packed rows are read from the arguments by the step that needs them: the packed form does not carry them)
+        const float* xrow = packed() ? CRUX_GLOBAL_PTR(float, pk_base) + (int64_t)rs * pk_stride + (lane & 3) * NXL : CRUX_GLOBAL_PTR(float, ka()->S) + (int64_t)rs * IN + (lane & 3) * NXL;
 #pragma unroll
         for (int e = 0; e < NXL; ++e) px[e] = ((lane & 3) * NXL + e < IN && vs) ? xrow[e] : 0.f;
       } else {
         p_lp = 0.f; p_adv = 0.f; p_ret = 0.f; p_cadv = 0.f;
 #pragma unroll
         for (int k = 0; k < NACT; ++k) p_act[k] = 0.f;
-        if (a.PACK && !LAG) {
-          if (lane < 16 && p_valid) { const float* q = CRUX_GLOBAL_PTR(float, a.PACK) + row * a.pack_stride;
-            if (KIND != MFK_VALUE) { p_lp = q[a.pack_lp]; p_adv = q[a.pack_lp + 1]; }
-            p_ret = q[a.pack_lp + 2];
-            if (KIND == MFK_CATEGORICAL) { const int ai = (int)q[a.pack_act];
+        if (packed() && !LAG) {
+          if (lane < 16 && p_valid) { const float* q = CRUX_GLOBAL_PTR(float, pk_base) + row * pk_stride;
+            if (KIND != MFK_VALUE) { p_lp = q[pk_lp]; p_adv = q[pk_lp + 1]; }
+            p_ret = q[pk_lp + 2];
+            if (KIND == MFK_CATEGORICAL) { const int ai = (int)q[pk_act];
 #pragma unroll
               for (int k = 0; k < OUT; ++k) p_abyte[k] = k == ai ? 1 : 0; }
             if (KIND == MFK_GAUSSIAN) {
 #pragma unroll
-              for (int k = 0; k < OUT; ++k) p_act[k] = q[a.pack_act + k]; } }
+              for (int k = 0; k < OUT; ++k) p_act[k] = q[pk_act + k]; } }
         } else
-        if (lane < 16 && p_valid) {
-          if constexpr (LAG) p_cadv = CRUX_GLOBAL_PTR(float, a.CADV)[row];
-          if (KIND != MFK_VALUE) { p_lp = CRUX_GLOBAL_PTR(float, a.LP)[row]; p_adv = CRUX_GLOBAL_PTR(float, a.ADV)[row]; }
-          p_ret = a.RET ? CRUX_GLOBAL_PTR(float, a.RET)[row] : 0.f;
-          if (KIND == MFK_CATEGORICAL) { const auto* av = CRUX_GLOBAL_PTR(uint8_t, a.A) + row * OUT;
+        if (lane < 16 && p_valid) { const auto* k = ka();
+          if constexpr (LAG) p_cadv = CRUX_GLOBAL_PTR(float, k->CADV)[row];
+          if (KIND != MFK_VALUE) { p_lp = CRUX_GLOBAL_PTR(float, k->LP)[row]; p_adv = CRUX_GLOBAL_PTR(float, k->ADV)[row]; }
+          { const float* const RET = k->RET; p_ret = RET ? CRUX_GLOBAL_PTR(float, RET)[row] : 0.f; }
+          if (KIND == MFK_CATEGORICAL) { const auto* av = CRUX_GLOBAL_PTR(uint8_t, k->A) + row * OUT;
 #pragma unroll
             for (int k = 0; k < OUT; ++k) p_abyte[k] = av[k]; }
-          if (KIND == MFK_GAUSSIAN) { const auto* av = CRUX_GLOBAL_PTR(float, a.A) + row * OUT;
+          if (KIND == MFK_GAUSSIAN) { const auto* av = CRUX_GLOBAL_PTR(float, k->A) + row * OUT;
 #pragma unroll
             for (int k = 0; k < OUT; ++k) p_act[k] = av[k]; }
         }
@@ -1057,10 +1131,10 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         f32x4 gW2[WT];
         dw2_send(gW2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every store of this lane has reached the L2 (and the prefetched rows are in)
-        if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(sm + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FS2_T(4);
         if (ct == 0) {
-          fs2_flag_wait(sm + Lt::cACK, (unsigned)NW * tag);        // all eight waves' W2 stores are acknowledged (the compute waves report after dH1)
+          fs2_flag_wait(smr + Lt::cACK, (unsigned)NW * tag);        // all eight waves' W2 stores are acknowledged (the compute waves report after dH1)
           (void)__hip_atomic_fetch_add(a.xctr + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ARRIVAL 1
           const unsigned want = (unsigned)NWG * tag; unsigned spins = 0; bool ok = true;
           while (__hip_atomic_load(a.xctr + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) { __builtin_amdgcn_s_sleep(1);
@@ -1070,11 +1144,11 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
             uint32_t xcc = 0; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); xcc &= 0xf;
             for (int q = 0; q < NWG; ++q) { const unsigned peer_xcc = __hip_atomic_load(a.xctr + 8 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (peer_xcc != xcc + 1u) { ok = false; why = 2u; } } }   // 2: the workgroups of this learner sit on different XCDs
-          if (!ok) { __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (fs2_flag_get(sm + Lt::fERR) == 0u) fs2_flag_set(sm + Lt::fERR, why); }
-          fs2_flag_set(sm + Lt::fP1, tag);
+          if (!ok) { __hip_atomic_store(a.xctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (fs2_flag_get(smr + Lt::fERR) == 0u) fs2_flag_set(smr + Lt::fERR, why); }
+          fs2_flag_set(smr + Lt::fP1, tag);
         }
         FS2_T(5);
-        fs2_flag_wait(sm + Lt::cCOMP, (unsigned)NWC * tag);      // the compute waves have passed B_2: the small partials of both tiles are in LDS, nobody reads the W2 masters (dH1) any more
+        fs2_flag_wait(smr + Lt::cCOMP, (unsigned)NWC * tag);      // the compute waves have passed B_2: the small partials of both tiles are in LDS, nobody reads the W2 masters (dH1) any more
         int any_bad = 0; st_now = st;
         if (!step_tail(tag, gW2, any_bad)) break;
         const bool go = step_exit(invB, any_bad != 0);
@@ -1089,6 +1163,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   }
   // ---- write back parameters, Adam state and the launch status ------------------------------------------------------
   __syncthreads();
+  const auto* kz = ka(); float* const P = kz->p; float* const M = kz->m; float* const V = kz->v;
   if (p == 0) {
     // (the element addresses are formed again from a laundered thread index: shared with the loads at the top of the kernel, the compiler kept the 64-bit addresses alive
     //  across the whole launch -- in scratch, at the 256-register limit of the wide heads)
@@ -1098,18 +1173,18 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     for (int mm = 0; mm < WT; ++mm)
 #pragma unroll
       for (int r = 0; r < 4; ++r) { const int pc = Lt::cW2 + (16 * mp2 + 4 * g2 + r) + H2 * (16 * (m2 + mm) + c2);
-        a.p[pc] = tW2[mm][r]; a.m[pc] = mW2[mm][r]; a.v[pc] = vW2[mm][r]; } }
-  if (p == 0) { for (int s = tid; s < ns_valid; s += NT) { const int pc = s_canon(s); a.p[pc] = sm[s_master(s)]; a.m[pc] = sm[Lt::oMS + s]; a.v[pc] = sm[Lt::oVS + s]; } }
-  if (TIMING && lane == 0 && a.dbg) { for (int k = 0; k < 16; ++k) a.dbg[(NW * p + w) * 16 + k] = tacc[k]; }
+        P[pc] = tW2[mm][r]; M[pc] = mW2[mm][r]; V[pc] = vW2[mm][r]; } }
+  if (p == 0) { for (int s = tid; s < ns_valid; s += NT) { const int pc = s_canon(s); P[pc] = sm[s_master(s)]; M[pc] = sm[Lt::oMS + s]; V[pc] = sm[Lt::oVS + s]; } }
+  if (TIMING && lane == 0) { if (unsigned long long* const dbg = kz->dbg) { for (int k = 0; k < 16; ++k) dbg[(NW * p + w) * 16 + k] = tacc[k]; } }
   if (PX && tid == 0 && p == 0) *(unsigned long long*)(px_mine + CRUX_PX_COUNT) = px0 + (unsigned long long)pxc;
   if constexpr (PX && PXK) {      // periodic form: a replica that leaves on a NaN step between two exchanges will not show up at the next one -- its peers must not wait for the timeout
-    if (tid == 0 && p == 0 && err == CRUX_ENAN) { for (int r = 0; r < a.px_n; ++r) if (r != a.px_rank) __hip_atomic_store((unsigned*)(a.px_tab[r] + CRUX_PX_ABORT), 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } }
-  if (tid == 0 && (p == 0 || err)) {
-    a.status[0] = err; a.status[1] = (int32_t)total_batches; a.status[2] = epochs_run; a.status[3] = (order_cur == a.order_a) ? 0 : 1;
-    if (err == CRUX_EHIP) a.status[4] = why_failed;      // 1 a workgroup of the learner is missing, 2 workgroups on different XCDs, 3 replica group timeout / abort, 4 a workgroup missed the abort-latch consensus
-    a.bp[0] = bp1; a.bp[1] = bp2;
-    if constexpr (LAG) { if (p == 0) { a.lag->I = lgs[0]; a.lag->smooth_delta = lgs[1]; a.lag->smooth_Jc = lgs[2]; a.lag->Jc_prev = lgs[3]; a.lag->deriv_term = lgs[4]; a.lag->penalty = lgs[5]; a.lag->cur_cost = lgs[6]; } }
-    if (err && a.epoch_infos && epochs_run == 0) { a.epoch_infos[CRUX_INFO_LOSS] = sm[Lt::iLOSS]; a.epoch_infos[CRUX_INFO_GRAD_NORM] = NAN; }
+    if (tid == 0 && p == 0 && err == CRUX_ENAN) { for (int r = 0; r < kz->px_n; ++r) if (r != kz->px_rank) __hip_atomic_store((unsigned*)(kz->px_tab[r] + CRUX_PX_ABORT), 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } }
+  if (tid == 0 && (p == 0 || err)) { int32_t* const status = kz->status; double* const bp = kz->bp; float* const infos = kz->epoch_infos;
+    status[0] = err; status[1] = (int32_t)total_batches; status[2] = epochs_run; status[3] = (order_cur == kz->order_a) ? 0 : 1;
+    if (err == CRUX_EHIP) status[4] = why_failed;      // 1 a workgroup of the learner is missing, 2 workgroups on different XCDs, 3 replica group timeout / abort, 4 a workgroup missed the abort-latch consensus
+    bp[0] = bp1; bp[1] = bp2;
+    if constexpr (LAG) { if (p == 0) { crux_lagrange* const lag = kz->lag; lag->I = lgs[0]; lag->smooth_delta = lgs[1]; lag->smooth_Jc = lgs[2]; lag->Jc_prev = lgs[3]; lag->deriv_term = lgs[4]; lag->penalty = lgs[5]; lag->cur_cost = lgs[6]; } }
+    if (err && infos && epochs_run == 0) { infos[CRUX_INFO_LOSS] = smr[Lt::iLOSS]; infos[CRUX_INFO_GRAD_NORM] = NAN; }
   }
 #undef FS2_T
 }
