@@ -138,6 +138,7 @@ SIGNATURES = {
     "crux_buffer_shuffle": (i32, [vp, u64, u64]),
     "crux_gail_d_step": (i32, [vp, vp, i64, i64, vp, i64, i64, vp]),
     "crux_gail_reward": (i32, [vp, vp, f32, f32, vp]),
+    "crux_gail_d_step_gan": (i32, [vp, vp, i64, i64, vp, i64, i64, i32, f32, u64, u64, vp]),
     "crux_fill_gae_multi": (i32, [i32, vp, vp, f32, f32, i32]),
     "crux_whiten_multi": (i32, [i32, vp, i32]),
     "crux_ctx_set_learner_cus": (i32, [vp, i32]),
@@ -183,9 +184,11 @@ SIGNATURES = {
     "crux_asaf_actor_step": (i32, [vp, vp, i64, i64, vp, vp, vp, f32, vp, vp]),
     "crux_asaf_batch_train": (i32, [vp, vp, vp, vp, i32, i32, i32, u64, u64, f32, vp, vp]),
     "crux_gail_d_batch_train": (i32, [vp, vp, vp, i32, i32, i32, u64, u64, vp, vp]),
+    "crux_gail_d_batch_train_gan": (i32, [vp, vp, vp, i32, i32, i32, u64, u64, i32, vp, vp]),
     "crux_nda_reward_cost": (i32, [vp, vp, vp, f32, vp]),
     "crux_nda_advantages": (i32, [vp, vp, vp, f32, f32]),
     "crux_nda_gail_round": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, u64, i32, i32, i32, u64, u64, f32, f32, f32, vp, vp, vp]),
+    "crux_nda_gail_round_gan": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, u64, i32, i32, i32, u64, u64, f32, f32, f32, i32, vp, vp, vp]),
     "crux_ensemble_forward": (i32, [P(vp), i32, i32, vp, i64, vp, vp, vp, vp]),
     "crux_ensemble_logpdf": (i32, [P(vp), i32, i32, vp, vp, i64, vp]),
     "crux_ensemble_step": (i32, [P(vp), i32, i32, vp, vp, vp, i64, vp]),

@@ -31,7 +31,7 @@ from .on_policy import (  # noqa: F401
     A2C, LagrangePPO, OnPolicySolver, PPO, REINFORCE, allreduce_mean_, policy_gradient_training, policy_gradient_training_multi, policy_gradient_training_synced, solve)
 from .imitation import *   # noqa: F401,F403
 from .imitation import (  # noqa: F401
-    BC, BatchSolver, NDA_GAIL_JS, OnPolicyGAIL, _solve_batch, batch_train_gail_d_, batch_train_gail_d_chain_, nda_advantages_, nda_gail_round_, nda_reward_cost_, gail_d_loss, gail_reward_, logpdf_bc_loss, loss_value, mse_action_loss, stop_on_validation_increase)
+    BC, BatchSolver, NDA_GAIL_JS, OnPolicyGAIL, _solve_batch, batch_train_gail_d_, batch_train_gail_d_chain_, nda_advantages_, nda_gail_round_, nda_reward_cost_, gail_d_loss, GANLoss, GANLosses, GAN_BCELoss, GAN_LSLoss, GAN_HingeLoss, GAN_WLoss, GAN_WLossGP, gail_reward_, logpdf_bc_loss, loss_value, mse_action_loss, stop_on_validation_increase)
 from .off_policy import *   # noqa: F401,F403
 from .off_policy import (  # noqa: F401
     DDPG, DQN, OffPolicySolver, SAC, SoftQ, TD3, _PendingInfo, _dpg_solver, _info_ring, _post_sample, _set_stream_for, _solve_off_policy, _solve_small_dqn, _upload_target,

@@ -1302,6 +1302,7 @@ class TrainingParams:
         self.optimizer = optimizer or Adam(np.float32(3e-4))
         self.batch_size, self.epochs, self.target_kl, self.name, self.max_batches = int(batch_size), int(epochs), target_kl, name, max_batches
         self.shuffle_seed, self.shuffle_counter = int(shuffle_seed), 0
+        self.gp_counter = 0      # gail_d_loss(GAN_WLossGP()): the steps taken so far, the Philox counter of the next step's penalty draws
 
 
 class OrthogonalRegularizer:

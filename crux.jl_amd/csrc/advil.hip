@@ -51,10 +51,13 @@ __global__ __launch_bounds__(256) void k_advil_sa(const float* __restrict__ s, c
   if (e < od) { const float v = s[j * od + e]; if (esa) esa[i] = v; psa[i] = v; if (v != v) atomicOr((int*)nanflag, 1); }
   else { const float v = a[j * ad + e - od]; if (esa) esa[i] = v; psa[i] = mu[j * ad + e - od]; if (v != v) atomicOr((int*)nanflag, 1); }
 }
-// advil_d_loss head (one block of 256, fixed order): z [1 x 3B]; stats[0] = sum D(expert), stats[1] = sum D(policy)
-__global__ __launch_bounds__(256) void k_advil_d_head(const float* __restrict__ z, int64_t B, const int32_t* __restrict__ nanflag, float* __restrict__ dy, double* __restrict__ stats) {
+// advil_d_loss head (one block of 256, fixed order): z [1 x 3B]; stats[0] = sum D(expert), stats[1] = sum D(policy). sign = 1: advil_d_loss (mean D(expert) - mean D(policy));
+// sign = -1: the Wasserstein term of GAN_WLossGP (extras/gans.jl:34-40: mean D(policy) - mean D(expert)), the opposite seeds. Multiplying by +-1 is exact.
+// unit: the loss columns are seeded with +-1 and the caller scales their weight gradient by 1 / B instead -- the seeds then cancel exactly in the output bias' gradient,
+// which the loss does not depend on (GanHeadOp's reason, sac.hip); advil_d_loss keeps the seeds it always had.
+__global__ __launch_bounds__(256) void k_advil_d_head(const float* __restrict__ z, int64_t B, float sign, int unit, const int32_t* __restrict__ nanflag, float* __restrict__ dy, double* __restrict__ stats) {
   __shared__ double red[4];
-  const bool poison = nanflag[0] != 0; const float invB = 1.f / (float)B;
+  const bool poison = nanflag[0] != 0; const float invB = unit ? sign : sign * (1.f / (float)B);
   double se = 0, sp = 0;
   for (int64_t j = threadIdx.x; j < B; j += 256) {
     se += (double)z[j]; sp += (double)z[B + j];
@@ -64,11 +67,11 @@ __global__ __launch_bounds__(256) void k_advil_d_head(const float* __restrict__ 
   if (threadIdx.x == 0) { const double pz = poison ? NAN : 0.0; stats[0] = se + pz; stats[1] = sp + pz; }
 }
 // info row LOSS, GRAD_NORM and {mean D(expert), mean D(pi), P, lambda_GP P}; st[4] = sum_j (|g_j| - target)^2 (k_iq_gp_head)
-__global__ void k_advil_d_info(const double* __restrict__ st, const double* __restrict__ ssq, int64_t B, float lambda_gp, float* __restrict__ dinfo, float* __restrict__ adv) {
+__global__ void k_advil_d_info(const double* __restrict__ st, const double* __restrict__ ssq, int64_t B, float sign, float lambda_gp, float* __restrict__ dinfo, float* __restrict__ adv) {
   if (threadIdx.x != 0) return;
   ssq_finalize(ssq);
   const float me = (float)(st[0] / (double)B), mp = (float)(st[1] / (double)B), P = (float)(st[4] / (double)B), gp = lambda_gp * P;
-  dinfo[CRUX_INFO_LOSS] = (me - mp) + gp; dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
+  dinfo[CRUX_INFO_LOSS] = sign * (me - mp) + gp; dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
   adv[0] = me; adv[1] = mp; adv[2] = P; adv[3] = gp;
 }
 // advil_pi_loss head (one block of 256, fixed order): z [1 x B]; seed 1/B; stats[0] = sum D(s, pi(s))
@@ -142,6 +145,29 @@ static int32_t advil_check(crux_ctx* c, const crux_mlp* actor, const crux_mlp* D
   return CRUX_OK;
 }
 
+// "Wasserstein + penalty" over the 3B columns [expert | policy | xhat] the caller left in ib.X (k_iq_expand; ib.nanflag set by then), enqueued only: D's forward pass, the
+// head with its sign, the data gradient, the weight gradient over the first 2B columns, k_iq_gp_head, the penalty sweeps (iq.hip), the norm, the info row and the gated
+// Adam. crux_advil_d_step (sign = 1) and the GAN_WLossGP step of crux_gail_d_step_gan (nda_gail.hip; sign = -1, unit seeds, target 1) are this one sequence.
+static int32_t wgp_enqueue(crux_mlp* D, int64_t B, float sign, bool unit, float lambda_gp, float gp_target, const IqBufs& ib) {
+  crux_ctx* c = D->ctx; const NetDesc& nd = D->nd; const int64_t NC = 3 * B; const int sd = nd.dims[0];
+  int32_t rc = crux_dense_forward(D, ib.X, NC, c->stream); if (rc) return rc;
+  hipLaunchKernelGGL(k_advil_d_head, dim3(1), dim3(256), 0, c->stream, (const float*)crux_dense_act(D, nd.L), B, sign, unit ? 1 : 0, (const int32_t*)ib.nanflag, ib.dy, ib.stats);
+  rc = crux_launch_check(c, "k_advil_d_head"); if (rc) return rc;
+  rc = iq_dgrad(D, B, B, ib); if (rc) return rc;
+  for (int l = 1; l <= nd.L; ++l) {       // the loss's weight gradient over the expert and policy columns only
+    const float* hx = l == 1 ? ib.X : crux_dense_act(D, l - 1);
+    rc = iq_wgrad(c, ib.Z[l], hx, nd.dims[l], nd.dims[l - 1], 2 * B, D->g + nd.woff[l - 1], D->g + nd.boff[l - 1], unit ? 1.f / (float)B : 1.f); if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_iq_gp_head, dim3(1), dim3(256), 0, c->stream, (const float*)(ib.G[0] + 2 * B * sd), sd, B, gp_target, lambda_gp, (const int32_t*)ib.nanflag, ib.gb[0], ib.stats);
+  rc = crux_launch_check(c, "k_iq_gp_head"); if (rc) return rc;
+  rc = iq_penalty_sweeps(D, B, B, ib); if (rc) return rc;
+  rc = iq_add_penalty(D, ib); if (rc) return rc;
+  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
+  hipLaunchKernelGGL(k_advil_d_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, sign, lambda_gp, ib.dinfo, ib.extra);
+  rc = crux_launch_check(c, "k_advil_d_info"); if (rc) return rc;
+  return adam_gated(D, ib.ssq, ib.status);
+}
+
 extern "C" {
 
 int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float* value_out) { CRUX_PLAIN_ONLY("crux_orthogonal_reg", net);
@@ -164,7 +190,7 @@ int32_t crux_orthogonal_reg(crux_mlp* net, float beta, int32_t accumulate, float
 
 int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float lambda_gp, float gp_target, uint64_t seed, uint64_t counter, float* info_out, float* adv_out) { CRUX_PLAIN_ONLY("crux_advil_d_step", actor, D);
   if (!actor || !D || !b) return CRUX_EINVAL;
-  crux_ctx* c = D->ctx; const char* who = "advil_d_loss"; const NetDesc& nd = D->nd;
+  crux_ctx* c = D->ctx; const char* who = "advil_d_loss";
   int32_t rc = advil_check(c, actor, D, b, who); if (rc) return rc;
   if (!D->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
   const int64_t B = b->elements, NC = 3 * B; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad;
@@ -177,22 +203,7 @@ int32_t crux_advil_d_step(crux_mlp* actor, crux_mlp* D, crux_buffer* b, float la
   rc = crux_launch_check(c, "k_advil_sa"); if (rc) return rc;
   hipLaunchKernelGGL(k_iq_expand, dim3(nblk(NC)), dim3(256), 0, c->stream, (const float*)esa, (const float*)psa, B, (const float*)esa, (const float*)psa, B, sd, seed, counter, ib.X, ib.nanflag);
   rc = crux_launch_check(c, "k_iq_expand"); if (rc) return rc;
-  rc = crux_dense_forward(D, ib.X, NC, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_advil_d_head, dim3(1), dim3(256), 0, c->stream, (const float*)crux_dense_act(D, nd.L), B, (const int32_t*)ib.nanflag, ib.dy, ib.stats);
-  rc = crux_launch_check(c, "k_advil_d_head"); if (rc) return rc;
-  rc = iq_dgrad(D, B, B, ib); if (rc) return rc;
-  for (int l = 1; l <= nd.L; ++l) {       // the loss's weight gradient over the expert and policy columns only
-    const float* hx = l == 1 ? ib.X : crux_dense_act(D, l - 1);
-    rc = iq_wgrad(c, ib.Z[l], hx, nd.dims[l], nd.dims[l - 1], 2 * B, D->g + nd.woff[l - 1], D->g + nd.boff[l - 1]); if (rc) return rc;
-  }
-  hipLaunchKernelGGL(k_iq_gp_head, dim3(1), dim3(256), 0, c->stream, (const float*)(ib.G[0] + 2 * B * sd), sd, B, gp_target, lambda_gp, (const int32_t*)ib.nanflag, ib.gb[0], ib.stats);
-  rc = crux_launch_check(c, "k_iq_gp_head"); if (rc) return rc;
-  rc = iq_penalty_sweeps(D, B, B, ib); if (rc) return rc;
-  rc = iq_add_penalty(D, ib); if (rc) return rc;
-  crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ib.ssq, Sumsq2Fix{});
-  hipLaunchKernelGGL(k_advil_d_info, dim3(1), dim3(1), 0, c->stream, (const double*)ib.stats, (const double*)ib.ssq, B, lambda_gp, ib.dinfo, ib.extra);
-  rc = crux_launch_check(c, "k_advil_d_info"); if (rc) return rc;
-  rc = adam_gated(D, ib.ssq, ib.status); if (rc) return rc;
+  rc = wgp_enqueue(D, B, 1.f, false, lambda_gp, gp_target, ib); if (rc) return rc;
   return finish_step(c, ib.dinfo, ib.extra, 4, ib.status, info_out, adv_out, who);
 }
 

@@ -163,10 +163,10 @@ static int32_t iq_gemm(crux_ctx* c, const float* A, int64_t sAi, int64_t sAk, co
   q.ysrc = nullptr; q.act = CRUX_ACT_IDENTITY;
   return launch_gemm(c, q, c->stream);
 }
-// dW[o, k] = sum_j dZ[o, j] X[k, j] over K columns (db[o] = sum_j dZ[o, j] when db != NULL)
-static int32_t iq_wgrad(crux_ctx* c, const float* dZ, const float* X, int out, int in, int64_t K, float* dW, float* db) {
+// dW[o, k] = scale sum_j dZ[o, j] X[k, j] over K columns (db[o] = scale sum_j dZ[o, j] when db != NULL)
+static int32_t iq_wgrad(crux_ctx* c, const float* dZ, const float* X, int out, int in, int64_t K, float* dW, float* db, float scale = 1.0f) {
   GemmArgs q{}; q.A = dZ; q.sAi = 1; q.sAk = out; q.B = X; q.sBk = in; q.sBj = 1; q.M = out; q.N = in; q.K = (int)K;
-  q.C = dW; q.sCj = out; q.epi = EPI_WGRAD; q.scale = 1.0f; q.gbias = db; q.nf = nullptr;
+  q.C = dW; q.sCj = out; q.epi = EPI_WGRAD; q.scale = scale; q.gbias = db; q.nf = nullptr;
   return launch_gemm(c, q, c->stream);
 }
 // data-gradient pass over all NC columns after the forward pass and the seeds: Z_l = dZ_l, G_l = W_{l+1}^T dZ_{l+1} (G_0 over the H penalty columns only)

@@ -14,6 +14,11 @@
 // The round (crux_nda_gail_round): both copies refilled from the batch, the chain of D, the chain of Dnda on the SAME status word, the reward / cost and the advantage tail
 // (advantage.hip: crux_nda_adv_enqueue), each gated on that word, one host synchronisation. One stream, no graph capture: the two chains follow each other.
 // No float atomics anywhere: two identical calls give identical bits.
+//
+// The loss kind (src/extras/gans.jl; CRUX_GAN_* of cruxhip.h): the chain and the round take BCE, LS, hinge and W -- only the head of a step differs (sac.hip: GailHeadOp,
+// GanHeadOp), so every *_gan entry with kind BCE is the entry without the suffix, bit for bit. GAN_WLossGP (gans.jl:34-40) is a step of its own kind
+// (crux_gail_d_step_gan): vcat(a, s) of both halves, k_iq_expand to [x_E | x_pi | xhat], then advil.hip's wgp_enqueue with the sign turned round and target 1. Its
+// penalty takes its scratch per step (iq_prepare), a chain owns one block for its whole length (chain.h), so the chain and the round refuse it.
 #include "common.h"
 #include "exec.h"
 
@@ -69,13 +74,13 @@ static int32_t gd_check(crux_ctx* c, crux_mlp* D, crux_buffer* ex, crux_buffer* 
 }
 // epochs x (shuffle both, one step per zipped pair), enqueued only; rows [epochs x CRUX_INFO_N] and status are the caller's (zeroed)
 static int32_t gd_enqueue_chain(crux_mlp* D, crux_buffer* ex, crux_buffer* pi, int32_t B, int32_t epochs, int32_t max_batches, uint64_t seed, uint64_t counter, const GailStepBufs& gb,
-                                float* rows, int32_t* status, int64_t* total_out, int* epochs_run_out) {
+                                float* rows, int32_t* status, int64_t* total_out, int* epochs_run_out, int32_t gan_kind) {
   return chain_epochs(epochs, gd_plan(ex, pi, B).nb, max_batches,
                       [&](int ep) { const uint64_t k = counter + (uint64_t)ep;
                         const int32_t rc = crux_buffer_shuffle(ex, seed, 2 * k); return rc ? rc : crux_buffer_shuffle(pi, seed, 2 * k + 1); },
                       [&](int ep, int64_t q) {                                                                          // zip(partition(...)...) (:40): the shorter one ends it
                         const int64_t ne = (ex->elements - q * B) < B ? (ex->elements - q * B) : B, np = (pi->elements - q * B) < B ? (pi->elements - q * B) : B;
-                        return gail_enqueue_step(D, ex, q * B, ne, pi, q * B, np, gb, rows + (size_t)ep * CRUX_INFO_N, status, true); },
+                        return gail_enqueue_step(D, ex, q * B, ne, pi, q * B, np, gb, rows + (size_t)ep * CRUX_INFO_N, status, true, gan_kind); },
                       total_out, epochs_run_out);
 }
 
@@ -121,13 +126,19 @@ static int32_t nda_refill(crux_buffer* copy, const crux_buffer* batch) {
   return CRUX_OK;
 }
 
-extern "C" {
+// the kinds a chain of steps takes: the four with a head
+static int32_t gd_check_kind(crux_ctx* c, int32_t gan_kind, const char* who) {
+  if (gan_kind == CRUX_GAN_WGP) return crux_fail(c, CRUX_EUNSUP, "%s: GAN_WLossGP cannot run inside a chain: the gradient penalty takes its scratch per step, a chain owns one block for all of its steps; loop crux_gail_d_step_gan on the host", who);
+  if (gan_kind < CRUX_GAN_BCE || gan_kind > CRUX_GAN_WGP) return crux_fail(c, CRUX_EINVAL, "%s: unknown loss kind %d", who, gan_kind);
+  return CRUX_OK;
+}
 
-int32_t crux_gail_d_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
-                                float* info_out, float* epoch_rows) {
+static int32_t gd_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                              int32_t gan_kind, float* info_out, float* epoch_rows) {
   if (!D || !expert || !policy) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "batch_train! (gail_d_loss)";
-  int32_t rc = gd_check(c, D, expert, policy, batch_size, epochs, who); if (rc) return rc;
+  int32_t rc = gd_check_kind(c, gan_kind, who); if (rc) return rc;
+  rc = gd_check(c, D, expert, policy, batch_size, epochs, who); if (rc) return rc;
   const GdPlan pl = gd_plan(expert, policy, batch_size); const int sd = expert->obs_dim + expert->act_dim; const int64_t NC = pl.bmax_ex + pl.bmax_pi;
   rc = ensure_ws(D, NC); if (rc) return rc;      // the workspace must not be re-allocated between the steps
   // one scratch block for the whole chain, its own pieces behind the shuffles' staging (chain.h)
@@ -137,11 +148,50 @@ int32_t crux_gail_d_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* p
   Carve cv{base + front, 0}; const GailStepBufs gb = gd_step_carve(cv, sd, NC); hd.carve(cv, epochs);
   rc = hd.zero(c); if (rc) return rc;
   int64_t total = 0; int epochs_run = 0;
-  rc = gd_enqueue_chain(D, expert, policy, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, gb, hd.rows, hd.status, &total, &epochs_run); if (rc) return rc;
+  rc = gd_enqueue_chain(D, expert, policy, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, gb, hd.rows, hd.status, &total, &epochs_run, gan_kind); if (rc) return rc;
   int32_t st; const char* h; rc = hd.fetch(c, hd.run_bytes(epochs_run), who, &st, &h); if (rc) return rc;
   const int last = chain_report(st, (const float*)(h + 256), CRUX_INFO_N, epochs_run, total, true, info_out, epoch_rows);
   if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s, epoch %d", who, last + 1);
   return CRUX_OK;
+}
+
+extern "C" {
+
+int32_t crux_gail_d_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                                float* info_out, float* epoch_rows) {
+  return gd_batch_train(D, expert, policy, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, CRUX_GAN_BCE, info_out, epoch_rows);
+}
+int32_t crux_gail_d_batch_train_gan(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                                    int32_t gan_kind, float* info_out, float* epoch_rows) {
+  return gd_batch_train(D, expert, policy, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, gan_kind, info_out, epoch_rows);
+}
+
+int32_t crux_gail_d_step_gan(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, int32_t gan_kind, float lambda_gp, uint64_t gp_seed,
+                             uint64_t gp_counter, float* info_out) {
+  if (!D || !ex || !pi) return CRUX_EINVAL;
+  crux_ctx* c = D->ctx; const char* who = "gail_d_loss (GAN_WLossGP)";
+  if (gan_kind < CRUX_GAN_BCE || gan_kind > CRUX_GAN_WGP) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: unknown loss kind %d", gan_kind);
+  if (gan_kind != CRUX_GAN_WGP) return gail_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, gan_kind, info_out);
+  CRUX_PLAIN_ONLY("crux_gail_d_step_gan (GAN_WLossGP)", D);      // the sweeps read the raw weights
+  if (n_ex <= 0 || n_pi <= 0 || off_ex < 0 || off_pi < 0 || off_ex + n_ex > ex->elements || off_pi + n_pi > pi->elements) return crux_fail(c, CRUX_EINVAL, "%s: row ranges outside the buffers", who);
+  if (n_ex != n_pi)      // the interpolation broadcasts the halves against each other (gradient_penalty.jl): DimensionMismatch in the reference
+    return crux_fail(c, CRUX_EINVAL, "%s: the gradient penalty needs as many expert rows as policy rows (%lld, %lld)", who, (long long)n_ex, (long long)n_pi);
+  int32_t rc = iq_check_net(c, D, who); if (rc) return rc;
+  if (ex->ctx != c || pi->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: the discriminator and the buffers belong to different contexts", who);
+  rc = gail_check(c, D, ex, pi); if (rc) return rc;
+  if (D->nd.n_extra != 0) return crux_fail(c, CRUX_EINVAL, "%s: the discriminator must be a handle without trailing extras", who);
+  if (!D->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
+  const int64_t B = n_ex, NC = 3 * B; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad;
+  if (NC > (1 << 20)) return crux_fail(c, CRUX_EINVAL, "%s: %lld rows give %lld columns, more than the 2^20 one forward pass takes", who, (long long)B, (long long)NC);
+  const size_t half = (((size_t)sd * (size_t)B + 63) / 64) * 64;      // x_E and x_pi, each on a 256-byte boundary
+  IqBufs ib{}; rc = iq_prepare(D, B, B, true, ib, who, 2 * half); if (rc) return rc;
+  float* xe = ib.own; float* xp = ib.own + half; const int u8 = ex->act_kind == CRUX_ACTION_DISCRETE ? 1 : 0;
+  crux_launch<ConcatAsOp>(nblk(B * sd), 256, c->stream, (const void*)ex->col[CRUX_COL_A], u8, (const float*)ex->col[CRUX_COL_S], od, ad, off_ex, B, xe);
+  crux_launch<ConcatAsOp>(nblk(B * sd), 256, c->stream, (const void*)pi->col[CRUX_COL_A], u8, (const float*)pi->col[CRUX_COL_S], od, ad, off_pi, B, xp);
+  hipLaunchKernelGGL(k_iq_expand, dim3(nblk(NC)), dim3(256), 0, c->stream, (const float*)xe, (const float*)xp, B, (const float*)xe, (const float*)xp, B, sd, gp_seed, gp_counter, ib.X, ib.nanflag);
+  rc = crux_launch_check(c, "k_iq_expand"); if (rc) return rc;
+  rc = wgp_enqueue(D, B, -1.f, true, lambda_gp, 1.0f, ib); if (rc) return rc;      // Lᴰ = mean D(policy) - mean D(expert) + lambda gradient_penalty(D, x_E, x_pi; target = 1f0)
+  return finish_step(c, ib.dinfo, ib.status, info_out, who);
 }
 
 int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, float alpha_r, float* out3) {
@@ -160,12 +210,16 @@ int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, floa
   return CRUX_OK;
 }
 
-int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
-                            int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
-                            int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
-                            float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3) { CRUX_PLAIN_ONLY("crux_nda_gail_round", V, Vc);
+}  // extern "C"
+
+// one loss kind for both discriminators (nda_gail_js.jl:19-20)
+static int32_t nda_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
+                         int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                         int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
+                         float alpha_r, float lambda, float gamma, int32_t gan_kind, float* info_D, float* info_Dnda, float* out3) { CRUX_PLAIN_ONLY("crux_nda_gail_round", V, Vc);
   if (!D || !Dnda || !demo || !nda || !batch || !copyD || !copyN || !V || !Vc) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "GAIL_callback (NDA-GAIL)";
+  { const int32_t rk = gd_check_kind(c, gan_kind, who); if (rk) return rk; }
   // every check first: nothing is launched and no buffer is touched when one fails
   if (D == Dnda) return crux_fail(c, CRUX_EINVAL, "%s: D and Dnda are the same handle (each is trained by its own chain)", who);
   if (copyD == copyN || copyD == demo || copyD == nda || copyN == demo || copyN == nda) return crux_fail(c, CRUX_EINVAL, "%s: the two copies must be buffers of their own", who);
@@ -194,8 +248,8 @@ int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux
   rc = nda_refill(copyD, batch); if (rc) return rc;                                                                      // deepcopy(𝒟) (:29, :30)
   rc = nda_refill(copyN, batch); if (rc) return rc;
   int64_t totD = 0, totN = 0; int erD = 0, erN = 0;
-  rc = gd_enqueue_chain(D, demo, copyD, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, gb, hd.rows, hd.status, &totD, &erD); if (rc) return rc;                               // :29
-  rc = gd_enqueue_chain(Dnda, nda, copyN, batch_size_nda, epochs_nda, max_batches_nda, shuffle_seed_nda, shuffle_counter_nda, gb, rowsN, hd.status, &totN, &erN); if (rc) return rc;      // :30
+  rc = gd_enqueue_chain(D, demo, copyD, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, gb, hd.rows, hd.status, &totD, &erD, gan_kind); if (rc) return rc;                               // :29
+  rc = gd_enqueue_chain(Dnda, nda, copyN, batch_size_nda, epochs_nda, max_batches_nda, shuffle_seed_nda, shuffle_counter_nda, gb, rowsN, hd.status, &totN, &erN, gan_kind); if (rc) return rc;      // :30
   rc = rc_enqueue(D, Dnda, batch, alpha_r, xr, part, hd.status); if (rc) return rc;                                      // :33-49
   int32_t* flags = nullptr;
   rc = crux_nda_adv_enqueue(batch, V, Vc, lambda, gamma, adv, hd.status, &flags); if (rc) return rc;                     // :51-61
@@ -214,6 +268,23 @@ int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux
   if (fl[0]) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
   if (fl[1]) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN cost advantage (@assert !isnan(A))");
   return CRUX_OK;
+}
+
+extern "C" {
+
+int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
+                            int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                            int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
+                            float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3) {
+  return nda_round(D, Dnda, demo, nda, batch, copyD, copyN, V, Vc, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, batch_size_nda, epochs_nda, max_batches_nda, shuffle_seed_nda,
+                   shuffle_counter_nda, alpha_r, lambda, gamma, CRUX_GAN_BCE, info_D, info_Dnda, out3);
+}
+int32_t crux_nda_gail_round_gan(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
+                            int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                            int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
+                            float alpha_r, float lambda, float gamma, int32_t gan_kind, float* info_D, float* info_Dnda, float* out3) {
+  return nda_round(D, Dnda, demo, nda, batch, copyD, copyN, V, Vc, batch_size, epochs, max_batches, shuffle_seed, shuffle_counter, batch_size_nda, epochs_nda, max_batches_nda, shuffle_seed_nda,
+                   shuffle_counter_nda, alpha_r, lambda, gamma, gan_kind, info_D, info_Dnda, out3);
 }
 
 }  // extern "C"

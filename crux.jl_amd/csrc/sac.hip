@@ -302,6 +302,26 @@ struct GailHeadOp { static constexpr int max_threads = 256; static __device__ __
   le = block_sum256(le, red); lp = block_sum256(lp, red);
   if (threadIdx.x == 0) { stats[0] = le; stats[1] = lp; }
 } };
+// The other discriminator losses of Lᴰ (src/extras/gans.jl:14 LS, :19 hinge, :24 W; wD = 1f0) in GailHeadOp's form: one block of 256, the halves split at n_ex, both half-sums in
+// Float64 through block_sum256 (fixed order, no float atomics), stats laid out so that GailInfoOp forms the row as it does for BCE ((float)(st[0] / n_ex) + (float)(st[1] / n_pi)).
+//   LS      mean_e((sg - 1)^2) + mean_p(sg^2), sg = sigmoid(z)     seeds 2 (sg - 1) sg (1 - sg) / n_ex,  2 sg^2 (1 - sg) / n_pi
+//   hinge   mean_e(relu(1 - z)) + mean_p(relu(1 + z))              seeds -[z < 1] / n_ex,  [z > -1] / n_pi; relu' at exactly 0 is 0 (Zygote's rule) [3P-memory]
+//   W       mean_p(z) - mean_e(z)                                  seeds -1 / n_ex,  1 / n_pi, stored as -n_pi and n_ex: the pullback scales by 1 / (n_ex n_pi)
+// W's seeds sum to zero, and so does the output bias' gradient of an identity output layer (the loss does not see that bias). Rounded quotients would leave a residue of
+// an ulp there, which Adam's first steps turn into a full lr sign(g); the integers cancel exactly (their partial sums stay below 2^24 up to 4096 x 4096 columns).
+// The hinge's comparisons and W's constants do not see a NaN, so a NaN z is handed on as that column's seed and term (Julia's relu and mean propagate it).
+template <int KIND> struct GanHeadOp { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, int64_t n_ex, int64_t n_pi, float* __restrict__ dz, double* __restrict__ stats /* [2] */) {
+  __shared__ double red[4];
+  double le = 0, lp = 0;
+  for (int64_t j = threadIdx.x; j < n_ex + n_pi; j += 256) { const float v = z[j]; const bool ex = j < n_ex; float l, d;
+    if (KIND == CRUX_GAN_LS) { const float sg = 1.f / (1.f + expf(-v)); const float t = ex ? sg - 1.f : sg; l = t * t; d = 2.f * t * sg * (1.f - sg); }
+    else if (KIND == CRUX_GAN_HINGE) { const float t = ex ? 1.f - v : 1.f + v; l = t > 0.f ? t : 0.f; d = t > 0.f ? (ex ? -1.f : 1.f) : 0.f; if (v != v) { l = v; d = v; } }
+    else { l = ex ? -v : v; d = v != v ? v : (ex ? -(float)n_pi : (float)n_ex); }
+    if (ex) le += (double)l; else lp += (double)l;
+    dz[j] = KIND == CRUX_GAN_W ? d : d / (float)(ex ? n_ex : n_pi); }
+  le = block_sum256(le, red); lp = block_sum256(lp, red);
+  if (threadIdx.x == 0) { stats[0] = le; stats[1] = lp; }
+} };
 struct GailInfoOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const double* __restrict__ st, const double* __restrict__ ssq, int64_t n_ex, int64_t n_pi, float* __restrict__ dinfo) { if (threadIdx.x != 0) return;
   ssq_finalize(ssq);
   dinfo[CRUX_INFO_LOSS] = (float)(st[0] / (double)n_ex) + (float)(st[1] / (double)n_pi); dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
@@ -461,8 +481,8 @@ int32_t crux_q_step(crux_mlp* q, crux_buffer* b, const float* d_y, int32_t use_w
 
 }  // extern "C"
 
-// One discriminator step of gail_d_loss(GAN_BCELoss()), enqueued only: the gather of both halves, the dense forward pass, the two BCE heads, the dense backward pass, the
-// norm, the info row and the gated Adam. crux_gail_d_step is this plus the read-back; the chain of nda_gail.hip enqueues it once per minibatch pair with chained = true
+// One discriminator step of gail_d_loss(gan_loss), enqueued only: the gather of both halves, the dense forward pass, the head of the loss kind (BCE: GailHeadOp; LS, hinge,
+// W: GanHeadOp; GAN_WLossGP is not a head, nda_gail.hip composes it from iq.hip's sweeps), the dense backward pass, the norm, the info row and the gated Adam. crux_gail_d_step is this plus the read-back; the chain of nda_gail.hip enqueues it once per minibatch pair with chained = true
 // (all steps share `status`, and no row is written once it holds CRUX_ENAN). The caller has zeroed dinfo and status.
 struct GailStepBufs { float* x; float* dz; double* st2; double* ssq; };
 static int32_t gail_check(crux_ctx* c, const crux_mlp* D, const crux_buffer* ex, const crux_buffer* pi) {
@@ -472,23 +492,30 @@ static int32_t gail_check(crux_ctx* c, const crux_mlp* D, const crux_buffer* ex,
   return CRUX_OK;
 }
 static int32_t gail_enqueue_step(crux_mlp* D, const crux_buffer* ex, int64_t off_ex, int64_t n_ex, const crux_buffer* pi, int64_t off_pi, int64_t n_pi, const GailStepBufs& gb, float* dinfo,
-                                 int32_t* status, bool chained) {
+                                 int32_t* status, bool chained, int32_t gan_kind) {
   crux_ctx* c = D->ctx; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad; const int64_t B = n_ex + n_pi;
   const int u8 = ex->act_kind == CRUX_ACTION_DISCRETE ? 1 : 0;
   crux_launch<ConcatAsOp>(nblk(n_ex * sd), 256, c->stream, (const void*)ex->col[CRUX_COL_A], u8, (const float*)ex->col[CRUX_COL_S], od, ad, off_ex, n_ex, gb.x);
   crux_launch<ConcatAsOp>(nblk(n_pi * sd), 256, c->stream, (const void*)pi->col[CRUX_COL_A], u8, (const float*)pi->col[CRUX_COL_S], od, ad, off_pi, n_pi, gb.x + (size_t)n_ex * sd);
   int32_t rc = crux_dense_forward(D, gb.x, B, c->stream); if (rc) return rc;
-  crux_launch<GailHeadOp>(1, 256, c->stream, crux_dense_act(D, D->nd.L), n_ex, n_pi, gb.dz, gb.st2);
-  rc = crux_dense_backward(D, gb.x, B, gb.dz, 1.0f, true, nullptr, c->stream); if (rc) return rc;
+  const float* z = crux_dense_act(D, D->nd.L);
+  switch (gan_kind) {
+    case CRUX_GAN_BCE: crux_launch<GailHeadOp>(1, 256, c->stream, z, n_ex, n_pi, gb.dz, gb.st2); break;
+    case CRUX_GAN_LS: crux_launch<GanHeadOp<CRUX_GAN_LS>>(1, 256, c->stream, z, n_ex, n_pi, gb.dz, gb.st2); break;
+    case CRUX_GAN_HINGE: crux_launch<GanHeadOp<CRUX_GAN_HINGE>>(1, 256, c->stream, z, n_ex, n_pi, gb.dz, gb.st2); break;
+    case CRUX_GAN_W: crux_launch<GanHeadOp<CRUX_GAN_W>>(1, 256, c->stream, z, n_ex, n_pi, gb.dz, gb.st2); break;
+    default: return crux_fail(c, CRUX_EINVAL, "gail_d_loss: loss kind %d has no head", gan_kind);
+  }
+  const float gscale = gan_kind == CRUX_GAN_W ? (float)(1.0 / ((double)n_ex * (double)n_pi)) : 1.0f;      // W's seeds are the integers -n_pi and n_ex (GanHeadOp)
+  rc = crux_dense_backward(D, gb.x, B, gb.dz, gscale, true, nullptr, c->stream); if (rc) return rc;
   CRUX_RUN(c, Sumsq2Op, SUMSQ_BLOCKS, 256, c->stream, D->g, (int64_t)D->nd.n_params, (float*)nullptr, (int64_t)0, gb.ssq, Sumsq2Fix{});
   if (chained) hipLaunchKernelGGL(k_gail_info_chain, dim3(1), dim3(1), 0, c->stream, (const double*)gb.st2, (const double*)gb.ssq, n_ex, n_pi, (const int32_t*)status, dinfo);
   else crux_launch<GailInfoOp>(1, 1, c->stream, gb.st2, gb.ssq, n_ex, n_pi, dinfo);
   return adam_gated(D, gb.ssq, status);
 }
 
-extern "C" {
-
-int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, float* info_out) {
+// crux_gail_d_step and, for the head kinds, crux_gail_d_step_gan (nda_gail.hip)
+static int32_t gail_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, int32_t gan_kind, float* info_out) {
   if (!D || !ex || !pi) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad;
   if (n_ex <= 0 || n_pi <= 0 || off_ex < 0 || off_pi < 0 || off_ex + n_ex > ex->elements || off_pi + n_pi > pi->elements) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: row ranges outside the buffers");
@@ -498,8 +525,14 @@ int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n
   GailStepBufs gb; gb.x = cv.take<float>((size_t)B * sd); gb.dz = cv.take<float>((size_t)B); float* dinfo = cv.take<float>(CRUX_INFO_N);
   gb.st2 = cv.take<double>(2); gb.ssq = cv.take<double>(2 + SUMSQ_BLOCKS); int32_t* st = cv.take<int32_t>(1);
   HIPCHK(c, hipMemsetAsync(dinfo, 0, 256 * 6, c->stream));
-  rc = gail_enqueue_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, gb, dinfo, st, false); if (rc) return rc;
+  rc = gail_enqueue_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, gb, dinfo, st, false, gan_kind); if (rc) return rc;
   return finish_step(c, dinfo, st, info_out, "gail_d_loss");
+}
+
+extern "C" {
+
+int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, float* info_out) {
+  return gail_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, CRUX_GAN_BCE, info_out);
 }
 
 int32_t crux_gail_reward(crux_mlp* D, crux_buffer* b, float alpha_r, float rscale, float* mean_r) {

@@ -21,16 +21,89 @@ from .on_policy import (  # noqa: F401
 # --------------------------------------------------------------------------------------------------------------
 # OnPolicyGAIL (src/model_free/il/on_policy_gail.jl) -- the discriminator is trained by batch_train! over TWO buffers (training.jl:28-44)
 # --------------------------------------------------------------------------------------------------------------
-gail_d_loss = _Loss("gail_d")     # gail_d_loss(GAN_BCELoss()) (on_policy_gail.jl:1-5, extras/gans.jl:7-9)
+class GANLoss:
+    """The discriminator losses of src/extras/gans.jl (abstract type GANLoss, :1); `kind` is the C ABI's CRUX_GAN_* number."""
+    kind, name = -1, ""
+
+    def __repr__(self):
+        return "GAN_%s()" % self.name
+
+
+class GAN_BCELoss(GANLoss):      # gans.jl:5-9
+    kind, name = 0, "BCELoss"
+
+
+class GAN_LSLoss(GANLoss):       # gans.jl:12-14
+    kind, name = 1, "LSLoss"
+
+
+class GAN_HingeLoss(GANLoss):    # gans.jl:17-19
+    kind, name = 2, "HingeLoss"
+
+
+class GAN_WLoss(GANLoss):        # gans.jl:22-24
+    kind, name = 3, "WLoss"
+
+
+class GAN_WLossGP(GANLoss):
+    """GAN_WLossGP(; λ = 10f0, noise_range = 1f0) (gans.jl:28-40): the Wasserstein loss + λ gradient_penalty(D, x_E, x_π). noise_range is carried and never read, as in
+    the reference (:31). seed: the Philox seed of the penalty's draws ε (stream IQ_GP); the counter is the step count kept on the TrainingParams (gp_counter)."""
+    kind, name = 4, "WLossGP"
+
+    def __init__(self, λ=10.0, noise_range=1.0, seed=0):
+        self.λ, self.noise_range, self.seed = float(np.float32(λ)), float(np.float32(noise_range)), int(seed)
+
+    def __repr__(self):
+        return "GAN_WLossGP(λ=%g, noise_range=%g, seed=%d)" % (self.λ, self.noise_range, self.seed)
+
+
+GANLosses = {"BCE": GAN_BCELoss(), "LS": GAN_LSLoss(), "Hinge": GAN_HingeLoss(), "W": GAN_WLoss(), "WGP": GAN_WLossGP()}      # src/extras/gans.jl, exported by src/Crux.jl:83
+
+
+class _GailDLoss(_Loss):
+    """gail_d_loss(gan_loss) (on_policy_gail.jl:1-5): a loss that carries its GANLoss. The module-level object `gail_d_loss` is the BCE one, so TrainingParams(loss=gail_d_loss)
+    means what it always did; calling it -- gail_d_loss(GAN_HingeLoss()) -- returns the loss of that kind."""
+
+    def __init__(self, gan_loss=None):
+        super().__init__("gail_d")
+        self.gan_loss = gan_loss if gan_loss is not None else GAN_BCELoss()
+        if not isinstance(self.gan_loss, GANLoss):
+            raise TypeError("gail_d_loss: %r is not a GANLoss" % (gan_loss,))
+
+    def __call__(self, gan_loss):
+        return _GailDLoss(gan_loss)
+
+
+gail_d_loss = _GailDLoss()     # gail_d_loss(GAN_BCELoss()) (on_policy_gail.jl:1-5, extras/gans.jl:7-9)
+
+
+def _gan(p):
+    """the GANLoss a TrainingParams' loss carries (BCE for anything that carries none)"""
+    return getattr(p.loss, "gan_loss", None) or GAN_BCELoss()
+
+
+def _gail_pairs(n_ex, n_pi, B):
+    """zip(partition(1:n_ex, B), partition(1:n_pi, B)) (training.jl:40) as (offset, n_ex, n_pi): the shorter buffer ends the epoch"""
+    nb = min(-(-n_ex // B), -(-n_pi // B))
+    return [(k * B, min(B, n_ex - k * B), min(B, n_pi - k * B)) for k in range(nb)]
 
 
 def batch_train_gail_d_(Dnet, p, D_expert, D_policy, info=None):
     """batch_train!(D, d_opt, (;), D_demo, deepcopy(D)) (on_policy_gail.jl:47, training.jl:28-55): every epoch shuffles both buffers, zips their
     minibatch partitions (the shorter buffer ends the epoch) and takes one discriminator step per pair. Shuffle k of this TrainingParams uses
-    permutation counter 2k for the expert buffer and 2k+1 for the policy buffer. Epoch info = its last minibatch, result = mean over epochs."""
+    permutation counter 2k for the expert buffer and 2k+1 for the policy buffer. Epoch info = its last minibatch, result = mean over epochs.
+    The loss kind is p.loss's (gail_d_loss(gan_loss)); BCE makes the calls it always made. GAN_WLossGP draws step t's ε from (gan_loss.seed, p.gp_counter), which advances
+    by one per step taken, and needs equal halves in every pair: checked here for the whole epoch before any step (the reference throws DimensionMismatch in the
+    first unequal pair, after the steps before it)."""
     _ensure_opt(Dnet, p)
     B, infos, total = p.batch_size, [], 0
     nb = min(-(-len(D_expert) // B), -(-len(D_policy) // B))
+    gl = _gan(p)
+    if gl.kind == GAN_WLossGP.kind:
+        bad = [(ne, npi) for _, ne, npi in _gail_pairs(len(D_expert), len(D_policy), B) if ne != npi]
+        if bad:
+            raise ValueError("gail_d_loss(GAN_WLossGP): the gradient penalty needs as many expert rows as policy rows in every minibatch pair; buffers of %d and %d rows "
+                             "under batch_size %d give a pair of %d and %d" % (len(D_expert), len(D_policy), B, bad[0][0], bad[0][1]))
     stop = False
     for _ in range(p.epochs):
         shuffle_device_(D_expert, p.shuffle_seed, 2 * p.shuffle_counter); shuffle_device_(D_policy, p.shuffle_seed, 2 * p.shuffle_counter + 1)
@@ -38,7 +111,12 @@ def batch_train_gail_d_(Dnet, p, D_expert, D_policy, info=None):
         raw = np.zeros(L.INFO_N, np.float32)
         for k in range(nb):
             ne, npi = min(B, len(D_expert) - k * B), min(B, len(D_policy) - k * B)
-            Dnet.ctx.check(Dnet.ctx.lib.crux_gail_d_step(Dnet.h, D_expert.h, k * B, ne, D_policy.h, k * B, npi, _vp(raw)))
+            if gl.kind == GAN_BCELoss.kind:
+                Dnet.ctx.check(Dnet.ctx.lib.crux_gail_d_step(Dnet.h, D_expert.h, k * B, ne, D_policy.h, k * B, npi, _vp(raw)))
+            else:
+                Dnet.ctx.check(Dnet.ctx.lib.crux_gail_d_step_gan(Dnet.h, D_expert.h, k * B, ne, D_policy.h, k * B, npi, gl.kind, getattr(gl, "λ", 0.0), getattr(gl, "seed", 0),
+                                                                 p.gp_counter, _vp(raw)))
+                p.gp_counter += 1 if gl.kind == GAN_WLossGP.kind else 0
             total += 1
             if total >= p.max_batches:
                 stop = True; break
@@ -59,12 +137,13 @@ def gail_reward_(Dnet, buf, alpha_r=0.5, Rscale=1.0):
     return float(m[0])
 
 
-def OnPolicyGAIL(pi, S, gamma, D, demo, lambda_gae=0.95, alpha_r=0.5, normalize_demo=True, solver=None, d_opt=None, Rscale=1.0, **kw):
+def OnPolicyGAIL(pi, S, gamma, D, demo, lambda_gae=0.95, alpha_r=0.5, normalize_demo=True, solver=None, d_opt=None, Rscale=1.0, gan_loss=None, **kw):
     """OnPolicyGAIL(; pi, S, gamma, lambda_gae, D_demo, alpha_r, normalize_demo, D::ContinuousNetwork, solver=PPO, gan_loss=GAN_BCELoss(), d_opt, Rscale)
     (src/model_free/il/on_policy_gail.jl:26-69): PPO whose post_batch_callback trains the discriminator on (demo, copy of the fresh batch),
-    overwrites the rewards with the discriminator's, and refills GAE / returns / whitened advantages."""
+    overwrites the rewards with the discriminator's, and refills GAE / returns / whitened advantages. gan_loss: one of GANLosses (None: GAN_BCELoss()); the reward
+    does not depend on it (:51)."""
     d = dict(d_opt or {}); d.setdefault("name", "discriminator_")
-    dp = TrainingParams(loss=gail_d_loss, **d)
+    dp = TrainingParams(loss=gail_d_loss if gan_loss is None else gail_d_loss(gan_loss), **d)
     A = pi.space if hasattr(pi, "space") else ContinuousSpace(actor(pi).network.dims[-1])
     demo = copy_buffer(demo)
     if normalize_demo:
@@ -96,11 +175,16 @@ def _d_info(p, rows, raw):
 
 
 def batch_train_gail_d_chain_(Dnet, p, D_expert, D_policy, info=None):
-    """batch_train_gail_d_ as one C call (crux_gail_d_batch_train): the same shuffles, pairs and steps, bit for bit, with one host synchronisation."""
+    """batch_train_gail_d_ as one C call (crux_gail_d_batch_train; crux_gail_d_batch_train_gan for LS, hinge and W): the same shuffles, pairs and steps, bit for bit, with one
+    host synchronisation. GAN_WLossGP is refused by the entry (CRUX_EUNSUP: the penalty takes its scratch per step); batch_train_gail_d_ is its path."""
     _ensure_opt(Dnet, p)
     raw, rows = np.zeros(L.INFO_N, np.float32), np.zeros((p.epochs, L.INFO_N), np.float32)
+    gl, lib = _gan(p), Dnet.ctx.lib
     try:
-        Dnet.ctx.check(Dnet.ctx.lib.crux_gail_d_batch_train(Dnet.h, D_expert.h, D_policy.h, p.batch_size, p.epochs, _max_batches(p), p.shuffle_seed, p.shuffle_counter, _vp(raw), _vp(rows)))
+        if gl.kind == GAN_BCELoss.kind:
+            Dnet.ctx.check(lib.crux_gail_d_batch_train(Dnet.h, D_expert.h, D_policy.h, p.batch_size, p.epochs, _max_batches(p), p.shuffle_seed, p.shuffle_counter, _vp(raw), _vp(rows)))
+        else:
+            Dnet.ctx.check(lib.crux_gail_d_batch_train_gan(Dnet.h, D_expert.h, D_policy.h, p.batch_size, p.epochs, _max_batches(p), p.shuffle_seed, p.shuffle_counter, gl.kind, _vp(raw), _vp(rows)))
     finally:
         p.shuffle_counter += int(raw[L.INFO["epochs_run"]]) if raw[L.INFO["epochs_run"]] > 0 else 0
     out = _d_info(p, rows, raw)
@@ -123,14 +207,18 @@ def nda_advantages_(buf, V, Vc, lambda_gae, gamma):
 
 
 def nda_gail_round_(Dnet, Dnda, dp, dpn, demo, nda, buf, copyD, copyN, V, Vc, alpha_r, lambda_gae, gamma, info=None):
-    """The whole GAIL_callback (nda_gail_js.jl:28-63) as one C call (crux_nda_gail_round); both shuffle counters advance by the epochs run."""
+    """The whole GAIL_callback (nda_gail_js.jl:28-63) as one C call (crux_nda_gail_round; crux_nda_gail_round_gan for LS, hinge and W, the kind of dp.loss for both
+    discriminators); both shuffle counters advance by the epochs run."""
     _ensure_opt(Dnet, dp); _ensure_opt(Dnda, dpn)
     rD, rN, out3 = np.zeros(L.INFO_N, np.float32), np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
+    gl, lib = _gan(dp), Dnet.ctx.lib
+    head = (Dnet.h, Dnda.h, demo.h, nda.h, buf.h, copyD.h, copyN.h, V.h, Vc.h, dp.batch_size, dp.epochs, _max_batches(dp), dp.shuffle_seed, dp.shuffle_counter,
+            dpn.batch_size, dpn.epochs, _max_batches(dpn), dpn.shuffle_seed, dpn.shuffle_counter, float(alpha_r), float(lambda_gae), float(gamma))
     try:
-        Dnet.ctx.check(Dnet.ctx.lib.crux_nda_gail_round(Dnet.h, Dnda.h, demo.h, nda.h, buf.h, copyD.h, copyN.h, V.h, Vc.h,
-                                                        dp.batch_size, dp.epochs, _max_batches(dp), dp.shuffle_seed, dp.shuffle_counter,
-                                                        dpn.batch_size, dpn.epochs, _max_batches(dpn), dpn.shuffle_seed, dpn.shuffle_counter,
-                                                        float(alpha_r), float(lambda_gae), float(gamma), _vp(rD), _vp(rN), _vp(out3)))
+        if gl.kind == GAN_BCELoss.kind:
+            Dnet.ctx.check(lib.crux_nda_gail_round(*head, _vp(rD), _vp(rN), _vp(out3)))
+        else:
+            Dnet.ctx.check(lib.crux_nda_gail_round_gan(*head, gl.kind, _vp(rD), _vp(rN), _vp(out3)))
     finally:
         for p, raw in ((dp, rD), (dpn, rN)):
             p.shuffle_counter += int(raw[L.INFO["epochs_run"]]) if raw[L.INFO["epochs_run"]] > 0 else 0
@@ -142,15 +230,18 @@ def nda_gail_round_(Dnet, Dnda, dp, dpn, demo, nda, buf, copyD, copyN, V, Vc, al
     return info
 
 
-def NDA_GAIL_JS(pi, S, D_demo, D_nda, Vc, gamma, D, Dnda, lambda_gae=0.95, alpha_r=0.5, normalize_demo=True, solver=None, d_opt=None, d_opt_nda=None, **kw):
+def NDA_GAIL_JS(pi, S, D_demo, D_nda, Vc, gamma, D, Dnda, lambda_gae=0.95, alpha_r=0.5, normalize_demo=True, solver=None, d_opt=None, d_opt_nda=None, gan_loss=None, **kw):
     """NDA_GAIL_JS(; π, S, 𝒟_demo, 𝒟_nda, Vc, γ, λ_gae=0.95, αr=0.5, normalize_demo=true, D, Dnda, solver=LagrangePPO, gan_loss=GAN_BCELoss(), d_opt, d_opt_nda)
     (src/model_free/il/nda_gail_js.jl:1-65): the solver (LagrangePPO: cost critic Vc, :cost columns, PID penalty) with a post_batch_callback that trains D on
     (demonstrations, copy of the fresh batch) and Dnda on (negative demonstrations, another copy), sets :r from D, :cost = max(0, r_nda - r), and refills GAE, returns
     and both whitened advantages with the actor-critic's critic and Vc. The callback replaces the solver's own (the later keyword wins in the reference, :64) and is one
-    C call (crux_nda_gail_round). Both demonstration buffers are copied, and normalised when asked; the caller's stay as they were."""
+    C call (crux_nda_gail_round). Both demonstration buffers are copied, and normalised when asked; the caller's stay as they were.
+    gan_loss: one kind for both discriminators (:19-20; None: GAN_BCELoss()). LS, hinge and W take the round's _gan form; GAN_WLossGP cannot run inside a chain, so its
+    callback is the round's parts in turn: batch_train_gail_d_ per discriminator (a host loop of steps), nda_reward_cost_, nda_advantages_."""
     d = dict(d_opt or {}); d.setdefault("name", "discriminator_")
     dn = dict(d_opt_nda or {}); dn.setdefault("name", "nda_discriminator_")
-    dp, dpn = TrainingParams(loss=gail_d_loss, **d), TrainingParams(loss=gail_d_loss, **dn)
+    loss = gail_d_loss if gan_loss is None else gail_d_loss(gan_loss)
+    dp, dpn = TrainingParams(loss=loss, **d), TrainingParams(loss=loss, **dn)
     A = pi.space if hasattr(pi, "space") else ContinuousSpace(actor(pi).network.dims[-1])
     demo, nda = copy_buffer(D_demo), copy_buffer(D_nda)
     if normalize_demo:
@@ -159,6 +250,11 @@ def NDA_GAIL_JS(pi, S, D_demo, D_nda, Vc, gamma, D, Dnda, lambda_gae=0.95, alpha
     copies = []
 
     def GAIL_callback(buf, info):
+        if _gan(dp).kind == GAN_WLossGP.kind:
+            batch_train_gail_d_(D, dp, demo, copy_buffer(buf), info=info); batch_train_gail_d_(Dnda, dpn, nda, copy_buffer(buf), info=info)      # :29, :30
+            info["disc_reward"], info["disc_nda_cost"], _ = nda_reward_cost_(D, Dnda, buf, alpha_r)                                             # :33-49
+            nda_advantages_(buf, critic(sv.agent.pi), Vc, lambda_gae, gamma)                                                                     # :51-61
+            return
         if not copies or copies[0].capacity < len(buf):
             copies[:] = [buffer_like(buf, capacity=buf.capacity), buffer_like(buf, capacity=buf.capacity)]      # the two deepcopy(𝒟) (:29, :30), refilled on the device every round
         nda_gail_round_(D, Dnda, dp, dpn, demo, nda, buf, copies[0], copies[1], critic(sv.agent.pi), Vc, alpha_r, lambda_gae, gamma, info=info)

@@ -7,6 +7,8 @@ changes. The recording stores (theta, thetadot) while the library's Pendulum obs
 
 ActorCritic(GaussianPolicy(3 -> 64 -> 64 -> 1 relu, logSigma 0), critic 3 -> 64 -> 64 -> 1), Vc of the critic's shape, D and Dnda 4 -> 64 -> 64 -> 1; dN = 1024 steps from
 8 environments per iteration, every learner 4 epochs of minibatches of 256. The callback of every iteration is one C call (crux_nda_gail_round).
+--gan-loss picks the discriminators' loss from GANLosses (src/extras/gans.jl): BCE (the default), LS, Hinge and W keep the one-call round; WGP (Wasserstein + gradient
+penalty) runs the round's parts in turn with a host loop of discriminator steps -- 512 demonstration rows and 1024 rollout rows under minibatches of 256 give equal halves.
 lagrange_ppo_loss estimates the episode cost from EVERY minibatch (sum(cost) / sum(episode_end), ppo.jl:86), which needs episode ends in every minibatch: episodes of
 16 steps put 64 of them into the 1024 rows."""
 import argparse
@@ -27,6 +29,7 @@ def net(dims, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=20 * 1024); ap.add_argument("--dN", type=int, default=1024); ap.add_argument("--n_envs", type=int, default=8)
+    ap.add_argument("--gan-loss", choices=list(crux.GANLosses), default="BCE")
     a = ap.parse_args()
     d = dict(np.load(os.path.join(ROOT, "tests", "golden", "pendulum_transitions.npz")))
     n = d["s"].shape[1]; S, A = crux.ContinuousSpace(3), crux.ContinuousSpace(1)
@@ -40,8 +43,8 @@ def main():
     D, Dnda = crux.ContinuousNetwork(net([4, 64, 64, 1], 3)[0], seed=3), crux.ContinuousNetwork(net([4, 64, 64, 1], 4)[0], seed=4)
     opt = {"epochs": 4, "batch_size": 256}
     sv = crux.NDA_GAIL_JS(pi, S, demo, nda, Vc, 0.99, D, Dnda, N=a.N, dN=a.dN, max_steps=16, normalize_demo=False, a_opt=dict(opt), c_opt=dict(opt), cost_opt=dict(opt),
-                          d_opt=dict(opt), d_opt_nda=dict(opt))
-    print("demonstrations: %d rows, as many negative ones; %d iterations of %d steps" % (n, a.N // a.dN, a.dN))
+                          d_opt=dict(opt), d_opt_nda=dict(opt), gan_loss=crux.GANLosses[a.gan_loss])
+    print("demonstrations: %d rows, as many negative ones; %d iterations of %d steps; discriminator loss %r" % (n, a.N // a.dN, a.dN, crux.GANLosses[a.gan_loss]))
     crux.solve(sv, crux.PendulumMDP(n_envs=a.n_envs, seed=0))
     for k in (0, len(sv.history) - 1):
         h = sv.history[k]

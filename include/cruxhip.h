@@ -118,7 +118,7 @@ int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
  * (include/crux_rng.h). Allocates; call it outside any chain. crux_mlp_get_spectral (synchronises; tests, checkpoints): u, v (in_l values per SN layer) and sigma
  * (one per SN layer) of the last forward call; any pointer may be NULL. crux_mlp_spectral_layers: the n_iter the handle carries, returns the number of SN layers.
  * An SN handle is accepted by crux_mlp_forward*, crux_mlp_forward_cached / crux_mlp_backward, crux_gail_d_step, crux_gail_d_batch_train, crux_gail_reward,
- * crux_nda_reward_cost, crux_nda_gail_round (D and Dnda), crux_offgail_d_step / _round / _reward, get / set params, the Adam entries and crux_mlp_copy (equal SN
+ * crux_nda_reward_cost, crux_nda_gail_round (D and Dnda), their *_gan forms with every kind but CRUX_GAN_WGP, crux_offgail_d_step / _round / _reward, get / set params, the Adam entries and crux_mlp_copy (equal SN
  * layers in both handles). Every other entry that takes a crux_mlp reads the raw weights and returns CRUX_EUNSUP naming itself.
  * Deviation: L_D(GAN_BCELoss) calls D on the expert half and then on the policy half (src/extras/gans.jl:9), so the reference advances u twice per
  * on-policy discriminator step and the halves see slightly different sigma; the device forms ONE pass over both halves, u advances once. The two coincide at the
@@ -796,6 +796,10 @@ int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo,
  * act_dim + obs_dim -> 1; no crux_adam_init. CRUX_EUNSUP: recording into a fused sequence.                                                                         */
 int32_t crux_gail_d_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed,
                                 uint64_t shuffle_counter, float* info_out, float* epoch_rows);
+/* crux_gail_d_batch_train with the loss kind (CRUX_GAN_BCE, _LS, _HINGE, _W; one step = crux_gail_d_step_gan's arithmetic, bit-identical to the host loop over it; kind
+ * BCE is crux_gail_d_batch_train). CRUX_GAN_WGP is refused with CRUX_EUNSUP: the penalty takes its scratch per step, a chain owns one block for all of its steps. */
+int32_t crux_gail_d_batch_train_gan(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed,
+                                    uint64_t shuffle_counter, int32_t gan_kind, float* info_out, float* epoch_rows);
 /* The reward and the hinge cost of GAIL_callback (nda_gail_js.jl:33-49) over all rows of buf: one gather of vcat(a, s) (one-hot actions as 0/1) feeds both networks;
  * r = ar logsigmoid(D_out) - (1 - ar) logcompsigmoid(D_out) (:34, the Float32 operation order of crux_gail_reward: buf[:r] is bit-identical to
  * crux_gail_reward(D, buf, ar, 1)), r_nda the same from Dnda (:43), c = max(0, r_nda - r) (:44); buf[:r] = r, buf[:cost] = c. out3 (host [3]): mean(r)
@@ -823,6 +827,11 @@ int32_t crux_nda_gail_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux
                             int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
                             int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
                             float alpha_r, float lambda, float gamma, float* info_D, float* info_Dnda, float* out3);
+/* crux_nda_gail_round with one loss kind for both discriminators (nda_gail_js.jl:19-20): the four kinds of crux_gail_d_batch_train_gan, WGP refused as there. */
+int32_t crux_nda_gail_round_gan(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
+                                int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
+                                int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
+                                float alpha_r, float lambda, float gamma, int32_t gan_kind, float* info_D, float* info_Dnda, float* out3);
 
 /* DeepEnsemble / DeepClassificationEnsemble (src/extras/deep_ensembles.jl) on the member-grouped passes of the dense engine ---------------------------------------
  * nets: M in 1..16 distinct ContinuousNetwork handles of ONE context with equal widths and activations (the members, :3, :41). All members read the same input
@@ -875,6 +884,26 @@ int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* expert, int64_t off_ex, int64
 /* GAIL_callback reward (:49-55): D_out = value(D, a, s); r = ar*logsigmoid(D_out) - (1-ar)*logcompsigmoid(D_out) (src/utils.jl:140-143);
  * buffer[:r] .= r .* Rscale; *mean_r = mean(r) (info["disc_reward"]). fill_gae!/fill_returns!/whiten follow as separate calls.                      */
 int32_t crux_gail_reward(crux_mlp* D, crux_buffer* buf, float alpha_r, float rscale, float* mean_r);
+/* The discriminator losses of the GAIL family (src/extras/gans.jl; GANLosses, src/Crux.jl:83): gail_d_loss calls Lᴰ(gan_loss, D, a_E, a_pi, yD = (s_E,), yG = (s_pi,))
+ * with wD = 1f0 (on_policy_gail.jl:3). z = D(vcat(a, s)), sg = sigmoid(z), mean_e / mean_p over the n_ex expert and n_pi policy columns:
+ *   BCE    gans.jl:7-9     LBCE(z_e, 1) + LBCE(z_p, 0)                          (crux_gail_d_step)
+ *   LS     gans.jl:14      mean_e((sg - 1)^2) + mean_p(sg^2)                    seeds 2 (sg - 1) sg (1 - sg) / n_ex,  2 sg^2 (1 - sg) / n_pi
+ *   HINGE  gans.jl:19      mean_e(relu(1 - z)) + mean_p(relu(1 + z))            seeds -[z < 1] / n_ex,  [z > -1] / n_pi
+ *   W      gans.jl:24      mean_p(z) - mean_e(z)                                seeds -1 / n_ex,  1 / n_pi
+ *   WGP    gans.jl:34-40   W + lambda gradient_penalty(D, x_E, x_pi; target = 1f0) (src/extras/gradient_penalty.jl), lambda = 10f0 in the reference; noise_range
+ *                          (gans.jl:31) is carried by the reference and never read, so it has no argument here
+ * Kinks: relu's derivative at exactly 0 is taken as 0, so the hinge's seed vanishes at z = 1 (expert) and z = -1 (policy) [3P-memory: Zygote's rule, not
+ * re-checked against its source]. |d D / d xhat| = 0 gives a NaN penalty seed (0 / 0) as in crux_gradient_penalty. A NaN z gives a NaN seed for its column. */
+enum { CRUX_GAN_BCE = 0, CRUX_GAN_LS = 1, CRUX_GAN_HINGE = 2, CRUX_GAN_W = 3, CRUX_GAN_WGP = 4 };
+/* crux_gail_d_step with the loss kind. BCE, LS, HINGE, W: only the head differs (two Float64 half-sums in a fixed order, no float atomics); kind BCE is
+ * crux_gail_d_step bit for bit; DenseSN discriminators are taken as there; lambda_gp, gp_seed and gp_counter are not read. WGP: plain Dense handles only
+ * (CRUX_EUNSUP for a DenseSN one: the sweeps read the raw weights) with identity / relu / tanh layers; the interpolation broadcasts the halves against each other, so
+ * n_ex != n_pi is CRUX_EINVAL (the message names both; the reference throws DimensionMismatch), refused before anything is enqueued. The 3 B columns are
+ * [x_E | x_pi | xhat], xhat_j = eps_j x_pi,j + (1 - eps_j) x_E,j, eps_j = (float)u53(Philox(gp_seed, gp_counter, j, IQ_GP)) -- crux_gradient_penalty's draw; the
+ * rest is crux_advil_d_step's sequence with the opposite sign. info_out: LOSS (with lambda P for WGP), GRAD_NORM. A NaN in either half surfaces as CRUX_ENAN with the
+ * parameters untouched, for every kind. Two identical calls give identical bits.                                                                              */
+int32_t crux_gail_d_step_gan(crux_mlp* D, crux_buffer* expert, int64_t off_ex, int64_t n_ex, crux_buffer* policy, int64_t off_pi, int64_t n_pi, int32_t gan_kind, float lambda_gp,
+                             uint64_t gp_seed, uint64_t gp_counter, float* info_out);
 
 /* ddpg_target (ddpg.jl:6-8) when q2_targ = NULL and smooth_sigma < 0; td3_target (td3.jl:4-7) with both targets and the
  * smoothing policy GaussianNoiseExplorationPolicy(sigma; eps_min, eps_max, a_min, a_max) (policies.jl:510-514):

@@ -309,6 +309,27 @@ end
 gail_d_step!(D::HipNetwork, ex::HipBuffer, r_ex::UnitRange, pol::HipBuffer, r_pol::UnitRange, info=zeros(Float32, INFO_N)) =                     # il/on_policy_gail.jl:1-5 under training.jl:40-44
     (check(D.ctx, ccall((:crux_gail_d_step, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Float32}),
                         D.h, ex.h, first(r_ex) - 1, length(r_ex), pol.h, first(r_pol) - 1, length(r_pol), info)); info)
+# the discriminator losses of extras/gans.jl as the C ABI numbers them (CRUX_GAN_*); gan_kind maps the reference's loss objects onto them
+const GAN_BCE, GAN_LS, GAN_HINGE, GAN_W, GAN_WGP = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
+gan_kind(::Crux.GAN_BCELoss) = GAN_BCE; gan_kind(::Crux.GAN_LSLoss) = GAN_LS; gan_kind(::Crux.GAN_HingeLoss) = GAN_HINGE; gan_kind(::Crux.GAN_WLoss) = GAN_W; gan_kind(::Crux.GAN_WLossGP) = GAN_WGP
+gail_d_step_gan!(D::HipNetwork, ex::HipBuffer, r_ex::UnitRange, pol::HipBuffer, r_pol::UnitRange, kind::Int32, info=zeros(Float32, INFO_N); λ::Float32=10f0, seed::UInt64=UInt64(0), ctr::UInt64=UInt64(0)) =   # Lᴰ(gan_loss, ...) (gans.jl:14,19,24,34-40); WGP draws ε from (seed, ctr)
+    (check(D.ctx, ccall((:crux_gail_d_step_gan, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Int32, Float32, UInt64, UInt64, Ptr{Float32}),
+                        D.h, ex.h, first(r_ex) - 1, length(r_ex), pol.h, first(r_pol) - 1, length(r_pol), kind, λ, seed, ctr, info)); info)
+function gail_d_batch_train_gan!(D::HipNetwork, ex::HipBuffer, pol::HipBuffer, B::Integer, epochs::Integer, max_batches::Integer, seed::UInt64, ctr::UInt64, kind::Int32)   # batch_train!(D, d_opt, (;), 𝒟_demo, 𝒟) (training.jl:28-55), one synchronisation; not WGP
+    info = zeros(Float32, INFO_N); rows = zeros(Float32, INFO_N, epochs)
+    check(D.ctx, ccall((:crux_gail_d_batch_train_gan, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, UInt64, UInt64, Int32, Ptr{Float32}, Ptr{Float32}),
+                       D.h, ex.h, pol.h, Int32(B), Int32(epochs), Int32(max_batches), seed, ctr, kind, info, rows))
+    info, rows
+end
+function nda_gail_round_gan!(D::HipNetwork, Dnda::HipNetwork, demo::HipBuffer, nda::HipBuffer, 𝒟::HipBuffer, copyD::HipBuffer, copyN::HipBuffer, V::HipNetwork, Vc::HipNetwork,
+                             optD::NTuple{5,Integer}, optN::NTuple{5,Integer}, αr::Float32, λ_gae::Float32, γ::Float32, kind::Int32)      # GAIL_callback (nda_gail_js.jl:28-63); opt = (batch_size, epochs, max_batches, seed, counter)
+    iD = zeros(Float32, INFO_N); iN = zeros(Float32, INFO_N); out3 = zeros(Float32, 3)
+    check(D.ctx, ccall((:crux_nda_gail_round_gan, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                                                                Int32, Int32, Int32, UInt64, UInt64, Int32, Int32, Int32, UInt64, UInt64, Float32, Float32, Float32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                       D.h, Dnda.h, demo.h, nda.h, 𝒟.h, copyD.h, copyN.h, V.h, Vc.h, Int32(optD[1]), Int32(optD[2]), Int32(optD[3]), UInt64(optD[4]), UInt64(optD[5]),
+                       Int32(optN[1]), Int32(optN[2]), Int32(optN[3]), UInt64(optN[4]), UInt64(optN[5]), αr, λ_gae, γ, kind, iD, iN, out3))
+    iD, iN, out3
+end
 gail_reward!(D::HipNetwork, 𝒟::HipBuffer; αr=0.5f0, Rscale=1f0) = (m = Ref{Float32}(0); check(D.ctx, ccall((:crux_gail_reward, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float32, Float32, Ref{Float32}), D.h, 𝒟.h, αr, Rscale, m)); m[])   # :50-55
 
 # ---------------------------------------------------------------------------------------------------- LagrangePPO (rl/ppo.jl:70-215)
