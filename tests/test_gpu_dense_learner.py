@@ -115,7 +115,8 @@ WINDOW_CASES = [("categorical", [4, 64, 64, 2], RELU, 256), ("categorical", [4, 
 @pytest.mark.parametrize("kind,dims,act,bs", WINDOW_CASES, ids=["%s_%s_%s_bs%d" % (k, "-".join(map(str, d)), a, b) for k, d, a, b in WINDOW_CASES])
 def test_dense_learner_teacher_forced_windows(gpu_ctx, capfd, kind, dims, act, bs):
     """Two teacher-forced windows of four minibatch steps (steps 2..5 and 9..12 of the oracle's trajectory) as in test_learner_dispatch_over_random_shapes_matches_the_oracle,
-    with named shapes instead of drawn ones and the minibatches of the reference's examples."""
+    with named shapes instead of drawn ones and the minibatches of the reference's examples.
+    (Its Gaussian rows of 4..8 actions train on fully clipped, dead surrogate gradients -- logprob ~ N(-1.2, 0.05); live gradients and the row edges: test_gpu_learner_row_edges.py.)"""
     rng = np.random.default_rng(2027); od = dims[0]; ad = dims[-1] if kind != "value" else 2; disc = kind == "categorical"; N = bs * 14
     acts = parity.CRITIC_ACTS["cheetah_ref"] if act == "cheetah_critic" else [act, act, "identity"]
     act_col = np.eye(ad, dtype=bool)[:, rng.integers(0, ad, N)] if disc else rng.normal(0, 0.7, (ad, N)).astype(np.float32)

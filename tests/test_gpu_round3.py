@@ -383,7 +383,8 @@ def test_learner_dispatch_over_random_shapes_matches_the_oracle(gpu_ctx):
     """Which kernel trains a network is decided by its shape (feature-split / two-CU / one-CU register-resident kernels, the dense engine, the generic one-workgroup learner),
     and every shape list is closed. Twenty random Chain(Dense, Dense, Dense) learners -- inputs 2..20, hidden widths in and out of the 64-wide family, 1..6 outputs, relu /
     tanh / mixed activations, categorical / Gaussian / critic heads, minibatches of 32..200 -- each replay two teacher-forced windows of four minibatch steps from the oracle's
-    state (steps 2..5 and 9..12 of its trajectory): whatever kernel the dispatch picks must land on the oracle's parameters."""
+    state (steps 2..5 and 9..12 of its trajectory): whatever kernel the dispatch picks must land on the oracle's parameters.
+    (Its Gaussian rows of 4..8 actions train on fully clipped, dead surrogate gradients -- logprob ~ N(-1.2, 0.05); live gradients and the row edges: test_gpu_learner_row_edges.py.)"""
     rng = np.random.default_rng(2026)
     hid = [(64, 64), (64, 32), (32, 32), (128, 128), (48, 48), (64, 16), (256, 64), (64, 64), (64, 64)]
     worst = 0.0
@@ -538,7 +539,8 @@ def test_softq_refuses_a_non_positive_alpha_before_any_device_work(gpu_ctx):
 def test_gym_shapes_on_the_feature_split_kernel(gpu_ctx, capfd, od, ad, kind, act):
     """The standard Gym observation / action sizes added to the feature-split learner's dispatch in round 3 (Acrobot 6 / 3, MountainCar 2 / 3, LunarLanderContinuous 8 / 2, Hopper 11 / 3,
     BipedalWalker 24 / 4, Ant 27 / 8; 64-64 hidden): two teacher-forced windows of eight full-minibatch steps each against the oracle (B = 128: the feature-split kernel;
-    CRUX_FS=0 would send these shapes to the dense engine)."""
+    CRUX_FS=0 would send these shapes to the dense engine).
+    (Its Gaussian rows of 4..8 actions train on fully clipped, dead surrogate gradients -- logprob ~ N(-1.2, 0.05); live gradients and the row edges: test_gpu_learner_row_edges.py.)"""
     rng = np.random.default_rng(77 + od + ad); bs = 128; N = bs * 20; disc = kind == "categorical"
     if disc:
         ai = rng.integers(0, ad, N); actn = np.eye(ad, dtype=bool)[:, ai]
