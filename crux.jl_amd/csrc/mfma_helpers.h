@@ -70,6 +70,14 @@ __device__ __forceinline__ float row16_reduce_scatter(const float (&v)[16], int 
   const float snd = b0 ? v2[0] : v2[1], kp = b0 ? v2[1] : v2[0];
   return kp + dpp_x<0xB1>(snd);
 }
+// Sum of ONE per-lane value over the 16 lanes of a row; every lane gets the total. The pairing tree is the one row16_reduce_scatter applies to every index -- {c, 15-c},
+// then c^7, c^3, c^1, the own partial as the left operand -- so lane c holds the bits the scatter leaves in lane c for an index whose per-lane values are v.
+__device__ __forceinline__ float row16_sum_all(float v) {
+  v = v + dpp_x<0x140>(v);
+  v = v + dpp_x<0x141>(v);
+  v = v + dpp_x<0x1B>(v);
+  return v + dpp_x<0xB1>(v);
+}
 // Sum over the 4 lanes that share c (one per 16-lane row); every lane gets the total. v_permlane16/32_swap are written as
 // inline asm: the hipcc (ROCm 7.2) builtins return the same register for both results when both inputs are one value.
 // s_nop 1 before = the VALU-write -> permlane-read hazard (2 wait states); the trailing s_nop covers the consumer.

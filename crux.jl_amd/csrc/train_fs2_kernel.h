@@ -179,6 +179,14 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   // 27-input Gaussian head, at 256 vector registers with 61 spilled either way. There ka() is the plain kernarg pointer (the compiler hoists its loads to the entry, as it does
   // a.field), smr is sm, and the predicates, the KL test, the carried order_nxt and the packed rows' scalars are written as before.
   constexpr bool PT = PXK && IN >= 27 && KIND == MFK_GAUSSIAN;
+  // The plain forms (and their timing twins) alone: (1) STAT_SKIP -- a step whose statistics nobody reads forms none (the head's gradient words, b3 | log-sigma, number four or
+  // fewer: each is summed over the row on its own); (2) W2_TILED -- a wave's two W2 tiles are totalled and updated one after the other, the second tile's peer loads still landing.
+  // The replica-group and lagrange forms keep the parent's text at both sites.
+  constexpr bool PLAIN = !PX && !LAG;
+  constexpr int NGW = OUT + (KIND == MFK_GAUSSIAN ? OUT : 0);
+  // (forms that gain spilled scalar registers with STAT_SKIP keep their text: the timing twins of the value heads, 1 - 4 more, and the 8-64-64-2 Gaussian heads, 16 -> 18)
+  constexpr bool STAT_SKIP = PLAIN && NGW <= 4 && !(TIMING && KIND == MFK_VALUE) && !(IN == 8 && OUT == 2 && KIND == MFK_GAUSSIAN);
+  constexpr bool W2_TILED = PLAIN && WT == 2;
   auto ka = [&]() { auto* q = (const __attribute__((address_space(4))) TrainArgs*)__builtin_amdgcn_kernarg_segment_ptr(); if constexpr (!PT) asm volatile("" : "+s"(q)); return q; };
   const int p = (int)(blockIdx.x >> 3);
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -402,12 +410,20 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   };
   // the three peers' partials of the own tiles: issue the loads (phase 1 is complete: they are in the L2) ...
   auto w2_loads = [&](f32x4 (&pw)[NWG - 1][WT]) {
+    if constexpr (W2_TILED) {      // tile-major: the three loads of tile 0 are the first to land
+#pragma unroll
+      for (int mm = 0; mm < WT; ++mm)
+#pragma unroll
+        for (int j = 0; j < NWG - 1; ++j) { const int q = j == 0 ? (p ^ 1) : ((p ^ 2) & 2) + (j - 1);
+          const float* peer = a.xbuf + (size_t)(((int)(xstep & 1u) * NWG + q)) * XSLOT;
+          asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(pw[j][mm]) : "v"(peer + Lt::xW2 + tid * (4 * WT) + 4 * mm) : "memory"); }
+    } else {
 #pragma unroll
     for (int j = 0; j < NWG - 1; ++j) { const int q = j == 0 ? (p ^ 1) : ((p ^ 2) & 2) + (j - 1);      // partner, then the other pair's first and second workgroup
       const float* peer = a.xbuf + (size_t)(((int)(xstep & 1u) * NWG + q)) * XSLOT;
 #pragma unroll
       for (int mm = 0; mm < WT; ++mm)
-        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(pw[j][mm]) : "v"(peer + Lt::xW2 + tid * (4 * WT) + 4 * mm) : "memory"); }
+        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(pw[j][mm]) : "v"(peer + Lt::xW2 + tid * (4 * WT) + 4 * mm) : "memory"); } }
   };
   // ... and, once they are in (the caller has waited), the total (s0 + s1) + (s2 + s3) -- own + partner, the other pair in index order, then the two pair sums: the same bits
   // in all four workgroups
@@ -436,6 +452,22 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         mW2[mm][r] = m_; vW2[mm][r] = v_; tW2[mm][r] -= d;
         sm[Lt::oW2R + (16 * mp0 + 4 * g + r) * FS_LD + 16 * (m0 + mm) + c] = tW2[mm][r]; }
       *(f32x4*)&sm[Lt::oW2C + (16 * (m0 + mm) + c) * FS_LD + 16 * mp0 + 4 * g] = tW2[mm]; } };
+  // W2_TILED: total, suspect test, norm share and Adam of ONE owned tile (the caller has waited for that tile's three loads): per element the arithmetic of w2_total / w2_check /
+  // adam_w2, the tiles in the same order -- the same bits, the gradient norm's terms included
+  auto w2_tile = [&](const int mm, f32x4 (&gW2)[WT], f32x4 (&pw)[NWG - 1][WT], bool want_ssq, float& ssq, bool& bad) {
+#pragma unroll
+    for (int j = 0; j < NWG - 1; ++j) asm volatile("" : "+v"(pw[j][mm]));      // (asm statements keep their order: every use of a loaded value follows the wait)
+    gW2[mm] = (gW2[mm] + pw[0][mm]) + (pw[1][mm] + pw[2][mm]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bad = bad || isnan(gW2[mm][r]);
+    if (want_ssq) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ssq += gW2[mm][r] * gW2[mm][r]; }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { float m_ = mW2[mm][r], v_ = vW2[mm][r]; const float d = adam1(gW2[mm][r], m_, v_, ak);
+      mW2[mm][r] = m_; vW2[mm][r] = v_; tW2[mm][r] -= d;
+      sm[Lt::oW2R + (16 * mp0 + 4 * g + r) * FS_LD + 16 * (m0 + mm) + c] = tW2[mm][r]; }
+    *(f32x4*)&sm[Lt::oW2C + (16 * (m0 + mm) + c) * FS_LD + 16 * mp0 + 4 * g] = tW2[mm]; };
   // the small parameters (everything but W2), shared by all 512 threads
   int so_part[NSC], so_master[NSC]; bool so_ok[NSC], so_ex[NSC];
 #pragma unroll
@@ -607,7 +639,19 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     // the W2 partials (phase 1 complete) are in the L2 already -- same box: C2 5.40 -> 5.396, C5 7.61 -> 7.50 us per step. (The per-step replica-group form needs both totals
     // before its exchange.)
     constexpr bool W2_FIRST = !(PX && !PXK);
-    if constexpr (W2_FIRST) {
+    if constexpr (W2_TILED) {
+      // Tile 0 is totalled and updated while tile 1's three loads are still landing. The partial wait is counted by hand: vmcnt counts every vector-memory operation of the
+      // wave, the granule stores put above included, and a store may retire out of order with a load -- but loads return their data in the order they were issued (the gfx9
+      // rule the compiler's own counted waits rest on), and the six loads are the youngest vector-memory operations of the wave. At most NWG - 1 = 3 operations outstanding
+      // therefore means at most the LAST three loads -- tile 1's: tile 0's have landed whatever the stores did. Stores still in flight can only make it wait longer.
+      static_assert(NWG - 1 == 3, "the partial wait counts a tile's three peer loads");
+      if (!failed) {      // (every compute wave is past B_2: nobody reads the W2 masters any more)
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        w2_tile(0, gW2, pw, want_ssq, ssq, bad_tot);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        w2_tile(1, gW2, pw, want_ssq, ssq, bad_tot); }
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if constexpr (W2_FIRST) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (!failed) { w2_total(gW2, pw); w2_check(gW2, want_ssq, ssq, bad_tot); adam_w2(gW2); }      // (every compute wave is past B_2: nobody reads the W2 masters any more)
     }
@@ -760,6 +804,9 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         if constexpr (LAG) lag_advance(xcur);
         const float* xs_c = xs + xcur * XSB; const float* sc_c = sc + xcur * SCB;
         FS2_T(1);
+        // the head's seven statistics sums have three readers: the report below (static_report || kl_on, or a suspect step -- whose row reaches the caller from the first epoch
+        // only: the write-back's infos[CRUX_INFO_LOSS]), step_exit's KL test (kl_on) and the replica group's statistics word (PX: not a plain form). Like want_ssq, plus epoch 0.
+        auto want_stats = [&]() -> bool { return !STAT_SKIP || static_report(st) || kl_on() || epochs_run == 0; };      // (formed where it is read: no register across the forward pass)
         // ======================= forward, C orientation: D[feature 16m+4g+r][sample c] =======================
         f32x4 h1[4]; f32x4 h2[MH];
         constexpr bool W3_REG = OUT <= 2;
@@ -905,6 +952,13 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
             for (int mm = 0; mm < MH; ++mm)
 #pragma unroll
               for (int r = 0; r < 4; ++r) h2[mm][r] = actg<ACT2>(h2[mm][r], d2[mm][r]); }       // h2 now holds dZ2 of this half
+          if (STAT_SKIP && h == 0 && !want_stats()) {      // nobody reads this step's statistics: the gradient words of b3 | log-sigma alone, each summed over the row; the
+            float gq = 0.f;                               // statistic words of the partial block keep their last values (the tail exchanges them, no one looks)
+            int ln = lane; asm volatile("" : "+v"(ln));   // (the lane predicates are formed here: hoisted out of the step they are lane masks that do not fit the scalar file)
+#pragma unroll
+            for (int o = 0; o < NGW; ++o) { const float tot = row16_sum_all(o < OUT ? dz[o < OUT ? o : 0] : dex[o < OUT ? 0 : o - OUT]); gq = ((ln & 15) == 7 + o) ? tot : gq; }
+            if ((unsigned)(ln - 7) < (unsigned)NGW) part[Lt::pMISC + ln] = gq;      // row g == 0, c = 7 .. 7 + NGW - 1: the words the reduce-scatter's lanes write
+          } else
           if (h == 0) {
             constexpr int NVB = 7 + OUT + (KIND == MFK_GAUSSIAN ? OUT : 0), NV = NVB + (LAG ? 1 : 0);
             float mv[((NV + 15) / 16) * 16];
