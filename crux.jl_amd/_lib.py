@@ -195,6 +195,11 @@ SIGNATURES = {
     "crux_ensemble_train": (i32, [P(vp), i32, i32, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
     "crux_ensemble_passes": (i32, [P(vp), i32, vp, i64, P(vp), P(vp)]),
     "crux_ensemble_forward_recording": (i32, [P(vp), i32, i32, vp, i64, vp, vp]),
+    "crux_mixture_weights": (i32, [P(vp), i32, vp, vp, i64, vp, vp]),
+    "crux_mixture_logpdf": (i32, [P(vp), i32, vp, vp, vp, i64, vp]),
+    "crux_mixture_explore": (i32, [P(vp), i32, vp, vp, i64, u64, u64, u32, vp, vp, vp]),
+    "crux_mixture_step": (i32, [P(vp), i32, vp, vp, vp, vp, i64, vp]),
+    "crux_mixture_train": (i32, [P(vp), i32, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),

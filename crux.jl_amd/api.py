@@ -52,8 +52,10 @@ from .continual import (  # noqa: F401
     DiagonalFisherRegularizer, add_fisher_information_diagonal_, continual_learning, log_multitask_performances_, update_fisher_)
 from .ensembles import *   # noqa: F401,F403
 from .ensembles import DeepClassificationEnsemble, DeepEnsemble, individual_forward, logpdf, training_loss   # noqa: F401
+from .mixture import *   # noqa: F401,F403
+from .mixture import MixtureNetwork   # noqa: F401
 from .on_policy import _solve_on_policy
-from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles, continual   # noqa: F401
+from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles, continual, mixture   # noqa: F401
 
 
 def solve(solver, mdp=None):  # noqa: F811

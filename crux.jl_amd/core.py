@@ -465,6 +465,14 @@ def refuse_spectral(pi, who):
                              "(OnPolicyGAIL, OffPolicyGAIL, NDA_GAIL_JS) only" % who)
 
 
+def refuse_standalone(pi, who):
+    """Policy classes that the Sampler and the solvers do not take yet carry the reason in `not_a_solver_policy` (MixtureNetwork, mixture.py)."""
+    for q in ([] if pi is None else _leaves(pi)):
+        why = getattr(q, "not_a_solver_policy", None)
+        if why:
+            raise NotImplementedError("%s: %s" % (who, why))
+
+
 def polyak_average_(to, frm, tau=1.0):
     """polyak_average!(to, from, tau) (src/policies.jl:48-59) over every layer of the (possibly composite) policy."""
     for t, f in zip(_leaves(to), _leaves(frm)):
@@ -479,6 +487,7 @@ def copyto_(to, frm):
 
 def clone_policy(pi):
     """deepcopy(pi) for pi_minus (src/policies.jl:24-36): same architecture, copied parameters."""
+    refuse_standalone(pi, "clone_policy")
     if isinstance(pi, ActorCritic):
         return ActorCritic(clone_policy(pi.A), clone_policy(pi.C))
     if isinstance(pi, DoubleNetwork):
@@ -503,6 +512,7 @@ class PolicyParams:
     def __init__(self, pi, space=None, pi_explore=None, pi_minus=None, pa=None):
         self.pi, self.pi_explore, self.pi_minus = pi, pi_explore if pi_explore is not None else pi, pi_minus
         for q in (pi, pi_explore, pi_minus, pa):
+            refuse_standalone(q, "PolicyParams")
             refuse_spectral(q, "PolicyParams")
         self.pa = pa                                   # nominal action policy (policies.jl:17): the reference distribution of :importance_weight (sampler.jl:108-111)
         a = actor(pi)

@@ -874,6 +874,49 @@ int32_t crux_ensemble_train(crux_mlp* const* nets, int32_t M, int32_t kind, cons
 int32_t crux_ensemble_passes(crux_mlp* const* nets, int32_t M, const float* d_x, int64_t B, const float* const* d_dy, float* const* d_out);
 int32_t crux_ensemble_forward_recording(crux_mlp* const* nets, int32_t M, int32_t kind, const float* d_x, int64_t B, float* d_mean, float* d_evar);
 
+/* MixtureNetwork (src/policies.jl:189-242): a mixture-density policy on the member-grouped passes of the dense engine ------------------------------------------------
+ * nets: K in 1..16 distinct GaussianPolicy handles of ONE context with equal widths and activations: component k gives mu_k(s) [nd x B], its nd trailing extras are
+ * the constant trainable logSigma_k, unclamped (gaussian_logpdf, :333-336). wnet: the weights, either a ContinuousNetwork handle in -> K whose output the head turns
+ * into alpha_.j = softmax(z_.j) (max-subtracted: the reference's Chain(..., softmax)), or a handle without layers (crux_mlp_create with n_layers 0) whose K extras are
+ * the constant alpha, used raw and not renormalised (ConstantLayer; trainable). Arrays are (features, batch), Float32, device memory unless noted.
+ *   l_kj = sum_d [ -(a_dj - mu_kdj)^2 / (2 sigma_kd^2) - 0.9189385332046727f0 - logSigma_kd ],  t_kj = log alpha_kj + l_kj,
+ *   lp_j = m_j + log sum_k exp(t_kj - m_j) with m_j = max_k t_kj, k ascending; log alpha_kj = (z_kj - max z) - log sum exp(z - max z) for a weight network.
+ * Two deliberate differences from :229-233: the reference evaluates log(sum(alpha[i] .* exp.(logpdf_i))) directly, -Inf once every l_k < -103 (the form here is its
+ * commented-out weighted_logsumexp, utils.jl:147; they agree wherever the naive one is finite); and its alpha[i] is linear indexing, which with a weight network and
+ * B > 1 reads column 1's weights for every column, where alpha_kj here is per column (equal for constant weights and for B = 1).
+ * CRUX_EINVAL (nothing enqueued): K outside 1..16, a NULL or repeated handle, components of different widths, activations or contexts or without nd logSigma extras,
+ * a weight handle of another context, of another input or output width, with trailing extras (network form) or with other than K extras (constant form), B outside
+ * 1..2^20, and for step / train a handle without crux_adam_init or with other Adam hyper-parameters than component 0 (one optimiser covers all K + 1 handles).
+ * CRUX_EUNSUP: DenseSN layers anywhere, a SquashedGaussianPolicy component, K nd > 128 (the head's tile), a call while the fused executor records.                  */
+/* weights(pi, s): d_alpha [K x B] (the constant form broadcast over the columns); d_mu [K][nd x B] (or NULL) receives the components' means from the grouped forward
+ * pass. Enqueued only.                                                                                                                                              */
+int32_t crux_mixture_weights(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, const float* d_s, int64_t B, float* d_alpha, float* d_mu);
+/* logpdf(pi, s, a): d_a [nd x B] -> d_out [1 x B]. The grouped forward pass, the weight network's, one head launch. A NaN in s gives NaN. Enqueued only.            */
+int32_t crux_mixture_logpdf(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, const float* d_s, const float* d_a, int64_t B, float* d_out);
+/* exploration(pi, s) (:213-227, without its println). Column j: u = the Float32 uniform of Philox(seed, counter + j, stream, CRUX_RNG_ACTION); the component is the
+ * first k whose running sum of alpha_.j reaches u sum_k alpha_kj (the last one on rounding); eps_d = the Gaussian head's normal of Philox(seed, (counter + j)
+ * ceil(nd / 2) + d / 2, stream, CRUX_RNG_NOISE), output d & 1; a = mu_k + exp(logSigma_k) eps; logprob = lp_j of that a by crux_mixture_logpdf's arithmetic.
+ * d_a [nd x B], d_logprob [1 x B], d_component int32 [B] (0-based). Enqueued only.                                                                                  */
+int32_t crux_mixture_explore(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, const float* d_s, int64_t B, uint64_t seed, uint64_t counter, uint32_t stream, float* d_a, float* d_logprob,
+                             int32_t* d_component);
+/* train! (src/training.jl:13-25) with L = -(1 / B) sum_j w_j lp_j (mixture_network_tests.jl:61), d_w [1 x B] or NULL = ones. With r_kj = exp(t_kj - lp_j):
+ * dL/dmu_kdj = -(w_j / B) r_kj (a - mu) / sigma^2, dL/dlogSigma_kd = -(1 / B) sum_j w_j r_kj ((a - mu)^2 / sigma^2 - 1), dL/dz_kj = -(w_j / B)(r_kj - alpha_kj),
+ * dL/dalpha_k = -(1 / B) sum_j w_j r_kj / alpha_k (constant form). Launches: the grouped forward (L), the weight network's forward, the head (all seeds, Float64 block
+ * partials), a finishing launch that adds the partials in block order into the logSigma / alpha gradient slots, the grouped pullback (2 L - 1), the weight network's
+ * pullback, one sum-of-squares launch, one gated Adam launch over all K + 1 handles. info_out (host [CRUX_INFO_N + K]): LOSS, GRAD_NORM = the norm over all handles'
+ * gradients, then at [CRUX_INFO_N + k] component k's mean responsibility (1 / B) sum_j r_kj. A NaN in s, a, w, a parameter or any handle's gradient norm updates NO
+ * handle and returns CRUX_ENAN ("NaN detected!", :20). One host synchronisation. No float atomics: two identical calls give identical bits.                         */
+int32_t crux_mixture_step(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, const float* d_s, const float* d_a, const float* d_w, int64_t B, float* info_out);
+/* batch_train! (src/training.jl:28-55) over d_S [in x N], d_A [nd x N], d_W [1 x N] (or NULL), enqueued whole with one host synchronisation at the end. perms (HOST,
+ * [epochs][N] int64, 0-based): the row order of every epoch -- the entry draws nothing. Per partition of batch_size columns (a short last one runs, :40) the columns
+ * are gathered into the staging all handles read, then crux_mixture_step's launches follow; max_batches > 0 ends the call after that many steps (:45, :50).
+ * Bit-identical to crux_mixture_step on the same minibatches. epoch_rows (host [epochs x (CRUX_INFO_N + K)] or NULL): per epoch run, the row of its last step;
+ * info_out (host [CRUX_INFO_N + K]): the last epoch's row with BATCHES_TRAINED and EPOCHS_RUN. After a NaN norm no later step updates anything or writes a row; the
+ * call returns CRUX_ENAN and info_out is the row of the step that stopped. CRUX_EINVAL also for batch_size < 1, epochs outside 1..4096, N < 1 and a permutation entry
+ * outside 0..N-1.                                                                                                                                                   */
+int32_t crux_mixture_train(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, const float* d_S, const float* d_A, const float* d_W, int64_t N, int32_t batch_size, int32_t epochs,
+                           int32_t max_batches, const int64_t* perms, float* info_out, float* epoch_rows);
+
 /* DDPG / TD3 (src/model_free/rl/ddpg.jl, td3.jl) -----------------------------------------------------------
  * actor: deterministic ContinuousNetwork s -> a; critics: ContinuousNetwork over vcat(s, a).              */
 /* OnPolicyGAIL (src/model_free/il/on_policy_gail.jl): train!(D, gail_d_loss(GAN_BCELoss())) on rows [off_ex, off_ex+n_ex) of the expert buffer
