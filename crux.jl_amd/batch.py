@@ -40,7 +40,8 @@ def _check_actor_critic(pi, who):
     if not (isinstance(pi, ActorCritic) and isinstance(pi.A, GaussianPolicy) and isinstance(pi.C, DoubleNetwork)
             and isinstance(pi.C.N1, ContinuousNetwork) and isinstance(pi.C.N2, ContinuousNetwork)):
         raise TypeError("%s: pi must be ActorCritic(GaussianPolicy, DoubleNetwork(ContinuousNetwork, ContinuousNetwork))" % who)
-    # (a SquashedGaussianPolicy actor passes this test and is refused by the library -- CRUX_EUNSUP -- at the first step, as in SAC)
+    # (a constant-logSigma SquashedGaussianPolicy actor passes this test and is refused by the library -- CRUX_EUNSUP -- at the first step, as in SAC; the two-headed form
+    #  -- logSigma a network on mu's trunk -- is taken, squashed or not)
 
 
 def _check_advil(solver):
@@ -172,7 +173,7 @@ def BatchSAC(pi, S, D_train, dN=50, SAC_alpha=1.0, SAC_H_target=None, SAC_alpha_
     param_optimizers, normalize_training_data=true) (src/model_free/batch/sac.jl:27-55). With normalize_training_data the solver trains on
     normalize!(deepcopy(D_train), S, action_space(pi)): the caller's buffer is left as it is. param_optimizers: extra (ParamVector, TrainingParams) pairs."""
     _check_actor_critic(pi, "BatchSAC")
-    ad = pi.A.network.dims[-1]
+    ad = pi.A.act_dim if pi.A.two_headed else pi.A.network.dims[-1]      # SAC_H_target = -dim(A): the action's rows, not the two-headed output's 2 ad
     A = PolicyParams(pi).space
     if normalize_training_data:
         D_train = normalize_(copy_buffer(D_train), S, A)
@@ -192,6 +193,9 @@ def CQL(pi, S, D_train, CQL_alpha=1.0, CQL_is_distribution=None, CQL_alpha_thres
     a_opt, c_opt) (src/model_free/batch/cql.jl): BatchSAC plus the parameter optimiser CQL_alpha_ on CQL_log_alpha and the critic loss
     double_Q_loss + conservative_loss. CQL_is_distribution: None (U(-1, 1)^ad) or a UniformBox; anything else is not implemented."""
     _check_actor_critic(pi, "CQL")
+    if pi.A.two_headed:
+        raise NotImplementedError("CQL: a GaussianPolicy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only; CQL's sampled-action "
+                                  "terms draw from constant logSigma extras")
     if CQL_is_distribution is None:
         CQL_is_distribution = UniformBox(-1.0, 1.0)
     if not isinstance(CQL_is_distribution, UniformBox):

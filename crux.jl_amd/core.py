@@ -379,14 +379,111 @@ class DiscreteNetwork(NetworkPolicy):
             raise ValueError("DiscreteNetwork: %d outputs for %d logits" % (len(self.outputs), network.dims[-1]))
 
 
+def _chain_of(x):
+    return x.network if isinstance(x, NetworkPolicy) else x
+
+
+def _two_headed_chain(mu_chain, ls_chain, who):
+    """The ONE Chain of a Gaussian actor whose logSigma network shares its trunk with mu -- `Chain(base..., Dense(h, ad))` twice over the same `base` layers (the reference's
+    idiom, examples/rl/half_cheetah_mujoco.jl:37-43): the trunk, then a last layer of 2 ad rows [mu; logSigma]. Anything else is not implemented, by name."""
+    if any(isinstance(l, DenseSN) for l in mu_chain.layers + ls_chain.layers):
+        raise NotImplementedError("%s: DenseSN layers in mu or logSigma (the policy kernels read the raw weights)" % who)
+    tm, tl = mu_chain.layers[:-1], ls_chain.layers[:-1]
+    if len(tm) != len(tl) or any(a is not b for a, b in zip(tm, tl)):
+        raise NotImplementedError("%s: mu and logSigma have separate trunks; only networks that share every layer but the last (the same Dense objects, "
+                                  "Chain(base..., Dense(h, ad)) twice) are implemented" % who)
+    hm, hl = mu_chain.layers[-1], ls_chain.layers[-1]
+    if hm.act != "identity" or hl.act != "identity":
+        raise NotImplementedError("%s: the two head layers must have the identity activation (got %s / %s)" % (who, hm.act, hl.act))
+    if (hm.inp, hm.out) != (hl.inp, hl.out):
+        raise NotImplementedError("%s: the two head layers differ in shape (%d -> %d and %d -> %d)" % (who, hm.inp, hm.out, hl.inp, hl.out))
+    return Chain(*tm, Dense(hm.inp, 2 * hm.out)), hm.out
+
+
 class GaussianPolicy(NetworkPolicy):
-    """GaussianPolicy(mu::ContinuousNetwork, logSigma::AbstractArray): constant trainable log-std (src/policies.jl:315-350)."""
+    """GaussianPolicy(mu::ContinuousNetwork, logSigma) (src/policies.jl:315-350). logSigma an array: the constant trainable log-std. logSigma a Chain (or a ContinuousNetwork)
+    that shares every layer but the last with mu: the two-headed form -- one device handle whose last layer has 2 ad rows, [mu; logSigma(s)] (`two_headed`, `act_dim`).
+    The two-headed form is taken by SAC / BatchSAC, the Sampler and the methods action / exploration / logpdf / entropy below; the on-policy learners, BC, CQL, the
+    off-policy imitation learners (SQIL, OffPolicyGAIL, AdRIL) and MixtureNetwork refuse it by name. Separate (non-sharing) mu and logSigma networks are not implemented."""
     head = "gaussian"
+    two_headed = False
 
     def __init__(self, mu_chain, logSigma, **kw):
+        if isinstance(logSigma, (Chain, NetworkPolicy)):
+            self.mu_chain, self.logSigma_chain = _chain_of(mu_chain), _chain_of(logSigma)
+            net, ad = _two_headed_chain(self.mu_chain, self.logSigma_chain, type(self).__name__)
+            super().__init__(net, n_extra=0, **kw)
+            self.two_headed, self.act_dim = True, ad
+            self.ctx.check(self.ctx.lib.crux_mlp_set_sigma_head(self.h, 1))
+            # each head is Glorot-initialised as a layer of its own (fan_out = ad, what two separate Dense(h, ad) give): the joint layer was drawn with fan_out = 2 ad
+            h = net.dims[-2]; p = self.get_params(); n = 2 * ad * h; w0 = p.size - n - 2 * ad
+            p[w0:w0 + n] *= np.float32(np.sqrt((h + 2.0 * ad) / (h + ad))); self.set_params(p)
+            return
         logSigma = np.asarray(logSigma, np.float32).reshape(-1)
-        super().__init__(mu_chain, n_extra=logSigma.size, **kw)
+        super().__init__(_chain_of(mu_chain), n_extra=logSigma.size, **kw)
         p = self.get_params(); p[-logSigma.size:] = logSigma; self.set_params(p)
+
+    @property
+    def ascale_or_zero(self):
+        return float(getattr(self, "ascale", 0.0))
+
+    def params(self):
+        """Flux.params order. Two-headed: the shared trunk once (W, b, ...), then W_mu, b_mu, then W_logSigma, b_logSigma (policy_tests.jl:295: six arrays for a one-layer
+        trunk). get_params / set_params stay the device's flat vector, whose last layer interleaves the heads' rows (W [2 ad x h] column-major)."""
+        out = super().params()
+        if not self.two_headed:
+            return out
+        W, b, ad = out[-2], out[-1], self.act_dim
+        return out[:-2] + [np.asfortranarray(W[:ad]), b[:ad].copy(), np.asfortranarray(W[ad:]), b[ad:].copy()]
+
+    def set_flux_params(self, arrays):
+        """the inverse of params() for a two-headed policy: arrays in Flux order -> the device's flat vector"""
+        arrays = [np.asarray(a, np.float32) for a in arrays]
+        if self.two_headed:
+            arrays = arrays[:-4] + [np.vstack([arrays[-4], arrays[-2]]), np.concatenate([arrays[-3], arrays[-1]])]
+        self.set_params(np.concatenate([a.reshape(-1, order="F") for a in arrays]))
+
+    def _need_two(self, what):
+        if not self.two_headed:
+            raise NotImplementedError("%s.%s: implemented for the two-headed form (logSigma a network on mu's trunk) only" % (type(self).__name__, what))
+
+    def _cols(self, x, rows, what):
+        x = np.asarray(x, np.float32)
+        x = x.reshape(rows, 1) if x.ndim == 1 else x
+        if x.shape[0] != rows:
+            raise ValueError("%s: %d rows, expected %d" % (what, x.shape[0], rows))
+        return np.asfortranarray(x)
+
+    def action(self, s):
+        """action(pi, s) (policies.jl:331, 372): mu(s), ascale tanh(mu(s)) when squashed; [ad x B]"""
+        self._need_two("action"); s = self._cols(s, self.network.dims[0], "action"); B = s.shape[1]
+        a = np.empty((self.act_dim, B), np.float32, order="F")
+        self.ctx.check(self.ctx.lib.crux_sigma_head_explore(self.h, _vp(s), B, 0, 0, 0, _vp(a), None))
+        return a
+
+    def exploration(self, s, seed=0, counter=0):
+        """exploration(pi, s) (policies.jl:338-344, 388-394): (a [ad x B], logprob [1 x B]); eps of column j, row d = randn(Philox(seed, counter, stream = j ad + d, NOISE))"""
+        self._need_two("exploration"); s = self._cols(s, self.network.dims[0], "exploration"); B = s.shape[1]
+        a = np.empty((self.act_dim, B), np.float32, order="F"); lp = np.empty((1, B), np.float32)
+        self.ctx.check(self.ctx.lib.crux_sigma_head_explore(self.h, _vp(s), B, 1, int(seed), int(counter), _vp(a), _vp(lp)))
+        return a, lp
+
+    def logpdf(self, s, a):
+        """logpdf(pi, s, a) (policies.jl:346, 396): [1 x B]"""
+        self._need_two("logpdf"); s = self._cols(s, self.network.dims[0], "logpdf"); a = self._cols(a, self.act_dim, "logpdf"); B = s.shape[1]
+        if a.shape[1] != B:
+            raise ValueError("logpdf: %d states and %d actions" % (B, a.shape[1]))
+        lp = np.empty((1, B), np.float32)
+        self.ctx.check(self.ctx.lib.crux_sigma_head_logpdf(self.h, _vp(s), _vp(a), B, _vp(lp), None))
+        return lp
+
+    def entropy(self, s):
+        """entropy(pi, s): 1.4189385 + sum(logSigma(s)). GaussianPolicy: the reference's scalar over EVERYTHING (policies.jl:348: `sum` without dims);
+        SquashedGaussianPolicy: [1 x B] (policies.jl:398)."""
+        self._need_two("entropy"); s = self._cols(s, self.network.dims[0], "entropy"); B = s.shape[1]
+        sl = np.empty((1, B), np.float32)
+        self.ctx.check(self.ctx.lib.crux_sigma_head_logpdf(self.h, _vp(s), None, B, None, _vp(sl)))
+        return np.float32(1.4189385332046727) + (sl if self.ascale_or_zero > 0 else np.float32(sl.sum(dtype=np.float32)))
 
 
 
@@ -396,7 +493,7 @@ class SquashedGaussianPolicy(GaussianPolicy):
     (examples/rl/pendulum.jl:20, half_cheetah_mujoco.jl:42). Greedy action = ascale*tanh(mu(s)) (:372)."""
 
     def __init__(self, mu_chain, logSigma, ascale=1.0, **kw):
-        super().__init__(mu_chain, logSigma, **kw)
+        super().__init__(mu_chain, logSigma, **kw)      # (logSigma a Chain on mu's trunk: the two-headed form, see GaussianPolicy)
         self.ascale = float(np.float32(ascale))
         self.ctx.check(self.ctx.lib.crux_mlp_set_squash(self.h, self.ascale))
 
@@ -473,6 +570,16 @@ def refuse_standalone(pi, who):
             raise NotImplementedError("%s: %s" % (who, why))
 
 
+def refuse_two_headed(pi, who):
+    """Two-headed Gaussian actors (logSigma a network on mu's trunk) are taken by SAC / BatchSAC and the Sampler only: the on-policy learner kernels, BC, CQL's sampled-action
+    terms and the mixture head read constant logSigma extras, and the off-policy imitation learners (SQIL, OffPolicyGAIL, AdRIL) are not covered by tests with such an actor.
+    Raised at construction, by name, before any device call."""
+    for q in ([] if pi is None else _leaves(pi)):
+        if getattr(q, "two_headed", False):
+            raise NotImplementedError("%s: a %s whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only; "
+                                      "this learner needs the constant-logSigma form" % (who, type(q).__name__))
+
+
 def polyak_average_(to, frm, tau=1.0):
     """polyak_average!(to, from, tau) (src/policies.jl:48-59) over every layer of the (possibly composite) policy."""
     for t, f in zip(_leaves(to), _leaves(frm)):
@@ -492,7 +599,10 @@ def clone_policy(pi):
         return ActorCritic(clone_policy(pi.A), clone_policy(pi.C))
     if isinstance(pi, DoubleNetwork):
         return DoubleNetwork(clone_policy(pi.N1), clone_policy(pi.N2))
-    if isinstance(pi, SquashedGaussianPolicy):
+    if getattr(pi, "two_headed", False):
+        new = (SquashedGaussianPolicy(pi.mu_chain, pi.logSigma_chain, pi.ascale, ctx=pi.ctx) if isinstance(pi, SquashedGaussianPolicy)
+               else GaussianPolicy(pi.mu_chain, pi.logSigma_chain, ctx=pi.ctx))
+    elif isinstance(pi, SquashedGaussianPolicy):
         new = SquashedGaussianPolicy(pi.network, np.zeros(pi.n_extra, np.float32), pi.ascale, ctx=pi.ctx)
     elif isinstance(pi, GaussianPolicy):
         new = GaussianPolicy(pi.network, np.zeros(pi.n_extra, np.float32), ctx=pi.ctx)
@@ -516,7 +626,7 @@ class PolicyParams:
             refuse_spectral(q, "PolicyParams")
         self.pa = pa                                   # nominal action policy (policies.jl:17): the reference distribution of :importance_weight (sampler.jl:108-111)
         a = actor(pi)
-        self.space = space or (DiscreteSpace(len(a.outputs), a.outputs) if isinstance(a, DiscreteNetwork) else ContinuousSpace(a.network.dims[-1]))
+        self.space = space or (DiscreteSpace(len(a.outputs), a.outputs) if isinstance(a, DiscreteNetwork) else ContinuousSpace(getattr(a, "act_dim", None) or a.network.dims[-1]))
 
 
 class Adam:
@@ -1031,7 +1141,7 @@ def steps_(sampler, buffer=None, Nsteps=1, explore=False, i=0, reset=False, cb=N
 def policy_explore(pi, cfg, svec, seed, steps_taken):
     """crux_policy_explore (cruxhip.h): `a, logprob = exploration(pi_explore, svec; pi_on, i)` / `(action(pi, svec), NaN)` (src/sampler.jl:73) for the columns of svec at once.
     Returns (actions [act_dim x E] Bool one-hot or Float32, logprob [E])."""
-    svec = np.asfortranarray(svec, np.float32); E = svec.shape[1]; nout = pi.network.dims[-1]
+    svec = np.asfortranarray(svec, np.float32); E = svec.shape[1]; nout = getattr(pi, "act_dim", None) or pi.network.dims[-1]
     disc = cfg.head in (L.HEAD["categorical"], L.HEAD["greedy_q"])
     a = np.zeros((nout, E), np.bool_ if disc else np.float32, order="F"); lp = np.empty(E, np.float32)
     st = np.ascontiguousarray(steps_taken, np.int64)

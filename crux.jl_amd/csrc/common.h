@@ -159,6 +159,7 @@ struct crux_mlp {
   double eta = 0, b1 = 0, b2 = 0, eps = 0;
   bool has_adam = false;
   float squash = 0.f;   // > 0: SquashedGaussianPolicy with this ascale (policies.jl:353-400) wherever the Gaussian head is used
+  bool sigma_head = false;   // two-headed Gaussian actor (crux_mlp_set_sigma_head): output rows [0, ad) are mu, [ad, 2 ad) logSigma(s); n_extra == 0
   float* ws = nullptr;  // dense-engine workspace (dense.hip): cached activations 1..L + two delta buffers, capacity ws_B samples
   int64_t ws_B = 0;
   crux_sn* sn = nullptr;   // NULL: a plain Chain(Dense...), every path as without DenseSN

@@ -188,6 +188,8 @@ static int32_t cql_backward(crux_mlp* n, const float* sa, int64_t NB, const floa
 struct CqlBufs : StepSmall { float* sa; float* lp; float* dy1; float* dy2; float* part; };
 static int32_t cql_check(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
+  // check_sac takes a two-headed actor (crux_mlp_set_sigma_head) for the SAC entries; k_cql_expand reads a constant logSigma from the extras and [ad x B] means, so not here
+  if (actor && actor->sigma_head) return crux_fail(c, CRUX_EUNSUP, "%s: CQL's sampled-action terms are not implemented for a two-headed actor (logSigma network); use a constant logSigma", who);
   int32_t rc = check_sac(c, actor, q1, q2, la, b, who); if (rc) return rc;
   if (n_samples < 1 || n_samples > 1024) return crux_fail(c, CRUX_EINVAL, "%s: CQL_n_action_samples = %d out of range [1, 1024]", who, n_samples);
   if (!(hi > lo)) return crux_fail(c, CRUX_EINVAL, "%s: the IS box needs lo < hi (got %g, %g)", who, (double)lo, (double)hi);

@@ -74,6 +74,18 @@ __global__ __launch_bounds__(256) void k_rollout_wide(RolloutArgs a) {
   __shared__ float sh_misc[ENV_MAXOBS + 8];
   rollout_generic_wave<256>(a, blockIdx.x, threadIdx.x, hbuf, sh_misc);
 }
+// the two generic kernels for a two-headed Gaussian policy handle (crux_mlp_set_sigma_head): the same body with rollout_head_sigma as its head. Kernels of their own, so that
+// k_rollout and k_rollout_wide keep their code and registers
+__global__ __launch_bounds__(64) void k_rollout_sigma(RolloutArgs a) {
+  __shared__ float hbuf[2][1024];
+  __shared__ float sh_misc[ENV_MAXOBS + 8];
+  rollout_generic_wave<64, true>(a, blockIdx.x, threadIdx.x, hbuf, sh_misc);
+}
+__global__ __launch_bounds__(256) void k_rollout_wide_sigma(RolloutArgs a) {
+  __shared__ float hbuf[2][1024];
+  __shared__ float sh_misc[ENV_MAXOBS + 8];
+  rollout_generic_wave<256, true>(a, blockIdx.x, threadIdx.x, hbuf, sh_misc);
+}
 
 // ---- register-resident WIDE policy: IN -> H -> H -> OUT with H = 256 or 128 (the off-policy configurations C3 / C4: 8->256->256->4, 3->256->256->1) -------------------------
 // One workgroup of 256 threads (one wave per SIMD: up to 512 registers per thread) per environment. Thread o keeps row o of W1 and of W2 -- H weights of the second layer -- in
@@ -258,6 +270,7 @@ __global__ __launch_bounds__(NT) void k_explore_generic(RolloutArgs a) {
   if (NT == 64) { RO_WAVE_SYNC(); } else { __syncthreads(); }
   const int cur = rollout_generic_forward<NT>(a, lane, hbuf);
   if (lane == 0) { float aout[ENV_MAXOBS]; int ai; float logprob;
+    if (a.sigma_head) rollout_head_sigma(a, hbuf[cur], a.ad, e, (uint64_t)a.steps_taken[e], aout, ai, logprob); else
     rollout_head(a, hbuf[cur], a.ad, nout, e, a.cfg.i0 + (uint64_t)e, (uint64_t)a.steps_taken[e], aout, ai, logprob);
     explore_store(a, e, a.ad, aout, logprob); }
 }
@@ -389,13 +402,19 @@ int32_t crux_rollout(crux_env* e, crux_mlp* policy, const crux_rollout_cfg* cfg,
   const int nout = policy->nd.dims[policy->nd.L];
   if ((cfg->head == CRUX_HEAD_CATEGORICAL || cfg->head == CRUX_HEAD_GREEDY_Q) && (nout != e->act_dim || buf->act_kind != CRUX_ACTION_DISCRETE))
     return crux_fail(c, CRUX_EINVAL, "steps!: discrete head needs %d logits and a one-hot action column", e->act_dim);
-  if ((cfg->head == CRUX_HEAD_GAUSSIAN || cfg->head == CRUX_HEAD_DETERMINISTIC) && (nout != e->act_dim || buf->act_kind != CRUX_ACTION_CONTINUOUS))
+  const bool two = policy->sigma_head;      // two-headed Gaussian handle: 2 act_dim outputs [mu; logSigma], no extras; the generic kernels only
+  if (two && ((cfg->head != CRUX_HEAD_GAUSSIAN && cfg->head != CRUX_HEAD_DETERMINISTIC) || nout != 2 * e->act_dim || policy->nd.n_extra != 0 || buf->act_kind != CRUX_ACTION_CONTINUOUS))
+    return crux_fail(c, CRUX_EINVAL, "steps!: a two-headed Gaussian policy needs a continuous head, 2 x %d outputs, no extras and a Float32 action column", e->act_dim);
+  if (!two && (cfg->head == CRUX_HEAD_GAUSSIAN || cfg->head == CRUX_HEAD_DETERMINISTIC) && (nout != e->act_dim || buf->act_kind != CRUX_ACTION_CONTINUOUS))
     return crux_fail(c, CRUX_EINVAL, "steps!: continuous head needs %d outputs and a Float32 action column", e->act_dim);
-  if (cfg->head == CRUX_HEAD_GAUSSIAN && policy->nd.n_extra != e->act_dim) return crux_fail(c, CRUX_EINVAL, "steps!: GaussianPolicy needs %d logSigma extras", e->act_dim);
+  if (!two && cfg->head == CRUX_HEAD_GAUSSIAN && policy->nd.n_extra != e->act_dim) return crux_fail(c, CRUX_EINVAL, "steps!: GaussianPolicy needs %d logSigma extras", e->act_dim);
   RolloutArgs a; fill_rollout_args(a, e, policy, cfg, buf, T);
   crux_prof_begin(c, CRUX_PROF_ROLLOUT);
   const NetDesc& pn = policy->nd;
   bool push_done = false; int pt_touch = 0;
+  if (two) {      // never a register-resident form (a 3-64-64-2 Pendulum actor has an instantiated shape by its dims)
+    if (policy->nd.maxdim >= 128) hipLaunchKernelGGL(k_rollout_wide_sigma, dim3(e->n_envs), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_rollout_sigma, dim3(e->n_envs), dim3(64), 0, c->stream, a); } else
   if (is_h64(pn) && !crux_sw().force_generic && launch_rollout_h64(pn, e->kind, dim3(e->n_envs), c->stream, a, nullptr)) {} else
   // wide two-hidden-layer policies (C3 / C4): the register-resident kernel when the launch is long enough to pay for loading W2 into registers (a step costs 8 round trips
   // streamed; the load costs 8 once) -- always, from two steps on
@@ -433,11 +452,12 @@ int32_t crux_policy_explore(crux_mlp* policy, const crux_rollout_cfg* cfg, int32
   if (!policy || !cfg || !obs || !actions_out || n_envs < 1) return CRUX_EINVAL;
   crux_ctx* c = policy->ctx; const NetDesc& pn = policy->nd;
   if (pn.L < 1) return crux_fail(c, CRUX_EINVAL, "policy_explore: the policy has no layers");
-  const int od = pn.dims[0], nout = pn.dims[pn.L];
+  const bool two = policy->sigma_head; const int od = pn.dims[0], nout = two ? pn.dims[pn.L] / 2 : pn.dims[pn.L];      // (two-headed: nout = act_dim, the rows of an action)
   if (od > ENV_MAXOBS || nout > ENV_MAXOBS) return crux_fail(c, CRUX_EUNSUP, "policy_explore: observation / action widths (%d, %d) above %d", od, nout, ENV_MAXOBS);
   if (pn.maxdim > 1024) return crux_fail(c, CRUX_EUNSUP, "policy_explore: layer width %d > 1024", pn.maxdim);
   if (cfg->head < CRUX_HEAD_CATEGORICAL || cfg->head > CRUX_HEAD_DETERMINISTIC) return crux_fail(c, CRUX_EINVAL, "policy_explore: head %d", cfg->head);
-  if (cfg->head == CRUX_HEAD_GAUSSIAN && pn.n_extra != nout) return crux_fail(c, CRUX_EINVAL, "policy_explore: GaussianPolicy needs %d logSigma extras", nout);
+  if (two && ((cfg->head != CRUX_HEAD_GAUSSIAN && cfg->head != CRUX_HEAD_DETERMINISTIC) || pn.n_extra != 0)) return crux_fail(c, CRUX_EINVAL, "policy_explore: a two-headed Gaussian policy needs a continuous head and no extras");
+  if (!two && cfg->head == CRUX_HEAD_GAUSSIAN && pn.n_extra != nout) return crux_fail(c, CRUX_EINVAL, "policy_explore: GaussianPolicy needs %d logSigma extras", nout);
   const bool disc = cfg->head == CRUX_HEAD_CATEGORICAL || cfg->head == CRUX_HEAD_GREEDY_Q;
   const size_t E = (size_t)n_envs, b_obs = (4 * E * od + 255) / 256 * 256, b_st = (8 * E + 255) / 256 * 256, b_act = (E * nout * (disc ? 1 : 4) + 255) / 256 * 256, b_lp = (4 * E + 255) / 256 * 256;
   // ONE launch per call: observations, step counters, actions and log-probabilities live in a pinned, device-mapped block of the context -- the kernel
@@ -448,14 +468,14 @@ int32_t crux_policy_explore(crux_mlp* policy, const crux_rollout_cfg* cfg, int32
   char* sc = zc ? (char*)c->pinned_mapped_dev : (char*)crux_scratch(c, b_obs + b_st + b_act + b_lp); if (!sc) return crux_fail(c, CRUX_ENOMEM, "policy_explore: scratch");
   RolloutArgs a = RolloutArgs{};
   a.nd = pn; a.p = policy->p; a.E = n_envs; a.od = od; a.ad = nout; a.act_kind = disc ? CRUX_ACTION_DISCRETE : CRUX_ACTION_CONTINUOUS; a.seed = seed;
-  a.svec = (float*)sc; a.steps_taken = (int64_t*)(sc + b_obs); a.A = sc + b_obs + b_st; a.LP = (float*)(sc + b_obs + b_st + b_act); a.cfg = *cfg; a.squash = policy->squash;
+  a.svec = (float*)sc; a.steps_taken = (int64_t*)(sc + b_obs); a.A = sc + b_obs + b_st; a.LP = (float*)(sc + b_obs + b_st + b_act); a.cfg = *cfg; a.squash = policy->squash; a.sigma_head = two ? 1 : 0;
   if (zc) { memcpy(hs, obs, 4 * E * od);
     if (steps_taken) memcpy(hs + b_obs, steps_taken, 8 * E); else memset(hs + b_obs, 0, 8 * E); }
   else { HIPCHK(c, hipMemcpyAsync(a.svec, obs, 4 * E * od, hipMemcpyHostToDevice, c->stream));
     if (steps_taken) HIPCHK(c, hipMemcpyAsync(a.steps_taken, steps_taken, 8 * E, hipMemcpyHostToDevice, c->stream));
     else HIPCHK(c, hipMemsetAsync(a.steps_taken, 0, 8 * E, c->stream)); }
   // the arithmetic of the rollout kernel that serves this policy shape (crux_rollout: the register-resident form for the instantiated IN-64-64-OUT shapes, else the generic one)
-  const bool h64 = is_h64(pn) && !crux_sw().force_generic;
+  const bool h64 = is_h64(pn) && !two && !crux_sw().force_generic;      // (a 3-64-64-2 two-headed Pendulum actor has an instantiated shape: never the register-resident form)
 #define EX_CASE(I, O, A_, K) if (h64 && od == I && nout == O && pn.acts[0] == A_) hipLaunchKernelGGL((k_explore_h64<I, O, A_>), dim3(n_envs), dim3(64), 0, c->stream, a); else
   H64_SHAPES(EX_CASE)
 #undef EX_CASE
@@ -508,7 +528,7 @@ int32_t crux_rollout_multi(int32_t n, crux_env* const* envs, crux_mlp* const* po
   if (n < 1 || !envs || !policies || !cfg || !bufs || T < 1) return CRUX_EINVAL;
   for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_rollout_multi", policies[i]);
   crux_ctx* c = envs[0]->ctx; crux_env* e0 = envs[0]; const NetDesc& pn = policies[0]->nd;
-  if (!is_h64(pn)) return crux_fail(c, CRUX_EUNSUP, "steps! (multi): only the 64-wide register-resident rollout kernel is batched");
+  if (!is_h64(pn) || policies[0]->sigma_head) return crux_fail(c, CRUX_EUNSUP, "steps! (multi): only the 64-wide register-resident rollout kernel is batched");
   std::vector<RolloutArgs> as((size_t)n);
   for (int i = 0; i < n; ++i) {
     crux_env* e = envs[i]; crux_buffer* b = bufs[i]; crux_mlp* p = policies[i];

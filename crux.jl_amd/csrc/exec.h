@@ -37,7 +37,8 @@
   X(OP_ACTOR_EXPLORE_TILE, ActorExploreTileOp, 0) X(OP_SAC_CRITIC_TILE, SacCriticTileOp, 0) X(OP_CRITIC_INFO2, CriticInfo2Op, 0) X(OP_SAC_ACTOR_TILE, SacActorTileOp, 0) \
   X(OP_ACTOR_INFO2, ActorInfo2Op, 0) X(OP_CRITIC_DX_TILE, CriticDxActorGradTileOp, 0) X(OP_DQN_TD_TILE, DqnTdTileOp, 0) X(OP_TD_INFO2, TdInfo2Op, 0)     /* sac_fused.h (round 4) */ \
   X(OP_LEAF_TOUCH, LeafTouchOp, 0)                                     /* per.hip: leaf re-sum + root paths in one launch (round 4) */ \
-  X(OP_ADAM_SELF, AdamSelfOp, 0) X(OP_ADAM_ADVANCE_SELF, AdamAdvanceSelfOp, 0)      /* sac.hip: Adam gated on the producers' NaN flags, in the phase of the norm (round 4) */
+  X(OP_ADAM_SELF, AdamSelfOp, 0) X(OP_ADAM_ADVANCE_SELF, AdamAdvanceSelfOp, 0)      /* sac.hip: Adam gated on the producers' NaN flags, in the phase of the norm (round 4) */ \
+  X(OP_SIGMA_EXPLORE, SigmaExploreOp, 0) X(OP_SIGMA_ACTOR_GRAD, SigmaActorGradOp, 0)      /* sac.hip: two-headed Gaussian actors; they take OP_GAUSS_EXPLORE's / OP_ACTOR_GRAD's phases */
 
 #define EXEC_OP_ENUM(id, ...) id,
 enum { OP_NONE = 0 /* an unused slot of a phase record */, CRUX_EXEC_OPS(EXEC_OP_ENUM, EXEC_OP_ENUM) };

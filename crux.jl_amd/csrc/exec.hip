@@ -655,7 +655,8 @@ bool SacRun::tile_case(int32_t uc, int32_t ua) const {
   const int64_t B = batch->capacity; crux_mlp* all[5] = {actor, q1, q2, q1t, q2t};
   for (crux_mlp* n : all) { if (n->nd.L != 3 || !crux_dense_fwd_fused(n) || n->nd.acts[2] != CRUX_ACT_IDENTITY || n->nd.dims[2] != actor->nd.dims[2]) return false; }
   if (!crux_dense_bwd_fused3(actor, B) || !crux_dense_bwd_fused3(q1, B) || !crux_dense_bwd_fused3(q2, B)) return false;
-  if (batch->act_dim > 4 || batch->obs_dim + batch->act_dim > 16 || actor->nd.dims[3] != batch->act_dim || q1->nd.dims[3] != 1 || q2->nd.dims[3] != 1) return false;
+  // (a two-headed actor stays off the tile plan, whose ops read constant logSigma extras: its 2 act_dim output rows already fail dims[3] == act_dim, and the flag says so by name)
+  if (actor->sigma_head || batch->act_dim > 4 || batch->obs_dim + batch->act_dim > 16 || actor->nd.dims[3] != batch->act_dim || q1->nd.dims[3] != 1 || q2->nd.dims[3] != 1) return false;
   if (q1t->nd.dims[3] != 1 || q2t->nd.dims[3] != 1 || q1->nd.dims[0] != batch->obs_dim + batch->act_dim) return false;
   return true;
 }
@@ -779,6 +780,9 @@ int32_t SacRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample
   // The order inside every chain is the reference's (temperature before critic before actor: each sees the parameters the previous step left).
   // The temperature chain (X .. X + 3) is independent of the sequential group at X (ActorCriticPlan: the constants and the rules shared with DDPG / TD3).
   const ActorCriticPlan P(actor, q1, B, update_critic); const NetPlan& pa = P.pa; const int FA = P.FA, FQ = P.FQ, BA = P.BA, DQ = P.DQ, X = P.X, Y = P.Y;
+  // a two-headed actor (crux_mlp_set_sigma_head) records SigmaExploreOp / SigmaActorGradOp where GaussExploreOp / ActorGradOp stand, in their phases; nothing takes
+  // RowsumOp's place (the seed [dmu; dlogSigma] goes straight into the actor's pullback)
+  const int EXPL = actor->sigma_head ? OP_SIGMA_EXPLORE : OP_GAUSS_EXPLORE, AGRAD = actor->sigma_head ? OP_SIGMA_ACTOR_GRAD : OP_ACTOR_GRAD;
   EpochTags tg(c, fuse, "sac_epoch", 3, 3);
   if (!P.ok(q2, q1_targ, q2_targ) || net_plan(q2, B).one != P.pq.one) tg.plan_ok = false;       // (the early actor forward needs X + 1 + FA < Y)
   // chained epochs: phases 0 (ids) and 1 (gather, fills) of a later epoch run beside the previous epoch's actor norm and info + Adam (neither reads the batch), and its
@@ -787,10 +791,10 @@ int32_t SacRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample
   rc = crux_uniform_sample(batch, source, B, nullptr, sample_counter); if (rc) return bail(rc);
   tg.tag([&](int kid, int&) { return P.sampling(kid); });
   rc = crux_sac_target(actor, q1_targ, q2_targ, log_alpha, batch, gamma, noise_seed, noise_counter, d_y); if (rc) return bail(rc);
-  tg.tag([&](int kid, int& g) { return P.target(kid, g, OP_GAUSS_EXPLORE, OP_SAC_TARGET); });
+  tg.tag([&](int kid, int& g) { return P.target(kid, g, EXPL, OP_SAC_TARGET); });
   rc = crux_sac_temp_step(actor, log_alpha, batch, H_target, noise_seed, noise_counter + 1, info_temp); if (rc) return bail(rc);
   tg.tag([&](int kid, int& g) { if (kid == OP_FILL) return 1; if (is_mm(kid)) { const int k = g++; return k < FA ? 3 + FA + k : -1; }
-    return kid == OP_GAUSS_EXPLORE ? X : kid == OP_TEMP_HEAD ? X + 1 : kid == OP_ADAM_GATED ? X + 2 : kid == OP_ADAM_ADVANCE ? X + 3 : -1; });
+    return kid == EXPL ? X : kid == OP_TEMP_HEAD ? X + 1 : kid == OP_ADAM_GATED ? X + 2 : kid == OP_ADAM_ADVANCE ? X + 3 : -1; });
   if (update_critic) {
     rc = crux_double_q_step(q1, q2, batch, d_y, use_weight, info_critic); if (rc) return bail(rc);
     tg.tag([&](int kid, int& g) { return P.critic(kid, g); });
@@ -803,7 +807,7 @@ int32_t SacRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample
       // phases (X + 1 ..), after the temperature step's last read of the actor's activations (its exploration at X)
       if (is_mm(kid)) { const int k = g++; if (k < FA) return X + 1 + k; if (k < FA + 2 * FQ) return Y + (k - FA) % FQ;
         if (k < FA + 2 * FQ + 2 * DQ) return Y + 1 + FQ + (k - FA - 2 * FQ) % DQ; return Y + 2 + FQ + DQ + pa.stage(k - FA - 2 * FQ - 2 * DQ); }
-      return kid == OP_GAUSS_EXPLORE ? X + 1 + FA : kid == OP_ACTOR_HEAD ? Y + FQ : kid == OP_ACTOR_GRAD ? Y + 1 + FQ + DQ : kid == OP_ROWSUM ? Y + 2 + FQ + DQ :
+      return kid == EXPL ? X + 1 + FA : kid == OP_ACTOR_HEAD ? Y + FQ : kid == AGRAD ? Y + 1 + FQ + DQ : kid == OP_ROWSUM ? Y + 2 + FQ + DQ :
              kid == OP_SUMSQ2 ? Y + BA + 2 + FQ + DQ : (kid == OP_ACTOR_INFO || kid == OP_ADAM_GATED) ? Y + BA + 3 + FQ + DQ : kid == OP_ADAM_ADVANCE ? Y + BA + 4 + FQ + DQ : -1; });
     if (actor_targ) { rc = crux_polyak(actor_targ, actor, tau); if (rc) return bail(rc); }
     rc = crux_polyak(q1_targ, q1, tau); if (rc) return bail(rc);

@@ -284,6 +284,17 @@ int32_t crux_mlp_set_squash(crux_mlp* n, float ascale) {
 }
 float crux_mlp_get_squash(const crux_mlp* n) { return n ? n->squash : 0.f; }
 
+// GaussianPolicy / SquashedGaussianPolicy whose logSigma is a network sharing mu's trunk (policies.jl:316-320, 355-360): one Chain with 2 ad output rows
+int32_t crux_mlp_set_sigma_head(crux_mlp* n, int32_t on) {
+  if (!n) return CRUX_EINVAL;
+  CRUX_PLAIN_ONLY("crux_mlp_set_sigma_head", n);
+  if (on && (n->nd.L < 1 || n->nd.n_extra != 0 || (n->nd.dims[n->nd.L] & 1)))
+    return crux_fail(n->ctx, CRUX_EINVAL, "set_sigma_head: needs a Chain with an even last width (2 x act_dim: mu rows, then logSigma rows) and no trailing extras (last width %d, %d extras)",
+                     n->nd.L < 1 ? 0 : n->nd.dims[n->nd.L], n->nd.n_extra);
+  n->sigma_head = on != 0; return CRUX_OK;
+}
+int32_t crux_mlp_get_sigma_head(const crux_mlp* n) { return n && n->sigma_head ? 1 : 0; }
+
 int32_t crux_adam_state_ptrs(crux_mlp* n, float** d_m, float** d_v) { if (!n) return CRUX_EINVAL; if (d_m) *d_m = n->m; if (d_v) *d_v = n->v; return CRUX_OK; }
 
 int32_t crux_adam_apply(crux_mlp* n, float grad_scale) {

@@ -140,6 +140,7 @@ struct RolloutArgs {
   int64_t base, C, T;
   crux_rollout_cfg cfg;
   float squash;      // SquashedGaussianPolicy ascale, 0 = GaussianPolicy
+  int32_t sigma_head;      // two-headed policy handle (crux_mlp_set_sigma_head): z holds 2 ad rows, [mu; logSigma]. Read by k_explore_generic only (the rollout side is dispatched by the host: k_rollout_sigma / k_rollout_wide_sigma). (Sits in what was padding: the struct keeps its size)
   // push!'s priority bookkeeping finished by the rollout launch itself (k_rollout_res with one environment; per_tree.h: push_touch_block); pt_pr == NULL: not asked for
   int64_t* pt_ids; float* pt_pr; float* pt_pminmax; float* pt_run; float* pt_total; float pt_alpha; int32_t pt_nlev, pt_touch; int64_t pt_N;
 };
@@ -202,8 +203,35 @@ __device__ __forceinline__ void rollout_head(const RolloutArgs& a, const float* 
       }
       if (a.cfg.explore == 2) logprob = NAN;      // action(pi, s) of an always_stochastic policy: exploration(pi, s)[1] with logprob NaN (policies.jl:124, sampler.jl:73)
 }
+// The head of a two-headed Gaussian policy handle (z = [mu; logSigma(s)], 2 ad rows; policies.jl:338-344, 372-394, 510-513), instantiated by the generic kernels only
+// (k_rollout_sigma, k_rollout_wide_sigma -- k_rollout's and k_rollout_wide's body with this head --, k_explore_generic): the register-resident kernels never see such a handle and keep rollout_head's code as it was.
+//   CRUX_HEAD_GAUSSIAN       exploration(pi, s): rollout_head's normals and operation order, logSigma read from z[ad + q]; squashed: its clamp and tanh correction
+//   CRUX_HEAD_DETERMINISTIC  action(pi_on, s) = mu, ascale tanh(mu) when squashed (policies.jl:372), THEN the Gaussian noise and its clamps (:510-513)
+__device__ __forceinline__ void rollout_head_sigma(const RolloutArgs& a, const float* z, const int ad, const int e, const uint64_t ctr, float* aout, int& ai, float& logprob) {
+      logprob = NAN; ai = 0;
+      if (a.cfg.head == CRUX_HEAD_GAUSSIAN) { float lp = 0.f;
+        for (int q = 0; q < ad; ++q) { const float mu = z[q], ls = z[ad + q];
+          if (!a.cfg.explore) { aout[q] = a.squash > 0.f ? __fmul_rn(a.squash, tanhf(mu)) : mu; continue; }
+          const float sg = expf(a.squash > 0.f ? sq_clampls(ls) : ls);
+          const float epsn = randn_f32(a.seed, ctr * (uint64_t)((ad + 1) / 2) + (uint64_t)(q / 2), (uint32_t)e, q & 1);
+          const float u = __fadd_rn(__fmul_rn(epsn, sg), mu); const float s2 = __fmul_rn(sg, sg); const float dd = __fsub_rn(u, mu);
+          float t = __fsub_rn(__fsub_rn(__fdiv_rn(-__fmul_rn(dd, dd), __fmul_rn(2.f, s2)), 0.9189385332046727f), ls);
+          if (a.squash > 0.f) { t = __fsub_rn(t, sq_corr(u)); aout[q] = __fmul_rn(a.squash, tanhf(u)); } else aout[q] = u;
+          lp = __fadd_rn(lp, t); }
+        logprob = a.cfg.explore ? lp : NAN;
+      } else {
+        for (int q = 0; q < ad; ++q) { float av = a.squash > 0.f ? __fmul_rn(a.squash, tanhf(z[q])) : z[q];
+          if (a.cfg.explore && a.cfg.noise_sigma >= 0.f) {
+            float n0 = __fmul_rn(randn_f32(a.seed, ctr * (uint64_t)((ad + 1) / 2) + (uint64_t)(q / 2), (uint32_t)e, q & 1), a.cfg.noise_sigma);
+            n0 = n0 < a.cfg.noise_eps_min ? a.cfg.noise_eps_min : n0 > a.cfg.noise_eps_max ? a.cfg.noise_eps_max : n0; av = __fadd_rn(av, n0);
+            av = av < a.cfg.a_min ? a.cfg.a_min : av > a.cfg.a_max ? a.cfg.a_max : av; }
+          aout[q] = av; }
+      }
+      if (a.cfg.explore == 2) logprob = NAN;
+}
 // Everything of step! after the policy forward (sampler.jl:73-136): action + logprob from the head, env transition, column writes,
 // episode bookkeeping. `writer` lanes store to the buffer; all callers advance identical copies of the sampler state.
+template <bool SIGMA = false>      // SIGMA: the two-headed head (generic kernels only)
 __device__ __forceinline__ void rollout_tail(const RolloutArgs& a, const float* z, const int od, const int ad, const int nout, const int kind, const int e,
                                              const int64_t t, const int64_t j, const bool writer, double* st, int64_t& ep_len, int64_t& n_resets,
                                              int64_t& steps_taken, double& sum_r, int64_t& nee, float* next_obs, const int par_lane = -1,
@@ -213,6 +241,7 @@ __device__ __forceinline__ void rollout_tail(const RolloutArgs& a, const float* 
       const uint64_t gi = a.cfg.i0 + (uint64_t)t * (uint64_t)a.E + (uint64_t)e;    // i + (j-1), env-minor (sampler.jl:161-163)
       const uint64_t ctr = (uint64_t)steps_taken;
       float logprob; int ai; float aout[ENV_MAXOBS];
+      if constexpr (SIGMA) rollout_head_sigma(a, z, ad, e, ctr, aout, ai, logprob); else
       rollout_head(a, z, ad, nout, e, gi, ctr, aout, ai, logprob);
       // ---- env transition (sampler.jl:93-97)
       double sn[ENV_MAXSD]; float r; uint8_t done; float o[ENV_MAXOBS], spv[ENV_MAXOBS];
@@ -330,7 +359,7 @@ __device__ __forceinline__ int rollout_generic_forward(const RolloutArgs& a, con
     }
     return cur;
 }
-template <int NT = 64>
+template <int NT = 64, bool HEADS2 = false>      // HEADS2: the instantiations for two-headed policy handles (k_rollout_sigma, k_rollout_wide_sigma); every other one is as it was
 __device__ __forceinline__ void rollout_generic_wave(const RolloutArgs& a, const int e, const int lane, float (*hbuf)[1024], float* sh_misc) {
 #define RO_SYNC() do { if (NT == 64) { RO_WAVE_SYNC(); } else { __syncthreads(); } } while (0)
   const NetDesc& nd = a.nd;
@@ -353,6 +382,10 @@ __device__ __forceinline__ void rollout_generic_wave(const RolloutArgs& a, const
     // the tail with compile-time kind and dimensions for the restated environments (its per-step arrays are then registers; with run-time dimensions they are
     // private memory and the step costs ~3x more), the run-time form for everything else (SYNTH envs of any width)
     if (lane == 0) {
+      if constexpr (HEADS2) {      // (nout = 2 ad here; Pendulum, the SAC examples' environment, gets its compile-time tail as below)
+        if (a.kind == CRUX_ENV_PENDULUM && od == 3 && ad == 1 && nout == 2) rollout_tail<true>(a, hbuf[cur], 3, 1, 2, CRUX_ENV_PENDULUM, e, t, j, true, st, ep_len, n_resets, steps_taken, sum_r, nee, sh_misc);
+        else rollout_tail<true>(a, hbuf[cur], od, ad, nout, a.kind, e, t, j, true, st, ep_len, n_resets, steps_taken, sum_r, nee, sh_misc);
+      } else
       if (a.kind == CRUX_ENV_CARTPOLE && od == 4 && ad == 2 && nout == 2) rollout_tail(a, hbuf[cur], 4, 2, 2, CRUX_ENV_CARTPOLE, e, t, j, true, st, ep_len, n_resets, steps_taken, sum_r, nee, sh_misc);
       else if (a.kind == CRUX_ENV_GRIDWORLD && od == 2 && ad == 4 && nout == 4) rollout_tail(a, hbuf[cur], 2, 4, 4, CRUX_ENV_GRIDWORLD, e, t, j, true, st, ep_len, n_resets, steps_taken, sum_r, nee, sh_misc);
       else if (a.kind == CRUX_ENV_PENDULUM && od == 3 && ad == 1 && nout == 1) rollout_tail(a, hbuf[cur], 3, 1, 1, CRUX_ENV_PENDULUM, e, t, j, true, st, ep_len, n_resets, steps_taken, sum_r, nee, sh_misc);
@@ -383,7 +416,7 @@ static void fill_rollout_args(RolloutArgs& a, crux_env* e, crux_mlp* policy, con
   a.RET = has_col(buf, CRUX_COL_RETURN) ? (float*)buf->col[CRUX_COL_RETURN] : nullptr; a.ADV = has_col(buf, CRUX_COL_ADVANTAGE) ? (float*)buf->col[CRUX_COL_ADVANTAGE] : nullptr;
   a.COST = has_col(buf, CRUX_COL_COST) ? (float*)buf->col[CRUX_COL_COST] : nullptr; a.CADV = has_col(buf, CRUX_COL_COST_ADVANTAGE) ? (float*)buf->col[CRUX_COL_COST_ADVANTAGE] : nullptr;
   a.CRET = has_col(buf, CRUX_COL_COST_RETURN) ? (float*)buf->col[CRUX_COL_COST_RETURN] : nullptr;
-  a.base = buf->next_ind; a.C = buf->capacity; a.T = T; a.cfg = *cfg; a.squash = policy->squash;
+  a.base = buf->next_ind; a.C = buf->capacity; a.T = T; a.cfg = *cfg; a.squash = policy->squash; a.sigma_head = policy->sigma_head ? 1 : 0;
 }
 // the (sum of rewards, episode ends) pairs the rollout kernels leave per environment in acc [2 x E] (a host copy) -> the totals steps! reports; either output may be NULL
 static void rollout_acc_sum(const double* acc, int E, double* sum_r, int64_t* n_episode_end) {

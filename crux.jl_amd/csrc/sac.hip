@@ -191,6 +191,70 @@ struct RowsumOp { static constexpr int max_threads = 256; static __device__ __fo
   __syncthreads();
   if (threadIdx.x == 0) { const float r_ = ((red[0] + red[1]) + red[2]) + red[3]; out[d] = r_; if (nf && r_ != r_) atomicOr((int*)nf, 1); }
 } };
+// ---- two-headed Gaussian actors (crux_mlp_set_sigma_head): z = net(s) [2 ad x B], mu = z[d], logSigma = z[ad + d] (policies.jl:338-344, 374-396) --------------------------
+// exploration(pi, s) from the cached outputs, GaussExploreOp's draws (stream j ad + d) and column layout; ascale > 0: sigma = exp(clamp(l, -5, 2)), a = ascale tanh(u),
+// the tanh correction, and the -l term unclamped (policies.jl:385). uo [ad x B] (or NULL): the un-tanh'd action the reverse pass needs. a_out [ad x B] (or NULL): the action alone.
+struct SigmaExploreOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, const float* __restrict__ s, int od, int ad, int64_t B, float ascale,
+                                uint64_t seed, uint64_t counter, float* __restrict__ sa, float* __restrict__ lp, float* __restrict__ eps, float* __restrict__ uo, float* __restrict__ a_out) {
+  const int64_t j = (int64_t)bid_ * blockDim.x + threadIdx.x; if (j >= B) return;
+  const float* zj = z + j * 2 * ad; float acc = 0.f;
+  for (int d = 0; d < ad; ++d) {
+    const float m = zj[d], l = zj[ad + d]; const float sg = expf(ascale > 0.f ? sq_clampls(l) : l); const float e = sac_randn(seed, counter, (uint32_t)(j * ad + d));
+    const float u = __fadd_rn(__fmul_rn(e, sg), m); const float s2 = __fmul_rn(sg, sg), df = __fsub_rn(u, m);
+    float t = __fsub_rn(__fsub_rn(-(__fmul_rn(df, df)) / __fmul_rn(2.f, s2), 0.9189385332046727f), l);
+    if (ascale > 0.f) t = __fsub_rn(t, sq_corr(u));
+    acc = __fadd_rn(acc, t);
+    const float a = ascale > 0.f ? __fmul_rn(ascale, tanhf(u)) : u;
+    if (sa) sa[j * (od + ad) + od + d] = a;
+    if (a_out) a_out[j * ad + d] = a;
+    if (eps) eps[j * ad + d] = e;
+    if (uo) uo[j * ad + d] = u;
+  }
+  if (sa) for (int k = 0; k < od; ++k) sa[j * (od + ad) + k] = s[j * od + k];
+  if (lp) lp[j] = acc;
+} };
+// action(pi, s): mu(s), ascale tanh(mu(s)) when squashed (policies.jl:331, 372); one thread per element (launched only)
+struct SigmaActionOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, int ad, int64_t B, float ascale, float* __restrict__ a_out) {
+  const int64_t i = (int64_t)bid_ * blockDim.x + threadIdx.x; if (i >= B * ad) return;
+  const int64_t j = i / ad; const int d = (int)(i - j * ad); const float m = z[j * 2 * ad + d];
+  a_out[i] = ascale > 0.f ? __fmul_rn(ascale, tanhf(m)) : m;
+} };
+// logpdf(pi, s, a) of stored actions a [ad x B] (NULL: skipped) and the per-column sum_d logSigma(s) that entropy(pi, s) adds 1.4189385 to (launched only)
+struct SigmaLogpdfOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, const float* __restrict__ a, int ad, int64_t B, float ascale,
+                               float* __restrict__ lp, float* __restrict__ sum_ls) {
+  const int64_t j = (int64_t)bid_ * blockDim.x + threadIdx.x; if (j >= B) return;
+  const float* zj = z + j * 2 * ad; float acc = 0.f, sl = 0.f;
+  for (int d = 0; d < ad; ++d) {
+    const float m = zj[d], l = zj[ad + d]; sl = __fadd_rn(sl, l);
+    if (!a) continue;
+    const float sg = expf(ascale > 0.f ? sq_clampls(l) : l); const float u = ascale > 0.f ? sq_untanh(a[j * ad + d], ascale) : a[j * ad + d];
+    const float s2 = __fmul_rn(sg, sg), df = __fsub_rn(u, m);
+    float t = __fsub_rn(__fsub_rn(-(__fmul_rn(df, df)) / __fmul_rn(2.f, s2), 0.9189385332046727f), l);
+    if (ascale > 0.f) t = __fsub_rn(t, sq_corr(u));
+    acc = __fadd_rn(acc, t);
+  }
+  if (a && lp) lp[j] = acc;
+  if (sum_ls) sum_ls[j] = sl;
+} };
+// reverse pass of sac_actor_loss through exploration(): the output layer's seed dz [2 ad x B] = [dmu; dlogSigma] of crux_dense_backward (no row sums: logSigma is per sample).
+// c = exp(log alpha) / B; g_a = the critics' input gradient at the action rows (carries -1 / B). The clamp passes its gradient strictly inside (-5, 2) (tests/asaf_reference.py).
+struct SigmaActorGradOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const float* __restrict__ z, const float* __restrict__ uo, const float* __restrict__ eps,
+                             const float* __restrict__ dsa1, const float* __restrict__ dsa2, const float* __restrict__ log_alpha, int od, int ad, int64_t B, float ascale, float* __restrict__ dz) {
+  const int64_t i = (int64_t)bid_ * blockDim.x + threadIdx.x; if (i >= B * ad) return;
+  const int64_t j = i / ad; const int d = (int)(i - j * ad);
+  const float alpha = expf(log_alpha[0]); const float clp = alpha * (1.f / (float)B);
+  const float m = z[j * 2 * ad + d], l = z[j * 2 * ad + ad + d]; const float sg = expf(ascale > 0.f ? sq_clampls(l) : l), s2 = sg * sg, u = uo[i], df = u - m;
+  const float dq = dsa1[j * (od + ad) + od + d] + dsa2[j * (od + ad) + od + d];   // only the selected network's entry is non-zero
+  float dmu, dl;
+  if (ascale > 0.f) { const float th = tanhf(u); const float ubar = dq * ascale * (1.f - th * th) + clp * (-(df / s2) + 2.f * th);
+    dmu = clp * (df / s2) + ubar;
+    dl = ((l > -5.f && l < 2.f) ? clp * ((df * df) / s2) + ubar * (eps[i] * sg) : 0.f) - clp;
+    if (l != l) dl = l; }      // a NaN logSigma fails both comparisons: hand it on to the gate
+  else { const float abar = clp * (-(df / s2)) + dq;
+    dmu = clp * (df / s2) + abar;
+    dl = clp * ((df * df) / s2 - 1.f) + abar * (eps[i] * sg); }
+  dz[j * 2 * ad + d] = dmu; dz[j * 2 * ad + ad + d] = dl;
+} };
 struct ActorInfoOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, const double* __restrict__ st, const double* __restrict__ ssq, int64_t B, float* __restrict__ dinfo) { if (threadIdx.x != 0) return;
   ssq_finalize(ssq);
   dinfo[CRUX_INFO_LOSS] = (float)(st[0] / (double)B); dinfo[CRUX_INFO_ENTROPY] = (float)(-(st[1] / (double)B)); dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
@@ -365,11 +429,14 @@ static inline Carve small_carve(crux_ctx* c, Carve& cv, size_t bytes) {
 }
 
 static int32_t check_sac(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const char* who) {
-  if (actor && actor->squash > 0.f) return crux_fail(c, CRUX_EUNSUP, "%s: SquashedGaussianPolicy actors are implemented for the on-policy learners (PPO / A2C / REINFORCE / BC) only", who);
+  const bool two = actor && actor->sigma_head;      // logSigma(s) from the output rows (crux_mlp_set_sigma_head): plain or squashed
+  if (actor && actor->squash > 0.f && !two) return crux_fail(c, CRUX_EUNSUP, "%s: SquashedGaussianPolicy actors with a constant logSigma are implemented for the on-policy learners (PPO / A2C / REINFORCE / BC) only", who);
   const int od = b->obs_dim, ad = b->act_dim;
   if (b->elements < 1) return crux_fail(c, CRUX_EINVAL, "%s: empty batch", who);
   if (b->act_kind != CRUX_ACTION_CONTINUOUS) return crux_fail(c, CRUX_EINVAL, "%s: needs a continuous action column", who);
-  if (actor && (actor->nd.L < 1 || actor->nd.dims[0] != od || actor->nd.dims[actor->nd.L] != ad || actor->nd.n_extra != ad || ad > 64))
+  if (two && (actor->nd.L < 1 || actor->nd.dims[0] != od || actor->nd.dims[actor->nd.L] != 2 * ad || actor->nd.n_extra != 0 || ad > 64))
+    return crux_fail(c, CRUX_EINVAL, "%s: a two-headed actor must map %d -> 2 x %d (mu rows, then logSigma rows) with no extras", who, od, ad);
+  if (actor && !two && (actor->nd.L < 1 || actor->nd.dims[0] != od || actor->nd.dims[actor->nd.L] != ad || actor->nd.n_extra != ad || ad > 64))
     return crux_fail(c, CRUX_EINVAL, "%s: actor must be a GaussianPolicy handle %d -> %d with %d logSigma extras", who, od, ad, ad);
   crux_mlp* qs[2] = {q1, q2};
   for (int t = 0; t < 2; ++t) if (qs[t] && (qs[t]->nd.L < 1 || qs[t]->nd.dims[0] != od + ad || qs[t]->nd.dims[qs[t]->nd.L] != 1))
@@ -422,6 +489,8 @@ int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1t, crux_mlp* q2t, crux_mlp*
   float* sa = cv.take<float>((size_t)B * (od + ad)); float* lp = cv.take<float>((size_t)B);
   const float* SP = (const float*)b->col[CRUX_COL_SP];
   rc = crux_dense_forward(actor, SP, B, c->stream); if (rc) return rc;
+  if (actor->sigma_head) CRUX_RUN(c, SigmaExploreOp, nblk(B), 256, c->stream, (const float*)crux_dense_act(actor, actor->nd.L), SP, od, ad, B, actor->squash, seed, counter, sa, lp, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  else
   CRUX_RUN(c, GaussExploreOp, nblk(B), 256, c->stream, crux_dense_act(actor, actor->nd.L), actor->p + actor->nd.xoff, SP, od, ad, B, seed, counter, sa, lp, (float*)nullptr);
   rc = crux_dense_forward(q1t, sa, B, c->stream); if (rc) return rc;
   rc = crux_dense_forward(q2t, sa, B, c->stream); if (rc) return rc;
@@ -439,6 +508,8 @@ int32_t crux_sac_temp_step(crux_mlp* actor, crux_mlp* la, crux_buffer* b, float 
   { const int32_t rz = crux_exec_zero(c, dinfo, 256 * 5, c->stream); if (rz) return rz; }
   const float* S = (const float*)b->col[CRUX_COL_S];
   rc = crux_dense_forward(actor, S, B, c->stream); if (rc) return rc;
+  if (actor->sigma_head) CRUX_RUN(c, SigmaExploreOp, nblk(B), 256, c->stream, (const float*)crux_dense_act(actor, actor->nd.L), S, od, ad, B, actor->squash, seed, counter, (float*)nullptr, lp, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  else
   CRUX_RUN(c, GaussExploreOp, nblk(B), 256, c->stream, crux_dense_act(actor, actor->nd.L), actor->p + actor->nd.xoff, S, od, ad, B, seed, counter, (float*)nullptr, lp, (float*)nullptr);
   { const int32_t rz = crux_exec_zero(c, la->g, sizeof(float) * (size_t)la->nd.n_params, c->stream); if (rz) return rz; }
   CRUX_RUN(c, TempHeadOp, 1, 256, c->stream, lp, B, H_target, la->p, la->g, dinfo, ssq);
@@ -600,9 +671,10 @@ int32_t crux_sac_actor_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
   if (!actor || !q1 || !q2 || !la || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; int32_t rc = check_sac(c, actor, q1, q2, la, b, "sac_actor_loss"); if (rc) return rc;
   const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad;
-  Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (3 * sd + 3 * ad + 3) + 16384), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "sac_actor: scratch");
+  const bool two = actor->sigma_head;      // two-headed: eps, u and the seed [dmu; dlogSigma] = 4 ad floats per column instead of eps, dmu, dls
+  Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (3 * sd + (two ? 4 : 3) * ad + 3) + 16384), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "sac_actor: scratch");
   float* sa = cv.take<float>((size_t)B * sd); float* dsa1 = cv.take<float>((size_t)B * sd); float* dsa2 = cv.take<float>((size_t)B * sd);
-  float* eps = cv.take<float>((size_t)B * ad); float* dmu = cv.take<float>((size_t)B * ad); float* dls = cv.take<float>((size_t)B * ad);
+  float* eps = cv.take<float>((size_t)B * ad); float* dmu = cv.take<float>((size_t)B * ad * (two ? 2 : 1)); float* dls = cv.take<float>((size_t)B * ad);      // (two-headed: dmu is the seed dz, dls holds u)
   float* lp = cv.take<float>((size_t)B); float* dy1 = cv.take<float>((size_t)B); float* dy2 = cv.take<float>((size_t)B);
   Carve sv = small_carve(c, cv, 256 * 6); if (!sv.p) return crux_fail(c, CRUX_ENOMEM, "sac_actor: executor region");
   float* dinfo = sv.take<float>(CRUX_INFO_N); double* stats = sv.take<double>(2); double* ssq = sv.take<double>(2 + SUMSQ_BLOCKS); int32_t* st = sv.take<int32_t>(1);
@@ -610,20 +682,66 @@ int32_t crux_sac_actor_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
   const float* S = (const float*)b->col[CRUX_COL_S];
   rc = crux_dense_forward(actor, S, B, c->stream); if (rc) return rc;
   float* mu = crux_dense_act(actor, actor->nd.L);
+  if (two) CRUX_RUN(c, SigmaExploreOp, nblk(B), 256, c->stream, (const float*)mu, S, od, ad, B, actor->squash, seed, counter, sa, lp, eps, dls, (float*)nullptr);
+  else
   CRUX_RUN(c, GaussExploreOp, nblk(B), 256, c->stream, mu, actor->p + actor->nd.xoff, S, od, ad, B, seed, counter, sa, lp, eps);
   rc = crux_dense_forward(q1, sa, B, c->stream); if (rc) return rc;
   rc = crux_dense_forward(q2, sa, B, c->stream); if (rc) return rc;
   CRUX_RUN(c, ActorHeadOp, 1, 256, c->stream, crux_dense_act(q1, q1->nd.L), crux_dense_act(q2, q2->nd.L), lp, la->p, B, dy1, dy2, stats);
   rc = crux_dense_backward(q1, sa, B, dy1, 1.0f, false, dsa1, c->stream); if (rc) return rc;     // gradient w.r.t. vcat(s, a) only: the Q parameters are not trained here
   rc = crux_dense_backward(q2, sa, B, dy2, 1.0f, false, dsa2, c->stream); if (rc) return rc;
+  if (two) CRUX_RUN(c, SigmaActorGradOp, nblk(B * ad), 256, c->stream, (const float*)mu, (const float*)dls, (const float*)eps, (const float*)dsa1, (const float*)dsa2, (const float*)la->p, od, ad, B, actor->squash, dmu);
+  else
   CRUX_RUN(c, ActorGradOp, nblk(B * ad), 256, c->stream, sa, mu, eps, actor->p + actor->nd.xoff, dsa1, dsa2, la->p, od, ad, B, dmu, dls);
   Sumsq2Fix fx{};
   rc = crux_dense_backward(actor, S, B, dmu, 1.0f, true, nullptr, c->stream, &fx, 0); if (rc) return rc;
-  CRUX_RUN(c, RowsumOp, ad, 256, c->stream, dls, ad, B, actor->g + actor->nd.xoff, (int32_t*)nullptr);
+  if (!two) CRUX_RUN(c, RowsumOp, ad, 256, c->stream, dls, ad, B, actor->g + actor->nd.xoff, (int32_t*)nullptr);
   CRUX_RUN(c, Sumsq2Op, SUMSQ_BLOCKS, 256, c->stream, actor->g, (int64_t)actor->nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
   CRUX_RUN(c, ActorInfoOp, 1, 1, c->stream, stats, ssq, B, dinfo);
   rc = adam_gated(actor, ssq, st); if (rc) return rc;
   return finish_step(c, dinfo, st, info_out, "sac_actor_loss");
+}
+
+// exploration(pi, s) / action(pi, s) and logpdf(pi, s, a) / sum(logSigma(s)) of a two-headed handle on host columns (cruxhip.h)
+static int32_t sigma_head_check(crux_mlp* n, const char* who) {
+  if (!n->sigma_head) return crux_fail(n->ctx, CRUX_EINVAL, "%s: the handle is not two-headed (crux_mlp_set_sigma_head)", who);
+  if (crux_exec_recording(n->ctx)) return crux_fail(n->ctx, CRUX_EUNSUP, "%s: inside a recording", who);
+  return CRUX_OK;
+}
+int32_t crux_sigma_head_explore(crux_mlp* net, const float* s, int64_t B, int32_t explore, uint64_t seed, uint64_t counter, float* a_out, float* lp_out) { CRUX_PLAIN_ONLY("crux_sigma_head_explore", net);
+  if (!net || !s || !a_out || B < 0) return CRUX_EINVAL;
+  crux_ctx* c = net->ctx; int32_t rc = sigma_head_check(net, "sigma_head_explore"); if (rc) return rc;
+  if (B == 0) return CRUX_OK;
+  const int od = net->nd.dims[0], ad = net->nd.dims[net->nd.L] / 2;
+  Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (od + ad + 1) + 1024), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "sigma_head_explore: scratch");
+  float* ds = cv.take<float>((size_t)B * od); float* da = cv.take<float>((size_t)B * ad); float* dlp = cv.take<float>((size_t)B);
+  HIPCHK(c, hipMemcpyAsync(ds, s, sizeof(float) * (size_t)B * od, hipMemcpyHostToDevice, c->stream));
+  rc = crux_dense_forward(net, ds, B, c->stream); if (rc) return rc;
+  const float* z = crux_dense_act(net, net->nd.L);
+  if (explore) crux_launch<SigmaExploreOp>(nblk(B), 256, c->stream, z, (const float*)ds, od, ad, B, net->squash, seed, counter, (float*)nullptr, dlp, (float*)nullptr, (float*)nullptr, da);
+  else crux_launch<SigmaActionOp>(nblk(B * ad), 256, c->stream, z, ad, B, net->squash, da);
+  rc = crux_launch_check(c, "sigma_head_explore"); if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(a_out, da, sizeof(float) * (size_t)B * ad, hipMemcpyDeviceToHost, c->stream));
+  if (explore && lp_out) HIPCHK(c, hipMemcpyAsync(lp_out, dlp, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CRUX_OK;
+}
+int32_t crux_sigma_head_logpdf(crux_mlp* net, const float* s, const float* a, int64_t B, float* lp_out, float* sum_logsigma_out) { CRUX_PLAIN_ONLY("crux_sigma_head_logpdf", net);
+  if (!net || !s || B < 0 || (a && !lp_out)) return CRUX_EINVAL;
+  crux_ctx* c = net->ctx; int32_t rc = sigma_head_check(net, "sigma_head_logpdf"); if (rc) return rc;
+  if (B == 0) return CRUX_OK;
+  const int od = net->nd.dims[0], ad = net->nd.dims[net->nd.L] / 2;
+  Carve cv{(char*)crux_scratch(c, 4 * (size_t)B * (od + ad + 2) + 1024), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "sigma_head_logpdf: scratch");
+  float* ds = cv.take<float>((size_t)B * od); float* da = cv.take<float>((size_t)B * ad); float* dlp = cv.take<float>((size_t)B); float* dsl = cv.take<float>((size_t)B);
+  HIPCHK(c, hipMemcpyAsync(ds, s, sizeof(float) * (size_t)B * od, hipMemcpyHostToDevice, c->stream));
+  if (a) HIPCHK(c, hipMemcpyAsync(da, a, sizeof(float) * (size_t)B * ad, hipMemcpyHostToDevice, c->stream));
+  rc = crux_dense_forward(net, ds, B, c->stream); if (rc) return rc;
+  crux_launch<SigmaLogpdfOp>(nblk(B), 256, c->stream, (const float*)crux_dense_act(net, net->nd.L), a ? (const float*)da : (const float*)nullptr, ad, B, net->squash, dlp, dsl);
+  rc = crux_launch_check(c, "sigma_head_logpdf"); if (rc) return rc;
+  if (a) HIPCHK(c, hipMemcpyAsync(lp_out, dlp, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+  if (sum_logsigma_out) HIPCHK(c, hipMemcpyAsync(sum_logsigma_out, dsl, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CRUX_OK;
 }
 
 }  // extern "C"

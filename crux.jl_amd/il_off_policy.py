@@ -16,6 +16,7 @@ from . import _lib as L
 from .logging import aggregate_info
 from .core import (ContinuousNetwork, ContinuousSpace, DiscreteNetwork, DiscreteSpace, ExperienceBuffer, TrainingParams, _Loss, _ensure_opt, _vp, copy_buffer, normalize_,
                    split_batches)
+from .core import refuse_two_headed
 from .off_policy import SAC, SoftQ
 
 
@@ -142,6 +143,7 @@ def SQIL(pi, S, demo, normalize_demo=True, solver=SAC, **kw):
     demonstrations, which must carry :r, as an extra buffer at [1/2, 1/2]."""
     if not demo.haskey("r"):
         raise ValueError("SQIL requires a reward value for the demonstrations")
+    refuse_two_headed(pi, "SQIL")
     d = _demo_buffer(demo, S, _space(pi, demo), normalize_demo)
     sv = solver(pi=pi, S=S, post_sample_callback=sqil_callback, extra_buffers=[d], buffer_fractions=[0.5, 0.5], **kw)
     sv.demo = d
@@ -203,6 +205,7 @@ def OffPolicyGAIL(pi, S, demo, D, ndas=(), normalize_demo=True, solver=SAC, d_op
 
     Works with every solver whose value_training honours post_batch_callback (SAC, DDPG / TD3, DQN / SoftQ). Deviation: normalize_demo=False with NDA buffers
     is allowed and leaves them as they are; the reference assigns `false` to 𝒟_ndas[i] in that case (:44), which fails at the first rand!."""
+    refuse_two_headed(pi, "OffPolicyGAIL")
     d = dict(d_opt or {}); d.setdefault("epochs", 5); d.setdefault("name", "discriminator_")
     dp = TrainingParams(loss=None, **d)                                                                  # loss = () -> nothing (:31)
     ndas = list(ndas)
@@ -238,6 +241,7 @@ def AdRIL(pi, S, demo, dN=50, solver=SAC, normalize_demo=True, expert_frac=0.5, 
     crux_adril_relabel) instead of through post_sample_callback's host copies."""
     if not demo.haskey("r"):
         raise ValueError("AdRIL requires a reward value for the demonstrations")
+    refuse_two_headed(pi, "AdRIL")
     A = _space(pi.A if hasattr(pi, "A") else pi, demo)
     d = _demo_buffer(demo, S, A, normalize_demo)
     if buffer is None:

@@ -88,6 +88,8 @@ def ASAF(pi, S, D_demo, normalize_demo=True, dN=50, lambda_orth=1e-4, a_opt=None
         raise NotImplementedError("ASAF: the categorical head (DiscreteNetwork) is not implemented; the policy must be a GaussianPolicy or SquashedGaussianPolicy")
     if not isinstance(pi, GaussianPolicy):
         raise TypeError("ASAF: pi must be a GaussianPolicy or SquashedGaussianPolicy (logpdf and entropy are needed)")
+    if getattr(pi, "two_headed", False):
+        raise NotImplementedError("ASAF: a policy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only")
     agent = PolicyParams(pi, space=ContinuousSpace(pi.network.dims[-1]))
     demo = copy_buffer(D_demo)
     if normalize_demo:

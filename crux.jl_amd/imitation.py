@@ -330,6 +330,8 @@ def BC(pi, S, D_demo, normalize_demo=True, loss=None, validation_fraction=0.3, w
     """BC(; pi, S, D_demo, normalize_demo, loss, validation_fraction=0.3, window=100, lambda_e=1f-3, opt) (src/model_free/il/bc.jl:37-70):
     mse_action_loss for a ContinuousNetwork, logpdf_bc_loss otherwise; the demonstrations are normalised, shuffled once and split into
     training / validation parts; early stopping on the validation error. shuffle_perm: optional 1-based permutation for the initial shuffle!."""
+    if getattr(actor(pi), "two_headed", False):
+        raise NotImplementedError("BC: a policy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only")
     loss = loss or (mse_action_loss if type(pi) is ContinuousNetwork else logpdf_bc_loss)
     A = pi.space if hasattr(pi, "space") else (DiscreteSpace(len(pi.outputs), pi.outputs) if isinstance(pi, DiscreteNetwork) else ContinuousSpace(pi.network.dims[-1]))
     D = buffer_like(D_demo, capacity=len(D_demo)); D.push_({k: D_demo[k] for k in D_demo.keys()})      # deepcopy(D_demo) (:52)

@@ -42,6 +42,8 @@ class MixtureNetwork:
             if isinstance(n, DiscreteNetwork):
                 raise NotImplementedError("%s: DiscreteNetwork components (a mixture of categoricals is itself a categorical, and the reference's own test marks its action "
                                           "as broken); the device head is the Gaussian one" % name)
+            if getattr(n, "two_headed", False):
+                raise NotImplementedError("%s: components whose logSigma is a network (two-headed actors); the mixture head reads constant logSigma extras" % name)
             if isinstance(n, SquashedGaussianPolicy):
                 raise NotImplementedError("%s: SquashedGaussianPolicy components (the mixture head has no tanh correction)" % name)
             if not isinstance(n, GaussianPolicy):

@@ -504,7 +504,7 @@ def SAC(pi, S, N, dN=50, SAC_alpha=1.0, SAC_H_target=None, pi_explore=None, SAC_
     SAC_alpha_opt, a_opt, c_opt(epochs=dN), ...) (src/model_free/rl/sac.jl:75-106)."""
     if not (isinstance(pi, ActorCritic) and isinstance(pi.A, GaussianPolicy) and isinstance(pi.C, DoubleNetwork)):
         raise TypeError("SAC: pi must be ActorCritic(GaussianPolicy, DoubleNetwork(ContinuousNetwork, ContinuousNetwork))")
-    ad = pi.A.network.dims[-1]
+    ad = pi.A.act_dim if pi.A.two_headed else pi.A.network.dims[-1]      # SAC_H_target = -dim(A): the action's rows, not the two-headed output's 2 ad
     P = {"SAC_log_alpha": ParamVector([np.log(np.float32(SAC_alpha))], ctx=pi.A.ctx), "SAC_H_target": np.float32(-ad if SAC_H_target is None else SAC_H_target)}
     c = dict(c_opt or {}); c.setdefault("name", "critic_"); c.setdefault("epochs", dN)
     a = dict(a_opt or {}); a.setdefault("name", "actor_")

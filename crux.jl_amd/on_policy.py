@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
-from .core import refuse_spectral   # noqa: F401
+from .core import refuse_spectral, refuse_two_headed   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -27,6 +27,7 @@ class OnPolicySolver:
     def __init__(self, agent, S, N=1000, dN=200, max_steps=100, a_opt=None, c_opt=None, P=None, lambda_gae=0.95,
                  required_columns=(), post_batch_callback=None, post_sample_callback=None, i=0, log=None, Vc=None, cost_opt=None, param_optimizers=None, interaction_storage=None):
         self.interaction_storage = interaction_storage      # a list: every steps! block is appended to it (on_policy.jl:44,96)
+        refuse_two_headed(agent.pi, "OnPolicySolver (PPO / A2C / REINFORCE / ASAF)")
         refuse_spectral(Vc, "OnPolicySolver (Vc)")
         self.Vc, self.cost_opt = Vc, cost_opt      # cost constraints: a separate value network and its TrainingParams (on_policy.jl:50-53)
         self.param_optimizers = list(param_optimizers or [])     # [(ParamVector, TrainingParams(loss=ParamLoss(...)))]: trained before the actor (on_policy.jl:59-61)

@@ -103,6 +103,21 @@ int32_t crux_mlp_backward(crux_mlp* net, const float* d_x, int64_t B, const floa
  * atanh(clamp(a/ascale, -1+1f-5, 1-1f-5)) for stored actions; entropy stays 1.4189385 + sum(logSigma) (:398). ascale = 0 restores GaussianPolicy. */
 int32_t crux_mlp_set_squash(crux_mlp* net, float ascale);
 float crux_mlp_get_squash(const crux_mlp* net);
+/* GaussianPolicy(mu, logSigma::ContinuousNetwork) / SquashedGaussianPolicy(mu, logSigma, ascale) whose two networks share their trunk (the `base...` idiom of
+ * examples/rl/half_cheetah_mujoco.jl:37-43, test/policy_tests.jl:284-321): a shared trunk with two Dense(h, ad) heads is ONE Chain whose last layer has 2 ad rows. on = 1 marks
+ * the handle "two-headed": output rows [0, ad) are mu(s), rows [ad, 2 ad) logSigma(s). Needs n_extra == 0 and an even last width (else CRUX_EINVAL). crux_mlp_set_squash keeps its
+ * meaning (ascale > 0: squashed, sigma = exp(clamp(logSigma(s), -5, 2)), the -logSigma term of the log-density unclamped as in policies.jl:385). Parameters, copy, polyak and Adam
+ * see one flat vector. Served by the SAC entries (below), crux_rollout / crux_policy_explore (generic kernels) and crux_sigma_head_explore / _logpdf. The CQL entries refuse it
+ * by the flag (CRUX_EUNSUP: their sampled-action terms read a constant logSigma); every other Gaussian-head learner refuses it through its own shape check (it has no logSigma
+ * extras). Separate, non-sharing mu and logSigma networks are not implemented.                                                                                                */
+int32_t crux_mlp_set_sigma_head(crux_mlp* net, int32_t on);
+int32_t crux_mlp_get_sigma_head(const crux_mlp* net);
+/* exploration(pi, s) (explore = 1: a [ad x B] and logprob [B], eps of column j, row d = randn(Philox(seed, counter, stream = j ad + d, NOISE))) or action(pi, s) (explore = 0:
+ * mu(s), ascale tanh(mu(s)) when squashed; lp_out untouched) of a two-headed handle for B host columns s [obs x B].                                                          */
+int32_t crux_sigma_head_explore(crux_mlp* net, const float* s, int64_t B, int32_t explore, uint64_t seed, uint64_t counter, float* a_out, float* lp_out);
+/* logpdf(pi, s, a) [B] (stored squashed actions are un-tanh'd as atanh(clamp(a / ascale, -1 + 1f-5, 1 - 1f-5))) and the per-column sum_d logSigma(s) [B] that entropy(pi, s) =
+ * 1.4189385 + sum(logSigma(s)) is made of (policies.jl:348, 398); a = NULL: only the sums. Host arrays.                                                                       */
+int32_t crux_sigma_head_logpdf(crux_mlp* net, const float* s, const float* a, int64_t B, float* lp_out, float* sum_logsigma_out);
 /* copyto!(to, from) (src/policies.jl:61-65) and polyak_average!(to, from, tau) (:48-59).         */
 int32_t crux_mlp_copy(crux_mlp* to, const crux_mlp* from);
 int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau);
@@ -228,6 +243,9 @@ enum { CRUX_HEAD_CATEGORICAL = 0 /* DiscreteNetwork softmax head (policies.jl:10
        CRUX_HEAD_GAUSSIAN = 1    /* GaussianPolicy, const logSigma extras (policies.jl:315-350)    */,
        CRUX_HEAD_GREEDY_Q = 2    /* action(::DiscreteNetwork) argmax (policies.jl:124)             */,
        CRUX_HEAD_DETERMINISTIC = 3 /* ContinuousNetwork action (policies.jl:92)                    */ };
+/* A two-headed policy handle (crux_mlp_set_sigma_head; 2 act_dim outputs, no extras) is served by the generic rollout / explore kernels only. CRUX_HEAD_GAUSSIAN reads logSigma
+ * from output row act_dim + q (squashed: the clamp and tanh correction of the constant-logSigma squashed head; the same normals). CRUX_HEAD_DETERMINISTIC is action(pi_on, s):
+ * rows [0, act_dim), ascale tanh(mu) when squashed, BEFORE the Gaussian noise and its clamps (policies.jl:372, 510-513) -- SAC's default pi_explore.                          */
 /* n_envs Samplers of one mdp kind (Sampler struct, src/sampler.jl:1-22). obs_mu/obs_sigma: the
  * ContinuousSpace whitening of tovec (src/spaces.jl:25); NULL => 0 / 1. synth_* used by SYNTH.    */
 int32_t crux_env_create(crux_ctx* ctx, int32_t kind, int32_t n_envs, int32_t max_steps, float gamma,
@@ -610,7 +628,10 @@ int32_t crux_dqn_small_solve(crux_mlp* net, crux_mlp* target_net, crux_env* env,
  * (continuous actions). exploration's randn(Float32, size(mu)) (policies.jl:341) for batch column j, action
  * dim d is randn(Philox(seed, counter, stream = j*act_dim + d, NOISE)); the three draws of one epoch (target,
  * temperature, actor) take three different counters. Every *_step is train! (training.jl:13-25): loss ->
- * gradient -> norm (NaN => CRUX_ENAN, no update) -> Adam. info_out is host [CRUX_INFO_N].                 */
+ * gradient -> norm (NaN => CRUX_ENAN, no update) -> Adam. info_out is host [CRUX_INFO_N].
+ * The actor may instead be a two-headed handle obs -> 2 act_dim with no extras (crux_mlp_set_sigma_head), plain or squashed: logSigma(s) comes from the output rows, the
+ * squashed head adds the clamp and the tanh correction, and the reverse pass seeds the output layer with [dmu; dlogSigma] directly (no row sums). Same draws. A squashed
+ * handle with CONSTANT logSigma is refused as before (CRUX_EUNSUP). The chained epochs below record such an actor on the generic plan (never the tile plan).              */
 /* sac_target (sac.jl:4-9): y = r + gamma (1-done) (min(Q1-,Q2-)(sp,a') - exp(log_alpha) logprob(a')), a' ~ actor(sp). */
 int32_t crux_sac_target(crux_mlp* actor, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha, crux_buffer* batch,
                         float gamma, uint64_t seed, uint64_t counter, float* d_y);

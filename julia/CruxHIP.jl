@@ -300,6 +300,8 @@ end
 
 # --- SquashedGaussianPolicy, reservoir pushes, GAIL pieces: thin wrappers over the same handles
 set_squash!(π::HipNetwork, ascale::Real) = check(π.ctx, ccall((:crux_mlp_set_squash, LIB), Int32, (Ptr{Cvoid}, Float32), π.h, Float32(ascale)))   # SquashedGaussianPolicy(μ, logΣ, ascale) (policies.jl:353-400)
+# GaussianPolicy / SquashedGaussianPolicy whose logΣ network shares μ's trunk (Chain(base..., Dense(h, ad)) twice): one handle with 2 ad output rows, [μ; logΣ]
+set_sigma_head!(π::HipNetwork, on::Bool=true) = check(π.ctx, ccall((:crux_mlp_set_sigma_head, LIB), Int32, (Ptr{Cvoid}, Int32), π.h, Int32(on)))
 function Crux.push_reservoir!(b::HipBuffer, data::Dict{Symbol,<:AbstractArray}; weighted=false, seed=0, counter=0)                                # experience_buffer.jl:262-288
     cols = fill(C_NULL, NCOLS); keep = Any[]
     for (k, v) in data; haskey(COL, k) || continue; a = Array(v); push!(keep, a); cols[COL[k] + 1] = pointer(a); end
