@@ -28,6 +28,7 @@
 //   P1: load the peers' partials of the own W2 tiles -> W2 total + Adam (the small granules are still on their way)
 //   poll the peers' granules (the tag is the flag: ONE round trip) -> small total + Adam
 //   (replica group, PX: the group's all-reduce of the totals sits between the totals and Adam; PXK: its theta / m / v average after every k-th Adam step)
+//   (plain forms, LATE_W3 / LATE_B2: the dW3 partials are formed behind the acknowledgement, with dZ1 / db1 / dW1, and db2 between the dW2 stores and dH1)
 //   ============================== B_b (s_barrier): masters updated ==========================================================
 //
 //   (1) the W2 partials (89 % of the bytes) leave right after dW2 as before, but their hand-shake (drain, arrival counter, wait) is now run by the helper leader WHILE the
@@ -53,6 +54,9 @@
 #include "peer_wait.h"
 
 #define FS_LD 72
+#ifndef CRUX_FS2_LATE_PARTS
+#define CRUX_FS2_LATE_PARTS 3          // LATE_B2 (bit 0) and LATE_W3 (bit 1) in the kernel; a build with one of them alone is what profiles/fs2_helper_partials_ab.txt compares
+#endif
 __device__ __forceinline__ int fs_tx(int q) { return (4 - q) & 3; }   // {0,3,2,1}
 
 // H2: width of the second hidden layer, 64 or 32 (the first is MF_HID = 64): the reference's HalfCheetah PPO networks are 17-64-32-6 / 17-64-32-1
@@ -187,6 +191,16 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   // (forms that gain spilled scalar registers with STAT_SKIP keep their text: the timing twins of the value heads, 1 - 4 more, and the 8-64-64-2 Gaussian heads, 16 -> 18)
   constexpr bool STAT_SKIP = PLAIN && NGW <= 4 && !(TIMING && KIND == MFK_VALUE) && !(IN == 8 && OUT == 2 && KIND == MFK_GAUSSIAN);
   constexpr bool W2_TILED = PLAIN && WT == 2;
+  // (3) two reductions of the compute waves whose results nobody reads before B_2 leave the places where they cost most. LATE_W3: the dW3 partials stood in front of B_1,
+  // which every wave of the workgroup waits for; they are formed behind the wave's acknowledgement of its W2 stores (from a register copy of h2 taken before dZ2 overwrites
+  // it), where only the compute waves' own way to B_2 carries them. LATE_B2: db2 stood in the VALU-bound phase behind dH1; it is formed between the dW2 stores and dH1,
+  // beside the MFMAs. The same operations on the same values in the same lanes and order: the same bits. What was measured and not adopted (the helper waves forming
+  // either, db2 in front of dW2, dW3 beside the MFMAs, the b3 row sums behind B_1): DESIGN 4.1, profiles/fs2_helper_partials_ab.txt.
+  // LATE_B2 where the head's dW3 partials take one reduce-scatter pass: with the three passes of the 17-64-64-6 head it took back more than half of what LATE_W3 gives
+  // there (and that head's timing twin gained scratch with it).
+  constexpr int W3_PASSES = (OUT + 16 / (4 * MH) - 1) / (16 / (4 * MH));
+  constexpr bool LATE_B2 = PLAIN && (CRUX_FS2_LATE_PARTS & 1) && W3_PASSES == 1;
+  constexpr bool LATE_W3 = PLAIN && (CRUX_FS2_LATE_PARTS & 2);
   auto ka = [&]() { auto* q = (const __attribute__((address_space(4))) TrainArgs*)__builtin_amdgcn_kernarg_segment_ptr(); if constexpr (!PT) asm volatile("" : "+s"(q)); return q; };
   const int p = (int)(blockIdx.x >> 3);
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -809,6 +823,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         auto want_stats = [&]() -> bool { return !STAT_SKIP || static_report(st) || kl_on() || epochs_run == 0; };      // (formed where it is read: no register across the forward pass)
         // ======================= forward, C orientation: D[feature 16m+4g+r][sample c] =======================
         f32x4 h1[4]; f32x4 h2[MH];
+        f32x4 h2a[MH];      // LATE_W3: h2 as the forward pass left it (h2 itself becomes dZ2)
         constexpr bool W3_REG = OUT <= 2;
         f32x4 w3[OUT <= 2 ? OUT : 1][MH];
         float zp[OUT];
@@ -928,17 +943,23 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
             for (int k = 0; k < OUT; ++k) ent_pre += sm[Lt::oEX + k]; }
           // ======================= backward, own samples, own feature half =======================
           constexpr int FPL = 4 * MH, PER = 16 / FPL;
-#pragma unroll
-          for (int o2 = 0; o2 < (OUT + PER - 1) / PER; ++o2) { float pv[16];
-#pragma unroll
-            for (int oo = 0; oo < PER; ++oo)
-#pragma unroll
-              for (int mm = 0; mm < MH; ++mm)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pv[FPL * oo + 4 * mm + r] = (PER * o2 + oo < OUT) ? dz[(PER * o2 + oo < OUT) ? PER * o2 + oo : 0] * h2[mm][r] : 0.f;
-            const float sred = row16_reduce_scatter(pv, c);
-            const int oo = c / FPL;
+          // the dW3 partials of the own samples and feature half from the activations HV: PER outputs per reduce-scatter pass, into the tile's partial block
+#define FS2_DW3_PART(HV) \
+          _Pragma("unroll") \
+          for (int o2 = 0; o2 < (OUT + PER - 1) / PER; ++o2) { float pv[16]; \
+            _Pragma("unroll") \
+            for (int oo = 0; oo < PER; ++oo) \
+              _Pragma("unroll") \
+              for (int mm = 0; mm < MH; ++mm) \
+                _Pragma("unroll") \
+                for (int r = 0; r < 4; ++r) pv[FPL * oo + 4 * mm + r] = (PER * o2 + oo < OUT) ? dz[(PER * o2 + oo < OUT) ? PER * o2 + oo : 0] * HV[mm][r] : 0.f; \
+            const float sred = row16_reduce_scatter(pv, c); \
+            const int oo = c / FPL; \
             if (PER * o2 + oo < OUT) part[Lt::pW3 + (PER * o2 + oo) * H2 + HH * h + 16 * ((c >> 2) & (MH - 1)) + 4 * g + (c & 3)] = sred; }
+          if constexpr (LATE_W3) {      // they wait until the wave has acknowledged its W2 stores: the activations stay in registers for them
+#pragma unroll
+            for (int mm = 0; mm < MH; ++mm) h2a[mm] = h2[mm];
+          } else { FS2_DW3_PART(h2) }
           { f32x4 d2[MH];
 #pragma unroll
             for (int mm = 0; mm < MH; ++mm) d2[mm] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -987,6 +1008,17 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         FS2_T(6);
         f32x4 gW2[WT];
         dw2_send(gW2);
+        if constexpr (LATE_B2) {      // db2 from the dZ2 tile (visible since B_1), beside the MFMAs of this phase; the partial block is read behind B_2
+          float gb2[MH];
+#pragma unroll
+          for (int mm = 0; mm < MH; ++mm) { float sb2 = 0.f;
+            const f32x4 d2 = *(const f32x4*)&T2[t_rd + 256 * (MH * h + mm)];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sb2 += d2[r];
+            gb2[mm] = g4_sum(sb2); }
+          if (g == 0) {
+#pragma unroll
+            for (int mm = 0; mm < MH; ++mm) part[Lt::pB2 + HH * h + 16 * mm + c] = gb2[mm]; } }
         // dH1 (R) for the h1 features [32h, 32h + 32)
         f32x4 dz1r[2];
         { const float* dq = sm + Lt::oD2X + ((t * 2 + (1 - h)) * MH) * 256 + lane * 4;
@@ -1005,6 +1037,8 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the dW2 stores left before dH1: acknowledged by now -- tell the helper leader (phase 1)
         if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FS2_T(7);
+        if constexpr (LATE_W3) { constexpr int FPL = 4 * MH, PER = 16 / FPL; FS2_DW3_PART(h2a) }
+#undef FS2_DW3_PART
         float gb1[2], gb2[MH];
 #pragma unroll
         for (int mm = 0; mm < 2; ++mm) { float sb1 = 0.f;
@@ -1012,17 +1046,19 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) { const float d = actg<ACT>(h1r[r], dz1r[mm][r]); dz1r[mm][r] = d; sb1 += d; }
           gb1[mm] = g4_sum(sb1); }
+        if constexpr (!LATE_B2) {
 #pragma unroll
         for (int mm = 0; mm < MH; ++mm) { float sb2 = 0.f;
           const f32x4 d2 = *(const f32x4*)&T2[t_rd + 256 * (MH * h + mm)];
 #pragma unroll
           for (int r = 0; r < 4; ++r) sb2 += d2[r];
-          gb2[mm] = g4_sum(sb2); }
+          gb2[mm] = g4_sum(sb2); } }
         if (g == 0) {
 #pragma unroll
           for (int mm = 0; mm < 2; ++mm) part[Lt::pB1 + 32 * h + 16 * mm + c] = gb1[mm];
+          if constexpr (!LATE_B2) {
 #pragma unroll
-          for (int mm = 0; mm < MH; ++mm) part[Lt::pB2 + HH * h + 16 * mm + c] = gb2[mm]; }
+          for (int mm = 0; mm < MH; ++mm) part[Lt::pB2 + HH * h + 16 * mm + c] = gb2[mm]; } }
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt) {
           float xR[4];
