@@ -455,6 +455,7 @@ __global__ void k_importance_fills(const float* __restrict__ iw, const uint8_t* 
 extern "C" int32_t crux_importance_weight_rows(crux_buffer* b, crux_mlp* nominal, int32_t head, int64_t first_row, int64_t n_rows) { CRUX_PLAIN_ONLY("crux_importance_weight_rows", nominal);
   if (!b || !nominal) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
+  if (nominal->sigma_head) return crux_fail(c, CRUX_EUNSUP, "importance_weight: a two-headed Gaussian actor (logSigma network) as the nominal policy is not implemented");
   if (!has_col(b, CRUX_COL_IMPORTANCE_WEIGHT) || !has_col(b, CRUX_COL_LOGPROB)) return crux_fail(c, CRUX_EINVAL, "importance_weight: the buffer needs :importance_weight and :logprob columns");
   if (n_rows == 0) return CRUX_OK;
   if (first_row < 0 || n_rows < 0 || first_row + n_rows > b->capacity) return crux_fail(c, CRUX_EINVAL, "importance_weight: rows [%lld, %lld) outside the buffer (a wrapped range takes two calls)", (long long)first_row, (long long)(first_row + n_rows));

@@ -497,6 +497,7 @@ int32_t crux_steps_push(crux_buffer* buf, int64_t n, const void* const* cols, in
                         crux_mlp* cost_critic, crux_mlp* nominal, int32_t nominal_head, int64_t* first_row_out) { CRUX_PLAIN_ONLY("crux_steps_push", critic, cost_critic, nominal);
   if (!buf || !cols || n < 0) return CRUX_EINVAL;
   crux_ctx* c = buf->ctx;
+  if (nominal && nominal->sigma_head) return crux_fail(c, CRUX_EUNSUP, "steps_push: a two-headed Gaussian actor (logSigma network) as the nominal policy of :importance_weight is not implemented");
   if (n > buf->capacity && (has_col(buf, CRUX_COL_ADVANTAGE) || has_col(buf, CRUX_COL_RETURN) || has_col(buf, CRUX_COL_COST_ADVANTAGE) || has_col(buf, CRUX_COL_COST_RETURN) ||
                             has_col(buf, CRUX_COL_FWD_IMPORTANCE_WEIGHT) || has_col(buf, CRUX_COL_CUM_IMPORTANCE_WEIGHT) || has_col(buf, CRUX_COL_REV_IMPORTANCE_WEIGHT) || (nominal && has_col(buf, CRUX_COL_IMPORTANCE_WEIGHT))))
     return crux_fail(c, CRUX_EINVAL, "steps!: a block of %lld transitions does not fit the buffer (capacity %lld) whose advantage / return / importance-weight columns it must fill", (long long)n, (long long)buf->capacity);

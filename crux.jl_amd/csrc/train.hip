@@ -86,7 +86,10 @@ static int32_t fill_args(TrainArgs& a, crux_mlp* net, crux_buffer* buf, const cr
   }
   if (CRUX_IS_PG(internal_loss)) {
     if (!a.LP || !a.ADV) return crux_fail(c, CRUX_EINVAL, "ppo_loss: buffer needs :logprob and :advantage columns");
-    if (cfg->head == CRUX_HEAD_CATEGORICAL) { if (nout != buf->act_dim || buf->act_kind != CRUX_ACTION_DISCRETE || nout > 32) return crux_fail(c, CRUX_EINVAL, "ppo_loss: categorical head needs %d logits over a one-hot action column", buf->act_dim); }
+    if (net->sigma_head && cfg->head == CRUX_HEAD_GAUSSIAN) {      // two-headed Gaussian actor (crux_mlp_set_sigma_head): [mu; logSigma(s)] rows, no extras -- the dense-engine learner's k_pg_head_sigma
+      if (nout != 2 * buf->act_dim || net->nd.n_extra != 0 || buf->act_kind != CRUX_ACTION_CONTINUOUS)
+        return crux_fail(c, CRUX_EINVAL, "ppo_loss: a two-headed gaussian head needs 2 x %d output rows (mu, then logSigma), no extras and a Float32 action column (got %d rows, %d extras)", buf->act_dim, nout, net->nd.n_extra); }
+    else if (cfg->head == CRUX_HEAD_CATEGORICAL) { if (nout != buf->act_dim || buf->act_kind != CRUX_ACTION_DISCRETE || nout > 32) return crux_fail(c, CRUX_EINVAL, "ppo_loss: categorical head needs %d logits over a one-hot action column", buf->act_dim); }
     else if (cfg->head == CRUX_HEAD_GAUSSIAN) { if (nout != buf->act_dim || buf->act_kind != CRUX_ACTION_CONTINUOUS || net->nd.n_extra != buf->act_dim) return crux_fail(c, CRUX_EINVAL, "ppo_loss: gaussian head needs %d means + %d logSigma extras over a Float32 action column", buf->act_dim, buf->act_dim); }
     else return crux_fail(c, CRUX_EINVAL, "ppo_loss: head %d unsupported", cfg->head);
   } else if (internal_loss == CRUX_LOSS_VALUE_MSE) {
@@ -96,6 +99,8 @@ static int32_t fill_args(TrainArgs& a, crux_mlp* net, crux_buffer* buf, const cr
       a.RET = (const float*)buf->col[k];
     }
     if (!a.RET || nout != 1) return crux_fail(c, CRUX_EINVAL, "critic mse: needs a :return column and a scalar-output network");
+  } else if (internal_loss == CRUX_LOSS_MSE_ACTION && net->sigma_head) {
+    return crux_fail(c, CRUX_EUNSUP, "mse_action_loss on a two-headed Gaussian actor (logSigma network) is not implemented: its learners are ppo_loss, a2c_loss, reinforce_loss and logpdf_bc_loss");
   } else if (internal_loss == CRUX_LOSS_MSE_ACTION && net->squash > 0.f) {
     return crux_fail(c, CRUX_EUNSUP, "mse_action_loss through a SquashedGaussianPolicy (ascale*tanh(mu)) is not implemented");
   } else if (internal_loss == CRUX_LOSS_MSE_ACTION) {
@@ -186,6 +191,19 @@ int32_t crux_train_fs_launch(crux_ctx* c, const TrainArgs& a, bool* handled, hip
 static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_t stream = nullptr, const crux_fisher* reg = nullptr) {
   bool handled = false;
   if (!stream) stream = c->stream;
+  const bool two = a.host_net && ((const crux_mlp*)a.host_net)->sigma_head;      // two-headed Gaussian actor: the dense-engine learner only, at every size
+  if (two) {      // never the register-resident kernels or the generic learner (a 3-64-64-2 handle has an instantiated shape by its dims): their heads read constant logSigma extras
+    if (reg) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a DiagonalFisherRegularizer: not implemented for a two-headed Gaussian actor (logSigma network)");
+    if (crux_grouped(c) && a.apply && !a.ids) return crux_fail(c, CRUX_EUNSUP, "batch_train! of a two-headed Gaussian actor (logSigma network) with a replica group attached is not implemented");
+    if (a.lag) return crux_fail(c, CRUX_EUNSUP, "lagrange_ppo_loss is not implemented for a two-headed Gaussian actor (logSigma network)");
+    if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false, true)) return crux_fail(c, CRUX_EUNSUP, "train!: a two-headed Gaussian actor trains with ppo_loss / a2c_loss / reinforce_loss / logpdf_bc_loss on the dense-engine learner only (loss %d, head %d)", a.loss, a.head);
+    a.need_px = 0; a.px_timeout = c->peer_timeout_ticks; a.px_every = 1;
+    const bool prof_t = stream == c->stream;
+    if (prof_t) crux_prof_begin(c, prof_slot);
+    const int32_t rct = crux_train_dense_run(c, a, stream, prof_t ? 0 : 1);
+    if (prof_t) crux_prof_end(c, prof_slot);
+    return rct;
+  }
   if (reg) {
     a.need_px = 0; a.px_timeout = c->peer_timeout_ticks; a.px_every = 1;
     if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false, true)) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a DiagonalFisherRegularizer: the dense-engine learner has no loss %d / head %d for this handle", a.loss, a.head);
@@ -255,7 +273,7 @@ static int32_t run_batch(crux_mlp* net, crux_buffer* buf, TrainArgs& a, int n_ep
     int32_t* oa = nullptr; rc = build_orders(c, buf, 0, nullptr, a.shuffle_seed, a.shuffle_counter, a.perms, n_epochs, c->stream, &oa); if (rc) return rc;
     a.ord_all = oa;
   }
-  if (!a.ids && !reg) { rc = ensure_pack(c, buf, c->stream, a, nullptr); if (rc) return rc; }      // (the dense chain gathers through the order, not from packed rows)
+  if (!a.ids && !reg && !net->sigma_head) { rc = ensure_pack(c, buf, c->stream, a, nullptr); if (rc) return rc; }      // (the dense chain -- a regularised or two-headed handle's only route -- gathers through the order, not from packed rows)
   rc = launch_train(c, a, slot, nullptr, reg); if (rc) return rc;
   int32_t st[8]; std::vector<float> ei((size_t)CRUX_INFO_N * (size_t)(n_epochs > 0 ? n_epochs : 1));
   HIPCHK(c, hipMemcpyAsync(st, a.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -296,6 +314,10 @@ static int32_t upload_perms(crux_ctx* c, const int64_t* perms, int epochs, int64
 // copied in before the launch and back after it
 static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos, const crux_fisher* reg = nullptr) {
   crux_ctx* c = net->ctx;
+  if (net->sigma_head) {      // refused by name before anything is enqueued (cruxhip.h: two-headed handles)
+    const char* what = lag ? "lagrange_ppo_loss" : reg ? "a DiagonalFisherRegularizer" : crux_grouped(c) ? "a replica group attached" : nullptr;
+    if (what) return crux_fail(c, CRUX_EUNSUP, "batch_train! of a two-headed Gaussian actor (logSigma network) with %s is not implemented", what);
+  }
   TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, lag ? CRUX_LOSS_PPO : cfg->loss); if (rc) return rc;
   if (lag) {
     if (!c->lag_dev) { if (hipMalloc(&c->lag_dev, 256) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "lagrange state"); }
@@ -325,6 +347,7 @@ int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
 int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_lagrange", net);
   if (!net || !buf || !cfg || !lag) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
+  if (net->sigma_head) return crux_fail(c, CRUX_EUNSUP, "batch_train! (lagrange): lagrange_ppo_loss is not implemented for a two-headed Gaussian actor (logSigma network)");
   if (cfg->loss != CRUX_LOSS_LAGRANGE_PPO) return crux_fail(c, CRUX_EINVAL, "batch_train! (lagrange): cfg.loss must be CRUX_LOSS_LAGRANGE_PPO");
   if (buf->elements <= 0 || cfg->epochs < 1) return crux_fail(c, CRUX_EINVAL, "batch_train! (lagrange): empty buffer or epochs %d", cfg->epochs);
   if (!has_col(buf, CRUX_COL_COST) || !has_col(buf, CRUX_COL_COST_ADVANTAGE)) return crux_fail(c, CRUX_EINVAL, "lagrange_ppo_loss: buffer needs :cost and :cost_advantage columns (ppo.jl:211)");
@@ -337,6 +360,7 @@ int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_tr
 int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_fisher", net);
   if (!net || !R || !buf || !cfg) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const char* who = "batch_train! with a DiagonalFisherRegularizer";
+  if (net->sigma_head) return crux_fail(c, CRUX_EUNSUP, "%s: not implemented for a two-headed Gaussian actor (logSigma network)", who);
   if (R->net != net) return crux_fail(c, CRUX_EUNSUP, "%s: the regulariser belongs to another handle", who);
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
   if (crux_grouped(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not in a replica group", who);
@@ -588,7 +612,7 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
               buf->elements < ((int64_t)1 << 31) && crux_sw().spec_pair;
   { const bool fs_on = (crux_sw().fs != 0) && cfg_a->batch_size > 64 && cfg_a->batch_size <= 128;      // the feature-split kernel also takes a 32-wide second layer
     auto mfma_family = [fs_on](const crux_mlp* n) { const NetDesc& d = n->nd; return d.L == 3 && d.dims[1] == 64 && (d.dims[2] == 64 || (d.dims[2] == 32 && fs_on)); };
-    bool family = mfma_family(actor) && mfma_family(critic);
+    bool family = mfma_family(actor) && mfma_family(critic) && !actor->sigma_head && !critic->sigma_head;      // (a two-headed actor: the dense engine's pair, or one learner after the other)
     if (family && (exact || spec) && fs_on && c->learner_cus == 0 && buf->elements >= cfg_a->batch_size && cfg_a->batch_size == cfg_c->batch_size) {      // 64 wide, but does a register-resident kernel instantiate these shapes?
       TrainArgs pa, pk; bool ha = false, hk = false;
       if (!fill_args(pa, actor, buf, cfg_a, cfg_a->loss) && !fill_args(pk, critic, buf, cfg_c, cfg_c->loss)) { pa.need_px = pk.need_px = crux_grouped(c) ? 1 : 0;
@@ -680,6 +704,7 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
   if (n < 1 || !actors || !critics || !bufs || !cfg_a || !cfg_c) return CRUX_EINVAL;
   for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_policy_gradient_training_multi", actors[i], critics[i]);
   crux_ctx* c = actors[0]->ctx;
+  for (int i = 0; i < n; ++i) if ((actors[i] && actors[i]->sigma_head) || (critics[i] && critics[i]->sigma_head)) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: two-headed Gaussian actors (logSigma network) are not batched");
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: early stopping / max_batches need the sequential single-learner call");
   if (cfg_a->epochs < 1 || cfg_c->epochs < 1) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_multi: epochs < 1");
   { const int32_t rca = ensure_aux_stream(c); if (rca) return rca; }
@@ -763,6 +788,7 @@ extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_ml
                                                         int32_t sync_every, float* info_a, float* info_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training_synced", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c || sync_every < 1) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
+  if (actor->sigma_head || critic->sigma_head) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_synced: not implemented for a two-headed Gaussian actor (logSigma network)");
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_synced: early stopping / max_batches would let replicas diverge in epoch count");
   if (buf->elements <= 0 || cfg_a->epochs < 1 || cfg_c->epochs != cfg_a->epochs) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training_synced: empty buffer, epochs < 1 or actor/critic epoch counts differ");
   const int64_t len = buf->elements; if (len >= ((int64_t)1 << 31)) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_synced: buffer too long");

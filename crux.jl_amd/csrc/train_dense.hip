@@ -148,6 +148,66 @@ __global__ void k_pg_info(const double* __restrict__ st, const double* __restric
   dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
 }
 
+// ---- two-headed Gaussian actors (crux_mlp_set_sigma_head): z = net(s) [2 ad x nb], mu = z[d], l = z[ad + d] (policies.jl:315-350, 355-400) -----------------------------------
+// ppo_loss / a2c_loss (and, through fill_args' mappings, reinforce_loss / logpdf_bc_loss) of GaussianPolicy(mu, logSigma::ContinuousNetwork) and its squashed form. A kernel of
+// its own -- k_pg_head and k_pg_info above stay as they are for every other handle. One thread per column over a GRID of 256-thread blocks (the reference's on-policy
+// minibatches are 512 and 4000 columns): logSigma is an output row, so its gradient is a seed like mu's, written straight into dy [2 ad x nb] -- no per-parameter reduction,
+// no gx. Only the eight statistics sums cross threads: every block leaves Float64 partials (block_sum256's order) and k_pg_info_sigma adds them in block order; no atomics,
+// two identical calls give identical bits.
+//   sigma = exp(l), u = a                                           (GaussianPolicy)
+//   sigma = exp(clamp(l, -5, 2)), u = atanh(clamp(a / ascale))      (SquashedGaussianPolicy; the -l of the log-density stays unclamped)
+//   dy[d] = (1/B) cf (u - mu) / sigma^2;   dy[ad + d] = (1/B) cf ((u - mu)^2 / sigma^2 inr - 1) - lambda_e e,   cf = -lambda_p g r as in k_pg_head, inr = 0 where the clamp is active
+// The entropy term follows the reference LITERALLY: entropy(::GaussianPolicy, s) = 1.4189385 .+ sum(logSigma(s)) has no `dims` (policies.jl:348) -- one scalar over the whole
+// minibatch, so e_loss = -mean(scalar) = -(1.4189385 + sum_j sum_d l) and e = 1; the squashed policy sums per column (policies.jl:398), e = 1/B. (The reference's own Gaussian
+// PPO examples run with lambda_e = 0.) NaN: a NaN in s / z, a, the old logprob or the advantage reaches dy, the norm, and the gate of adam_gated / k_nan_status (CRUX_ENAN).
+struct PgSigmaArgs {
+  const float* z; const int32_t* rows; int64_t nb; const float* A; int ad; const float* LP; const float* ADV; const float* RET;
+  int loss; float lo, hi, lambda_p, lambda_e, squash;
+  float* dy;             // [2 ad x nb]
+  double* part;          // [gridDim.x x 8]: the blocks' partial sums, k_pg_head's eight statistics
+};
+__global__ __launch_bounds__(256) void k_pg_head_sigma(PgSigmaArgs q) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x; const int64_t s = (int64_t)blockIdx.x * 256 + tid;
+  const float invB = 1.0f / (float)q.nb; const bool a2c = q.loss == CRUX_LOSS_A2C; const float sq = q.squash; const int ad = q.ad;
+  double s_lossp = 0, s_H = 0, s_kl = 0, s_adv = 0, s_ret = 0, s_clip = 0;
+  if (s < q.nb) {
+    const int64_t row = q.rows[s]; const float* z = q.z + s * (2 * ad); float* dy = q.dy + s * (2 * ad); const float* av = q.A + row * ad;
+    const float A = q.ADV[row], oldlp = q.LP[row]; float newlp = 0.f;
+    for (int k = 0; k < ad; ++k) { const float l = z[ad + k]; const float sg = expf(sq > 0.f ? sq_clampls(l) : l); const float uk = sq > 0.f ? sq_untanh(av[k], sq) : av[k]; const float d = uk - z[k];
+      newlp += (-(d * d) / (2.f * sg * sg) - 0.9189385332046727f - l); if (sq > 0.f) newlp -= sq_corr(uk);
+      s_H += (double)l; }
+    float r = expf(newlp - oldlp); const float u = r * A, rc = fminf(fmaxf(r, q.lo), q.hi), cl = rc * A;
+    float g = (cl < u) ? 0.f : A;      // (u <= cl) ? A : 0 on ordered operands; a NaN advantage stays in g and reaches the norm
+    s_lossp = (double)(a2c ? newlp * A : (u <= cl ? u : cl));
+    if (a2c) { g = A; r = 1.f; }
+    const float cf = -q.lambda_p * g * r; const float le = q.lambda_e * (sq > 0.f ? invB : 1.f);
+    for (int k = 0; k < ad; ++k) { const float l = z[ad + k]; const float sg = expf(sq > 0.f ? sq_clampls(l) : l); const float s2 = sg * sg; const float uk = sq > 0.f ? sq_untanh(av[k], sq) : av[k]; const float d = uk - z[k];
+      const float inr = (sq > 0.f && !(l >= -5.f && l <= 2.f)) ? 0.f : 1.f;
+      dy[k] = invB * (cf * (d / s2));
+      dy[ad + k] = invB * (cf * (((d * d) / s2) * inr - 1.f)) - le; }
+    s_kl = (double)(oldlp - newlp); s_adv = (double)A; if (q.RET) s_ret = (double)q.RET[row];
+    if (!a2c && (r > q.hi || r < q.lo)) s_clip = 1.0;
+  }
+  const double t0 = block_sum256(s_lossp, red), t1 = block_sum256(s_H, red), t2 = block_sum256(s_kl, red), t3 = block_sum256(s_adv, red), t4 = block_sum256(s_ret, red), t5 = block_sum256(s_clip, red);
+  if (tid == 0) { double* o = q.part + (size_t)blockIdx.x * 8; o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[4] = t4; o[5] = t5; o[6] = 0.0; o[7] = 0.0; }
+}
+// the blocks' partials in block order -> st[8], then the info row of k_pg_info's policy-gradient branch with the entropy of logSigma(s): GaussianPolicy 1.4189385 + s_H (the
+// scalar over the minibatch), SquashedGaussianPolicy 1.4189385 + s_H / B
+__global__ void k_pg_info_sigma(const double* __restrict__ part, int nblk, double* __restrict__ st, const double* __restrict__ ssq, int64_t nb, float lambda_p, float lambda_e, float squash,
+                                float* __restrict__ dinfo) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  ssq_finalize(ssq);
+  for (int k = 0; k < 8; ++k) { double t = 0.0; for (int b = 0; b < nblk; ++b) t += part[(size_t)b * 8 + k]; st[k] = t; }
+  for (int k = 0; k < CRUX_INFO_N; ++k) dinfo[k] = 0.f;
+  const float p_loss = (float)(-(st[0] / (double)nb));
+  const float entropy = 1.4189385332046727f + (float)(squash > 0.f ? st[1] / (double)nb : st[1]); const float e_loss = -entropy;
+  dinfo[CRUX_INFO_LOSS] = lambda_p * p_loss + lambda_e * e_loss; dinfo[CRUX_INFO_ENTROPY] = entropy; dinfo[CRUX_INFO_KL] = (float)(st[2] / (double)nb);
+  dinfo[CRUX_INFO_CLIP_FRACTION] = (float)st[5] / (float)nb; dinfo[CRUX_INFO_AVG_ADVANTAGE] = (float)(st[3] / (double)nb); dinfo[CRUX_INFO_AVG_RETURN] = (float)(st[4] / (double)nb);
+  dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
+}
+static inline bool train_two_headed(const TrainArgs& a) { return a.host_net && ((const crux_mlp*)a.host_net)->sigma_head; }
+
 // Replica group (comm.hip "peer") for the dense-engine learner: the SUM all-reduce of the flat minibatch gradient (and of the head's eight statistics sums) between the pullback
 // (training.jl:18) and Flux.update! (:21) as ONE launch of one workgroup, in chunks of a peer slot: chunk k is exchange number x0 + k of this learner stream -- written into
 // slot [parity][my rank] of every peer, system-scope release, flag, wait for the N - 1 flags in the own region, acquire, add the N contributions in rank order (the own one from
@@ -204,6 +264,7 @@ bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool forc
   if (!(CRUX_IS_PG(a.loss) || a.loss == CRUX_LOSS_VALUE_MSE || (a.loss == CRUX_LOSS_MSE_ACTION && a.squash == 0.f))) return false;
   if (CRUX_IS_PG(a.loss) && a.head != CRUX_HEAD_CATEGORICAL && a.head != CRUX_HEAD_GAUSSIAN) return false;
   if (a.nd.L < 1 || a.nd.n_extra > CRUX_MAXEXTRA) return false;
+  if (train_two_headed(a)) return CRUX_IS_PG(a.loss) && a.head == CRUX_HEAD_GAUSSIAN;      // no other learner has the two-headed head (k_pg_head_sigma): every size, single steps included
   if (any_size) return true;
   if (generic_lds > 160 * 1024 - 64) return true;                                   // the generic learner cannot hold it at all
   return !force_generic && a.nd.n_params >= 512 && a.bs >= 32 && !a.ids;            // single steps and tiny networks (the README's 2-8-4) stay on the one-launch generic learner
@@ -221,13 +282,16 @@ int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int wh
   const int64_t total_rows = a.ids ? a.n_ids : a.len; const int n_epochs = a.ids ? 1 : a.epochs;
   const int64_t bmax = total_rows < a.bs ? total_rows : a.bs;
   // a block of the context that nothing else carves (the caller's status / info rows live in the scratch block)
-  { const size_t need = 4 * (size_t)bmax * (size_t)(od + nout) + 256 * 8 + 4096;
+  const bool two = net->sigma_head && CRUX_IS_PG(a.loss);      // two-headed Gaussian actor: k_pg_head_sigma over a grid of head blocks
+  const int64_t hblk = two ? (bmax + 255) / 256 : 0;
+  { const size_t need = 4 * (size_t)bmax * (size_t)(od + nout) + 256 * 8 + 4096 + (two ? Carve::span<double>(8 * (size_t)hblk) : 0);
     if (dtmp_bytes < need) { if (dtmp) { HIPCHK(c, hipStreamSynchronize(strm)); (void)hipFree(dtmp); dtmp = nullptr; dtmp_bytes = 0; }
       if (hipMalloc(&dtmp, 2 * need) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "batch_train! (dense): %zu bytes of staging", 2 * need);
       dtmp_bytes = 2 * need; } }
   Carve cv{(char*)dtmp, 0};
   float* x = cv.take<float>((size_t)bmax * od); float* dy = cv.take<float>((size_t)bmax * nout);
   float* dinfo = cv.take<float>(CRUX_INFO_N); double* st = cv.take<double>(8); double* ssq = cv.take<double>(2 + SUMSQ_BLOCKS); int32_t* status = cv.take<int32_t>(4);
+  double* hpart = two ? cv.take<double>(8 * (size_t)hblk) : nullptr;
   HIPCHK(c, hipMemsetAsync(status, 0, 16, strm));
   if (which && !c->dense_pinned2 && hipHostMalloc(&c->dense_pinned2, 256, hipHostMallocDefault) != hipSuccess) { c->dense_pinned2 = nullptr; return crux_fail(c, CRUX_ENOMEM, "batch_train! (dense): pinned staging"); }
   float* hinfo = which ? (float*)c->dense_pinned2 : (float*)crux_pinned(c, sizeof(float) * CRUX_INFO_N + 16); if (!hinfo) return crux_fail(c, CRUX_ENOMEM, "batch_train! (dense): pinned staging");
@@ -249,10 +313,17 @@ int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int wh
       hipLaunchKernelGGL(k_gather_obs, dim3((unsigned)((nb * od + 255) / 256)), dim3(256), 0, strm, a.S, od, order + s0, nb, x);
       int32_t rc = crux_dense_forward(net, x, nb, strm); if (rc) return rc;
       if (a.lag) hipLaunchKernelGGL(k_lagrange_pid, dim3(1), dim3(256), 0, strm, a.lag, a.COST, a.EE, order + s0, nb, (float* const*)((a.need_px && c->peer_n > 1) ? c->peer_tab + which * CRUX_PX_MAXR : nullptr), c->peer_rank, c->peer_n, status, c->peer_timeout_ticks);
-      PgHeadArgs q{}; q.lag = a.lag; q.CADV = a.CADV; q.z = crux_dense_act(net, nd.L); q.nout = nout; q.rows = order + s0; q.nb = nb; q.A = a.A; q.ad = a.ad; q.LP = a.LP; q.ADV = a.ADV; q.RET = a.RET;
-      q.loss = a.loss; q.head = a.head; q.lo = 1.f - a.eps_clip; q.hi = 1.f + a.eps_clip; q.lambda_p = a.lambda_p; q.lambda_e = a.lambda_e; q.squash = a.squash;
-      q.ls = net->p + nd.xoff; q.dy = dy; q.gx = net->g + nd.xoff; q.stats = st;
-      hipLaunchKernelGGL(k_pg_head, dim3(1), dim3(256), 0, strm, q);
+      const unsigned nhb = (unsigned)((nb + 255) / 256);      // head blocks of the two-headed head
+      if (two) {      // two-headed Gaussian actor: the seeds of mu and logSigma(s) per column, block partials of the statistics (no logSigma extras, no gx)
+        PgSigmaArgs h{}; h.z = crux_dense_act(net, nd.L); h.rows = order + s0; h.nb = nb; h.A = (const float*)a.A; h.ad = a.ad; h.LP = a.LP; h.ADV = a.ADV; h.RET = a.RET; h.loss = a.loss;
+        h.lo = 1.f - a.eps_clip; h.hi = 1.f + a.eps_clip; h.lambda_p = a.lambda_p; h.lambda_e = a.lambda_e; h.squash = a.squash; h.dy = dy; h.part = hpart;
+        hipLaunchKernelGGL(k_pg_head_sigma, dim3(nhb), dim3(256), 0, strm, h);
+      } else {
+        PgHeadArgs q{}; q.lag = a.lag; q.CADV = a.CADV; q.z = crux_dense_act(net, nd.L); q.nout = nout; q.rows = order + s0; q.nb = nb; q.A = a.A; q.ad = a.ad; q.LP = a.LP; q.ADV = a.ADV; q.RET = a.RET;
+        q.loss = a.loss; q.head = a.head; q.lo = 1.f - a.eps_clip; q.hi = 1.f + a.eps_clip; q.lambda_p = a.lambda_p; q.lambda_e = a.lambda_e; q.squash = a.squash;
+        q.ls = net->p + nd.xoff; q.dy = dy; q.gx = net->g + nd.xoff; q.stats = st;
+        hipLaunchKernelGGL(k_pg_head, dim3(1), dim3(256), 0, strm, q);
+      }
       // (round 4) the fused pullback of layers 1 / 0 where it applies (dense_fused.h: three launches instead of five); it leaves layer 0's gradient as quarter partials that
       // Sumsq2Op completes -- not in a replica group, whose flat all-reduce reads the whole gradient before the norm
       const bool group = a.need_px && c->peer_n > 1; Sumsq2Fix fx{};
@@ -261,7 +332,8 @@ int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm, int wh
         hipLaunchKernelGGL(k_px_allreduce_flat, dim3(1), dim3(1024), 0, strm, net->g, (int64_t)nd.n_params, st, (float* const*)(c->peer_tab + which * CRUX_PX_MAXR), c->peer_rank, c->peer_n, status, c->peer_timeout_ticks);
       if (fisher_active(reg)) fisher_enqueue_reg(reg, true, strm);
       crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, strm, (float*)net->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
-      hipLaunchKernelGGL(k_pg_info, dim3(1), dim3(1), 0, strm, (const double*)st, (const double*)ssq, nb, a.loss, a.head, a.lambda_p, a.lambda_e, (const float*)(net->p + nd.xoff), a.ad, dinfo, (const crux_lagrange*)a.lag);
+      if (two) hipLaunchKernelGGL(k_pg_info_sigma, dim3(1), dim3(1), 0, strm, (const double*)hpart, (int)nhb, st, (const double*)ssq, nb, a.lambda_p, a.lambda_e, a.squash, dinfo);      // (adds the head blocks' partials into st first)
+      else hipLaunchKernelGGL(k_pg_info, dim3(1), dim3(1), 0, strm, (const double*)st, (const double*)ssq, nb, a.loss, a.head, a.lambda_p, a.lambda_e, (const float*)(net->p + nd.xoff), a.ad, dinfo, (const crux_lagrange*)a.lag);
       if (fisher_active(reg)) fisher_enqueue_finish(reg, dinfo, strm);
       if (a.apply) { rc = adam_gated(net, ssq, status, true, strm); if (rc) return rc; }
       else hipLaunchKernelGGL(k_nan_status, dim3(1), dim3(1), 0, strm, (const double*)ssq, status);

@@ -5,6 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
+from .core import refuse_two_headed, require_two_headed_opt_in   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -326,14 +327,16 @@ def stop_on_validation_increase(pi, P, D_val, p, window=5):
     return f
 
 
-def BC(pi, S, D_demo, normalize_demo=True, loss=None, validation_fraction=0.3, window=100, lambda_e=1e-3, opt=None, shuffle_perm=None, **kw):
+def BC(pi, S, D_demo, normalize_demo=True, loss=None, validation_fraction=0.3, window=100, lambda_e=1e-3, opt=None, shuffle_perm=None, two_headed=False, **kw):
     """BC(; pi, S, D_demo, normalize_demo, loss, validation_fraction=0.3, window=100, lambda_e=1f-3, opt) (src/model_free/il/bc.jl:37-70):
     mse_action_loss for a ContinuousNetwork, logpdf_bc_loss otherwise; the demonstrations are normalised, shuffled once and split into
     training / validation parts; early stopping on the validation error. shuffle_perm: optional 1-based permutation for the initial shuffle!."""
-    if getattr(actor(pi), "two_headed", False):
-        raise NotImplementedError("BC: a policy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only")
+    require_two_headed_opt_in(actor(pi), "BC", two_headed)      # (two_headed=True: a two-headed Gaussian actor with logpdf_bc_loss; without the keyword it is refused as before -- the keyword's only purpose, see core.require_two_headed_opt_in)
     loss = loss or (mse_action_loss if type(pi) is ContinuousNetwork else logpdf_bc_loss)
-    A = pi.space if hasattr(pi, "space") else (DiscreteSpace(len(pi.outputs), pi.outputs) if isinstance(pi, DiscreteNetwork) else ContinuousSpace(pi.network.dims[-1]))
+    if getattr(actor(pi), "two_headed", False) and (isinstance(loss, CustomLoss) or loss.name != "logpdf_bc"):      # a two-headed actor: logpdf_bc_loss only (k_pg_head_sigma)
+        refuse_two_headed(actor(pi), "BC with %s" % ("a CustomLoss" if isinstance(loss, CustomLoss) else loss.name + "_loss"))
+    A = pi.space if hasattr(pi, "space") else (DiscreteSpace(len(pi.outputs), pi.outputs) if isinstance(pi, DiscreteNetwork)
+                                               else ContinuousSpace(getattr(pi, "act_dim", None) or pi.network.dims[-1]))
     D = buffer_like(D_demo, capacity=len(D_demo)); D.push_({k: D_demo[k] for k in D_demo.keys()})      # deepcopy(D_demo) (:52)
     if normalize_demo:
         normalize_(D, S, A)

@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
-from .core import refuse_spectral, refuse_two_headed   # noqa: F401
+from .core import refuse_spectral, refuse_two_headed, require_two_headed_opt_in, _refuse_two_headed_params   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -25,9 +25,15 @@ class OnPolicySolver:
     (src/model_free/on_policy.jl:31-54)."""
 
     def __init__(self, agent, S, N=1000, dN=200, max_steps=100, a_opt=None, c_opt=None, P=None, lambda_gae=0.95,
-                 required_columns=(), post_batch_callback=None, post_sample_callback=None, i=0, log=None, Vc=None, cost_opt=None, param_optimizers=None, interaction_storage=None):
+                 required_columns=(), post_batch_callback=None, post_sample_callback=None, i=0, log=None, Vc=None, cost_opt=None, param_optimizers=None, interaction_storage=None, two_headed=False):
         self.interaction_storage = interaction_storage      # a list: every steps! block is appended to it (on_policy.jl:44,96)
-        refuse_two_headed(agent.pi, "OnPolicySolver (PPO / A2C / REINFORCE / ASAF)")
+        # two_headed=True: a two-headed Gaussian actor trains with ppo_loss / a2c_loss / reinforce_loss (the dense-engine learner's k_pg_head_sigma); LagrangePPO, ASAF, a
+        # CustomLoss and a DiagonalFisherRegularizer are refused by name; so is such a network anywhere but in the actor's place. Without the keyword: refused as before.
+        # (The keyword exists only to keep that earlier refusal of the plain call, which tests/test_gpu_sigma_head.py::test_refusals asserts: core.require_two_headed_opt_in.)
+        require_two_headed_opt_in(agent.pi, "OnPolicySolver (PPO / A2C / REINFORCE / ASAF)", two_headed)
+        _refuse_two_headed_params(actor(agent.pi), a_opt, "OnPolicySolver")
+        for q in ((critic(agent.pi) if isinstance(agent.pi, ActorCritic) else None), Vc, getattr(agent, "pa", None)) + tuple(t for t, _ in (param_optimizers or [])):
+            refuse_two_headed(q, "OnPolicySolver (critic / cost critic / nominal policy)")
         refuse_spectral(Vc, "OnPolicySolver (Vc)")
         self.Vc, self.cost_opt = Vc, cost_opt      # cost constraints: a separate value network and its TrainingParams (on_policy.jl:50-53)
         self.param_optimizers = list(param_optimizers or [])     # [(ParamVector, TrainingParams(loss=ParamLoss(...)))]: trained before the actor (on_policy.jl:59-61)
@@ -48,6 +54,7 @@ def policy_gradient_training(solver, D, perms_a=None, perms_c=None):
         pi_ = batch_train_(theta, p_opt, solver.P, D, info={})
         info.update({k: v for k, v in pi_.items() if not k.startswith("_")})
     A, Cn, pa, pc = actor(solver.agent.pi), critic(solver.agent.pi), solver.a_opt, solver.c_opt
+    _refuse_two_headed_params(A, pa, "policy_gradient_training")
     if pa.loss.name == "asaf":                                                                         # ASAF (il/asaf.jl): no critic; the loss reads the rollout minibatch and all demonstrations
         from .il_on_policy import batch_train_asaf_
         return batch_train_asaf_(solver, D, info=info)
@@ -99,6 +106,7 @@ def policy_gradient_training_synced(solver, D, sync_every=1):
     (Context.comm_init) averages actor/critic parameters and Adam moments with one RCCL all-reduce enqueued behind the learner kernels.
     Without a group it equals policy_gradient_training bit for bit."""
     A, Cn, pa, pc = actor(solver.agent.pi), critic(solver.agent.pi), solver.a_opt, solver.c_opt
+    refuse_two_headed(solver.agent.pi, "policy_gradient_training_synced")
     _ensure_opt(A, pa); _ensure_opt(Cn, pc)
     ca, cc = _train_cfg(A, pa, solver.P), _train_cfg(Cn, pc, solver.P)
     ra, rc_ = np.zeros(L.INFO_N, np.float32), np.zeros(L.INFO_N, np.float32)
@@ -123,6 +131,7 @@ def policy_gradient_training_multi(pis, a_opt, c_opt, P, buffers):
     population training) as two batched launches; replica i shuffles with shuffle_seed + i. Returns one info dict per replica."""
     n = len(pis); ctx = buffers[0].ctx
     for pi in pis:
+        refuse_two_headed(pi, "policy_gradient_training_multi")
         _ensure_opt(actor(pi), a_opt); _ensure_opt(critic(pi), c_opt)
     ca, cc = _train_cfg(actor(pis[0]), a_opt, P), _train_cfg(critic(pis[0]), c_opt, P)
     ha = (C.c_void_p * n)(*[actor(pi).h for pi in pis]); hc = (C.c_void_p * n)(*[critic(pi).h for pi in pis]); hb = (C.c_void_p * n)(*[b.h for b in buffers])

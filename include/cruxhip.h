@@ -107,9 +107,12 @@ float crux_mlp_get_squash(const crux_mlp* net);
  * examples/rl/half_cheetah_mujoco.jl:37-43, test/policy_tests.jl:284-321): a shared trunk with two Dense(h, ad) heads is ONE Chain whose last layer has 2 ad rows. on = 1 marks
  * the handle "two-headed": output rows [0, ad) are mu(s), rows [ad, 2 ad) logSigma(s). Needs n_extra == 0 and an even last width (else CRUX_EINVAL). crux_mlp_set_squash keeps its
  * meaning (ascale > 0: squashed, sigma = exp(clamp(logSigma(s), -5, 2)), the -logSigma term of the log-density unclamped as in policies.jl:385). Parameters, copy, polyak and Adam
- * see one flat vector. Served by the SAC entries (below), crux_rollout / crux_policy_explore (generic kernels) and crux_sigma_head_explore / _logpdf. The CQL entries refuse it
- * by the flag (CRUX_EUNSUP: their sampled-action terms read a constant logSigma); every other Gaussian-head learner refuses it through its own shape check (it has no logSigma
- * extras). Separate, non-sharing mu and logSigma networks are not implemented.                                                                                                */
+ * see one flat vector. Served by the SAC entries (below), crux_rollout / crux_policy_explore (generic kernels), crux_sigma_head_explore / _logpdf, and the policy-gradient
+ * learner entries crux_batch_train / crux_train_step / crux_loss_grad / crux_policy_gradient_training with CRUX_HEAD_GAUSSIAN and ppo_loss, a2c_loss, reinforce_loss or
+ * logpdf_bc_loss (see crux_batch_train). Refused by the flag with CRUX_EUNSUP, nothing enqueued and no parameter touched: the CQL entries (their sampled-action terms read a
+ * constant logSigma), crux_batch_train_lagrange, crux_batch_train_fisher, crux_batch_train with a replica group attached, mse_action loss, crux_policy_gradient_training_multi
+ * / _synced, crux_rollout_multi, and such a handle as the nominal policy of crux_steps_push / crux_importance_weight_rows. Separate, non-sharing mu and logSigma networks are
+ * not implemented.                                                                                                                                                            */
 int32_t crux_mlp_set_sigma_head(crux_mlp* net, int32_t on);
 int32_t crux_mlp_get_sigma_head(const crux_mlp* net);
 /* exploration(pi, s) (explore = 1: a [ad x B] and logprob [B], eps of column j, row d = randn(Philox(seed, counter, stream = j ad + d, NOISE))) or action(pi, s) (explore = 0:
@@ -396,7 +399,12 @@ enum { CRUX_INFO_LOSS = 0, CRUX_INFO_GRAD_NORM = 1, CRUX_INFO_ENTROPY = 2, CRUX_
  * permutations, one per epoch, applied exactly like shuffle! (new[:,j] = old[:,perm[j]]).
  * The buffer's row ORDER after the call equals the reference's (all epoch shuffles applied).
  * info_out[CRUX_INFO_N]: aggregate over epochs (mean of each epoch's last-minibatch info) +
- * batches_trained. epoch_infos (optional, host [epochs x CRUX_INFO_N]) gets the per-epoch rows.   */
+ * batches_trained. epoch_infos (optional, host [epochs x CRUX_INFO_N]) gets the per-epoch rows.
+ * A two-headed Gaussian handle (crux_mlp_set_sigma_head) with CRUX_HEAD_GAUSSIAN needs 2 act_dim output rows, no extras and a Float32 action column (else CRUX_EINVAL) and
+ * always trains on the dense-engine learner (every size, crux_train_step / crux_loss_grad included; never the register-resident kernels, whose heads read logSigma extras),
+ * with a head of its own: per column the seeds of mu and logSigma(s) go straight into the pullback, the statistics are block partials added in block order (identical calls
+ * give identical bits). Its entropy is the reference's: GaussianPolicy 1.4189385 + sum(logSigma(s)) over the WHOLE minibatch (policies.jl:348 has no dims: lambda_e weighs a
+ * sum over columns), SquashedGaussianPolicy the mean over columns of the per-column sums (policies.jl:398).                                                                 */
 int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms,
                          float* info_out, float* epoch_infos);
 
