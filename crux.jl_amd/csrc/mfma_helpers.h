@@ -1,6 +1,6 @@
 // mfma_helpers.h -- lane-level helpers shared by the MFMA learner kernels (gfx950).
 #pragma once
-#include "train_args.h"
+#include "learner_shapes.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -9,20 +9,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MF_TLD 36           // row stride of the exchange tiles [64 features][32 samples + 4 pad]
 #define EPS32F 1.1920928955078125e-07f
 
-enum { MFK_CATEGORICAL = 0, MFK_GAUSSIAN = 1, MFK_VALUE = 2 };
-
-// ---- host side: what the register-resident dispatchers (train_mfma*.hip, train_fs2.hip) share ----
-// The IN -> 64 -> 64 -> OUT family with an identity output layer. fs2 = k_train_fs2's wider test: a 32-wide second layer and a second activation of its own
-// are allowed too (the one- and two-CU forms take one activation for both hidden layers).
-static inline bool mf_family(const NetDesc& nd, bool fs2) {
-  if (nd.L != 3 || nd.dims[1] != MF_HID || nd.acts[2] != CRUX_ACT_IDENTITY) return false;
-  return fs2 ? (nd.dims[2] == 64 || nd.dims[2] == 32) : (nd.dims[2] == MF_HID && nd.acts[0] == nd.acts[1]);
-}
-// (loss, head) -> MFK_*, -1 = no kernel head for it. Which losses a dispatcher accepts is its own filter.
-static inline int mf_kind(int loss, int head) {
-  if (loss == CRUX_LOSS_VALUE_MSE) return MFK_VALUE;
-  return head == CRUX_HEAD_CATEGORICAL ? MFK_CATEGORICAL : head == CRUX_HEAD_GAUSSIAN ? MFK_GAUSSIAN : -1;
-}
+// ---- host side: what the register-resident dispatchers (train_mfma*.hip, train_fs2.hip) share beside the shape table ----
 // CRUX_MFMA_TIMING=1 (development): the timing instantiations write per-wave s_memtime totals of 16 phases into TrainArgs.dbg, row r at dbg[16 r].
 #define MF_TIMING_WORDS 512
 // The buffer: one per device (and dispatcher), allocated on first use; NULL = no memory.

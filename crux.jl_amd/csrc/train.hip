@@ -5,17 +5,23 @@
 //
 // This is the shape-generic kernel: every Dense layer is a loop, activations live in LDS in chunks of TR_CH samples,
 // parameters / moments stay in global memory (L2 resident). It is the correctness baseline and the fallback for shapes
-// the MFMA kernel (train_mfma.hip) does not cover. Both implement the same TrainArgs contract.
-#include "train_args.h"
+// the register-resident kernels (learner_shapes.h) do not cover. Both implement the same TrainArgs contract.
+#include "learner_route.h"
 #include <thread>
 #include "exec.h"
 #include "ops_small.h"
 
 int32_t crux_buffer_apply_order(crux_buffer* b, const int32_t* d_order, int64_t n);
 int32_t crux_buffer_apply_order_multi(int32_t n, crux_buffer* const* bufs, const int32_t* const* d_orders);
-int32_t crux_train_mfma_launch(crux_ctx* c, const TrainArgs& a, bool* handled, hipStream_t stream);
-int32_t crux_train_mfma_x2_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as, bool* handled, hipStream_t stream);   // train_mfma_x2.hip
-int32_t crux_train_mfma8_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as, bool* handled, hipStream_t stream);     // train_mfma8.hip
+// the launchers of the register-resident forms: `row` is the call's row of learner_shapes.h, the route (learner_route.h) has decided
+int32_t crux_launch_fs2(crux_ctx* c, const TrainArgs& a, const LearnerShape* row, hipStream_t stream);                   // train_fs2.hip
+int32_t crux_launch_x2(crux_ctx* c, const TrainArgs& a, const LearnerShape* row, hipStream_t stream);                    // train_mfma_x2.hip
+int32_t crux_launch_x2_multi(crux_ctx* c, std::vector<TrainArgs>& as, const LearnerShape* row, hipStream_t stream);
+int32_t crux_launch_one8(crux_ctx* c, const TrainArgs& a, const LearnerShape* row, hipStream_t stream);                  // train_mfma8.hip
+int32_t crux_launch_one8_multi(crux_ctx* c, std::vector<TrainArgs>& as, const LearnerShape* row, hipStream_t stream);
+int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm = nullptr, int which = 0, const crux_fisher* reg = nullptr);      // train_dense.hip
+extern "C" int crux_x2_placement_ok(crux_ctx* c);      // train_mfma_x2.hip; what the route reads of a context:
+static RouteEnv route_env(crux_ctx* c) { return RouteEnv{crux_sw(), c->learner_cus, crux_grouped(c), c->peer_every, [c]() { return crux_x2_placement_ok(c) != 0; }}; }
 
 #include "train_generic.h"
 __global__ __launch_bounds__(256) void k_train_generic(TrainArgs a) {
@@ -140,7 +146,6 @@ static int32_t build_orders(crux_ctx* c, crux_buffer* buf, int slot, const int32
   return crux_launch_check(c, "k_compose_order");
 }
 
-bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic, bool any_size = false);     // train_dense.hip
 // ---- packed learner rows --------------------------------------------------------------------------------------------------------------------
 // One line per transition with everything a policy-gradient / critic minibatch step reads of it: [s | action | logprob | advantage | return], padded to a power of two of
 // floats (C2: 8 floats = 32 B, C5: 32 floats = 128 B). Written once per batch_train! call (the columns do not change while the learners run; :advantage was whitened before);
@@ -184,76 +189,35 @@ static int32_t ensure_pack(crux_ctx* c, crux_buffer* buf, hipStream_t st, TrainA
     t->PACK = buf->pack; t->pack_stride = stride; t->pack_act = od; t->pack_lp = od + na; }
   return crux_launch_check(c, "k_pack_rows");
 }
-int32_t crux_train_dense_run(crux_ctx* c, TrainArgs& a, hipStream_t strm = nullptr, int which = 0, const crux_fisher* reg = nullptr);
-int32_t crux_train_fs_launch(crux_ctx* c, const TrainArgs& a, bool* handled, hipStream_t stream, bool probe);      // train_fs2.hip
-// reg (crux_batch_train_fisher): the regulariser rides in the dense-engine learner's chain only -- the register-resident family is skipped, every shape whose loss the dense
-// learner has takes that route, anything else is CRUX_EUNSUP (the host falls back to its seam)
+// the learner the route names, between the profile marks. reg (crux_batch_train_fisher): the regulariser rides in the dense-engine learner's chain only
 static int32_t launch_train(crux_ctx* c, TrainArgs& a, int prof_slot, hipStream_t stream = nullptr, const crux_fisher* reg = nullptr) {
-  bool handled = false;
   if (!stream) stream = c->stream;
-  const bool two = a.host_net && ((const crux_mlp*)a.host_net)->sigma_head;      // two-headed Gaussian actor: the dense-engine learner only, at every size
-  if (two) {      // never the register-resident kernels or the generic learner (a 3-64-64-2 handle has an instantiated shape by its dims): their heads read constant logSigma extras
-    if (reg) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a DiagonalFisherRegularizer: not implemented for a two-headed Gaussian actor (logSigma network)");
-    if (crux_grouped(c) && a.apply && !a.ids) return crux_fail(c, CRUX_EUNSUP, "batch_train! of a two-headed Gaussian actor (logSigma network) with a replica group attached is not implemented");
-    if (a.lag) return crux_fail(c, CRUX_EUNSUP, "lagrange_ppo_loss is not implemented for a two-headed Gaussian actor (logSigma network)");
-    if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false, true)) return crux_fail(c, CRUX_EUNSUP, "train!: a two-headed Gaussian actor trains with ppo_loss / a2c_loss / reinforce_loss / logpdf_bc_loss on the dense-engine learner only (loss %d, head %d)", a.loss, a.head);
-    a.need_px = 0; a.px_timeout = c->peer_timeout_ticks; a.px_every = 1;
-    const bool prof_t = stream == c->stream;
-    if (prof_t) crux_prof_begin(c, prof_slot);
-    const int32_t rct = crux_train_dense_run(c, a, stream, prof_t ? 0 : 1);
-    if (prof_t) crux_prof_end(c, prof_slot);
-    return rct;
-  }
-  if (reg) {
-    a.need_px = 0; a.px_timeout = c->peer_timeout_ticks; a.px_every = 1;
-    if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false, true)) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a DiagonalFisherRegularizer: the dense-engine learner has no loss %d / head %d for this handle", a.loss, a.head);
-    const bool prof_r = stream == c->stream;
-    if (prof_r) crux_prof_begin(c, prof_slot);
-    const int32_t rcr = crux_train_dense_run(c, a, stream, stream == c->stream ? 0 : 1, reg);
-    if (prof_r) crux_prof_end(c, prof_slot);
-    return rcr;
-  }
+  const RoutePlan plan = learner_route(route_env(c), a, reg != nullptr, a.ord_all != nullptr);
+  if (plan.code) return crux_fail(c, plan.code, "%s", plan.msg);
+  a.need_px = plan.need_px; a.px_every = plan.px_every; a.px_timeout = c->peer_timeout_ticks;
   const bool prof = stream == c->stream;      // HIP-event timing is kept on the context's main stream
   if (prof) crux_prof_begin(c, prof_slot);
-  // a replica group is attached (comm.hip "peer"): the per-minibatch gradient all-reduce lives in k_train_fs2's replica-group forms and in the dense-engine learner
-  // (train_dense.hip); a learner that would update its parameters through any other kernel is refused rather than trained un-synchronised (gradient-only /
-  // single-step calls stay local)
-  a.need_px = (crux_grouped(c) && a.apply && !a.ids) ? 1 : 0;
-  a.px_timeout = c->peer_timeout_ticks;
-  a.px_every = 1;
-  if (a.need_px && c->peer_every > 1) {      // periodic form: k_train_fs2<..., PX, PXK> only, and only where every replica provably takes the same number of steps
-    bool fs = false; int32_t prc = crux_train_fs_launch(c, a, &fs, stream, /*probe=*/true); if (prc) return prc;
-    if (!fs) return crux_fail(c, CRUX_EUNSUP, "peer sync_every = %d: the periodic exchange lives in the register-resident learner kernels (IN-64-{64,32}-OUT, 64 < batch <= 128); this learner has the per-step gradient exchange only", c->peer_every);
-    if (a.target_kl >= 0.f || a.max_batches > 0) return crux_fail(c, CRUX_EINVAL, "peer sync_every = %d: no KL early stopping / max_batches (the replicas' statistics are local between exchanges)", c->peer_every);
-    const int64_t nmb = (a.len + a.bs - 1) / a.bs;
-    if (nmb % c->peer_every != 0) return crux_fail(c, CRUX_EINVAL, "peer sync_every = %d must divide the %lld minibatches of an epoch (every call returns with identical replicas)", c->peer_every, (long long)nmb);
-    a.px_every = c->peer_every;
-  }
-  int32_t rc = crux_train_mfma_launch(c, a, &handled, stream);
-  if (rc) return rc;
-  const bool dense_ok = !handled && crux_train_dense_eligible(a, generic_lds_bytes(a.nd), crux_sw().force_generic);      // (on the second learner stream too: its own resource set)
-  if (a.need_px && !handled && !dense_ok) return crux_fail(c, CRUX_EUNSUP, "batch_train! with a replica group attached needs a learner with the gradient exchange (the register-resident kernels, or the dense-engine learner for other Chain(Dense...) shapes; not lagrange_ppo_loss): this learner would run un-synchronised");
-  if (dense_ok) {
-    // outside the register-resident family: the MFMA dense engine, one chain of tile GEMMs per minibatch (train_dense.hip)
-    rc = crux_train_dense_run(c, a, stream, stream == c->stream ? 0 : 1);
-    if (prof) crux_prof_end(c, prof_slot);
-    return rc;
-  }
-  if (!handled) {
-    // the generic learner is one workgroup of scalar loops: right for tiny networks and single steps, ~60x slower per minibatch than the MFMA family
-    // on anything 64 wide -- say so once instead of silently falling off the cliff
-    if (!a.ids && a.apply && a.nd.n_params >= 2048 && !crux_sw().force_generic && !crux_sw().quiet) {
-      static bool warned = false;
-      if (!warned) { warned = true; char shape[128]; int o = 0; for (int l = 0; l <= a.nd.L && o < 100; ++l) o += snprintf(shape + o, sizeof shape - o, l ? "-%d" : "%d", a.nd.dims[l]);
-        fprintf(stderr, "[cruxhip] batch_train!: network %s (batch %d, loss %d) is outside the MFMA learner family (IN-64-64-OUT with IN in {3,4,8,17}, batch <= 128) and not a case of the "
-                        "dense-engine learner (PPO / A2C / value losses): running the generic single-workgroup learner, 40-1000x slower per minibatch. (CRUX_QUIET=1 silences this.)\n", shape, a.bs, a.loss); }
+  int32_t rc = CRUX_OK;
+  switch (plan.route) {
+    case ROUTE_FS2: rc = crux_launch_fs2(c, a, plan.row, stream); break;
+    case ROUTE_X2: rc = crux_launch_x2(c, a, plan.row, stream); break;
+    case ROUTE_ONE8: rc = crux_launch_one8(c, a, plan.row, stream); break;
+    case ROUTE_DENSE: rc = crux_train_dense_run(c, a, stream, prof ? 0 : 1, reg); break;      // (on the second learner stream: its own resource set)
+    case ROUTE_GENERIC: {
+      // the generic learner is one workgroup of scalar loops: right for tiny networks and single steps, ~60x slower per minibatch than the MFMA family
+      // on anything 64 wide -- say so once instead of silently falling off the cliff
+      if (!a.ids && a.apply && a.nd.n_params >= 2048 && !crux_sw().force_generic && !crux_sw().quiet) {
+        static bool warned = false;
+        if (!warned) { warned = true; char shape[128]; int o = 0; for (int l = 0; l <= a.nd.L && o < 100; ++l) o += snprintf(shape + o, sizeof shape - o, l ? "-%d" : "%d", a.nd.dims[l]);
+          fprintf(stderr, "[cruxhip] batch_train!: network %s (batch %d, loss %d) is outside the MFMA learner family (%s, batch <= 128) and not a case of the "
+                          "dense-engine learner (PPO / A2C / value losses): running the generic single-workgroup learner, 40-1000x slower per minibatch. (CRUX_QUIET=1 silences this.)\n", shape, a.bs, a.loss, learner_family_text().c_str()); }
+      }
+      const size_t lds = generic_lds_bytes(a.nd);
+      static size_t attr_set = 0;
+      if (lds > 64 * 1024 && lds > attr_set) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = lds; }
+      hipLaunchKernelGGL(k_train_generic, dim3(1), dim3(256), lds, stream, a);
+      rc = crux_launch_check(c, "k_train_generic");
     }
-    const size_t lds = generic_lds_bytes(a.nd);
-    if (lds > 160 * 1024 - 64) return crux_fail(c, CRUX_EUNSUP, "train!: network too wide for the generic learner kernel (%zu B of LDS)", lds);
-    static size_t attr_set = 0;
-    if (lds > 64 * 1024 && lds > attr_set) { HIPCHK(c, hipFuncSetAttribute((const void*)k_train_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set = lds; }
-    hipLaunchKernelGGL(k_train_generic, dim3(1), dim3(256), lds, stream, a);
-    rc = crux_launch_check(c, "k_train_generic");
   }
   if (prof) crux_prof_end(c, prof_slot);
   return rc;
@@ -314,10 +278,8 @@ static int32_t upload_perms(crux_ctx* c, const int64_t* perms, int epochs, int64
 // copied in before the launch and back after it
 static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos, const crux_fisher* reg = nullptr) {
   crux_ctx* c = net->ctx;
-  if (net->sigma_head) {      // refused by name before anything is enqueued (cruxhip.h: two-headed handles)
-    const char* what = lag ? "lagrange_ppo_loss" : reg ? "a DiagonalFisherRegularizer" : crux_grouped(c) ? "a replica group attached" : nullptr;
-    if (what) return crux_fail(c, CRUX_EUNSUP, "batch_train! of a two-headed Gaussian actor (logSigma network) with %s is not implemented", what);
-  }
+  // refused by name before anything is enqueued (cruxhip.h: two-headed handles; lagrange_ppo_loss and the regulariser were refused by their entry points)
+  if (net->sigma_head && crux_grouped(c)) return crux_fail(c, CRUX_EUNSUP, "batch_train! of a two-headed Gaussian actor (logSigma network) with a replica group attached is not implemented");
   TrainArgs a; int32_t rc = fill_args(a, net, buf, cfg, lag ? CRUX_LOSS_PPO : cfg->loss); if (rc) return rc;
   if (lag) {
     if (!c->lag_dev) { if (hipMalloc(&c->lag_dev, 256) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "lagrange state"); }
@@ -579,9 +541,7 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
   const int64_t len = buf->elements; if (len >= ((int64_t)1 << 31)) return CRUX_EUNSUP;
   TrainArgs a, k; int32_t rc = fill_args(a, actor, buf, cfg_a, cfg_a->loss); if (rc) return rc;
   rc = fill_args(k, critic, buf, cfg_c, cfg_c->loss); if (rc) return rc;
-  a.ord_all = (const int32_t*)1; k.ord_all = (const int32_t*)1;      // (placeholders for the eligibility test: the orders are built below)
-  if (!crux_train_dense_eligible(a, generic_lds_bytes(a.nd), false) || !crux_train_dense_eligible(k, generic_lds_bytes(k.nd), false)) return CRUX_EUNSUP;
-  a.ord_all = nullptr; k.ord_all = nullptr;
+  if (!route_dense_takes(a, /*orders_ahead=*/true, false) || !route_dense_takes(k, true, false)) return CRUX_EUNSUP;      // (the orders are built below)
   { const int32_t rca = ensure_aux_stream(c); if (rca) return rca; }
   rc = pair_scratch(c, len, cfg_a, cfg_c, perms_a, perms_c, a, k, 0, nullptr); if (rc) return rc;
   rc = pair_orders(c, buf, cfg_a, cfg_c, a, k); if (rc) return rc;
@@ -598,6 +558,10 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
   return pair_tail(c, buf, k, cfg_c->epochs, info_c, epoch_infos_c, sta, "learner");
 }
 
+// the pair driver's test by widths alone (not the table): IN-64-64-OUT, or IN-64-32-OUT while the feature-split kernel may run. A pair inside it that the feature-split
+// kernel is not asked about (small minibatches, CRUX_FS=0, learner_cus) goes to the two learner streams through launch_train, whatever its route
+static bool pair_widths(const NetDesc& d, bool fs_on) { return d.L == 3 && d.dims[1] == 64 && (d.dims[2] == 64 || (d.dims[2] == 32 && fs_on)); }
+
 extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
                                                  const int64_t* perms_a, const int64_t* perms_c, float* info_a, float* info_c, float* epoch_infos_a, float* epoch_infos_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c) return CRUX_EINVAL;
@@ -610,14 +574,12 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
   // actor does not stop. CRUX_SPEC_PAIR=0: the sequential order.
   bool spec = !exact && cfg_a->target_kl >= 0.f && cfg_a->max_batches <= 0 && cfg_c->max_batches <= 0 && CRUX_IS_PG(cfg_a->loss) && cfg_c->loss == CRUX_LOSS_VALUE_MSE && !crux_grouped(c) &&
               buf->elements < ((int64_t)1 << 31) && crux_sw().spec_pair;
+  TrainArgs a, k; bool filled = false;
   { const bool fs_on = (crux_sw().fs != 0) && cfg_a->batch_size > 64 && cfg_a->batch_size <= 128;      // the feature-split kernel also takes a 32-wide second layer
-    auto mfma_family = [fs_on](const crux_mlp* n) { const NetDesc& d = n->nd; return d.L == 3 && d.dims[1] == 64 && (d.dims[2] == 64 || (d.dims[2] == 32 && fs_on)); };
-    bool family = mfma_family(actor) && mfma_family(critic) && !actor->sigma_head && !critic->sigma_head;      // (a two-headed actor: the dense engine's pair, or one learner after the other)
-    if (family && (exact || spec) && fs_on && c->learner_cus == 0 && buf->elements >= cfg_a->batch_size && cfg_a->batch_size == cfg_c->batch_size) {      // 64 wide, but does a register-resident kernel instantiate these shapes?
-      TrainArgs pa, pk; bool ha = false, hk = false;
-      if (!fill_args(pa, actor, buf, cfg_a, cfg_a->loss) && !fill_args(pk, critic, buf, cfg_c, cfg_c->loss)) { pa.need_px = pk.need_px = crux_grouped(c) ? 1 : 0;
-        (void)crux_train_fs_launch(c, pa, &ha, c->stream, true); (void)crux_train_fs_launch(c, pk, &hk, c->stream, true);
-        if (!ha || !hk) family = false; } }      // no: the dense engine's pair below instead of one learner after the other
+    bool family = pair_widths(actor->nd, fs_on) && pair_widths(critic->nd, fs_on) && !actor->sigma_head && !critic->sigma_head;      // (a two-headed actor: the dense engine's pair, or one learner after the other)
+    if (family && (exact || spec) && fs_on && c->learner_cus == 0 && buf->elements >= cfg_a->batch_size && cfg_a->batch_size == cfg_c->batch_size) {      // 64 wide, but does the feature-split kernel take both?
+      filled = !fill_args(a, actor, buf, cfg_a, cfg_a->loss) && !fill_args(k, critic, buf, cfg_c, cfg_c->loss);
+      if (filled) { const RouteEnv env = route_env(c); if (!route_fs2_takes(env, a) || !route_fs2_takes(env, k)) family = false; } }      // no: the dense engine's pair below instead of one learner after the other
     else spec = false;                           // (the abort latch lives in the feature-split kernel only)
     if (!family) spec = false;
     if (!family) {
@@ -633,8 +595,9 @@ extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* crit
   }
   if (buf->elements <= 0 || cfg_a->epochs < 1 || cfg_c->epochs < 1) return crux_fail(c, CRUX_EINVAL, "policy_gradient_training: empty buffer or epochs < 1");
   { const int32_t rca = ensure_aux_stream(c); if (rca) return rca; }
-  TrainArgs a, k; int32_t rc = fill_args(a, actor, buf, cfg_a, cfg_a->loss); if (rc) return rc;
-  rc = fill_args(k, critic, buf, cfg_c, cfg_c->loss); if (rc) return rc;
+  int32_t rc = CRUX_OK;
+  if (!filled) { rc = fill_args(a, actor, buf, cfg_a, cfg_a->loss); if (rc) return rc;
+    rc = fill_args(k, critic, buf, cfg_c, cfg_c->loss); if (rc) return rc; }
   const int64_t len = buf->elements;
   const size_t np_c = (size_t)critic->nd.n_params, snap = spec ? Carve::span<char>(3 * 4 * np_c + 64) : 0;      // speculative start: the critic's parameters, Adam moments and beta powers as they are now
   char* snap_at = nullptr;
@@ -737,9 +700,9 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
   // peer that is waiting for its CU, so that size always takes the one-CU form
   const bool one_cu = c->learner_cus == 1 || n > 64;
   auto launch_many = [&](std::vector<TrainArgs>& v, hipStream_t st, bool* h) -> int32_t {
-    *h = false; int32_t r = CRUX_OK;
-    if (!one_cu) { r = crux_train_mfma_x2_launch_multi(c, v, h, st); if (r || *h) return r; }
-    return crux_train_mfma8_launch_multi(c, v, h, st);
+    LearnerRoute form = ROUTE_ONE8; const LearnerShape* row = learner_route_multi(route_env(c), v[0], one_cu, &form);
+    *h = row != nullptr; if (!row) return CRUX_OK;
+    return form == ROUTE_X2 ? crux_launch_x2_multi(c, v, row, st) : crux_launch_one8_multi(c, v, row, st);
   };
   bool handled = false;
   rc = launch_many(ks, c->aux_stream, &handled); if (rc) return rc;

@@ -55,6 +55,15 @@ inline void train_args_net(TrainArgs& a, const crux_mlp* net) {
   a.nd = net->nd; a.p = net->p; a.g = net->g; a.m = net->m; a.v = net->v; a.bp = net->bp; a.eta = net->eta; a.b1 = net->b1; a.b2 = net->b2; a.eps = net->eps;
 }
 
+#define CRUX_MAXEXTRA 64      // logSigma entries a Gaussian head may carry on the dense-engine learner (train_dense.hip; act_dim <= 64, as in check_sac)
+#define TR_CH 32
+// dynamic LDS of the generic learner (train_generic.h: train_generic_run) for a network: the carve at the top of its body, in bytes
+static size_t generic_lds_bytes(const NetDesc& nd) {
+  size_t fl = 0; for (int l = 0; l <= nd.L; ++l) fl += (size_t)nd.dims[l] * TR_CH;
+  fl += 2 * (size_t)nd.maxdim * TR_CH + (size_t)TR_CH * (nd.n_extra > 0 ? nd.n_extra : 1);
+  return fl * sizeof(float);
+}
+
 // The minibatch rows are device global memory. Typing the per-step loads as address_space(1) makes them global_load instead of the flat_load a
 // generic pointer compiles to: flat accesses also count on lgkmcnt, so every LDS wait after the prefetch of the next minibatch was issued
 // waited for that prefetch as well (an L2 round trip per step), and their 64-bit addresses cost extra VALU adds.

@@ -11,7 +11,6 @@
 #include "train_args.h"
 #include "peer_wait.h"
 #include "mfma_helpers.h"      // EPS32F
-#define CRUX_MAXEXTRA 64      // logSigma entries a Gaussian head may carry here (act_dim <= 64, as in check_sac)
 
 __global__ void k_gather_obs(const float* __restrict__ S, int od, const int32_t* __restrict__ rows, int64_t nb, float* __restrict__ x) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; if (i >= nb * od) return;
@@ -206,8 +205,6 @@ __global__ void k_pg_info_sigma(const double* __restrict__ part, int nblk, doubl
   dinfo[CRUX_INFO_CLIP_FRACTION] = (float)st[5] / (float)nb; dinfo[CRUX_INFO_AVG_ADVANTAGE] = (float)(st[3] / (double)nb); dinfo[CRUX_INFO_AVG_RETURN] = (float)(st[4] / (double)nb);
   dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]);
 }
-static inline bool train_two_headed(const TrainArgs& a) { return a.host_net && ((const crux_mlp*)a.host_net)->sigma_head; }
-
 // Replica group (comm.hip "peer") for the dense-engine learner: the SUM all-reduce of the flat minibatch gradient (and of the head's eight statistics sums) between the pullback
 // (training.jl:18) and Flux.update! (:21) as ONE launch of one workgroup, in chunks of a peer slot: chunk k is exchange number x0 + k of this learner stream -- written into
 // slot [parity][my rank] of every peer, system-scope release, flag, wait for the N - 1 flags in the own region, acquire, add the N contributions in rank order (the own one from
@@ -257,19 +254,7 @@ __global__ __launch_bounds__(1024) void k_px_allreduce_flat(float* __restrict__ 
 
 __global__ void k_nan_status(const double* __restrict__ ssq, int32_t* __restrict__ status) { if (isnan(ssq[0])) status[0] = CRUX_ENAN; }   // gradient-only calls: the NaN check of training.jl:20 without the update
 
-// which learners take this path (called by launch_train after the MFMA family declined)
-// any_size: a regularised chain (crux_batch_train_fisher) -- no other learner carries the regulariser, so the size thresholds do not apply
-bool crux_train_dense_eligible(const TrainArgs& a, size_t generic_lds, bool force_generic, bool any_size) {
-  if (!a.host_net || !(a.ids || a.ord_all)) return false;
-  if (!(CRUX_IS_PG(a.loss) || a.loss == CRUX_LOSS_VALUE_MSE || (a.loss == CRUX_LOSS_MSE_ACTION && a.squash == 0.f))) return false;
-  if (CRUX_IS_PG(a.loss) && a.head != CRUX_HEAD_CATEGORICAL && a.head != CRUX_HEAD_GAUSSIAN) return false;
-  if (a.nd.L < 1 || a.nd.n_extra > CRUX_MAXEXTRA) return false;
-  if (train_two_headed(a)) return CRUX_IS_PG(a.loss) && a.head == CRUX_HEAD_GAUSSIAN;      // no other learner has the two-headed head (k_pg_head_sigma): every size, single steps included
-  if (any_size) return true;
-  if (generic_lds > 160 * 1024 - 64) return true;                                   // the generic learner cannot hold it at all
-  return !force_generic && a.nd.n_params >= 512 && a.bs >= 32 && !a.ids;            // single steps and tiny networks (the README's 2-8-4) stay on the one-launch generic learner
-}
-
+// (which calls take this path: learner_route.h)
 // `strm` / `which`: the stream the chain runs on and the resource set it uses (0: the context's main stream; 1: the second learner stream -- policy_gradient_training runs the
 // critic's chain there, from a second host thread, beside the actor's: both chains are launch-bound, two queues interleave them on the device).
 // reg (or NULL): the DiagonalFisherRegularizer of this network (fisher.hip) -- per minibatch its gradient joins the pullback's before the norm and its value the info row's loss

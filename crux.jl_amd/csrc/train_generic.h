@@ -3,14 +3,6 @@
 #include "train_args.h"
 #include "mfma_helpers.h"      // EPS32F
 
-#define TR_CH 32
-// dynamic LDS of train_generic_run for a network: the carve at the top of its body, in bytes
-static size_t generic_lds_bytes(const NetDesc& nd) {
-  size_t fl = 0; for (int l = 0; l <= nd.L; ++l) fl += (size_t)nd.dims[l] * TR_CH;
-  fl += 2 * (size_t)nd.maxdim * TR_CH + (size_t)TR_CH * (nd.n_extra > 0 ? nd.n_extra : 1);
-  return fl * sizeof(float);
-}
-
 __device__ __forceinline__ double block_sum_d(double v, double* red, int tid) {
   // 256 threads = 4 waves. Deterministic: wave butterfly then fixed-order sum of 4 partials.
   v = wave_sum_d(v);

@@ -5,12 +5,19 @@
 
 // ---- dispatch ---------------------------------------------------------------------------------------------------
 template <int IN, int OUT, int KIND, int ACT, bool TIMING = false>
-static int32_t launch_one8(crux_ctx* c, const TrainArgs& a, hipStream_t stream) {
+static int32_t launch_one8(crux_ctx* c, TrainArgs a, hipStream_t stream) {
   using Lt = MfLayout<IN, OUT, 8>;
   constexpr size_t lds = sizeof(float) * (size_t)Lt::TOTAL;
   { const int32_t rc = crux_lds_attr_once<k_train_mfma<IN, OUT, KIND, ACT, 8, 1, TIMING>>(c, lds); if (rc) return rc; }
+  if constexpr (TIMING) { a.dbg = mf_timing_buf(c); if (!a.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer"); }      // CRUX_MFMA_TIMING=1 (development, the LF_ONE8_TIMING row)
   hipLaunchKernelGGL((k_train_mfma<IN, OUT, KIND, ACT, 8, 1, TIMING>), dim3(1), dim3(512), lds, stream, a, (const TrainArgs*)nullptr);
-  return crux_launch_check(c, TIMING ? "k_train_mfma<8,1,timing>" : "k_train_mfma<8,1>");
+  const int32_t rc = crux_launch_check(c, TIMING ? "k_train_mfma<8,1,timing>" : "k_train_mfma<8,1>");
+  if constexpr (TIMING) {      // per-phase s_memtime totals of waves 0, 3 and 6
+    if (rc) return rc;
+    MfTimingRow rows[3];
+    for (int i = 0; i < 3; ++i) { rows[i].row = 3 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[one-cu-timing] wave %d:", 3 * i); }
+    return mf_timing_dump(c, stream, rows, 3);
+  } else return rc;
 }
 
 // n independent learners, one CU each (grid n): argument blocks uploaded to a per-stream device array
@@ -32,40 +39,19 @@ static int32_t launch_multi8(crux_ctx* c, std::vector<TrainArgs>& as, hipStream_
   return crux_launch_check(c, "k_train_mfma<8,1> (multi)");
 }
 
-int32_t crux_train_mfma8_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as, bool* handled, hipStream_t stream) {
-  *handled = false;
-  if (as.empty()) return CRUX_OK;
-  const TrainArgs& a = as[0]; const NetDesc& nd = a.nd;
-  if (!mf_family(nd, false) || a.ids || !a.apply || a.bs > 128 || a.len < a.bs) return CRUX_OK;
-  const int in = nd.dims[0], out = nd.dims[3], act = nd.acts[0];
-  const int kind = mf_kind(a.loss, a.head);
-  if (!(a.loss == CRUX_LOSS_VALUE_MSE || CRUX_IS_PG(a.loss)) || kind < 0) return CRUX_OK;
-#define MF8M_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_multi8<I, O, K, A_>(c, as, stream); }
-  MF8M_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
-  MF8M_CASE(4, 1, MFK_VALUE, CRUX_ACT_RELU)
-  MF8M_CASE(3, 1, MFK_GAUSSIAN, CRUX_ACT_RELU)
-  MF8M_CASE(3, 1, MFK_VALUE, CRUX_ACT_RELU)
-#undef MF8M_CASE
-  return CRUX_OK;
+// launch_train's ROUTE_ONE8 and the population launch (learner_route.h decided; `row` is the call's row of the table)
+int32_t crux_launch_one8(crux_ctx* c, const TrainArgs& a, const LearnerShape* row, hipStream_t stream) {
+  const bool timing = crux_sw().mfma_timing;
+#define ONE8_ROW(I, O, K, A_, H, A2, F) if constexpr (((F) & LF_ONE8) != 0) if (row->is(I, O, K, A_, H, A2)) { \
+    if constexpr (((F) & LF_ONE8_TIMING) != 0) if (timing) return launch_one8<I, O, K, A_, true>(c, a, stream); \
+    return launch_one8<I, O, K, A_>(c, a, stream); }
+  CRUX_LEARNER_SHAPES(ONE8_ROW)
+#undef ONE8_ROW
+  return crux_fail(c, CRUX_EINVAL, "k_train_mfma<8,1>: no instantiation for this shape");
 }
-
-// Called by crux_train_mfma_launch after its shape checks; handles the narrow-input members of the family.
-int32_t crux_train_mfma8_launch(crux_ctx* c, const TrainArgs& a, int kind, bool* handled, hipStream_t stream) {
-  *handled = false;
-  const int in = a.nd.dims[0], out = a.nd.dims[3], act = a.nd.acts[0];
-  if (crux_sw().mfma_timing && in == 4 && out == 2 && kind == MFK_CATEGORICAL && act == CRUX_ACT_RELU) {      // CRUX_MFMA_TIMING=1: per-phase s_memtime totals of the C2 actor (development)
-    TrainArgs b = a; b.dbg = mf_timing_buf(c); *handled = true;
-    if (!b.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
-    const int32_t rc = launch_one8<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, true>(c, b, stream); if (rc) return rc;
-    MfTimingRow rows[3];
-    for (int i = 0; i < 3; ++i) { rows[i].row = 3 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[one-cu-timing] wave %d:", 3 * i); }
-    return mf_timing_dump(c, stream, rows, 3);
-  }
-#define MF8_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_one8<I, O, K, A_>(c, a, stream); }
-  MF8_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)     // C2 actor  (PPO CartPole)
-  MF8_CASE(4, 1, MFK_VALUE, CRUX_ACT_RELU)           // C2 critic
-  MF8_CASE(3, 1, MFK_GAUSSIAN, CRUX_ACT_RELU)        // Pendulum actor
-  MF8_CASE(3, 1, MFK_VALUE, CRUX_ACT_RELU)           // Pendulum critic
-#undef MF8_CASE
-  return CRUX_OK;
+int32_t crux_launch_one8_multi(crux_ctx* c, std::vector<TrainArgs>& as, const LearnerShape* row, hipStream_t stream) {
+#define ONE8M_ROW(I, O, K, A_, H, A2, F) if constexpr (((F) & LF_ONE8_MULTI) != 0) if (row->is(I, O, K, A_, H, A2)) return launch_multi8<I, O, K, A_>(c, as, stream);
+  CRUX_LEARNER_SHAPES(ONE8M_ROW)
+#undef ONE8M_ROW
+  return crux_fail(c, CRUX_EINVAL, "k_train_mfma<8,1> (multi): no instantiation for this shape");
 }

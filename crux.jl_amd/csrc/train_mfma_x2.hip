@@ -8,8 +8,6 @@ __global__ void k_xcc_probe(uint32_t* out) {
   uint32_t id; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
   if (threadIdx.x == 0) out[blockIdx.x] = id & 0xf;
 }
-extern "C" int crux_x2_placement_ok(crux_ctx* c);
-static int x2_placement_ok(crux_ctx* c) { return crux_x2_placement_ok(c); }
 // also called when a replica group is attached: the probe ends in a hipFree, which waits for the whole device -- it must not run for the first time
 // while a peer replica on the same device already spins in its learner kernel
 extern "C" int crux_x2_placement_ok(crux_ctx* c) {
@@ -49,7 +47,14 @@ static int32_t launch_x2(crux_ctx* c, TrainArgs a, hipStream_t stream) {
   a.xbuf = (float*)c->xbuf[which]; a.xctr = (unsigned*)((char*)c->xbuf[which] + sizeof(float) * CRUX_XBUF_FLOATS);
   HIPCHK(c, hipMemsetAsync(a.xctr, 0, 256, stream));
   if constexpr (KIND != MFK_VALUE && !TIMING) { if (a.lag) return launch_x2_form<IN, OUT, KIND, ACT, false, true>(c, a, lds, stream); }      // lagrange_ppo_loss (ppo.jl:70-131)
-  return launch_x2_form<IN, OUT, KIND, ACT, TIMING>(c, a, lds, stream);
+  if constexpr (TIMING) {      // CRUX_MFMA_TIMING=1 (development, the LF_X2_TIMING rows): the per-phase totals of wave 0 of both workgroups
+    a.dbg = mf_timing_buf(c);
+    if (!a.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
+    const int32_t rc = launch_x2_form<IN, OUT, KIND, ACT, true>(c, a, lds, stream); if (rc) return rc;
+    MfTimingRow rows[2];
+    for (int i = 0; i < 2; ++i) { rows[i].row = 4 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[x2-timing] %d-%d wg %d wave 0:", IN, OUT, i); }
+    return mf_timing_dump(c, stream, rows, 2);
+  } else return launch_x2_form<IN, OUT, KIND, ACT, false>(c, a, lds, stream);
 }
 
 // n independent learners in one launch (grid 16 n): argument blocks uploaded to a per-stream device array, one exchange area each
@@ -76,62 +81,19 @@ static int32_t launch_x2_multi(crux_ctx* c, std::vector<TrainArgs>& as, hipStrea
   return crux_launch_check(c, "k_train_mfma<4,2> (multi)");
 }
 
-int32_t crux_train_mfma_x2_launch_multi(crux_ctx* c, std::vector<TrainArgs>& as, bool* handled, hipStream_t stream) {
-  *handled = false;
-  if (as.empty() || !x2_placement_ok(c)) return CRUX_OK;
-  const TrainArgs& a = as[0];
-  const NetDesc& nd = a.nd;
-  if (!mf_family(nd, false) || a.ids || !a.apply || a.bs <= 64 || a.bs > 128 || a.len < a.bs) return CRUX_OK;
-  const int in = nd.dims[0], out = nd.dims[3], act = nd.acts[0];
-  const int kind = mf_kind(a.loss, a.head);
-  if (!(a.loss == CRUX_LOSS_VALUE_MSE || CRUX_IS_PG(a.loss)) || kind < 0) return CRUX_OK;
-#define MFXM_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2_multi<I, O, K, A_>(c, as, stream); }
-  MFXM_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
-  MFXM_CASE(4, 1, MFK_VALUE, CRUX_ACT_RELU)
-  MFXM_CASE(17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH)
-  MFXM_CASE(17, 1, MFK_VALUE, CRUX_ACT_TANH)
-#undef MFXM_CASE
-  return CRUX_OK;
+// launch_train's ROUTE_X2 and the population launch (learner_route.h decided; `row` is the call's row of the table). With lagrange_ppo_loss the LAG form, never the timers
+int32_t crux_launch_x2(crux_ctx* c, const TrainArgs& a, const LearnerShape* row, hipStream_t stream) {
+  const bool timing = !a.lag && crux_sw().mfma_timing;
+#define X2_ROW(I, O, K, A_, H, A2, F) if constexpr (((F) & LF_X2) != 0) if (row->is(I, O, K, A_, H, A2)) { \
+    if constexpr (((F) & LF_X2_TIMING) != 0) if (timing) return launch_x2<I, O, K, A_, true>(c, a, stream); \
+    return launch_x2<I, O, K, A_>(c, a, stream); }
+  CRUX_LEARNER_SHAPES(X2_ROW)
+#undef X2_ROW
+  return crux_fail(c, CRUX_EINVAL, "k_train_mfma<4,2>: no instantiation for this shape");
 }
-
-// Called by crux_train_mfma_launch after its shape checks, before the single-CU kernels.
-// any_mode = false: only full minibatch loops of 65..128 rows (where two CUs pay); true: also single steps, gradient-only calls and small minibatches
-// (workgroup 1 then idles on empty tiles) -- used for the shapes that have no one-CU instantiation.
-int32_t crux_train_mfma_x2_launch(crux_ctx* c, const TrainArgs& a, int kind, bool* handled, hipStream_t stream, bool any_mode) {
-  *handled = false;
-  if (!crux_sw().mfma_x2) return CRUX_OK;
-  if (crux_grouped(c) && a.need_px) return CRUX_OK;      // no replica-group form: grouped updates run on k_train_fs2 or the dense-engine learner
-  if (!any_mode && (a.ids || !a.apply || a.bs <= 64 || a.len < a.bs)) return CRUX_OK;     // single steps and small batches stay on one CU when it has the shape
-  if (!x2_placement_ok(c)) return CRUX_OK;
-  const int in = a.nd.dims[0], out = a.nd.dims[3], act = a.nd.acts[0];
-  if (a.lag) {     // lagrange_ppo_loss: its own instantiations, for the shapes below; every other shape stays on the dense-engine learner
-#define MFXL_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2<I, O, K, A_>(c, a, stream); }
-    MFXL_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)
-    MFXL_CASE(8, 4, MFK_CATEGORICAL, CRUX_ACT_RELU)
-    MFXL_CASE(3, 1, MFK_GAUSSIAN, CRUX_ACT_RELU)
-    MFXL_CASE(17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH)
-#undef MFXL_CASE
-    return CRUX_OK;
-  }
-  if (crux_sw().mfma_timing && ((in == 4 && out == 2 && kind == MFK_CATEGORICAL && act == CRUX_ACT_RELU) || (in == 17 && out == 6 && kind == MFK_GAUSSIAN && act == CRUX_ACT_TANH))) {
-    TrainArgs b = a; b.dbg = mf_timing_buf(c); *handled = true;
-    if (!b.dbg) return crux_fail(c, CRUX_ENOMEM, "timing buffer");
-    const int32_t rc = in == 4 ? launch_x2<4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU, true>(c, b, stream) : launch_x2<17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH, true>(c, b, stream); if (rc) return rc;
-    MfTimingRow rows[2];
-    for (int i = 0; i < 2; ++i) { rows[i].row = 4 * i; rows[i].names = MF_PHASES; snprintf(rows[i].label, sizeof rows[i].label, "[x2-timing] %d-%d wg %d wave 0:", in, out, i); }
-    return mf_timing_dump(c, stream, rows, 2);
-  }
-#define MFX_CASE(I, O, K, A_) if (in == I && out == O && kind == K && act == A_) { *handled = true; return launch_x2<I, O, K, A_>(c, a, stream); }
-  MFX_CASE(4, 2, MFK_CATEGORICAL, CRUX_ACT_RELU)     // C2 actor  (PPO CartPole)
-  MFX_CASE(4, 1, MFK_VALUE, CRUX_ACT_RELU)           // C2 critic
-  MFX_CASE(3, 1, MFK_GAUSSIAN, CRUX_ACT_RELU)        // Pendulum actor
-  MFX_CASE(3, 1, MFK_VALUE, CRUX_ACT_RELU)           // Pendulum critic
-  MFX_CASE(17, 6, MFK_GAUSSIAN, CRUX_ACT_RELU)       // C5 actor  (PPO HalfCheetah-shaped, 17 obs / 6 act): 4 waves per workgroup keep the 17-wide layout inside 160 KB
-  MFX_CASE(17, 6, MFK_GAUSSIAN, CRUX_ACT_TANH)
-  MFX_CASE(17, 1, MFK_VALUE, CRUX_ACT_RELU)          // C5 critic
-  MFX_CASE(17, 1, MFK_VALUE, CRUX_ACT_TANH)
-  MFX_CASE(8, 4, MFK_CATEGORICAL, CRUX_ACT_RELU)     // 8 observations / 4 discrete actions (LunarLander-shaped, the C3 environment under an on-policy learner)
-  MFX_CASE(8, 1, MFK_VALUE, CRUX_ACT_RELU)
-#undef MFX_CASE
-  return CRUX_OK;
+int32_t crux_launch_x2_multi(crux_ctx* c, std::vector<TrainArgs>& as, const LearnerShape* row, hipStream_t stream) {
+#define X2M_ROW(I, O, K, A_, H, A2, F) if constexpr (((F) & LF_X2_MULTI) != 0) if (row->is(I, O, K, A_, H, A2)) return launch_x2_multi<I, O, K, A_>(c, as, stream);
+  CRUX_LEARNER_SHAPES(X2M_ROW)
+#undef X2M_ROW
+  return crux_fail(c, CRUX_EINVAL, "k_train_mfma<4,2> (multi): no instantiation for this shape");
 }

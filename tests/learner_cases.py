@@ -2,8 +2,9 @@
 
 Host only: nothing here needs a device until Case.gpu_net() / whole_epoch_windows(g=...) are called (tests/test_learner_cases.py uses the oracle alone).
 
-  FS2_ROWS / MFX_ROWS / MF8_ROWS   the closed shape lists of the three dispatchers as data: (in, out, kind, act1, h2, act2); test_learner_cases.py parses the .hip files and
-                                    requires equality, so a dispatcher row added without a case fails without a GPU
+  FS2_ROWS / MFX_ROWS / MF8_ROWS   the closed shape lists of the three dispatchers as data: (in, out, kind, act1, h2, act2); test_learner_cases.py parses the one table
+                                    they instantiate from (csrc/learner_shapes.h: the LF_FS2 / LF_X2 / LF_ONE8 flags of its rows) and requires equality -- FS2_ROWS in the
+                                    table's order, which the (bs, r) schedule counts in --, so a row added without a case fails without a GPU
   make_case(row, bs, r, seed)       oracle network + buffer data of N = 3 bs + r rows whose :logprob column is CONSISTENT with the network: the float64 log-density of the freshly
                                     initialised policy at the stored action plus N(0, LOGPROB_SIGMA). The older window tests draw logprob ~ N(-1.2, 0.05) whatever the action
                                     dimension; at 4..8 Gaussian actions the true density is near -10, every ratio is e^-9, every row is clipped and the surrogate contributes
@@ -29,7 +30,7 @@ def _r(i, o, k, a, h2=64, a2=None):
     return (i, o, k, a, h2, a if a2 is None else a2)
 
 
-# train_fs2.hip: FS2_CASE(I, O, K, A) = FS2_CASE2(I, O, K, A, 64, A), in the order of the file
+# learner_shapes.h: every row (all carry LF_FS2), in the order of the file
 FS2_ROWS = [_r(4, 2, CAT, RELU), _r(4, 1, VAL, RELU), _r(17, 6, GAU, TANH), _r(17, 1, VAL, TANH),
             _r(3, 1, GAU, RELU), _r(3, 1, VAL, RELU), _r(17, 6, GAU, RELU), _r(17, 1, VAL, RELU), _r(8, 4, CAT, RELU), _r(8, 1, VAL, RELU), _r(2, 1, GAU, RELU), _r(2, 1, VAL, RELU),
             _r(6, 3, CAT, RELU), _r(6, 1, VAL, RELU), _r(2, 3, CAT, RELU),
@@ -38,10 +39,10 @@ FS2_ROWS = [_r(4, 2, CAT, RELU), _r(4, 1, VAL, RELU), _r(17, 6, GAU, TANH), _r(1
             _r(24, 4, GAU, RELU), _r(24, 4, GAU, TANH), _r(24, 1, VAL, RELU), _r(24, 1, VAL, TANH),
             _r(27, 8, GAU, RELU), _r(27, 8, GAU, TANH), _r(27, 1, VAL, RELU), _r(27, 1, VAL, TANH),
             _r(17, 6, GAU, TANH, 32, TANH), _r(17, 1, VAL, TANH, 32, IDENT), _r(17, 1, VAL, TANH, 32, TANH)]
-# train_mfma_x2.hip: MFX_CASE(I, O, K, A): the two-CU form, 64-64 hidden
+# the LF_X2 rows: the two-CU form, 64-64 hidden (this order feeds case ids)
 MFX_ROWS = [_r(4, 2, CAT, RELU), _r(4, 1, VAL, RELU), _r(3, 1, GAU, RELU), _r(3, 1, VAL, RELU), _r(17, 6, GAU, RELU), _r(17, 6, GAU, TANH), _r(17, 1, VAL, RELU), _r(17, 1, VAL, TANH),
             _r(8, 4, CAT, RELU), _r(8, 1, VAL, RELU)]
-# train_mfma8.hip: MF8_CASE(I, O, K, A): the one-CU form
+# the LF_ONE8 rows: the one-CU form
 MF8_ROWS = [_r(4, 2, CAT, RELU), _r(4, 1, VAL, RELU), _r(3, 1, GAU, RELU), _r(3, 1, VAL, RELU)]
 # small minibatches and single steps: the one-CU kernel where it has the shape, the two-CU kernel's any-mode path for the 17- and 8-wide rows
 SMALL_ROWS = MF8_ROWS + [r for r in MFX_ROWS if r not in MF8_ROWS]
@@ -60,7 +61,7 @@ M_SHIFT_MIN = 5e-5        # sensitivity: dropping ONE row must move Adam's m by 
 SEED_OVERRIDES = {(12, 128, 1): 7707}      # 6-3 categorical at a tail of one row: the default draw moved m by 4.4e-5
 
 
-# The rule "row i takes pairs (3 i + j) % 12" gives a row the offset 3 (i % 4), and the file order of train_fs2.hip alternates policies and critics: every row with
+# The rule "row i takes pairs (3 i + j) % 12" gives a row the offset 3 (i % 4), and the order of the table alternates policies and critics: every row with
 # i % 4 == 1 is a critic, the four categorical rows sit at i % 4 in {0, 0, 0, 2}, no Gaussian row at i % 4 == 1 and no critic at i % 4 == 2. The rule alone therefore cannot
 # meet "every pair under every head"; these rows take the missing pairs IN ADDITION to their own three (nothing of the rule is dropped): 99 + 12 = 111 cases.
 FS2_EXTRA_PAIRS = {8: [3, 4, 5], 12: [9, 10, 11],      # categorical 8-4 and 6-3

@@ -4,7 +4,7 @@ Every minibatch above 128 trains on the dense engine: k_gather_obs, the staging 
 per-step host sync under target_kl / max_batches and the NaN gate (adam_gated behind k_sumsq2) all depend on the minibatch size. The steps are driven through batch_train_ with
 injected permutations (single-step entry points carry ids, which crux_train_dense_eligible sends to the generic learner), and every tolerance is one the suite already asserts:
 gradient 1e-4 x scale, infos 1e-4, parameters 2e-5, Adam moments 1e-5 (test_gpu_components.py), teacher-forced windows 2e-6 (test_gpu_round3.py).
-That the dense chain is what runs: no minibatch above 128 is taken by the register-resident kernels (train_mfma.hip: a.bs > 128), and the generic learner announces itself on
+That the dense chain is what runs: no minibatch above 128 is taken by the register-resident kernels (learner_route.h: a.bs > 128), and the generic learner announces itself on
 stderr for every network of 2048 parameters or more -- the tests assert that it did not (the hook of test_gpu_round2.py / test_gpu_round3.py).
 """
 import ctypes as C

@@ -192,7 +192,7 @@ def test_batch_train_equals_the_step_by_step_chain(gpu_ctx, sc):
     Both routes of a two-headed handle are the same chain of launches of the dense-engine learner, hence bit for bit. The constant-logSigma form of the same shape
     (GaussianPolicy 3-64-64-1, 9 steps at lr 1e-2) does NOT have this property, on the parent commit as now (its path is untouched): tools/sigma_pg_chain_probe.py measures
     it, profiles/sigma_pg_chain_probe.txt holds the result -- close, not the same bits. There the batch runs the feature-split register-resident kernel and a single step with
-    ids the one-CU kernel (crux_train_fs_launch declines a.ids), two kernels with different summation orders. For that form the 2e-5 parameter tolerance would be the
+    ids the one-CU kernel (learner_route.h: k_train_fs2 takes no ids), two kernels with different summation orders. For that form the 2e-5 parameter tolerance would be the
     comparison; this form is held to the bits because it has them by construction."""
     ctx = gpu_ctx; n, bs, E, seed, kind, lr = 300, 128, 3, 29, "ppo", 1e-2; c = _batch("3-64-64-2x1", n, sc, kind); mbs = _minibatches(n, bs, E, seed)
     states, infos = _step_loop(ctx, c, kind, mbs, lr); kls = [float(i[L.INFO["kl"]]) for i in infos]

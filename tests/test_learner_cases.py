@@ -1,4 +1,4 @@
-"""The case lists of tests/learner_cases.py, checked without a GPU: the dispatch tables are the ones of the .hip files, the (bs, r) schedule covers every head at every edge, the
+"""The case lists of tests/learner_cases.py, checked without a GPU: the dispatch tables are the flags of csrc/learner_shapes.h, the (bs, r) schedule covers every head at every edge, the
 gradients of every case are live (the surrogate is not clipped away) and every case is sensitive to ONE dropped row by five times the bound the GPU module asserts on Adam's m.
 Nothing here runs a kernel: the reference alone."""
 import os
@@ -15,28 +15,52 @@ KIND = {"MFK_CATEGORICAL": LC.CAT, "MFK_GAUSSIAN": LC.GAU, "MFK_VALUE": LC.VAL}
 ACT = {"CRUX_ACT_RELU": LC.RELU, "CRUX_ACT_TANH": LC.TANH, "CRUX_ACT_IDENTITY": LC.IDENT}
 
 
-def _parse(fname, macros):
-    """the uses of `macros` in a dispatcher, in file order, as table rows; #define lines are skipped, and \\b keeps MFXL_ / MFXM_ / MF8M_CASE out"""
+def _parse():
+    """the rows of CRUX_LEARNER_SHAPES in csrc/learner_shapes.h, in file order: [(row, {flag names})]"""
     rows = []
-    with open(os.path.join(CSRC, fname)) as f:
+    with open(os.path.join(CSRC, "learner_shapes.h")) as f:
         for line in f:
-            if line.lstrip().startswith("#"):
+            m = re.match(r"\s*X\(([^()]*)\)", line)
+            if not m:
                 continue
-            for name, args in re.findall(r"\b(%s)\(([^()]*)\)" % "|".join(macros), line):
-                a = [x.strip() for x in args.split(",")]
-                assert len(a) == (6 if name == "FS2_CASE2" else 4), (fname, line)
-                row = (int(a[0]), int(a[1]), KIND[a[2]], ACT[a[3]]) + ((int(a[4]), ACT[a[5]]) if name == "FS2_CASE2" else (64, ACT[a[3]]))
-                rows.append(row)
+            a = [x.strip() for x in m.group(1).split(",")]
+            assert len(a) == 7, line
+            flags = {x.strip() for x in a[6].split("|")}
+            assert all(re.fullmatch(r"LF_[A-Z0-9_]+", x) for x in flags), line
+            rows.append(((int(a[0]), int(a[1]), KIND[a[2]], ACT[a[3]], int(a[4]), ACT[a[5]]), flags))
     return rows
 
 
-def test_the_dispatch_tables_are_the_ones_of_the_hip_files():
-    fs2, mfx, mf8 = _parse("train_fs2.hip", ["FS2_CASE2", "FS2_CASE"]), _parse("train_mfma_x2.hip", ["MFX_CASE"]), _parse("train_mfma8.hip", ["MF8_CASE"])
+def _with(table, flag):
+    return [row for row, flags in table if flag in flags]
+
+
+# the lists the flags replace, written out from the dispatchers they stood in (train_fs2.hip: FS2_HAS_LAG and HAS_TIMING, the CRUX_FS2_MINIMAL rows; train_mfma_x2.hip:
+# MFXL_CASE, MFXM_CASE and the timing pair; train_mfma8.hip: MF8M_CASE and the timing shape)
+_C2A, _C2C, _C5A, _C5C = LC._r(4, 2, LC.CAT, LC.RELU), LC._r(4, 1, LC.VAL, LC.RELU), LC._r(17, 6, LC.GAU, LC.TANH), LC._r(17, 1, LC.VAL, LC.TANH)
+_LAG = [_C2A, LC._r(8, 4, LC.CAT, LC.RELU), LC._r(3, 1, LC.GAU, LC.RELU), _C5A]
+SUBSETS = {"LF_FS2_MIN": [_C2A, _C2C, _C5A, _C5C], "LF_FS2_LAG": _LAG, "LF_FS2_TIMING": [_C2A, _C2C, _C5A, _C5C],
+           "LF_X2_LAG": _LAG, "LF_X2_MULTI": [_C2A, _C2C, _C5A, _C5C], "LF_X2_TIMING": [_C2A, _C5A],
+           "LF_ONE8_MULTI": [_C2A, _C2C, LC._r(3, 1, LC.GAU, LC.RELU), LC._r(3, 1, LC.VAL, LC.RELU)], "LF_ONE8_TIMING": [_C2A]}
+
+
+def test_the_dispatch_tables_are_the_ones_of_the_shape_table():
+    table = _parse()
+    fs2, mfx, mf8 = _with(table, "LF_FS2"), _with(table, "LF_X2"), _with(table, "LF_ONE8")
     assert (len(fs2), len(mfx), len(mf8)) == (33, 10, 4)
-    assert fs2 == LC.FS2_ROWS and mfx == LC.MFX_ROWS and mf8 == LC.MF8_ROWS
-    for rows in (fs2, mfx, mf8):
+    assert len(table) == 33 and fs2 == LC.FS2_ROWS      # every row is a k_train_fs2 row, in the order the (bs, r) schedule counts in
+    assert set(mfx) == set(LC.MFX_ROWS) and set(mf8) == set(LC.MF8_ROWS)      # (their dispatchers match disjoint rows: no order to keep)
+    for rows in (fs2, mfx, mf8, LC.MFX_ROWS, LC.MF8_ROWS):
         assert len(set(rows)) == len(rows)
     assert set(LC.MF8_ROWS) <= set(LC.MFX_ROWS) and sorted(LC.SMALL_ROWS) == sorted(LC.MFX_ROWS)
+
+
+@pytest.mark.parametrize("flag", sorted(SUBSETS))
+def test_the_flag_subsets_are_the_lists_they_replace(flag):
+    table = _parse()
+    assert {f for _, flags in table for f in flags} == set(SUBSETS) | {"LF_FS2", "LF_X2", "LF_ONE8"}
+    got = _with(table, flag)
+    assert len(got) == len(set(got)) and set(got) == set(SUBSETS[flag]), (flag, got)
 
 
 def test_the_edge_schedule_covers_every_head_at_every_pair():
