@@ -34,7 +34,7 @@ static int32_t launch_fs2_row(crux_ctx* c, TrainArgs a, hipStream_t stream) {
     int32_t rc = launch_fs2_form<IN, OUT, KIND, ACT, H2, ACT2, true>(c, a, stream); if (rc) return rc;
     static const char* const nc[16] = {"loop", "wait staged", "fwdL1+T1", "fwdL2", "L3+pair barrier+head", "dW3+dZ2+stats+T2", "wait B_1", "dW2+send+dH1", "dZ1+db+dW1", "B_2+reduce+granules", "wait P1",
                                        "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+report+exit"};
-    static const char* const nh[16] = {"loop", "fetch", "stage next", "wait B_1", "dW2+send+drain", "arrival 1+wait(leader)", "-", "-", "-", "wait B_2+reduce+granules", "wait P1",
+    static const char* const nh[16] = {"loop", "fetch", "stage next", "wait B_1", "dW2+send+drain", "arrival 1+wait(leader)", "acks+arrival 1 (HELP_B2)", "db2 (HELP_B2)", "-", "wait B_2+reduce+granules", "wait P1",
                                        "W2 loads+granule poll", "drain loads", "totals+adam W2+ssq", "adam small", "B_b+exit"};
     MfTimingRow rows[12];      // per workgroup: compute wave 0, the helper leader, the last helper wave
     for (int i = 0; i < 12; ++i) { const int wg = i / 3, w = i % 3 == 0 ? 0 : i % 3 == 1 ? 4 : 7; rows[i].row = 8 * wg + w; rows[i].names = w == 0 ? nc : nh;

@@ -29,6 +29,8 @@
 //   poll the peers' granules (the tag is the flag: ONE round trip) -> small total + Adam
 //   (replica group, PX: the group's all-reduce of the totals sits between the totals and Adam; PXK: its theta / m / v average after every k-th Adam step)
 //   (plain forms, LATE_W3 / LATE_B2: the dW3 partials are formed behind the acknowledgement, with dZ1 / db1 / dW1, and db2 between the dW2 stores and dH1)
+//   (plain forms, EARLY_ACK / HELP_B2: the compute waves acknowledge after a quarter of dH1, and db2 is formed by helper wave 4 + wt behind its own acknowledgement -- the
+//    helpers then count at the compute barrier too)
 //   ============================== B_b (s_barrier): masters updated ==========================================================
 //
 //   (1) the W2 partials (89 % of the bytes) leave right after dW2 as before, but their hand-shake (drain, arrival counter, wait) is now run by the helper leader WHILE the
@@ -56,6 +58,15 @@
 #define FS_LD 72
 #ifndef CRUX_FS2_LATE_PARTS
 #define CRUX_FS2_LATE_PARTS 3          // LATE_B2 (bit 0) and LATE_W3 (bit 1) in the kernel; a build with one of them alone is what profiles/fs2_helper_partials_ab.txt compares
+#endif
+#ifndef CRUX_FS2_ACK_K
+#define CRUX_FS2_ACK_K 4               // EARLY_ACK: sixteenths of dH1's k-steps a compute wave issues in front of its acknowledgement of the W2 stores (16: behind all of dH1, the parent's place)
+#endif
+#ifndef CRUX_FS2_HELPER_PARTS
+#define CRUX_FS2_HELPER_PARTS 1        // HELP_B2 (bit 0): the helper wave of the same (tile, half) forms db2, behind its own acknowledgement (0: the compute wave, LATE_B2's place)
+#endif
+#ifndef CRUX_FS2_HELP_TIMERS
+#define CRUX_FS2_HELP_TIMERS 0         // 1 = the timing twins also close phases 6 / 7 of the helper waves around the HELP_B2 block (two more spilled scalar registers there)
 #endif
 __device__ __forceinline__ int fs_tx(int q) { return (4 - q) & 3; }   // {0,3,2,1}
 
@@ -201,6 +212,18 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
   constexpr int W3_PASSES = (OUT + 16 / (4 * MH) - 1) / (16 / (4 * MH));
   constexpr bool LATE_B2 = PLAIN && (CRUX_FS2_LATE_PARTS & 1) && W3_PASSES == 1;
   constexpr bool LATE_W3 = PLAIN && (CRUX_FS2_LATE_PARTS & 2);
+  // (4) EARLY_ACK and HELP_B2, adopted together (neither pays alone: profiles/fs2_early_ack_ab.txt). The hop to P1 depends on the dW2 stores, not on dH1: a compute wave
+  // acknowledges them after ACK_KS of dH1's k-steps (one acc0 and one acc1 MFMA each) instead of behind all sixteen; the operands of the remaining k-steps are in registers
+  // by then and the accumulation order is unchanged. P1 is then set before the compute waves need it, their own way to B_2 is the step's critical path, and db2 leaves it:
+  // helper wave 4 + wt forms it BEHIND its own acknowledgement (the leader: between its ARRIVAL 1 add and its first poll of the arrival counter), the same text on the same
+  // values in the same lanes. The helpers then write words that every wave's tail reads, so they are counted at the B_2 meeting point (B2_WAVES).
+  // (forms that gain spilled scalar registers with them keep the parent's text at both sites: the value heads of 27 inputs, 2 -> 3, and of 17 inputs with the 32-wide second
+  //  layer, 0 -> 3)
+  constexpr bool EA_FORM = PLAIN && !(KIND == MFK_VALUE && (IN == 27 || (IN == 17 && H2 == 32)));
+  constexpr int DH1_KS = 8 * MH, ACK_KS = EA_FORM && (CRUX_FS2_ACK_K) < 16 ? ((CRUX_FS2_ACK_K) * DH1_KS) / 16 : DH1_KS;
+  constexpr bool HELP_B2 = LATE_B2 && EA_FORM && ((CRUX_FS2_HELPER_PARTS) & 1);
+  constexpr bool EARLY_ACK = ACK_KS < DH1_KS && (HELP_B2 || !((CRUX_FS2_HELPER_PARTS) & 1));      // (with HELP_B2 in the build: where the helper takes db2 -- alone it gives nothing, the C5 actor included)
+  constexpr int B2_WAVES = HELP_B2 ? NW : NWC;      // waves that write partial words in front of B_2
   auto ka = [&]() { auto* q = (const __attribute__((address_space(4))) TrainArgs*)__builtin_amdgcn_kernarg_segment_ptr(); if constexpr (!PT) asm volatile("" : "+s"(q)); return q; };
   const int p = (int)(blockIdx.x >> 3);
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -801,6 +824,19 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     return true;
   };
 
+  // db2 of a (tile, half) from the dZ2 tile (visible since B_1), by its compute wave (LATE_B2) or by helper wave 4 + wt (HELP_B2): one text, so the same operations in the
+  // same lanes and order wherever it stands. The partial block is read behind B_2.
+#define FS2_DB2_PART \
+        { float gb2[MH]; \
+          _Pragma("unroll") \
+          for (int mm = 0; mm < MH; ++mm) { float sb2 = 0.f; \
+            const f32x4 d2 = *(const f32x4*)&T2[t_rd + 256 * (MH * h + mm)]; \
+            _Pragma("unroll") \
+            for (int r = 0; r < 4; ++r) sb2 += d2[r]; \
+            gb2[mm] = g4_sum(sb2); } \
+          if (g == 0) { \
+            _Pragma("unroll") \
+            for (int mm = 0; mm < MH; ++mm) part[Lt::pB2 + HH * h + 16 * mm + c] = gb2[mm]; } }
   if (cw) {
     // =====================================================================================================================================================
     // COMPUTE WAVES
@@ -1008,19 +1044,30 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         FS2_T(6);
         f32x4 gW2[WT];
         dw2_send(gW2);
-        if constexpr (LATE_B2) {      // db2 from the dZ2 tile (visible since B_1), beside the MFMAs of this phase; the partial block is read behind B_2
-          float gb2[MH];
-#pragma unroll
-          for (int mm = 0; mm < MH; ++mm) { float sb2 = 0.f;
-            const f32x4 d2 = *(const f32x4*)&T2[t_rd + 256 * (MH * h + mm)];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sb2 += d2[r];
-            gb2[mm] = g4_sum(sb2); }
-          if (g == 0) {
-#pragma unroll
-            for (int mm = 0; mm < MH; ++mm) part[Lt::pB2 + HH * h + 16 * mm + c] = gb2[mm]; } }
+        if constexpr (LATE_B2 && !HELP_B2) FS2_DB2_PART      // beside the MFMAs of this phase
         // dH1 (R) for the h1 features [32h, 32h + 32)
         f32x4 dz1r[2];
+        if constexpr (EARLY_ACK) {
+          // the operands of every k-step are read first: the wait's memory clobber then puts no LDS round trip between the two parts of the chain. The accumulators pass
+          // through the wait statement, so the k-steps stay on the side of it they are written on.
+          const float* dq = sm + Lt::oD2X + ((t * 2 + (1 - h)) * MH) * 256 + lane * 4;
+          f32x4 av[2 * MH], wv0[2 * MH], wv1[2 * MH];
+#pragma unroll
+          for (int mm = 0; mm < MH; ++mm) { av[mm] = h2[mm]; av[MH + mm] = *(const f32x4*)&dq[256 * mm]; }
+#pragma unroll
+          for (int q = 0; q < 2 * MH; ++q) { const int fo = HH * ((q >= MH) ? 1 - h : h) + 16 * (q % MH);
+            wv0[q] = *(const f32x4*)&sm[Lt::oW2C + (32 * h + c) * FS_LD + fo + 4 * g];
+            wv1[q] = *(const f32x4*)&sm[Lt::oW2C + (32 * h + 16 + c) * FS_LD + fo + 4 * g]; }
+          f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < DH1_KS; ++ks) { const int q = ks >> 2, r = ks & 3;
+            if (ks == ACK_KS) {
+              asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc0), "+v"(acc1) :: "memory");     // the dW2 stores have been acknowledged -- tell the helper leader (phase 1)
+              if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][r], wv0[q][r], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q][r], wv1[q][r], acc1, 0, 0, 0); }
+          dz1r[0] = acc0; dz1r[1] = acc1;
+        } else {
         { const float* dq = sm + Lt::oD2X + ((t * 2 + (1 - h)) * MH) * 256 + lane * 4;
           f32x4 av[2 * MH];
 #pragma unroll
@@ -1036,6 +1083,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
           dz1r[0] = acc0; dz1r[1] = acc1; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the dW2 stores left before dH1: acknowledged by now -- tell the helper leader (phase 1)
         if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
         FS2_T(7);
         if constexpr (LATE_W3) { constexpr int FPL = 4 * MH, PER = 16 / FPL; FS2_DW3_PART(h2a) }
 #undef FS2_DW3_PART
@@ -1071,7 +1119,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
             if (16 * jt + c < Lt::W1ROWS) *(f32x4*)&part[Lt::pW1 + (16 * jt + c) * FS_LD + 32 * h + 16 * mm + 4 * g] = acc; }
         }
         FS2_T(8);
-        fs2_group_barrier(smr + Lt::cCOMP, (unsigned)NWC * (xstep + 1u), lane);   // ---- B_2: the small partial gradients of both tiles are visible (compute waves only)
+        fs2_group_barrier(smr + Lt::cCOMP, (unsigned)B2_WAVES * (xstep + 1u), lane);   // ---- B_2: the small partial gradients of both tiles are visible (the waves that write them: the compute waves; HELP_B2: all eight)
         const unsigned tag = xstep + 1u;
         int any_bad = 0; st_now = st;
         if (!step_tail(tag, gW2, any_bad)) break;
@@ -1223,9 +1271,29 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every store of this lane has reached the L2 (and the prefetched rows are in)
         if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cACK), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FS2_T(4);
+        if constexpr (HELP_B2) {
+          // The leader's lane: all eight acknowledgements, then ARRIVAL 1 -- whose result nobody reads: the hop takes its time whatever this wave does meanwhile. Then every
+          // helper wave forms db2 of its (tile, half) and counts itself in at B_2 (cCOMP), the leader BEFORE its first poll of the arrival counter: the compute waves' B_2
+          // must not wait for P1. Between B_1 and this add no path leaves the step or skips the add -- ragged minibatches and tiles without a valid sample run the same
+          // text on zeros; a failed exchange, a suspect step and max_batches end the step in step_tail / step_exit, behind B_2 -- so every counted wave adds once per step
+          // and the targets stay multiples of xstep + 1.
+          if (ct == 0) {
+            fs2_flag_wait(smr + Lt::cACK, (unsigned)NW * tag);
+            (void)__hip_atomic_fetch_add(a.xctr + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }      // ARRIVAL 1
+          if constexpr (CRUX_FS2_HELP_TIMERS) FS2_T(6);
+          { // (the block's lane predicate is formed here, from a thread index the compiler cannot see through: hoisted out of the step it is a lane mask held across it)
+            int tl = tid; asm volatile("" : "+v"(tl));
+            const int c = tl & 15, g = (tl >> 4) & 3, h = (tl >> 6) & 1;
+            FS2_DB2_PART }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          if (lane == 0) (void)__hip_atomic_fetch_add((unsigned*)(smr + Lt::cCOMP), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if constexpr (CRUX_FS2_HELP_TIMERS) FS2_T(7);
+        }
         if (ct == 0) {
+          if constexpr (!HELP_B2) {
           fs2_flag_wait(smr + Lt::cACK, (unsigned)NW * tag);        // all eight waves' W2 stores are acknowledged (the compute waves report after dH1)
           (void)__hip_atomic_fetch_add(a.xctr + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ARRIVAL 1
+          }
           const unsigned want = (unsigned)NWG * tag; unsigned spins = 0; bool ok = true;
           while (__hip_atomic_load(a.xctr + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) { __builtin_amdgcn_s_sleep(1);
             if (++spins > (1u << 24) || __hip_atomic_load(a.xctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = false; break; } }   // never hang the GPU
@@ -1238,7 +1306,7 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
           fs2_flag_set(smr + Lt::fP1, tag);
         }
         FS2_T(5);
-        fs2_flag_wait(smr + Lt::cCOMP, (unsigned)NWC * tag);      // the compute waves have passed B_2: the small partials of both tiles are in LDS, nobody reads the W2 masters (dH1) any more
+        fs2_flag_wait(smr + Lt::cCOMP, (unsigned)B2_WAVES * tag);      // the compute waves have passed B_2 (HELP_B2: and every helper has written its db2): the small partials of both tiles are in LDS, nobody reads the W2 masters (dH1) any more
         int any_bad = 0; st_now = st;
         if (!step_tail(tag, gW2, any_bad)) break;
         const bool go = step_exit(invB, any_bad != 0);
@@ -1276,5 +1344,6 @@ __global__ __launch_bounds__(512) void k_train_fs2(TrainArgs a) {
     if constexpr (LAG) { if (p == 0) { crux_lagrange* const lag = kz->lag; lag->I = lgs[0]; lag->smooth_delta = lgs[1]; lag->smooth_Jc = lgs[2]; lag->Jc_prev = lgs[3]; lag->deriv_term = lgs[4]; lag->penalty = lgs[5]; lag->cur_cost = lgs[6]; } }
     if (err && infos && epochs_run == 0) { infos[CRUX_INFO_LOSS] = smr[Lt::iLOSS]; infos[CRUX_INFO_GRAD_NORM] = NAN; }
   }
+#undef FS2_DB2_PART
 #undef FS2_T
 }
