@@ -1302,21 +1302,20 @@ def _fill_importance_weights(sampler, buffer, first, Nsteps, reset):
 
 
 def _fill_traj_weights(sampler, buffer, first, Nsteps, reset):
-    if True:
-        # data[:traj_importance_weight][1, ep] .= sampler.traj_weight_fn(sampler.agent, data, ep) (sampler.jl:62): a host function of the episode's rows
-        fn = getattr(sampler, "traj_weight_fn", None)
-        if fn is None:
-            raise L.CruxError(L.EINVAL, "steps!: the buffer has a :traj_importance_weight column but the sampler has no traj_weight_fn (sampler.jl:21,62)")
-        C_ = buffer.capacity; ids = (first + np.arange(Nsteps)) % C_ + 1
-        rows = buffer.minibatch(ids); ee = rows["episode_end"].reshape(-1).astype(bool); seg = Nsteps // sampler.n_envs
-        out = rows["traj_importance_weight"].reshape(-1).copy(); start = 0
-        for j in range(Nsteps):
-            last_of_seg = (j + 1) % seg == 0
-            if ee[j] or (last_of_seg and reset):
-                ep = np.arange(start, j + 1); out[ep] = np.float32(fn(sampler.agent, rows, ep)); start = j + 1
-            elif last_of_seg:
-                out[start:j + 1] = 1.0; start = j + 1          # an episode left open: the fresh data block's ones
-        col = buffer["traj_importance_weight"]; col[..., ids - 1] = out; buffer["traj_importance_weight"] = col
+    # data[:traj_importance_weight][1, ep] .= sampler.traj_weight_fn(sampler.agent, data, ep) (sampler.jl:62): a host function of the episode's rows
+    fn = getattr(sampler, "traj_weight_fn", None)
+    if fn is None:
+        raise L.CruxError(L.EINVAL, "steps!: the buffer has a :traj_importance_weight column but the sampler has no traj_weight_fn (sampler.jl:21,62)")
+    C_ = buffer.capacity; ids = (first + np.arange(Nsteps)) % C_ + 1
+    rows = buffer.minibatch(ids); ee = rows["episode_end"].reshape(-1).astype(bool); seg = Nsteps // sampler.n_envs
+    out = rows["traj_importance_weight"].reshape(-1).copy(); start = 0
+    for j in range(Nsteps):
+        last_of_seg = (j + 1) % seg == 0
+        if ee[j] or (last_of_seg and reset):
+            ep = np.arange(start, j + 1); out[ep] = np.float32(fn(sampler.agent, rows, ep)); start = j + 1
+        elif last_of_seg:
+            out[start:j + 1] = 1.0; start = j + 1          # an episode left open: the fresh data block's ones
+    col = buffer["traj_importance_weight"]; col[..., ids - 1] = out; buffer["traj_importance_weight"] = col
 
 
 def episodes_(sampler, Neps=1, explore=False, i=0, seed_offset=0x45564C):

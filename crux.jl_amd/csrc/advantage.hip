@@ -5,34 +5,45 @@
 
 int32_t crux_mlp_forward_impl(crux_mlp* net, const float* d_x, int64_t B, float* d_y, const float* params_override);
 
-// One thread per episode: a thread sitting on an episode-end row (or the last row) walks its episode backwards.
+// A block of rows to scan: block row k lives at physical row (first + k) mod cap of the ring, and rows [e*seg, (e+1)*seg) of the block belong to environment e:
+// no episode crosses that boundary. A run ends on an :episode_end row, on the last row of its segment and on the block's last row. close_last: such a trailing
+// run is an episode even without :episode_end (episodes(d) closes a trailing episode at length(d), experience_buffer.jl:207-211; steps!(reset=true) sets the flag
+// itself); otherwise its rows keep what mdp_data put into the reference's fresh `data` block, which terminate_episode! never reached (sampler.jl:53-57,140-148).
+// The whole buffer is the physical rows {0, elements, capacity} as one closed segment, wherever next_ind stands: phys(k) == k.
+struct ScanRange {
+  int64_t first, n, cap, seg; int close_last;
+  __device__ __forceinline__ int64_t phys(int64_t k) const { const int64_t q = first + k; return q >= cap ? q - cap : q; }
+  // row i ends a run: lo = the first row of its segment, open = the run trails the segment and stays as the fresh block left it
+  __device__ __forceinline__ bool ends_run(const uint8_t* __restrict__ ee, int64_t i, int64_t& lo, bool& open) const {
+    const bool closed = ee[phys(i)];
+    if (!(closed || i == n - 1 || (i + 1) % seg == 0)) return false;
+    lo = (i / seg) * seg; open = !closed && !close_last; return true;
+  }
+};
+__host__ __device__ __forceinline__ ScanRange scan_range(int64_t first, int64_t n, int64_t cap, int64_t seg, int close_last) {      // seg <= 0: one segment of n rows
+  return ScanRange{first, n, cap, seg > 0 ? seg : n, close_last ? 1 : 0};
+}
+__host__ __device__ __forceinline__ ScanRange scan_whole(int64_t n, int64_t cap) { return scan_range(0, n, cap, 0, 1); }
+
+// One thread per episode: a thread sitting on a row that ends a run walks the run backwards.
 // The recurrence is evaluated sequentially in Float32 with the reference's association
 //   A = ((c*A + r) + ((1f0 - done)*gamma)*Vsp) - Vs        (sampler.jl:269)
 //   R = r + gamma*R                                        (sampler.jl:278)
-// so results are bit-identical to the scalar loop given the same V(s), V(sp).
-// Row k of the scanned block lives at physical row (first + k) mod cap (a ring range; first = 0, cap = n for a whole buffer); Vs / Vsp are
-// indexed by k. close_last: the block's last row terminates an episode even without :episode_end (episodes(d) closes a trailing episode at
-// length(d), experience_buffer.jl:207-211; steps!(reset=true) sets the flag itself); otherwise the trailing open rows get 0 -- the values
-// mdp_data initialised them with in the reference's fresh `data` block, which terminate_episode! never reached (sampler.jl:53-57,140-148).
+// so results are bit-identical to the scalar loop given the same V(s), V(sp). Vs / Vsp are indexed by the block row; an open trailing run gets 0.
 __device__ __forceinline__ void gae_returns_body(const float* __restrict__ r, const uint8_t* __restrict__ done, const uint8_t* __restrict__ ee,
-                              const float* __restrict__ Vs, const float* __restrict__ Vsp, float lambda, float gamma, int64_t n,
-                              float* __restrict__ adv, float* __restrict__ ret, int32_t* __restrict__ nan_flag,
-                              int64_t first = 0, int64_t cap = 0, int close_last = 1, int64_t seg = 0) {
-  if (cap <= 0) cap = n;
-  if (seg <= 0) seg = n;        // env-major blocks: rows [e*seg, (e+1)*seg) belong to environment e and no episode crosses that boundary
-  auto phys = [&](int64_t k) -> int64_t { const int64_t q = first + k; return q >= cap ? q - cap : q; };
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const bool closed = ee[phys(i)];
-    if (!(closed || i == n - 1 || (i + 1) % seg == 0)) continue;
-    const int64_t k0 = (i / seg) * seg;     // first row of this environment's segment
-    if (!closed && !close_last) {          // trailing rows of an episode that is still open at the end of the segment
-      for (int64_t k = i; k >= k0 && !ee[phys(k)]; --k) { if (adv) adv[phys(k)] = 0.f; if (ret) ret[phys(k)] = 0.f; }
+                              const float* __restrict__ Vs, const float* __restrict__ Vsp, float lambda, float gamma, const ScanRange g,
+                              float* __restrict__ adv, float* __restrict__ ret, int32_t* __restrict__ nan_flag) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t k0; bool open;
+    if (!g.ends_run(ee, i, k0, open)) continue;
+    if (open) {
+      for (int64_t k = i; k >= k0 && !ee[g.phys(k)]; --k) { if (adv) adv[g.phys(k)] = 0.f; if (ret) ret[g.phys(k)] = 0.f; }
       continue;
     }
     float A = 0.f, R = 0.f; const float c = __fmul_rn(lambda, gamma);
     bool bad = false;
-    for (int64_t k = i; k >= k0 && (k == i || !ee[phys(k)]); --k) {
-      const int64_t q = phys(k);
+    for (int64_t k = i; k >= k0 && (k == i || !ee[g.phys(k)]); --k) {
+      const int64_t q = g.phys(k);
       const float rk = r[q];
       if (adv) {
         const float t2 = __fadd_rn(__fmul_rn(c, A), rk);
@@ -46,19 +57,14 @@ __device__ __forceinline__ void gae_returns_body(const float* __restrict__ r, co
   }
 }
 __global__ void k_gae_returns(const float* __restrict__ r, const uint8_t* __restrict__ done, const uint8_t* __restrict__ ee,
-                              const float* __restrict__ Vs, const float* __restrict__ Vsp, float lambda, float gamma, int64_t n,
+                              const float* __restrict__ Vs, const float* __restrict__ Vsp, float lambda, float gamma, const ScanRange g,
                               float* __restrict__ adv, float* __restrict__ ret, int32_t* __restrict__ nan_flag) {
-  gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, n, adv, ret, nan_flag);
-}
-__global__ void k_gae_returns_rows(const float* __restrict__ r, const uint8_t* __restrict__ done, const uint8_t* __restrict__ ee,
-                                   const float* __restrict__ Vs, const float* __restrict__ Vsp, float lambda, float gamma, int64_t n,
-                                   float* __restrict__ adv, float* __restrict__ ret, int32_t* __restrict__ nan_flag, int64_t first, int64_t cap, int close_last, int64_t seg) {
-  gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, n, adv, ret, nan_flag, first, cap, close_last, seg);
+  gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, g, adv, ret, nan_flag);
 }
 struct GaeJob { const float* r; const uint8_t* done; const uint8_t* ee; const float* Vs; const float* Vsp; float* adv; float* ret; int32_t* flag; };
-__global__ void k_gae_returns_multi(const GaeJob* __restrict__ jobs, float lambda, float gamma, int64_t n) {     // grid.y = buffer
+__global__ void k_gae_returns_multi(const GaeJob* __restrict__ jobs, float lambda, float gamma, int64_t n) {     // grid.y = buffer, each scanned whole
   const GaeJob j = jobs[blockIdx.y];
-  gae_returns_body(j.r, j.done, j.ee, j.Vs, j.Vsp, lambda, gamma, n, j.adv, j.ret, j.flag);
+  gae_returns_body(j.r, j.done, j.ee, j.Vs, j.Vsp, lambda, gamma, scan_whole(n, n), j.adv, j.ret, j.flag);
 }
 
 // whiten(v) = (v .- mean(v)) ./ std(v) (utils.jl:41-42) with Julia's own Float32 reductions: Statistics.mean = sum(A) / length(A), Statistics.std = sqrt(centralize_sumabs2(A, m) / (n - 1)),
@@ -124,8 +130,8 @@ __global__ void k_nda_gae2(const float* __restrict__ r, const float* __restrict_
                            const float* __restrict__ Vsp, const float* __restrict__ Cs, const float* __restrict__ Csp, float lambda, float gamma, int64_t n, float* __restrict__ adv,
                            float* __restrict__ ret, float* __restrict__ cadv, float* __restrict__ cret, int32_t* __restrict__ flags, const int32_t* __restrict__ gate) {
   if (gate && gate[0] == CRUX_ENAN) return;
-  if (blockIdx.y == 0) gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, n, adv, ret, flags);
-  else gae_returns_body(cost, done, ee, Cs, Csp, lambda, gamma, n, cadv, cret, flags + 1);
+  if (blockIdx.y == 0) gae_returns_body(r, done, ee, Vs, Vsp, lambda, gamma, scan_whole(n, n), adv, ret, flags);
+  else gae_returns_body(cost, done, ee, Cs, Csp, lambda, gamma, scan_whole(n, n), cadv, cret, flags + 1);
 }
 __global__ __launch_bounds__(1024) void k_nda_whiten2(float* __restrict__ v0, float* __restrict__ v1, int64_t n, const int32_t* __restrict__ gate) {
   if (gate && gate[0] == CRUX_ENAN) return;
@@ -154,6 +160,65 @@ __global__ void k_first_episode_metrics(const float* __restrict__ r, const uint8
 // a Float32 one-row column that exists (fill_gae!/fill_returns! `source=` / `target=` keywords, sampler.jl:65-66,255,275)
 static bool f32_scalar_col(const crux_buffer* b, int k) { return (k == CRUX_COL_R || has_col(b, k)) && col_rows(b, k) == 1 && col_elem(b, k) == 4; }
 
+// ---- the scan driver: fill_gae!(data, ep, V, lambda, gamma) / fill_returns!(data, ep, gamma) on a block of rows -------------------------------------------------------
+// everything that can refuse a scan, before anything is enqueued (critic: NULL for fill_returns!)
+static int32_t scan_check(const crux_buffer* b, const crux_mlp* critic, int32_t source, int32_t target, const ScanRange& g, const char* who) {
+  crux_ctx* c = b->ctx;
+  if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "%s: buffer lacks the source / target column (%d -> %d)", who, source, target);
+  if (critic && (critic->nd.dims[critic->nd.L] != 1 || critic->nd.dims[0] != b->obs_dim)) return crux_fail(c, CRUX_EINVAL, "%s: critic must map obs(%d) -> 1 (@assert length(Vs) == 1)", who, b->obs_dim);
+  if (g.first < 0 || g.first >= g.cap || g.n < 0 || g.n > g.cap) return crux_fail(c, CRUX_EINVAL, "%s: rows [%lld, +%lld) outside the ring of %lld", who, (long long)g.first, (long long)g.n, (long long)g.cap);
+  return CRUX_OK;
+}
+// V(s), V(sp) of the block's rows in block order: the rows up to the ring's end, then the wrapped ones
+static int32_t block_values(crux_mlp* critic, const crux_buffer* b, const ScanRange& g, float* Vs, float* Vsp) {
+  const int64_t n1 = g.first + g.n <= g.cap ? g.n : g.cap - g.first, n2 = g.n - n1; const int od = b->obs_dim;
+  int32_t rc = values(critic, (const float*)b->col[CRUX_COL_S] + g.first * od, n1, Vs); if (rc) return rc;
+  rc = values(critic, (const float*)b->col[CRUX_COL_SP] + g.first * od, n1, Vsp); if (rc) return rc;
+  if (n2 > 0) { rc = values(critic, (const float*)b->col[CRUX_COL_S], n2, Vs + n1); if (rc) return rc;
+    rc = values(critic, (const float*)b->col[CRUX_COL_SP], n2, Vsp + n1); if (rc) return rc; }
+  return CRUX_OK;
+}
+// the scan's one launch; adv_target / ret_target: -1 = not filled
+static void scan_enqueue(const crux_buffer* b, float lambda, float gamma, const ScanRange& g, int32_t source, int32_t adv_target, int32_t ret_target, const float* Vs, const float* Vsp, int32_t* flag) {
+  hipLaunchKernelGGL(k_gae_returns, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, b->ctx->stream, (const float*)b->col[source], (const uint8_t*)b->col[CRUX_COL_DONE],
+                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], Vs, Vsp, lambda, gamma, g, adv_target >= 0 ? (float*)b->col[adv_target] : (float*)nullptr,
+                     ret_target >= 0 ? (float*)b->col[ret_target] : (float*)nullptr, flag);
+}
+static int32_t scan_flag(crux_ctx* c, const int32_t* flag) {      // the scan's one host synchronisation
+  int32_t h = 0;
+  HIPCHK(c, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return h ? crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))") : CRUX_OK;
+}
+// critic: source -> target is an advantage, its NaN flag is read back; NULL: a return, enqueued only (the flag word is a valid address and nothing more)
+static int32_t scan_fill(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, const ScanRange g, int32_t source, int32_t target) {
+  crux_ctx* c = b->ctx; const char* who = critic ? "fill_gae!" : "fill_returns!";
+  int32_t rc = scan_check(b, critic, source, target, g, who); if (rc) return rc;
+  if (g.n == 0) return CRUX_OK;
+  const size_t vb = critic ? Carve::span<float>((size_t)g.n) : 0;
+  char* sc = (char*)crux_scratch(c, 2 * vb + 256);
+  if (!sc) return crux_fail(c, CRUX_ENOMEM, "%s: scratch", who);
+  float* Vs = (float*)sc; float* Vsp = (float*)(sc + vb); int32_t* flag = (int32_t*)(sc + 2 * vb);
+  if (critic) {
+    HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    crux_prof_begin(c, CRUX_PROF_VALUES);
+    rc = block_values(critic, b, g, Vs, Vsp); if (rc) return rc;
+    crux_prof_end(c, CRUX_PROF_VALUES);
+  }
+  crux_prof_begin(c, CRUX_PROF_GAE);
+  scan_enqueue(b, lambda, gamma, g, source, critic ? target : -1, critic ? -1 : target, critic ? Vs : nullptr, critic ? Vsp : nullptr, flag);
+  crux_prof_end(c, CRUX_PROF_GAE);
+  rc = crux_launch_check(c, "k_gae_returns"); if (rc) return rc;
+  return critic ? scan_flag(c, flag) : CRUX_OK;
+}
+static ScanRange whole_buffer(const crux_buffer* b) { return scan_whole(b->elements, b->capacity); }
+
+// what stands between a column and whiten_block: it is no 1 x N Float32 column, holds fewer than 2 elements, or more than the pairwise reduction's leaf tables take
+enum { WHITEN_COLUMN = 1, WHITEN_FEW = 2, WHITEN_MANY = 4 };
+static int whiten_unfit(const crux_buffer* b, int key) {
+  return (has_col(b, key) && col_elem(b, key) == 4 && col_rows(b, key) == 1 ? 0 : WHITEN_COLUMN) | (b->elements < 2 ? WHITEN_FEW : 0) | (b->elements > (int64_t)JLW_MAXLEAF * 512 ? WHITEN_MANY : 0);
+}
+
 extern "C" {
 
 int32_t crux_first_episode_metrics(crux_buffer* b, int32_t n_envs, int64_t T, float gamma, float* undisc, float* disc, int64_t* length, uint8_t* complete) {
@@ -174,33 +239,28 @@ int32_t crux_first_episode_metrics(crux_buffer* b, int32_t n_envs, int64_t T, fl
   return CRUX_OK;
 }
 
+// The whole-buffer forms scan the physical rows 0 .. length(b)-1; the _rows forms scan what terminate_episode! applies fill_gae! / fill_returns! to: the block a steps!
+// call just produced (sampler.jl:53-57,140-148), on the ring rows [first_row, first_row + n_rows) mod capacity that it was pushed to.
 int32_t crux_fill_gae_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int32_t source, int32_t target) { CRUX_PLAIN_ONLY("crux_fill_gae_keys", critic);
   if (!b || !critic) return CRUX_EINVAL;
-  crux_ctx* c = b->ctx;
-  if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_gae!: buffer lacks the source / target column (%d -> %d)", source, target);
-  if (critic->nd.dims[critic->nd.L] != 1 || critic->nd.dims[0] != b->obs_dim) return crux_fail(c, CRUX_EINVAL, "fill_gae!: critic must map obs(%d) -> 1 (@assert length(Vs) == 1)", b->obs_dim);
-  const int64_t n = b->elements; if (n == 0) return CRUX_OK;
-  const size_t vb = ((4 * (size_t)n + 255) / 256) * 256;
-  char* sc = (char*)crux_scratch(c, 2 * vb + 256);
-  if (!sc) return crux_fail(c, CRUX_ENOMEM, "fill_gae!: scratch");
-  float* Vs = (float*)sc; float* Vsp = (float*)(sc + vb); int32_t* flag = (int32_t*)(sc + 2 * vb);
-  HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
-  crux_prof_begin(c, CRUX_PROF_VALUES);
-  int32_t rc = values(critic, (const float*)b->col[CRUX_COL_S], n, Vs); if (rc) return rc;
-  rc = values(critic, (const float*)b->col[CRUX_COL_SP], n, Vsp); if (rc) return rc;
-  crux_prof_end(c, CRUX_PROF_VALUES);
-  crux_prof_begin(c, CRUX_PROF_GAE);
-  hipLaunchKernelGGL(k_gae_returns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[source], (const uint8_t*)b->col[CRUX_COL_DONE],
-                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], Vs, Vsp, lambda, gamma, n, (float*)b->col[target], (float*)nullptr, flag);
-  crux_prof_end(c, CRUX_PROF_GAE);
-  rc = crux_launch_check(c, "k_gae_returns"); if (rc) return rc;
-  int32_t h = 0;
-  HIPCHK(c, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
-  return CRUX_OK;
+  return scan_fill(b, critic, lambda, gamma, whole_buffer(b), source, target);
 }
 int32_t crux_fill_gae(crux_buffer* b, crux_mlp* critic, float lambda, float gamma) { CRUX_PLAIN_ONLY("crux_fill_gae", critic); return crux_fill_gae_keys(b, critic, lambda, gamma, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
+int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) { CRUX_PLAIN_ONLY("crux_fill_gae_rows_keys", critic);
+  if (!b || !critic) return CRUX_EINVAL;
+  return scan_fill(b, critic, lambda, gamma, scan_range(first_row, n_rows, b->capacity, rows_per_env, close_last), source, target);
+}
+int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { CRUX_PLAIN_ONLY("crux_fill_gae_rows", critic); return crux_fill_gae_rows_keys(b, critic, lambda, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
+int32_t crux_fill_returns_keys(crux_buffer* b, float gamma, int32_t source, int32_t target) {
+  if (!b) return CRUX_EINVAL;
+  return scan_fill(b, nullptr, 0.f, gamma, whole_buffer(b), source, target);
+}
+int32_t crux_fill_returns(crux_buffer* b, float gamma) { return crux_fill_returns_keys(b, gamma, CRUX_COL_R, CRUX_COL_RETURN); }
+int32_t crux_fill_returns_rows_keys(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) {
+  if (!b) return CRUX_EINVAL;
+  return scan_fill(b, nullptr, 0.f, gamma, scan_range(first_row, n_rows, b->capacity, rows_per_env, close_last), source, target);
+}
+int32_t crux_fill_returns_rows(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { return crux_fill_returns_rows_keys(b, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_RETURN); }
 
 // fill_gae! + fill_returns! for n buffers (the tail of a batched rollout): everything is enqueued, ONE host synchronisation reads the n NaN flags
 int32_t crux_fill_gae_multi(int32_t n, crux_buffer* const* bufs, crux_mlp* const* critics, float lambda, float gamma, int32_t with_returns) {
@@ -235,20 +295,16 @@ int32_t crux_fill_gae_multi(int32_t n, crux_buffer* const* bufs, crux_mlp* const
     crux_prof_begin(c, CRUX_PROF_GAE);
     hipLaunchKernelGGL(k_gae_returns_multi, dim3((unsigned)((m0 + 255) / 256), (unsigned)n), dim3(256), 0, c->stream, (const GaeJob*)(sc + fb + sizeof(crux_fwd_job) * 2 * (size_t)n), lambda, gamma, m0);
     crux_prof_end(c, CRUX_PROF_GAE);
-  } else {
-  crux_prof_begin(c, CRUX_PROF_VALUES);
-  for (int i = 0; i < n; ++i) { crux_buffer* b = bufs[i]; const int64_t m = b->elements; if (m == 0) continue;
-    float* Vs = (float*)(vals + (size_t)i * 2 * vb); float* Vsp = (float*)(vals + (size_t)i * 2 * vb + vb);
-    int32_t rc = values(critics[i], (const float*)b->col[CRUX_COL_S], m, Vs); if (rc) return rc;
-    rc = values(critics[i], (const float*)b->col[CRUX_COL_SP], m, Vsp); if (rc) return rc; }
-  crux_prof_end(c, CRUX_PROF_VALUES);
-  crux_prof_begin(c, CRUX_PROF_GAE);
-  for (int i = 0; i < n; ++i) { crux_buffer* b = bufs[i]; const int64_t m = b->elements; if (m == 0) continue;
-    float* Vs = (float*)(vals + (size_t)i * 2 * vb); float* Vsp = (float*)(vals + (size_t)i * 2 * vb + vb);
-    hipLaunchKernelGGL(k_gae_returns, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_R], (const uint8_t*)b->col[CRUX_COL_DONE],
-                       (const uint8_t*)b->col[CRUX_COL_EPISODE_END], (const float*)Vs, (const float*)Vsp, lambda, gamma, m, (float*)b->col[CRUX_COL_ADVANTAGE],
-                       with_returns ? (float*)b->col[CRUX_COL_RETURN] : (float*)nullptr, flags + i); }
-  crux_prof_end(c, CRUX_PROF_GAE);
+  } else {                  // the single buffer's passes, one buffer after the other: all values, then all scans
+    crux_prof_begin(c, CRUX_PROF_VALUES);
+    for (int i = 0; i < n; ++i) { if (bufs[i]->elements == 0) continue;
+      int32_t rc = block_values(critics[i], bufs[i], whole_buffer(bufs[i]), (float*)(vals + (size_t)i * 2 * vb), (float*)(vals + (size_t)i * 2 * vb + vb)); if (rc) return rc; }
+    crux_prof_end(c, CRUX_PROF_VALUES);
+    crux_prof_begin(c, CRUX_PROF_GAE);
+    for (int i = 0; i < n; ++i) { if (bufs[i]->elements == 0) continue;
+      scan_enqueue(bufs[i], lambda, gamma, whole_buffer(bufs[i]), CRUX_COL_R, CRUX_COL_ADVANTAGE, with_returns ? CRUX_COL_RETURN : -1, (const float*)(vals + (size_t)i * 2 * vb),
+                   (const float*)(vals + (size_t)i * 2 * vb + vb), flags + i); }
+    crux_prof_end(c, CRUX_PROF_GAE);
   }
   int32_t rc = crux_launch_check(c, "k_gae_returns (multi)"); if (rc) return rc;
   std::vector<int32_t> h((size_t)n);
@@ -261,11 +317,11 @@ int32_t crux_fill_gae_multi(int32_t n, crux_buffer* const* bufs, crux_mlp* const
 int32_t crux_whiten_multi(int32_t n, crux_buffer* const* bufs, int32_t key) {
   if (n < 1 || !bufs) return CRUX_EINVAL;
   crux_ctx* c = bufs[0]->ctx; const int64_t len = bufs[0]->elements;
-  if (len > (int64_t)JLW_MAXLEAF * 512) return crux_fail(c, CRUX_EUNSUP, "whiten (multi): %lld elements per buffer (the pairwise reduction is laid out for at most %d leaves)", (long long)len, JLW_MAXLEAF);      // the same bound as crux_whiten: k_whiten_multi keeps the leaf tables in LDS
+  if (whiten_unfit(bufs[0], key) & WHITEN_MANY) return crux_fail(c, CRUX_EUNSUP, "whiten (multi): %lld elements per buffer (the pairwise reduction is laid out for at most %d leaves)", (long long)len, JLW_MAXLEAF);      // k_whiten_multi keeps the leaf tables in LDS
   std::vector<float*> hp((size_t)n);
-  for (int i = 0; i < n; ++i) { crux_buffer* b = bufs[i];
-    if (!b || !has_col(b, key) || col_elem(b, key) != 4 || col_rows(b, key) != 1) return crux_fail(c, CRUX_EINVAL, "whiten: column %d of buffer %d is not a 1 x N Float32 column", key, i);
-    if (b->elements != len || len < 2) return crux_fail(c, CRUX_EINVAL, "whiten (multi): buffers must hold the same number (>= 2) of elements");
+  for (int i = 0; i < n; ++i) { crux_buffer* b = bufs[i]; const int unfit = b ? whiten_unfit(b, key) : WHITEN_COLUMN;
+    if (unfit & WHITEN_COLUMN) return crux_fail(c, CRUX_EINVAL, "whiten: column %d of buffer %d is not a 1 x N Float32 column", key, i);
+    if (b->elements != len || (unfit & WHITEN_FEW)) return crux_fail(c, CRUX_EINVAL, "whiten (multi): buffers must hold the same number (>= 2) of elements");
     hp[(size_t)i] = (float*)b->col[key]; }
   float** dp = (float**)crux_scratch(c, 8 * (size_t)n + 256); if (!dp) return crux_fail(c, CRUX_ENOMEM, "whiten (multi): scratch");
   HIPCHK(c, hipMemcpyAsync(dp, hp.data(), 8 * (size_t)n, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -275,81 +331,13 @@ int32_t crux_whiten_multi(int32_t n, crux_buffer* const* bufs, int32_t key) {
   return crux_launch_check(c, "k_whiten_multi");
 }
 
-// fill_gae!(data, ep, V, lambda, gamma) / fill_returns!(data, ep, gamma) as terminate_episode! applies them to the block a steps! call just
-// produced (sampler.jl:53-57,140-148), on the ring rows [first_row, first_row + n_rows) mod capacity that the block was pushed to.
-int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) { CRUX_PLAIN_ONLY("crux_fill_gae_rows_keys", critic);
-  if (!b || !critic) return CRUX_EINVAL;
-  crux_ctx* c = b->ctx;
-  if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_gae!: buffer lacks the source / target column (%d -> %d)", source, target);
-  if (critic->nd.dims[critic->nd.L] != 1 || critic->nd.dims[0] != b->obs_dim) return crux_fail(c, CRUX_EINVAL, "fill_gae!: critic must map obs(%d) -> 1 (@assert length(Vs) == 1)", b->obs_dim);
-  const int64_t C = b->capacity, n = n_rows;
-  if (first_row < 0 || first_row >= C || n < 0 || n > C) return crux_fail(c, CRUX_EINVAL, "fill_gae!: rows [%lld, +%lld) outside the ring of %lld", (long long)first_row, (long long)n, (long long)C);
-  if (n == 0) return CRUX_OK;
-  const size_t vb = ((4 * (size_t)n + 255) / 256) * 256;
-  char* sc = (char*)crux_scratch(c, 2 * vb + 256);
-  if (!sc) return crux_fail(c, CRUX_ENOMEM, "fill_gae!: scratch");
-  float* Vs = (float*)sc; float* Vsp = (float*)(sc + vb); int32_t* flag = (int32_t*)(sc + 2 * vb);
-  HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
-  const int64_t n1 = first_row + n <= C ? n : C - first_row, n2 = n - n1; const int od = b->obs_dim;
-  crux_prof_begin(c, CRUX_PROF_VALUES);
-  int32_t rc = values(critic, (const float*)b->col[CRUX_COL_S] + first_row * od, n1, Vs); if (rc) return rc;
-  rc = values(critic, (const float*)b->col[CRUX_COL_SP] + first_row * od, n1, Vsp); if (rc) return rc;
-  if (n2 > 0) { rc = values(critic, (const float*)b->col[CRUX_COL_S], n2, Vs + n1); if (rc) return rc;
-    rc = values(critic, (const float*)b->col[CRUX_COL_SP], n2, Vsp + n1); if (rc) return rc; }
-  crux_prof_end(c, CRUX_PROF_VALUES);
-  crux_prof_begin(c, CRUX_PROF_GAE);
-  hipLaunchKernelGGL(k_gae_returns_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[source], (const uint8_t*)b->col[CRUX_COL_DONE],
-                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], (const float*)Vs, (const float*)Vsp, lambda, gamma, n, (float*)b->col[target], (float*)nullptr, flag,
-                     first_row, C, close_last ? 1 : 0, rows_per_env);
-  crux_prof_end(c, CRUX_PROF_GAE);
-  rc = crux_launch_check(c, "k_gae_returns_rows"); if (rc) return rc;
-  int32_t h = 0;
-  HIPCHK(c, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h) return crux_fail(c, CRUX_ENAN, "fill_gae!: NaN advantage (@assert !isnan(A))");
-  return CRUX_OK;
-}
-int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { CRUX_PLAIN_ONLY("crux_fill_gae_rows", critic); return crux_fill_gae_rows_keys(b, critic, lambda, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
-int32_t crux_fill_returns_rows_keys(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last, int32_t source, int32_t target) {
-  if (!b) return CRUX_EINVAL;
-  crux_ctx* c = b->ctx;
-  if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_returns!: buffer lacks the source / target column (%d -> %d)", source, target);
-  const int64_t C = b->capacity, n = n_rows;
-  if (first_row < 0 || first_row >= C || n < 0 || n > C) return crux_fail(c, CRUX_EINVAL, "fill_returns!: rows [%lld, +%lld) outside the ring of %lld", (long long)first_row, (long long)n, (long long)C);
-  if (n == 0) return CRUX_OK;
-  int32_t* flag = (int32_t*)crux_scratch(c, 256);
-  if (!flag) return crux_fail(c, CRUX_ENOMEM, "fill_returns!: scratch");
-  crux_prof_begin(c, CRUX_PROF_GAE);
-  hipLaunchKernelGGL(k_gae_returns_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[source], (const uint8_t*)b->col[CRUX_COL_DONE],
-                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], (const float*)nullptr, (const float*)nullptr, 0.f, gamma, n, (float*)nullptr, (float*)b->col[target], flag,
-                     first_row, C, close_last ? 1 : 0, rows_per_env);
-  crux_prof_end(c, CRUX_PROF_GAE);
-  return crux_launch_check(c, "k_gae_returns_rows");
-}
-int32_t crux_fill_returns_rows(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { return crux_fill_returns_rows_keys(b, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_RETURN); }
-
-int32_t crux_fill_returns_keys(crux_buffer* b, float gamma, int32_t source, int32_t target) {
-  if (!b) return CRUX_EINVAL;
-  crux_ctx* c = b->ctx;
-  if (!f32_scalar_col(b, source) || !f32_scalar_col(b, target)) return crux_fail(c, CRUX_EINVAL, "fill_returns!: buffer lacks the source / target column (%d -> %d)", source, target);
-  const int64_t n = b->elements; if (n == 0) return CRUX_OK;
-  int32_t* flag = (int32_t*)crux_scratch(c, 256);
-  if (!flag) return crux_fail(c, CRUX_ENOMEM, "fill_returns!: scratch");
-  crux_prof_begin(c, CRUX_PROF_GAE);
-  hipLaunchKernelGGL(k_gae_returns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[source], (const uint8_t*)b->col[CRUX_COL_DONE],
-                     (const uint8_t*)b->col[CRUX_COL_EPISODE_END], (const float*)nullptr, (const float*)nullptr, 0.f, gamma, n, (float*)nullptr, (float*)b->col[target], flag);
-  crux_prof_end(c, CRUX_PROF_GAE);
-  return crux_launch_check(c, "k_gae_returns");
-}
-int32_t crux_fill_returns(crux_buffer* b, float gamma) { return crux_fill_returns_keys(b, gamma, CRUX_COL_R, CRUX_COL_RETURN); }
-
 int32_t crux_whiten(crux_buffer* b, int32_t key) {
   if (!b) return CRUX_EINVAL;
   crux_ctx* c = b->ctx;
-  if (!has_col(b, key) || col_elem(b, key) != 4 || col_rows(b, key) != 1) return crux_fail(c, CRUX_EINVAL, "whiten: column %d is not a 1 x N Float32 column", key);
-  const int64_t n = b->elements;
-  if (n < 2) return crux_fail(c, CRUX_EINVAL, "whiten: need at least 2 elements");
-  if (n > (int64_t)JLW_MAXLEAF * 512) return crux_fail(c, CRUX_EUNSUP, "whiten: %lld elements (the pairwise reduction is laid out for at most %d leaves)", (long long)n, JLW_MAXLEAF);
+  const int64_t n = b->elements; const int unfit = whiten_unfit(b, key);
+  if (unfit & WHITEN_COLUMN) return crux_fail(c, CRUX_EINVAL, "whiten: column %d is not a 1 x N Float32 column", key);
+  if (unfit & WHITEN_FEW) return crux_fail(c, CRUX_EINVAL, "whiten: need at least 2 elements");
+  if (unfit & WHITEN_MANY) return crux_fail(c, CRUX_EUNSUP, "whiten: %lld elements (the pairwise reduction is laid out for at most %d leaves)", (long long)n, JLW_MAXLEAF);
   crux_prof_begin(c, CRUX_PROF_WHITEN);
   hipLaunchKernelGGL(k_whiten, dim3(1), dim3(1024), 0, c->stream, (float*)b->col[key], n);
   crux_prof_end(c, CRUX_PROF_WHITEN);
@@ -368,9 +356,9 @@ int32_t crux_nda_adv_check(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, const char
   if (V->ctx != c || Vc->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: the critics and the buffer belong to different contexts", who);
   for (crux_mlp* q : {V, Vc}) if (q->nd.L < 1 || q->nd.dims[q->nd.L] != 1 || q->nd.dims[0] != b->obs_dim)
     return crux_fail(c, CRUX_EINVAL, "%s: both critics must map obs(%d) -> 1 (@assert length(Vs) == 1)", who, b->obs_dim);
-  const int64_t n = b->elements;
-  if (n < 2) return crux_fail(c, CRUX_EINVAL, "%s: whiten needs at least 2 elements", who);
-  if (n > (int64_t)JLW_MAXLEAF * 512) return crux_fail(c, CRUX_EUNSUP, "%s: %lld elements (the pairwise reduction is laid out for at most %d leaves)", who, (long long)n, JLW_MAXLEAF);
+  const int unfit = whiten_unfit(b, CRUX_COL_ADVANTAGE);      // (:cost_advantage has the same shape: both passed the column test above)
+  if (unfit & WHITEN_FEW) return crux_fail(c, CRUX_EINVAL, "%s: whiten needs at least 2 elements", who);
+  if (unfit & WHITEN_MANY) return crux_fail(c, CRUX_EUNSUP, "%s: %lld elements (the pairwise reduction is laid out for at most %d leaves)", who, (long long)b->elements, JLW_MAXLEAF);
   return CRUX_OK;
 }
 // everything enqueued, nothing read: flags_out[0] / [1] are raised by a NaN reward / cost advantage (@assert !isnan(A), sampler.jl:270)
@@ -379,12 +367,9 @@ int32_t crux_nda_adv_enqueue(crux_buffer* b, crux_mlp* V, crux_mlp* Vc, float la
   Carve cv{sc, 0}; float* Vs = cv.take<float>((size_t)n); float* Vsp = cv.take<float>((size_t)n); float* Cs = cv.take<float>((size_t)n); float* Csp = cv.take<float>((size_t)n);
   int32_t* flags = cv.take<int32_t>(2);
   HIPCHK(c, hipMemsetAsync(flags, 0, 256, c->stream));
-  const float* S = (const float*)b->col[CRUX_COL_S]; const float* SP = (const float*)b->col[CRUX_COL_SP];
   crux_prof_begin(c, CRUX_PROF_VALUES);
-  int32_t rc = values(V, S, n, Vs); if (rc) return rc;
-  rc = values(V, SP, n, Vsp); if (rc) return rc;
-  rc = values(Vc, S, n, Cs); if (rc) return rc;
-  rc = values(Vc, SP, n, Csp); if (rc) return rc;
+  int32_t rc = block_values(V, b, whole_buffer(b), Vs, Vsp); if (rc) return rc;
+  rc = block_values(Vc, b, whole_buffer(b), Cs, Csp); if (rc) return rc;
   crux_prof_end(c, CRUX_PROF_VALUES);
   crux_prof_begin(c, CRUX_PROF_GAE);
   hipLaunchKernelGGL(k_nda_gae2, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_R], (const float*)b->col[CRUX_COL_COST], (const uint8_t*)b->col[CRUX_COL_DONE],
@@ -430,26 +415,21 @@ __global__ void k_importance_weight(const float* __restrict__ z, int nout, const
   }
   iw[j] = expf(__fsub_rn(nom, lp[j]));
 }
-// one thread per episode (the one sitting on its last row), as gae_returns_body: rev walks the episode backwards, fwd forwards, cum is the product of the whole episode
-__global__ void k_importance_fills(const float* __restrict__ iw, const uint8_t* __restrict__ ee, int64_t n, float* __restrict__ fwd, float* __restrict__ cum, float* __restrict__ rev,
-                                   int64_t first, int64_t cap, int close_last, int64_t seg) {
-  if (cap <= 0) cap = n;
-  if (seg <= 0) seg = n;
-  auto phys = [&](int64_t k) -> int64_t { const int64_t q = first + k; return q >= cap ? q - cap : q; };
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const bool closed = ee[phys(i)];
-    if (!(closed || i == n - 1 || (i + 1) % seg == 0)) continue;
-    const int64_t k0 = (i / seg) * seg;
-    int64_t start = i; while (start > k0 && !ee[phys(start - 1)]) --start;
-    if (!closed && !close_last) {            // an episode still open at the end of the segment: terminate_episode! never reached it, the fresh data block holds ones
-      for (int64_t k = start; k <= i; ++k) { const int64_t q = phys(k); if (fwd) fwd[q] = 1.f; if (cum) cum[q] = 1.f; if (rev) rev[q] = 1.f; }
+// one thread per episode (the one sitting on the row that ends its run): rev walks the episode backwards, fwd forwards, cum is the product of the whole episode
+__global__ void k_importance_fills(const float* __restrict__ iw, const uint8_t* __restrict__ ee, const ScanRange g, float* __restrict__ fwd, float* __restrict__ cum, float* __restrict__ rev) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.n; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t k0; bool open;
+    if (!g.ends_run(ee, i, k0, open)) continue;
+    int64_t start = i; while (start > k0 && !ee[g.phys(start - 1)]) --start;
+    if (open) {                              // terminate_episode! never reached it, the fresh data block holds ones
+      for (int64_t k = start; k <= i; ++k) { const int64_t q = g.phys(k); if (fwd) fwd[q] = 1.f; if (cum) cum[q] = 1.f; if (rev) rev[q] = 1.f; }
       continue;
     }
     float w = 1.f;
-    if (rev) for (int64_t k = i; k >= start; --k) { const int64_t q = phys(k); w = __fmul_rn(iw[q], w); rev[q] = w; }      // :301-308
+    if (rev) for (int64_t k = i; k >= start; --k) { const int64_t q = g.phys(k); w = __fmul_rn(iw[q], w); rev[q] = w; }      // :301-308
     w = 1.f;
-    for (int64_t k = start; k <= i; ++k) { const int64_t q = phys(k); w = __fmul_rn(iw[q], w); if (fwd) fwd[q] = w; }     // :283-290
-    if (cum) for (int64_t k = start; k <= i; ++k) cum[phys(k)] = w;                                                          // :292-299
+    for (int64_t k = start; k <= i; ++k) { const int64_t q = g.phys(k); w = __fmul_rn(iw[q], w); if (fwd) fwd[q] = w; }     // :283-290
+    if (cum) for (int64_t k = start; k <= i; ++k) cum[g.phys(k)] = w;                                                          // :292-299
   }
 }
 extern "C" int32_t crux_importance_weight_rows(crux_buffer* b, crux_mlp* nominal, int32_t head, int64_t first_row, int64_t n_rows) { CRUX_PLAIN_ONLY("crux_importance_weight_rows", nominal);
@@ -479,8 +459,8 @@ extern "C" int32_t crux_fill_importance_weights_rows(crux_buffer* b, int64_t fir
   if (!has_col(b, CRUX_COL_IMPORTANCE_WEIGHT)) return crux_fail(c, CRUX_EINVAL, "fill_*_importance_weight!: the buffer has no :importance_weight column (@assert haskey(data, :importance_weight), sampler.jl:284)");
   if (n_rows == 0) return CRUX_OK;
   if (first_row < 0 || first_row >= b->capacity || n_rows < 0 || n_rows > b->capacity) return crux_fail(c, CRUX_EINVAL, "fill_*_importance_weight!: rows out of range");
-  hipLaunchKernelGGL(k_importance_fills, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_IMPORTANCE_WEIGHT], (const uint8_t*)b->col[CRUX_COL_EPISODE_END], n_rows,
-                     hf ? (float*)b->col[CRUX_COL_FWD_IMPORTANCE_WEIGHT] : (float*)nullptr, hc ? (float*)b->col[CRUX_COL_CUM_IMPORTANCE_WEIGHT] : (float*)nullptr, hr ? (float*)b->col[CRUX_COL_REV_IMPORTANCE_WEIGHT] : (float*)nullptr,
-                     first_row, b->capacity, close_last, rows_per_env);
+  hipLaunchKernelGGL(k_importance_fills, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_IMPORTANCE_WEIGHT], (const uint8_t*)b->col[CRUX_COL_EPISODE_END],
+                     scan_range(first_row, n_rows, b->capacity, rows_per_env, close_last),
+                     hf ? (float*)b->col[CRUX_COL_FWD_IMPORTANCE_WEIGHT] : (float*)nullptr, hc ? (float*)b->col[CRUX_COL_CUM_IMPORTANCE_WEIGHT] : (float*)nullptr, hr ? (float*)b->col[CRUX_COL_REV_IMPORTANCE_WEIGHT] : (float*)nullptr);
   return crux_launch_check(c, "k_importance_fills");
 }

@@ -214,6 +214,14 @@ def block_case(cid):
     return c
 
 
+def ring_columns(c):
+    """({key: the physical column over rows 0 .. length(b)-1}, length(b)) of the ring once the GPU test has filled it: junk everywhere, the block at block_rows"""
+    rows = block_rows(c["first"], c["n"], c["cap"]); m = min(c["cap"], c["first"] + c["n"]); out = {}
+    for k, junk in c["junk"].items():
+        col = junk.copy(); col[..., rows] = c[k]; out[k] = col[..., :m]
+    return out, m
+
+
 def nan_row(c):
     """a block row that lies past the wrap and inside an episode that ends on :episode_end (closed whatever close_last): a NaN reward there must reach the advantage"""
     k_first_wrapped = c["cap"] - c["first"]

@@ -166,6 +166,27 @@ def test_grid_case_tells_the_wrong_scans_apart(cid, close_last):
     assert cid in (4, 7) or c["empty_segment"] != c["E"] - 1      # the exception above is case 4's alone (case 7 has one segment and no empty one)
 
 
+@pytest.mark.parametrize("cid", [1, 6])
+def test_whole_buffer_cases_tell_the_wrong_whole_buffer_scans_apart(cid):
+    """The whole-buffer fills scan the PHYSICAL rows 0 .. length(b)-1 as one closed segment. On the rings of cases 1 and 6 (test_gpu_block_fills.py) that differs from
+    a scan that leaves the trailing run open (case 1: the last physical row is no :episode_end), from one cut every T rows, and -- case 6, next_ind at 200 -- from the
+    ring's rows scanned in push order."""
+    c = R.block_case(cid); p, m = R.ring_columns(c); ee = p["episode_end"]; T = c["T"]
+    assert m == 390 and (c["first"] + c["n"]) % c["cap"] == {1: 390, 6: 200}[cid]
+    Vs, Vsp = (R.mlp(c["pV"], c["dims"], c["acts"], p[k], F)[0] for k in ("s", "sp"))
+    scans = [("returns", R.returns_block, (p["r"], ee, R.GAMMA)), ("gae", R.gae_block, (p["r"], p["done"], ee, Vs, Vsp, R.LAM, R.GAMMA))]
+    rows = R.block_rows(c["first"], c["n"], c["cap"])            # push order IS block order: block row k lies at physical row rows[k]
+    block_order = [(c["r"], c["episode_end"], R.GAMMA), (c["r"], c["done"], c["episode_end"], *R.case_values(c), R.LAM, R.GAMMA)]
+    for (name, scan, cols), pushed in zip(scans, block_order):
+        truth = scan(*cols, seg=0, close_last=1)
+        assert _differs(scan(*cols, seg=T, close_last=1), truth), (name, "T-row segments")
+        if cid == 1:
+            assert not ee[m - 1] and _differs(scan(*cols, seg=0, close_last=0), truth), (name, "trailing run left open")
+        else:
+            in_push_order = np.empty(m, F); in_push_order[rows] = scan(*pushed, seg=0, close_last=1)
+            assert _differs(in_push_order, truth), (name, "push order")
+
+
 def test_nan_rows_of_the_gpu_test_sit_where_they_must():
     """the NaN-reward rows of test_gpu_block_fills.py: a wrapped block row inside a CLOSED episode (whatever close_last), and a ring row outside the block"""
     for cid in (3, 4):

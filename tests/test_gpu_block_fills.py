@@ -1,4 +1,4 @@
-"""GPU: what every steps! call leaves on the ring rows [first, first + n) mod capacity of the block it produced (csrc/advantage.hip: k_gae_returns_rows,
+"""GPU: what every steps! call leaves on the ring rows [first, first + n) mod capacity of the block it produced (csrc/advantage.hip: k_gae_returns,
 k_importance_weight, k_importance_fills behind crux_fill_gae_rows[_keys], crux_fill_returns_rows[_keys], crux_importance_weight_rows and
 crux_fill_importance_weights_rows) against the plain scans of tests/block_fill_reference.py.
 
@@ -117,6 +117,102 @@ def test_nan_reward_is_reported_from_a_wrapped_row_and_ignored_outside_the_block
         assert "NaN advantage" in (lib.crux_last_error(gpu_ctx.h) or b"").decode()
     finally:
         _put(b, "r", r0)
+
+
+# ---- 1b. the whole-buffer forms: the physical rows 0 .. length(b)-1 as one closed segment, wherever next_ind stands ----------------------------------------------------
+WHOLE_KEYS = ("return", "cost_return", "advantage", "cost_advantage")
+
+
+def _whole_fills(lib, ctx, b, V, Vc, rows=None):
+    """the four fills through the whole-buffer entry points, or through the _rows forms on `rows` = (first_row, n_rows, rows_per_env, close_last)"""
+    cost = (L.COL["cost"], L.COL["cost_return"]), (L.COL["cost"], L.COL["cost_advantage"])
+    if rows is None:
+        rcs = [lib.crux_fill_returns(b.h, R.GAMMA), lib.crux_fill_returns_keys(b.h, R.GAMMA, *cost[0]),
+               lib.crux_fill_gae(b.h, V.h, R.LAM, R.GAMMA), lib.crux_fill_gae_keys(b.h, Vc.h, R.LAM, R.GAMMA, *cost[1])]
+    else:
+        rcs = [lib.crux_fill_returns_rows(b.h, R.GAMMA, *rows), lib.crux_fill_returns_rows_keys(b.h, R.GAMMA, *rows, *cost[0]),
+               lib.crux_fill_gae_rows(b.h, V.h, R.LAM, R.GAMMA, *rows), lib.crux_fill_gae_rows_keys(b.h, Vc.h, R.LAM, R.GAMMA, *rows, *cost[1])]
+    for rc in rcs:
+        ctx.check(rc)
+
+
+@pytest.mark.parametrize("cid", [1, 6])
+def test_whole_buffer_fills_scan_the_physical_rows_as_one_closed_segment(gpu_ctx, cid):
+    """crux_fill_returns[_keys] / crux_fill_gae[_keys] on case 1 (390 rows in a ring of 500, next_ind at 390) and case 6 (a full ring of 390 that wrapped, next_ind at
+    200) against the plain scans of the PHYSICAL columns with seg = 0, close_last = 1; the _rows forms on (0, length(b), 0, 1) write the same bits. What makes the
+    wrong scans (push order, T-row segments, an open trailing run) show on these rows: tests/test_block_fill_reference.py."""
+    g = _ring(gpu_ctx, cid); b, lib = g.buf, gpu_ctx.lib; n = len(b); cap = b.capacity
+    assert (n, cap, b.next_ind - 1) == {1: (390, 500, 390), 6: (390, 390, 200)}[cid]
+    phys = {k: _get(b, k)[..., :n] for k in ("s", "sp", "r", "cost", "done", "episode_end")}
+    r, cost, done, ee = (phys[k][0] for k in ("r", "cost", "done", "episode_end"))
+    want = {"return": R.returns_block(r, ee, R.GAMMA, seg=0, close_last=1), "cost_return": R.returns_block(cost, ee, R.GAMMA, seg=0, close_last=1),
+            "advantage": R.gae_block(r, done, ee, g.V.forward(phys["s"])[0], g.V.forward(phys["sp"])[0], R.LAM, R.GAMMA, seg=0, close_last=1),
+            "cost_advantage": R.gae_block(cost, done, ee, g.Vc.forward(phys["s"])[0], g.Vc.forward(phys["sp"])[0], R.LAM, R.GAMMA, seg=0, close_last=1)}
+    for k in WHOLE_KEYS:
+        _put(b, k, SENTINEL)
+    _whole_fills(lib, gpu_ctx, b, g.V, g.Vc)
+    whole = {k: _get(b, k)[0] for k in WHOLE_KEYS}
+    for k in WHOLE_KEYS:
+        bad = np.flatnonzero(_bits(whole[k][:n]) != _bits(want[k]))
+        assert bad.size == 0, "whole-buffer :%s: %d of %d rows differ, first at physical row %d: %r, expected %r" % (k, bad.size, n, bad[0], whole[k][bad[0]], want[k][bad[0]])
+        assert (_bits(whole[k][n:]) == _bits(SENTINEL)).all(), "whole-buffer :%s: rows past length(b) were written" % k
+    for k in WHOLE_KEYS:
+        _put(b, k, SENTINEL)
+    _whole_fills(lib, gpu_ctx, b, g.V, g.Vc, rows=(0, n, 0, 1))
+    for k in WHOLE_KEYS:
+        assert np.array_equal(_bits(_get(b, k)[0]), _bits(whole[k])), "the _rows form on (0, length(b), 0, 1) and the whole-buffer form differ in :" + k
+
+
+def test_whole_buffer_fills_of_an_empty_buffer_write_nothing(gpu_ctx):
+    b = crux.ExperienceBuffer(crux.ContinuousSpace(R.OBS_DIM), crux.ContinuousSpace(1), 8, EXTRAS, ctx=gpu_ctx)
+    c = R.block_case(1); V = _net(gpu_ctx, c["dims"], c["acts"], c["pV"])
+    assert len(b) == 0
+    for k in WHOLE_KEYS:
+        _put(b, k, SENTINEL)
+    _whole_fills(gpu_ctx.lib, gpu_ctx, b, V, V)                     # every call returns CRUX_OK
+    for k in WHOLE_KEYS:
+        assert (_bits(_get(b, k)) == _bits(SENTINEL)).all(), k
+
+
+def _unequal_pair(ctx, nan_at=None):
+    """two buffers of 96 rows (capacity 128) and 130 rows (full) with critics 4-32-32-1 and 4-16-16-1; :advantage and :return pre-set to the sentinel"""
+    out = []
+    for j, (n, cap, hidden) in enumerate(((96, 128, 32), (130, 130, 16))):
+        rng = np.random.default_rng(3000 + j); dims = [R.OBS_DIM, hidden, hidden, 1]
+        ee = rng.random(n) < 0.05; done = ee & (rng.random(n) < 0.5)
+        r = rng.normal(0, 1, n).astype(F)
+        if nan_at is not None and j == 1:
+            r[nan_at] = np.nan
+        b = crux.ExperienceBuffer(crux.ContinuousSpace(R.OBS_DIM), crux.ContinuousSpace(1), cap, ["return", "advantage"], ctx=ctx)
+        b.push_({"s": rng.normal(0, 1, (R.OBS_DIM, n)).astype(F), "a": rng.uniform(-1, 1, (1, n)).astype(F), "sp": rng.normal(0, 1, (R.OBS_DIM, n)).astype(F),
+                 "r": r, "done": done, "episode_end": ee})
+        assert len(b) == n and ee.sum() >= 2 and not ee[-1]
+        for k in ("return", "advantage"):
+            _put(b, k, SENTINEL)
+        out.append((b, _net(ctx, dims, R.ACTS, R.init_params(dims, rng))))
+    return out
+
+
+def _fill_multi(lib, pairs, with_returns=1):
+    import ctypes as C
+    hb = (C.c_void_p * len(pairs))(*[b.h for b, _ in pairs]); hc = (C.c_void_p * len(pairs))(*[V.h for _, V in pairs])
+    return lib.crux_fill_gae_multi(len(pairs), hb, hc, R.LAM, R.GAMMA, with_returns)
+
+
+def test_fill_gae_multi_of_unequal_buffers_equals_the_single_fills(gpu_ctx):
+    """buffers of different lengths and critics of different widths take crux_fill_gae_multi's one-buffer-after-the-other branch: bit for bit what crux_fill_gae +
+    crux_fill_returns leave on twin buffers (rows past length(b) untouched); a NaN reward in the second buffer is reported as buffer 1's"""
+    lib = gpu_ctx.lib; multi, single = _unequal_pair(gpu_ctx), _unequal_pair(gpu_ctx)
+    gpu_ctx.check(_fill_multi(lib, multi))
+    for j, ((bm, _), (bs, V)) in enumerate(zip(multi, single)):
+        gpu_ctx.check(lib.crux_fill_gae(bs.h, V.h, R.LAM, R.GAMMA)); gpu_ctx.check(lib.crux_fill_returns(bs.h, R.GAMMA))
+        for k in ("advantage", "return"):
+            got, want = _get(bm, k)[0], _get(bs, k)[0]
+            assert np.isfinite(want[:len(bs)]).all() and (_bits(want[len(bs):]) == _bits(SENTINEL)).all()
+            assert np.array_equal(_bits(got), _bits(want)), "buffer %d :%s" % (j, k)
+    assert _fill_multi(lib, _unequal_pair(gpu_ctx, nan_at=57)) == L.ENAN
+    msg = (lib.crux_last_error(gpu_ctx.h) or b"").decode()
+    assert "NaN advantage" in msg and "buffer 1" in msg, msg
 
 
 # ---- 2. the running products ----------------------------------------------------------------------------------------------------------------------------------------
