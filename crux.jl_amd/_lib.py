@@ -171,6 +171,9 @@ SIGNATURES = {
     "crux_cql_critic_step": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, u64, u64, vp]),
     "crux_cql_alpha_step": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp]),
     "crux_cql_conservative": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp, vp, vp]),
+    "crux_cql_critic_step_sigma": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, i32, u64, u64, vp]),      # the three for a two-headed actor (crux_mlp_set_sigma_head)
+    "crux_cql_alpha_step_sigma": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp]),
+    "crux_cql_conservative_sigma": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, u64, u64, vp, vp, vp]),
     "crux_gradient_penalty": (i32, [vp, vp, vp, i64, f32, f32, i32, u64, u64, vp]),
     "crux_iq_step": (i32, [vp, vp, i64, f32, i32, f32, i32, f32, u64, u64, vp, vp]),
     "crux_offgail_d_step": (i32, [vp, P(vp), i32, i64, u64, u64, vp]),

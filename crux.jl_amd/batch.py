@@ -66,8 +66,9 @@ def _param_step(solver, theta, p, mb, base, info):
     _ensure_opt(theta, p)
     raw = np.zeros(L.INFO_N, np.float32)
     if p.loss is cql_alpha_loss:
-        ctx.check(ctx.lib.crux_cql_alpha_step(pi.A.h, pi.C.N1.h, pi.C.N2.h, theta.h, mb.h, int(P["CQL_n_action_samples"]), P["CQL_is_distribution"].lo,
-                                              P["CQL_is_distribution"].hi, float(P["CQL_alpha_thresh"]), solver.noise_seed, base + CTR_CQL_ALPHA, _vp(raw)))
+        step = ctx.lib.crux_cql_alpha_step_sigma if pi.A.two_headed else ctx.lib.crux_cql_alpha_step      # (a two-headed actor got here through CQL(..., two_headed=True))
+        ctx.check(step(pi.A.h, pi.C.N1.h, pi.C.N2.h, theta.h, mb.h, int(P["CQL_n_action_samples"]), P["CQL_is_distribution"].lo,
+                       P["CQL_is_distribution"].hi, float(P["CQL_alpha_thresh"]), solver.noise_seed, base + CTR_CQL_ALPHA, _vp(raw)))
         info.update({p.name + "loss": float(raw[0]), p.name + "grad_norm": float(raw[1]), "CQL alpha": float(raw[L.INFO["alpha"]])})
     elif p.loss is sac_temp_loss:
         ctx.check(ctx.lib.crux_sac_temp_step(pi.A.h, theta.h, mb.h, float(P["SAC_H_target"]), solver.noise_seed, base + CTR_SAC_TEMP, _vp(raw)))
@@ -135,9 +136,10 @@ def _solve_batch_ac(solver, mdp=None):
                 elif y is None:
                     raise NotImplementedError("BatchSolver: a critic without a target_fn has no device implementation")
                 elif c_opt.loss is cql_critic_loss:
-                    ctx.check(lib.crux_cql_critic_step(A.h, Q.N1.h, Q.N2.h, P["CQL_log_alpha"].h, mb.h, y, int(P["CQL_n_action_samples"]), P["CQL_is_distribution"].lo,
-                                                       P["CQL_is_distribution"].hi, float(P["CQL_alpha_thresh"]), 1 if solver.weighted_loss else 0, solver.noise_seed,
-                                                       base + CTR_CQL_CRITIC, _vp(raw)))
+                    step = lib.crux_cql_critic_step_sigma if A.two_headed else lib.crux_cql_critic_step
+                    ctx.check(step(A.h, Q.N1.h, Q.N2.h, P["CQL_log_alpha"].h, mb.h, y, int(P["CQL_n_action_samples"]), P["CQL_is_distribution"].lo,
+                                   P["CQL_is_distribution"].hi, float(P["CQL_alpha_thresh"]), 1 if solver.weighted_loss else 0, solver.noise_seed,
+                                   base + CTR_CQL_CRITIC, _vp(raw)))
                 elif c_opt.loss is double_Q_loss:
                     ctx.check(lib.crux_double_q_step(Q.N1.h, Q.N2.h, mb.h, y, 1 if solver.weighted_loss else 0, _vp(raw)))
                 else:
@@ -188,14 +190,18 @@ def BatchSAC(pi, S, D_train, dN=50, SAC_alpha=1.0, SAC_H_target=None, SAC_alpha_
                        a_opt=TrainingParams(loss=sac_actor_loss, **a), c_opt=TrainingParams(loss=c_loss, **c), target_fn="sac", **kw)
 
 
-def CQL(pi, S, D_train, CQL_alpha=1.0, CQL_is_distribution=None, CQL_alpha_thresh=10.0, CQL_n_action_samples=10, CQL_alpha_opt=None, a_opt=None, c_opt=None, **kw):
+def CQL(pi, S, D_train, CQL_alpha=1.0, CQL_is_distribution=None, CQL_alpha_thresh=10.0, CQL_n_action_samples=10, CQL_alpha_opt=None, a_opt=None, c_opt=None, two_headed=False,
+        **kw):
     """CQL(; pi, solver_type=BatchSAC, CQL_alpha=1f0, CQL_is_distribution=product(Uniform(-1, 1)), CQL_alpha_thresh=10f0, CQL_n_action_samples=10, CQL_alpha_opt,
     a_opt, c_opt) (src/model_free/batch/cql.jl): BatchSAC plus the parameter optimiser CQL_alpha_ on CQL_log_alpha and the critic loss
-    double_Q_loss + conservative_loss. CQL_is_distribution: None (U(-1, 1)^ad) or a UniformBox; anything else is not implemented."""
+    double_Q_loss + conservative_loss. CQL_is_distribution: None (U(-1, 1)^ad) or a UniformBox; anything else is not implemented.
+    two_headed=True: a two-headed actor (logSigma a network on mu's trunk, the SAC_A() of examples/offline rl/hopper_medium.jl) is taken; cql_alpha_loss and cql_critic_loss then
+    go to the crux_cql_*_sigma entries. Without the keyword such an actor is refused by name, as before (core.require_two_headed_opt_in: tests/test_gpu_sigma_head.py::test_refusals
+    asserts that refusal of the plain call). With a constant-logSigma actor the keyword changes nothing."""
     _check_actor_critic(pi, "CQL")
-    if pi.A.two_headed:
-        raise NotImplementedError("CQL: a GaussianPolicy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only; CQL's sampled-action "
-                                  "terms draw from constant logSigma extras")
+    if pi.A.two_headed and not two_headed:
+        raise NotImplementedError("CQL: a %s whose logSigma is a network (two-headed actor) is taken by this solver only when it is asked for with two_headed=True "
+                                  "(the sampled-action terms then draw from logSigma(s): crux_cql_*_sigma); SAC / BatchSAC take it as it is" % type(pi.A).__name__)
     if CQL_is_distribution is None:
         CQL_is_distribution = UniformBox(-1.0, 1.0)
     if not isinstance(CQL_is_distribution, UniformBox):

@@ -404,10 +404,10 @@ class GaussianPolicy(NetworkPolicy):
     """GaussianPolicy(mu::ContinuousNetwork, logSigma) (src/policies.jl:315-350). logSigma an array: the constant trainable log-std. logSigma a Chain (or a ContinuousNetwork)
     that shares every layer but the last with mu: the two-headed form -- one device handle whose last layer has 2 ad rows, [mu; logSigma(s)] (`two_headed`, `act_dim`).
     The two-headed form is taken by SAC / BatchSAC, the Sampler, the methods action / exploration / logpdf / entropy below, and the policy-gradient learners: PPO, A2C and
-    REINFORCE (ppo_loss, a2c_loss, reinforce_loss) and BC with logpdf_bc_loss, all on the dense-engine learner (csrc/train_dense.hip: k_pg_head_sigma); those four solver
-    constructors take it when called with two_headed=True and refuse it by name otherwise, as before (train_ / batch_train_ need no keyword). LagrangePPO, ASAF,
-    mse_action_loss, CustomLoss, a DiagonalFisherRegularizer / continual_learning, the replica-group and multi-seed forms of policy_gradient_training, CQL, the off-policy
-    imitation learners (SQIL, OffPolicyGAIL, AdRIL) and MixtureNetwork refuse it by name. Separate (non-sharing) mu and logSigma networks are not implemented.
+    REINFORCE (ppo_loss, a2c_loss, reinforce_loss) and BC with logpdf_bc_loss, all on the dense-engine learner (csrc/train_dense.hip: k_pg_head_sigma), CQL (the
+    crux_cql_*_sigma entries, csrc/cql.hip) and ASAF (csrc/asaf.hip: k_asaf_head_sigma); those six solver constructors take it when called with two_headed=True and refuse it
+    by name otherwise, as before (train_ / batch_train_ need no keyword). LagrangePPO, mse_action_loss, CustomLoss, a DiagonalFisherRegularizer / continual_learning, the
+    replica-group and multi-seed forms of policy_gradient_training, the off-policy imitation learners (SQIL, OffPolicyGAIL, AdRIL) and MixtureNetwork refuse it by name. Separate (non-sharing) mu and logSigma networks are not implemented.
     The entropy bonus of a two-headed plain GaussianPolicy is the reference's, literally: entropy(pi, s) sums logSigma(s) over the WHOLE minibatch (policies.jl:348 has no
     `dims`), so lambda_e weighs a sum over columns, not a mean; SquashedGaussianPolicy sums per column. The reference's own Gaussian PPO examples run with lambda_e = 0."""
     head = "gaussian"
@@ -576,34 +576,36 @@ def refuse_standalone(pi, who):
 
 
 def refuse_two_headed(pi, who):
-    """Two-headed Gaussian actors (logSigma a network on mu's trunk) are taken by SAC / BatchSAC, the Sampler and the policy-gradient learners (PPO, A2C, REINFORCE, BC with
-    logpdf_bc_loss). Everything else calls this: LagrangePPO, ASAF, CQL's sampled-action terms and the mixture head read constant logSigma extras, a DiagonalFisherRegularizer
-    and the replica-group / multi-seed learners have no two-headed head, and the off-policy imitation learners (SQIL, OffPolicyGAIL, AdRIL) are not covered by tests with such
+    """Two-headed Gaussian actors (logSigma a network on mu's trunk) are taken by SAC / BatchSAC, the Sampler, the policy-gradient learners (PPO, A2C, REINFORCE, BC with
+    logpdf_bc_loss), CQL and ASAF (the last six when asked for with two_headed=True: require_two_headed_opt_in). Everything else calls this: LagrangePPO and the mixture head
+    read constant logSigma extras, a DiagonalFisherRegularizer and the replica-group / multi-seed learners have no two-headed head, and the off-policy imitation learners (SQIL, OffPolicyGAIL, AdRIL) are not covered by tests with such
     an actor. Raised by name, before any device call."""
     for q in ([] if pi is None else _leaves(pi)):
         if getattr(q, "two_headed", False):
-            raise NotImplementedError("%s: a %s whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC, PPO, A2C, REINFORCE and BC (logpdf_bc_loss) only; "
+            raise NotImplementedError("%s: a %s whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC, PPO, A2C, REINFORCE, BC (logpdf_bc_loss), CQL and ASAF only; "
                                       "this learner needs the constant-logSigma form" % (who, type(q).__name__))
 
 
-_TWO_HEADED_LOSSES = ("ppo", "a2c", "reinforce", "logpdf_bc")
+_TWO_HEADED_LOSSES = ("ppo", "a2c", "reinforce", "logpdf_bc", "asaf")
 
 
 def require_two_headed_opt_in(pi, who, asked):
-    """The solver constructors (OnPolicySolver and PPO / A2C / REINFORCE through it, BC) take a two-headed actor only when called with two_headed=True: without the keyword
-    they refuse it by name, as they did before the policy-gradient learners had a head for it, so code that relied on that refusal keeps it.
-    The keyword has no other purpose: tests/test_gpu_sigma_head.py::test_refusals asserts that the plain calls PPO(ActorCritic(pi, critic), S) and BC(pi, S, D) raise for such an
-    actor. When those two assertions go, this function, the two_headed parameters of OnPolicySolver and BC and their uses can go with them: the constructors then simply accept."""
+    """The solver constructors (OnPolicySolver and PPO / A2C / REINFORCE / ASAF through it, BC; CQL has the same rule in batch.py) take a two-headed actor only when called
+    with two_headed=True: without the keyword they refuse it by name, as they did before the learners had a head for it, so code that relied on that refusal keeps it.
+    The keyword has no other purpose: tests/test_gpu_sigma_head.py::test_refusals asserts that the plain calls PPO(ActorCritic(pi, critic), S), BC(pi, S, D) and CQL(ac, S, D) raise
+    for such an actor, tests/test_gpu_sigma_pg.py::test_host_mirror_refuses_by_name that ASAF(pi, S, b) does. When those assertions go, this function, the two_headed parameters
+    of OnPolicySolver, BC, CQL and ASAF and their uses can go with them: the constructors then simply accept."""
     if asked:
         return
     for q in ([] if pi is None else _leaves(pi)):
         if getattr(q, "two_headed", False):
             raise NotImplementedError("%s: a %s whose logSigma is a network (two-headed actor) is taken by this solver only when it is asked for with two_headed=True "
-                                      "(ppo_loss, a2c_loss, reinforce_loss, logpdf_bc_loss on the dense-engine learner); SAC / BatchSAC take it as it is" % (who, type(q).__name__))
+                                      "(ppo_loss, a2c_loss, reinforce_loss, logpdf_bc_loss on the dense-engine learner, asaf_loss); SAC / BatchSAC take it as it is" % (who, type(q).__name__))
 
 
 def _refuse_two_headed_params(pi, p, who):
-    """the TrainingParams a two-headed actor can be trained with: one of the four losses of k_pg_head_sigma, no CustomLoss, no DiagonalFisherRegularizer"""
+    """the TrainingParams a two-headed actor can be trained with: one of the four losses of k_pg_head_sigma or asaf_loss (an OnPolicySolver's a_opt: policy_gradient_training
+    sends it to batch_train_asaf_), no CustomLoss, no DiagonalFisherRegularizer"""
     if not getattr(pi, "two_headed", False) or p is None:
         return
     if isinstance(p.loss, CustomLoss):

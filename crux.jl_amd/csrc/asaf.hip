@@ -13,6 +13,8 @@
 //                 w ((u - mu)^2 / sigma^2 [logSigma inside the clamp] - 1) per logSigma slot -- wave sums added into LDS in a fixed order, no per-thread arrays
 //   k_asaf_gx     the block partials added in block order: g[logSigma] = sum - 0.1 (the entropy's share), the two softplus sums; poisoned when the NaN flag is set
 //   dense backward, Sumsq2Op (norm over the raw gradient), k_asaf_info, k_asaf_clip (optional: clamp to +-clip_value after the norm, ClipValue before Adam), gated Adam
+// A two-headed policy (crux_mlp_set_sigma_head: logSigma(s) from the output rows [ad, 2 ad)) takes k_asaf_logpdf_sigma / k_asaf_head_sigma / k_asaf_sums_sigma / k_asaf_info_sigma
+// in the same places: the seed is [dmu; dl] per column, the entropy is a sum over the rollout columns, and there is no logSigma-extras gradient.
 // No float atomics anywhere: two identical calls give identical bits. The engine's relu maps NaN to 0 where NNlib's propagates it, so NaN inputs are flagged and the head
 // poisons what it forms (the idiom of k_iq_expand / k_iq_head).
 // The chain (crux_asaf_batch_train) enqueues epochs x (crux_buffer_shuffle, every minibatch step) with one host synchronisation at the end: chain.h holds the loop, the
@@ -105,14 +107,87 @@ __global__ __launch_bounds__(256) void k_asaf_clip(float* __restrict__ g, float 
   const float v = g[i]; g[i] = v > c ? c : (v < -c ? -c : v);
 }
 
+// ---- two-headed actors (crux_mlp_set_sigma_head): z = pi(s) [2 ad x columns], mu = z[d], l = logSigma(s) = z[ad + d] -----------------------------------------------------
+// logpdf(pi, s, a) of one column: SigmaLogpdfOp's arithmetic (sac.hip) restated; *sum_l (or NULL) receives sum_d l, the column's share of the entropy
+__device__ __forceinline__ float asaf_logpdf_sigma(const float* __restrict__ zj, const float* __restrict__ av, int ad, float sq, float* sum_l) {
+  float acc = 0.f, sl = 0.f;
+  for (int d = 0; d < ad; ++d) {
+    const float m = zj[d], l = zj[ad + d]; sl = __fadd_rn(sl, l);
+    const float sg = expf(sq > 0.f ? sq_clampls(l) : l); const float u = sq > 0.f ? sq_untanh(av[d], sq) : av[d];
+    const float s2 = __fmul_rn(sg, sg), df = __fsub_rn(u, m);
+    float tt = __fsub_rn(__fsub_rn(-(__fmul_rn(df, df)) / __fmul_rn(2.f, s2), 0.9189385332046727f), l);
+    if (sq > 0.f) tt = __fsub_rn(tt, sq_corr(u));
+    acc = __fadd_rn(acc, tt);
+  }
+  if (sum_l) *sum_l = sl;
+  return acc;
+}
+// out[j] = logpdf(pi, s_j, a_j) over n columns of z [2 ad x n]; a NaN in s_j gives NaN (the engine's relu would have dropped it)
+__global__ __launch_bounds__(256) void k_asaf_logpdf_sigma(const float* __restrict__ z, const float* __restrict__ s, const float* __restrict__ a, int od, int ad, float sq, int64_t n,
+                                                           float* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; if (j >= n) return;
+  bool bad = false; for (int e = 0; e < od; ++e) { const float v = s[j * od + e]; bad = bad || v != v; }
+  const float lp = asaf_logpdf_sigma(z + j * 2 * ad, a + j * ad, ad, sq, nullptr);
+  out[j] = bad ? NAN : lp;
+}
+// z [2 ad x (n + N_E)]; dz the same shape, the seed [dmu; dl] of crux_dense_backward (logSigma is per column: no row sums, no extras gradient). With w = dL/dlogpdf as in
+// k_asaf_head: dmu = w (u - mu) / sigma^2, dl = w ((u - mu)^2 / sigma^2 [l inside the clamp when squashed] - 1) - 0.1 ce [rollout column]; ce = d mean(entropy(pi, s)) / dl
+// = 1 for the GaussianPolicy (entropy sums logSigma(s) over the whole matrix, policies.jl:348: one scalar) and 1 / n for the squashed one (per column, :398) -- the reference's
+// own two forms, as in train_dense.hip's two-headed head. part [ASAF_BLOCKS x 3]: this block's share of sum softplus (expert), sum softplus (policy), sum of l over the rollout columns
+__global__ __launch_bounds__(256) void k_asaf_head_sigma(const float* __restrict__ z, const float* __restrict__ A, int64_t off, int64_t n, const float* __restrict__ gG, const float* __restrict__ AE,
+                                                         int64_t NE, const float* __restrict__ gE, int ad, float sq, const int32_t* __restrict__ nanflag, float* __restrict__ dz,
+                                                         double* __restrict__ part) {
+  __shared__ double acc[4][3];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane < 3) acc[wv][lane] = 0.0;
+  __syncthreads();
+  const bool poison = nanflag[0] != 0; const int64_t NC = n + NE; const float wg = 1.f / (float)n, we = 1.f / (float)NE; const float ge = 0.1f * (sq > 0.f ? wg : 1.f);
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < NC; base += (int64_t)ASAF_BLOCKS * 256) {      // the bound is the block's: every lane takes part in every wave sum
+    const int64_t j = base + threadIdx.x; const bool on = j < NC, ex = j >= n;
+    const float* zj = z + (on ? j : 0) * 2 * ad; const float* av = !on ? A + off * ad : (ex ? AE + (j - n) * ad : A + (off + j) * ad);
+    float sp = 0.f, sl = 0.f;
+    if (on) { const float l = asaf_logpdf_sigma(zj, av, ad, sq, &sl); const float x = ex ? gE[j - n] - l : l - gG[off + j];
+      sp = sq_softplus(x); const float sg = 1.f / (1.f + expf(-x)); const float w = ex ? -(sg * we) : sg * wg;
+      float* dj = dz + j * 2 * ad;
+      for (int k = 0; k < ad; ++k) { const float lk = zj[ad + k]; const float sk = expf(sq > 0.f ? sq_clampls(lk) : lk), s2 = sk * sk; const float uk = sq > 0.f ? sq_untanh(av[k], sq) : av[k];
+        const float d = uk - zj[k]; const float inr = (sq > 0.f && !(lk >= -5.f && lk <= 2.f)) ? 0.f : 1.f;      // d sigma / d l = 0 outside the clamp; the - l term is unclamped
+        dj[k] = poison ? NAN : w * (d / s2);
+        dj[ad + k] = poison ? NAN : w * (((d * d) / s2) * inr - 1.f) - (ex ? 0.f : ge); } }
+    double v = wave_sum_d(on && ex ? (double)sp : 0.0); if (lane == 0) acc[wv][0] += v;
+    v = wave_sum_d(on && !ex ? (double)sp : 0.0); if (lane == 0) acc[wv][1] += v;
+    v = wave_sum_d(on && !ex ? (double)sl : 0.0); if (lane == 0) acc[wv][2] += v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) part[(int64_t)blockIdx.x * 3 + threadIdx.x] = ((acc[0][threadIdx.x] + acc[1][threadIdx.x]) + acc[2][threadIdx.x]) + acc[3][threadIdx.x];
+}
+// the block partials in block order: stats[0] = sum softplus (expert), stats[1] = sum softplus (policy), stats[2] = sum of logSigma(s) over the rollout columns
+__global__ __launch_bounds__(64) void k_asaf_sums_sigma(const double* __restrict__ part, const int32_t* __restrict__ nanflag, double* __restrict__ stats) {
+  const int k = threadIdx.x; if (k >= 3) return;
+  double t = 0; for (int b = 0; b < ASAF_BLOCKS; ++b) t += part[(int64_t)b * 3 + k];
+  if (nanflag[0] != 0) t = NAN;
+  stats[k] = t;
+}
+// k_asaf_info for the two-headed head: entropy = mean(entropy(pi, s)) as the loss uses it, 1.4189385 + sum(l) (Gaussian) or 1.4189385 + sum(l) / n (squashed)
+__global__ void k_asaf_info_sigma(const double* __restrict__ st, const double* __restrict__ ssq, int64_t n, int64_t NE, float sq, const int32_t* __restrict__ status,
+                                  float* __restrict__ dinfo, float* __restrict__ aout) {
+  if (threadIdx.x != 0) return;
+  ssq_finalize(ssq);
+  if (status[0] == CRUX_ENAN) return;
+  const float H = 1.4189385332046727f + (float)(sq > 0.f ? st[2] / (double)n : st[2]);
+  const float pe = (float)(st[0] / (double)NE), pp = (float)(st[1] / (double)n);
+  dinfo[CRUX_INFO_LOSS] = (pe + pp) - 0.1f * H; dinfo[CRUX_INFO_GRAD_NORM] = (float)sqrt(ssq[0]); dinfo[CRUX_INFO_ENTROPY] = H;
+  aout[0] = H; aout[1] = pe; aout[2] = pp;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------------------------
 #define ASAF_SMALL 1536      // per step: stats 256 B | sum-of-squares partials 768 B | NaN flag 256 B | spare 256 B
 struct AsafBufs { float* X; float* dy; double* part; char* small; };
-static size_t asaf_bytes(int od, int ad, int64_t NC) {
-  return Carve::span<float>((size_t)od * NC) + Carve::span<float>((size_t)ad * NC) + Carve::span<double>((size_t)ASAF_BLOCKS * (ASAF_MAXAD + 2)) + ASAF_SMALL;
+static inline int asaf_seed_rows(const crux_mlp* pi, int ad) { return pi->sigma_head ? 2 * ad : ad; }      // dy rows: [dmu] or the two-headed [dmu; dl]
+static size_t asaf_bytes(int od, int zr, int64_t NC) {
+  return Carve::span<float>((size_t)od * NC) + Carve::span<float>((size_t)zr * NC) + Carve::span<double>((size_t)ASAF_BLOCKS * (ASAF_MAXAD + 2)) + ASAF_SMALL;
 }
-static AsafBufs asaf_carve(Carve& cv, int od, int ad, int64_t NC) {
-  AsafBufs ab; ab.X = cv.take<float>((size_t)od * NC); ab.dy = cv.take<float>((size_t)ad * NC); ab.part = cv.take<double>((size_t)ASAF_BLOCKS * (ASAF_MAXAD + 2));
+static AsafBufs asaf_carve(Carve& cv, int od, int zr, int64_t NC) {
+  AsafBufs ab; ab.X = cv.take<float>((size_t)od * NC); ab.dy = cv.take<float>((size_t)zr * NC); ab.part = cv.take<double>((size_t)ASAF_BLOCKS * (ASAF_MAXAD + 2));
   ab.small = cv.take<char>(ASAF_SMALL); return ab;
 }
 static int32_t asaf_check_pi(crux_ctx* c, const crux_mlp* pi, const crux_buffer* b, const char* who) {
@@ -120,6 +195,11 @@ static int32_t asaf_check_pi(crux_ctx* c, const crux_mlp* pi, const crux_buffer*
   if (b->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: the policy and the buffer belong to different contexts", who);
   if (b->act_kind != CRUX_ACTION_CONTINUOUS) return crux_fail(c, CRUX_EINVAL, "%s: needs a continuous action column (the categorical head is not implemented)", who);
   const NetDesc& nd = pi->nd;
+  if (pi->sigma_head) {      // two-headed: [mu; logSigma(s)] rows, no extras (check_sac's rule)
+    if (nd.dims[0] != b->obs_dim || nd.dims[nd.L] != 2 * b->act_dim || nd.n_extra != 0 || b->act_dim > ASAF_MAXAD)
+      return crux_fail(c, CRUX_EINVAL, "%s: a two-headed policy must map %d -> 2 x %d (mu rows, then logSigma rows) with no extras (act_dim at most %d)", who, b->obs_dim, b->act_dim, ASAF_MAXAD);
+    return CRUX_OK;
+  }
   if (nd.n_extra == 0) return crux_fail(c, CRUX_EUNSUP, "%s: the policy must be a GaussianPolicy or SquashedGaussianPolicy (a handle with trailing logSigma extras)", who);
   if (nd.dims[0] != b->obs_dim || nd.dims[nd.L] != b->act_dim || nd.n_extra != b->act_dim || b->act_dim > ASAF_MAXAD)
     return crux_fail(c, CRUX_EINVAL, "%s: the policy must map %d -> %d with %d logSigma entries (at most %d)", who, b->obs_dim, b->act_dim, b->act_dim, ASAF_MAXAD);
@@ -146,13 +226,20 @@ static int32_t asaf_enqueue_step(crux_mlp* pi, const crux_buffer* b, int64_t off
   hipLaunchKernelGGL(k_asaf_cols, dim3(nblk(NC)), dim3(256), 0, c->stream, (const float*)b->col[CRUX_COL_S], A, off, n, (const float*)demo->col[CRUX_COL_S], AE, NE, od, ad, ab.X, nanflag);
   int32_t rc = crux_launch_check(c, "k_asaf_cols"); if (rc) return rc;
   rc = crux_dense_forward(pi, ab.X, NC, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_asaf_head, dim3(ASAF_BLOCKS), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, nd.L), A, off, n, d_gG, AE, NE, d_gE, ls, ad, pi->squash, (const int32_t*)nanflag, ab.dy, ab.part);
-  hipLaunchKernelGGL(k_asaf_gx, dim3(1), dim3(128), 0, c->stream, (const double*)ab.part, ad, (const int32_t*)nanflag, pi->g + nd.xoff, stats);
+  const bool two = pi->sigma_head;
+  if (two) {
+    hipLaunchKernelGGL(k_asaf_head_sigma, dim3(ASAF_BLOCKS), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, nd.L), A, off, n, d_gG, AE, NE, d_gE, ad, pi->squash, (const int32_t*)nanflag, ab.dy, ab.part);
+    hipLaunchKernelGGL(k_asaf_sums_sigma, dim3(1), dim3(64), 0, c->stream, (const double*)ab.part, (const int32_t*)nanflag, stats);
+  } else {
+    hipLaunchKernelGGL(k_asaf_head, dim3(ASAF_BLOCKS), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, nd.L), A, off, n, d_gG, AE, NE, d_gE, ls, ad, pi->squash, (const int32_t*)nanflag, ab.dy, ab.part);
+    hipLaunchKernelGGL(k_asaf_gx, dim3(1), dim3(128), 0, c->stream, (const double*)ab.part, ad, (const int32_t*)nanflag, pi->g + nd.xoff, stats);
+  }
   rc = crux_launch_check(c, "k_asaf_head"); if (rc) return rc;
   Sumsq2Fix fx{};
   rc = crux_dense_backward(pi, ab.X, NC, ab.dy, 1.0f, true, nullptr, c->stream, &fx, 0); if (rc) return rc;
   crux_launch<Sumsq2Op>(SUMSQ_BLOCKS, 256, c->stream, pi->g, (int64_t)nd.n_params, (float*)nullptr, (int64_t)0, ssq, fx);
-  hipLaunchKernelGGL(k_asaf_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, n, NE, ls, ad, (const int32_t*)status, row, row + CRUX_INFO_N);
+  if (two) hipLaunchKernelGGL(k_asaf_info_sigma, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, n, NE, pi->squash, (const int32_t*)status, row, row + CRUX_INFO_N);
+  else hipLaunchKernelGGL(k_asaf_info, dim3(1), dim3(1), 0, c->stream, (const double*)stats, (const double*)ssq, n, NE, ls, ad, (const int32_t*)status, row, row + CRUX_INFO_N);
   if (clip > 0.f && clip < INFINITY) hipLaunchKernelGGL(k_asaf_clip, dim3(nblk(nd.n_params)), dim3(256), 0, c->stream, pi->g, clip, (int64_t)nd.n_params);
   rc = crux_launch_check(c, "k_asaf_info"); if (rc) return rc;
   return adam_gated(pi, ssq, status);
@@ -170,7 +257,8 @@ int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int6
   const int od = buf->obs_dim, ad = buf->act_dim;
   const float* S = (const float*)buf->col[CRUX_COL_S] + first_row * od; const float* A = (const float*)buf->col[CRUX_COL_A] + first_row * ad;
   rc = crux_dense_forward(pi, S, n_rows, c->stream); if (rc) return rc;
-  hipLaunchKernelGGL(k_asaf_logpdf, dim3(nblk(n_rows)), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, pi->nd.L), S, A, (const float*)(pi->p + pi->nd.xoff), od, ad, pi->squash, n_rows, d_out);
+  if (pi->sigma_head) hipLaunchKernelGGL(k_asaf_logpdf_sigma, dim3(nblk(n_rows)), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, pi->nd.L), S, A, od, ad, pi->squash, n_rows, d_out);
+  else hipLaunchKernelGGL(k_asaf_logpdf, dim3(nblk(n_rows)), dim3(256), 0, c->stream, (const float*)crux_dense_act(pi, pi->nd.L), S, A, (const float*)(pi->p + pi->nd.xoff), od, ad, pi->squash, n_rows, d_out);
   rc = crux_launch_check(c, "k_asaf_logpdf"); if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return CRUX_OK;
@@ -181,9 +269,9 @@ int32_t crux_asaf_actor_step(crux_mlp* pi, crux_buffer* buf, int64_t off, int64_
   crux_ctx* c = pi->ctx; const char* who = "asaf_actor_loss";
   int32_t rc = asaf_check_step(c, pi, buf, off, n, demo, who); if (rc) return rc;
   const int od = buf->obs_dim, ad = buf->act_dim; const int64_t NC = n + demo->elements;
-  const size_t bytes = asaf_bytes(od, ad, NC) + 512;
+  const size_t bytes = asaf_bytes(od, asaf_seed_rows(pi, ad), NC) + 512;
   Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
-  const AsafBufs ab = asaf_carve(cv, od, ad, NC); float* row = cv.take<float>(ASAF_ROW); int32_t* status = cv.take<int32_t>(1);
+  const AsafBufs ab = asaf_carve(cv, od, asaf_seed_rows(pi, ad), NC); float* row = cv.take<float>(ASAF_ROW); int32_t* status = cv.take<int32_t>(1);
   HIPCHK(c, hipMemsetAsync(row, 0, 512, c->stream));
   rc = asaf_enqueue_step(pi, buf, off, n, d_gG, demo, d_gE, clip_value, ab, row, status); if (rc) return rc;
   return finish_step(c, row, row + CRUX_INFO_N, ASAF_NOUT, status, info_out, asaf_out, who);
@@ -202,9 +290,9 @@ int32_t crux_asaf_batch_train(crux_mlp* pi, crux_buffer* buf, crux_buffer* demo,
   rc = ensure_ws(pi, NC); if (rc) return rc;      // the workspace must not be re-allocated between the steps
   // one scratch block for the whole chain, its own pieces behind the shuffles' staging (chain.h)
   ChainHead hd{ASAF_ROW}; const size_t front = shuffle_front(buf);
-  const size_t bytes = front + asaf_bytes(od, ad, NC) + hd.bytes(epochs);
+  const size_t bytes = front + asaf_bytes(od, asaf_seed_rows(pi, ad), NC) + hd.bytes(epochs);
   char* base = (char*)crux_scratch(c, bytes); if (!base) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
-  Carve cv{base + front, 0}; const AsafBufs ab = asaf_carve(cv, od, ad, NC); hd.carve(cv, epochs);
+  Carve cv{base + front, 0}; const AsafBufs ab = asaf_carve(cv, od, asaf_seed_rows(pi, ad), NC); hd.carve(cv, epochs);
   rc = hd.zero(c); if (rc) return rc;
   int64_t total = 0; int epochs_run = 0;
   rc = chain_epochs(epochs, (len + batch_size - 1) / batch_size, max_batches,

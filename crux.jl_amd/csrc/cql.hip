@@ -50,6 +50,46 @@ __global__ __launch_bounds__(256) void k_cql_expand(const float* __restrict__ mu
   if (bad) atomicOr((int*)nanflag, 1);
 }
 
+// The same matrix for a two-headed actor (crux_mlp_set_sigma_head): z = actor(s) [2 ad x B], mu = z[d], logSigma(s) = z[ad + d]. Policy sample k of column j restates
+// SigmaExploreOp (sac.hip) operation for operation on the stream (k B + j) ad + d, so block k = 0 and its logprob are crux_sigma_head_explore's bits; ascale > 0 is the
+// squashed head (sigma = exp(clamp(l, -5, 2)), a = ascale tanh(u), the tanh correction, -l unclamped: policies.jl:374-396). Data and uniform blocks as in k_cql_expand.
+__global__ __launch_bounds__(256) void k_cql_expand_sigma(const float* __restrict__ z, const float* __restrict__ s, const float* __restrict__ a, int od, int ad, int64_t B, int N, float ascale,
+                                                          float lo, float hi, uint64_t seed, uint64_t counter, float* __restrict__ sa, float* __restrict__ lp, float* __restrict__ samples,
+                                                          int32_t* __restrict__ nanflag) {
+  const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; if (col >= (int64_t)(1 + 2 * N) * B) return;
+  const int blk = (int)(col / B); const int64_t j = col - (int64_t)blk * B; const int sd = od + ad;
+  float* o = sa + col * sd;
+  for (int k = 0; k < od; ++k) o[k] = s[j * od + k];
+  const int64_t q = col - B;                                            // (blk - 1) B + j: the sample's slot in lp / samples
+  if (blk == 0) {
+    for (int d = 0; d < ad; ++d) o[od + d] = a[j * ad + d];
+  } else if (blk <= N) {
+    const int k = blk - 1; const float* zj = z + j * 2 * ad; float acc = 0.f;
+    for (int d = 0; d < ad; ++d) {                                      // SigmaExploreOp (sac.hip), stream (k B + j) ad + d
+      const float m = zj[d], l = zj[ad + d]; const float sg = expf(ascale > 0.f ? sq_clampls(l) : l);
+      const float e = sac_randn(seed, counter, (uint32_t)(((int64_t)k * B + j) * ad + d));
+      const float u = __fadd_rn(__fmul_rn(e, sg), m); const float s2 = __fmul_rn(sg, sg), df = __fsub_rn(u, m);
+      float t = __fsub_rn(__fsub_rn(-(__fmul_rn(df, df)) / __fmul_rn(2.f, s2), 0.9189385332046727f), l);
+      if (ascale > 0.f) t = __fsub_rn(t, sq_corr(u));
+      acc = __fadd_rn(acc, t);
+      const float av = ascale > 0.f ? __fmul_rn(ascale, tanhf(u)) : u;
+      o[od + d] = av; if (samples) samples[q * ad + d] = av;
+    }
+    lp[q] = acc;
+  } else {
+    const int k = blk - 1 - N; const double dlo = (double)lo, w = (double)hi - (double)lo;
+    for (int d = 0; d < ad; ++d) {
+      const crux_u32x4 x = crux_philox(seed, counter, (uint32_t)(((int64_t)k * B + j) * ad + d), CRUX_RNG_CQL_UNIFORM);
+      const float av = (float)(dlo + w * crux_u32x2_to_f64(x.v[0], x.v[1]));
+      o[od + d] = av; if (samples) samples[q * ad + d] = av;
+    }
+    lp[q] = (float)(-(double)ad * log(w));
+  }
+  bool bad = blk > 0 && lp[q] != lp[q];                                  // the NaN flag of k_cql_expand
+  for (int r = 0; r < sd; ++r) bad = bad || o[r] != o[r];
+  if (bad) atomicOr((int*)nanflag, 1);
+}
+
 // ---- the head: log-sum-exp over the 2N samples of every state, dL/dQ seeds, reductions (one block of 256, fixed order) -------------------------------------------
 // stats: [0] mean lse, [1] mean qbar(s, a_data), [2] beta, [3] beta (5 L - thresh), [4] double_Q_loss, [5] Q1avg, [6] Q2avg, [7] exp(log_alpha) (unclamped)
 // dy (critic step only): sample columns 5 beta 0.5 softmax_k / B for both nets; data columns 0.5 * 2 (Q_t - y) w / B - 5 beta 0.5 / B
@@ -186,16 +226,26 @@ static int32_t cql_backward(crux_mlp* n, const float* sa, int64_t NB, const floa
 
 // expand + forward of both nets + head: shared by the three entry points. dy1 / dy2 / y NULL: no seeds (alpha step, conservative value)
 struct CqlBufs : StepSmall { float* sa; float* lp; float* dy1; float* dy2; float* part; };
-static int32_t cql_check(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
-  if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
-  // check_sac takes a two-headed actor (crux_mlp_set_sigma_head) for the SAC entries; k_cql_expand reads a constant logSigma from the extras and [ad x B] means, so not here
-  if (actor && actor->sigma_head) return crux_fail(c, CRUX_EUNSUP, "%s: CQL's sampled-action terms are not implemented for a two-headed actor (logSigma network); use a constant logSigma", who);
-  int32_t rc = check_sac(c, actor, q1, q2, la, b, who); if (rc) return rc;
+static int32_t cql_ranges(crux_ctx* c, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
   if (n_samples < 1 || n_samples > 1024) return crux_fail(c, CRUX_EINVAL, "%s: CQL_n_action_samples = %d out of range [1, 1024]", who, n_samples);
   if (!(hi > lo)) return crux_fail(c, CRUX_EINVAL, "%s: the IS box needs lo < hi (got %g, %g)", who, (double)lo, (double)hi);
   const int64_t NB = (int64_t)(1 + 2 * n_samples) * b->elements;
   if (NB > (1 << 20) || (int64_t)2 * n_samples * b->elements * b->act_dim >= ((int64_t)1 << 32)) return crux_fail(c, CRUX_EINVAL, "%s: (1 + 2N) B = %lld columns is too many", who, (long long)NB);
   return CRUX_OK;
+}
+static int32_t cql_check(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
+  if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
+  // check_sac takes a two-headed actor (crux_mlp_set_sigma_head) for the SAC entries; k_cql_expand reads a constant logSigma from the extras and [ad x B] means, so not here
+  if (actor && actor->sigma_head) return crux_fail(c, CRUX_EUNSUP, "%s: CQL's sampled-action terms are not implemented for a two-headed actor (logSigma network); use a constant logSigma", who);
+  int32_t rc = check_sac(c, actor, q1, q2, la, b, who); if (rc) return rc;
+  return cql_ranges(c, b, n_samples, lo, hi, who);
+}
+// the _sigma entries: a two-headed actor only ("not two-headed" is sigma_head_check's CRUX_EINVAL), then check_sac's two-headed branch (od -> 2 ad, no extras, ad <= 64)
+static int32_t cql_check_sigma(crux_ctx* c, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int n_samples, float lo, float hi, const char* who) {
+  if (!actor->sigma_head) return crux_fail(c, CRUX_EINVAL, "%s: the actor handle is not two-headed (crux_mlp_set_sigma_head); the plain entry takes a constant logSigma", who);
+  if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
+  int32_t rc = check_sac(c, actor, q1, q2, la, b, who); if (rc) return rc;
+  return cql_ranges(c, b, n_samples, lo, hi, who);
 }
 static int32_t cql_prepare(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_buffer* b, int N, bool seeds, CqlBufs& cb, const char* who) {
   crux_ctx* c = actor->ctx; const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad; const int64_t NB = (int64_t)(1 + 2 * N) * B;
@@ -213,8 +263,12 @@ static int32_t cql_forward_head(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, cru
   crux_ctx* c = actor->ctx; const int64_t B = b->elements; const int od = b->obs_dim, ad = b->act_dim; const int64_t NB = (int64_t)(1 + 2 * N) * B;
   const float* S = (const float*)b->col[CRUX_COL_S];
   int32_t rc = crux_dense_forward(actor, S, B, c->stream); if (rc) return rc;          // the means; mu does not depend on k
-  hipLaunchKernelGGL(k_cql_expand, dim3(nblk(NB)), dim3(256), 0, c->stream, (const float*)crux_dense_act(actor, actor->nd.L), (const float*)(actor->p + actor->nd.xoff), S,
-                     (const float*)b->col[CRUX_COL_A], od, ad, B, N, lo, hi, seed, counter, cb.sa, cb.lp, d_samples, cb.nanflag);
+  if (actor->sigma_head)       // [mu; logSigma(s)] from the one forward pass (the _sigma entries only: cql_check refuses the flag)
+    hipLaunchKernelGGL(k_cql_expand_sigma, dim3(nblk(NB)), dim3(256), 0, c->stream, (const float*)crux_dense_act(actor, actor->nd.L), S, (const float*)b->col[CRUX_COL_A], od, ad, B, N,
+                       actor->squash, lo, hi, seed, counter, cb.sa, cb.lp, d_samples, cb.nanflag);
+  else
+    hipLaunchKernelGGL(k_cql_expand, dim3(nblk(NB)), dim3(256), 0, c->stream, (const float*)crux_dense_act(actor, actor->nd.L), (const float*)(actor->p + actor->nd.xoff), S,
+                       (const float*)b->col[CRUX_COL_A], od, ad, B, N, lo, hi, seed, counter, cb.sa, cb.lp, d_samples, cb.nanflag);
   rc = crux_launch_check(c, "k_cql_expand"); if (rc) return rc;
   rc = crux_dense_forward(q1, cb.sa, NB, c->stream); if (rc) return rc;
   rc = crux_dense_forward(q2, cb.sa, NB, c->stream); if (rc) return rc;
@@ -225,13 +279,13 @@ static int32_t cql_forward_head(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, cru
   return crux_launch_check(c, "k_cql_head");
 }
 
-extern "C" {
-
-int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const float* d_y, int32_t n_samples, float is_lo, float is_hi,
-                             float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_cql_critic_step", actor, q1, q2, la);
+// the bodies of the entry points: check = cql_check (constant logSigma extras) or cql_check_sigma (two-headed actor, the _sigma entries); everything behind the expansion is shared
+typedef int32_t (*CqlCheck)(crux_ctx*, crux_mlp*, crux_mlp*, crux_mlp*, crux_mlp*, crux_buffer*, int, float, float, const char*);
+static int32_t cql_critic_step(CqlCheck check, const char* entry, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const float* d_y, int32_t n_samples, float is_lo, float is_hi,
+                             float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY(entry, actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b || !d_y) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "cql_critic_loss";
-  int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
+  int32_t rc = check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
   if (use_weight && !has_col(b, CRUX_COL_WEIGHT)) return crux_fail(c, CRUX_EINVAL, "%s(weight=:weight): batch has no :weight column", who);
   CqlBufs cb{}; rc = cql_prepare(actor, q1, q2, b, n_samples, true, cb, who); if (rc) return rc;
   rc = cql_forward_head(actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, d_y, use_weight, seed, counter, cb, nullptr, nullptr); if (rc) return rc;
@@ -245,11 +299,11 @@ int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_m
   return finish_step(c, cb.dinfo, cb.status, info_out, who);
 }
 
-int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
-                            uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY("crux_cql_alpha_step", actor, q1, q2, la);
+static int32_t cql_alpha_step(CqlCheck check, const char* entry, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                            uint64_t seed, uint64_t counter, float* info_out) { CRUX_PLAIN_ONLY(entry, actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "cql_alpha_loss";
-  int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
+  int32_t rc = check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
   CqlBufs cb{}; rc = cql_prepare(actor, q1, q2, b, n_samples, false, cb, who); if (rc) return rc;
   rc = cql_forward_head(actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, nullptr, 0, seed, counter, cb, nullptr, nullptr); if (rc) return rc;
   HIPCHK(c, hipMemsetAsync(la->g, 0, sizeof(float) * (size_t)la->nd.n_params, c->stream));
@@ -259,17 +313,45 @@ int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
   return finish_step(c, cb.dinfo, cb.status, info_out, who);
 }
 
-int32_t crux_cql_conservative(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
-                              uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) { CRUX_PLAIN_ONLY("crux_cql_conservative", actor, q1, q2, la);
+static int32_t cql_conservative(CqlCheck check, const char* entry, crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                              uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) { CRUX_PLAIN_ONLY(entry, actor, q1, q2, la);
   if (!actor || !q1 || !q2 || !la || !b || !out4) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx; const char* who = "conservative_loss";
-  int32_t rc = cql_check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
+  int32_t rc = check(c, actor, q1, q2, la, b, n_samples, is_lo, is_hi, who); if (rc) return rc;
   CqlBufs cb{}; rc = cql_prepare(actor, q1, q2, b, n_samples, false, cb, who); if (rc) return rc;
   rc = cql_forward_head(actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, nullptr, 0, seed, counter, cb, d_samples, d_logprobs); if (rc) return rc;
   double h[8];
   HIPCHK(c, hipMemcpyAsync(h, cb.stats, sizeof h, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream));
   out4[0] = (float)h[0]; out4[1] = (float)h[1]; out4[2] = (float)h[2]; out4[3] = (float)h[3];
   return CRUX_OK;
+}
+
+extern "C" {
+
+int32_t crux_cql_critic_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const float* d_y, int32_t n_samples, float is_lo, float is_hi,
+                             float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) {
+  return cql_critic_step(cql_check, "crux_cql_critic_step", actor, q1, q2, la, b, d_y, n_samples, is_lo, is_hi, thresh, use_weight, seed, counter, info_out);
+}
+int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                            uint64_t seed, uint64_t counter, float* info_out) {
+  return cql_alpha_step(cql_check, "crux_cql_alpha_step", actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, seed, counter, info_out);
+}
+int32_t crux_cql_conservative(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                              uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) {
+  return cql_conservative(cql_check, "crux_cql_conservative", actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, seed, counter, out4, d_samples, d_logprobs);
+}
+// the same three for a two-headed actor (crux_mlp_set_sigma_head): k_cql_expand_sigma draws the policy samples; CRUX_EINVAL for a handle without the flag
+int32_t crux_cql_critic_step_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, const float* d_y, int32_t n_samples, float is_lo, float is_hi,
+                                   float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out) {
+  return cql_critic_step(cql_check_sigma, "crux_cql_critic_step_sigma", actor, q1, q2, la, b, d_y, n_samples, is_lo, is_hi, thresh, use_weight, seed, counter, info_out);
+}
+int32_t crux_cql_alpha_step_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                                  uint64_t seed, uint64_t counter, float* info_out) {
+  return cql_alpha_step(cql_check_sigma, "crux_cql_alpha_step_sigma", actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, seed, counter, info_out);
+}
+int32_t crux_cql_conservative_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* la, crux_buffer* b, int32_t n_samples, float is_lo, float is_hi, float thresh,
+                                    uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs) {
+  return cql_conservative(cql_check_sigma, "crux_cql_conservative_sigma", actor, q1, q2, la, b, n_samples, is_lo, is_hi, thresh, seed, counter, out4, d_samples, d_logprobs);
 }
 
 }  // extern "C"

@@ -77,20 +77,25 @@ def batch_train_asaf_(solver, D, info=None):
     return info
 
 
-def ASAF(pi, S, D_demo, normalize_demo=True, dN=50, lambda_orth=1e-4, a_opt=None, c_opt=None, clip_value=None, log=None, required_columns=(), **kw):
+def ASAF(pi, S, D_demo, normalize_demo=True, dN=50, lambda_orth=1e-4, a_opt=None, c_opt=None, clip_value=None, log=None, required_columns=(), two_headed=False, **kw):
     """ASAF(; π, S, 𝒟_demo, normalize_demo=true, ΔN=50, λ_orth=1f-4, a_opt, c_opt, log, kwargs...) (asaf.jl:40-61): an OnPolicySolver with no critic whose
     post_batch_callback freezes the policy; a_opt is named actor_ with loss asaf_loss. lambda_orth and c_opt are accepted and unused, as in the reference.
     normalize_demo normalises a copy of the demonstrations (the caller's buffer stays as it was). clip_value: element-wise gradient clamp before Adam
     (Optimiser(ClipValue(c), Adam), examples/il/pendulum.jl); None = off. log: a dict of LoggerParams arguments over the reference's defaults dir="log/ASAF",
     period=100 ({} for exactly those); None, as for every solver here, logs nothing.
-    The freeze writes gG = logpdf(piG, s, a) into the buffer's :logprob column (see the module docstring) and gE into solver.gE."""
+    The freeze writes gG = logpdf(piG, s, a) into the buffer's :logprob column (see the module docstring) and gE into solver.gE.
+    two_headed=True: a policy whose logSigma is a network on mu's trunk is taken (csrc/asaf.hip: k_asaf_logpdf_sigma, k_asaf_head_sigma); the freeze and batch_train_asaf_ go
+    through the same entries, and the Sampler rolls such a policy out on the generic kernels. Without the keyword it is refused by name, as before
+    (core.require_two_headed_opt_in: tests/test_gpu_sigma_pg.py::test_host_mirror_refuses_by_name asserts that refusal of the plain call)."""
     if isinstance(pi, DiscreteNetwork):
         raise NotImplementedError("ASAF: the categorical head (DiscreteNetwork) is not implemented; the policy must be a GaussianPolicy or SquashedGaussianPolicy")
     if not isinstance(pi, GaussianPolicy):
         raise TypeError("ASAF: pi must be a GaussianPolicy or SquashedGaussianPolicy (logpdf and entropy are needed)")
-    if getattr(pi, "two_headed", False):
-        raise NotImplementedError("ASAF: a policy whose logSigma is a network (two-headed actor) is implemented for SAC / BatchSAC only")
-    agent = PolicyParams(pi, space=ContinuousSpace(pi.network.dims[-1]))
+    two = getattr(pi, "two_headed", False)
+    if two and not two_headed:
+        raise NotImplementedError("ASAF: a %s whose logSigma is a network (two-headed actor) is taken by this solver only when it is asked for with two_headed=True; "
+                                  "SAC / BatchSAC take it as it is" % type(pi).__name__)
+    agent = PolicyParams(pi, space=ContinuousSpace(pi.act_dim if two else pi.network.dims[-1]))
     demo = copy_buffer(D_demo)
     if normalize_demo:
         normalize_(demo, S, agent.space)
@@ -100,7 +105,7 @@ def ASAF(pi, S, D_demo, normalize_demo=True, dN=50, lambda_orth=1e-4, a_opt=None
         lg = {"dir": "log/ASAF", "period": 100}; lg.update(log)
         kw["log"] = LoggerParams(**lg)
     cols = list(dict.fromkeys(list(required_columns) + ["logprob"]))
-    sv = OnPolicySolver(agent=agent, S=S, dN=dN, a_opt=TrainingParams(**a), c_opt=None, required_columns=cols, **kw)
+    sv = OnPolicySolver(agent=agent, S=S, dN=dN, a_opt=TrainingParams(**a), c_opt=None, required_columns=cols, two_headed=bool(two_headed), **kw)
     sv.demo, sv.gE, sv.clip_value, sv.lambda_orth = demo, _DeviceVec(pi.ctx, max(len(demo), 1)), clip_value, lambda_orth
 
     def freeze(D, info):                                                        # S.a_opt.loss = asaf_actor_loss(deepcopy(S.agent.pi), D_demo) (:57)

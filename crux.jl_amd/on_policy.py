@@ -27,7 +27,7 @@ class OnPolicySolver:
     def __init__(self, agent, S, N=1000, dN=200, max_steps=100, a_opt=None, c_opt=None, P=None, lambda_gae=0.95,
                  required_columns=(), post_batch_callback=None, post_sample_callback=None, i=0, log=None, Vc=None, cost_opt=None, param_optimizers=None, interaction_storage=None, two_headed=False):
         self.interaction_storage = interaction_storage      # a list: every steps! block is appended to it (on_policy.jl:44,96)
-        # two_headed=True: a two-headed Gaussian actor trains with ppo_loss / a2c_loss / reinforce_loss (the dense-engine learner's k_pg_head_sigma); LagrangePPO, ASAF, a
+        # two_headed=True: a two-headed Gaussian actor trains with ppo_loss / a2c_loss / reinforce_loss (the dense-engine learner's k_pg_head_sigma) or asaf_loss (csrc/asaf.hip); LagrangePPO, a
         # CustomLoss and a DiagonalFisherRegularizer are refused by name; so is such a network anywhere but in the actor's place. Without the keyword: refused as before.
         # (The keyword exists only to keep that earlier refusal of the plain call, which tests/test_gpu_sigma_head.py::test_refusals asserts: core.require_two_headed_opt_in.)
         require_two_headed_opt_in(agent.pi, "OnPolicySolver (PPO / A2C / REINFORCE / ASAF)", two_headed)

@@ -109,8 +109,8 @@ float crux_mlp_get_squash(const crux_mlp* net);
  * meaning (ascale > 0: squashed, sigma = exp(clamp(logSigma(s), -5, 2)), the -logSigma term of the log-density unclamped as in policies.jl:385). Parameters, copy, polyak and Adam
  * see one flat vector. Served by the SAC entries (below), crux_rollout / crux_policy_explore (generic kernels), crux_sigma_head_explore / _logpdf, and the policy-gradient
  * learner entries crux_batch_train / crux_train_step / crux_loss_grad / crux_policy_gradient_training with CRUX_HEAD_GAUSSIAN and ppo_loss, a2c_loss, reinforce_loss or
- * logpdf_bc_loss (see crux_batch_train). Refused by the flag with CRUX_EUNSUP, nothing enqueued and no parameter touched: the CQL entries (their sampled-action terms read a
- * constant logSigma), crux_batch_train_lagrange, crux_batch_train_fisher, crux_batch_train with a replica group attached, mse_action loss, crux_policy_gradient_training_multi
+ * logpdf_bc_loss (see crux_batch_train). The three crux_cql_*_sigma entries take it too. Refused by the flag with CRUX_EUNSUP, nothing enqueued and no parameter touched: the plain CQL
+ * entries (their sampled-action terms read a constant logSigma; their _sigma twins serve such a handle), crux_batch_train_lagrange, crux_batch_train_fisher, crux_batch_train with a replica group attached, mse_action loss, crux_policy_gradient_training_multi
  * / _synced, crux_rollout_multi, and such a handle as the nominal policy of crux_steps_push / crux_importance_weight_rows. Separate, non-sharing mu and logSigma networks are
  * not implemented.                                                                                                                                                            */
 int32_t crux_mlp_set_sigma_head(crux_mlp* net, int32_t on);
@@ -676,6 +676,18 @@ int32_t crux_cql_alpha_step(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_ml
  * policy samples first, column (k B + j)) and d_logprobs (device [2N B]) are written when not NULL.                                                            */
 int32_t crux_cql_conservative(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, int32_t n_samples, float is_lo, float is_hi,
                               float thresh, uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs);
+/* The same three entries for a two-headed actor (crux_mlp_set_sigma_head; the actor of examples/offline rl/hopper_medium.jl): parameters, outputs, counters and streams as
+ * their plain twins. z = actor(s) [2 act_dim x B] comes from one forward pass; policy sample k of column j, dimension d is SigmaExploreOp's arithmetic on the stream
+ * (k B + j) act_dim + d: sigma = exp(logSigma(s)) (squashed: exp(clamp(logSigma(s), -5, 2))), u = mu + sigma randn, a = u or ascale tanh(u), logprob = sum_d [-(u - mu)^2 /
+ * (2 sigma^2) - 0.9189385 - logSigma(s) (- the tanh correction)], so sample block k = 0 and its logprobs equal crux_sigma_head_explore(actor, s, B, 1, seed, counter) bit for
+ * bit. Data and uniform blocks, both critics' passes, the head, the gradients and the gated Adam are the plain entries'. CRUX_EINVAL for a handle without the flag ("not
+ * two-headed") or one that does not map obs -> 2 act_dim without extras (act_dim <= 64); CRUX_EUNSUP while recording. The plain entries keep refusing the flag (CRUX_EUNSUP). */
+int32_t crux_cql_critic_step_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, const float* d_y, int32_t n_samples,
+                                   float is_lo, float is_hi, float thresh, int32_t use_weight, uint64_t seed, uint64_t counter, float* info_out);
+int32_t crux_cql_alpha_step_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, int32_t n_samples, float is_lo, float is_hi,
+                                  float thresh, uint64_t seed, uint64_t counter, float* info_out);
+int32_t crux_cql_conservative_sigma(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* cql_log_alpha, crux_buffer* batch, int32_t n_samples, float is_lo, float is_hi,
+                                    float thresh, uint64_t seed, uint64_t counter, float* out4, float* d_samples, float* d_logprobs);
 
 /* OnlineIQLearn (src/model_free/il/iqlearn.jl) and gradient_penalty (src/extras/gradient_penalty.jl) on the dense engine -----------------------------------
  * gradient_penalty(D, x, xtilde; target): per column j of B, xhat_j = eps_j xtilde_j + (1 - eps_j) x_j with eps_j = (float)u53(Philox(seed, counter, j, IQ_GP))
@@ -784,6 +796,10 @@ int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf,
  * d_out[i] = logpdf(pi, s_i, a_i) for rows [first_row, first_row + n_rows) of buf (device, n_rows floats; it may be a column of buf itself). pi: a GaussianPolicy handle
  * (trailing act_dim extras = logSigma; gaussian_logpdf, policies.jl:333-336, summed over the action) or a SquashedGaussianPolicy handle (crux_mlp_get_squash != 0;
  * squashed_gaussian_logprob, :383-396, of atanh(clamp(a / ascale, -1 + 1f-5, 1 - 1f-5)) with sigma = exp(clamp(logSigma, -5, 2)) and the unclamped - logSigma term).
+ * A two-headed handle (crux_mlp_set_sigma_head: obs -> 2 act_dim, no extras, act_dim <= 64) is taken by the three entries as well: logSigma(s) comes from the output rows
+ * [act_dim, 2 act_dim) per column (crux_sigma_head_logpdf's arithmetic), the step's seed is [dmu; dlogSigma] per column with no extras gradient, and mean(entropy(pi, s))
+ * is 1.4189385 + the sum of logSigma(s) over the whole rollout minibatch for the GaussianPolicy (policies.jl:348) and 1.4189385 + its per-column mean for the squashed one (:398).
+ * A handle with neither extras nor the flag: CRUX_EUNSUP.
  * One forward pass and one head kernel; no parameter and no gradient buffer changes. A NaN in s_i or a_i gives d_out[i] = NaN. One host synchronisation.
  * CRUX_EINVAL / CRUX_EUNSUP as crux_asaf_actor_step (policy, buffer, row range; n_rows <= 2^20).                                                                  */
 int32_t crux_asaf_freeze(crux_mlp* pi, crux_buffer* buf, int64_t first_row, int64_t n_rows, float* d_out);

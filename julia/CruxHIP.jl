@@ -550,6 +550,23 @@ function cql_conservative(A::HipNetwork, Q1::HipNetwork, Q2::HipNetwork, logα::
                        A.h, Q1.h, Q2.h, logα.h, mb.h, N, lo, hi, thresh, seed, ctr, out, C_NULL, C_NULL))
     out
 end
+# the same three for a two-headed actor (crux_mlp_set_sigma_head: a SquashedGaussianPolicy / GaussianPolicy whose logΣ is a network on μ's trunk, the SAC_A() of
+# examples/offline rl/hopper_medium.jl); the plain entries above refuse such a handle
+cql_critic_step_sigma!(A::HipNetwork, Q1::HipNetwork, Q2::HipNetwork, logα::HipNetwork, mb::HipBuffer, d_y::Ptr{Float32}, N::Integer, lo::Float32, hi::Float32, thresh::Float32,
+                       weighted::Bool, seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N)) =
+    (check(A.ctx, ccall((:crux_cql_critic_step_sigma, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Int32, Float32, Float32, Float32, Int32, UInt64, UInt64, Ptr{Float32}),
+                        A.h, Q1.h, Q2.h, logα.h, mb.h, d_y, N, lo, hi, thresh, Int32(weighted), seed, ctr, info)); info)
+cql_alpha_step_sigma!(A::HipNetwork, Q1::HipNetwork, Q2::HipNetwork, logα::HipNetwork, mb::HipBuffer, N::Integer, lo::Float32, hi::Float32, thresh::Float32,
+                      seed::UInt64, ctr::UInt64, info=zeros(Float32, INFO_N)) =
+    (check(A.ctx, ccall((:crux_cql_alpha_step_sigma, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, Float32, UInt64, UInt64, Ptr{Float32}),
+                        A.h, Q1.h, Q2.h, logα.h, mb.h, N, lo, hi, thresh, seed, ctr, info)); info)
+function cql_conservative_sigma(A::HipNetwork, Q1::HipNetwork, Q2::HipNetwork, logα::HipNetwork, mb::HipBuffer, N::Integer, lo::Float32, hi::Float32, thresh::Float32,
+                                seed::UInt64, ctr::UInt64)
+    out = zeros(Float32, 4)
+    check(A.ctx, ccall((:crux_cql_conservative_sigma, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, Float32, UInt64, UInt64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                       A.h, Q1.h, Q2.h, logα.h, mb.h, N, lo, hi, thresh, seed, ctr, out, C_NULL, C_NULL))
+    out
+end
 
 # OnlineIQLearn (src/model_free/il/iqlearn.jl): the staging minibatch holds n_policy buffer rows, then the demo rows (split_batches of rand! with fracs [1/2, 1/2]);
 # the penalty's interpolation weights are Philox(noise_seed, i epochs + epoch, j, IQ_GP) (include/crux_rng.h)
