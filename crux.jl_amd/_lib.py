@@ -34,6 +34,12 @@ class TrainCfg(C.Structure):
                 ("shuffle_counter", u64), ("reserved0", i32), ("target_col", i32)]
 
 
+class ConvLayer(C.Structure):
+    """crux_conv_layer (include/cruxhip.h): one Conv of a convolutional trunk."""
+    _fields_ = [("k1", i32), ("k2", i32), ("cin", i32), ("cout", i32), ("stride1", i32), ("stride2", i32), ("pad1", i32), ("pad2", i32), ("act", i32),
+                ("dilation1", i32), ("dilation2", i32), ("groups", i32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/cruxhip.h appears here (checked by tests).
 SIGNATURES = {
     "crux_ctx_create": (i32, [i32, vp, P(vp)]),
@@ -210,6 +216,17 @@ SIGNATURES = {
     "crux_dpg_target": (i32, [vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, u64, u64, vp]),
     "crux_q_step": (i32, [vp, vp, vp, i32, vp]),
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),
+    "crux_conv_create": (i32, [vp, i32, i32, i32, f32, i32, P(ConvLayer), P(vp)]),
+    "crux_conv_destroy": (i32, [vp]),
+    "crux_conv_n_params": (i64, [vp]),
+    "crux_conv_out_features": (i64, [vp]),
+    "crux_conv_init_glorot": (i32, [vp, vp, u64, u32]),
+    "crux_conv_forward": (i32, [vp, vp, vp, i64, vp]),
+    "crux_conv_forward_cached": (i32, [vp, vp, vp, i64, vp]),
+    "crux_conv_backward": (i32, [vp, vp, vp, i64, vp, f32, i32, vp]),
+    "crux_conv_dqn_target": (i32, [vp, vp, vp, vp, f32, vp]),
+    "crux_conv_td_step": (i32, [vp, vp, vp, vp, vp, i32, vp]),
+    "crux_conv_td_step_with_error": (i32, [vp, vp, vp, vp, vp, i32, vp, vp]),
 }
 
 _lib = None

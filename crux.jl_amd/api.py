@@ -54,6 +54,8 @@ from .ensembles import *   # noqa: F401,F403
 from .ensembles import DeepClassificationEnsemble, DeepEnsemble, individual_forward, logpdf, training_loss   # noqa: F401
 from .mixture import *   # noqa: F401,F403
 from .mixture import MixtureNetwork   # noqa: F401
+from .conv import Conv, ConvSpec, ConvTrunk, Scale, flatten   # noqa: F401
+from .core import refuse_conv   # noqa: F401
 from .on_policy import _solve_on_policy
 from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles, continual, mixture   # noqa: F401
 

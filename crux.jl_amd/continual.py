@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .core import refuse_conv
 from .core import CustomLoss, ParamLoss, Sampler, _ensure_opt, _info_dict, _train_cfg, _vp, clone_policy, refuse_two_headed, shuffle_device_, undiscounted_return
 
 
@@ -18,7 +19,7 @@ class DiagonalFisherRegularizer:
     F, N and theta_prev read host copies; lam is settable; set_() loads a checkpoint."""
 
     def __init__(self, net, lam=1.0):
-        refuse_two_headed(net, "DiagonalFisherRegularizer (EWC, continual_learning)")
+        refuse_two_headed(net, "DiagonalFisherRegularizer (EWC, continual_learning)"); refuse_conv(net, "DiagonalFisherRegularizer (EWC, continual_learning)")
         self.net, self.ctx = net, net.ctx
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.crux_fisher_create(net.h, float(np.float32(lam)), C.byref(h)))

@@ -225,9 +225,14 @@ class DenseSN(Dense):
 
 
 class Chain:
-    """Flux.Chain(Dense | DenseSN ...)."""
+    """Flux.Chain(Dense | DenseSN ...), or a conv chain Chain([Scale,] Conv..., flatten, Dense..., input=(W, H, C)) (conv.py): `conv` then describes the trunk and `layers`,
+    `dims`, `acts` the dense head behind flatten."""
 
-    def __init__(self, *layers):
+    def __init__(self, *layers, input=None):
+        self.conv = None
+        if any(getattr(l, "conv_kind", None) for l in layers):
+            from .conv import split_chain
+            self.conv, layers = split_chain(layers, input)
         self.layers = list(layers)
         for a, b in zip(self.layers[:-1], self.layers[1:]):
             if a.out != b.inp:
@@ -261,8 +266,43 @@ class NetworkPolicy:
         self.h = h
         self.ctx.check(self.ctx.lib.crux_mlp_init_glorot(self.h, int(seed), int(stream), float(extra_init)))
         self.optimizer = None
+        self.trunk = None      # a conv policy (conv.py): the convolutional trunk in front of this handle, which is then the dense head behind flatten
+        if getattr(network, "conv", None) is not None:
+            from .conv import ConvTrunk
+            self.trunk = ConvTrunk(network.conv, ctx=self.ctx, seed=seed, stream=stream)
         if any(network.sn_iterations):
             self.set_spectral([l.u for l in network.layers if isinstance(l, DenseSN)], seed=seed, stream=stream)
+
+    @property
+    def is_conv(self):
+        """"conv": the policy is a convolutional trunk + dense head; None: a plain MLP"""
+        return "conv" if self.__dict__.get("trunk") is not None else None
+
+    # `h` is the crux_mlp handle of the whole network. A conv policy has no such handle: its dense head is `head_h`, for the code that knows about the trunk (conv.py, DQN's
+    # value_training, the parameter accessors below). Whatever else reads `.h` -- a solver, a discriminator step, fill_gae!, an ensemble -- would run the head as the whole
+    # network over raw observations, silently so where flatten's width equals the observation's; it raises here instead, behind the named refusals of refuse_conv.
+    @property
+    def h(self):
+        if self.__dict__.get("trunk") is not None:
+            raise NotImplementedError("a policy with a convolutional trunk (Conv layers in its Chain) has no single network handle: this path would treat the dense head as the "
+                                      "whole network; conv policies are implemented for value, the parameter accessors, polyak / copy / clone and DQN on a HostMDP only")
+        return self.__dict__.get("_h")
+
+    @h.setter
+    def h(self, v):
+        self._h = v
+
+    @property
+    def head_h(self):
+        """the handle of the dense layers: the whole network of an MLP policy, the head behind flatten of a conv policy"""
+        return self.__dict__.get("_h")
+
+    def _handles(self):
+        """the crux_mlp handles that own this policy's parameters, in Flux.params order"""
+        return ([self.trunk.p.h] if self.is_conv else []) + [self.head_h]
+
+    def _sizes(self):
+        return [int(self.ctx.lib.crux_mlp_n_params(h)) for h in self._handles()]
 
     def set_spectral(self, us=None, seed=0, stream=0):
         """Switch the DenseSN layers of the chain on (crux_mlp_set_spectral). us: one u per SN layer; a missing one (or us=None) is drawn as standard normals."""
@@ -299,20 +339,31 @@ class NetworkPolicy:
     # Flux.params(pi) as one flat Float32 vector in Flux order (W1,b1,W2,b2,...,extras)
     @property
     def n_params(self):
-        return int(self.ctx.lib.crux_mlp_n_params(self.h))
+        return sum(self._sizes())
 
     def get_params(self):
-        out = np.empty(self.n_params, np.float32)
-        self.ctx.check(self.ctx.lib.crux_mlp_get_params(self.h, _vp(out), out.size))
+        out = np.empty(self.n_params, np.float32); off = 0
+        for h, n in zip(self._handles(), self._sizes()):      # (a conv policy: trunk, then head)
+            part = np.empty(n, np.float32)
+            self.ctx.check(self.ctx.lib.crux_mlp_get_params(h, _vp(part), n)); out[off:off + n] = part; off += n
         return out
 
     def set_params(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
-        self.ctx.check(self.ctx.lib.crux_mlp_set_params(self.h, _vp(flat), flat.size))
+        if not self.is_conv:
+            self.ctx.check(self.ctx.lib.crux_mlp_set_params(self.h, _vp(flat), flat.size))
+            return
+        flat, off = flat.reshape(-1), 0
+        if flat.size != self.n_params:
+            raise ValueError("set_params: %d values for the %d parameters of trunk and head" % (flat.size, self.n_params))
+        for h, n in zip(self._handles(), self._sizes()):
+            part = np.ascontiguousarray(flat[off:off + n])
+            self.ctx.check(self.ctx.lib.crux_mlp_set_params(h, _vp(part), n)); off += n
 
     def params(self):
-        """List of arrays like Flux.params: W (out,in) column-major, b (out,), ..., extras."""
-        flat, out, off = self.get_params(), [], 0
+        """List of arrays like Flux.params: W (out,in) column-major, b (out,), ..., extras; a conv policy's trunk arrays come first, its weights 4-D (k1, k2, cin, cout)."""
+        out, off = ([] if not self.is_conv else self.trunk.params()), 0
+        flat = self.get_params()[self.n_params - self._sizes()[-1]:]
         d = self.network.dims
         for l in range(len(d) - 1):
             n = d[l + 1] * d[l]
@@ -325,6 +376,8 @@ class NetworkPolicy:
     def forward(self, s):
         """value(pi, s) for ContinuousNetwork / raw logits for DiscreteNetwork (src/policies.jl:94,120)."""
         s = np.asarray(s, np.float32)
+        if self.is_conv:      # the trunk on the observations, the head on its features (conv.py)
+            return self.trunk.head_forward(self, s)
         d_in, d_out = self.network.dims[0], self.network.dims[-1]
         if s.ndim == 1:
             s = s.reshape(d_in, 1)
@@ -338,22 +391,29 @@ class NetworkPolicy:
 
     def attach_optimizer(self, opt):
         self.optimizer = opt
-        self.ctx.check(self.ctx.lib.crux_adam_init(self.h, opt.eta, opt.beta[0], opt.beta[1], opt.epsilon))
+        for h in self._handles():
+            self.ctx.check(self.ctx.lib.crux_adam_init(h, opt.eta, opt.beta[0], opt.beta[1], opt.epsilon))
 
     def adam_state(self):
-        m, v, bp = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32), np.empty(2, np.float64)
-        self.ctx.check(self.ctx.lib.crux_adam_get_state(self.h, _vp(m), _vp(v), _vp(bp)))
-        return m, v, bp
+        """(m, v, [beta1^t, beta2^t]); a conv policy: trunk then head, the beta powers of the head (both handles step together)"""
+        ms, vs, bp = [], [], np.empty(2, np.float64)
+        for h, n in zip(self._handles(), self._sizes()):
+            m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+            self.ctx.check(self.ctx.lib.crux_adam_get_state(h, _vp(m), _vp(v), _vp(bp))); ms.append(m); vs.append(v)
+        return np.concatenate(ms), np.concatenate(vs), bp
 
     def set_adam_state(self, m, v, beta_pow):
         """Load Adam's (m, v, [beta1^t, beta2^t]) -- the IdDict entry Flux keeps per parameter array (checkpoint restore, parity tests)."""
         m, v, bp = np.ascontiguousarray(m, np.float32), np.ascontiguousarray(v, np.float32), np.ascontiguousarray(beta_pow, np.float64)
-        self.ctx.check(self.ctx.lib.crux_adam_set_state(self.h, _vp(m), _vp(v), _vp(bp)))
+        off = 0
+        for h, n in zip(self._handles(), self._sizes()):
+            mp, vq = np.ascontiguousarray(m[off:off + n]), np.ascontiguousarray(v[off:off + n])
+            self.ctx.check(self.ctx.lib.crux_adam_set_state(h, _vp(mp), _vp(vq), _vp(bp))); off += n
 
     def __del__(self):
         try:
-            if getattr(self, "h", None) and self.ctx.h:
-                self.ctx.lib.crux_mlp_destroy(self.h)
+            if self.head_h and self.ctx.h:
+                self.ctx.lib.crux_mlp_destroy(self.head_h)
         except Exception:
             pass
 
@@ -567,6 +627,29 @@ def refuse_spectral(pi, who):
                              "(OnPolicyGAIL, OffPolicyGAIL, NDA_GAIL_JS) only" % who)
 
 
+def refuse_conv(pi, who):
+    """A conv policy (convolutional trunk + dense head, conv.py) is taken by value / forward, the parameter accessors, polyak_average_, copyto_, clone_policy, policy_explore on
+    a HostMDP and DQN. The entry points that take a network call this and refuse by their own name before any device call: the solver constructors (by name: PPO, LagrangePPO,
+    A2C, REINFORCE, SAC, SoftQ, DDPG, TD3; the others through PolicyParams), a Sampler on a device MDP, train! / batch_train!, fill_gae!, the GAIL discriminator steps and
+    reward, the replica-group and multi-seed learners. Behind them stands NetworkPolicy.h itself: a conv policy has no whole-network handle, so any other path that reads
+    `.h` (an ensemble member, a mixture's weight network, a Fisher regulariser's network, a custom-loss seam) raises the same NotImplementedError at that read instead of
+    running the head as the whole network. (bson.py loads buffers only: there is no policy loader to guard.)"""
+    for q in ([] if pi is None else _leaves(pi)):
+        if getattr(q, "is_conv", None):
+            raise NotImplementedError("%s: a policy with a convolutional trunk (Conv layers in its Chain) is implemented for DQN on a HostMDP only; "
+                                      "this path would treat the dense head as the whole network" % who)
+
+
+def _param_handles(pi):
+    """(ctx, crux_mlp handle) of every parameter vector the (possibly composite) policy is made of; a conv policy contributes its trunk, then its head"""
+    out = []
+    for q in _leaves(pi):
+        if getattr(q, "is_conv", None):
+            out.append((q.ctx, q.trunk.p.h))
+        out.append((q.ctx, q.head_h if isinstance(q, NetworkPolicy) else q.h))
+    return out
+
+
 def refuse_standalone(pi, who):
     """Policy classes that the Sampler and the solvers do not take yet carry the reason in `not_a_solver_policy` (MixtureNetwork, mixture.py)."""
     for q in ([] if pi is None else _leaves(pi)):
@@ -618,14 +701,14 @@ def _refuse_two_headed_params(pi, p, who):
 
 def polyak_average_(to, frm, tau=1.0):
     """polyak_average!(to, from, tau) (src/policies.jl:48-59) over every layer of the (possibly composite) policy."""
-    for t, f in zip(_leaves(to), _leaves(frm)):
-        t.ctx.check(t.ctx.lib.crux_polyak(t.h, f.h, float(tau)))
+    for (ctx, t), (_, f) in zip(_param_handles(to), _param_handles(frm)):
+        ctx.check(ctx.lib.crux_polyak(t, f, float(tau)))
 
 
 def copyto_(to, frm):
     """Base.copyto!(to, from) on network parameters (src/policies.jl:61-65)."""
-    for t, f in zip(_leaves(to), _leaves(frm)):
-        t.ctx.check(t.ctx.lib.crux_mlp_copy(t.h, f.h))
+    for (ctx, t), (_, f) in zip(_param_handles(to), _param_handles(frm)):
+        ctx.check(ctx.lib.crux_mlp_copy(t, f))
 
 
 def clone_policy(pi):
@@ -655,11 +738,13 @@ def clone_policy(pi):
 class PolicyParams:
     """PolicyParams(pi; space, pi_explore, pi_minus) (src/policies.jl:12-19)."""
 
-    def __init__(self, pi, space=None, pi_explore=None, pi_minus=None, pa=None):
+    def __init__(self, pi, space=None, pi_explore=None, pi_minus=None, pa=None, conv_ok=False):
         self.pi, self.pi_explore, self.pi_minus = pi, pi_explore if pi_explore is not None else pi, pi_minus
         for q in (pi, pi_explore, pi_minus, pa):
             refuse_standalone(q, "PolicyParams")
             refuse_spectral(q, "PolicyParams")
+            if not conv_ok:      # (DQN and a Sampler on a HostMDP pass conv_ok=True: the one solver and the one seam that take a conv policy)
+                refuse_conv(q, "PolicyParams (every solver but DQN)")
         self.pa = pa                                   # nominal action policy (policies.jl:17): the reference distribution of :importance_weight (sampler.jl:108-111)
         a = actor(pi)
         self.space = space or (DiscreteSpace(len(a.outputs), a.outputs) if isinstance(a, DiscreteNetwork) else ContinuousSpace(getattr(a, "act_dim", None) or a.network.dims[-1]))
@@ -1072,7 +1157,10 @@ class Sampler:
         self.mdp = mdp
         self.traj_weight_fn = traj_weight_fn     # weight of a trajectory (Sampler.traj_weight_fn, src/sampler.jl:21): (agent, data, ep) -> the :traj_importance_weight of the episode's rows (:62)
         self.Vc = Vc                             # cost value network (Sampler.Vc, src/sampler.jl:20): fill_gae!(..., source=:cost, target=:cost_advantage) (:65)
-        self.agent = agent if isinstance(agent, PolicyParams) else PolicyParams(agent)
+        self.agent = agent if isinstance(agent, PolicyParams) else PolicyParams(agent, conv_ok=True)
+        if not isinstance(mdp, HostMDP):      # crux_rollout and the device environments read the policy handle as an MLP over the observation
+            for q in (self.agent.pi, self.agent.pi_minus, Vc):
+                refuse_conv(q, "Sampler on a device MDP (%s)" % getattr(mdp, "kind", type(mdp).__name__))
         self.S = S or mdp.state_space()
         self.max_steps, self.required_columns = int(max_steps), list(required_columns)
         self.gamma, self.lam = np.float32(discount(mdp)), np.float32(lam)
@@ -1177,7 +1265,15 @@ def steps_(sampler, buffer=None, Nsteps=1, explore=False, i=0, reset=False, cb=N
 def policy_explore(pi, cfg, svec, seed, steps_taken):
     """crux_policy_explore (cruxhip.h): `a, logprob = exploration(pi_explore, svec; pi_on, i)` / `(action(pi, svec), NaN)` (src/sampler.jl:73) for the columns of svec at once.
     Returns (actions [act_dim x E] Bool one-hot or Float32, logprob [E])."""
-    svec = np.asfortranarray(svec, np.float32); E = svec.shape[1]; nout = getattr(pi, "act_dim", None) or pi.network.dims[-1]
+    svec = np.asfortranarray(svec, np.float32)
+    if getattr(pi, "is_conv", None):      # trunk and head on the E observations, then the exploration kernel over the head's output (ConvTrunk.explore_tail): the draws of an MLP with these outputs
+        if cfg.head not in (L.HEAD["categorical"], L.HEAD["greedy_q"], L.HEAD["deterministic"]):
+            refuse_conv(pi, "policy_explore with a Gaussian head")
+        svec = np.asfortranarray(pi.forward(svec))
+        if not np.isfinite(svec).all():      # the identity layer would turn one Inf into a column of NaN (0 * Inf); a network that has diverged is reported, not explored with
+            raise L.CruxError(L.ENAN, "policy_explore: the conv policy's output is not finite")
+        pi = pi.trunk.explore_tail(svec.shape[0])
+    E = svec.shape[1]; nout = getattr(pi, "act_dim", None) or pi.network.dims[-1]
     disc = cfg.head in (L.HEAD["categorical"], L.HEAD["greedy_q"])
     a = np.zeros((nout, E), np.bool_ if disc else np.float32, order="F"); lp = np.empty(E, np.float32)
     st = np.ascontiguousarray(steps_taken, np.int64)
@@ -1378,6 +1474,7 @@ def steps_multi_(samplers, buffers, Nsteps=1, explore=False, i=0, reset=False):
 
 def fill_gae_(buffer, V, lam, gamma):
     """fill_gae!(d::ExperienceBuffer, V, lambda, gamma) (src/sampler.jl:255-273)."""
+    refuse_conv(V, "fill_gae!")
     buffer.ctx.check(buffer.ctx.lib.crux_fill_gae(buffer.h, critic(V).h, float(lam), float(gamma)))
 
 
@@ -1470,6 +1567,7 @@ class OrthogonalRegularizer:
 
 def orthogonal_regularizer(net, beta=1e-4, accumulate=False):
     """OrthogonalRegularizer(beta)(net): returns the value. accumulate: its gradient 4 beta W_l R_l is added to the weight slots of the network's gradient buffer."""
+    refuse_conv(net, "OrthogonalRegularizer")
     out = np.zeros(1, np.float32)
     net.ctx.check(net.ctx.lib.crux_orthogonal_reg(net.h, float(np.float32(beta)), 1 if accumulate else 0, _vp(out)))
     return float(out[0])
@@ -1618,6 +1716,7 @@ def train_(pi, p, P, D, indices, info=None):
     """Flux.Optimise.train!(pi, loss, p; info) on minibatch(D, indices) (src/training.jl:13-25); 1-based indices.
     Raises CruxError(ENAN) like `error("NaN detected!")` (:20)."""
     _refuse_two_headed_params(pi, p, "train!")
+    refuse_conv(pi, "train!")
     _ensure_opt(pi, p)
     ids = np.ascontiguousarray(np.asarray(indices, np.int64) - 1)
     if _uses_seam(p):
@@ -1634,6 +1733,7 @@ def batch_train_(pi, p, P, D, info=None, perms=None):
     """batch_train!(pi, p, P, D; info) (src/training.jl:28-55): epochs x (shuffle!, partition, train!) with max_batches and
     early stopping, as ONE persistent kernel. perms: optional (epochs, len) 1-based permutations (else Philox)."""
     _refuse_two_headed_params(pi, p, "batch_train!")
+    refuse_conv(pi, "batch_train!")
     _ensure_opt(pi, p)
     if _fisher_reg(p) is not None:                     # a DiagonalFisherRegularizer of this network: the dense-engine learner's chain (crux_batch_train_fisher) where it applies
         from .continual import _batch_train_fisher

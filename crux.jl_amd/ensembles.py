@@ -55,6 +55,8 @@ class _Ensemble:
                 raise NotImplementedError("%s: members of different shapes (the grouped device passes need one shape)" % type(self).__name__)
         if self.kind == "gauss" and chains[0].dims[-1] % 2:
             raise ValueError("DeepEnsemble: the output width %d is odd (mean and variance halves)" % chains[0].dims[-1])
+        if any(getattr(ch, "conv", None) is not None for ch in chains):
+            raise NotImplementedError("%s: members with a convolutional trunk (Conv layers in their Chain) are not implemented" % type(self).__name__)
         self.models = [ContinuousNetwork(ch, ctx=self.ctx, seed=seed, stream=m) for m, ch in enumerate(chains)]      # independent Glorot streams
         self.dims = chains[0].dims
         self.optimizer = None

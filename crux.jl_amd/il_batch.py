@@ -6,6 +6,7 @@ advil_pi_loss (a DPG-style step through the critic plus a BC term) with an Ortho
 import numpy as np
 
 from . import _lib as L
+from .core import refuse_conv
 from .core import ActorCritic, ContinuousNetwork, OrthogonalRegularizer, PolicyParams, TrainingParams, _Loss, _vp, copy_buffer, normalize_
 from .imitation import BatchSolver
 
@@ -16,6 +17,7 @@ ADVIL_GP_TARGET = 0.4      # gradient_penalty(critic(pi), expert_sa, pi_sa, targ
 
 def advil_d_step_(A, D, mb, lambda_GP, seed, counter, target=ADVIL_GP_TARGET):
     """train!(critic(pi), advil_d_loss) on the staging minibatch (crux_advil_d_step): returns the raw info row and [mean D(expert), mean D(pi), P, lambda_GP P]."""
+    refuse_conv(A, "advil_d_step_ (A)"); refuse_conv(D, "advil_d_step_ (D)")
     raw, adv = np.zeros(L.INFO_N, np.float32), np.zeros(4, np.float32)
     D.ctx.check(D.ctx.lib.crux_advil_d_step(A.h, D.h, mb.h, float(np.float32(lambda_GP)), float(np.float32(target)), int(seed), int(counter), _vp(raw), _vp(adv)))
     return raw, adv
@@ -24,6 +26,7 @@ def advil_d_step_(A, D, mb, lambda_GP, seed, counter, target=ADVIL_GP_TARGET):
 def advil_actor_step_(A, D, mb, lambda_BC, beta_orth):
     """train!(actor(pi), advil_pi_loss + OrthogonalRegularizer(beta_orth)) on the staging minibatch (crux_advil_actor_step): returns the raw info row and
     [mean D(s, pi(s)), mse, beta_orth reg]."""
+    refuse_conv(A, "advil_actor_step_ (A)"); refuse_conv(D, "advil_actor_step_ (D)")
     raw, adv = np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
     D.ctx.check(D.ctx.lib.crux_advil_actor_step(A.h, D.h, mb.h, float(np.float32(lambda_BC)), float(np.float32(beta_orth)), _vp(raw), _vp(adv)))
     return raw, adv

@@ -16,6 +16,7 @@ from . import _lib as L
 from .logging import aggregate_info
 from .core import (ContinuousNetwork, ContinuousSpace, DiscreteNetwork, DiscreteSpace, ExperienceBuffer, TrainingParams, _Loss, _ensure_opt, _vp, copy_buffer, normalize_,
                    split_batches)
+from .core import refuse_conv
 from .core import refuse_two_headed
 from .off_policy import SAC, SoftQ
 
@@ -48,6 +49,7 @@ def gradient_penalty(net, x, xtilde=None, target=1.0, seed=0, counter=0):
 
     The draws are a pure function of (seed, counter): calls with the same pair interpolate with the same eps. The reference draws fresh uniforms on every call,
     so a caller that wants that must pass a counter of its own per call (OnlineIQLearn passes noise_seed and i epochs + epoch)."""
+    refuse_conv(net, "gradient_penalty")
     ctx = net.ctx
     d_in = net.network.dims[0]
     for name, v in (("x", x), ("xtilde", xtilde)):
@@ -156,6 +158,7 @@ def _handles(bufs):
 
 def offgail_d_step_(D, sources, Bd, seed, counter):
     """One discriminator step of OffPolicyGAIL (off_policy_gail.jl:65-98) over `sources` = [demo, buffer, ndas...]: returns the raw info row (crux_offgail_d_step)."""
+    refuse_conv(D, "offgail_d_step_")
     raw = np.zeros(L.INFO_N, np.float32)
     D.ctx.check(D.ctx.lib.crux_offgail_d_step(D.h, _handles(sources), len(sources), int(Bd), int(seed), int(counter), _vp(raw)))
     return raw
@@ -163,6 +166,7 @@ def offgail_d_step_(D, sources, Bd, seed, counter):
 
 def offgail_round_(D, sources, Bd, d_epochs, batch, seed, counter0):
     """GAIL_callback (off_policy_gail.jl:64-125) as one call: d_epochs discriminator steps, then batch[:r] rewritten; returns the last step's raw info row."""
+    refuse_conv(D, "offgail_round_")
     raw = np.zeros(L.INFO_N, np.float32)
     D.ctx.check(D.ctx.lib.crux_offgail_round(D.h, _handles(sources), len(sources), int(Bd), int(d_epochs), batch.h, int(seed), int(counter0), _vp(raw)))
     return raw
@@ -170,6 +174,7 @@ def offgail_round_(D, sources, Bd, d_epochs, batch, seed, counter0):
 
 def offgail_reward_(D, batch, K):
     """batch[:r] .= sum((log.(softmax(D(s, a)) .+ 1f-5) .- log.(1f0 .- softmax(D(s, a)) .+ 1f-5)) .* w, dims=1) (off_policy_gail.jl:121-124); returns mean(r)."""
+    refuse_conv(D, "offgail_reward_")
     out = np.zeros(1, np.float32)
     D.ctx.check(D.ctx.lib.crux_offgail_reward(D.h, batch.h, int(K), _vp(out)))
     return float(out[0])
@@ -205,6 +210,7 @@ def OffPolicyGAIL(pi, S, demo, D, ndas=(), normalize_demo=True, solver=SAC, d_op
 
     Works with every solver whose value_training honours post_batch_callback (SAC, DDPG / TD3, DQN / SoftQ). Deviation: normalize_demo=False with NDA buffers
     is allowed and leaves them as they are; the reference assigns `false` to 𝒟_ndas[i] in that case (:44), which fails at the first rand!."""
+    refuse_conv(pi, "OffPolicyGAIL (pi)"); refuse_conv(D, "OffPolicyGAIL (D)")
     refuse_two_headed(pi, "OffPolicyGAIL")
     d = dict(d_opt or {}); d.setdefault("epochs", 5); d.setdefault("name", "discriminator_")
     dp = TrainingParams(loss=None, **d)                                                                  # loss = () -> nothing (:31)

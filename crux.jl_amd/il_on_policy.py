@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from .core import refuse_conv
 from .core import ContinuousSpace, DiscreteNetwork, GaussianPolicy, PolicyParams, TrainingParams, _Loss, _ensure_opt, _vp, copy_buffer, normalize_
 from .on_policy import OnPolicySolver
 
@@ -21,6 +22,7 @@ ASAF_ROW = L.INFO_N + 4       # one epoch row of crux_asaf_batch_train: the info
 
 def asaf_freeze_(pi, buf, d_out, first_row=0, n_rows=None):
     """d_out[i] = logpdf(pi, s_i, a_i) over rows [first_row, first_row + n_rows) of buf (crux_asaf_freeze); d_out: a device pointer, n_rows floats."""
+    refuse_conv(pi, "asaf_freeze_")
     n = len(buf) - first_row if n_rows is None else n_rows
     pi.ctx.check(pi.ctx.lib.crux_asaf_freeze(pi.h, buf.h, int(first_row), int(n), d_out))
 
@@ -32,6 +34,7 @@ def _clip(clip_value):
 def asaf_actor_step_(pi, buf, off, n, d_gG, demo, d_gE, clip_value=None):
     """train!(actor(pi), asaf_actor_loss) on rows [off, off + n) of buf (0-based) and all rows of demo (crux_asaf_actor_step): returns the raw info row and
     [entropy, the expert term, the policy term]. d_gG is aligned with buf's rows, d_gE with demo's."""
+    refuse_conv(pi, "asaf_actor_step_")
     raw, out = np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
     pi.ctx.check(pi.ctx.lib.crux_asaf_actor_step(pi.h, buf.h, int(off), int(n), d_gG, demo.h, d_gE, _clip(clip_value), _vp(raw), _vp(out)))
     return raw, out

@@ -5,6 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
+from .core import refuse_conv
 from .core import refuse_two_headed, require_two_headed_opt_in   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
@@ -96,6 +97,7 @@ def batch_train_gail_d_(Dnet, p, D_expert, D_policy, info=None):
     The loss kind is p.loss's (gail_d_loss(gan_loss)); BCE makes the calls it always made. GAN_WLossGP draws step t's ε from (gan_loss.seed, p.gp_counter), which advances
     by one per step taken, and needs equal halves in every pair: checked here for the whole epoch before any step (the reference throws DimensionMismatch in the
     first unequal pair, after the steps before it)."""
+    refuse_conv(Dnet, "batch_train_gail_d_")
     _ensure_opt(Dnet, p)
     B, infos, total = p.batch_size, [], 0
     nb = min(-(-len(D_expert) // B), -(-len(D_policy) // B))
@@ -133,6 +135,7 @@ def batch_train_gail_d_(Dnet, p, D_expert, D_policy, info=None):
 
 def gail_reward_(Dnet, buf, alpha_r=0.5, Rscale=1.0):
     """r = ar*logsigmoid(D(a,s)) - (1-ar)*logcompsigmoid(D(a,s)); buf[:r] .= r .* Rscale; returns mean(r) (on_policy_gail.jl:50-55)."""
+    refuse_conv(Dnet, "gail_reward_")
     m = np.zeros(1, np.float32)
     Dnet.ctx.check(Dnet.ctx.lib.crux_gail_reward(Dnet.h, buf.h, float(alpha_r), float(Rscale), _vp(m)))
     return float(m[0])
@@ -143,6 +146,7 @@ def OnPolicyGAIL(pi, S, gamma, D, demo, lambda_gae=0.95, alpha_r=0.5, normalize_
     (src/model_free/il/on_policy_gail.jl:26-69): PPO whose post_batch_callback trains the discriminator on (demo, copy of the fresh batch),
     overwrites the rewards with the discriminator's, and refills GAE / returns / whitened advantages. gan_loss: one of GANLosses (None: GAN_BCELoss()); the reward
     does not depend on it (:51)."""
+    refuse_conv(pi, "OnPolicyGAIL (pi)"); refuse_conv(D, "OnPolicyGAIL (D)")
     d = dict(d_opt or {}); d.setdefault("name", "discriminator_")
     dp = TrainingParams(loss=gail_d_loss if gan_loss is None else gail_d_loss(gan_loss), **d)
     A = pi.space if hasattr(pi, "space") else ContinuousSpace(actor(pi).network.dims[-1])
@@ -178,6 +182,7 @@ def _d_info(p, rows, raw):
 def batch_train_gail_d_chain_(Dnet, p, D_expert, D_policy, info=None):
     """batch_train_gail_d_ as one C call (crux_gail_d_batch_train; crux_gail_d_batch_train_gan for LS, hinge and W): the same shuffles, pairs and steps, bit for bit, with one
     host synchronisation. GAN_WLossGP is refused by the entry (CRUX_EUNSUP: the penalty takes its scratch per step); batch_train_gail_d_ is its path."""
+    refuse_conv(Dnet, "batch_train_gail_d_chain_")
     _ensure_opt(Dnet, p)
     raw, rows = np.zeros(L.INFO_N, np.float32), np.zeros((p.epochs, L.INFO_N), np.float32)
     gl, lib = _gan(p), Dnet.ctx.lib
@@ -197,6 +202,7 @@ def batch_train_gail_d_chain_(Dnet, p, D_expert, D_policy, info=None):
 
 def nda_reward_cost_(Dnet, Dnda, buf, alpha_r=0.5):
     """buf[:r] and buf[:cost] from the two discriminators (nda_gail_js.jl:33-49, crux_nda_reward_cost); returns (mean(r), sum(c) / sum(episode_end), sum(episode_end))."""
+    refuse_conv(Dnet, "nda_reward_cost_ (Dnet)"); refuse_conv(Dnda, "nda_reward_cost_ (Dnda)")
     out = np.zeros(3, np.float32)
     Dnet.ctx.check(Dnet.ctx.lib.crux_nda_reward_cost(Dnet.h, Dnda.h, buf.h, float(alpha_r), _vp(out)))
     return float(out[0]), float(out[1]), float(out[2])
@@ -204,12 +210,14 @@ def nda_reward_cost_(Dnet, Dnda, buf, alpha_r=0.5):
 
 def nda_advantages_(buf, V, Vc, lambda_gae, gamma):
     """fill_gae! / fill_returns! of :r and :cost with V and Vc and both whitens (nda_gail_js.jl:51-61) as one C call (crux_nda_advantages)."""
+    refuse_conv(V, "nda_advantages_ (V)"); refuse_conv(Vc, "nda_advantages_ (Vc)")
     buf.ctx.check(buf.ctx.lib.crux_nda_advantages(buf.h, V.h, Vc.h, float(lambda_gae), float(gamma)))
 
 
 def nda_gail_round_(Dnet, Dnda, dp, dpn, demo, nda, buf, copyD, copyN, V, Vc, alpha_r, lambda_gae, gamma, info=None):
     """The whole GAIL_callback (nda_gail_js.jl:28-63) as one C call (crux_nda_gail_round; crux_nda_gail_round_gan for LS, hinge and W, the kind of dp.loss for both
     discriminators); both shuffle counters advance by the epochs run."""
+    refuse_conv(Dnet, "nda_gail_round_ (Dnet)"); refuse_conv(Dnda, "nda_gail_round_ (Dnda)"); refuse_conv(V, "nda_gail_round_ (V)"); refuse_conv(Vc, "nda_gail_round_ (Vc)")
     _ensure_opt(Dnet, dp); _ensure_opt(Dnda, dpn)
     rD, rN, out3 = np.zeros(L.INFO_N, np.float32), np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
     gl, lib = _gan(dp), Dnet.ctx.lib
@@ -239,6 +247,7 @@ def NDA_GAIL_JS(pi, S, D_demo, D_nda, Vc, gamma, D, Dnda, lambda_gae=0.95, alpha
     C call (crux_nda_gail_round). Both demonstration buffers are copied, and normalised when asked; the caller's stay as they were.
     gan_loss: one kind for both discriminators (:19-20; None: GAN_BCELoss()). LS, hinge and W take the round's _gan form; GAN_WLossGP cannot run inside a chain, so its
     callback is the round's parts in turn: batch_train_gail_d_ per discriminator (a host loop of steps), nda_reward_cost_, nda_advantages_."""
+    refuse_conv(pi, "NDA_GAIL_JS (pi)"); refuse_conv(Vc, "NDA_GAIL_JS (Vc)"); refuse_conv(D, "NDA_GAIL_JS (D)"); refuse_conv(Dnda, "NDA_GAIL_JS (Dnda)")
     d = dict(d_opt or {}); d.setdefault("name", "discriminator_")
     dn = dict(d_opt_nda or {}); dn.setdefault("name", "nda_discriminator_")
     loss = gail_d_loss if gan_loss is None else gail_d_loss(gan_loss)
@@ -269,6 +278,7 @@ mse_action_loss, logpdf_bc_loss = _Loss("mse_action"), _Loss("logpdf_bc")   # sr
 
 def loss_value(pi, p, P, D):
     """loss(pi, P, D) evaluated on the whole buffer, no update (the validation error of stop_on_validation_increase, src/utils.jl:59-72)."""
+    refuse_conv(pi, "loss_value")
     _ensure_opt(pi, p)
     cfg = _train_cfg(pi, p, P); n = len(D)
     ids = np.arange(n, dtype=np.int64); raw = np.zeros(L.INFO_N, np.float32)

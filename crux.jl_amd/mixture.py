@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .core import refuse_conv
 from .core import Chain, ContinuousNetwork, ContinuousSpace, DenseSN, DiscreteNetwork, GaussianPolicy, ParamVector, SquashedGaussianPolicy, _vp, default_context
 from .ensembles import _DeviceArrays
 
@@ -36,6 +37,10 @@ class MixtureNetwork:
         name = type(self).__name__; networks = list(networks); K = len(networks)
         if K < 1:
             raise ValueError("%s: no components" % name)
+        for q in networks + [weights]:      # (a Chain carries its trunk in .conv, a network in .trunk)
+            if getattr(q, "conv", None) is not None:
+                raise NotImplementedError("%s: a weight network with a convolutional trunk (Conv layers in its Chain) is not implemented" % name)
+            refuse_conv(q, name)
         if K > MAX_COMPONENTS:
             raise NotImplementedError("%s: %d components; the grouped device passes take at most %d" % (name, K, MAX_COMPONENTS))
         for n in networks:

@@ -12,7 +12,7 @@ from .core import (  # noqa: F401
     PolicyParams, SAMPLE_SEED, Sampler, SimpleGridWorld, SquashedGaussianPolicy, SynthMDP, TrainingParams, _F32_KEYS, _Loss, _batch_train_seam, _ensure_opt, _fill_block,
     _fill_importance_weights, _info_dict, _leaves, _np_dtype, _rollout_cfg, _train_cfg, _train_seam, _uses_seam, _vp, a2c_loss, actor, batch_train_, buffer_like, capacity,
     clone_policy, copy_buffer, copyto_, cost_value_mse_loss, critic, default_context, dim, discount, discounted_return, episodes, episodes_, extra_columns, failure, fill_gae_,
-    fill_returns_, get_episodes, hcat, lagrange_ppo_loss, mdp_data, normalize_, peer_attach_local, polyak_average_, ppo_loss, prioritized_sample_, rand_, reinforce_loss,
+    fill_returns_, get_episodes, hcat, lagrange_ppo_loss, mdp_data, normalize_, peer_attach_local, polyak_average_, ppo_loss, prioritized_sample_, rand_, refuse_conv, reinforce_loss,
     reload_switches, set_default_context, set_sample_stream_, shuffle_device_, split, split_batches, steps_, steps_multi_, train_, trim_, undiscounted_return, uniform_sample_,
     value, value_mse_loss, whiten_, whiten_multi_)
 from .on_policy import (  # noqa: F401
@@ -278,7 +278,10 @@ def value_training(solver, D, gamma):
     if solver._dy is None:
         solver._dy, solver._derr = ctx.alloc(4 * B), ctx.alloc(4 * B)
     infos = []
-    fused = solver.target_fn in ("dqn", "softq") and solver.fused_epochs and not solver.custom_seams()
+    conv = pi.trunk if getattr(pi, "is_conv", None) else None      # a conv policy always takes the call-by-call loop (the fused / async chains are not extended to it)
+    if conv is not None and (solver.target_fn != "dqn" or solver.priority_fn is not None):      # SoftQ, a custom target_fn or priority_fn would read pi.h as the whole network
+        refuse_conv(pi, "value_training with target_fn = %r%s" % (solver.target_fn, "" if solver.priority_fn is None else " and a custom priority_fn"))
+    fused = solver.target_fn in ("dqn", "softq") and solver.fused_epochs and not solver.custom_seams() and conv is None
     if fused:
         # the whole epoch loop (:69-93) in one C call: for wide networks all c_opt.epochs epochs are recorded into one list and run without a host round trip
         # between them (cruxhip.h: crux_dqn_epochs); same steps, same order, same draws as the separate calls below
@@ -305,9 +308,17 @@ def value_training(solver, D, gamma):
             y_host = _upload_target(solver, D, solver.target_fn(pim, solver.P, D, gamma, i=solver.i))  # :80 with the caller's target
         elif solver.target_fn == "softq":
             ctx.check(ctx.lib.crux_softq_target(pim.h, D.h, float(gamma), alpha, solver._dy))            # :80  softq.jl:4-13
+        elif conv is not None:
+            ctx.check(ctx.lib.crux_conv_dqn_target(conv.h, pim.trunk.p.h, pim.head_h, D.h, float(gamma), solver._dy))   # :80 over trunk + head of pi_minus
         else:
             ctx.check(ctx.lib.crux_dqn_target(pim.h, D.h, float(gamma), solver._dy))                    # :80  dqn.jl:4-6
-        if buf.isprioritized() and solver.priority_fn is not None:                                     # :83 with the caller's priority function
+        w_ = 1 if solver.weighted_loss else 0
+        if conv is not None and buf.isprioritized():                                                   # :83 and :91-93 in one call, both handles updated
+            ctx.check(ctx.lib.crux_conv_td_step_with_error(conv.h, conv.p.h, pi.head_h, D.h, solver._dy, w_, solver._derr, _vp(raw)))
+            ctx.check(ctx.lib.crux_per_update_device(buf.h, ctx.lib.crux_buffer_indices_ptr(D.h), solver._derr, B))
+        elif conv is not None:
+            ctx.check(ctx.lib.crux_conv_td_step(conv.h, conv.p.h, pi.head_h, D.h, solver._dy, w_, _vp(raw)))
+        elif buf.isprioritized() and solver.priority_fn is not None:                                     # :83 with the caller's priority function
             if y_host is None:
                 y_host = np.empty(B, np.float32); ctx.d2h(solver._dy, y_host)
             v = np.ascontiguousarray(np.asarray(solver.priority_fn(pi, solver.P, D, y_host), np.float32).reshape(-1))
@@ -386,7 +397,7 @@ def _solve_small_dqn(solver, D, s, gamma, i, stop):
     pe, pi, buf = solver.agent.pi_explore, solver.agent.pi, solver.buffer
     if not (s.h is not None and solver.fused_epochs and solver.target_fn == "dqn" and not solver.custom_seams() and solver.post_sample_callback is None and solver.post_sample_device is None and solver.pre_train_callback is None
             and solver.log is None and solver.interaction_storage is None and isinstance(pe, EpsGreedyPolicy) and isinstance(pi, DiscreteNetwork)
-            and not buf.isprioritized() and not solver.weighted_loss and max(pi.network.dims) < 128 and D.capacity <= 256 and s.n_envs <= 4 and solver.dN % s.n_envs == 0 and i <= stop):
+            and not buf.isprioritized() and not solver.weighted_loss and not pi.is_conv and max(pi.network.dims) < 128 and D.capacity <= 256 and s.n_envs <= 4 and solver.dN % s.n_envs == 0 and i <= stop):
         return i
     p, ctx = solver.c_opt, buf.ctx
     _ensure_opt(pi, p); _set_stream_for(buf, solver.sample_seed)
@@ -489,10 +500,15 @@ def _solve_off_policy(solver, mdp):
 def DQN(pi, S, N, dN=4, pi_explore=None, c_opt=None, **kw):
     """DQN(; pi::DiscreteNetwork, N, dN=4, pi_explore=eps-greedy(LinearDecaySchedule(1., 0.1, N/2)), c_opt, ...) (src/model_free/rl/dqn.jl:27-46)."""
     import copy
+    if pi.is_conv:      # trunk + head (conv.py): the call-by-call loop over crux_conv_dqn_target / crux_conv_td_step on a HostMDP
+        if int(np.prod(S.dims)) != pi.trunk.spec.in_features:
+            raise ValueError("DQN: S has %d features, the policy's trunk takes W H C = %d" % (int(np.prod(S.dims)), pi.trunk.spec.in_features))
+        if callable(kw.get("target_fn")):
+            raise NotImplementedError("DQN: a custom target_fn with a conv policy is not implemented (the built-in dqn_target only)")
     pe = pi_explore or EpsGreedyPolicy(LinearDecaySchedule(1.0, 0.1, N // 2), pi.outputs)
     pim = DiscreteNetwork(pi.network, pi.outputs, ctx=pi.ctx); copyto_(pim, pi)                          # pi_minus = deepcopy(pi)
     c = dict(c_opt or {}); c.setdefault("name", "critic_")
-    return OffPolicySolver(agent=PolicyParams(pi, pi_explore=pe, pi_minus=pim), S=S, N=N, dN=dN,
+    return OffPolicySolver(agent=PolicyParams(pi, pi_explore=pe, pi_minus=pim, conv_ok=True), S=S, N=N, dN=dN,
                            c_opt=TrainingParams(loss=td_loss, epochs=dN, **c), **kw)
 
 
@@ -502,6 +518,7 @@ sac_actor_loss, sac_temp_loss, double_Q_loss = _Loss("sac_actor"), _Loss("sac_te
 def SAC(pi, S, N, dN=50, SAC_alpha=1.0, SAC_H_target=None, pi_explore=None, SAC_alpha_opt=None, a_opt=None, c_opt=None, **kw):
     """SAC(; pi::ActorCritic{GaussianPolicy, DoubleNetwork}, dN=50, SAC_alpha=1f0, SAC_H_target=-dim(A), pi_explore=GaussianNoiseExplorationPolicy(0.1f0),
     SAC_alpha_opt, a_opt, c_opt(epochs=dN), ...) (src/model_free/rl/sac.jl:75-106)."""
+    refuse_conv(pi, "SAC")
     if not (isinstance(pi, ActorCritic) and isinstance(pi.A, GaussianPolicy) and isinstance(pi.C, DoubleNetwork)):
         raise TypeError("SAC: pi must be ActorCritic(GaussianPolicy, DoubleNetwork(ContinuousNetwork, ContinuousNetwork))")
     ad = pi.A.act_dim if pi.A.two_headed else pi.A.network.dims[-1]      # SAC_H_target = -dim(A): the action's rows, not the two-headed output's 2 ad
@@ -525,6 +542,7 @@ def _softq_alpha(alpha):
 def SoftQ(pi, S, N, dN=4, c_opt=None, alpha=1.0, **kw):
     """SoftQ(; pi::DiscreteNetwork, N, dN=4, c_opt=(epochs=4,), alpha=1f0) (src/model_free/rl/softq.jl:31-58): the policy samples from
     softmax(Q ./ alpha) (always_stochastic, :52-53), target = softq_target(alpha). ValueError unless alpha > 0."""
+    refuse_conv(pi, "SoftQ")
     pi.always_stochastic, pi.logit_div = True, _softq_alpha(alpha)
     pim = DiscreteNetwork(pi.network, pi.outputs, ctx=pi.ctx); copyto_(pim, pi)
     c = dict(c_opt or {}); c.setdefault("name", "critic_"); c.setdefault("epochs", 4)
@@ -535,6 +553,7 @@ ddpg_actor_loss, td3_actor_loss = _Loss("ddpg_actor"), _Loss("td3_actor")   # dd
 
 
 def _dpg_solver(pi, S, N, dN, pi_explore, a_opt, c_opt, target_fn, a_loss, c_loss, pi_smooth, kw):
+    refuse_conv(pi, "DDPG" if target_fn == "ddpg" else "TD3")
     c = dict(c_opt or {}); c.setdefault("name", "critic_"); c.setdefault("epochs", dN)
     a = dict(a_opt or {}); a.setdefault("name", "actor_")
     return OffPolicySolver(agent=PolicyParams(pi, pi_explore=pi_explore or GaussianNoiseExplorationPolicy(0.1), pi_minus=clone_policy(pi)), S=S, N=N, dN=dN,

@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
-from .core import refuse_spectral, refuse_two_headed, require_two_headed_opt_in, _refuse_two_headed_params   # noqa: F401
+from .core import refuse_conv, refuse_spectral, refuse_two_headed, require_two_headed_opt_in, _refuse_two_headed_params   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -123,6 +123,7 @@ def policy_gradient_training_synced(solver, D, sync_every=1):
 
 def allreduce_mean_(net):
     """average a network's parameters and Adam moments over the replica group (stream-ordered; no-op without a group)."""
+    refuse_conv(net, "allreduce_mean_ (replica groups)")
     net.ctx.check(net.ctx.lib.crux_allreduce_mean(net.h))
 
 
@@ -131,7 +132,7 @@ def policy_gradient_training_multi(pis, a_opt, c_opt, P, buffers):
     population training) as two batched launches; replica i shuffles with shuffle_seed + i. Returns one info dict per replica."""
     n = len(pis); ctx = buffers[0].ctx
     for pi in pis:
-        refuse_two_headed(pi, "policy_gradient_training_multi")
+        refuse_two_headed(pi, "policy_gradient_training_multi"); refuse_conv(pi, "policy_gradient_training_multi (multi-seed learners)")
         _ensure_opt(actor(pi), a_opt); _ensure_opt(critic(pi), c_opt)
     ca, cc = _train_cfg(actor(pis[0]), a_opt, P), _train_cfg(critic(pis[0]), c_opt, P)
     ha = (C.c_void_p * n)(*[actor(pi).h for pi in pis]); hc = (C.c_void_p * n)(*[critic(pi).h for pi in pis]); hb = (C.c_void_p * n)(*[b.h for b in buffers])
@@ -180,6 +181,7 @@ def solve(solver, mdp):
 
 def PPO(pi, S, eps=0.2, lambda_p=1.0, lambda_e=0.1, target_kl=0.012, a_opt=None, c_opt=None, required_columns=(), **kw):
     """PPO(; pi::ActorCritic, eps, lambda_p, lambda_e, target_kl, a_opt, c_opt, ...) (src/model_free/rl/ppo.jl:40-65)."""
+    refuse_conv(pi, "PPO")
     a_opt, c_opt = dict(a_opt or {}), dict(c_opt or {})
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob", "advantage"]))
     return OnPolicySolver(agent=PolicyParams(pi), S=S, P={"eps": eps, "lambda_p": lambda_p, "lambda_e": lambda_e},
@@ -194,6 +196,7 @@ def LagrangePPO(pi, Vc, S, eps=0.2, lambda_p=1.0, lambda_e=0.1, lambda_gae=0.95,
     """LagrangePPO(; pi::ActorCritic, Vc::ContinuousNetwork, ...) (src/model_free/rl/ppo.jl:138-215): PPO whose actor loss carries a PID-controlled cost
     penalty (lagrange_ppo_loss, :70-131), a cost critic Vc regressed on :cost_return, and the cost columns filled by the sampler (sampler.jl:65-66,114).
     The controller's state (I, Jc_prev, smooth_delta, smooth_Jc: the one-element arrays of P, :192-201) lives in P["lagrange"]."""
+    refuse_conv(pi, "LagrangePPO"); refuse_conv(Vc, "LagrangePPO (Vc)")
     a_opt, c_opt, cost_opt = dict(a_opt or {}), dict(c_opt or {}), dict(cost_opt or {})
     lag = L.Lagrange(); lag.target_cost, lag.penalty_max, lag.Ki_max, lag.Ki, lag.Kp, lag.Kd, lag.ema_alpha = target_cost, penalty_max, Ki_max, Ki, Kp, Kd, ema_alpha
     cols = list(dict.fromkeys(list(required_columns) + ["return", "advantage", "logprob", "cost_advantage", "cost", "cost_return"]))
@@ -209,6 +212,7 @@ def LagrangePPO(pi, Vc, S, eps=0.2, lambda_p=1.0, lambda_e=0.1, lambda_gae=0.95,
 def A2C(pi, S, lambda_p=1.0, lambda_e=0.1, a_opt=None, c_opt=None, required_columns=(), **kw):
     """A2C(; pi::ActorCritic, a_opt, c_opt, lambda_p=1f0, lambda_e=0.1f0, ...) (src/model_free/rl/a2c.jl:32-52): a2c_loss with the 0.015 KL early stop,
     critic mse, advantages whitened after sampling (post_sample_callback, :48)."""
+    refuse_conv(pi, "A2C")
     a_opt, c_opt = dict(a_opt or {}), dict(c_opt or {})
     a_opt.setdefault("target_kl", 0.015)
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob", "advantage"]))
@@ -219,6 +223,7 @@ def A2C(pi, S, lambda_p=1.0, lambda_e=0.1, a_opt=None, c_opt=None, required_colu
 
 def REINFORCE(pi, S, a_opt=None, required_columns=(), **kw):
     """REINFORCE(; pi, a_opt, ...) (src/model_free/rl/reinforce.jl:30-42): reinforce_loss with the 0.015 KL early stop; no critic, no GAE."""
+    refuse_conv(pi, "REINFORCE")
     a_opt = dict(a_opt or {}); a_opt.setdefault("target_kl", 0.015)
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob"]))
     return OnPolicySolver(agent=PolicyParams(pi), S=S, a_opt=TrainingParams(loss=reinforce_loss, name="actor_", **a_opt), c_opt=None, required_columns=cols, **kw)

@@ -1005,6 +1005,47 @@ int32_t crux_q_step(crux_mlp* q, crux_buffer* batch, const float* d_y, int32_t u
  * critic.N1 (TD3); only the actor is updated. LOSS, GRAD_NORM.                                                              */
 int32_t crux_dpg_actor_step(crux_mlp* actor, crux_mlp* q, crux_buffer* batch, float* info_out);
 
+/* convolutional trunk (csrc/conv.hip) ------------------------------------------------------------------------------------------------
+ * Chain([x -> in_scale * x,] Conv(...)..., flatten) with Flux's semantics, in front of a dense head (examples/rl/atari.jl). Images are WHCN column-major: a flattened
+ * observation has index w + W (h + H c); a layer's parameters are its (k1, k2, cin, cout) column-major weights followed by its cout biases, layer after layer (Flux.params
+ * order). Conv is a true convolution (the kernel is flipped): Conv((2,1), 1=>1) with weight [a, b] on [x1, x2, x3] gives [a x2 + b x1, a x3 + b x2]. The output extent is
+ * floor((W + 2 pad1 - k1) / stride1) + 1 (likewise the second axis), flatten yields ow + OW (oh + OH co) per sample. pad is symmetric per axis (pad < k), act one of
+ * CRUX_ACT_*. dilation other than 1 and groups other than 1 are CRUX_EUNSUP. 1 <= n_layers <= 4.
+ * The handle owns NO parameters: every entry takes a bare-vector crux_mlp (crux_mlp_create with n_layers = 0, n_extra = crux_conv_n_params) and reads crux_mlp_params_ptr /
+ * writes crux_mlp_grads_ptr of it, so Adam (crux_adam_init / crux_adam_apply), crux_mlp_copy, crux_polyak, get / set params and the Adam state accessors are the existing
+ * entries. One crux_conv serves any number of parameter handles (a policy and its target). Its workspace (cached layer outputs, weight-gradient partials) is its own, grows
+ * once to a power-of-two capacity and is re-used at smaller B. Not recordable into a fused sequence (CRUX_EUNSUP). Results are bit-reproducible run to run: no float
+ * atomics; the weight gradient's reduction over the B OH OW columns is cut into chunks of 512 columns (a constant) that are added in chunk order.                        */
+typedef struct crux_conv crux_conv;
+typedef struct {
+  int32_t k1, k2, cin, cout, stride1, stride2, pad1, pad2, act;
+  int32_t dilation1, dilation2, groups;      /* 1, 1, 1: anything else is refused by name */
+} crux_conv_layer;
+int32_t crux_conv_create(crux_ctx* ctx, int32_t W, int32_t H, int32_t C, float in_scale, int32_t n_layers, const crux_conv_layer* layers, crux_conv** out);
+int32_t crux_conv_destroy(crux_conv* conv);
+int64_t crux_conv_n_params(const crux_conv* conv);
+int64_t crux_conv_out_features(const crux_conv* conv);
+/* Flux's glorot_uniform for Conv: weights U(+-sqrt(6 / (k1 k2 cin + k1 k2 cout))), zero biases. Draw convention (crux_rng.h, as crux_mlp_init_glorot): weight number n of
+ * the trunk, counted through the layers' weight arrays in parameter order (biases not counted), is (u - 0.5) * 2 limit with u = crux_u32_to_f32 of word 0 of
+ * philox(seed, counter = n, stream, CRUX_RNG_INIT).                                                                                                                    */
+int32_t crux_conv_init_glorot(crux_conv* conv, crux_mlp* params, uint64_t seed, uint32_t stream);
+/* d_y [out_features x B] = trunk(d_x [W H C x B]); device pointers. _cached is the same pass (every pass keeps its layer outputs in the workspace for the backward call
+ * that follows) with d_y optional (NULL = keep internal only).                                                                                                         */
+int32_t crux_conv_forward(crux_conv* conv, crux_mlp* params, const float* d_x, int64_t B, float* d_y);
+int32_t crux_conv_forward_cached(crux_conv* conv, crux_mlp* params, const float* d_x, int64_t B, float* d_y);
+/* After a forward pass with the same d_x, B and parameters: for d(loss)/d(features) = d_dy [out_features x B] (not modified) the weight and bias gradients scaled by
+ * grad_scale into crux_mlp_grads_ptr(params) (skipped when want_param_grads = 0) and d(loss)/d(x), in_scale included, into d_dx [W H C x B] (NULL = skip: what the
+ * solver passes). Input elements that no window covers (stride > kernel) get exactly 0.                                                                                */
+int32_t crux_conv_backward(crux_conv* conv, crux_mlp* params, const float* d_x, int64_t B, const float* d_dy, float grad_scale, int32_t want_param_grads, float* d_dx);
+/* DQN over trunk + dense head. dqn_target (rl/dqn.jl:4-6): y = r + gamma (1 - done) max_a Q-(sp), trunk and head of the TARGET network on column SP.
+ * td_step = train!(pi, td_loss) (utils.jl:76-87, training.jl:13-25) as crux_td_step: trunk and head forward on column S, the td-loss head (weight = :weight when
+ * use_weight), head and trunk backward, ONE gradient norm over both handles (norm(grads) sees all of Flux.params), Adam on both (crux_adam_init on each first), gated on
+ * that norm. info_out: LOSS, GRAD_NORM, [2] = Qavg; one host synchronisation, none when info_out is NULL (then a NaN norm still skips both updates but is not reported).
+ * _with_error also writes td_error(pi, D, y) [B] of the same forward pass to d_err (device), for update_priorities!.                                                   */
+int32_t crux_conv_dqn_target(crux_conv* conv, crux_mlp* trunk_target, crux_mlp* head_target, crux_buffer* batch, float gamma, float* d_y);
+int32_t crux_conv_td_step(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out);
+int32_t crux_conv_td_step_with_error(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, crux_buffer* batch, const float* d_y, int32_t use_weight, float* d_err, float* info_out);
+
 #ifdef __cplusplus
 }
 #endif
