@@ -57,6 +57,7 @@ SIGNATURES = {
     "crux_prof_reset": (i32, [vp]),
     "crux_prof_get": (i32, [vp, i32, P(f64), P(i64)]),
     "crux_mlp_create": (i32, [vp, i32, P(i32), P(i32), i32, P(vp)]),
+    "crux_mlp_create_wide": (i32, [vp, i32, P(i32), P(i32), i32, P(vp)]),
     "crux_mlp_destroy": (i32, [vp]),
     "crux_mlp_n_params": (i64, [vp]),
     "crux_mlp_set_params": (i32, [vp, vp, i64]),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "crux_adam_get_state": (i32, [vp, vp, vp, vp]),
     "crux_adam_set_state": (i32, [vp, vp, vp, vp]),
     "crux_adam_state_ptrs": (i32, [vp, P(vp), P(vp)]),
+    "crux_adam_set_clip_value": (i32, [vp, f32]),
+    "crux_adam_get_clip_value": (f32, [vp]),
     "crux_buffer_create": (i32, [vp, i32, i32, i32, i64, u32, i32, f32, P(vp)]),
     "crux_buffer_destroy": (i32, [vp]),
     "crux_buffer_len": (i64, [vp]),

@@ -56,6 +56,7 @@ from .mixture import *   # noqa: F401,F403
 from .mixture import MixtureNetwork   # noqa: F401
 from .conv import Conv, ConvSpec, ConvTrunk, Scale, flatten   # noqa: F401
 from .core import refuse_conv   # noqa: F401
+from .core import ClipValue, Optimiser, refuse_optimiser_chain   # noqa: F401
 from .on_policy import _solve_on_policy
 from . import core, on_policy, imitation, off_policy, batch, il_off_policy, il_batch, il_on_policy, ensembles, continual, mixture   # noqa: F401
 

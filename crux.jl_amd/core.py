@@ -262,9 +262,12 @@ class NetworkPolicy:
         dims = (C.c_int32 * len(network.dims))(*network.dims)
         acts = (C.c_int32 * len(network.acts))(*network.acts)
         h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.crux_mlp_create(self.ctx.h, len(network.layers), dims, acts, self.n_extra, C.byref(h)))
+        # the dense head of a conv chain may be wider than 1024 (atari.jl:10 Dense(2048, 256)): crux_mlp_create_wide, a handle the dense engine's entries take. A plain MLP
+        # chain keeps crux_mlp_create and its refusal: the rollout, the learners and crux_mlp_forward behind an MLP policy do not take a wide handle.
+        create = self.ctx.lib.crux_mlp_create_wide if getattr(network, "conv", None) is not None else self.ctx.lib.crux_mlp_create
+        self.ctx.check(create(self.ctx.h, len(network.layers), dims, acts, self.n_extra, C.byref(h)))
         self.h = h
-        self.ctx.check(self.ctx.lib.crux_mlp_init_glorot(self.h, int(seed), int(stream), float(extra_init)))
+        self.ctx.check(self.ctx.lib.crux_mlp_init_glorot(self.head_h, int(seed), int(stream), float(extra_init)))
         self.optimizer = None
         self.trunk = None      # a conv policy (conv.py): the convolutional trunk in front of this handle, which is then the dense head behind flatten
         if getattr(network, "conv", None) is not None:
@@ -390,9 +393,12 @@ class NetworkPolicy:
         return y
 
     def attach_optimizer(self, opt):
+        """Adam, or Optimiser(ClipValue(c), Adam): the clamp is set on (a plain Adam: cleared from) every handle of the policy"""
         self.optimizer = opt
+        clip = getattr(opt, "clip", None)
         for h in self._handles():
             self.ctx.check(self.ctx.lib.crux_adam_init(h, opt.eta, opt.beta[0], opt.beta[1], opt.epsilon))
+            self.ctx.check(self.ctx.lib.crux_adam_set_clip_value(h, float(clip.thresh) if clip is not None else 0.0))
 
     def adam_state(self):
         """(m, v, [beta1^t, beta2^t]); a conv policy: trunk then head, the beta powers of the head (both handles step together)"""
@@ -756,6 +762,50 @@ class Adam:
     def __init__(self, eta=0.001, beta=(0.9, 0.999), epsilon=1e-8):
         self.eta = float(np.float32(eta)) if isinstance(eta, np.float32) else float(eta)
         self.beta, self.epsilon = (float(beta[0]), float(beta[1])), float(epsilon)
+
+
+class ClipValue:
+    """Flux.Optimise.ClipValue(thresh): clamp!(dx, -thresh, thresh) in front of the next optimiser of an Optimiser chain [3P-memory]"""
+
+    def __init__(self, thresh):
+        t = float(np.float32(thresh))
+        if not (t > 0.0 and math.isfinite(t)):
+            raise ValueError("ClipValue: thresh must be positive and finite, got %r" % (thresh,))
+        self.thresh = t
+
+
+class Optimiser:
+    """Flux.Optimiser(parts...): (Adam,) or (ClipValue, Adam) -- atari.jl:17's Optimiser(ClipValue(1f0), Adam(1f-3)). Exposes the Adam's eta / beta / epsilon and `clip`
+    (the ClipValue or None), so code that reads an optimiser's Adam fields keeps working. Any other composition (ClipNorm, WeightDecay, two Adams, a clamp behind Adam) is
+    not implemented."""
+
+    def __init__(self, *parts):
+        kinds = tuple(type(q) for q in parts)
+        if kinds == (Adam,):
+            self.clip, adam = None, parts[0]
+        elif kinds == (ClipValue, Adam):
+            self.clip, adam = parts
+        else:
+            raise NotImplementedError("Optimiser(%s): only Optimiser(Adam) and Optimiser(ClipValue, Adam) are implemented" % ", ".join(k.__name__ for k in kinds))
+        self.parts = tuple(parts)
+        self.eta, self.beta, self.epsilon = adam.eta, adam.beta, adam.epsilon
+
+
+def refuse_optimiser_chain(opt, who):
+    """Optimiser(ClipValue, Adam) is implemented where the update is the stand-alone gated Adam step: DQN over a conv policy or over an MLP at least 128 wide (call by call).
+    Every other receiver of an optimiser -- the other solver constructors, DQN over a narrower network, train! / batch_train!, the discriminator steps, ensembles, mixtures,
+    replica groups and multi-seed learners -- calls this and refuses by its own name before any device call; the device refuses the same updates itself
+    (crux_adam_set_clip_value in cruxhip.h). An Optimiser of a lone Adam carries no clamp and passes."""
+    if getattr(opt, "clip", None) is not None:
+        raise NotImplementedError("%s: Optimiser(ClipValue(%g), Adam) is implemented for DQN over a conv policy or a network at least 128 wide only; "
+                                  "this update would ignore the clamp" % (who, opt.clip.thresh))
+
+
+def refuse_chain_params(who, *params):
+    """refuse_optimiser_chain over TrainingParams (None entries skipped) that were not admitted by DQN"""
+    for p in params:
+        if p is not None and not getattr(p, "chain_ok", False):
+            refuse_optimiser_chain(p.optimizer, who)
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -1554,6 +1604,7 @@ class TrainingParams:
         self.optimizer = optimizer or Adam(np.float32(3e-4))
         self.batch_size, self.epochs, self.target_kl, self.name, self.max_batches = int(batch_size), int(epochs), target_kl, name, max_batches
         self.shuffle_seed, self.shuffle_counter = int(shuffle_seed), 0
+        self.chain_ok = False      # set by DQN alone: this optimiser may be Optimiser(ClipValue, Adam) (refuse_optimiser_chain)
         self.gp_counter = 0      # gail_d_loss(GAN_WLossGP()): the steps taken so far, the Philox counter of the next step's penalty draws
 
 
@@ -1708,6 +1759,7 @@ def _info_dict(p, raw, extra=True):
 
 
 def _ensure_opt(pi, p):
+    refuse_chain_params("train! (%s_loss)" % getattr(p.loss, "name", "custom"), p)      # DQN's admitted c_opt carries chain_ok (off_policy.DQN)
     if pi.optimizer is not p.optimizer:
         pi.attach_optimizer(p.optimizer)
 

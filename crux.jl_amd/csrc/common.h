@@ -158,6 +158,8 @@ struct crux_mlp {
   double* bp = nullptr; // device: [beta1^t, beta2^t]
   double eta = 0, b1 = 0, b2 = 0, eps = 0;
   bool has_adam = false;
+  float clip = 0.f;     // > 0: Optimiser(ClipValue(clip), Adam) -- the gradient element is clamped to [-clip, clip] as AdamClipGatedOp reads it (crux_adam_set_clip_value); 0: plain Adam
+  bool wide = false;    // a dimension above 1024 (crux_mlp_create_wide): taken by the dense engine's passes and the entries listed in DESIGN.md only
   float squash = 0.f;   // > 0: SquashedGaussianPolicy with this ascale (policies.jl:353-400) wherever the Gaussian head is used
   bool sigma_head = false;   // two-headed Gaussian actor (crux_mlp_set_sigma_head): output rows [0, ad) are mu, [ad, 2 ad) logSigma(s); n_extra == 0
   float* ws = nullptr;  // dense-engine workspace (dense.hip): cached activations 1..L + two delta buffers, capacity ws_B samples
@@ -293,5 +295,15 @@ int32_t crux_sn_grad(crux_mlp* n, hipStream_t st);
 void crux_sn_free(crux_mlp* n);
 // Entries whose kernels read n->p directly refuse a handle with DenseSN layers (CRUX_EUNSUP, the message names the entry): they would silently use un-normalised weights.
 int32_t crux_plain_only(const char* entry, std::initializer_list<const crux_mlp*> nets);
-#define CRUX_PLAIN_ONLY(entry, ...) do { const int32_t rc_sn__ = crux_plain_only(entry, {__VA_ARGS__}); if (rc_sn__) return rc_sn__; } while (0)
+// Entries outside the dense engine's own passes refuse a wide handle (crux_mlp_create_wide: a dimension above 1024) the same way, before anything is enqueued or changed: their
+// kernels hold a layer in LDS or registers sized for 1024 (the learners, the rollout's hbuf, the generic forward's tile) or were never run past it.
+int32_t crux_narrow_only(const char* entry, std::initializer_list<const crux_mlp*> nets);
+// Every place that applies Adam to a handle other than adam_gated's stand-alone launch (sac.hip) refuses a handle whose ClipValue prelude is on: a clamp that is set is never ignored.
+int32_t crux_no_clip(const char* entry, std::initializer_list<const crux_mlp*> nets);
+#define CRUX_CHECK_NETS(fn, entry, ...) do { const int32_t rc_chk__ = fn(entry, {__VA_ARGS__}); if (rc_chk__) return rc_chk__; } while (0)
+#define CRUX_NO_SN(entry, ...) CRUX_CHECK_NETS(crux_plain_only, entry, __VA_ARGS__)          /* raw-weight readers that take a wide handle: crux_polyak, the conv head */
+#define CRUX_NARROW_ONLY(entry, ...) CRUX_CHECK_NETS(crux_narrow_only, entry, __VA_ARGS__)   /* entries that take a DenseSN handle but no wide one */
+#define CRUX_NO_CLIP(entry, ...) CRUX_CHECK_NETS(crux_no_clip, entry, __VA_ARGS__)
+// plain = a Chain(Dense...) without DenseSN layers and no wider than 1024: what every entry outside the two lists above asks for
+#define CRUX_PLAIN_ONLY(entry, ...) do { CRUX_NO_SN(entry, __VA_ARGS__); CRUX_NARROW_ONLY(entry, __VA_ARGS__); } while (0)
 #define CRUX_DENSE_MIN_WIDTH 128   // networks at least this wide go through the multi-CU dense engine

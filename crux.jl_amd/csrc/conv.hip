@@ -410,7 +410,7 @@ int32_t crux_conv_backward(crux_conv* v, crux_mlp* params, const float* d_x, int
   return conv_backward_ws("crux_conv_backward", v, params, d_x, B, d_dy, grad_scale, want_param_grads != 0, d_dx);
 }
 
-int32_t crux_conv_dqn_target(crux_conv* v, crux_mlp* trunk_target, crux_mlp* head_target, crux_buffer* b, float gamma, float* d_y) { CRUX_PLAIN_ONLY("crux_conv_dqn_target", head_target);
+int32_t crux_conv_dqn_target(crux_conv* v, crux_mlp* trunk_target, crux_mlp* head_target, crux_buffer* b, float gamma, float* d_y) { CRUX_NO_SN("crux_conv_dqn_target", head_target);      // the head may be wide (crux_mlp_create_wide)
   if (!d_y) return CRUX_EINVAL;
   int32_t rc = conv_pair_check("crux_conv_dqn_target", v, trunk_target, head_target, b); if (rc) return rc;
   crux_ctx* c = v->ctx; const int64_t B = b->elements;
@@ -420,10 +420,10 @@ int32_t crux_conv_dqn_target(crux_conv* v, crux_mlp* trunk_target, crux_mlp* hea
                            (const float*)b->col[CRUX_COL_R], (const uint8_t*)b->col[CRUX_COL_DONE], gamma, B, d_y);
   return crux_launch_check(c, "crux_conv_dqn_target");
 }
-int32_t crux_conv_td_step(crux_conv* v, crux_mlp* trunk, crux_mlp* head, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) { CRUX_PLAIN_ONLY("crux_conv_td_step", head);
+int32_t crux_conv_td_step(crux_conv* v, crux_mlp* trunk, crux_mlp* head, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out) { CRUX_NO_SN("crux_conv_td_step", head);
   return conv_td_step_impl("crux_conv_td_step", v, trunk, head, b, d_y, use_weight, info_out, nullptr);
 }
-int32_t crux_conv_td_step_with_error(crux_conv* v, crux_mlp* trunk, crux_mlp* head, crux_buffer* b, const float* d_y, int32_t use_weight, float* d_err, float* info_out) { CRUX_PLAIN_ONLY("crux_conv_td_step_with_error", head);
+int32_t crux_conv_td_step_with_error(crux_conv* v, crux_mlp* trunk, crux_mlp* head, crux_buffer* b, const float* d_y, int32_t use_weight, float* d_err, float* info_out) { CRUX_NO_SN("crux_conv_td_step_with_error", head);
   if (!d_err) return CRUX_EINVAL;
   return conv_td_step_impl("crux_conv_td_step_with_error", v, trunk, head, b, d_y, use_weight, info_out, d_err);
 }

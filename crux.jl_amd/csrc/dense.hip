@@ -137,8 +137,9 @@ struct GemmOp { static __device__ __forceinline__ void run(const unsigned bid_, 
 #include "dense_fused.h"
 // CRUX_DENSE_FUSED=0: every layer through its own Gemm16 launch (the round-3 chains; tests compare the two forms bit for bit). Read once.
 static bool dense_fused_on() { return crux_sw().dense_fused != 0; }
-bool crux_dense_fwd_fused(const crux_mlp* n) { return dense_fused_on() && df_fwd12_ok(n->nd); }                      // layers 0 + 1 in one launch (exec.hip's phase plans ask)
-bool crux_dense_bwd_fused(const crux_mlp* n, int64_t B) { return dense_fused_on() && df_bwd_ok(n->nd, B); }
+// (a wide handle takes launch_gemm's passes only: the pair ops were written and measured for the 256-wide families)
+bool crux_dense_fwd_fused(const crux_mlp* n) { return dense_fused_on() && !n->wide && df_fwd12_ok(n->nd); }                      // layers 0 + 1 in one launch (exec.hip's phase plans ask)
+bool crux_dense_bwd_fused(const crux_mlp* n, int64_t B) { return dense_fused_on() && !n->wide && df_bwd_ok(n->nd, B); }
 bool crux_dense_bwd_fused3(const crux_mlp* n, int64_t B) {      // + the output layer's data gradient folded into the pair: the whole pullback of a three-layer network is ONE phase
   const bool on3 = crux_sw().dense_fused != 2;      // CRUX_DENSE_FUSED=2: the pair without the folded output layer (tests)
   return on3 && crux_dense_bwd_fused(n, B) && n->nd.L == 3 && (n->nd.dims[3] == 1 || n->nd.dims[3] == 4) && n->nd.acts[2] == CRUX_ACT_IDENTITY; }        // layer 1's dW beside (layer 1's dX -> layer 0's dW) in one phase
@@ -369,6 +370,7 @@ static int32_t dense_group_check(crux_mlp* const* nets, int M, int64_t B, const 
   if (M > CRUX_GROUP_MAX) return crux_fail(c, CRUX_EINVAL, "%s: %d members, at most %d", who, M, CRUX_GROUP_MAX);
   for (int m = 0; m < M; ++m) {
     if (!nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d is NULL", who, m);
+    CRUX_NARROW_ONLY(who, nets[m]);
     if (nets[m]->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: member %d belongs to another context", who, m);
     for (int k = 0; k < m; ++k) if (nets[k] == nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: members %d and %d are one handle", who, k, m);
     const NetDesc& md = nets[m]->nd;

@@ -168,6 +168,7 @@ static int32_t ens_check(crux_mlp* const* nets, int32_t M, int32_t kind, int64_t
   if (train) for (int m = 0; m < M; ++m) {
     const crux_mlp* n = nets[m], *n0 = nets[0];
     if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on member %d", m);
+    CRUX_NO_CLIP(who, n);      // k_ens_adam is plain Adam
     if (n->eta != n0->eta || n->b1 != n0->b1 || n->b2 != n0->b2 || n->eps != n0->eps) return crux_fail(c, CRUX_EINVAL, "%s: member %d's Adam differs from member 0's (one optimiser covers the ensemble)", who, m);
   }
   return dense_group_check(nets, M, B, who);      // distinct handles of one context and one shape, the batch range, no recording

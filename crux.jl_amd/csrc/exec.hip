@@ -584,7 +584,7 @@ int32_t DqnRun::epoch(int e, float* const* host_rows) const {
 }
 
 int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                       uint64_t sample_counter, float* info_out) { CRUX_PLAIN_ONLY("crux_dqn_epoch", net, target_net);
+                       uint64_t sample_counter, float* info_out) { CRUX_PLAIN_ONLY("crux_dqn_epoch", net, target_net); CRUX_NO_CLIP("crux_dqn_epoch", net);
   return DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_DQN, 0.f, use_weight, beta, sample_counter, 1, -1.f}.epoch(0, &info_out);
 }
 // value_training's epoch loop (off_policy.jl:69: `for epoch in 1:c_opt.epochs`) for the DQN family as ONE recorded list: the n epochs are recorded back to back, the
@@ -592,12 +592,12 @@ int32_t crux_dqn_epoch(crux_mlp* net, crux_mlp* target_net, crux_buffer* source,
 // the iteration's (rand!(…, i = S.i)). infos: host [n x CRUX_INFO_N]. Falls back to n single-epoch calls wherever an epoch cannot be chained (narrow networks, a
 // priority tree that needs a full rebuild between epochs).
 int32_t crux_dqn_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, int32_t use_weight, float beta,
-                        uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs", net, target_net);
+                        uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_dqn_epochs", net, target_net); CRUX_NO_CLIP("crux_dqn_epochs", net);
   return run_family(DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_DQN, 0.f, use_weight, beta, sample_counter0, n_epochs, -1.f}, &infos, nullptr);
 }
 // the same loop with softq_target(alpha) (rl/softq.jl:4-13) in place of dqn_target: SoftQ's value_training
 int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float alpha, int32_t use_weight, float beta,
-                          uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_softq_epochs", net, target_net);
+                          uint64_t sample_counter0, int32_t n_epochs, float* infos) { CRUX_PLAIN_ONLY("crux_softq_epochs", net, target_net); CRUX_NO_CLIP("crux_softq_epochs", net);
   if (!(alpha > 0.f)) return CRUX_EINVAL;
   return run_family(DqnRun{net, target_net, source, batch, gamma, DqnRun::TARGET_SOFTQ, alpha, use_weight, beta, sample_counter0, n_epochs, -1.f}, &infos, nullptr);
 }
@@ -606,7 +606,7 @@ int32_t crux_softq_epochs(crux_mlp* net, crux_mlp* target_net, crux_buffer* sour
 // polyak_average!(target_net, net, tau) rides in the last epoch's final phase (tau < 0: none). softq_alpha == 0 selects dqn_target, > 0 softq_target(alpha): a SoftQ caller
 // must pass alpha > 0. CRUX_EUNSUP for networks that do not take the recorded form (the caller uses crux_dqn_epochs / crux_softq_epochs).
 int32_t crux_dqn_value_training_async(crux_mlp* net, crux_mlp* target_net, crux_buffer* source, crux_buffer* batch, float gamma, float softq_alpha, int32_t use_weight, float beta,
-                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_value_training_async", net, target_net);
+                                      uint64_t sample_counter0, int32_t n_epochs, float tau, float* d_infos) { CRUX_PLAIN_ONLY("crux_dqn_value_training_async", net, target_net); CRUX_NO_CLIP("crux_dqn_value_training_async", net);
   if (!d_infos || softq_alpha < 0.f || tau > 1.f) return CRUX_EINVAL;
   if (!net || !target_net || !dqn_chain_case(net, target_net)) return CRUX_EUNSUP;
   if (tau >= 0.f && net->nd.n_params != target_net->nd.n_params) return crux_fail(net->ctx, CRUX_EINVAL, "value_training: polyak_average! needs equal parameter counts");
@@ -819,7 +819,7 @@ int32_t SacRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample
 
 int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                        crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t update_critic, int32_t update_actor,
-                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) { CRUX_PLAIN_ONLY("crux_sac_epoch", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
+                       uint64_t sample_counter, uint64_t noise_seed, uint64_t noise_counter0, float* info_temp, float* info_critic, float* info_actor) { CRUX_PLAIN_ONLY("crux_sac_epoch", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha); CRUX_NO_CLIP("crux_sac_epoch", actor, q1, q2, log_alpha);
   const SacRun run{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, 0, 1, 1, 1, sample_counter, noise_seed, noise_counter0};
   return run.one(update_critic, update_actor, sample_counter, noise_counter0, info_temp, info_critic, info_actor);
 }
@@ -829,7 +829,7 @@ int32_t crux_sac_epoch(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* ac
 int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                         crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
                         int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0,
-                        float* infos_temp, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_sac_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
+                        float* infos_temp, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_sac_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha); CRUX_NO_CLIP("crux_sac_epochs", actor, q1, q2, log_alpha);
   float* const host_rows[3] = {infos_temp, infos_critic, infos_actor};
   return run_family(SacRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
                            sample_counter0, noise_seed, noise_counter0}, host_rows, nullptr);
@@ -838,7 +838,7 @@ int32_t crux_sac_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
 // epoch (rows of steps an epoch skipped -- critic_every / actor_every -- are left as they were).
 int32_t crux_sac_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_mlp* log_alpha,
                               crux_buffer* source, crux_buffer* batch, float gamma, float H_target, float tau, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_sac_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha);
+                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_sac_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha); CRUX_NO_CLIP("crux_sac_epochs_async", actor, q1, q2, log_alpha);
   if (!d_infos) return CRUX_EINVAL;
   return run_family(SacRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, log_alpha, source, batch, gamma, H_target, tau, use_weight, epoch0, n_epochs, critic_every, actor_every,
                            sample_counter0, noise_seed, noise_counter0}, nullptr, d_infos);
@@ -906,7 +906,7 @@ int32_t DpgRun::one(int32_t update_critic, int32_t update_actor, uint64_t sample
 // (DDPG); otherwise TD3's clamp(a' + clamp(sigma randn, eps_min, eps_max), a_min, a_max) with noise counters noise_counter0 + e. infos_*: host [n x CRUX_INFO_N].
 int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                         float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_dpg_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ);
+                        int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* infos_critic, float* infos_actor) { CRUX_PLAIN_ONLY("crux_dpg_epochs", actor, q1, q2, actor_targ, q1_targ, q2_targ); CRUX_NO_CLIP("crux_dpg_epochs", actor, q1, q2);
   float* const host_rows[2] = {infos_critic, infos_actor};
   return run_family(DpgRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
                            sample_counter0, noise_seed, noise_counter0}, host_rows, nullptr);
@@ -914,7 +914,7 @@ int32_t crux_dpg_epochs(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* a
 // crux_dpg_epochs without the host in the loop (see crux_dqn_value_training_async): d_infos is DEVICE memory, [n_epochs][2][CRUX_INFO_N] = critic | actor rows of every epoch
 int32_t crux_dpg_epochs_async(crux_mlp* actor, crux_mlp* q1, crux_mlp* q2, crux_mlp* actor_targ, crux_mlp* q1_targ, crux_mlp* q2_targ, crux_buffer* source, crux_buffer* batch,
                               float gamma, float tau, float sigma, float eps_min, float eps_max, float a_min, float a_max, int32_t use_weight, int32_t epoch0, int32_t n_epochs,
-                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_dpg_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ);
+                              int32_t critic_every, int32_t actor_every, uint64_t sample_counter0, uint64_t noise_seed, uint64_t noise_counter0, float* d_infos) { CRUX_PLAIN_ONLY("crux_dpg_epochs_async", actor, q1, q2, actor_targ, q1_targ, q2_targ); CRUX_NO_CLIP("crux_dpg_epochs_async", actor, q1, q2);
   if (!d_infos) return CRUX_EINVAL;
   return run_family(DpgRun{actor, q1, q2, actor_targ, q1_targ, q2_targ, source, batch, gamma, tau, sigma, eps_min, eps_max, a_min, a_max, use_weight, epoch0, n_epochs, critic_every, actor_every,
                            sample_counter0, noise_seed, noise_counter0}, nullptr, d_infos);

@@ -223,12 +223,14 @@ static int32_t og_run(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64
 
 int32_t crux_offgail_d_step(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64_t Bd, uint64_t seed, uint64_t counter, float* info_out) {
   if (!D || !sources) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_offgail_d_step", D);
   const char* who = "offgail_d_step"; int32_t rc = og_check(D->ctx, D, sources, K, Bd, nullptr, who); if (rc) return rc;
   return og_run(D, sources, K, Bd, 1, nullptr, seed, counter, info_out, who);
 }
 
 int32_t crux_offgail_round(crux_mlp* D, crux_buffer* const* sources, int32_t K, int64_t Bd, int32_t d_epochs, crux_buffer* batch, uint64_t seed, uint64_t counter0, float* info_out) {
   if (!D || !sources || !batch) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_offgail_round", D);
   const char* who = "GAIL_callback"; int32_t rc = og_check(D->ctx, D, sources, K, Bd, batch, who); if (rc) return rc;
   if (d_epochs < 1 || d_epochs > 4096) return crux_fail(D->ctx, CRUX_EINVAL, "%s: d_epochs = %d out of range", who, d_epochs);
   return og_run(D, sources, K, Bd, d_epochs, batch, seed, counter0, info_out, who);
@@ -236,6 +238,7 @@ int32_t crux_offgail_round(crux_mlp* D, crux_buffer* const* sources, int32_t K, 
 
 int32_t crux_offgail_reward(crux_mlp* D, crux_buffer* batch, int32_t K, float* mean_r) {
   if (!D || !batch) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_offgail_reward", D);
   crux_ctx* c = D->ctx; const char* who = "offgail_reward";
   int32_t rc = og_check(c, D, nullptr, K, 1, batch, who); if (rc) return rc;
   const int64_t B = batch->elements; if (B > (1 << 20)) return crux_fail(c, CRUX_EUNSUP, "%s: %lld columns, more than the 2^20 one forward pass takes", who, (long long)B);

@@ -205,6 +205,7 @@ static int32_t mix_check(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, int64
   for (int k = 0; k < K; ++k) if (nets[k]->squash > 0.f) return crux_fail(c, CRUX_EUNSUP, "%s: component %d is a SquashedGaussianPolicy (the mixture head has no tanh correction)", who, k);
   if ((int64_t)K * ad > MIX_MAXKD) return crux_fail(c, CRUX_EUNSUP, "%s: %d components x %d action rows, the head takes at most %d values per column", who, K, ad, MIX_MAXKD);
   if (wnet->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: the weight handle belongs to another context", who);
+  CRUX_NARROW_ONLY(who, wnet);
   for (int k = 0; k < K; ++k) if (nets[k] == wnet) return crux_fail(c, CRUX_EINVAL, "%s: the weight handle is component %d", who, k);
   const NetDesc& wd = wnet->nd;
   if (wd.L == 0) { if (wd.n_extra != K) return crux_fail(c, CRUX_EINVAL, "%s: %d constant weights for %d components", who, wd.n_extra, K); }
@@ -216,6 +217,7 @@ static int32_t mix_check(crux_mlp* const* nets, int32_t K, crux_mlp* wnet, int64
   if (train) for (int h = 0; h <= K; ++h) {
     const crux_mlp* n = h < K ? nets[h] : wnet, *n0 = nets[0];
     if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on %s", h < K ? "a component" : "the weight handle");
+    CRUX_NO_CLIP(who, n);      // k_mix_adam is plain Adam
     if (n->eta != n0->eta || n->b1 != n0->b1 || n->b2 != n0->b2 || n->eps != n0->eps) return crux_fail(c, CRUX_EINVAL, "%s: handle %d's Adam differs from component 0's (one optimiser covers the mixture)", who, h);
   }
   return CRUX_OK;

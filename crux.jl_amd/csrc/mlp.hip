@@ -153,12 +153,8 @@ __global__ void k_adam_apply(float* __restrict__ p, const float* __restrict__ g,
 }
 __global__ void k_adam_advance(double* bp, double b1, double b2) { bp[0] *= b1; bp[1] *= b2; }
 
-extern "C" {
-
-int32_t crux_mlp_create(crux_ctx* ctx, int32_t L, const int32_t* dims, const int32_t* acts, int32_t n_extra, crux_mlp** out) {
-  if (!ctx || !out || (L > 0 && (!dims || !acts))) return CRUX_EINVAL;
-  if (L < 0 || L > CRUX_MAXL || n_extra < 0 || (L == 0 && n_extra < 1)) return crux_fail(ctx, CRUX_EINVAL, "mlp: n_layers %d / n_extra %d out of range", L, n_extra);
-  for (int i = 0; i <= L && L > 0; ++i) if (dims[i] < 1 || dims[i] > 1024) return crux_fail(ctx, CRUX_EINVAL, "mlp: dim %d = %d unsupported", i, dims[i]);
+// the allocation behind crux_mlp_create and crux_mlp_create_wide: the caller has checked the dimensions against its own limit
+static int32_t mlp_create_impl(crux_ctx* ctx, int32_t L, const int32_t* dims, const int32_t* acts, int32_t n_extra, crux_mlp** out) {
   crux_mlp* n = new crux_mlp(); n->ctx = ctx;
   const int32_t dim0[1] = {0};
   fill_desc(n->nd, L, L > 0 ? dims : dim0, acts, n_extra);
@@ -168,7 +164,25 @@ int32_t crux_mlp_create(crux_ctx* ctx, int32_t L, const int32_t* dims, const int
   HIPCHK(ctx, hipMemsetAsync(n->p, 0, bytes, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(n->g, 0, bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(n->m, 0, bytes, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(n->v, 0, bytes, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(n->bp, 0, 4 * sizeof(double), ctx->stream));
+  n->wide = n->nd.maxdim > 1024;
   *out = n; return CRUX_OK;
+}
+
+extern "C" {
+
+int32_t crux_mlp_create(crux_ctx* ctx, int32_t L, const int32_t* dims, const int32_t* acts, int32_t n_extra, crux_mlp** out) {
+  if (!ctx || !out || (L > 0 && (!dims || !acts))) return CRUX_EINVAL;
+  if (L < 0 || L > CRUX_MAXL || n_extra < 0 || (L == 0 && n_extra < 1)) return crux_fail(ctx, CRUX_EINVAL, "mlp: n_layers %d / n_extra %d out of range", L, n_extra);
+  for (int i = 0; i <= L && L > 0; ++i) if (dims[i] < 1 || dims[i] > 1024) return crux_fail(ctx, CRUX_EINVAL, "mlp: dim %d = %d unsupported", i, dims[i]);
+  return mlp_create_impl(ctx, L, dims, acts, n_extra, out);
+}
+// A Chain(Dense...) with dimensions up to 4096 (examples/rl/atari.jl:10 Dense(2048, 256); the 3136-512 head of the 84 x 84 DQN trunk): NetDesc's int32 offsets hold
+// CRUX_MAXL layers of 4096 x 4096. With every dimension <= 1024 this is crux_mlp_create; otherwise the handle is `wide` and only the dense engine's entries take it.
+int32_t crux_mlp_create_wide(crux_ctx* ctx, int32_t L, const int32_t* dims, const int32_t* acts, int32_t n_extra, crux_mlp** out) {
+  if (!ctx || !out || (L > 0 && (!dims || !acts))) return CRUX_EINVAL;
+  if (L < 0 || L > CRUX_MAXL || n_extra < 0 || (L == 0 && n_extra < 1)) return crux_fail(ctx, CRUX_EINVAL, "mlp: n_layers %d / n_extra %d out of range", L, n_extra);
+  for (int i = 0; i <= L && L > 0; ++i) if (dims[i] < 1 || dims[i] > 4096) return crux_fail(ctx, CRUX_EINVAL, "mlp (wide): dim %d = %d unsupported (1..4096)", i, dims[i]);
+  return mlp_create_impl(ctx, L, dims, acts, n_extra, out);
 }
 
 int32_t crux_mlp_destroy(crux_mlp* n) {
@@ -207,11 +221,13 @@ int32_t crux_mlp_init_glorot(crux_mlp* n, uint64_t seed, uint32_t stream, float 
 
 int32_t crux_mlp_forward(crux_mlp* n, const float* d_x, int64_t B, float* d_y) {
   if (!n || !d_x || !d_y || B < 0) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_mlp_forward", n);
   return crux_mlp_forward_impl(n, d_x, B, d_y, nullptr);
 }
 
 int32_t crux_mlp_forward_host(crux_mlp* n, const float* x, int64_t B, float* y) {
   if (!n || !x || !y || B < 0) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_mlp_forward_host", n);
   if (B == 0) return CRUX_OK;
   crux_ctx* c = n->ctx;
   const size_t bi = sizeof(float) * (size_t)B * n->nd.dims[0], bo = sizeof(float) * (size_t)B * n->nd.dims[n->nd.L];
@@ -237,7 +253,7 @@ int32_t crux_mlp_copy(crux_mlp* to, const crux_mlp* from) {
 
 int32_t crux_polyak(crux_mlp* to, const crux_mlp* from, float tau) {
   if (!to || !from) return CRUX_EINVAL;
-  CRUX_PLAIN_ONLY("crux_polyak", to, from);
+  CRUX_NO_SN("crux_polyak", to, from);
   if (to->nd.n_params != from->nd.n_params) return crux_fail(to->ctx, CRUX_EINVAL, "polyak_average!: parameter counts differ");
   const int64_t n = to->nd.n_params;
   // inside a recorded chain the three polyak updates of an epoch share a phase with other ops: 64 grid-striding blocks each instead of n / 256 (a phase of > 768 blocks takes
@@ -297,8 +313,17 @@ int32_t crux_mlp_get_sigma_head(const crux_mlp* n) { return n && n->sigma_head ?
 
 int32_t crux_adam_state_ptrs(crux_mlp* n, float** d_m, float** d_v) { if (!n) return CRUX_EINVAL; if (d_m) *d_m = n->m; if (d_v) *d_v = n->v; return CRUX_OK; }
 
+// Flux.Optimiser(ClipValue(c), Adam(...)) (examples/rl/atari.jl:17): the clamp is a property of the handle's optimiser, beside eta / b1 / b2 / eps; 0 = plain Adam
+int32_t crux_adam_set_clip_value(crux_mlp* n, float c) {
+  if (!n) return CRUX_EINVAL;
+  if (!(c >= 0.f) || c > 3.4028234664e38f) return crux_fail(n->ctx, CRUX_EINVAL, "crux_adam_set_clip_value: ClipValue threshold %g must be finite and > 0 (or 0 to switch the clamp off)", (double)c);
+  n->clip = c; return CRUX_OK;
+}
+float crux_adam_get_clip_value(const crux_mlp* n) { return n ? n->clip : 0.f; }
+
 int32_t crux_adam_apply(crux_mlp* n, float grad_scale) {
   if (!n) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_adam_apply", n); CRUX_NO_CLIP("crux_adam_apply", n);
   if (!n->has_adam) return crux_fail(n->ctx, CRUX_EINVAL, "adam_apply: crux_adam_init was not called");
   const int64_t cnt = n->nd.n_params;
   hipLaunchKernelGGL(k_adam_apply, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->ctx->stream, n->p, n->g, n->m, n->v, n->bp,

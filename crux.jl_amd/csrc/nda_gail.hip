@@ -136,6 +136,7 @@ static int32_t gd_check_kind(crux_ctx* c, int32_t gan_kind, const char* who) {
 static int32_t gd_batch_train(crux_mlp* D, crux_buffer* expert, crux_buffer* policy, int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
                               int32_t gan_kind, float* info_out, float* epoch_rows) {
   if (!D || !expert || !policy) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_gail_d_batch_train", D);
   crux_ctx* c = D->ctx; const char* who = "batch_train! (gail_d_loss)";
   int32_t rc = gd_check_kind(c, gan_kind, who); if (rc) return rc;
   rc = gd_check(c, D, expert, policy, batch_size, epochs, who); if (rc) return rc;
@@ -169,6 +170,7 @@ int32_t crux_gail_d_batch_train_gan(crux_mlp* D, crux_buffer* expert, crux_buffe
 int32_t crux_gail_d_step_gan(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, int32_t gan_kind, float lambda_gp, uint64_t gp_seed,
                              uint64_t gp_counter, float* info_out) {
   if (!D || !ex || !pi) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_gail_d_step_gan", D);
   crux_ctx* c = D->ctx; const char* who = "gail_d_loss (GAN_WLossGP)";
   if (gan_kind < CRUX_GAN_BCE || gan_kind > CRUX_GAN_WGP) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: unknown loss kind %d", gan_kind);
   if (gan_kind != CRUX_GAN_WGP) return gail_step(D, ex, off_ex, n_ex, pi, off_pi, n_pi, gan_kind, info_out);
@@ -196,6 +198,7 @@ int32_t crux_gail_d_step_gan(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64
 
 int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, float alpha_r, float* out3) {
   if (!D || !Dnda || !buf) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_nda_reward_cost", D, Dnda);
   crux_ctx* c = D->ctx; const char* who = "NDA-GAIL reward / cost";
   int32_t rc = rc_check(c, D, Dnda, buf, who); if (rc) return rc;
   const int64_t n = buf->elements;
@@ -216,7 +219,7 @@ int32_t crux_nda_reward_cost(crux_mlp* D, crux_mlp* Dnda, crux_buffer* buf, floa
 static int32_t nda_round(crux_mlp* D, crux_mlp* Dnda, crux_buffer* demo, crux_buffer* nda, crux_buffer* batch, crux_buffer* copyD, crux_buffer* copyN, crux_mlp* V, crux_mlp* Vc,
                          int32_t batch_size, int32_t epochs, int32_t max_batches, uint64_t shuffle_seed, uint64_t shuffle_counter,
                          int32_t batch_size_nda, int32_t epochs_nda, int32_t max_batches_nda, uint64_t shuffle_seed_nda, uint64_t shuffle_counter_nda,
-                         float alpha_r, float lambda, float gamma, int32_t gan_kind, float* info_D, float* info_Dnda, float* out3) { CRUX_PLAIN_ONLY("crux_nda_gail_round", V, Vc);
+                         float alpha_r, float lambda, float gamma, int32_t gan_kind, float* info_D, float* info_Dnda, float* out3) { CRUX_PLAIN_ONLY("crux_nda_gail_round", V, Vc); CRUX_NARROW_ONLY("crux_nda_gail_round", D, Dnda);
   if (!D || !Dnda || !demo || !nda || !batch || !copyD || !copyN || !V || !Vc) return CRUX_EINVAL;
   crux_ctx* c = D->ctx; const char* who = "GAIL_callback (NDA-GAIL)";
   { const int32_t rk = gd_check_kind(c, gan_kind, who); if (rk) return rk; }

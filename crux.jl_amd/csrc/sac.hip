@@ -290,6 +290,28 @@ struct AdamGatedOp { static constexpr int max_threads = 256; static __device__ _
   if (bad) { if (bid_ == 0 && threadIdx.x == 0) status[0] = CRUX_ENAN; return; }
   adam_update(bid_, nb_, p, g, m, v, bp, eta, b1, b2, eps, n, advance);
 } };
+// Flux.Optimiser(ClipValue(c), Adam) (examples/rl/atari.jl:17) gated like AdamGatedOp: apply!(::ClipValue) is clamp!(dx, -thresh, thresh) [3P-memory], then Adam's apply! sees
+// the clamped dx. The gate, the norm and the reported grad_norm are of the RAW gradient (training.jl:16-21 take norm(grads) before update!), and g keeps the raw values: the
+// element is clamped in registers as it is read -- no second pass over the gradient, no extra launch. A NaN element passes both comparisons unchanged (the gate has closed by then).
+// Stand-alone launches only (adam_gated): not a member of the op table.
+__device__ __forceinline__ float clip_value(float g, float c) { return g > c ? c : g < -c ? -c : g; }
+struct AdamClipGatedOp { static constexpr int max_threads = 256; static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, double* __restrict__ bp,
+                                                    double eta, double b1, double b2, double eps, int64_t n, const double* __restrict__ ssq, int32_t* __restrict__ status, float clip) {
+  const bool bad = isnan(ssq[0]);
+  if (status[0] == CRUX_ENAN) return;      // as AdamGatedOp: no update after an earlier "NaN detected!" of this launch sequence
+  if (bad) { if (bid_ == 0 && threadIdx.x == 0) status[0] = CRUX_ENAN; return; }
+  const double c1 = 1.0 - bp[0], c2 = 1.0 - bp[1];
+  for (int64_t i = (int64_t)bid_ * blockDim.x + threadIdx.x; i < n; i += (int64_t)nb_ * blockDim.x) {     // adam_update's Float64 expressions on the clamped element
+    const double gd = (double)clip_value(g[i], clip);
+    const float mi = (float)(b1 * (double)m[i] + (1.0 - b1) * gd);
+    const float vi = (float)(b2 * (double)v[i] + ((1.0 - b2) * gd) * gd);
+    const float d = (float)((double)mi / c1 / (sqrt((double)vi / c2) + eps) * eta);
+    m[i] = mi; v[i] = vi; p[i] = p[i] - d;
+  }
+  __syncthreads();      // the beta powers advance once every block has used them (adam_update's ticket in bp[2])
+  if (threadIdx.x == 0) { __threadfence(); unsigned* ticket = (unsigned*)(bp + 2);
+    if (atomicAdd(ticket, 1u) == nb_ - 1) { bp[0] *= b1; bp[1] *= b2; *ticket = 0u; } }
+} };
 struct AdamAdvanceOp { static __device__ __forceinline__ void run(const unsigned bid_, const unsigned nb_, double* __restrict__ bp, double b1, double b2, const double* __restrict__ ssq) {
   if (bid_ == 0 && threadIdx.x == 0 && !isnan(ssq[0])) { bp[0] *= b1; bp[1] *= b2; }      // ssq[0] was written by the info op one phase earlier
 } };
@@ -340,6 +362,7 @@ static int32_t adam_self(crux_mlp* n, const int32_t* d_flags, int32_t* d_status,
   crux_ctx* c = n->ctx;
   if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
   if (!crux_exec_recording(c)) return crux_fail(c, CRUX_EHIP, "adam_self: outside a recording");
+  CRUX_NO_CLIP("adam_self (the self-gated Adam of a recorded sequence)", n);
   const int64_t cnt = n->nd.n_params; const unsigned nbk = (unsigned)((cnt + 255) / 256);
   const Sumsq2Slot fs{fx.part[slot], fx.out1[slot], fx.in0[slot], fx.woff[slot], fx.boff[slot], fx.scale[slot]};
   crux_exec_push<AdamSelfOp>(c, nbk < 64u ? nbk : 64u, n->p, n->g, n->m, n->v, (const double*)n->bp, n->eta, n->b1, n->b2, n->eps, cnt, d_flags, d_status, fs);
@@ -411,10 +434,15 @@ static int32_t adam_gated(crux_mlp* n, const double* d_ssq, int32_t* d_status, b
   if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
   const int64_t cnt = n->nd.n_params;
   if (crux_exec_recording(c)) {      // fused sequence: at most one round of blocks, beta powers advanced by a one-thread op of the next phase (no device-scope fence per block)
+    CRUX_NO_CLIP("adam_gated inside a recorded sequence (crux_exec_recording)", n);
     const unsigned nbk = (unsigned)((cnt + 255) / 256);
     crux_exec_push<AdamGatedOp>(c, nbk < 64u ? nbk : 64u, n->p, (const float*)n->g, n->m, n->v, n->bp, n->eta, n->b1, n->b2, n->eps, cnt, d_ssq, d_status, 0, partials ? 1 : 0);
     crux_exec_push<AdamAdvanceOp>(c, 1u, n->bp, n->b1, n->b2, d_ssq);
     return CRUX_OK;
+  }
+  if (n->clip > 0.f) {      // Optimiser(ClipValue, Adam): the same launch shape, the element clamped as it is read
+    crux_launch<AdamClipGatedOp>((unsigned)((cnt + 255) / 256), 256, strm, n->p, (const float*)n->g, n->m, n->v, n->bp, n->eta, n->b1, n->b2, n->eps, cnt, d_ssq, d_status, n->clip);
+    return crux_launch_check(c, "k_adam_clip_gated");
   }
   CRUX_RUN(c, AdamGatedOp, (unsigned)((cnt + 255) / 256), 256, strm, n->p, n->g, n->m, n->v, n->bp, n->eta, n->b1, n->b2, n->eps, cnt, d_ssq, d_status, 1, 0);
   return crux_launch_check(c, "k_adam_gated");
@@ -588,6 +616,7 @@ static int32_t gail_enqueue_step(crux_mlp* D, const crux_buffer* ex, int64_t off
 // crux_gail_d_step and, for the head kinds, crux_gail_d_step_gan (nda_gail.hip)
 static int32_t gail_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n_ex, crux_buffer* pi, int64_t off_pi, int64_t n_pi, int32_t gan_kind, float* info_out) {
   if (!D || !ex || !pi) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_gail_d_step", D);
   crux_ctx* c = D->ctx; const int od = ex->obs_dim, ad = ex->act_dim, sd = od + ad;
   if (n_ex <= 0 || n_pi <= 0 || off_ex < 0 || off_pi < 0 || off_ex + n_ex > ex->elements || off_pi + n_pi > pi->elements) return crux_fail(c, CRUX_EINVAL, "gail_d_loss: row ranges outside the buffers");
   int32_t rc = gail_check(c, D, ex, pi); if (rc) return rc;
@@ -608,6 +637,7 @@ int32_t crux_gail_d_step(crux_mlp* D, crux_buffer* ex, int64_t off_ex, int64_t n
 
 int32_t crux_gail_reward(crux_mlp* D, crux_buffer* b, float alpha_r, float rscale, float* mean_r) {
   if (!D || !b) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_gail_reward", D);
   crux_ctx* c = D->ctx; const int od = b->obs_dim, ad = b->act_dim, sd = od + ad; const int64_t n = b->elements;
   if (n <= 0) return crux_fail(c, CRUX_EINVAL, "GAIL reward: empty buffer");
   if (D->nd.L < 1 || D->nd.dims[0] != sd || D->nd.dims[D->nd.L] != 1) return crux_fail(c, CRUX_EINVAL, "GAIL reward: discriminator must map vcat(a, s) (%d) -> 1", sd);

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64) void k_dqn_tiny_solve(SmallSolveArgs q) {
 // batch capacity == B <= 256, at most 4 environments, dN a multiple of them, both networks narrower than the dense engine's threshold, a rollout that the
 // generic kernel would run. infos: host [iters x epochs x CRUX_INFO_N] (loss, grad norm, [2] = Qavg per epoch).
 extern "C" int32_t crux_dqn_small_solve(crux_mlp* net, crux_mlp* target_net, crux_env* e, const crux_rollout_cfg* cfg, crux_buffer* source, crux_buffer* batch,
-                                        int32_t iters, int32_t dN, int32_t epochs, float gamma, float tau, int32_t use_weight, uint64_t i0, float* infos, double* sum_r, int64_t* n_episode_end) { CRUX_PLAIN_ONLY("crux_dqn_small_solve", net, target_net);
+                                        int32_t iters, int32_t dN, int32_t epochs, float gamma, float tau, int32_t use_weight, uint64_t i0, float* infos, double* sum_r, int64_t* n_episode_end) { CRUX_PLAIN_ONLY("crux_dqn_small_solve", net, target_net); CRUX_NO_CLIP("crux_dqn_small_solve", net);
   if (!net || !target_net || !e || !cfg || !source || !batch || iters < 1 || dN < 1 || epochs < 1) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const int64_t B = batch->capacity; const int E = e->n_envs;
   const NetDesc& pn = net->nd;

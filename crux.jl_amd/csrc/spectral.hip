@@ -105,11 +105,22 @@ int32_t crux_plain_only(const char* entry, std::initializer_list<const crux_mlp*
     return crux_fail(q->ctx, CRUX_EUNSUP, "%s: a handle with spectrally normalised layers (crux_mlp_set_spectral) was passed; this entry reads the raw weights and would ignore the normalisation", entry);
   return CRUX_OK;
 }
+int32_t crux_narrow_only(const char* entry, std::initializer_list<const crux_mlp*> nets) {
+  for (const crux_mlp* q : nets) if (q && q->wide)
+    return crux_fail(q->ctx, CRUX_EUNSUP, "%s: a wide handle (crux_mlp_create_wide, widest layer %d > 1024) was passed; this entry is outside the dense engine's passes that take one", entry, q->nd.maxdim);
+  return CRUX_OK;
+}
+int32_t crux_no_clip(const char* entry, std::initializer_list<const crux_mlp*> nets) {
+  for (const crux_mlp* q : nets) if (q && q->clip > 0.f)
+    return crux_fail(q->ctx, CRUX_EUNSUP, "%s: a handle with ClipValue(%g) in front of Adam (crux_adam_set_clip_value) was passed; this update would ignore the clamp", entry, (double)q->clip);
+  return CRUX_OK;
+}
 
 extern "C" {
 
 int32_t crux_mlp_set_spectral(crux_mlp* n, const int32_t* n_iter, const float* host_u, uint64_t seed, uint32_t stream) {
   if (!n || !n_iter) return CRUX_EINVAL;
+  CRUX_NARROW_ONLY("crux_mlp_set_spectral", n);
   crux_ctx* c = n->ctx; const NetDesc& nd = n->nd;
   if (nd.L < 1) return crux_fail(c, CRUX_EINVAL, "set_spectral: the handle has no layers");
   int n_sn = 0, n_u = 0, n_v = 0;

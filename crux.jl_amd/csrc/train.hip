@@ -298,7 +298,7 @@ static int32_t batch_train_impl(crux_mlp* net, crux_buffer* buf, const crux_trai
 
 extern "C" {
 
-int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train", net);
+int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train", net); CRUX_NO_CLIP("crux_batch_train", net);
   if (!net || !buf || !cfg) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
   if (buf->elements <= 0) return crux_fail(c, CRUX_EINVAL, "batch_train!: empty buffer");
@@ -306,7 +306,7 @@ int32_t crux_batch_train(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
   return batch_train_impl(net, buf, cfg, nullptr, perms, info_out, epoch_infos);
 }
 
-int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_lagrange", net);
+int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, crux_lagrange* lag, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_lagrange", net); CRUX_NO_CLIP("crux_batch_train_lagrange", net);
   if (!net || !buf || !cfg || !lag) return CRUX_EINVAL;
   crux_ctx* c = net->ctx;
   if (net->sigma_head) return crux_fail(c, CRUX_EUNSUP, "batch_train! (lagrange): lagrange_ppo_loss is not implemented for a two-headed Gaussian actor (logSigma network)");
@@ -319,7 +319,7 @@ int32_t crux_batch_train_lagrange(crux_mlp* net, crux_buffer* buf, const crux_tr
 
 // batch_train!(net, opt, loss + R, D) (training.jl:13,28-55) with R a DiagonalFisherRegularizer (src/extras/fisher_information.jl): crux_batch_train with the regulariser
 // carried to the dense-engine learner's chain (train_dense.hip)
-int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_fisher", net);
+int32_t crux_batch_train_fisher(crux_mlp* net, crux_fisher* R, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* perms, float* info_out, float* epoch_infos) { CRUX_PLAIN_ONLY("crux_batch_train_fisher", net); CRUX_NO_CLIP("crux_batch_train_fisher", net);
   if (!net || !R || !buf || !cfg) return CRUX_EINVAL;
   crux_ctx* c = net->ctx; const char* who = "batch_train! with a DiagonalFisherRegularizer";
   if (net->sigma_head) return crux_fail(c, CRUX_EUNSUP, "%s: not implemented for a two-headed Gaussian actor (logSigma network)", who);
@@ -342,7 +342,7 @@ static int32_t step_impl(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* 
   return run_batch(net, buf, a, 1, info_out, nullptr, false);
 }
 
-int32_t crux_train_step(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) { CRUX_PLAIN_ONLY("crux_train_step", net);
+int32_t crux_train_step(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) { CRUX_PLAIN_ONLY("crux_train_step", net); CRUX_NO_CLIP("crux_train_step", net);
   return step_impl(net, buf, cfg, ids, n, info_out, 1);
 }
 int32_t crux_loss_grad(crux_mlp* net, crux_buffer* buf, const crux_train_cfg* cfg, const int64_t* ids, int64_t n, float* info_out) { CRUX_PLAIN_ONLY("crux_loss_grad", net);
@@ -563,7 +563,7 @@ static int32_t dense_pair(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, c
 static bool pair_widths(const NetDesc& d, bool fs_on) { return d.L == 3 && d.dims[1] == 64 && (d.dims[2] == 64 || (d.dims[2] == 32 && fs_on)); }
 
 extern "C" int32_t crux_policy_gradient_training(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
-                                                 const int64_t* perms_a, const int64_t* perms_c, float* info_a, float* info_c, float* epoch_infos_a, float* epoch_infos_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training", actor, critic);
+                                                 const int64_t* perms_a, const int64_t* perms_c, float* info_a, float* info_c, float* epoch_infos_a, float* epoch_infos_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training", actor, critic); CRUX_NO_CLIP("crux_policy_gradient_training", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
   bool exact = cfg_a->target_kl < 0.f && cfg_a->max_batches <= 0;
@@ -666,6 +666,7 @@ extern "C" int32_t crux_policy_gradient_training_multi(int32_t n, crux_mlp* cons
                                                        const crux_train_cfg* cfg_c, float* info_a, float* info_c) {
   if (n < 1 || !actors || !critics || !bufs || !cfg_a || !cfg_c) return CRUX_EINVAL;
   for (int i = 0; i < n; ++i) CRUX_PLAIN_ONLY("crux_policy_gradient_training_multi", actors[i], critics[i]);
+  for (int i = 0; i < n; ++i) CRUX_NO_CLIP("crux_policy_gradient_training_multi", actors[i], critics[i]);
   crux_ctx* c = actors[0]->ctx;
   for (int i = 0; i < n; ++i) if ((actors[i] && actors[i]->sigma_head) || (critics[i] && critics[i]->sigma_head)) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: two-headed Gaussian actors (logSigma network) are not batched");
   if (!(cfg_a->target_kl < 0.f) || cfg_a->max_batches > 0 || cfg_c->max_batches > 0) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_multi: early stopping / max_batches need the sequential single-learner call");
@@ -748,7 +749,7 @@ extern "C" int32_t crux_buffer_shuffle(crux_buffer* b, uint64_t seed, uint64_t c
 // group of 1) the all-reduce is skipped and the result is bit-identical to crux_policy_gradient_training (the epoch orders are precomposed,
 // the learner state persists in device memory between launches).
 extern "C" int32_t crux_policy_gradient_training_synced(crux_mlp* actor, crux_mlp* critic, crux_buffer* buf, const crux_train_cfg* cfg_a, const crux_train_cfg* cfg_c,
-                                                        int32_t sync_every, float* info_a, float* info_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training_synced", actor, critic);
+                                                        int32_t sync_every, float* info_a, float* info_c) { CRUX_PLAIN_ONLY("crux_policy_gradient_training_synced", actor, critic); CRUX_NO_CLIP("crux_policy_gradient_training_synced", actor, critic);
   if (!actor || !critic || !buf || !cfg_a || !cfg_c || sync_every < 1) return CRUX_EINVAL;
   crux_ctx* c = actor->ctx;
   if (actor->sigma_head || critic->sigma_head) return crux_fail(c, CRUX_EUNSUP, "policy_gradient_training_synced: not implemented for a two-headed Gaussian actor (logSigma network)");
@@ -817,6 +818,7 @@ static int32_t td_step_impl(crux_mlp* net, crux_buffer* batch, const float* d_y,
     if (net->nd.dims[0] != batch->obs_dim) return crux_fail(c, CRUX_EINVAL, "train!: network input %d != obs dim %d", net->nd.dims[0], batch->obs_dim);
     return crux_td_step_dense(net, batch, d_y, use_weight, info_out, d_err);
   }
+  CRUX_NO_CLIP("crux_td_step (a network narrower than CRUX_DENSE_MIN_WIDTH: the LDS-resident learner)", net);
   if (d_err) { const int32_t rce = crux_td_error(net, batch, d_y, d_err); if (rce) return rce; }   // narrow critics: the persistent kernel has no error output
   crux_train_cfg cfg{}; cfg.loss = CRUX_LOSS_VALUE_MSE; cfg.head = CRUX_HEAD_GREEDY_Q; cfg.batch_size = (int32_t)batch->elements; cfg.epochs = 1; cfg.target_kl = -1.f;
   TrainArgs a; int32_t rc = fill_args(a, net, batch, &cfg, CRUX_LOSS_TD_INTERNAL); if (rc) return rc;

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .core import Chain, ContinuousNetwork, DenseSN, _vp, default_context
+from .core import Chain, ContinuousNetwork, DenseSN, _vp, default_context, refuse_optimiser_chain
 
 MAX_MEMBERS = 16
 
@@ -111,6 +111,7 @@ class _Ensemble:
     # ---- training -----------------------------------------------------------------------------------------------------------------------------------------------
     def attach_optimizer(self, opt):
         """one Adam for the ensemble: element-wise, so one Adam per member with the same hyper-parameters"""
+        refuse_optimiser_chain(opt, type(self).__name__ + ".attach_optimizer (the grouped Adam of the ensemble step)")
         self.optimizer = opt
         for m in self.models:
             m.attach_optimizer(opt)

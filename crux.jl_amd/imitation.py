@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
-from .core import refuse_conv
+from .core import refuse_chain_params, refuse_conv
 from .core import refuse_two_headed, require_two_headed_opt_in   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
@@ -296,6 +296,7 @@ class BatchSolver:
 
     def __init__(self, agent, S, D_train, a_opt, P=None, early_stopping=None, max_steps=100, c_opt=None, param_optimizers=None, target_fn=None,
                  target_update=None, grad_steps=0, noise_seed=0, gamma=0.99, weighted_loss=False):
+        refuse_chain_params("BatchSolver (BC / BatchSAC / CQL / AdVIL)", a_opt, c_opt, *[p for _, p in (param_optimizers or [])])
         self.agent, self.S, self.D_train, self.a_opt, self.P = agent, S, D_train, a_opt, dict(P or {})
         self.early_stopping, self.max_steps, self.epoch, self.history = early_stopping, int(max_steps), 0, []
         self.c_opt, self.param_optimizers, self.target_fn, self.target_update = c_opt, list(param_optimizers or []), target_fn, target_update

@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .core import refuse_conv
+from .core import refuse_conv, refuse_optimiser_chain
 from .core import Chain, ContinuousNetwork, ContinuousSpace, DenseSN, DiscreteNetwork, GaussianPolicy, ParamVector, SquashedGaussianPolicy, _vp, default_context
 from .ensembles import _DeviceArrays
 
@@ -166,6 +166,7 @@ class MixtureNetwork:
     # ---- training -----------------------------------------------------------------------------------------------------------------------------------------------
     def attach_optimizer(self, opt):
         """one Adam over all K + 1 handles: element-wise, so one Adam per handle with the same hyper-parameters"""
+        refuse_optimiser_chain(opt, "MixtureNetwork.attach_optimizer (the grouped Adam of the mixture step)")
         self.optimizer = opt
         for n in self.networks + [self.weight_network]:
             n.attach_optimizer(opt)

@@ -6,6 +6,7 @@ import math
 import numpy as np
 from . import _lib as L
 from .logging import aggregate_info
+from .core import refuse_chain_params, refuse_optimiser_chain   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -45,6 +46,7 @@ class OffPolicySolver:
                  prioritized=False, weighted_loss=False, i=0, a_opt=None, param_optimizers=None, P=None, target_fn="dqn", noise_seed=0, log=None, sample_seed=SAMPLE_SEED,
                  target_update=None, priority_fn=None, post_sample_callback=None, post_batch_callback=None, pre_train_callback=None, extra_buffers=(),
                  buffer_fractions=None, required_columns=(), interaction_storage=None):
+        refuse_chain_params("OffPolicySolver (every off-policy solver but DQN)", c_opt, a_opt, *[p for _, p in (param_optimizers or [])])
         self.interaction_storage = interaction_storage      # a list: every steps! block is appended to it (off_policy.jl:18,49,126,138)
         self.agent, self.S, self.N, self.dN, self.max_steps, self.c_opt, self.i = agent, S, int(N), int(dN), int(max_steps), c_opt, int(i)
         self.log = log                         # LoggerParams (crux_jl_amd.logging) or None
@@ -281,7 +283,8 @@ def value_training(solver, D, gamma):
     conv = pi.trunk if getattr(pi, "is_conv", None) else None      # a conv policy always takes the call-by-call loop (the fused / async chains are not extended to it)
     if conv is not None and (solver.target_fn != "dqn" or solver.priority_fn is not None):      # SoftQ, a custom target_fn or priority_fn would read pi.h as the whole network
         refuse_conv(pi, "value_training with target_fn = %r%s" % (solver.target_fn, "" if solver.priority_fn is None else " and a custom priority_fn"))
-    fused = solver.target_fn in ("dqn", "softq") and solver.fused_epochs and not solver.custom_seams() and conv is None
+    chain = getattr(p.optimizer, "clip", None) is not None      # Optimiser(ClipValue, Adam), admitted by DQN: call by call from the first iteration (the recorded chains refuse the clamp)
+    fused = solver.target_fn in ("dqn", "softq") and solver.fused_epochs and not solver.custom_seams() and conv is None and not chain
     if fused:
         # the whole epoch loop (:69-93) in one C call: for wide networks all c_opt.epochs epochs are recorded into one list and run without a host round trip
         # between them (cruxhip.h: crux_dqn_epochs); same steps, same order, same draws as the separate calls below
@@ -508,8 +511,16 @@ def DQN(pi, S, N, dN=4, pi_explore=None, c_opt=None, **kw):
     pe = pi_explore or EpsGreedyPolicy(LinearDecaySchedule(1.0, 0.1, N // 2), pi.outputs)
     pim = DiscreteNetwork(pi.network, pi.outputs, ctx=pi.ctx); copyto_(pim, pi)                          # pi_minus = deepcopy(pi)
     c = dict(c_opt or {}); c.setdefault("name", "critic_")
-    return OffPolicySolver(agent=PolicyParams(pi, pi_explore=pe, pi_minus=pim, conv_ok=True), S=S, N=N, dN=dN,
-                           c_opt=TrainingParams(loss=td_loss, epochs=dN, **c), **kw)
+    p = TrainingParams(loss=td_loss, epochs=dN, **c)
+    # Optimiser(ClipValue, Adam) (atari.jl:17): the stand-alone gated Adam step of crux_conv_td_step / the dense-engine crux_td_step clamps; the LDS-resident learner of a
+    # narrower network, the fused epochs and the one-launch solve do not, so such a solver is refused here, and value_training runs an admitted one call by call
+    if getattr(p.optimizer, "clip", None) is not None:
+        if not pi.is_conv and max(pi.network.dims) < 128:
+            refuse_optimiser_chain(p.optimizer, "DQN over a network narrower than 128 (the LDS-resident learner)")
+        if kw.get("target_fn", "dqn") != "dqn" and not callable(kw.get("target_fn")):
+            refuse_optimiser_chain(p.optimizer, "DQN with target_fn = %r" % (kw.get("target_fn"),))
+        p.chain_ok = True
+    return OffPolicySolver(agent=PolicyParams(pi, pi_explore=pe, pi_minus=pim, conv_ok=True), S=S, N=N, dN=dN, c_opt=p, **kw)
 
 
 sac_actor_loss, sac_temp_loss, double_Q_loss = _Loss("sac_actor"), _Loss("sac_temp"), _Loss("double_q")   # sac.jl:34-52, utils.jl:89-96
@@ -543,6 +554,7 @@ def SoftQ(pi, S, N, dN=4, c_opt=None, alpha=1.0, **kw):
     """SoftQ(; pi::DiscreteNetwork, N, dN=4, c_opt=(epochs=4,), alpha=1f0) (src/model_free/rl/softq.jl:31-58): the policy samples from
     softmax(Q ./ alpha) (always_stochastic, :52-53), target = softq_target(alpha). ValueError unless alpha > 0."""
     refuse_conv(pi, "SoftQ")
+    refuse_optimiser_chain((c_opt or {}).get("optimizer"), "SoftQ")      # before the policy is switched to sampling
     pi.always_stochastic, pi.logit_div = True, _softq_alpha(alpha)
     pim = DiscreteNetwork(pi.network, pi.outputs, ctx=pi.ctx); copyto_(pim, pi)
     c = dict(c_opt or {}); c.setdefault("name", "critic_"); c.setdefault("epochs", 4)

@@ -5,7 +5,7 @@ import ctypes as C
 import math
 import numpy as np
 from . import _lib as L
-from .core import refuse_conv, refuse_spectral, refuse_two_headed, require_two_headed_opt_in, _refuse_two_headed_params   # noqa: F401
+from .core import refuse_chain_params, refuse_conv, refuse_spectral, refuse_two_headed, require_two_headed_opt_in, _refuse_two_headed_params   # noqa: F401
 from .core import (  # noqa: F401
     ActorCritic, Adam, CartPoleMDP, Chain, Context, ContinuousNetwork, ContinuousSpace, CustomLoss, Dense, DiscreteNetwork, DiscreteSpace, DoubleNetwork, EpsGreedyPolicy,
     ExperienceBuffer, GaussianNoiseExplorationPolicy, GaussianPolicy, GymMDP, LinearDecaySchedule, MultitaskDecaySchedule, NetworkPolicy, ParamLoss, ParamVector, PendulumMDP,
@@ -31,6 +31,7 @@ class OnPolicySolver:
         # CustomLoss and a DiagonalFisherRegularizer are refused by name; so is such a network anywhere but in the actor's place. Without the keyword: refused as before.
         # (The keyword exists only to keep that earlier refusal of the plain call, which tests/test_gpu_sigma_head.py::test_refusals asserts: core.require_two_headed_opt_in.)
         require_two_headed_opt_in(agent.pi, "OnPolicySolver (PPO / A2C / REINFORCE / ASAF)", two_headed)
+        refuse_chain_params("OnPolicySolver (PPO / LagrangePPO / A2C / REINFORCE / ASAF / OnPolicyGAIL)", a_opt, c_opt, cost_opt, *[p for _, p in (param_optimizers or [])])
         _refuse_two_headed_params(actor(agent.pi), a_opt, "OnPolicySolver")
         for q in ((critic(agent.pi) if isinstance(agent.pi, ActorCritic) else None), Vc, getattr(agent, "pa", None)) + tuple(t for t, _ in (param_optimizers or [])):
             refuse_two_headed(q, "OnPolicySolver (critic / cost critic / nominal policy)")

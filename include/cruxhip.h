@@ -80,6 +80,15 @@ int32_t crux_prof_get(crux_ctx* ctx, int32_t slot, double* ms_total, int64_t* la
 enum { CRUX_ACT_IDENTITY = 0, CRUX_ACT_RELU = 1, CRUX_ACT_TANH = 2 };
 int32_t crux_mlp_create(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n_layers+1*/,
                         const int32_t* acts /*n_layers*/, int32_t n_extra, crux_mlp** out);
+/* The same Chain with dimensions 1..4096: Dense(2048, 256, relu) of examples/rl/atari.jl:10, the 3136-512 head of the 84 x 84 DQN trunk. With every dimension <= 1024
+ * this IS crux_mlp_create. Otherwise the handle is "wide" and is taken only where the dense engine (crux_mlp_forward_cached / crux_mlp_backward) runs it:
+ * crux_mlp_destroy / _n_params / _params_ptr / _grads_ptr / _set_params / _get_params / _init_glorot, crux_mlp_forward_cached, crux_mlp_backward, crux_mlp_copy,
+ * crux_polyak, crux_adam_init / _get_state / _set_state / _state_ptrs / _set_clip_value / _get_clip_value, and as the head of crux_conv_dqn_target / crux_conv_td_step /
+ * crux_conv_td_step_with_error. Every other entry that takes a crux_mlp returns CRUX_EUNSUP naming itself and the wide handle before anything is enqueued or changed: their
+ * kernels keep a layer in LDS or registers sized for 1024 (the learners, the rollout, crux_mlp_forward's generic kernel) or were never run past it.
+ * crux_mlp_create itself keeps refusing a dimension above 1024. */
+int32_t crux_mlp_create_wide(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n_layers+1*/,
+                             const int32_t* acts /*n_layers*/, int32_t n_extra, crux_mlp** out);
 int32_t crux_mlp_destroy(crux_mlp* net);
 int64_t crux_mlp_n_params(const crux_mlp* net);
 int32_t crux_mlp_set_params(crux_mlp* net, const float* host_flat, int64_t n);
@@ -152,6 +161,17 @@ int32_t crux_adam_get_state(crux_mlp* net, float* m_host, float* v_host, double*
 int32_t crux_adam_set_state(crux_mlp* net, const float* m_host, const float* v_host, const double* beta_pow);
 /* device pointers to the moment vectors (replica averaging in the multi-GPU path). */
 int32_t crux_adam_state_ptrs(crux_mlp* net, float** d_m, float** d_v);
+/* Flux.Optimiser(ClipValue(c), Adam(eta)) (examples/rl/atari.jl:17, c_opt of its DQN): c > 0 and finite puts ClipValue in front of this handle's Adam, 0 takes it away,
+ * anything else is CRUX_EINVAL. A property of the handle beside eta / beta / eps: crux_mlp_copy does not copy it, crux_adam_init does not reset it. With the clamp on, the
+ * stand-alone gated Adam step of the dense-engine entries (crux_td_step / _with_error over a network at least CRUX_DENSE_MIN_WIDTH wide, crux_conv_td_step / _with_error, the
+ * other call-by-call steps of sac.hip's family) clamps each gradient element to [-c, c] as it reads it (clamp! inside apply!(::ClipValue), Flux [3P-memory]): moments and
+ * parameters see the clamped value; the norm, the NaN gate, the reported grad_norm (src/training.jl:16-21 take norm(grads) before update!) and the gradient buffer are the
+ * raw gradient's. Every other place that applies Adam returns CRUX_EUNSUP naming itself and ClipValue before launching: a recorded sequence (crux_dqn_epoch(s),
+ * crux_softq_epochs, crux_dqn_value_training_async, crux_sac_epoch(s)(_async), crux_dpg_epochs(_async)), crux_adam_apply, the learner kernels (crux_batch_train and its
+ * _lagrange / _fisher forms, crux_train_step, crux_policy_gradient_training and its _multi / _synced forms, crux_td_step over a narrower network), crux_dqn_small_solve,
+ * crux_ensemble_step / _train and crux_mixture_step / _train. */
+int32_t crux_adam_set_clip_value(crux_mlp* net, float c);
+float crux_adam_get_clip_value(const crux_mlp* net);
 
 /* experience buffer ------------------------------------------------------------------------------
  * replaces mdp_data / ExperienceBuffer (src/experience_buffer.jl:4-35,53-80). Columns are separate

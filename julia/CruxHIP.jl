@@ -49,6 +49,8 @@ const INFO_N = 16
 
 # ---------------------------------------------------------------------------------------------------- networks
 # A HipNetwork owns a crux_mlp handle mirroring a Flux Chain(Dense...) (src/policies.jl:68-157); n_extra trailing trainables = GaussianPolicy's logΣ (:315-320)
+# (Not bound here: the conv entries, and with them the wide-handle constructor for Dense(2048, 256) behind a conv trunk and the ClipValue setter of Optimiser(ClipValue, Adam)
+#  -- examples/rl/atari.jl; include/cruxhip.h and INTEGRATION.md describe them, crux.jl_amd/conv.py and core.py are their tested twin.)
 mutable struct HipNetwork <: Crux.NetworkPolicy
     ctx::Ctx; h::Ptr{Cvoid}; dims::Vector{Int32}; head::Int32; outputs
 end
