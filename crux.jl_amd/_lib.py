@@ -230,6 +230,10 @@ SIGNATURES = {
     "crux_conv_dqn_target": (i32, [vp, vp, vp, vp, f32, vp]),
     "crux_conv_td_step": (i32, [vp, vp, vp, vp, vp, i32, vp]),
     "crux_conv_td_step_with_error": (i32, [vp, vp, vp, vp, vp, i32, vp, vp]),
+    "crux_fill_gae_rows_values": (i32, [vp, vp, vp, f32, f32, i64, i64, i64, i32]),
+    "crux_conv_forward_pair":(i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
+    "crux_conv_backward_pair": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, i32, vp, vp]),
+    "crux_conv_pg_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, vp, vp]),
 }
 
 _lib = None

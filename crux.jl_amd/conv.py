@@ -8,7 +8,8 @@ no handle of the whole network, and code that reads one would run the head over 
 images (a flattened observation has index w + W (h + H c)), (k1, k2, cin, cout) weights, a true (flipped) convolution, flatten in WHC order.
 
 What takes a conv policy: value / forward, the parameter and optimiser accessors (trunk first, then head: Flux.params order), polyak_average_, copyto_, clone_policy,
-policy_explore on the host seam (a HostMDP: pixel environments live on the host), and DQN through solve. Everything else refuses it by name (core.refuse_conv)."""
+policy_explore on the host seam (a HostMDP: pixel environments live on the host), DQN through solve, and PPO / A2C / REINFORCE for a conv DiscreteNetwork actor (with a conv
+ContinuousNetwork critic in an ActorCritic: on_policy._conv_policy_gradient_training over csrc/conv_pair.hip). Everything else refuses it by name (core.refuse_conv)."""
 import ctypes as C
 
 import numpy as np

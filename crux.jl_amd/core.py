@@ -635,14 +635,17 @@ def refuse_spectral(pi, who):
 
 def refuse_conv(pi, who):
     """A conv policy (convolutional trunk + dense head, conv.py) is taken by value / forward, the parameter accessors, polyak_average_, copyto_, clone_policy, policy_explore on
-    a HostMDP and DQN. The entry points that take a network call this and refuse by their own name before any device call: the solver constructors (by name: PPO, LagrangePPO,
-    A2C, REINFORCE, SAC, SoftQ, DDPG, TD3; the others through PolicyParams), a Sampler on a device MDP, train! / batch_train!, fill_gae!, the GAIL discriminator steps and
-    reward, the replica-group and multi-seed learners. Behind them stands NetworkPolicy.h itself: a conv policy has no whole-network handle, so any other path that reads
+    a HostMDP, DQN, and -- as a conv DiscreteNetwork actor with (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic -- PPO, A2C and REINFORCE (on_policy.py). The
+    entry points that take a network call this and refuse by their own name before any device call: the other solver constructors (by name: LagrangePPO, SAC, SoftQ, DDPG,
+    TD3; BC, the GAIL family and the rest through PolicyParams), PPO / A2C / REINFORCE for a conv Gaussian actor or an actor / critic pair of which only one is conv, a
+    Sampler on a device MDP, train! / batch_train!, fill_gae!, the GAIL discriminator steps and reward, the replica-group and multi-seed learners, EWC, and
+    Optimiser(ClipValue, Adam) outside DQN (refuse_chain_params). Behind them stands NetworkPolicy.h itself: a conv policy has no whole-network handle, so any other path that reads
     `.h` (an ensemble member, a mixture's weight network, a Fisher regulariser's network, a custom-loss seam) raises the same NotImplementedError at that read instead of
     running the head as the whole network. (bson.py loads buffers only: there is no policy loader to guard.)"""
     for q in ([] if pi is None else _leaves(pi)):
         if getattr(q, "is_conv", None):
-            raise NotImplementedError("%s: a policy with a convolutional trunk (Conv layers in its Chain) is implemented for DQN on a HostMDP only; "
+            raise NotImplementedError("%s: a policy with a convolutional trunk (Conv layers in its Chain) is implemented on a HostMDP for DQN and for PPO / A2C / REINFORCE "
+                                      "(a conv DiscreteNetwork actor; PPO and A2C with a conv ContinuousNetwork critic, in an ActorCritic) only; "
                                       "this path would treat the dense head as the whole network" % who)
 
 
@@ -1389,9 +1392,13 @@ def _steps_host(sampler, buffer, Nsteps, cfg, pi_on, explore, i, reset, cb, stor
         arr = np.asfortranarray(v); keep.append(arr); ptrs[L.COL[k]] = arr.ctypes.data
     cr = critic(sampler.agent.pi) if buffer.haskey("advantage") else None
     fr = C.c_int64()
-    buffer.ctx.check(buffer.ctx.lib.crux_steps_push(buffer.h, int(Nsteps), ptrs, int(T), 1 if reset else 0, cr.h if cr is not None else None, float(sampler.lam), float(sampler.gamma),
-                                                    sampler.Vc.h if sampler.Vc is not None else None, pa.h if pa is not None else None,
-                                                    (L.HEAD["categorical"] if isinstance(pa, DiscreteNetwork) else L.HEAD["gaussian"]) if pa is not None else 0, C.byref(fr)))
+    if getattr(cr, "is_conv", None):      # a conv critic is no handle crux_steps_push can evaluate: the push, fill_gae! on V(s), V(sp) of trunk + head, fill_returns!
+        _push_block_conv_critic(sampler, buffer, data, cr, first, Nsteps, T, reset)
+        fr.value = first
+    else:
+        buffer.ctx.check(buffer.ctx.lib.crux_steps_push(buffer.h, int(Nsteps), ptrs, int(T), 1 if reset else 0, cr.h if cr is not None else None, float(sampler.lam), float(sampler.gamma),
+                                                        sampler.Vc.h if sampler.Vc is not None else None, pa.h if pa is not None else None,
+                                                        (L.HEAD["categorical"] if isinstance(pa, DiscreteNetwork) else L.HEAD["gaussian"]) if pa is not None else 0, C.byref(fr)))
     assert fr.value == first
     if buffer.haskey("traj_importance_weight"):
         _fill_traj_weights(sampler, buffer, first, Nsteps, reset)
@@ -1400,6 +1407,27 @@ def _steps_host(sampler, buffer, Nsteps, cfg, pi_on, explore, i, reset, cb, stor
     if store is not None:
         store.append(buffer.minibatch((first + np.arange(Nsteps)) % buffer.capacity + 1))
     return info_out
+
+
+def _push_block_conv_critic(sampler, buffer, data, cr, first, Nsteps, T, reset):
+    """crux_steps_push's work for an on-policy block whose critic is a conv policy: push!(buffer, data), fill_gae! with V(s), V(sp) from value(critic, .) (trunk + head on the
+    device; crux_fill_gae_rows_values scans them), fill_returns!. The importance-weight and cost columns belong to solvers that refuse a conv policy."""
+    ctx = buffer.ctx
+    for k in ("cost_advantage", "cost_return", "importance_weight", "fwd_importance_weight", "cum_importance_weight", "rev_importance_weight"):
+        if buffer.haskey(k):
+            refuse_conv(cr, "steps! into a buffer with a :%s column" % k)
+    if Nsteps > buffer.capacity:
+        raise L.CruxError(L.EINVAL, "steps!: a block of %d transitions does not fit the buffer (capacity %d) whose advantage column it must fill" % (Nsteps, buffer.capacity))
+    buffer.push_(data)
+    v = np.ascontiguousarray(np.concatenate([value(cr, data["s"]).reshape(-1), value(cr, data["sp"]).reshape(-1)]), np.float32)
+    d_v = ctx.alloc(v.nbytes)
+    try:
+        ctx.h2d(d_v, v)
+        ctx.check(ctx.lib.crux_fill_gae_rows_values(buffer.h, d_v, C.c_void_p(d_v.value + 4 * Nsteps), float(sampler.lam), float(sampler.gamma), int(first), int(Nsteps), int(T), 1 if reset else 0))
+    finally:
+        ctx.free(d_v)
+    if buffer.haskey("return"):
+        ctx.check(ctx.lib.crux_fill_returns_rows(buffer.h, float(sampler.gamma), int(first), int(Nsteps), int(T), 1 if reset else 0))
 
 
 def _fill_block(sampler, buffer, first, Nsteps, reset):

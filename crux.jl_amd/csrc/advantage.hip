@@ -251,6 +251,19 @@ int32_t crux_fill_gae_rows_keys(crux_buffer* b, crux_mlp* critic, float lambda, 
   return scan_fill(b, critic, lambda, gamma, scan_range(first_row, n_rows, b->capacity, rows_per_env, close_last), source, target);
 }
 int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) { CRUX_PLAIN_ONLY("crux_fill_gae_rows", critic); return crux_fill_gae_rows_keys(b, critic, lambda, gamma, first_row, n_rows, rows_per_env, close_last, CRUX_COL_R, CRUX_COL_ADVANTAGE); }
+// fill_gae! on a block of rows with V(s), V(sp) supplied by the caller (device, [n_rows] in block order): a critic that is no plain MLP over the observation -- a conv critic's
+// trunk + head (on_policy.py) -- evaluates them itself; the scan, its NaN flag and its one synchronisation are scan_fill's
+int32_t crux_fill_gae_rows_values(crux_buffer* b, const float* d_vs, const float* d_vsp, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last) {
+  if (!b || !d_vs || !d_vsp) return CRUX_EINVAL;
+  crux_ctx* c = b->ctx; const ScanRange g = scan_range(first_row, n_rows, b->capacity, rows_per_env, close_last);
+  int32_t rc = scan_check(b, nullptr, CRUX_COL_R, CRUX_COL_ADVANTAGE, g, "fill_gae!"); if (rc) return rc;
+  if (g.n == 0) return CRUX_OK;
+  int32_t* flag = (int32_t*)crux_scratch(c, 256); if (!flag) return crux_fail(c, CRUX_ENOMEM, "fill_gae!: scratch");
+  HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->stream));
+  scan_enqueue(b, lambda, gamma, g, CRUX_COL_R, CRUX_COL_ADVANTAGE, -1, d_vs, d_vsp, flag);
+  rc = crux_launch_check(c, "k_gae_returns"); if (rc) return rc;
+  return scan_flag(c, flag);
+}
 int32_t crux_fill_returns_keys(crux_buffer* b, float gamma, int32_t source, int32_t target) {
   if (!b) return CRUX_EINVAL;
   return scan_fill(b, nullptr, 0.f, gamma, whole_buffer(b), source, target);

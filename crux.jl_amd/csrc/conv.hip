@@ -20,6 +20,7 @@
 #include "common.h"
 #include "exec.h"
 #include "ops_small.h"
+#include "pg_head.h"
 
 #define CRUX_CONV_MAXL 4
 #define CONV_WG_CHUNK 512      // columns of one weight-gradient partial: a constant, so the sums do not depend on the grid or the card
@@ -50,9 +51,11 @@ __device__ __forceinline__ void conv_mfma64(const float (&a)[4][4], const float 
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][r], b[u][r], acc, 0, 0, 0);
 }
-#define CONV_KLOOP(kbeg, kend, load, compute)                                          \
+// AD: empty, or [2] for the two weight (or delta) operands that share one patch operand in conv_pair.hip
+#define CONV_KLOOP(kbeg, kend, load, compute) CONV_KLOOP_A(, kbeg, kend, load, compute)
+#define CONV_KLOOP_A(AD, kbeg, kend, load, compute)                                    \
   if ((kbeg) < (kend)) {                                                                \
-    float a0[4][4], b0[4][4], a1[4][4], b1[4][4];                                       \
+    float a0 AD[4][4], b0[4][4], a1 AD[4][4], b1[4][4];                                 \
     int64_t k0 = (kbeg); load(k0, a0, b0);                                              \
     for (;;) {                                                                          \
       bool more = k0 + 64 < (kend); if (more) load(k0 + 64, a1, b1);                    \
@@ -66,13 +69,14 @@ __device__ __forceinline__ void conv_mfma64(const float (&a)[4][4], const float 
 
 // VEC: k1 % 4 == 0, s1 % 4 == 0, p1 == 0, IW % 4 == 0 and both bases 16-byte aligned (conv_fwd_vec): four consecutive k share (u2, ci) and are four consecutive, aligned image
 // elements and four consecutive (descending) weights -- one 16-byte load each. Which k meets which is unchanged, so the bits do not depend on the form.
+// (each kernel's body is a device function of its argument pack and block index: conv_pair.hip launches the same bodies with the member of a trunk pair as blockIdx.y)
 template <bool VEC>
-__global__ __launch_bounds__(256) void k_conv_fwd(const ConvArgs q) {
+__device__ __forceinline__ void conv_fwd_body(const ConvArgs& q, const unsigned bid) {
   const ConvLayerDesc& d = q.d;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int OHW = d.OW * d.OH; const int64_t N = (int64_t)q.B * OHW;
   const int tm = (d.cout + 15) >> 4; const int64_t tn = (N + 15) >> 4;
-  const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
+  const int64_t tile = (int64_t)bid * 4 + wv;
   if (tile >= tm * tn) return;
   const int i0 = (int)(tile % tm) << 4; const int64_t j0 = (tile / tm) << 4;
   const int ia = i0 + c; const int64_t jb = j0 + c;
@@ -112,14 +116,15 @@ __global__ __launch_bounds__(256) void k_conv_fwd(const ConvArgs q) {
   for (int r = 0; r < 4; ++r) { const int i = i0 + 4 * g + r; if (i >= d.cout) continue;
     q.y[sp + (int64_t)OHW * (i + (int64_t)d.cout * b)] = crux_act(d.act, acc[r] + q.bias[i]); }
 }
+template <bool VEC> __global__ __launch_bounds__(256) void k_conv_fwd(const ConvArgs q) { conv_fwd_body<VEC>(q, blockIdx.x); }
 
 // weight gradient: wave (tile, chunk) sums dz[co, n] x[patch(kk, n)] over the chunk's columns n ascending; kk is the weight's own (unflipped) index t1 + k1 (t2 + k2 ci)
-__global__ __launch_bounds__(256) void k_conv_wgrad(const ConvArgs q) {
+__device__ __forceinline__ void conv_wgrad_body(const ConvArgs& q, const unsigned bid) {
   const ConvLayerDesc& d = q.d;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int OHW = d.OW * d.OH, K = d.K; const int64_t N = (int64_t)q.B * OHW;
   const int tm = (d.cout + 15) >> 4, tk = (K + 15) >> 4, ntile = tm * tk; const int64_t nch = (N + CONV_WG_CHUNK - 1) / CONV_WG_CHUNK;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + wv;
+  const int64_t wid = (int64_t)bid * 4 + wv;
   if (wid >= ntile * nch) return;
   const int tile = (int)(wid % ntile); const int64_t ch = wid / ntile;
   const int i0 = (tile % tm) << 4, j0 = (tile / tm) << 4;
@@ -165,21 +170,23 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const ConvArgs q) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) { const int i = i0 + 4 * g + r; if (i < d.cout) part[jb + (int64_t)K * i] = acc[r]; }
 }
+__global__ __launch_bounds__(256) void k_conv_wgrad(const ConvArgs q) { conv_wgrad_body(q, blockIdx.x); }
 // the chunks of one gradient element in chunk order, then the scale: g[woff + e], e over the layer's weights and biases (they are contiguous in the flat vector)
-__global__ void k_conv_wgrad_combine(const float* __restrict__ part, int64_t per, int64_t nch, float scale, float* __restrict__ gout) {
+__device__ __forceinline__ void conv_wgrad_combine_body(const float* __restrict__ part, int64_t per, int64_t nch, float scale, float* __restrict__ gout) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; if (e >= per) return;
   float s = part[e];
   for (int64_t ch = 1; ch < nch; ++ch) s += part[ch * per + e];
   gout[e] = scale * s;
 }
+__global__ void k_conv_wgrad_combine(const float* __restrict__ part, int64_t per, int64_t nch, float scale, float* __restrict__ gout) { conv_wgrad_combine_body(part, per, nch, scale, gout); }
 
 // data gradient, gather form
-__global__ __launch_bounds__(256) void k_conv_dgrad(const ConvArgs q) {
+__device__ __forceinline__ void conv_dgrad_body(const ConvArgs& q, const unsigned bid) {
   const ConvLayerDesc& d = q.d;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int IHW = d.IW * d.IH, OHW = d.OW * d.OH; const int64_t N = (int64_t)q.B * IHW;
   const int tm = (d.cin + 15) >> 4; const int64_t tn = (N + 15) >> 4;
-  const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
+  const int64_t tile = (int64_t)bid * 4 + wv;
   if (tile >= tm * tn) return;
   const int i0 = (int)(tile % tm) << 4; const int64_t j0 = (tile / tm) << 4;
   const int ia = i0 + c; const int64_t jb = j0 + c;
@@ -214,6 +221,7 @@ __global__ __launch_bounds__(256) void k_conv_dgrad(const ConvArgs q) {
     const int64_t e = sp + (int64_t)IHW * (i + (int64_t)d.cin * b);
     q.dx[e] = q.ysrc ? crux_act_grad(q.act_prev, q.ysrc[e], acc[r]) : acc[r] * q.dxscale; }
 }
+__global__ __launch_bounds__(256) void k_conv_dgrad(const ConvArgs q) { conv_dgrad_body(q, blockIdx.x); }
 
 // Flux's glorot_uniform for Conv: U(+-sqrt(6 / (k1 k2 cin + k1 k2 cout))) weights, zero biases. crux_rng.h convention of crux_mlp_init_glorot: weight number n of the
 // trunk (counted over the layers' weight arrays in order, biases not counted) is (crux_u32_to_f32(philox(seed, n, stream, CRUX_RNG_INIT).v[0]) - 0.5) * 2 limit

@@ -11,6 +11,7 @@
 #include "train_args.h"
 #include "peer_wait.h"
 #include "mfma_helpers.h"      // EPS32F
+#include "pg_head.h"
 
 __global__ void k_gather_obs(const float* __restrict__ S, int od, const int32_t* __restrict__ rows, int64_t nb, float* __restrict__ x) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; if (i >= nb * od) return;
@@ -91,22 +92,8 @@ __global__ __launch_bounds__(256) void k_pg_head(PgHeadArgs q) {
       continue; }
     const float A = q.ADV[row], oldlp = q.LP[row]; float newlp = 0.f, H = 0.f, r, g;
     if (q.head == CRUX_HEAD_CATEGORICAL) {
-      const uint8_t* av = (const uint8_t*)q.A + row * q.ad;
-      float mx = z[0]; for (int k = 1; k < q.nout; ++k) mx = z[k] > mx ? z[k] : mx;
-      float sum = 0.f; for (int k = 0; k < q.nout; ++k) sum += expf(z[k] - mx);
-      float qq = 0.f, hp = 0.f;
-      for (int k = 0; k < q.nout; ++k) { const float pk = expf(z[k] - mx) / sum; qq += pk * (av[k] ? 1.f : 0.f);
-        const float lg = logf(pk + EPS32F); H -= pk * lg; hp += (-lg - pk / (pk + EPS32F)) * pk; }
-      newlp = logf(qq);
-      r = expf(newlp - oldlp); const float u = r * A, rc = fminf(fmaxf(r, q.lo), q.hi), cl = rc * A;
-      g = (u <= cl) ? A : 0.f; s_lossp += (double)(a2c ? newlp * A : (u <= cl ? u : cl));
-      if (a2c) { g = A; r = 1.f; }
-      float gcr = 0.f;
-      if (lagr) { const float Ac = q.CADV[row]; const float uc = r * Ac, clc = rc * Ac; s_cost += (double)(uc >= clc ? uc : clc); gcr = (uc >= clc ? Ac : 0.f) * r; }
-      for (int k = 0; k < q.nout; ++k) { const float pk = expf(z[k] - mx) / sum; const float lg = logf(pk + EPS32F); const float hk = -lg - pk / (pk + EPS32F);
-        const float dlogpi = pk * ((av[k] ? 1.f : 0.f) / qq) - pk;
-        const float base = -q.lambda_p * g * r * dlogpi - q.lambda_e * (pk * (hk - hp));
-        dy[k] = lagr ? invB * ((base + pen * gcr * dlogpi) / (1.f + pen)) : invB * base; }
+      const PgCatTerms t = pg_categorical_sample(z, q.nout, (const uint8_t*)q.A + row * q.ad, A, oldlp, q.lo, q.hi, q.lambda_p, q.lambda_e, a2c, invB, lagr, pen, lagr ? q.CADV[row] : 0.f, dy);      // pg_head.h
+      newlp = t.newlp; H = t.H; r = t.r; s_lossp += (double)t.lossp; if (lagr) s_cost += (double)t.cost;
     } else {                                                                        // GaussianPolicy / SquashedGaussianPolicy (policies.jl:333-348,374-396)
       const float* av = (const float*)q.A + row * q.ad; const float sq = q.squash;
       for (int k = 0; k < q.ad; ++k) { const float sg = expf(sq > 0.f ? sq_clampls(q.ls[k]) : q.ls[k]); const float uk = sq > 0.f ? sq_untanh(av[k], sq) : av[k]; const float d = uk - z[k];

@@ -46,9 +46,80 @@ class OnPolicySolver:
         self.buffer, self.sampler, self.history = None, None, []
 
 
+def _conv_pg_policy(pi, who, with_critic):
+    """True: `pi` is what the conv policy-gradient step takes -- a conv DiscreteNetwork actor and (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic. False: no conv
+    network in it. Everything in between is refused by name: a conv Gaussian actor, and a pair of which only one member has a trunk (the step pairs two trunks)."""
+    if not any(getattr(q, "is_conv", None) for q in _leaves(pi)):
+        return False
+    A = actor(pi)
+    if not (isinstance(A, DiscreteNetwork) and A.is_conv):
+        refuse_conv(pi, "%s (the actor must be a DiscreteNetwork over a conv chain; conv Gaussian actors and conv critics behind an MLP actor are not implemented)" % who)
+    if with_critic:
+        Cn = critic(pi) if isinstance(pi, ActorCritic) else None
+        if not (type(Cn) is ContinuousNetwork and Cn.is_conv and Cn.network.dims[-1] == 1):
+            refuse_conv(pi, "%s (a conv actor needs a conv ContinuousNetwork critic ending in one value, in an ActorCritic)" % who)
+    return True
+
+
+def _conv_policy_gradient_training(solver, D):
+    """policy_gradient_training for a conv actor (and critic): the reference's loop (on_policy.jl:56-78, training.jl:28-55) on the host -- per epoch shuffle!(D) on the device,
+    then crux_conv_pg_step on each partition of batch_size rows, both networks in one step (the paired trunk passes of csrc/conv_pair.hip). The actor leaves the loop at its
+    KL early stop (training.jl:46,49), its epochs or max_batches; the critic trains on alone (loss = value_mse, no actor) until its own end. Both networks see the same
+    minibatches: the reference shuffles anew for the critic's batch_train!, which draws from the same distribution."""
+    pi, pa, pc, P = solver.agent.pi, solver.a_opt, solver.c_opt, solver.P
+    if getattr(solver, "param_optimizers", None) or getattr(solver, "cost_opt", None) is not None or pa.loss.name not in ("ppo", "a2c", "reinforce") or (pc is not None and pc.loss.name != "value_mse"):
+        refuse_conv(pi, "policy_gradient_training with %s_loss, a cost critic or param_optimizers" % pa.loss.name)
+    for p in (pa, pc):
+        if p is not None and (_uses_seam(p) or p.early_stopping is not None):
+            refuse_conv(pi, "policy_gradient_training with a regularizer, a CustomLoss or an early_stopping function")
+    A, Cn = actor(pi), (critic(pi) if pc is not None else None)
+    _ensure_opt(A, pa)
+    if Cn is not None:
+        _ensure_opt(Cn, pc)
+    ctx, lib, n, od, na = D.ctx, D.ctx.lib, len(D), A.trunk.spec.in_features, len(A.outputs)
+    col = {k: D.column_ptr(k) for k in ("s", "a", "logprob", "return") + (("advantage",) if pa.loss.name != "reinforce" else ())}
+    at = lambda k, row, width: C.c_void_p(col[k] + row * width) if k in col else None      # noqa: E731
+    ha, hc = (A.trunk.h, A.trunk.p.h, A.head_h), ((Cn.trunk.h, Cn.trunk.p.h, Cn.head_h) if Cn is not None else (None, None, None))
+    rows = {"a": [], "c": []}; done = {"a": False, "c": Cn is None}; nb = {"a": 0, "c": 0}; last = {"a": None, "c": None}
+    raw, craw = np.zeros(L.INFO_N, np.float32), np.zeros(2, np.float32)
+    kl_max = None if pa.target_kl is None else float(pa.target_kl)
+    for epoch in range(max(pa.epochs, pc.epochs if pc is not None else 0)):
+        done["a"] = done["a"] or epoch >= pa.epochs; done["c"] = done["c"] or epoch >= pc.epochs      # (no critic: done from the start, pc is not read)
+        if done["a"] and done["c"]:
+            break
+        shuffle_device_(D, pa.shuffle_seed, pa.shuffle_counter); pa.shuffle_counter += 1
+        live = {"a": not done["a"], "c": not done["c"]}      # who trains in this epoch; the actor's KL stop inside the epoch ends its minibatch loop (training.jl:46)
+        for s0 in range(0, n, pa.batch_size):
+            if not (live["a"] or live["c"]):
+                break
+            B = min(pa.batch_size, n - s0)
+            ctx.check(lib.crux_conv_pg_step(*(ha if live["a"] else (None, None, None)), *(hc if live["c"] else (None, None, None)), at("s", s0, 4 * od), at("a", s0, na), at("advantage", s0, 4),
+                                            at("return", s0, 4), at("logprob", s0, 4), B, L.LOSS[pa.loss.name] if live["a"] else L.LOSS["value_mse"],
+                                            float(P.get("eps", 0.2)), float(P.get("lambda_p", 1.0)), float(P.get("lambda_e", 0.1)), _vp(raw), _vp(craw)))
+            for k, p, r in (("a", pa, raw), ("c", pc, craw)):
+                if live[k]:
+                    nb[k] += 1; last[k] = r.copy()
+                    if p.max_batches not in (None, math.inf) and nb[k] >= p.max_batches:      # training.jl:45
+                        live[k] = False; done[k] = True
+            if live["a"] and kl_max is not None and raw[L.INFO["kl"]] > kl_max:                 # :46, and :49 ends the actor's epochs on the same KL
+                live["a"] = False; done["a"] = True
+        for k in ("a", "c"):      # the epoch's info is its last minibatch's (aggregate_info(minibatch_infos), SURVEY App. A-Q3)
+            if last[k] is not None:
+                rows[k].append(last[k]); last[k] = None
+    info = {}
+    if rows["a"]:
+        info.update(_info_dict(pa, np.mean(rows["a"], axis=0)))
+    info[pa.name + "batches_trained"] = nb["a"]
+    if Cn is not None:
+        m = np.mean(rows["c"], axis=0); info.update({pc.name + "loss": float(m[0]), pc.name + "grad_norm": float(m[1]), pc.name + "batches_trained": nb["c"]})
+    return info
+
+
 def policy_gradient_training(solver, D, perms_a=None, perms_c=None):
     """policy_gradient_training(S, D) (src/model_free/on_policy.jl:56-78): actor batch_train!, then critic batch_train!.
     One C call: the two persistent learner kernels overlap on two CUs whenever that is exact (see cruxhip.h)."""
+    if getattr(actor(solver.agent.pi), "is_conv", None):
+        return _conv_policy_gradient_training(solver, D)
     info = {}
     for theta, p_opt in getattr(solver, "param_optimizers", []):                                       # on_policy.jl:59-61: batch_train!(θs, p_opt, P, D, π_loss=agent.π)
         p_opt.pi_loss = solver.agent.pi
@@ -182,10 +253,10 @@ def solve(solver, mdp):
 
 def PPO(pi, S, eps=0.2, lambda_p=1.0, lambda_e=0.1, target_kl=0.012, a_opt=None, c_opt=None, required_columns=(), **kw):
     """PPO(; pi::ActorCritic, eps, lambda_p, lambda_e, target_kl, a_opt, c_opt, ...) (src/model_free/rl/ppo.jl:40-65)."""
-    refuse_conv(pi, "PPO")
+    conv = _conv_pg_policy(pi, "PPO", with_critic=True)
     a_opt, c_opt = dict(a_opt or {}), dict(c_opt or {})
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob", "advantage"]))
-    return OnPolicySolver(agent=PolicyParams(pi), S=S, P={"eps": eps, "lambda_p": lambda_p, "lambda_e": lambda_e},
+    return OnPolicySolver(agent=PolicyParams(pi, conv_ok=conv), S=S, P={"eps": eps, "lambda_p": lambda_p, "lambda_e": lambda_e},
                           a_opt=TrainingParams(loss=ppo_loss, target_kl=target_kl, name="actor_", **a_opt),
                           c_opt=TrainingParams(loss=value_mse_loss, name="critic_", **c_opt),
                           post_batch_callback=lambda D, info: whiten_(D, "advantage"),
@@ -213,21 +284,21 @@ def LagrangePPO(pi, Vc, S, eps=0.2, lambda_p=1.0, lambda_e=0.1, lambda_gae=0.95,
 def A2C(pi, S, lambda_p=1.0, lambda_e=0.1, a_opt=None, c_opt=None, required_columns=(), **kw):
     """A2C(; pi::ActorCritic, a_opt, c_opt, lambda_p=1f0, lambda_e=0.1f0, ...) (src/model_free/rl/a2c.jl:32-52): a2c_loss with the 0.015 KL early stop,
     critic mse, advantages whitened after sampling (post_sample_callback, :48)."""
-    refuse_conv(pi, "A2C")
+    conv = _conv_pg_policy(pi, "A2C", with_critic=True)
     a_opt, c_opt = dict(a_opt or {}), dict(c_opt or {})
     a_opt.setdefault("target_kl", 0.015)
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob", "advantage"]))
-    return OnPolicySolver(agent=PolicyParams(pi), S=S, P={"lambda_p": lambda_p, "lambda_e": lambda_e},
+    return OnPolicySolver(agent=PolicyParams(pi, conv_ok=conv), S=S, P={"lambda_p": lambda_p, "lambda_e": lambda_e},
                           a_opt=TrainingParams(loss=a2c_loss, name="actor_", **a_opt), c_opt=TrainingParams(loss=value_mse_loss, name="critic_", **c_opt),
                           post_sample_callback=lambda D, info: whiten_(D, "advantage"), required_columns=cols, **kw)
 
 
 def REINFORCE(pi, S, a_opt=None, required_columns=(), **kw):
     """REINFORCE(; pi, a_opt, ...) (src/model_free/rl/reinforce.jl:30-42): reinforce_loss with the 0.015 KL early stop; no critic, no GAE."""
-    refuse_conv(pi, "REINFORCE")
+    conv = _conv_pg_policy(pi, "REINFORCE", with_critic=False)
     a_opt = dict(a_opt or {}); a_opt.setdefault("target_kl", 0.015)
     cols = list(dict.fromkeys(list(required_columns) + ["return", "logprob"]))
-    return OnPolicySolver(agent=PolicyParams(pi), S=S, a_opt=TrainingParams(loss=reinforce_loss, name="actor_", **a_opt), c_opt=None, required_columns=cols, **kw)
+    return OnPolicySolver(agent=PolicyParams(pi, conv_ok=conv), S=S, a_opt=TrainingParams(loss=reinforce_loss, name="actor_", **a_opt), c_opt=None, required_columns=cols, **kw)
 
 
 _solve_on_policy = solve

@@ -84,7 +84,7 @@ int32_t crux_mlp_create(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n
  * this IS crux_mlp_create. Otherwise the handle is "wide" and is taken only where the dense engine (crux_mlp_forward_cached / crux_mlp_backward) runs it:
  * crux_mlp_destroy / _n_params / _params_ptr / _grads_ptr / _set_params / _get_params / _init_glorot, crux_mlp_forward_cached, crux_mlp_backward, crux_mlp_copy,
  * crux_polyak, crux_adam_init / _get_state / _set_state / _state_ptrs / _set_clip_value / _get_clip_value, and as the head of crux_conv_dqn_target / crux_conv_td_step /
- * crux_conv_td_step_with_error. Every other entry that takes a crux_mlp returns CRUX_EUNSUP naming itself and the wide handle before anything is enqueued or changed: their
+ * crux_conv_td_step_with_error / crux_conv_pg_step. Every other entry that takes a crux_mlp returns CRUX_EUNSUP naming itself and the wide handle before anything is enqueued or changed: their
  * kernels keep a layer in LDS or registers sized for 1024 (the learners, the rollout, crux_mlp_forward's generic kernel) or were never run past it.
  * crux_mlp_create itself keeps refusing a dimension above 1024. */
 int32_t crux_mlp_create_wide(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n_layers+1*/,
@@ -354,6 +354,9 @@ int32_t crux_fill_returns(crux_buffer* b, float gamma);
  * (0 = the block is one environment's).                                                                                                          */
 int32_t crux_fill_gae_rows(crux_buffer* b, crux_mlp* critic, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last);
 int32_t crux_fill_returns_rows(crux_buffer* b, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last);
+/* crux_fill_gae_rows with V(s), V(sp) of the block's rows supplied by the caller (device, [n_rows] each, in block order) instead of a critic handle: for a critic that is
+ * not an MLP over the observation (a conv critic: trunk + head). Same scan, same NaN check (CRUX_ENAN).                                             */
+int32_t crux_fill_gae_rows_values(crux_buffer* b, const float* d_vs, const float* d_vsp, float lambda, float gamma, int64_t first_row, int64_t n_rows, int64_t rows_per_env, int32_t close_last);
 /* the `source=` / `target=` keywords of fill_gae! / fill_returns! (sampler.jl:255,275), as terminate_episode! uses them for cost constraints (:65-66):
  * fill_gae!(data, ep, Vc, lambda, gamma, source=:cost, target=:cost_advantage), fill_returns!(data, ep, gamma, source=:cost, target=:cost_return).
  * source / target: CRUX_COL_* of Float32 one-row columns.                                                                                         */
@@ -1065,6 +1068,28 @@ int32_t crux_conv_backward(crux_conv* conv, crux_mlp* params, const float* d_x, 
 int32_t crux_conv_dqn_target(crux_conv* conv, crux_mlp* trunk_target, crux_mlp* head_target, crux_buffer* batch, float gamma, float* d_y);
 int32_t crux_conv_td_step(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, crux_buffer* batch, const float* d_y, int32_t use_weight, float* info_out);
 int32_t crux_conv_td_step_with_error(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, crux_buffer* batch, const float* d_y, int32_t use_weight, float* d_err, float* info_out);
+/* Two trunks over ONE input batch (csrc/conv_pair.hip: an actor's and a critic's chain of the same shape, examples/rl/cartpole.jl:8-9). With equal layer tables, input
+ * extents and scales, every layer of both members is one launch: layer 0 gathers each image tile once and multiplies it against both members' weights (forward and weight
+ * gradient), the later layers and the data gradient take the member as a grid index. Each member's results are bit-identical to crux_conv_forward_cached /
+ * crux_conv_backward on that member alone (same operands in the same order per output element; no float atomics). Trunks whose tables differ are run as those two
+ * single passes, silently. The two members need a crux_conv and a parameter handle of their own (CRUX_EINVAL otherwise) and the same number of input features.
+ * d_y0 / d_y1 (optional), d_dy0 / d_dy1, d_dx0 / d_dx1 (optional): as d_y, d_dy, d_dx of the single forms, per member.                                                */
+int32_t crux_conv_forward_pair(crux_conv* conv0, crux_mlp* params0, crux_conv* conv1, crux_mlp* params1, const float* d_x, int64_t B, float* d_y0, float* d_y1);
+int32_t crux_conv_backward_pair(crux_conv* conv0, crux_mlp* params0, crux_conv* conv1, crux_mlp* params1, const float* d_x, int64_t B, const float* d_dy0, const float* d_dy1,
+                                float grad_scale, int32_t want_param_grads, float* d_dx0, float* d_dx1);
+/* One minibatch of train!(actor, ppo_loss | a2c_loss | reinforce_loss) and train!(critic, Flux.mse(value, return)) (rl/ppo.jl:4-21,60, a2c.jl:4-15, reinforce.jl:4-13,
+ * training.jl:13-25) for a categorical actor and a value critic that are each a trunk + dense head (heads may be wide handles). Device inputs, column j = sample j:
+ * d_s [W H C x B], d_a [n x B] one-hot bytes, d_adv [B] (whitened by the caller: crux_whiten), d_ret [B], d_old_logprob [B]. Either network may be absent (all three of its
+ * handles NULL): no critic for reinforce_loss (or a critic that trains on after the actor's KL stop: loss = CRUX_LOSS_VALUE_MSE with no actor). Launch sequence: paired
+ * trunk forward (single when one network is absent), each head's dense forward, one column-head launch (per column the max-subtracted softmax, categorical_logpdf and
+ * entropy with the reference's eps, the loss's terms and d(loss)/d(logits), and the critic's seed 2 (v - ret) / B; block partials in Float64, added in block order), each
+ * head's dense backward, paired trunk backward, norm(grads) of each network over its trunk and head, Adam on all four handles (crux_adam_init on each first) behind ONE
+ * gate: a NaN norm of either network leaves all four untouched and returns CRUX_ENAN. One host synchronisation. info_out (host [CRUX_INFO_N]): the actor's LOSS,
+ * GRAD_NORM, ENTROPY, KL, CLIP_FRACTION, AVG_ADVANTAGE, AVG_RETURN (reinforce_loss: the return is the weight, lambda_p = 1, lambda_e = 0, as in crux_batch_train);
+ * critic_out (host [2] or NULL): the critic's loss and gradient norm. Two identical calls give identical bits.                                                          */
+int32_t crux_conv_pg_step(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp* actor_head, crux_conv* critic_conv, crux_mlp* critic_trunk, crux_mlp* critic_head,
+                          const float* d_s, const uint8_t* d_a, const float* d_adv, const float* d_ret, const float* d_old_logprob, int64_t B,
+                          int32_t loss, float eps_clip, float lambda_p, float lambda_e, float* info_out, float* critic_out);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,11 @@ library's side, on the same card; every figure is the median of `reps` windows o
 --atari: the TRUE network and optimiser of examples/rl/atari.jl -- 80x80x4 -> 16@(8,8)/4 -> 32@(4,4)/2 -> flatten -> Dense(2048, 256, relu) -> Dense(256, 6) (the head is a wide
 handle, crux_mlp_create_wide) with Optimiser(ClipValue(1), Adam(1e-3)) and with plain Adam(1e-3), B = 32 -- beside torch-ROCm eager with clip_grad_value_ before Adam.step.
 The head's forward (crux_mlp_forward_cached) and backward (crux_mlp_backward) are timed alone on the trunk's features; the update has no entry of its own, so its line is the
-whole step minus the four passes (derived, and says so). Writes profiles/conv_atari_bench.txt with --save."""
+whole step minus the four passes (derived, and says so). Writes profiles/conv_atari_bench.txt with --save.
+
+--pg: an actor's and a critic's Atari trunk over one batch (csrc/conv_pair.hip) -- forward + backward paired beside two single passes of the same build, and the whole
+crux_conv_pg_step (ppo_loss + critic mse, 2048-256-6 and 2048-256-1 heads) beside two single-trunk steps and beside the same step in torch-ROCm eager; B = 32 and 128.
+Writes profiles/conv_pg_bench.txt with --save."""
 import argparse
 import ctypes as C
 import json
@@ -87,6 +91,11 @@ def torch_child(a):
         for clip in (0, 1):
             out["atari_clip%d" % clip] = median_window(*torch_atari_step(32, x, clip), a.n, a.reps)
         print(json.dumps(out)); return
+    if a.pg:
+        for B in (32, 128):
+            step, passes, sync = torch_pg(B, np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32)))
+            out["step%d" % B] = median_window(step, sync, a.n, a.reps); out["passes%d" % B] = median_window(passes, sync, a.n, a.reps)
+        print(json.dumps(out)); return
     for B in (32, 128):
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
         out["trunk%d" % B] = median_window(*torch_side(32, B, x, False), a.n, a.reps); out["step%d" % B] = median_window(*torch_side(16, B, x, True), a.n, a.reps)
@@ -145,9 +154,81 @@ def atari(a, crux, L):
         open(os.path.join(ROOT, "profiles", "conv_atari_bench.txt"), "w").write(txt)
 
 
+def torch_pg(B, x_host):
+    """the PPO step of crux_conv_pg_step restated: actor and critic as two Sequential nets over one batch, clipped surrogate + entropy, critic mse, norms, two Adam steps;
+    and the two trunks' forward + backward alone"""
+    import torch
+    dev = torch.device("cuda")
+    mk = lambda nout: torch.nn.Sequential(torch.nn.Conv2d(4, 16, 8, 4), torch.nn.ReLU(), torch.nn.Conv2d(16, 32, 4, 2), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(2048, 256), torch.nn.ReLU(),      # noqa: E731
+                                          torch.nn.Linear(256, nout)).to(dev)
+    A, V = mk(6), mk(1); oa, ov = torch.optim.Adam(A.parameters(), lr=1e-3), torch.optim.Adam(V.parameters(), lr=1e-3)
+    x = torch.tensor(x_host.T.reshape(B, 4, 80, 80).copy(), device=dev); act = torch.zeros(B, dtype=torch.long, device=dev)
+    adv, ret, old = torch.randn(B, device=dev), torch.randn(B, device=dev), torch.full((B,), -1.79, device=dev); dy = torch.ones(B, 2048, device=dev)
+
+    def step():
+        oa.zero_grad(set_to_none=True); ov.zero_grad(set_to_none=True); xs = x * (1.0 / 255.0)
+        p = torch.softmax(A(xs), 1); lp = torch.log(p.gather(1, act[:, None])[:, 0]); r = torch.exp(lp - old)
+        loss = -torch.minimum(r * adv, torch.clamp(r, 0.8, 1.2) * adv).mean() + 0.1 * (p * torch.log(p + 1.1920929e-07)).sum(1).mean()
+        closs = ((V(xs)[:, 0] - ret) ** 2).mean(); (loss + closs).backward()
+        torch.nn.utils.clip_grad_norm_(A.parameters(), float("inf")); torch.nn.utils.clip_grad_norm_(V.parameters(), float("inf"))
+        oa.step(); ov.step(); return (old - lp).mean().item()      # the KL the host reads every step
+
+    def passes():
+        oa.zero_grad(set_to_none=True); ov.zero_grad(set_to_none=True); xs = x * (1.0 / 255.0)
+        A[:5](xs).backward(dy); V[:5](xs).backward(dy)
+    return step, passes, torch.cuda.synchronize
+
+
+def pg(a, crux, L):
+    """--pg: the paired trunk passes beside two single ones, and crux_conv_pg_step (PPO, actor + critic) beside two single-trunk steps and torch eager; Atari trunk, 2048-256 heads"""
+    ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
+    for B in (32, 128):
+        x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
+        A = crux.DiscreteNetwork(chain(32, 256), list(range(6)), seed=2, ctx=ctx)
+        V = crux.ContinuousNetwork(crux.Chain(crux.Scale(1.0 / 255.0), crux.Conv((8, 8), 4, 16, "relu", stride=4), crux.Conv((4, 4), 16, 32, "relu", stride=2), crux.flatten, crux.Dense(2048, 256, "relu"),
+                                              crux.Dense(256, 1), input=(80, 80, 4)), seed=3, ctx=ctx)
+        for q in (A, V):
+            q.attach_optimizer(crux.Adam(np.float32(1e-3)))
+        ta, tv, F = A.trunk, V.trunk, A.trunk.spec.out_features
+        arrs = [x, np.asfortranarray(np.eye(6, dtype=np.uint8)[:, rng.integers(0, 6, B)]), rng.normal(0, 1, B).astype(np.float32), rng.normal(0, 1, B).astype(np.float32), np.full(B, -1.79, np.float32),
+                np.ones((F, B), np.float32)]
+        d = [ctx.alloc(v.nbytes) for v in arrs]
+        for p, v in zip(d, arrs):
+            ctx.h2d(p, v)
+        d_x, d_a, d_adv, d_ret, d_lp, d_dy = d; raw, craw = np.zeros(L.INFO_N, np.float32), np.zeros(2, np.float32); vp = lambda v: v.ctypes.data_as(C.c_void_p)      # noqa: E731
+        pair = lambda: (ctx.check(ctx.lib.crux_conv_forward_pair(ta.h, ta.p.h, tv.h, tv.p.h, d_x, B, None, None)),                                # noqa: E731
+                        ctx.check(ctx.lib.crux_conv_backward_pair(ta.h, ta.p.h, tv.h, tv.p.h, d_x, B, d_dy, d_dy, 1.0, 1, None, None)))
+        two = lambda: [(ctx.check(ctx.lib.crux_conv_forward_cached(t.h, t.p.h, d_x, B, None)), ctx.check(ctx.lib.crux_conv_backward(t.h, t.p.h, d_x, B, d_dy, 1.0, 1, None))) for t in (ta, tv)]      # noqa: E731
+        ha, hv, no = (ta.h, ta.p.h, A.head_h), (tv.h, tv.p.h, V.head_h), (None, None, None)
+        call = lambda x1, x2, loss: ctx.check(ctx.lib.crux_conv_pg_step(*x1, *x2, d_x, d_a, d_adv, d_ret, d_lp, B, loss, 0.2, 1.0, 0.1, vp(raw), vp(craw)))      # noqa: E731
+        step = lambda: call(ha, hv, L.LOSS["ppo"])                                                      # noqa: E731
+        step2 = lambda: (call(ha, no, L.LOSS["ppo"]), call(no, hv, L.LOSS["value_mse"]))               # noqa: E731
+        ours[B] = {k: median_window(f, ctx.sync, a.n, a.reps) for k, f in (("pair", pair), ("two", two), ("step", step), ("step2", step2))}
+        for p in d:
+            ctx.free(p)
+    ctx.sync()
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-child", "--pg", "--n", str(a.n), "--reps", str(a.reps)], capture_output=True, text=True, timeout=300)
+    try:
+        tor = json.loads(child.stdout.strip().splitlines()[-1])
+    except Exception:      # noqa: BLE001
+        tor = None; sys.stderr.write(child.stderr[-2000:])
+    for B in (32, 128):
+        o = ours[B]; f = lambda t: "%.1f us (%.1f .. %.1f)" % t      # noqa: E731
+        tt = ("torch eager: not measured (the torch child process failed)", "torch eager: not measured") if tor is None else tuple(
+            "torch eager %s; ratio torch / ours %.2f" % (f(tuple(tor["%s%d" % (k, B)])), tor["%s%d" % (k, B)][0] / o[m][0]) for k, m in (("passes", "pair"), ("step", "step")))
+        verdict = lambda p, s: "paired is faster" if p[2] < s[1] else ("paired is SLOWER than two single passes beyond the spread" if p[1] > s[2] else "inside the run-to-run spread")      # noqa: E731
+        lines.append("two Atari trunks, forward + backward, B %3d: paired %s, two single passes %s, ratio two / paired %.2f (%s); %s" % (B, f(o["pair"]), f(o["two"]), o["two"][0] / o["pair"][0], verdict(o["pair"], o["two"]), tt[0]))
+        lines.append("crux_conv_pg_step (ppo_loss + critic mse, 2048-256-6 and 2048-256-1 heads), B %3d: %s, as two single-trunk steps (actor, then critic: two synchronisations) %s, ratio %.2f; %s"
+                     % (B, f(o["step"]), f(o["step2"]), o["step2"][0] / o["step"][0], tt[1]))
+    txt = "# tools/conv_bench.py --pg: one MI355X, f32, median of %d windows of %d calls (min .. max), host clock around synchronised windows\n" % (a.reps, a.n) + "\n".join(lines) + "\n"
+    print(txt)
+    if a.save:
+        open(os.path.join(ROOT, "profiles", "conv_pg_bench.txt"), "w").write(txt)
+
+
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=200); ap.add_argument("--reps", type=int, default=7); ap.add_argument("--save", action="store_true")
-    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true")
+    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true")
     a = ap.parse_args()
     if a.torch_child:
         return torch_child(a)
@@ -156,6 +237,8 @@ def main():
     from crux_jl_amd import _lib as L
     if a.atari:
         return atari(a, crux, L)
+    if a.pg:
+        return pg(a, crux, L)
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
     for B in (32, 128):
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
