@@ -234,6 +234,11 @@ SIGNATURES = {
     "crux_conv_forward_pair":(i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "crux_conv_backward_pair": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, i32, vp, vp]),
     "crux_conv_pg_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, vp, vp]),
+    "crux_conv_ensemble_forward": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, i64, vp, vp, vp, vp]),
+    "crux_conv_ensemble_logpdf": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, vp, i64, vp]),
+    "crux_conv_ensemble_step": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, vp, vp, i64, vp]),
+    "crux_conv_ensemble_train": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp]),
+    "crux_conv_ensemble_passes": (i32, [P(vp), P(vp), P(vp), i32, vp, i64, P(vp), P(vp), P(vp)]),
 }
 
 _lib = None

@@ -288,6 +288,9 @@ float* crux_dense_act(crux_mlp* n, int l);
 #define CRUX_GROUP_MAX 16
 int32_t crux_dense_forward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, hipStream_t st);
 int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags);
+// ... with one input matrix per member, and (d_dx, or NULL) one input gradient per member [dims[0] x B]: the dense heads behind an ensemble's conv trunks
+int32_t crux_dense_forward_group_x(crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, hipStream_t st);
+int32_t crux_dense_backward_group_dx(crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags, float* const* d_dx);
 int32_t crux_td_step_dense(crux_mlp* net, crux_buffer* b, const float* d_y, int32_t use_weight, float* info_out, float* d_err);   // sac.hip
 // spectral.hip: the power iteration + effective weights of one forward pass, the conversion of the weight gradient after one backward pass (enqueued only)
 int32_t crux_sn_power(crux_mlp* n, hipStream_t st);

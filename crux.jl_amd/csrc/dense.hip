@@ -364,13 +364,15 @@ __global__ void k_act_grad_group(const ActGradGroup t, const unsigned bpm, int a
   ActGradOp::run(blockIdx.x - m * bpm, bpm, t.dy[m], t.y[m], act, n, t.dz[m]);
 }
 // what every grouped pass asks of its handles: 1..CRUX_GROUP_MAX distinct plain handles of one context and one shape, outside a recording
-static int32_t dense_group_check(crux_mlp* const* nets, int M, int64_t B, const char* who) {
+// (wide_ok: asked by the test entry crux_conv_ensemble_passes alone, which calls the unchecked passes below itself -- Gemm16's tiles know no width, a wide handle's own
+// passes are launch_gemm's; every production pass refuses a wide handle here)
+static int32_t dense_group_check(crux_mlp* const* nets, int M, int64_t B, const char* who, bool wide_ok = false) {
   if (!nets || M < 1 || !nets[0]) return CRUX_EINVAL;
   crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
   if (M > CRUX_GROUP_MAX) return crux_fail(c, CRUX_EINVAL, "%s: %d members, at most %d", who, M, CRUX_GROUP_MAX);
   for (int m = 0; m < M; ++m) {
     if (!nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d is NULL", who, m);
-    CRUX_NARROW_ONLY(who, nets[m]);
+    if (!wide_ok) CRUX_NARROW_ONLY(who, nets[m]);
     if (nets[m]->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: member %d belongs to another context", who, m);
     for (int k = 0; k < m; ++k) if (nets[k] == nets[m]) return crux_fail(c, CRUX_EINVAL, "%s: members %d and %d are one handle", who, k, m);
     const NetDesc& md = nets[m]->nd;
@@ -383,29 +385,40 @@ static int32_t dense_group_check(crux_mlp* const* nets, int M, int64_t B, const 
   if (crux_exec_recording(c)) return crux_fail(c, CRUX_EUNSUP, "%s: not recordable into a fused sequence", who);
   return CRUX_OK;
 }
-// crux_dense_forward for every member over ONE input matrix d_x [dims[0] x B]: L launches. Each member keeps its own workspace and cached activations.
-int32_t crux_dense_forward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, hipStream_t st) {
-  int32_t rc = dense_group_check(nets, M, B, "crux_dense_forward_group"); if (rc) return rc;
+// crux_dense_forward for every member, member m over its own input matrix d_x[m] [dims[0] x B] (the heads behind an ensemble's conv trunks, conv_group.hip): L launches.
+// Each member keeps its own workspace and cached activations. (the passes behind the checked entries below; the caller has run dense_group_check)
+static int32_t dense_forward_group_run(crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, hipStream_t st) {
+  int32_t rc;
   crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
   for (int m = 0; m < M; ++m) { rc = ensure_ws(nets[m], B); if (rc) return rc; }
   for (int l = 0; l < nd.L; ++l) {
     const int in = nd.dims[l], out = nd.dims[l + 1];
     GemmArgs q{}; q.sAi = 1; q.sAk = out; q.sBk = 1; q.sBj = in; q.M = out; q.N = (int)B; q.K = in; q.sCj = out; q.epi = EPI_FWD; q.act = nd.acts[l];
     GemmGroup t{};
-    for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = l == 0 ? d_x : crux_dense_act(n, l); t.C[m] = crux_dense_act(n, l + 1); t.bias[m] = n->p + nd.boff[l]; }
+    for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = l == 0 ? d_x[m] : crux_dense_act(n, l); t.C[m] = crux_dense_act(n, l + 1); t.bias[m] = n->p + nd.boff[l]; }
     rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc;
   }
   return CRUX_OK;
 }
-// crux_dense_backward(want_g, no input gradient) for every member after crux_dense_forward_group with the same d_x: member m's parameter gradient of d_dy[m] [out_L x B]
-// (not modified) lands in its own gradient vector. 2 L - 1 launches (+ 1 for an output activation).
-int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags) {
-  int32_t rc = dense_group_check(nets, M, B, "crux_dense_backward_group"); if (rc) return rc;
+int32_t crux_dense_forward_group_x(crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, hipStream_t st) {
+  int32_t rc = dense_group_check(nets, M, B, "crux_dense_forward_group_x"); return rc ? rc : dense_forward_group_run(nets, M, d_x, B, st);
+}
+// ... over ONE input matrix d_x [dims[0] x B] that all members read
+int32_t crux_dense_forward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, hipStream_t st) {
+  int32_t rc = dense_group_check(nets, M, B, "crux_dense_forward_group"); if (rc) return rc;
+  const float* xs[CRUX_GROUP_MAX]; for (int m = 0; m < CRUX_GROUP_MAX; ++m) xs[m] = d_x;
+  return dense_forward_group_run(nets, M, xs, B, st);
+}
+// crux_dense_backward(want_g) for every member after crux_dense_forward_group_x with the same d_x[m]: member m's parameter gradient of d_dy[m] [out_L x B] (not modified)
+// lands in its own gradient vector. 2 L - 1 launches (+ 1 for an output activation); with d_dx (or NULL) one more, layer 0's data GEMM formed the way crux_dense_backward
+// forms its d_dx (no act'), into d_dx[m] [dims[0] x B].
+static int32_t dense_backward_group_run(const char* who, crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags, float* const* d_dx) {
+  int32_t rc;
   crux_ctx* c = nets[0]->ctx; const NetDesc& nd = nets[0]->nd;
   const float* dcur[CRUX_GROUP_MAX]; float* dnxt[CRUX_GROUP_MAX]; float* dspare[CRUX_GROUP_MAX];
   for (int m = 0; m < M; ++m) {
-    if (!nets[m]->ws || nets[m]->ws_B < B) return crux_fail(c, CRUX_EINVAL, "crux_dense_backward_group: member %d has no cached forward pass for this batch", m);
-    if (!d_dy[m]) return crux_fail(c, CRUX_EINVAL, "crux_dense_backward_group: member %d has no output gradient", m);
+    if (!nets[m]->ws || nets[m]->ws_B < B) return crux_fail(c, CRUX_EINVAL, "%s: member %d has no cached forward pass for this batch", who, m);
+    if (!d_dy[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d has no output gradient", who, m);
     dcur[m] = d_dy[m]; dnxt[m] = ws_delta(nets[m], 0); dspare[m] = ws_delta(nets[m], 1);
   }
   if (nd.acts[nd.L - 1] != CRUX_ACT_IDENTITY) {
@@ -420,17 +433,28 @@ int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x
     const int in = nd.dims[l], out = nd.dims[l + 1];
     { GemmArgs q{}; q.sAi = 1; q.sAk = out; q.sBk = in; q.sBj = 1; q.M = out; q.N = in; q.K = (int)B; q.sCj = out; q.epi = EPI_WGRAD; q.scale = gscale; q.nf = nanflags;
       GemmGroup t{};
-      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = dcur[m]; t.B[m] = l == 0 ? d_x : crux_dense_act(n, l); t.C[m] = n->g + nd.woff[l]; t.gbias[m] = n->g + nd.boff[l]; }
+      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = dcur[m]; t.B[m] = l == 0 ? d_x[m] : crux_dense_act(n, l); t.C[m] = n->g + nd.woff[l]; t.gbias[m] = n->g + nd.boff[l]; }
       rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc; }
-    if (l > 0) {
-      GemmArgs q{}; q.sAi = out; q.sAk = 1; q.sBk = 1; q.sBj = out; q.M = in; q.N = (int)B; q.K = out; q.sCj = in; q.epi = EPI_BWD_DATA; q.act = nd.acts[l - 1];
+    if (l > 0 || d_dx) {
+      GemmArgs q{}; q.sAi = out; q.sAk = 1; q.sBk = 1; q.sBj = out; q.M = in; q.N = (int)B; q.K = out; q.sCj = in; q.epi = EPI_BWD_DATA; q.act = l > 0 ? nd.acts[l - 1] : CRUX_ACT_IDENTITY;
       GemmGroup t{};
-      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = dcur[m]; t.C[m] = dnxt[m]; t.ysrc[m] = crux_dense_act(n, l); }
+      for (int m = 0; m < M; ++m) { crux_mlp* n = nets[m]; t.A[m] = n->p + nd.woff[l]; t.B[m] = dcur[m]; t.C[m] = l > 0 ? dnxt[m] : d_dx[m]; t.ysrc[m] = l > 0 ? crux_dense_act(n, l) : nullptr; }
       rc = launch_gemm_group(c, q, t, M, st); if (rc) return rc;
       for (int m = 0; m < M; ++m) { dcur[m] = dnxt[m]; float* x = dnxt[m]; dnxt[m] = dspare[m]; dspare[m] = x; }
     }
   }
   return CRUX_OK;
+}
+int32_t crux_dense_backward_group_dx(crux_mlp* const* nets, int M, const float* const* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags, float* const* d_dx) {
+  const char* who = "crux_dense_backward_group_dx";
+  int32_t rc = dense_group_check(nets, M, B, who); return rc ? rc : dense_backward_group_run(who, nets, M, d_x, B, d_dy, gscale, st, nanflags, d_dx);
+}
+// ... after crux_dense_forward_group over the one d_x, no input gradient
+int32_t crux_dense_backward_group(crux_mlp* const* nets, int M, const float* d_x, int64_t B, const float* const* d_dy, float gscale, hipStream_t st, int32_t* nanflags) {
+  const char* who = "crux_dense_backward_group";
+  int32_t rc = dense_group_check(nets, M, B, who); if (rc) return rc;
+  const float* xs[CRUX_GROUP_MAX]; for (int m = 0; m < CRUX_GROUP_MAX; ++m) xs[m] = d_x;
+  return dense_backward_group_run(who, nets, M, xs, B, d_dy, gscale, st, nanflags, nullptr);
 }
 
 extern "C" {

@@ -314,3 +314,199 @@ int32_t crux_ensemble_forward_recording(crux_mlp* const* nets, int32_t M, int32_
 }
 
 }  // extern "C"
+
+// ---- members with a convolutional trunk: Chain([Scale,] Conv..., flatten, Dense...) per member, the trunks on conv_group.hip's grouped passes, the heads on the grouped dense
+// passes with one input (the member's features) and one input gradient per member. A step is: grouped trunk forward, grouped head forward, k_ens_head, grouped head backward
+// with d_dx, grouped trunk backward, Sumsq2Op per member over its trunk's and its head's gradient, the info row and the gated Adam on all 2 M handles in one launch behind ONE
+// gate (a NaN flag or a NaN partial anywhere: no handle changes, the status goes to CRUX_ENAN). grad_norm is over all members' trunk and head gradients (norm(grads) over
+// Flux.params of the ensemble), member_grad_norms per member over both of its handles.
+__global__ __launch_bounds__(256) void k_conv_ens_sumsq(const EnsGrads tg, int64_t nt, const EnsGrads hg, int64_t nh, double* __restrict__ ssq) {
+  const unsigned m = blockIdx.x / SUMSQ_BLOCKS;
+  Sumsq2Op::run(blockIdx.x - m * SUMSQ_BLOCKS, SUMSQ_BLOCKS, tg.g[m], nt, hg.g[m], nh, ssq + (size_t)m * ENS_SSQ_STRIDE, Sumsq2Fix{});
+}
+// k_ens_adam over two handles per member: grid M x (bpt + bph), a member's first bpt blocks update its trunk (nt values), the others its head (nh values)
+struct ConvEnsAdam { EnsAdam t, h; };
+__global__ __launch_bounds__(256) void k_conv_ens_adam(const ConvEnsAdam a, int M, const unsigned bpt, const unsigned bph, double eta, double b1, double b2, double eps, int64_t nt, int64_t nh,
+                                                       double* __restrict__ ssq, const double* __restrict__ hpart, double denom, const int32_t* __restrict__ nanflag, int32_t* __restrict__ status, float* __restrict__ row) {
+  const unsigned mem = blockIdx.x / (bpt + bph), bid = blockIdx.x - mem * (bpt + bph);
+  bool b_ = nanflag[0] != 0;
+  for (int k = (int)(threadIdx.x & 63); k < M * SUMSQ_BLOCKS; k += 64) b_ = b_ || isnan(ssq[(size_t)(k / SUMSQ_BLOCKS) * ENS_SSQ_STRIDE + 1 + (k % SUMSQ_BLOCKS)]);
+  const bool bad = __ballot(b_) != 0ull;
+  if (status[0] == CRUX_ENAN) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double lsum = 0, gsum = 0;
+    for (int m = 0; m < M; ++m) {
+      double* sq = ssq + (size_t)m * ENS_SSQ_STRIDE; ssq_finalize(sq);
+      double l = 0; for (int k = 0; k < ENS_HEAD_BLOCKS; ++k) l += hpart[m * ENS_HEAD_BLOCKS + k];
+      l /= denom; lsum += l; gsum += sq[0];
+      row[CRUX_INFO_N + m] = (float)l; row[CRUX_INFO_N + M + m] = (float)sqrt(sq[0]);
+    }
+    row[CRUX_INFO_LOSS] = (float)(lsum / (double)M); row[CRUX_INFO_GRAD_NORM] = nanflag[0] != 0 ? NAN : (float)sqrt(gsum);
+    if (bad) status[0] = CRUX_ENAN;
+  }
+  if (bad) return;
+  if (bid < bpt) adam_update(bid, bpt, a.t.p[mem], a.t.g[mem], a.t.m[mem], a.t.v[mem], a.t.bp[mem], eta, b1, b2, eps, nt, 1);
+  else adam_update(bid - bpt, bph, a.h.p[mem], a.h.g[mem], a.h.m[mem], a.h.v[mem], a.h.bp[mem], eta, b1, b2, eps, nh, 1);
+}
+
+// (passes_only: the test entry runs no head arithmetic and no Adam, and takes heads wider than 1024 -- the trunk grid's padded and Atari cases flatten to 1600 and 2048
+// features; dense_group_check still refuses DenseSN, mixed shapes, repeated handles and a recording)
+static int32_t conv_ens_check(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, int64_t B, bool train, const char* who, bool passes_only = false) {
+  if (!convs || !trunks || !heads || M < 1 || !convs[0] || !trunks[0] || !heads[0]) return CRUX_EINVAL;
+  crux_ctx* c = convs[0]->ctx;
+  if (M > CRUX_GROUP_MAX) return crux_fail(c, CRUX_EINVAL, "%s: %d members, at most %d", who, M, CRUX_GROUP_MAX);
+  for (int m = 0; m < M; ++m) {
+    if (!heads[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d has no head", who, m);
+    if (heads[m]->wide && !passes_only) return crux_fail(c, CRUX_EUNSUP, "%s: member %d's head has a dimension above 1024 (wide handles are outside the grouped passes and the grouped Adam)", who, m);
+    if (heads[m]->ctx != c) return crux_fail(c, CRUX_EINVAL, "%s: member %d's head belongs to another context", who, m);
+  }
+  int32_t rc = conv_group_check(who, convs, trunks, M, B); if (rc) return rc;
+  rc = passes_only ? dense_group_check(heads, M, B, who, true) : ens_check(heads, M, kind, B, train, who); if (rc) return rc;      // DenseSN, ClipValue, the heads' Adam, one shape, the batch range, no recording
+  if (heads[0]->nd.dims[0] != convs[0]->feat[convs[0]->L]) return crux_fail(c, CRUX_EINVAL, "%s: the heads take %d features, the trunks flatten to %lld", who, heads[0]->nd.dims[0], (long long)convs[0]->feat[convs[0]->L]);
+  if (train) for (int m = 0; m < M; ++m) {
+    const crux_mlp* n = trunks[m], *n0 = heads[0];
+    if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on member %d's trunk", m);
+    CRUX_NO_CLIP(who, n);
+    if (n->eta != n0->eta || n->b1 != n0->b1 || n->b2 != n0->b2 || n->eps != n0->eps) return crux_fail(c, CRUX_EINVAL, "%s: the Adam of member %d's trunk differs from the heads' (one optimiser covers the ensemble)", who, m);
+  }
+  return CRUX_OK;
+}
+static void conv_ens_feats(crux_conv* const* convs, int M, const float** f) { for (int m = 0; m < M; ++m) f[m] = conv_act(convs[m], convs[m]->L); }
+static size_t conv_ens_step_bytes(crux_conv* const* convs, const NetDesc& nd, int M, int64_t B) { return ens_step_bytes(nd, M, B) + Carve::span<float>((size_t)M * (size_t)convs[0]->feat[convs[0]->L] * (size_t)B); }
+// one training_loss step over B columns, enqueued only; dfeat [M][features x B]; row: where its info row goes (device)
+static int32_t conv_ens_enqueue_step(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int M, int32_t kind, const float* d_x, const float* d_y, const float* d_w, int64_t B,
+                                     const EnsStepBufs& sb, float* dfeat, float* row, const char* who) {
+  crux_ctx* c = convs[0]->ctx; const NetDesc& nd = heads[0]->nd; const int nout = nd.dims[nd.L], ny = ens_ny(kind, nd); const int64_t F = convs[0]->feat[convs[0]->L];
+  int32_t rc = conv_forward_group_ws(who, convs, trunks, M, d_x, B); if (rc) return rc;
+  const float* feats[CRUX_GROUP_MAX]; conv_ens_feats(convs, M, feats);
+  rc = crux_dense_forward_group_x(heads, M, feats, B, c->stream); if (rc) return rc;
+  hipLaunchKernelGGL(k_ens_head, dim3((unsigned)M * ENS_HEAD_BLOCKS), dim3(256), 0, c->stream, ens_outputs(heads, M), M, (int)kind, ny, B, d_y, kind == CRUX_ENS_GAUSS ? d_w : (const float*)nullptr,
+                     sb.dy, sb.hpart, sb.nanflag);
+  rc = crux_launch_check(c, "k_ens_head"); if (rc) return rc;
+  const float* dys[CRUX_GROUP_MAX]; float* dfs[CRUX_GROUP_MAX];
+  for (int m = 0; m < M; ++m) { dys[m] = sb.dy + (size_t)m * (size_t)nout * (size_t)B; dfs[m] = dfeat + (size_t)m * (size_t)F * (size_t)B; }
+  rc = crux_dense_backward_group_dx(heads, M, feats, B, dys, 1.0f, c->stream, nullptr, dfs); if (rc) return rc;
+  rc = conv_backward_group_ws(who, convs, trunks, M, d_x, B, dfs, 1.0f); if (rc) return rc;
+  EnsGrads tg{}, hg{}; ConvEnsAdam ta{};
+  for (int m = 0; m < M; ++m) { crux_mlp* t = trunks[m]; crux_mlp* h = heads[m]; tg.g[m] = t->g; hg.g[m] = h->g;
+    ta.t.p[m] = t->p; ta.t.g[m] = t->g; ta.t.m[m] = t->m; ta.t.v[m] = t->v; ta.t.bp[m] = t->bp; ta.h.p[m] = h->p; ta.h.g[m] = h->g; ta.h.m[m] = h->m; ta.h.v[m] = h->v; ta.h.bp[m] = h->bp; }
+  const int64_t nt = trunks[0]->nd.n_params, nh = nd.n_params;
+  hipLaunchKernelGGL(k_conv_ens_sumsq, dim3((unsigned)M * SUMSQ_BLOCKS), dim3(256), 0, c->stream, tg, nt, hg, nh, sb.ssq);
+  rc = crux_launch_check(c, "k_conv_ens_sumsq"); if (rc) return rc;
+  const unsigned bpt = nblk(nt), bph = nblk(nh); const crux_mlp* n0 = heads[0];
+  hipLaunchKernelGGL(k_conv_ens_adam, dim3((bpt + bph) * (unsigned)M), dim3(256), 0, c->stream, ta, M, bpt, bph, n0->eta, n0->b1, n0->b2, n0->eps, nt, nh, sb.ssq, (const double*)sb.hpart,
+                     kind == CRUX_ENS_GAUSS ? (double)ny * (double)B : (double)B, (const int32_t*)sb.nanflag, sb.status, row);
+  return crux_launch_check(c, "k_conv_ens_adam");
+}
+static int32_t conv_ens_enqueue_forward(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int M, int32_t kind, const float* d_x, int64_t B, float* d_mu, float* d_var, float* d_mean, float* d_evar, const char* who) {
+  crux_ctx* c = convs[0]->ctx; const NetDesc& nd = heads[0]->nd; const int ny = ens_ny(kind, nd);
+  int32_t rc = conv_forward_group_ws(who, convs, trunks, M, d_x, B); if (rc) return rc;
+  const float* feats[CRUX_GROUP_MAX]; conv_ens_feats(convs, M, feats);
+  rc = crux_dense_forward_group_x(heads, M, feats, B, c->stream); if (rc) return rc;
+  const int64_t threads = kind == CRUX_ENS_GAUSS ? (int64_t)ny * B : B;
+  hipLaunchKernelGGL(k_ens_combine, dim3(nblk(threads)), dim3(256), 0, c->stream, ens_outputs(heads, M), M, (int)kind, ny, B, d_mu, d_var, d_mean, d_evar);
+  return crux_launch_check(c, "k_ens_combine");
+}
+
+extern "C" {
+
+int32_t crux_conv_ensemble_forward(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, int64_t B, float* d_mu, float* d_var, float* d_mean, float* d_evar) {
+  const char* who = "crux_conv_ensemble_forward";
+  int32_t rc = conv_ens_check(convs, trunks, heads, M, kind, B, false, who); if (rc) return rc;
+  if (!d_x || !d_mean || (kind == CRUX_ENS_GAUSS && !d_evar)) return crux_fail(convs[0]->ctx, CRUX_EINVAL, "%s: NULL input or mixture output", who);
+  return conv_ens_enqueue_forward(convs, trunks, heads, M, kind, d_x, B, d_mu, d_var, d_mean, d_evar, who);
+}
+
+int32_t crux_conv_ensemble_logpdf(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, const float* d_y, int64_t B, float* d_out) {
+  const char* who = "crux_conv_ensemble_logpdf";
+  int32_t rc = conv_ens_check(convs, trunks, heads, M, kind, B, false, who); if (rc) return rc;
+  crux_ctx* c = convs[0]->ctx; const int ny = ens_ny(kind, heads[0]->nd);
+  if (!d_x || !d_y || !d_out) return crux_fail(c, CRUX_EINVAL, "%s: NULL argument", who);
+  const size_t n = (size_t)ny * (size_t)B;
+  Carve cv{(char*)crux_scratch(c, 2 * Carve::span<float>(n)), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch", who);
+  float* mean = cv.take<float>(n); float* evar = cv.take<float>(n);
+  rc = conv_ens_enqueue_forward(convs, trunks, heads, M, kind, d_x, B, nullptr, nullptr, mean, evar, who); if (rc) return rc;
+  hipLaunchKernelGGL(k_ens_logpdf, dim3(nblk(kind == CRUX_ENS_GAUSS ? (int64_t)n : B)), dim3(256), 0, c->stream, (int)kind, ny, B, (const float*)mean, (const float*)evar, d_y, d_out);
+  return crux_launch_check(c, "k_ens_logpdf");
+}
+
+int32_t crux_conv_ensemble_step(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, const float* d_y, const float* d_w, int64_t B, float* info_out) {
+  const char* who = "training_loss (conv ensemble)";
+  int32_t rc = conv_ens_check(convs, trunks, heads, M, kind, B, true, "crux_conv_ensemble_step"); if (rc) return rc;
+  crux_ctx* c = convs[0]->ctx; const NetDesc& nd = heads[0]->nd;
+  if (!d_x || !d_y) return crux_fail(c, CRUX_EINVAL, "crux_conv_ensemble_step: NULL x or y");
+  ChainHead head{(size_t)CRUX_INFO_N + 2 * (size_t)M};
+  const size_t bytes = conv_ens_step_bytes(convs, nd, M, B) + head.bytes(1) + 256;
+  Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
+  EnsStepBufs sb{}; ens_step_carve(cv, nd, M, B, sb); float* dfeat = cv.take<float>((size_t)M * (size_t)convs[0]->feat[convs[0]->L] * (size_t)B);
+  head.carve(cv, 1); sb.nanflag = head.more<int32_t>(cv, 1); sb.status = head.status;
+  rc = head.zero(c); if (rc) return rc;
+  rc = conv_ens_enqueue_step(convs, trunks, heads, M, kind, d_x, d_y, d_w, B, sb, dfeat, head.rows, who); if (rc) return rc;
+  int32_t st; const char* h;
+  rc = head.fetch(c, head.run_bytes(1), who, &st, &h); if (rc) return rc;
+  if (info_out) memcpy(info_out, h + 256, sizeof(float) * head.stride);
+  if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s", who);
+  return CRUX_OK;
+}
+
+int32_t crux_conv_ensemble_train(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_X, const float* d_Y, const float* d_W, int64_t N,
+                                 int32_t batch_size, int32_t epochs, int32_t max_batches, const int64_t* perms, float* info_out, float* epoch_rows) {
+  const char* who = "batch_train! (conv ensemble)";
+  if (batch_size < 1) { if (convs && M >= 1 && convs[0]) return crux_fail(convs[0]->ctx, CRUX_EINVAL, "crux_conv_ensemble_train: batch_size %d", batch_size); return CRUX_EINVAL; }
+  const int64_t bs = batch_size < N ? batch_size : N;
+  int32_t rc = conv_ens_check(convs, trunks, heads, M, kind, bs > 0 ? bs : 1, true, "crux_conv_ensemble_train"); if (rc) return rc;
+  crux_ctx* c = convs[0]->ctx; const NetDesc& nd = heads[0]->nd; const int64_t nx = convs[0]->in_features; const int ny = ens_ny(kind, nd);
+  if (!d_X || !d_Y || !perms) return crux_fail(c, CRUX_EINVAL, "crux_conv_ensemble_train: NULL X, Y or permutations");
+  if (N < 1 || N > ((int64_t)1 << 31) || epochs < 1 || epochs > 4096) return crux_fail(c, CRUX_EINVAL, "crux_conv_ensemble_train: N %lld or epochs %d out of range", (long long)N, epochs);
+  if (nx > 0x7fffffffll / bs) return crux_fail(c, CRUX_EINVAL, "crux_conv_ensemble_train: a minibatch of %lld images of %lld features is out of range", (long long)bs, (long long)nx);
+  for (int64_t i = 0; i < (int64_t)epochs * N; ++i) if (perms[i] < 0 || perms[i] >= N) return crux_fail(c, CRUX_EINVAL, "crux_conv_ensemble_train: permutation entry %lld is %lld, outside 0..N-1", (long long)i, (long long)perms[i]);
+  const bool weighted = kind == CRUX_ENS_GAUSS && d_W;
+  ChainHead head{(size_t)CRUX_INFO_N + 2 * (size_t)M};
+  const size_t np = (size_t)epochs * (size_t)N;
+  const size_t bytes = Carve::span<int64_t>(np) + Carve::span<float>((size_t)nx * bs) + 2 * Carve::span<float>((size_t)ny * bs) + conv_ens_step_bytes(convs, nd, M, bs) + head.bytes(epochs) + 256;
+  Carve cv{(char*)crux_scratch(c, bytes), 0}; if (!cv.p) return crux_fail(c, CRUX_ENOMEM, "%s: scratch (%zu bytes)", who, bytes);
+  int64_t* d_perm = cv.take<int64_t>(np); float* xs = cv.take<float>((size_t)nx * bs); float* ys = cv.take<float>((size_t)ny * bs); float* ws = cv.take<float>((size_t)ny * bs);
+  EnsStepBufs sb{}; ens_step_carve(cv, nd, M, bs, sb); float* dfeat = cv.take<float>((size_t)M * (size_t)convs[0]->feat[convs[0]->L] * (size_t)bs);
+  head.carve(cv, epochs); sb.nanflag = head.more<int32_t>(cv, 1); sb.status = head.status;
+  rc = head.zero(c); if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(d_perm, perms, sizeof(int64_t) * np, hipMemcpyHostToDevice, c->stream));
+  const int64_t nparts = (N + bs - 1) / bs;
+  int64_t total = 0; int epochs_run = 0;
+  rc = chain_epochs(epochs, nparts, max_batches,
+    [&](int) { return (int32_t)CRUX_OK; },
+    [&](int ep, int64_t q) {
+      const int64_t off = q * bs, n = off + bs <= N ? bs : N - off;
+      const int64_t elems = n * (nx + ny + (weighted ? ny : 0));
+      hipLaunchKernelGGL(k_ens_gather, dim3(nblk(elems)), dim3(256), 0, c->stream, d_X, d_Y, weighted ? d_W : (const float*)nullptr, (const int64_t*)(d_perm + (size_t)ep * (size_t)N + off), (int)nx, ny, n, xs, ys, ws);
+      int32_t r = crux_launch_check(c, "k_ens_gather"); if (r) return r;
+      return conv_ens_enqueue_step(convs, trunks, heads, M, kind, xs, ys, weighted ? ws : (const float*)nullptr, n, sb, dfeat, head.rows + (size_t)ep * head.stride, who);
+    }, &total, &epochs_run);
+  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+  int32_t st; const char* h;
+  rc = head.fetch(c, head.run_bytes(epochs_run), who, &st, &h); if (rc) return rc;
+  const float* hr = (const float*)(h + 256);
+  const int last = chain_report(st, hr, head.stride, epochs_run, total, true, info_out, epoch_rows);
+  if (info_out) memcpy(info_out + CRUX_INFO_N, hr + (size_t)last * head.stride + CRUX_INFO_N, sizeof(float) * 2 * (size_t)M);
+  if (st == CRUX_ENAN) return crux_fail(c, CRUX_ENAN, "NaN detected! (grad norm is NaN, src/training.jl:20) in %s, epoch %d", who, last + 1);
+  return CRUX_OK;
+}
+
+// test entry: the grouped passes alone. Trunks and heads forward over d_x, member m's head output copied to d_out[m] [out x B]; then the pullback of d_dy[m] (grad_scale 1)
+// through head m -- its input gradient into d_dfeat[m] [features x B] -- and through trunk m: what tests compare bit for bit with crux_conv_forward_cached /
+// crux_mlp_forward_cached / crux_mlp_backward / crux_conv_backward per member. d_dy, d_out, d_dfeat: HOST arrays of M device pointers
+int32_t crux_conv_ensemble_passes(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, const float* d_x, int64_t B, const float* const* d_dy, float* const* d_out, float* const* d_dfeat) {
+  const char* who = "crux_conv_ensemble_passes";
+  if (!d_x || !d_dy || !d_out || !d_dfeat) return CRUX_EINVAL;
+  int32_t rc = conv_ens_check(convs, trunks, heads, M, CRUX_ENS_CLASS, B, false, who, true); if (rc) return rc;
+  crux_ctx* c = convs[0]->ctx; const NetDesc& nd = heads[0]->nd;
+  for (int m = 0; m < M; ++m) if (!d_dy[m] || !d_dfeat[m]) return crux_fail(c, CRUX_EINVAL, "%s: member %d has no output gradient or no feature-gradient buffer", who, m);
+  rc = conv_forward_group_ws(who, convs, trunks, M, d_x, B); if (rc) return rc;
+  const float* feats[CRUX_GROUP_MAX]; conv_ens_feats(convs, M, feats);
+  rc = dense_forward_group_run(heads, M, feats, B, c->stream); if (rc) return rc;      // unchecked: conv_ens_check has run dense_group_check with wide heads allowed
+  for (int m = 0; m < M; ++m) if (d_out[m]) HIPCHK(c, hipMemcpyAsync(d_out[m], crux_dense_act(heads[m], nd.L), sizeof(float) * (size_t)nd.dims[nd.L] * (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+  rc = dense_backward_group_run(who, heads, M, feats, B, d_dy, 1.0f, c->stream, nullptr, d_dfeat); if (rc) return rc;
+  const float* dfs[CRUX_GROUP_MAX]; for (int m = 0; m < M; ++m) dfs[m] = d_dfeat[m];
+  return conv_backward_group_ws(who, convs, trunks, M, d_x, B, dfs, 1.0f);
+}
+
+}  // extern "C"

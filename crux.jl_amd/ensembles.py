@@ -1,7 +1,11 @@
 """ensembles.py -- DeepEnsemble and DeepClassificationEnsemble (src/extras/deep_ensembles.jl) over the member-grouped dense passes (csrc/ensemble.hip).
 
+A generator may also return a conv chain, Chain([Scale,] Conv..., flatten, Dense..., input=(W, H, C)) (conv.py): the members are then conv ContinuousNetworks whose trunks run
+on the member-grouped conv passes (csrc/conv_group.hip) and whose heads on the grouped dense passes; x is (W, H, C, B) or (W H C, B).
+
 Arrays are (features, batch) as everywhere in core.py. Everything numerical runs on the device; what the device path does not cover raises NotImplementedError
-naming the reason (DenseSN layers, members of different shapes, more than 16 members) -- there is no host fallback."""
+naming the reason (DenseSN layers, members of different shapes or conv tables, conv and MLP members mixed, a conv member's head wider than 1024, more than 16
+members) -- there is no host fallback."""
 import ctypes as C
 
 import numpy as np
@@ -49,18 +53,36 @@ class _Ensemble:
         for ch in chains:
             if not isinstance(ch, Chain):
                 raise TypeError("%s: generator() must return a Chain" % type(self).__name__)
+        convs = [getattr(ch, "conv", None) for ch in chains]
+        self.conv = convs[0] if all(c is not None for c in convs) else None
+        if self.conv is None and any(c is not None for c in convs):
+            raise NotImplementedError("%s: conv and MLP members mixed (the grouped device passes need one shape)" % type(self).__name__)
+        for ch in chains:
             if any(isinstance(l, DenseSN) for l in ch.layers):
                 raise NotImplementedError("%s: DenseSN layers (the grouped device passes read the raw weights)" % type(self).__name__)
             if ch.dims != chains[0].dims or ch.acts != chains[0].acts:
                 raise NotImplementedError("%s: members of different shapes (the grouped device passes need one shape)" % type(self).__name__)
         if self.kind == "gauss" and chains[0].dims[-1] % 2:
             raise ValueError("DeepEnsemble: the output width %d is odd (mean and variance halves)" % chains[0].dims[-1])
-        if any(getattr(ch, "conv", None) is not None for ch in chains):
-            raise NotImplementedError("%s: members with a convolutional trunk (Conv layers in their Chain) are not implemented" % type(self).__name__)
-        self.models = [ContinuousNetwork(ch, ctx=self.ctx, seed=seed, stream=m) for m, ch in enumerate(chains)]      # independent Glorot streams
+        if self.conv is not None:
+            key = lambda c: (c.W, c.H, c.C, c.scale, [(l.k, l.cin, l.cout, l.act, l.stride, l.pad) for l in c.convs])      # noqa: E731
+            for m, c in enumerate(convs):
+                if key(c) != key(self.conv):
+                    raise NotImplementedError("%s: member %d's conv table differs from member 0's (the grouped conv passes need one layer table)" % (type(self).__name__, m))
+            if max(chains[0].dims) > 1024:
+                raise NotImplementedError("%s: a wide head (a dimension above 1024: %r) behind the conv trunk is outside the grouped dense passes and the grouped Adam" % (type(self).__name__, chains[0].dims))
+        self.models = [ContinuousNetwork(ch, ctx=self.ctx, seed=seed, stream=m) for m, ch in enumerate(chains)]      # independent Glorot streams (trunk and head)
         self.dims = chains[0].dims
+        self.nx = self.conv.in_features if self.conv is not None else self.dims[0]      # rows of x
         self.optimizer = None
-        self._nets = (C.c_void_p * N)(*[m.h.value for m in self.models])
+        arr = lambda hs: (C.c_void_p * N)(*[h.value for h in hs])      # noqa: E731
+        if self.conv is not None:      # a member is (crux_conv, the trunk's parameter handle, the head): the crux_conv_ensemble_* entries
+            self._nets = (arr([m.trunk.h for m in self.models]), arr([m.trunk.p.h for m in self.models]), arr([m.head_h for m in self.models]))
+        else:
+            self._nets = (arr([m.h for m in self.models]),)
+
+    def _entry(self, name):
+        return getattr(self.ctx.lib, ("crux_conv_ensemble_" if self.conv is not None else "crux_ensemble_") + name)
 
     # ---- shapes -------------------------------------------------------------------------------------------------------------------------------------------------
     @property
@@ -74,9 +96,11 @@ class _Ensemble:
 
     def _x(self, x):
         x = np.asarray(x, np.float32)
-        x = x.reshape(self.dims[0], 1) if x.ndim == 1 else x
-        if x.shape[0] != self.dims[0]:
-            raise ValueError("input has %d rows, the members expect %d" % (x.shape[0], self.dims[0]))
+        if self.conv is not None and x.ndim in (3, 4) and x.shape[:3] == (self.conv.W, self.conv.H, self.conv.C):      # (W, H, C[, B]) images: WHCN column-major
+            x = x.reshape((self.nx, -1), order="F")
+        x = x.reshape(self.nx, 1) if x.ndim == 1 else x
+        if x.ndim != 2 or x.shape[0] != self.nx:
+            raise ValueError("input has shape %s, the members expect %d rows%s" % (x.shape, self.nx, " or (W, H, C, B) images" if self.conv is not None else ""))
         return x
 
     def _y(self, y, B, what="y"):
@@ -92,7 +116,7 @@ class _Ensemble:
         with _DeviceArrays(self.ctx) as d:
             dx, dmean, devar = d.up(x), d.empty(n), d.empty(n)
             dmu, dvar = (d.empty(M * n), d.empty(M * n)) if members else (None, None)
-            self.ctx.check(lib.crux_ensemble_forward(self._nets, M, k, dx, B, dmu, dvar, dmean, devar))
+            self.ctx.check(self._entry("forward")(*self._nets, M, k, dx, B, dmu, dvar, dmean, devar))
             mean = d.down(dmean, (self.ny, B)); evar = d.down(devar, (self.ny, B)) if self.kind == "gauss" else None
             mus = vars_ = None
             if members:
@@ -105,7 +129,7 @@ class _Ensemble:
         x = self._x(x); B = x.shape[1]; y = self._y(y, B); rows = self.ny if self.kind == "gauss" else 1
         with _DeviceArrays(self.ctx) as d:
             dx, dy, do = d.up(x), d.up(y), d.empty(rows * B)
-            self.ctx.check(self.ctx.lib.crux_ensemble_logpdf(self._nets, self.M, L.ENS[self.kind], dx, dy, B, do))
+            self.ctx.check(self._entry("logpdf")(*self._nets, self.M, L.ENS[self.kind], dx, dy, B, do))
             return d.down(do, (rows, B))
 
     # ---- training -----------------------------------------------------------------------------------------------------------------------------------------------
@@ -129,7 +153,7 @@ class _Ensemble:
         raw = np.zeros(L.INFO_N + 2 * self.M, np.float32)
         with _DeviceArrays(self.ctx) as d:
             dx, dy, dw = d.up(x), d.up(y), (d.up(w) if w is not None else None)
-            self.ctx.check(self.ctx.lib.crux_ensemble_step(self._nets, self.M, L.ENS[self.kind], dx, dy, dw, B, _vp(raw)))
+            self.ctx.check(self._entry("step")(*self._nets, self.M, L.ENS[self.kind], dx, dy, dw, B, _vp(raw)))
         return self._info(raw)
 
     def fit(self, X, Y, batch_size=128, epochs=1, weights=None, seed=0, max_batches=None):
@@ -144,10 +168,11 @@ class _Ensemble:
 
     def fit_with_permutations(self, X, Y, W, batch_size, perms, max_batches=None):
         perms = np.ascontiguousarray(perms, np.int64); epochs, N = perms.shape; stride = L.INFO_N + 2 * self.M
+        X = self._x(X)
         raw, rows = np.zeros(stride, np.float32), np.zeros((epochs, stride), np.float32)
         with _DeviceArrays(self.ctx) as d:
             dX, dY, dW = d.up(X), d.up(Y), (d.up(W) if W is not None else None)
-            self.ctx.check(self.ctx.lib.crux_ensemble_train(self._nets, self.M, L.ENS[self.kind], dX, dY, dW, N, int(batch_size), epochs, int(max_batches or 0), _vp(perms), _vp(raw), _vp(rows)))
+            self.ctx.check(self._entry("train")(*self._nets, self.M, L.ENS[self.kind], dX, dY, dW, N, int(batch_size), epochs, int(max_batches or 0), _vp(perms), _vp(raw), _vp(rows)))
         out = self._info(raw); n_run = int(raw[L.INFO["epochs_run"]])
         out.update(batches_trained=int(raw[L.INFO["batches_trained"]]), epochs_run=n_run, epochs=[self._info(r) for r in rows[:n_run]])
         return out

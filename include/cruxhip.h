@@ -1090,6 +1090,32 @@ int32_t crux_conv_backward_pair(crux_conv* conv0, crux_mlp* params0, crux_conv* 
 int32_t crux_conv_pg_step(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp* actor_head, crux_conv* critic_conv, crux_mlp* critic_trunk, crux_mlp* critic_head,
                           const float* d_s, const uint8_t* d_a, const float* d_adv, const float* d_ret, const float* d_old_logprob, int64_t B,
                           int32_t loss, float eps_clip, float lambda_p, float lambda_e, float* info_out, float* critic_out);
+/* DeepEnsemble / DeepClassificationEnsemble whose members are conv chains (src/extras/deep_ensembles.jl:3, :41: generator() may return any Flux chain; here
+ * Chain([x -> c x,] Conv..., flatten, Dense...)): the counterparts of crux_ensemble_forward / _logpdf / _step / _train / _passes. Member m is convs[m] (its layer table and
+ * workspace), trunks[m] (its bare-vector parameter handle) and heads[m] (the dense layers behind flatten); M in 1..16. d_x is [W H C x B]; kinds, outputs, the info row
+ * [CRUX_INFO_N + 2 M], the gather by permutation (a row of d_X has W H C features), the short last minibatch and max_batches are crux_ensemble_*'s. Every conv layer of all
+ * members is ONE launch per pass (csrc/conv_group.hip): layer 0 forms each image tile's patch operand once per group of up to four members (forward and weight gradient),
+ * later layers and the data gradient take the member as a grid index; the heads run on the grouped dense passes with one input and one input gradient per member. Each
+ * member's outputs and gradients are bit-identical to crux_conv_forward_cached / crux_mlp_forward_cached / crux_mlp_backward / crux_conv_backward on that member alone.
+ * A step ends in one gradient norm per member over its trunk's and its head's gradient (member_grad_norms), GRAD_NORM over all members' (norm(grads) over Flux.params of
+ * the ensemble, training.jl:16-21), and Adam on all 2 M handles (crux_adam_init on each first) behind ONE gate: a NaN in o, y or w or a NaN norm leaves every handle
+ * untouched and returns CRUX_ENAN. No float atomics: two identical calls give identical bits.
+ * Refused by name before anything is enqueued: CRUX_EUNSUP for a head with a dimension above 1024 (crux_mlp_create_wide), DenseSN layers, a ClipValue prelude on any
+ * handle, a call while the fused executor records; CRUX_EINVAL for a member whose layer table, input extent or input scale differs from member 0's (the message names the
+ * member), repeated or NULL handles, handles of another context, heads of different widths or not as wide as flatten's output, and for step / train Adam
+ * hyper-parameters that differ between members or between a member's two handles.
+ * passes (test entry): forward of trunks and heads over d_x, member m's head output copied to d_out[m] [out x B] (or NULL), then the pullback of d_dy[m] (grad_scale 1)
+ * through head m, whose input gradient goes to d_dfeat[m] [features x B], and through trunk m; d_dy, d_out and d_dfeat are HOST arrays of M device pointers. It runs
+ * no head arithmetic and no Adam, and alone among these entries takes heads wider than 1024.                                                                       */
+int32_t crux_conv_ensemble_forward(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, int64_t B,
+                                   float* d_mu, float* d_var, float* d_mean, float* d_evar);
+int32_t crux_conv_ensemble_logpdf(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, const float* d_y, int64_t B, float* d_out);
+int32_t crux_conv_ensemble_step(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_x, const float* d_y, const float* d_w,
+                                int64_t B, float* info_out);
+int32_t crux_conv_ensemble_train(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, int32_t kind, const float* d_X, const float* d_Y, const float* d_W, int64_t N,
+                                 int32_t batch_size, int32_t epochs, int32_t max_batches, const int64_t* perms, float* info_out, float* epoch_rows);
+int32_t crux_conv_ensemble_passes(crux_conv* const* convs, crux_mlp* const* trunks, crux_mlp* const* heads, int32_t M, const float* d_x, int64_t B, const float* const* d_dy,
+                                  float* const* d_out, float* const* d_dfeat);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,14 @@ whole step minus the four passes (derived, and says so). Writes profiles/conv_at
 
 --pg: an actor's and a critic's Atari trunk over one batch (csrc/conv_pair.hip) -- forward + backward paired beside two single passes of the same build, and the whole
 crux_conv_pg_step (ppo_loss + critic mse, 2048-256-6 and 2048-256-1 heads) beside two single-trunk steps and beside the same step in torch-ROCm eager; B = 32 and 128.
-Writes profiles/conv_pg_bench.txt with --save."""
+Writes profiles/conv_pg_bench.txt with --save.
+
+--ensemble: M = 5 and 16 conv members over one batch (csrc/conv_group.hip, the conv entries of csrc/ensemble.hip), B = 32 and 128, at 16x16x2 -> 8@(4,4)/2 -> 12@(3,3)/1 with a
+300-64-10 head and at the Atari trunk with a 2048-1024-10 head. The grouped passes (crux_conv_ensemble_passes: trunks and heads, forward + backward) beside the same passes member
+by member (crux_conv_forward_cached, crux_mlp_forward_cached, crux_mlp_backward with d_dx, crux_conv_backward); and, at the small shape, the whole crux_conv_ensemble_step beside
+those passes plus crux_adam_apply per handle (the baseline has no entry for the loss head, the norms or the gate: it does less; it pays one device-to-device copy of the
+features per member, because crux_mlp_forward_cached reads them from a caller's buffer: both are said in the output lines). The Atari head is a wide handle, which the step
+refuses, so the Atari step is not measured. Writes profiles/conv_ensemble_bench.txt with --save."""
 import argparse
 import ctypes as C
 import json
@@ -226,9 +233,53 @@ def pg(a, crux, L):
         open(os.path.join(ROOT, "profiles", "conv_pg_bench.txt"), "w").write(txt)
 
 
+def ensemble(a, crux, L):
+    ctx = crux.default_context(); rng = np.random.default_rng(0); lines = []; vp = lambda v: v.ctypes.data_as(C.c_void_p); f = lambda t: "%.1f us (%.1f .. %.1f)" % t      # noqa: E731
+    arr = lambda hs: (C.c_void_p * len(hs))(*[getattr(h, "value", h) for h in hs])      # noqa: E731
+    small = lambda: crux.Chain(crux.Conv((4, 4), 2, 8, "relu", stride=2), crux.Conv((3, 3), 8, 12, "tanh"), crux.flatten, crux.Dense(300, 64, "relu"), crux.Dense(64, 10), input=(16, 16, 2))      # noqa: E731
+    atari = lambda: crux.Chain(crux.Scale(1.0 / 255.0), crux.Conv((8, 8), 4, 16, "relu", stride=4), crux.Conv((4, 4), 16, 32, "relu", stride=2), crux.flatten, crux.Dense(2048, 1024, "relu"),      # noqa: E731
+                               crux.Dense(1024, 10), input=(80, 80, 4))
+    for name, gen, nx, F, step_ok in (("16x16x2 -> 8@4/2 -> 12@3/1, head 300-64-10", small, 512, 300, True), ("Atari trunk, head 2048-1024-10", atari, 25600, 2048, False)):
+        for M in (5, 16):
+            nets = [crux.ContinuousNetwork(gen(), seed=1, stream=m, ctx=ctx) for m in range(M)]
+            for q in nets:
+                q.attach_optimizer(crux.Adam(np.float32(1e-3)))
+            hs = (arr([q.trunk.h for q in nets]), arr([q.trunk.p.h for q in nets]), arr([q.head_h for q in nets]))
+            for B in (32, 128):
+                host = [rng.integers(0, 2, (nx, B)).astype(np.float32), np.asfortranarray(np.eye(10, dtype=np.float32)[:, rng.integers(0, 10, B)]), np.full((10, B), 0.01, np.float32)]
+                d_x, d_y, d_dy = [ctx.alloc(v.nbytes) for v in host]
+                for p, v in zip((d_x, d_y, d_dy), host):
+                    ctx.h2d(p, v)
+                d_f, d_df = [ctx.alloc(4 * F * B) for _ in range(M)], [ctx.alloc(4 * F * B) for _ in range(M)]; raw = np.zeros(L.INFO_N + 2 * M, np.float32)
+                nul, dys, dfs = arr([None] * M), arr([d_dy] * M), arr(d_df)
+                grouped = lambda: ctx.check(ctx.lib.crux_conv_ensemble_passes(*hs, M, d_x, B, dys, nul, dfs))      # noqa: E731
+
+                def single(adam=False):
+                    for q, pf, pd in zip(nets, d_f, d_df):
+                        t = q.trunk
+                        ctx.check(ctx.lib.crux_conv_forward_cached(t.h, t.p.h, d_x, B, pf)); ctx.check(ctx.lib.crux_mlp_forward_cached(q.head_h, pf, B, None))
+                        ctx.check(ctx.lib.crux_mlp_backward(q.head_h, pf, B, d_dy, 1.0, 1, pd)); ctx.check(ctx.lib.crux_conv_backward(t.h, t.p.h, d_x, B, pd, 1.0, 1, None))
+                        if adam:
+                            ctx.check(ctx.lib.crux_adam_apply(t.p.h, 1.0)); ctx.check(ctx.lib.crux_adam_apply(q.head_h, 1.0))
+                g, o = median_window(grouped, ctx.sync, a.n, a.reps), median_window(single, ctx.sync, a.n, a.reps)
+                lines.append("%s, M %2d, B %3d: passes grouped %s, member by member (with a device copy of each member's features, which the head's entry reads from a caller's buffer) %s, ratio %.2f" % (name, M, B, f(g), f(o), o[0] / g[0]))
+                if step_ok:
+                    step = lambda: ctx.check(ctx.lib.crux_conv_ensemble_step(*hs, M, L.ENS["class"], d_x, d_y, None, B, vp(raw)))      # noqa: E731
+                    g, o = median_window(step, ctx.sync, a.n, a.reps), median_window(lambda: single(True), ctx.sync, a.n, a.reps)
+                    lines.append("%s, M %2d, B %3d: crux_conv_ensemble_step %s, member-by-member passes + crux_adam_apply per handle (no loss head, norms or gate) %s, ratio %.2f" % (name, M, B, f(g), f(o), o[0] / g[0]))
+                else:
+                    lines.append("%s, M %2d, B %3d: crux_conv_ensemble_step not measured (a 2048-wide head is a wide handle, which the step refuses)" % (name, M, B))
+                for p in [d_x, d_y, d_dy] + d_f + d_df:
+                    ctx.free(p)
+    txt = "# tools/conv_bench.py --ensemble: one MI355X, f32, median of %d windows of %d calls (min .. max), host clock around synchronised windows\n" % (a.reps, a.n) + "\n".join(lines) + "\n"
+    print(txt)
+    if a.save:
+        open(os.path.join(ROOT, "profiles", "conv_ensemble_bench.txt"), "w").write(txt)
+
+
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=200); ap.add_argument("--reps", type=int, default=7); ap.add_argument("--save", action="store_true")
-    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true")
+    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--ensemble", action="store_true")
     a = ap.parse_args()
     if a.torch_child:
         return torch_child(a)
@@ -239,6 +290,8 @@ def main():
         return atari(a, crux, L)
     if a.pg:
         return pg(a, crux, L)
+    if a.ensemble:
+        return ensemble(a, crux, L)
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
     for B in (32, 128):
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
