@@ -8,8 +8,10 @@ no handle of the whole network, and code that reads one would run the head over 
 images (a flattened observation has index w + W (h + H c)), (k1, k2, cin, cout) weights, a true (flipped) convolution, flatten in WHC order.
 
 What takes a conv policy: value / forward, the parameter and optimiser accessors (trunk first, then head: Flux.params order), polyak_average_, copyto_, clone_policy,
-policy_explore on the host seam (a HostMDP: pixel environments live on the host), DQN through solve, and PPO / A2C / REINFORCE for a conv DiscreteNetwork actor (with a conv
-ContinuousNetwork critic in an ActorCritic: on_policy._conv_policy_gradient_training over csrc/conv_pair.hip). Everything else refuses it by name (core.refuse_conv)."""
+policy_explore on the host seam (a HostMDP: pixel environments live on the host), DQN through solve, and PPO / A2C / REINFORCE for a conv DiscreteNetwork actor or a conv
+GaussianPolicy actor with a constant logSigma (with a conv ContinuousNetwork critic in an ActorCritic: on_policy._conv_policy_gradient_training over csrc/conv_pair.hip and,
+for the Gaussian actor, csrc/conv_gauss.hip; its action / logpdf / entropy take host observations). Everything else refuses it by name (core.refuse_conv); a
+SquashedGaussianPolicy or a two-headed GaussianPolicy over a conv chain is refused where it is built."""
 import ctypes as C
 
 import numpy as np
@@ -176,9 +178,17 @@ class ConvTrunk:
                 ctx.free(d)
         return y
 
-    def explore_tail(self, nout):
+    def explore_tail(self, nout, log_sigma=None):
         """Dense(n_out, n_out) with the identity matrix and no bias: crux_policy_explore over the head's OUTPUT. The exploration kernels take inputs up to 32 wide, a
-        flattened feature map is wider; their draws and head arithmetic depend on the network's output alone, and this layer hands the values on exactly (1 q + 0 ...)."""
+        flattened feature map is wider; their draws and head arithmetic depend on the network's output alone, and this layer hands the values on exactly (1 q + 0 ...).
+        log_sigma (a conv GaussianPolicy's current extras): the tail is a GaussianPolicy handle that carries them, so the Gaussian head draws a = mu + sigma eps and forms
+        logprob as for an MLP actor with these outputs; the vector is written on every call, it trains."""
+        if log_sigma is not None:
+            from .core import Chain, GaussianPolicy
+            if getattr(self, "_gtail", None) is None or self._gtail.network.dims[0] != nout:
+                self._gtail = GaussianPolicy(Chain(Dense(nout, nout)), np.zeros(nout, np.float32), ctx=self.ctx)
+            self._gtail.set_params(np.concatenate([np.eye(nout, dtype=np.float32).reshape(-1), np.zeros(nout, np.float32), np.asarray(log_sigma, np.float32)]))
+            return self._gtail
         if getattr(self, "_tail", None) is None or self._tail.network.dims[0] != nout:
             from .core import Chain, ContinuousNetwork
             self._tail = ContinuousNetwork(Chain(Dense(nout, nout)), ctx=self.ctx)

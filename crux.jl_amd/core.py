@@ -482,6 +482,9 @@ class GaussianPolicy(NetworkPolicy):
     def __init__(self, mu_chain, logSigma, **kw):
         if isinstance(logSigma, (Chain, NetworkPolicy)):
             self.mu_chain, self.logSigma_chain = _chain_of(mu_chain), _chain_of(logSigma)
+            if getattr(self.mu_chain, "conv", None) is not None or getattr(self.logSigma_chain, "conv", None) is not None:
+                raise NotImplementedError("%s: a two-headed actor (logSigma a network) over a conv chain is not implemented; a conv Gaussian actor takes a constant "
+                                          "logSigma vector" % type(self).__name__)
             net, ad = _two_headed_chain(self.mu_chain, self.logSigma_chain, type(self).__name__)
             super().__init__(net, n_extra=0, **kw)
             self.two_headed, self.act_dim = True, ad
@@ -491,6 +494,14 @@ class GaussianPolicy(NetworkPolicy):
             p[w0:w0 + n] *= np.float32(np.sqrt((h + 2.0 * ad) / (h + ad))); self.set_params(p)
             return
         logSigma = np.asarray(logSigma, np.float32).reshape(-1)
+        if getattr(_chain_of(mu_chain), "conv", None) is not None:      # a conv actor (csrc/conv_gauss.hip): trunk + head, logSigma the head handle's extras as below
+            if getattr(self, "squashed", False):
+                raise NotImplementedError("SquashedGaussianPolicy over a conv chain is not implemented (GaussianPolicy with a constant logSigma is)")
+            ad = _chain_of(mu_chain).dims[-1]
+            if logSigma.size != ad:
+                raise ValueError("GaussianPolicy: %d logSigma entries for a conv chain with %d outputs" % (logSigma.size, ad))
+            if ad > 32:
+                raise NotImplementedError("GaussianPolicy over a conv chain: act_dim = %d above 32, the width the exploration kernels take" % ad)
         super().__init__(_chain_of(mu_chain), n_extra=logSigma.size, **kw)
         p = self.get_params(); p[-logSigma.size:] = logSigma; self.set_params(p)
 
@@ -525,8 +536,25 @@ class GaussianPolicy(NetworkPolicy):
             raise ValueError("%s: %d rows, expected %d" % (what, x.shape[0], rows))
         return np.asfortranarray(x)
 
+    def log_sigma(self):
+        """the constant logSigma vector: the trailing extras of the (head) handle, read from the device"""
+        n = int(self.ctx.lib.crux_mlp_n_params(self.head_h)); out = np.empty(self.n_extra, np.float32)
+        return self.ctx.d2h(C.c_void_p(self.ctx.lib.crux_mlp_params_ptr(self.head_h) + 4 * (n - self.n_extra)), out)
+
+    def _conv_logpdf(self, s, a):
+        """gaussian_logpdf (policies.jl:333-336) summed over the action in Float32, term by term as the step's head forms it; mu(s) from trunk + head on the device"""
+        mu = self.forward(s); a = self._cols(a, mu.shape[0], "logpdf"); ls = self.log_sigma(); sg = np.exp(ls)
+        if a.shape[1] != mu.shape[1]:
+            raise ValueError("logpdf: %d states and %d actions" % (mu.shape[1], a.shape[1]))
+        lp = np.zeros((1, mu.shape[1]), np.float32)
+        for k in range(mu.shape[0]):
+            d = a[k] - mu[k]; lp[0] += (-(d * d) / (np.float32(2) * sg[k] * sg[k]) - np.float32(0.9189385332046727) - ls[k])
+        return lp
+
     def action(self, s):
         """action(pi, s) (policies.jl:331, 372): mu(s), ascale tanh(mu(s)) when squashed; [ad x B]"""
+        if self.is_conv:
+            return self.forward(s)
         self._need_two("action"); s = self._cols(s, self.network.dims[0], "action"); B = s.shape[1]
         a = np.empty((self.act_dim, B), np.float32, order="F")
         self.ctx.check(self.ctx.lib.crux_sigma_head_explore(self.h, _vp(s), B, 0, 0, 0, _vp(a), None))
@@ -541,6 +569,8 @@ class GaussianPolicy(NetworkPolicy):
 
     def logpdf(self, s, a):
         """logpdf(pi, s, a) (policies.jl:346, 396): [1 x B]"""
+        if self.is_conv:
+            return self._conv_logpdf(s, a)
         self._need_two("logpdf"); s = self._cols(s, self.network.dims[0], "logpdf"); a = self._cols(a, self.act_dim, "logpdf"); B = s.shape[1]
         if a.shape[1] != B:
             raise ValueError("logpdf: %d states and %d actions" % (B, a.shape[1]))
@@ -550,7 +580,9 @@ class GaussianPolicy(NetworkPolicy):
 
     def entropy(self, s):
         """entropy(pi, s): 1.4189385 + sum(logSigma(s)). GaussianPolicy: the reference's scalar over EVERYTHING (policies.jl:348: `sum` without dims);
-        SquashedGaussianPolicy: [1 x B] (policies.jl:398)."""
+        SquashedGaussianPolicy: [1 x B] (policies.jl:398). A conv actor's logSigma is constant: the scalar does not depend on s."""
+        if self.is_conv:
+            return np.float32(1.4189385332046727) + np.float32(self.log_sigma().sum(dtype=np.float32))
         self._need_two("entropy"); s = self._cols(s, self.network.dims[0], "entropy"); B = s.shape[1]
         sl = np.empty((1, B), np.float32)
         self.ctx.check(self.ctx.lib.crux_sigma_head_logpdf(self.h, _vp(s), None, B, None, _vp(sl)))
@@ -561,7 +593,8 @@ class GaussianPolicy(NetworkPolicy):
 class SquashedGaussianPolicy(GaussianPolicy):
     """SquashedGaussianPolicy(mu::ContinuousNetwork, logSigma::Array, ascale=1f0) (src/policies.jl:353-400): a = ascale*tanh(mu + sigma*eps),
     sigma = exp(clamp(logSigma, -5, 2)), logpdf with the tanh correction; the constant-logSigma form the reference's examples use
-    (examples/rl/pendulum.jl:20, half_cheetah_mujoco.jl:42). Greedy action = ascale*tanh(mu(s)) (:372)."""
+    (examples/rl/pendulum.jl:20, half_cheetah_mujoco.jl:42). Greedy action = ascale*tanh(mu(s)) (:372). Not implemented over a conv chain."""
+    squashed = True
 
     def __init__(self, mu_chain, logSigma, ascale=1.0, **kw):
         super().__init__(mu_chain, logSigma, **kw)      # (logSigma a Chain on mu's trunk: the two-headed form, see GaussianPolicy)
@@ -635,9 +668,11 @@ def refuse_spectral(pi, who):
 
 def refuse_conv(pi, who):
     """A conv policy (convolutional trunk + dense head, conv.py) is taken by value / forward, the parameter accessors, polyak_average_, copyto_, clone_policy, policy_explore on
-    a HostMDP, DQN, and -- as a conv DiscreteNetwork actor with (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic -- PPO, A2C and REINFORCE (on_policy.py). The
+    a HostMDP, DQN, and -- as a conv DiscreteNetwork or constant-logSigma GaussianPolicy actor with (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic -- PPO, A2C
+    and REINFORCE (on_policy.py). The
     entry points that take a network call this and refuse by their own name before any device call: the other solver constructors (by name: LagrangePPO, SAC, SoftQ, DDPG,
-    TD3; BC, the GAIL family and the rest through PolicyParams), PPO / A2C / REINFORCE for a conv Gaussian actor or an actor / critic pair of which only one is conv, a
+    TD3; BC, the GAIL family and the rest through PolicyParams), PPO / A2C / REINFORCE for an actor / critic pair of which only one is conv (a squashed or two-headed conv
+    Gaussian actor is refused where it is built), a
     Sampler on a device MDP, train! / batch_train!, fill_gae!, the GAIL discriminator steps and reward, the replica-group and multi-seed learners, EWC, and
     Optimiser(ClipValue, Adam) outside DQN (refuse_chain_params). Behind them stands NetworkPolicy.h itself: a conv policy has no whole-network handle, so any other path that reads
     `.h` (an ensemble member, a mixture's weight network, a Fisher regulariser's network, a custom-loss seam) raises the same NotImplementedError at that read instead of
@@ -645,7 +680,7 @@ def refuse_conv(pi, who):
     for q in ([] if pi is None else _leaves(pi)):
         if getattr(q, "is_conv", None):
             raise NotImplementedError("%s: a policy with a convolutional trunk (Conv layers in its Chain) is implemented on a HostMDP for DQN and for PPO / A2C / REINFORCE "
-                                      "(a conv DiscreteNetwork actor; PPO and A2C with a conv ContinuousNetwork critic, in an ActorCritic) only; "
+                                      "(a conv DiscreteNetwork or constant-logSigma GaussianPolicy actor; PPO and A2C with a conv ContinuousNetwork critic, in an ActorCritic) only; "
                                       "this path would treat the dense head as the whole network" % who)
 
 
@@ -1320,12 +1355,13 @@ def policy_explore(pi, cfg, svec, seed, steps_taken):
     Returns (actions [act_dim x E] Bool one-hot or Float32, logprob [E])."""
     svec = np.asfortranarray(svec, np.float32)
     if getattr(pi, "is_conv", None):      # trunk and head on the E observations, then the exploration kernel over the head's output (ConvTrunk.explore_tail): the draws of an MLP with these outputs
-        if cfg.head not in (L.HEAD["categorical"], L.HEAD["greedy_q"], L.HEAD["deterministic"]):
-            refuse_conv(pi, "policy_explore with a Gaussian head")
+        gauss = cfg.head == L.HEAD["gaussian"]      # a = mu + sigma eps and its logprob: the tail carries the actor's logSigma extras
+        if gauss and not (isinstance(pi, GaussianPolicy) and pi.n_extra and not pi.ascale_or_zero):
+            refuse_conv(pi, "policy_explore with a Gaussian head that is not a GaussianPolicy with a constant logSigma")
         svec = np.asfortranarray(pi.forward(svec))
         if not np.isfinite(svec).all():      # the identity layer would turn one Inf into a column of NaN (0 * Inf); a network that has diverged is reported, not explored with
             raise L.CruxError(L.ENAN, "policy_explore: the conv policy's output is not finite")
-        pi = pi.trunk.explore_tail(svec.shape[0])
+        pi = pi.trunk.explore_tail(svec.shape[0], pi.log_sigma() if gauss else None)
     E = svec.shape[1]; nout = getattr(pi, "act_dim", None) or pi.network.dims[-1]
     disc = cfg.head in (L.HEAD["categorical"], L.HEAD["greedy_q"])
     a = np.zeros((nout, E), np.bool_ if disc else np.float32, order="F"); lp = np.empty(E, np.float32)

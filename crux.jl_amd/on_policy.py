@@ -47,13 +47,15 @@ class OnPolicySolver:
 
 
 def _conv_pg_policy(pi, who, with_critic):
-    """True: `pi` is what the conv policy-gradient step takes -- a conv DiscreteNetwork actor and (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic. False: no conv
-    network in it. Everything in between is refused by name: a conv Gaussian actor, and a pair of which only one member has a trunk (the step pairs two trunks)."""
+    """True: `pi` is what the conv policy-gradient step takes -- a conv DiscreteNetwork actor, or a conv GaussianPolicy actor with a constant logSigma (csrc/conv_gauss.hip), and
+    (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic. False: no conv network in it. Everything in between is refused by name: a pair of which only one member has a
+    trunk (the step pairs two trunks)."""
     if not any(getattr(q, "is_conv", None) for q in _leaves(pi)):
         return False
     A = actor(pi)
-    if not (isinstance(A, DiscreteNetwork) and A.is_conv):
-        refuse_conv(pi, "%s (the actor must be a DiscreteNetwork over a conv chain; conv Gaussian actors and conv critics behind an MLP actor are not implemented)" % who)
+    gauss = isinstance(A, GaussianPolicy) and A.n_extra > 0 and not A.ascale_or_zero      # (squashed and two-headed conv actors do not get past their constructors)
+    if not ((isinstance(A, DiscreteNetwork) or gauss) and A.is_conv):
+        refuse_conv(pi, "%s (the actor must be a DiscreteNetwork or a constant-logSigma GaussianPolicy over a conv chain; conv critics behind an MLP actor are not implemented)" % who)
     if with_critic:
         Cn = critic(pi) if isinstance(pi, ActorCritic) else None
         if not (type(Cn) is ContinuousNetwork and Cn.is_conv and Cn.network.dims[-1] == 1):
@@ -76,7 +78,8 @@ def _conv_policy_gradient_training(solver, D):
     _ensure_opt(A, pa)
     if Cn is not None:
         _ensure_opt(Cn, pc)
-    ctx, lib, n, od, na = D.ctx, D.ctx.lib, len(D), A.trunk.spec.in_features, len(A.outputs)
+    ad = A.n_extra      # > 0: a Gaussian actor (logSigma extras on its head handle), the Float32 action column and crux_conv_pg_step_gauss
+    ctx, lib, n, od, na = D.ctx, D.ctx.lib, len(D), A.trunk.spec.in_features, (4 * ad if ad else len(A.outputs))
     col = {k: D.column_ptr(k) for k in ("s", "a", "logprob", "return") + (("advantage",) if pa.loss.name != "reinforce" else ())}
     at = lambda k, row, width: C.c_void_p(col[k] + row * width) if k in col else None      # noqa: E731
     ha, hc = (A.trunk.h, A.trunk.p.h, A.head_h), ((Cn.trunk.h, Cn.trunk.p.h, Cn.head_h) if Cn is not None else (None, None, None))
@@ -93,9 +96,10 @@ def _conv_policy_gradient_training(solver, D):
             if not (live["a"] or live["c"]):
                 break
             B = min(pa.batch_size, n - s0)
-            ctx.check(lib.crux_conv_pg_step(*(ha if live["a"] else (None, None, None)), *(hc if live["c"] else (None, None, None)), at("s", s0, 4 * od), at("a", s0, na), at("advantage", s0, 4),
-                                            at("return", s0, 4), at("logprob", s0, 4), B, L.LOSS[pa.loss.name] if live["a"] else L.LOSS["value_mse"],
-                                            float(P.get("eps", 0.2)), float(P.get("lambda_p", 1.0)), float(P.get("lambda_e", 0.1)), _vp(raw), _vp(craw)))
+            step, acts = (lib.crux_conv_pg_step_gauss, (at("a", s0, na), ad)) if ad else (lib.crux_conv_pg_step, (at("a", s0, na),))
+            ctx.check(step(*(ha if live["a"] else (None, None, None)), *(hc if live["c"] else (None, None, None)), at("s", s0, 4 * od), *acts, at("advantage", s0, 4),
+                           at("return", s0, 4), at("logprob", s0, 4), B, L.LOSS[pa.loss.name] if live["a"] else L.LOSS["value_mse"],
+                           float(P.get("eps", 0.2)), float(P.get("lambda_p", 1.0)), float(P.get("lambda_e", 0.1)), _vp(raw), _vp(craw)))
             for k, p, r in (("a", pa, raw), ("c", pc, craw)):
                 if live[k]:
                     nb[k] += 1; last[k] = r.copy()

@@ -84,7 +84,7 @@ int32_t crux_mlp_create(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n
  * this IS crux_mlp_create. Otherwise the handle is "wide" and is taken only where the dense engine (crux_mlp_forward_cached / crux_mlp_backward) runs it:
  * crux_mlp_destroy / _n_params / _params_ptr / _grads_ptr / _set_params / _get_params / _init_glorot, crux_mlp_forward_cached, crux_mlp_backward, crux_mlp_copy,
  * crux_polyak, crux_adam_init / _get_state / _set_state / _state_ptrs / _set_clip_value / _get_clip_value, and as the head of crux_conv_dqn_target / crux_conv_td_step /
- * crux_conv_td_step_with_error / crux_conv_pg_step. Every other entry that takes a crux_mlp returns CRUX_EUNSUP naming itself and the wide handle before anything is enqueued or changed: their
+ * crux_conv_td_step_with_error / crux_conv_pg_step / crux_conv_pg_step_gauss. Every other entry that takes a crux_mlp returns CRUX_EUNSUP naming itself and the wide handle before anything is enqueued or changed: their
  * kernels keep a layer in LDS or registers sized for 1024 (the learners, the rollout, crux_mlp_forward's generic kernel) or were never run past it.
  * crux_mlp_create itself keeps refusing a dimension above 1024. */
 int32_t crux_mlp_create_wide(crux_ctx* ctx, int32_t n_layers, const int32_t* dims /*n_layers+1*/,
@@ -1090,6 +1090,18 @@ int32_t crux_conv_backward_pair(crux_conv* conv0, crux_mlp* params0, crux_conv* 
 int32_t crux_conv_pg_step(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp* actor_head, crux_conv* critic_conv, crux_mlp* critic_trunk, crux_mlp* critic_head,
                           const float* d_s, const uint8_t* d_a, const float* d_adv, const float* d_ret, const float* d_old_logprob, int64_t B,
                           int32_t loss, float eps_clip, float lambda_p, float lambda_e, float* info_out, float* critic_out);
+/* crux_conv_pg_step for a CONTINUOUS action: the actor is GaussianPolicy(ContinuousNetwork(conv chain), logSigma) with a constant logSigma (policies.jl:315-350) -- its head
+ * handle ends in act_dim outputs (mu) and carries act_dim trailing extras (logSigma), as the MLP GaussianPolicy handle does. d_a [act_dim x B] Float32 actions; everything
+ * else as above, the critic included. Per column l = sum_d [-(a_d - mu_d)^2 / (2 sigma_d^2) - logSigma_d - log(2 pi) / 2], sigma = exp(logSigma) (the arithmetic of
+ * crux_batch_train's Gaussian head), the seed d(loss)/d(mu_d) = w (a_d - mu_d) / sigma_d^2 with w = d(loss)/dl, and d(loss)/d(logSigma_d) = sum_j w_j ((a_d - mu_d)^2 /
+ * sigma_d^2 - 1) - lambda_e as Float64 block sums added in block order (csrc/conv_gauss.hip; no float atomics). ENTROPY = 1.4189385 + sum(logSigma), the constant once as the reference
+ * writes it (policies.jl:348) and as crux_batch_train reports it. The actor's
+ * GRAD_NORM and its gate are over trunk, head layers and the logSigma entries (norm(grads) over Flux.params); Adam moves logSigma with the head. Two identical calls give
+ * identical bits. CRUX_EUNSUP: act_dim > 32 (what crux_policy_explore takes), a two-headed (crux_mlp_set_sigma_head) or squashed (crux_mlp_set_squash) head, a call while
+ * the fused executor records; CRUX_EINVAL: a head whose last width or number of extras is not act_dim.                                                               */
+int32_t crux_conv_pg_step_gauss(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp* actor_head, crux_conv* critic_conv, crux_mlp* critic_trunk, crux_mlp* critic_head,
+                                const float* d_s, const float* d_a, int32_t act_dim, const float* d_adv, const float* d_ret, const float* d_old_logprob, int64_t B,
+                                int32_t loss, float eps_clip, float lambda_p, float lambda_e, float* info_out, float* critic_out);
 /* DeepEnsemble / DeepClassificationEnsemble whose members are conv chains (src/extras/deep_ensembles.jl:3, :41: generator() may return any Flux chain; here
  * Chain([x -> c x,] Conv..., flatten, Dense...)): the counterparts of crux_ensemble_forward / _logpdf / _step / _train / _passes. Member m is convs[m] (its layer table and
  * workspace), trunks[m] (its bare-vector parameter handle) and heads[m] (the dense layers behind flatten); M in 1..16. d_x is [W H C x B]; kinds, outputs, the info row

@@ -16,6 +16,9 @@ whole step minus the four passes (derived, and says so). Writes profiles/conv_at
 crux_conv_pg_step (ppo_loss + critic mse, 2048-256-6 and 2048-256-1 heads) beside two single-trunk steps and beside the same step in torch-ROCm eager; B = 32 and 128.
 Writes profiles/conv_pg_bench.txt with --save.
 
+--pg-gauss: one PPO step of crux_conv_pg_step_gauss (csrc/conv_gauss.hip: Gaussian actor, ad = 3, 2048-256-3 and 2048-256-1 heads) beside crux_conv_pg_step with 3 categorical
+outputs at the same shapes, B = 32 and 128. Writes profiles/conv_gauss_bench.txt with --save.
+
 --ensemble: M = 5 and 16 conv members over one batch (csrc/conv_group.hip, the conv entries of csrc/ensemble.hip), B = 32 and 128, at 16x16x2 -> 8@(4,4)/2 -> 12@(3,3)/1 with a
 300-64-10 head and at the Atari trunk with a 2048-1024-10 head. The grouped passes (crux_conv_ensemble_passes: trunks and heads, forward + backward) beside the same passes member
 by member (crux_conv_forward_cached, crux_mlp_forward_cached, crux_mlp_backward with d_dx, crux_conv_backward); and, at the small shape, the whole crux_conv_ensemble_step beside
@@ -233,6 +236,37 @@ def pg(a, crux, L):
         open(os.path.join(ROOT, "profiles", "conv_pg_bench.txt"), "w").write(txt)
 
 
+def pg_gauss(a, crux, L):
+    """--pg-gauss: crux_conv_pg_step_gauss (PPO, Gaussian actor with ad = 3, critic) beside crux_conv_pg_step with 3 categorical outputs; Atari trunk, 2048-256 heads"""
+    ctx = crux.default_context(); rng = np.random.default_rng(0); lines = []; ad = 3; vp = lambda v: v.ctypes.data_as(C.c_void_p); f = lambda t: "%.1f us (%.1f .. %.1f)" % t      # noqa: E731
+    atari = lambda nout: crux.Chain(crux.Scale(1.0 / 255.0), crux.Conv((8, 8), 4, 16, "relu", stride=4), crux.Conv((4, 4), 16, 32, "relu", stride=2), crux.flatten, crux.Dense(2048, 256, "relu"),      # noqa: E731
+                                    crux.Dense(256, nout), input=(80, 80, 4))
+    for B in (32, 128):
+        G = crux.GaussianPolicy(crux.ContinuousNetwork(atari(ad), seed=2, ctx=ctx), np.full(ad, -0.5, np.float32), seed=2, ctx=ctx)
+        D = crux.DiscreteNetwork(atari(ad), list(range(ad)), seed=2, ctx=ctx); V = crux.ContinuousNetwork(atari(1), seed=3, ctx=ctx)
+        for q in (G, D, V):
+            q.attach_optimizer(crux.Adam(np.float32(1e-3)))
+        arrs = [np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32)), np.asfortranarray(rng.normal(0, 1, (ad, B)).astype(np.float32)),
+                np.asfortranarray(np.eye(ad, dtype=np.uint8)[:, rng.integers(0, ad, B)]), rng.normal(0, 1, B).astype(np.float32), rng.normal(0, 1, B).astype(np.float32), np.full(B, -1.79, np.float32)]
+        d = [ctx.alloc(v.nbytes) for v in arrs]
+        for p, v in zip(d, arrs):
+            ctx.h2d(p, v)
+        d_x, d_af, d_a8, d_adv, d_ret, d_lp = d; raw, craw = np.zeros(L.INFO_N, np.float32), np.zeros(2, np.float32)
+        hv = (V.trunk.h, V.trunk.p.h, V.head_h)
+        gauss = lambda: ctx.check(ctx.lib.crux_conv_pg_step_gauss(G.trunk.h, G.trunk.p.h, G.head_h, *hv, d_x, d_af, ad, d_adv, d_ret, d_lp, B, L.LOSS["ppo"], 0.2, 1.0, 0.1, vp(raw), vp(craw)))      # noqa: E731
+        cat = lambda: ctx.check(ctx.lib.crux_conv_pg_step(D.trunk.h, D.trunk.p.h, D.head_h, *hv, d_x, d_a8, d_adv, d_ret, d_lp, B, L.LOSS["ppo"], 0.2, 1.0, 0.1, vp(raw), vp(craw)))      # noqa: E731
+        g, c = median_window(gauss, ctx.sync, a.n, a.reps), median_window(cat, ctx.sync, a.n, a.reps)
+        verdict = "the Gaussian step is faster" if g[2] < c[1] else ("the Gaussian step is SLOWER beyond the spread of these windows" if g[1] > c[2] else "inside the run-to-run spread")
+        lines.append("PPO step, actor + critic, 2048-256-3 and 2048-256-1 heads, B %3d: crux_conv_pg_step_gauss (ad 3) %s, crux_conv_pg_step (3 categorical outputs) %s, ratio gauss / categorical %.3f (%s)"
+                     % (B, f(g), f(c), g[0] / c[0], verdict))
+        for p in d:
+            ctx.free(p)
+    txt = "# tools/conv_bench.py --pg-gauss: one MI355X, f32, median of %d windows of %d calls (min .. max), host clock around synchronised windows\n" % (a.reps, a.n) + "\n".join(lines) + "\n"
+    print(txt)
+    if a.save:
+        open(os.path.join(ROOT, "profiles", "conv_gauss_bench.txt"), "w").write(txt)
+
+
 def ensemble(a, crux, L):
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines = []; vp = lambda v: v.ctypes.data_as(C.c_void_p); f = lambda t: "%.1f us (%.1f .. %.1f)" % t      # noqa: E731
     arr = lambda hs: (C.c_void_p * len(hs))(*[getattr(h, "value", h) for h in hs])      # noqa: E731
@@ -279,7 +313,7 @@ def ensemble(a, crux, L):
 
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=200); ap.add_argument("--reps", type=int, default=7); ap.add_argument("--save", action="store_true")
-    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--ensemble", action="store_true")
+    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--pg-gauss", action="store_true"); ap.add_argument("--ensemble", action="store_true")
     a = ap.parse_args()
     if a.torch_child:
         return torch_child(a)
@@ -290,6 +324,8 @@ def main():
         return atari(a, crux, L)
     if a.pg:
         return pg(a, crux, L)
+    if a.pg_gauss:
+        return pg_gauss(a, crux, L)
     if a.ensemble:
         return ensemble(a, crux, L)
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
