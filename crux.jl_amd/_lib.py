@@ -40,6 +40,13 @@ class ConvLayer(C.Structure):
                 ("dilation1", i32), ("dilation2", i32), ("groups", i32)]
 
 
+class PoolLayer(C.Structure):
+    """crux_pool_layer (include/cruxhip.h): the pool behind one Conv of a trunk; kind 0 none, 1 max, 2 mean."""
+    _fields_ = [("kind", i32), ("k1", i32), ("k2", i32), ("stride1", i32), ("stride2", i32), ("pad1", i32), ("pad2", i32)]
+
+
+POOL_KIND = {"max": 1, "mean": 2}
+
 # name -> (restype, argtypes); every symbol declared in include/cruxhip.h appears here (checked by tests).
 SIGNATURES = {
     "crux_ctx_create": (i32, [i32, vp, P(vp)]),
@@ -221,6 +228,7 @@ SIGNATURES = {
     "crux_dpg_actor_step": (i32, [vp, vp, vp, vp]),
     "crux_conv_create": (i32, [vp, i32, i32, i32, f32, i32, P(ConvLayer), P(vp)]),
     "crux_conv_destroy": (i32, [vp]),
+    "crux_conv_set_pool": (i32, [vp, P(PoolLayer)]),
     "crux_conv_n_params": (i64, [vp]),
     "crux_conv_out_features": (i64, [vp]),
     "crux_conv_init_glorot": (i32, [vp, vp, u64, u32]),

@@ -2,7 +2,8 @@
 
     Chain(Scale(1 / 255), Conv((8, 8), 4, 16, "relu", stride=4), Conv((4, 4), 16, 32, "relu", stride=2), flatten, Dense(2048, 256, "relu"), Dense(256, n), input=(80, 80, 4))
 
-A chain that starts with `[Scale,] Conv+, flatten` is split into a trunk (a crux_conv descriptor plus a bare-vector parameter handle) and the dense head that follows; a
+A Conv may be followed by one MaxPool or MeanPool (csrc/conv_pool.hip): Chain(Conv((3, 3), 1, 8, "relu", pad=1), MaxPool((2, 2)), ..., flatten, Dense...).
+A chain that starts with `[Scale,] (Conv [pool])+, flatten` is split into a trunk (a crux_conv descriptor plus a bare-vector parameter handle) and the dense head that follows; a
 DiscreteNetwork / ContinuousNetwork over such a chain keeps the head in `.head_h` / `.network.dims` and the trunk in `.trunk`; its `.h` raises (core.NetworkPolicy.h: there is
 no handle of the whole network, and code that reads one would run the head over raw observations). Semantics are Flux's: WHCN column-major
 images (a flattened observation has index w + W (h + H c)), (k1, k2, cin, cout) weights, a true (flipped) convolution, flatten in WHC order.
@@ -43,6 +44,32 @@ class Conv:
             raise ValueError("Conv: activation %r, one of %s" % (self.act, sorted(L.ACT)))
 
 
+class _Pool:
+    """Flux.MaxPool / MeanPool((k1, k2); stride = (k1, k2), pad = 0) behind a Conv: pad symmetric per axis, pad < k. Max ignores padding taps, propagates NaN and breaks
+    ties towards the first element in window order; mean divides by k1 k2 always (NNlib; torch's count_include_pad)."""
+    conv_kind = "pool"
+
+    def __init__(self, k, stride=None, pad=0):
+        name = type(self).__name__
+        self.k = _two(k, "the window")
+        self.stride, self.pad = _two(self.k if stride is None else stride, "stride"), _two(pad, "pad")
+        if min(self.k) < 1 or min(self.stride) < 1 or min(self.pad) < 0 or self.pad[0] >= self.k[0] or self.pad[1] >= self.k[1]:
+            raise ValueError("%s: window %r, stride %r, pad %r: needs window >= 1, stride >= 1, 0 <= pad < window" % (name, self.k, self.stride, self.pad))
+        if self.kind == "max" and self.k[0] * self.k[1] > 256:
+            raise NotImplementedError("MaxPool: a window of %d x %d > 256 elements is not implemented" % self.k)
+
+    def out_extent(self, w, h):
+        return (w + 2 * self.pad[0] - self.k[0]) // self.stride[0] + 1, (h + 2 * self.pad[1] - self.k[1]) // self.stride[1] + 1
+
+
+class MaxPool(_Pool):
+    kind = "max"
+
+
+class MeanPool(_Pool):
+    kind = "mean"
+
+
 class _Flatten:
     """Flux.flatten: [OW, OH, cout, B] -> [OW OH cout, B]"""
     conv_kind = "flatten"
@@ -60,10 +87,13 @@ class Scale:
 
 
 class ConvSpec:
-    """the trunk of a chain: input extent, input scale, the Conv layers, and the extents between them"""
+    """the trunk of a chain: input extent, input scale, the Conv layers, the pool behind each (or None), and the extents between the layers (behind the pool)"""
 
-    def __init__(self, W, H, C_, scale, convs):
+    def __init__(self, W, H, C_, scale, convs, pools=None):
         self.W, self.H, self.C, self.scale, self.convs = int(W), int(H), int(C_), float(scale), list(convs)
+        self.pools = list(pools) if pools is not None else [None] * len(self.convs)
+        if len(self.pools) != len(self.convs):
+            raise ValueError("ConvSpec: %d pools for %d Conv layers (one entry per layer, None for no pool)" % (len(self.pools), len(self.convs)))
         self.extents = [(self.W, self.H, self.C)]
         for n, l in enumerate(self.convs):
             w, h, c = self.extents[-1]
@@ -72,6 +102,11 @@ class ConvSpec:
             ow, oh = (w + 2 * l.pad[0] - l.k[0]) // l.stride[0] + 1, (h + 2 * l.pad[1] - l.k[1]) // l.stride[1] + 1
             if l.k[0] > w + 2 * l.pad[0] or l.k[1] > h + 2 * l.pad[1] or ow < 1 or oh < 1:
                 raise ValueError("Chain: Conv layer %d (%d x %d) does not fit its %d x %d input with pad %r" % (n, l.k[0], l.k[1], w, h, l.pad))
+            q = self.pools[n]
+            if q is not None:
+                if q.k[0] > ow + 2 * q.pad[0] or q.k[1] > oh + 2 * q.pad[1]:
+                    raise ValueError("Chain: the %s (%d x %d) behind Conv layer %d does not fit its %d x %d output with pad %r" % (type(q).__name__, q.k[0], q.k[1], n, ow, oh, q.pad))
+                ow, oh = q.out_extent(ow, oh)
             self.extents.append((ow, oh, l.cout))
 
     @property
@@ -97,26 +132,36 @@ class ConvSpec:
 
 
 def split_chain(layers, input):
-    """[Scale,] Conv+, flatten, Dense+ -> (ConvSpec, the Dense layers), shapes checked against the input extent (W, H, C)"""
+    """[Scale,] (Conv [MaxPool | MeanPool])+, flatten, Dense+ -> (ConvSpec, the Dense layers), shapes checked against the input extent (W, H, C)"""
     layers = list(layers)
     if input is None or len(tuple(input)) != 3:
         raise ValueError("Chain: a chain with Conv layers needs its input extent, Chain(..., input=(W, H, C))")
     scale, n = 1.0, 0
     if isinstance(layers[0], Scale):
         scale, n = layers[0].c, 1
-    convs = []
-    while n < len(layers) and isinstance(layers[n], Conv):
-        convs.append(layers[n]); n += 1
+    convs, pools = [], []
+    while n < len(layers) and isinstance(layers[n], (Conv, _Pool)):
+        if isinstance(layers[n], Conv):
+            convs.append(layers[n]); pools.append(None)
+        elif not convs:
+            raise NotImplementedError("Chain: a %s before the first Conv is not implemented (a pool follows a Conv)" % type(layers[n]).__name__)
+        elif pools[-1] is not None:
+            raise NotImplementedError("Chain: two pooling layers in a row are not implemented (at most one pool per Conv)")
+        else:
+            pools[-1] = layers[n]
+        n += 1
     if not convs or n >= len(layers) or not isinstance(layers[n], _Flatten):
-        raise ValueError("Chain: a conv chain is [Scale,] Conv..., flatten, Dense... (Scale in the first position only, flatten after the last Conv)")
+        raise ValueError("Chain: a conv chain is [Scale,] Conv [pool]..., flatten, Dense... (Scale in the first position only, flatten after the last Conv or its pool)")
+    if any(isinstance(l, _Pool) for l in layers[n + 1:]):
+        raise NotImplementedError("Chain: a pooling layer after flatten is not implemented (a pool follows a Conv)")
     if len(convs) > 4:
         raise NotImplementedError("Chain: %d Conv layers, at most 4 are implemented" % len(convs))
     head = layers[n + 1:]
     if not head or any(getattr(l, "conv_kind", None) for l in head) or not all(isinstance(l, Dense) for l in head):
-        raise ValueError("Chain: flatten must be followed by Dense layers only (ConvSN, ConvTranspose, pooling and batch norm are not implemented)")
+        raise ValueError("Chain: flatten must be followed by Dense layers only (ConvSN, ConvTranspose and batch norm are not implemented)")
     if any(getattr(l, "n_iterations", 0) for l in head):
         raise NotImplementedError("Chain: DenseSN layers behind a conv trunk are not implemented")
-    spec = ConvSpec(input[0], input[1], input[2], scale, convs)
+    spec = ConvSpec(input[0], input[1], input[2], scale, convs, pools)
     if head[0].inp != spec.out_features:
         raise ValueError("Chain: flatten yields %d x %d x %d = %d features, the next Dense takes %d" % (spec.extents[-1] + (spec.out_features, head[0].inp)))
     return spec, head
@@ -137,6 +182,12 @@ class ConvTrunk:
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.crux_conv_create(self.ctx.h, spec.W, spec.H, spec.C, spec.scale, len(spec.convs), arr, C.byref(h)))
         self.h = h
+        if any(q is not None for q in spec.pools):
+            parr = (L.PoolLayer * len(spec.convs))()
+            for a, q in zip(parr, spec.pools):
+                if q is not None:
+                    a.kind, a.k1, a.k2, a.stride1, a.stride2, a.pad1, a.pad2 = (L.POOL_KIND[q.kind],) + q.k + q.stride + q.pad
+            self.ctx.check(self.ctx.lib.crux_conv_set_pool(self.h, parr))
         assert int(self.ctx.lib.crux_conv_n_params(self.h)) == spec.n_params and int(self.ctx.lib.crux_conv_out_features(self.h)) == spec.out_features
         self.p = ParamVector(np.zeros(spec.n_params, np.float32), ctx=self.ctx)
         self.ctx.check(self.ctx.lib.crux_conv_init_glorot(self.h, self.p.h, int(seed), (int(stream) + TRUNK_STREAM) & 0xFFFFFFFF))

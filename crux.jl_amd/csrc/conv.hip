@@ -32,6 +32,9 @@ struct crux_conv {
   ConvLayerDesc ly[CRUX_CONV_MAXL];
   int64_t n_params = 0, in_features = 0, feat[CRUX_CONV_MAXL + 1] = {0}, maxfeat = 0;      // feat[l]: features of one sample entering layer l (feat[L]: the flattened output)
   float* ws = nullptr; int64_t ws_B = 0;      // cached outputs of layers 1..L, two delta buffers, the weight-gradient partials; capacity ws_B samples
+  // crux_conv_set_pool (conv_pool.hip): layer l's pool, or kind 0. A pooled layer's cached output (what the next layer reads, feat[l + 1]) is P_l; its Y_l (yfeat[l] features)
+  // and index plane lie behind the partials, from float offset ws_pool
+  ConvPoolDesc pl[CRUX_CONV_MAXL] = {}; int64_t yfeat[CRUX_CONV_MAXL] = {0}; size_t ws_pool = 0;
 };
 
 struct ConvArgs {
@@ -253,7 +256,8 @@ static int32_t conv_ensure_ws(crux_conv* v, int64_t B) {
   size_t tot = 0; for (int l = 1; l <= v->L; ++l) tot += (size_t)v->feat[l] * (size_t)cap;
   tot += 2 * (size_t)v->maxfeat * (size_t)cap;
   size_t part = 0; for (int l = 0; l < v->L; ++l) { const size_t p = (size_t)conv_nch(v, l, cap) * (size_t)conv_per(v, l); if (p > part) part = p; }
-  tot += part;
+  tot += part; v->ws_pool = tot;
+  for (int l = 0; l < v->L; ++l) if (v->pl[l].kind) tot += (size_t)(v->yfeat[l] + (v->feat[l + 1] + 3) / 4) * (size_t)cap;
   if (hipMalloc(&v->ws, sizeof(float) * tot + 64) != hipSuccess) return crux_fail(c, CRUX_ENOMEM, "conv workspace: hipMalloc(%zu) failed", sizeof(float) * tot);
   v->ws_B = cap; return CRUX_OK;
 }
@@ -263,6 +267,16 @@ static float* conv_act(crux_conv* v, int l) {      // l in 1..L + 2: the cached 
   return v->ws + off;
 }
 static float* conv_part(crux_conv* v) { return conv_act(v, v->L + 3); }
+// a pooled layer l (0-based): its Y_l [yfeat[l] x ws_B], then its index plane (one byte per element of P_l)
+static float* conv_pool_y(crux_conv* v, int l) {
+  size_t off = v->ws_pool; for (int q = 0; q < l; ++q) if (v->pl[q].kind) off += (size_t)(v->yfeat[q] + (v->feat[q + 1] + 3) / 4) * (size_t)v->ws_B;
+  return v->ws + off;
+}
+static float* conv_layer_y(crux_conv* v, int l) { return v->pl[l].kind ? conv_pool_y(v, l) : conv_act(v, l + 1); }      // where layer l's forward kernel writes
+// member m of a pool launch over layer l: forward (dp = dz = NULL) or reverse
+static void conv_pool_member(ConvPoolGroup& t, int m, crux_conv* v, int l, int64_t B, const float* dp, float* dz) {
+  t.d = v->pl[l]; t.B = (int32_t)B; t.y[m] = conv_pool_y(v, l); t.p[m] = conv_act(v, l + 1); t.idx[m] = (uint8_t*)(t.y[m] + (size_t)v->yfeat[l] * (size_t)v->ws_B); t.dp[m] = dp; t.dz[m] = dz;
+}
 
 static int32_t conv_check(const char* who, crux_conv* v, crux_mlp* p, int64_t B) {
   if (!v || !p) return CRUX_EINVAL;
@@ -281,12 +295,13 @@ static int32_t conv_forward_ws(const char* who, crux_conv* v, crux_mlp* p, const
   crux_ctx* c = v->ctx; rc = conv_ensure_ws(v, B); if (rc) return rc;
   const float* x = d_x;
   for (int l = 0; l < v->L; ++l) {
-    ConvArgs q{}; q.d = v->ly[l]; q.B = (int32_t)B; q.w = p->p + q.d.woff; q.bias = p->p + q.d.boff; q.x = x; q.xscale = l == 0 ? v->scale : 1.f; q.y = conv_act(v, l + 1);
+    ConvArgs q{}; q.d = v->ly[l]; q.B = (int32_t)B; q.w = p->p + q.d.woff; q.bias = p->p + q.d.boff; q.x = x; q.xscale = l == 0 ? v->scale : 1.f; q.y = conv_layer_y(v, l);
     const int64_t tiles = (int64_t)((q.d.cout + 15) >> 4) * ((B * q.d.OW * q.d.OH + 15) >> 4);
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
     if (conv_fwd_vec(q.d, q.w, q.x)) hipLaunchKernelGGL((k_conv_fwd<true>), grid, block, 0, c->stream, q);
     else hipLaunchKernelGGL((k_conv_fwd<false>), grid, block, 0, c->stream, q);
-    x = q.y;
+    if (v->pl[l].kind) { ConvPoolGroup t{}; conv_pool_member(t, 0, v, l, B, nullptr, nullptr); conv_pool_launch_fwd(c->stream, t, 1); }
+    x = conv_act(v, l + 1);
   }
   return crux_launch_check(c, "k_conv_fwd");
 }
@@ -296,7 +311,10 @@ static int32_t conv_backward_ws(const char* who, crux_conv* v, crux_mlp* p, cons
   crux_ctx* c = v->ctx;
   if (!v->ws || v->ws_B < B) return crux_fail(c, CRUX_EINVAL, "%s: no cached forward pass for this batch", who);
   const float* dcur = d_dy; float* dnxt = conv_act(v, v->L + 1); float* dspare = conv_act(v, v->L + 2);
-  if (v->ly[v->L - 1].act != CRUX_ACT_IDENTITY) {      // dZ_L = act'(Y_L) .* dY
+  if (v->pl[v->L - 1].kind) {      // dZ_L = act'(Y_L) .* pool'(dP_L)
+    ConvPoolGroup t{}; conv_pool_member(t, 0, v, v->L - 1, B, d_dy, dnxt); conv_pool_launch_bwd(c->stream, t, 1);
+    dcur = dnxt; dnxt = dspare; dspare = const_cast<float*>(dcur);
+  } else if (v->ly[v->L - 1].act != CRUX_ACT_IDENTITY) {      // dZ_L = act'(Y_L) .* dY
     const int64_t cnt = v->feat[v->L] * B;
     crux_launch<ActGradOp>((unsigned)((cnt + 255) / 256), 256, c->stream, d_dy, (const float*)conv_act(v, v->L), (int)v->ly[v->L - 1].act, cnt, dnxt);
     dcur = dnxt; dnxt = dspare; dspare = const_cast<float*>(dcur);
@@ -310,10 +328,15 @@ static int32_t conv_backward_ws(const char* who, crux_conv* v, crux_mlp* p, cons
       hipLaunchKernelGGL(k_conv_wgrad_combine, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, c->stream, (const float*)q.part, per, nch, gscale, p->g + q.d.woff);
     }
     if (l > 0 || d_dx) {
-      q.dx = l > 0 ? dnxt : d_dx; q.ysrc = l > 0 ? q.x : nullptr; q.act_prev = l > 0 ? v->ly[l - 1].act : CRUX_ACT_IDENTITY; q.dxscale = v->scale;
+      const bool pooled = l > 0 && v->pl[l - 1].kind;      // then this launch writes dP_{l-1} as it is, and k_pool_bwd applies act' of Y_{l-1}
+      q.dx = l > 0 ? dnxt : d_dx; q.ysrc = l > 0 && !pooled ? q.x : nullptr; q.act_prev = l > 0 ? v->ly[l - 1].act : CRUX_ACT_IDENTITY; q.dxscale = pooled ? 1.f : v->scale;
       const int64_t tiles = (int64_t)((q.d.cin + 15) >> 4) * ((B * q.d.IW * q.d.IH + 15) >> 4);
       hipLaunchKernelGGL(k_conv_dgrad, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, c->stream, q);
       dcur = dnxt; float* t = dnxt; dnxt = dspare; dspare = t;
+      if (pooled) {      // the buffer that held dZ_l has been read by both kernels of layer l: it takes dZ_{l-1}
+        ConvPoolGroup g{}; conv_pool_member(g, 0, v, l - 1, B, dcur, dnxt); conv_pool_launch_bwd(c->stream, g, 1);
+        dcur = dnxt; t = dnxt; dnxt = dspare; dspare = t;
+      }
     }
   }
   return crux_launch_check(c, "conv backward");
@@ -381,7 +404,7 @@ int32_t crux_conv_create(crux_ctx* ctx, int32_t W, int32_t H, int32_t C, float i
     off += K * s.cout + s.cout;
     if (K > (1 << 20) || feat > (1 << 26) || off > 0x7fffffffll) { delete v; return crux_fail(ctx, CRUX_EINVAL, "crux_conv_create: layer %d is too large", l); }
     d.K = (int32_t)K; d.boff = (int32_t)(off - s.cout); d.woff = (int32_t)(d.boff - K * s.cout);
-    v->feat[l + 1] = feat; if (feat > v->maxfeat) v->maxfeat = feat;
+    v->feat[l + 1] = feat; v->yfeat[l] = feat; if (feat > v->maxfeat) v->maxfeat = feat;
     iw = d.OW; ih = d.OH; ic = s.cout;
   }
   v->n_params = off;
@@ -391,6 +414,37 @@ int32_t crux_conv_destroy(crux_conv* v) {
   if (!v) return CRUX_OK;
   if (v->ws) { crux_sync_before_free(v->ctx); (void)hipFree(v->ws); }
   delete v; return CRUX_OK;
+}
+int32_t crux_conv_set_pool(crux_conv* v, const crux_pool_layer* pools) {
+  if (!v || !pools) return CRUX_EINVAL;
+  crux_ctx* c = v->ctx; const char* who = "crux_conv_set_pool";
+  ConvLayerDesc ly[CRUX_CONV_MAXL]; ConvPoolDesc pl[CRUX_CONV_MAXL] = {}; int64_t feat[CRUX_CONV_MAXL + 1], yfeat[CRUX_CONV_MAXL], maxfeat = v->in_features;
+  int iw = v->W, ih = v->H; feat[0] = v->in_features;
+  for (int l = 0; l < v->L; ++l) {      // the whole table is derived and checked before the handle changes
+    ConvLayerDesc d = v->ly[l]; const crux_pool_layer& s = pools[l];
+    if (d.k1 > iw + 2 * d.p1 || d.k2 > ih + 2 * d.p2)
+      return crux_fail(c, CRUX_EINVAL, "%s: layer %d: Conv((%d, %d), pad (%d, %d)) no longer fits its input, %d x %d behind the pool of layer %d", who, l, d.k1, d.k2, d.p1, d.p2, iw, ih, l - 1);
+    d.IW = iw; d.IH = ih; d.OW = (iw + 2 * d.p1 - d.k1) / d.s1 + 1; d.OH = (ih + 2 * d.p2 - d.k2) / d.s2 + 1;
+    yfeat[l] = (int64_t)d.OW * d.OH * d.cout; int ow = d.OW, oh = d.OH;
+    if (s.kind != CONV_POOL_NONE) {
+      if (s.kind != CONV_POOL_MAX && s.kind != CONV_POOL_MEAN) return crux_fail(c, CRUX_EINVAL, "%s: layer %d: pool kind %d; 0 none, 1 max, 2 mean", who, l, s.kind);
+      const bool pos = s.k1 >= 1 && s.k2 >= 1 && s.stride1 >= 1 && s.stride2 >= 1 && s.pad1 >= 0 && s.pad2 >= 0;
+      if (pos && s.kind == CONV_POOL_MAX && (int64_t)s.k1 * s.k2 > 256)
+        return crux_fail(c, CRUX_EUNSUP, "%s: layer %d: MaxPool((%d, %d)): a window of more than 256 elements is not supported (the chosen offset is kept in one byte)", who, l, s.k1, s.k2);
+      if (!pos || s.pad1 >= s.k1 || s.pad2 >= s.k2 || s.k1 > ow + 2 * s.pad1 || s.k2 > oh + 2 * s.pad2)
+        return crux_fail(c, CRUX_EINVAL, "%s: layer %d: %s((%d, %d), stride (%d, %d), pad (%d, %d)) does not fit the layer's %d x %d output (pad < window <= extent + 2 pad)", who, l,
+                         s.kind == CONV_POOL_MAX ? "MaxPool" : "MeanPool", s.k1, s.k2, s.stride1, s.stride2, s.pad1, s.pad2, ow, oh);
+      ConvPoolDesc& q = pl[l]; q.kind = s.kind; q.k1 = s.k1; q.k2 = s.k2; q.s1 = s.stride1; q.s2 = s.stride2; q.p1 = s.pad1; q.p2 = s.pad2; q.IW = ow; q.IH = oh; q.C = d.cout; q.act = d.act;
+      q.PW = (ow + 2 * s.pad1 - s.k1) / s.stride1 + 1; q.PH = (oh + 2 * s.pad2 - s.k2) / s.stride2 + 1; ow = q.PW; oh = q.PH;
+    }
+    feat[l + 1] = (int64_t)ow * oh * d.cout;
+    if (yfeat[l] > maxfeat) maxfeat = yfeat[l];
+    if (feat[l + 1] > maxfeat) maxfeat = feat[l + 1];
+    ly[l] = d; iw = ow; ih = oh;
+  }
+  if (v->ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(v->ws); v->ws = nullptr; v->ws_B = 0; }      // sized for the old extents
+  for (int l = 0; l < v->L; ++l) { v->ly[l] = ly[l]; v->pl[l] = pl[l]; v->yfeat[l] = yfeat[l]; v->feat[l + 1] = feat[l + 1]; }
+  v->maxfeat = maxfeat; return CRUX_OK;
 }
 int64_t crux_conv_n_params(const crux_conv* v) { return v ? v->n_params : 0; }
 int64_t crux_conv_out_features(const crux_conv* v) { return v ? v->feat[v->L] : 0; }

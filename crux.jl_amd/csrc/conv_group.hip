@@ -201,13 +201,15 @@ static int32_t conv_forward_group_ws(const char* who, crux_conv* const* v, crux_
   for (int m = 0; m < M; ++m) { rc = conv_ensure_ws(v[m], B); if (rc) return rc; }
   for (int l = 0; l < v[0]->L; ++l) {
     ConvGroup t{}; t.d = v[0]->ly[l]; t.B = (int32_t)B; t.M = M; t.xscale = l == 0 ? v[0]->scale : 1.f; bool vec = true;
-    for (int m = 0; m < M; ++m) { t.w[m] = p[m]->p + t.d.woff; t.bias[m] = p[m]->p + t.d.boff; t.x[m] = l == 0 ? d_x : conv_act(v[m], l); t.y[m] = conv_act(v[m], l + 1);
+    for (int m = 0; m < M; ++m) { t.w[m] = p[m]->p + t.d.woff; t.bias[m] = p[m]->p + t.d.boff; t.x[m] = l == 0 ? d_x : conv_act(v[m], l); t.y[m] = conv_layer_y(v[m], l);
       vec = vec && conv_fwd_vec(t.d, t.w[m], t.x[m]); }      // one form for all members: the bits do not depend on it
     const int64_t tiles = (int64_t)((t.d.cout + 15) >> 4) * ((B * t.d.OW * t.d.OH + 15) >> 4);
     const dim3 grid((unsigned)((tiles + 3) / 4), l == 0 ? (unsigned)((M + CONV_GROUP_G - 1) / CONV_GROUP_G) : (unsigned)M), block(256);
     if (l == 0) { if (vec) hipLaunchKernelGGL((k_conv_fwd_g<true, CONV_GROUP_G>), grid, block, 0, c->stream, t); else hipLaunchKernelGGL((k_conv_fwd_g<false, CONV_GROUP_G>), grid, block, 0, c->stream, t); }
     else if (vec) hipLaunchKernelGGL((k_conv_fwd_gm<true>), grid, block, 0, c->stream, t);
     else hipLaunchKernelGGL((k_conv_fwd_gm<false>), grid, block, 0, c->stream, t);
+    if (v[0]->pl[l].kind) { ConvPoolGroup g{}; for (int m = 0; m < M; ++m) conv_pool_member(g, m, v[m], l, B, nullptr, nullptr);
+      conv_pool_launch_fwd(c->stream, g, M); }
   }
   return crux_launch_check(c, "k_conv_fwd (group)");
 }
@@ -222,7 +224,11 @@ static int32_t conv_backward_group_ws(const char* who, crux_conv* const* v, crux
   // the two delta buffers of each workspace take turns, in the same order for every member (conv_backward_ws)
   const float* dcur[CRUX_GROUP_MAX]; for (int m = 0; m < M; ++m) dcur[m] = d_dy[m];
   int nxt = L + 1, spare = L + 2;
-  if (v[0]->ly[L - 1].act != CRUX_ACT_IDENTITY) {
+  if (v[0]->pl[L - 1].kind) {
+    ConvPoolGroup g{}; for (int m = 0; m < M; ++m) { conv_pool_member(g, m, v[m], L - 1, B, dcur[m], conv_act(v[m], nxt)); dcur[m] = g.dz[m]; }
+    conv_pool_launch_bwd(c->stream, g, M);
+    const int s = nxt; nxt = spare; spare = s;
+  } else if (v[0]->ly[L - 1].act != CRUX_ACT_IDENTITY) {
     const int64_t cnt = v[0]->feat[L] * B; const unsigned bpm = (unsigned)((cnt + 255) / 256);
     ActGradGroup a{};
     for (int m = 0; m < M; ++m) { a.dy[m] = dcur[m]; a.y[m] = conv_act(v[m], L); a.dz[m] = conv_act(v[m], nxt); dcur[m] = a.dz[m]; }
@@ -240,10 +246,16 @@ static int32_t conv_backward_group_ws(const char* who, crux_conv* const* v, crux
     hipLaunchKernelGGL(k_conv_wgrad_combine_g, dim3((unsigned)((per + 255) / 256), (unsigned)M), dim3(256), 0, c->stream, cg, per, nch, gscale);
     if (l > 0) {
       const int64_t tiles = (int64_t)((d.cin + 15) >> 4) * ((B * d.IW * d.IH + 15) >> 4);
+      const bool pooled = v[0]->pl[l - 1].kind != 0;      // conv_backward_ws: the data gradient writes dP_{l-1} as it is (conv_group_member's scale is 1), k_pool_bwd applies act'
       t.act_prev = v[0]->ly[l - 1].act;
-      for (int m = 0; m < M; ++m) { t.dx[m] = conv_act(v[m], nxt); t.ysrc[m] = t.x[m]; dcur[m] = t.dx[m]; }
+      for (int m = 0; m < M; ++m) { t.dx[m] = conv_act(v[m], nxt); t.ysrc[m] = pooled ? nullptr : t.x[m]; dcur[m] = t.dx[m]; }
       hipLaunchKernelGGL(k_conv_dgrad_gm, dim3((unsigned)((tiles + 3) / 4), (unsigned)M), dim3(256), 0, c->stream, t);
-      const int s = nxt; nxt = spare; spare = s;
+      int s = nxt; nxt = spare; spare = s;
+      if (pooled) {
+        ConvPoolGroup g{}; for (int m = 0; m < M; ++m) { conv_pool_member(g, m, v[m], l - 1, B, dcur[m], conv_act(v[m], nxt)); dcur[m] = g.dz[m]; }
+        conv_pool_launch_bwd(c->stream, g, M);
+        s = nxt; nxt = spare; spare = s;
+      }
     }
   }
   return crux_launch_check(c, "conv backward (group)");

@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256) void k_conv_wgrad2(const ConvPair p) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------------------------
 static bool conv_same_desc(const crux_conv* a, const crux_conv* b) {
-  return a->L == b->L && a->W == b->W && a->H == b->H && a->C == b->C && a->scale == b->scale && memcmp(a->ly, b->ly, sizeof(ConvLayerDesc) * (size_t)a->L) == 0;
+  return a->L == b->L && a->W == b->W && a->H == b->H && a->C == b->C && a->scale == b->scale && memcmp(a->ly, b->ly, sizeof(ConvLayerDesc) * (size_t)a->L) == 0 &&
+         memcmp(a->pl, b->pl, sizeof(ConvPoolDesc) * (size_t)a->L) == 0;      // "equal tables" includes the pooling entries
 }
 static int32_t conv_pair_members(const char* who, crux_conv* const v[2], crux_mlp* const p[2], int64_t B) {
   if (!v[0] || !v[1] || !p[0] || !p[1]) return CRUX_EINVAL;
@@ -145,12 +146,14 @@ static int32_t conv_forward_pair_ws(const char* who, crux_conv* const v[2], crux
   for (int l = 0; l < v[0]->L; ++l) {
     ConvPair q{}; bool vec = true;
     for (int m = 0; m < 2; ++m) { ConvArgs& a = q.m[m]; a.d = v[m]->ly[l]; a.B = (int32_t)B; a.w = p[m]->p + a.d.woff; a.bias = p[m]->p + a.d.boff; a.x = l == 0 ? d_x : conv_act(v[m], l); a.xscale = l == 0 ? v[m]->scale : 1.f;
-      a.y = conv_act(v[m], l + 1); vec = vec && conv_fwd_vec(a.d, a.w, a.x); }      // one form for both members: the bits do not depend on it
+      a.y = conv_layer_y(v[m], l); vec = vec && conv_fwd_vec(a.d, a.w, a.x); }      // one form for both members: the bits do not depend on it
     const int64_t tiles = (int64_t)((q.m[0].d.cout + 15) >> 4) * ((B * q.m[0].d.OW * q.m[0].d.OH + 15) >> 4);
     const dim3 grid((unsigned)((tiles + 3) / 4), l == 0 ? 1u : 2u), block(256);
     if (l == 0) { if (vec) hipLaunchKernelGGL((k_conv_fwd2<true>), grid, block, 0, c->stream, q); else hipLaunchKernelGGL((k_conv_fwd2<false>), grid, block, 0, c->stream, q); }
     else if (vec) hipLaunchKernelGGL((k_conv_fwd_m<true>), grid, block, 0, c->stream, q);
     else hipLaunchKernelGGL((k_conv_fwd_m<false>), grid, block, 0, c->stream, q);
+    if (v[0]->pl[l].kind) { ConvPoolGroup t{}; for (int m = 0; m < 2; ++m) conv_pool_member(t, m, v[m], l, B, nullptr, nullptr);
+      conv_pool_launch_fwd(c->stream, t, 2); }
   }
   return crux_launch_check(c, "k_conv_fwd (pair)");
 }
@@ -162,7 +165,11 @@ static int32_t conv_backward_pair_ws(const char* who, crux_conv* const v[2], cru
   for (int m = 0; m < 2; ++m) if (!v[m]->ws || v[m]->ws_B < B) return crux_fail(c, CRUX_EINVAL, "%s: no cached forward pass for this batch", who);
   // the two delta buffers of each workspace take turns, in the same order for both members (conv_backward_ws)
   const float* dcur[2] = {d_dy[0], d_dy[1]}; int nxt = L + 1, spare = L + 2;
-  if (v[0]->ly[L - 1].act != CRUX_ACT_IDENTITY) {
+  if (v[0]->pl[L - 1].kind) {
+    ConvPoolGroup t{}; for (int m = 0; m < 2; ++m) { conv_pool_member(t, m, v[m], L - 1, B, d_dy[m], conv_act(v[m], nxt)); dcur[m] = t.dz[m]; }
+    conv_pool_launch_bwd(c->stream, t, 2);
+    const int s = nxt; nxt = spare; spare = s;
+  } else if (v[0]->ly[L - 1].act != CRUX_ACT_IDENTITY) {
     const int64_t cnt = v[0]->feat[L] * B;
     for (int m = 0; m < 2; ++m) { crux_launch<ActGradOp>((unsigned)((cnt + 255) / 256), 256, c->stream, d_dy[m], (const float*)conv_act(v[m], L), (int)v[m]->ly[L - 1].act, cnt, conv_act(v[m], nxt)); dcur[m] = conv_act(v[m], nxt); }
     const int t = nxt; nxt = spare; spare = t;
@@ -179,9 +186,15 @@ static int32_t conv_backward_pair_ws(const char* who, crux_conv* const v[2], cru
     }
     const int64_t tiles = (int64_t)((d.cin + 15) >> 4) * ((B * d.IW * d.IH + 15) >> 4);
     if (l > 0) {
-      for (int m = 0; m < 2; ++m) { ConvArgs& a = q.m[m]; a.dx = conv_act(v[m], nxt); a.ysrc = a.x; a.act_prev = v[m]->ly[l - 1].act; a.dxscale = v[m]->scale; dcur[m] = a.dx; }
+      const bool pooled = v[0]->pl[l - 1].kind != 0;      // conv_backward_ws: the data gradient writes dP_{l-1} as it is, k_pool_bwd applies act' of Y_{l-1}
+      for (int m = 0; m < 2; ++m) { ConvArgs& a = q.m[m]; a.dx = conv_act(v[m], nxt); a.ysrc = pooled ? nullptr : a.x; a.act_prev = v[m]->ly[l - 1].act; a.dxscale = pooled ? 1.f : v[m]->scale; dcur[m] = a.dx; }
       hipLaunchKernelGGL(k_conv_dgrad_m, dim3((unsigned)((tiles + 3) / 4), 2u), dim3(256), 0, c->stream, q);
-      const int t = nxt; nxt = spare; spare = t;
+      int t = nxt; nxt = spare; spare = t;
+      if (pooled) {
+        ConvPoolGroup g{}; for (int m = 0; m < 2; ++m) { conv_pool_member(g, m, v[m], l - 1, B, dcur[m], conv_act(v[m], nxt)); dcur[m] = g.dz[m]; }
+        conv_pool_launch_bwd(c->stream, g, 2);
+        t = nxt; nxt = spare; spare = t;
+      }
     } else for (int m = 0; m < 2; ++m) if (d_dx[m]) {      // the input gradient is asked of each member separately (the solver asks for none)
       ConvArgs& a = q.m[m]; a.dx = d_dx[m]; a.ysrc = nullptr; a.act_prev = CRUX_ACT_IDENTITY; a.dxscale = v[m]->scale;
       hipLaunchKernelGGL(k_conv_dgrad, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, c->stream, a);

@@ -65,7 +65,8 @@ class _Ensemble:
         if self.kind == "gauss" and chains[0].dims[-1] % 2:
             raise ValueError("DeepEnsemble: the output width %d is odd (mean and variance halves)" % chains[0].dims[-1])
         if self.conv is not None:
-            key = lambda c: (c.W, c.H, c.C, c.scale, [(l.k, l.cin, l.cout, l.act, l.stride, l.pad) for l in c.convs])      # noqa: E731
+            key = lambda c: (c.W, c.H, c.C, c.scale, [(l.k, l.cin, l.cout, l.act, l.stride, l.pad) for l in c.convs],
+                             [q and (q.kind, q.k, q.stride, q.pad) for q in c.pools])      # noqa: E731
             for m, c in enumerate(convs):
                 if key(c) != key(self.conv):
                     raise NotImplementedError("%s: member %d's conv table differs from member 0's (the grouped conv passes need one layer table)" % (type(self).__name__, m))

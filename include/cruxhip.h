@@ -1046,6 +1046,18 @@ typedef struct {
 } crux_conv_layer;
 int32_t crux_conv_create(crux_ctx* ctx, int32_t W, int32_t H, int32_t C, float in_scale, int32_t n_layers, const crux_conv_layer* layers, crux_conv** out);
 int32_t crux_conv_destroy(crux_conv* conv);
+/* Pooling layers in the trunk (csrc/conv_pool.hip): MaxPool((k1, k2); stride, pad) or MeanPool behind conv layer l, at most one per layer, pools[l] for every layer of
+ * the handle (kind 0: none). Flux / NNlib semantics, which are torch's defaults: the layer's output is P_l = pool(act(conv)); PW = floor((OW + 2 pad1 - k1) / stride1) + 1
+ * (likewise PH), trailing rows and columns no window reaches are dropped; pad symmetric per axis, pad < k. Max: padding taps do not take part, a NaN in a window gives NaN,
+ * ties go to the first element in window order (along W fastest). Mean: the window's taps inside the image summed, divided by k1 k2 always (count_include_pad). Reverse
+ * pass: the gradient of a pooled element goes to the chosen element (max) or, divided by k1 k2, to every element of its window (mean); elements no window covers get exactly
+ * 0; no float atomics, bit-reproducible. Called after crux_conv_create: re-derives the extents of every later layer and crux_conv_out_features, drops a workspace that was
+ * already sized; crux_conv_n_params and the parameter layout do not change. Every entry that takes the handle (single, pair, ensemble; the DQN and policy-gradient steps)
+ * then runs the pooled trunk; a pair's or an ensemble's "equal layer tables" include the pools. All kinds 0 returns the handle to a plain trunk.
+ * CRUX_EINVAL, naming the layer: a pool that does not fit its layer's output (pad < window <= extent + 2 pad, stride >= 1), an unknown kind, a later conv layer that no
+ * longer fits its shrunken input. CRUX_EUNSUP: a max window of more than 256 elements (the chosen offset is kept in one byte). A refused call leaves the handle as it was. */
+typedef struct { int32_t kind /* 0 none, 1 max, 2 mean */, k1, k2, stride1, stride2, pad1, pad2; } crux_pool_layer;
+int32_t crux_conv_set_pool(crux_conv* conv, const crux_pool_layer* pools /* one per conv layer */);
 int64_t crux_conv_n_params(const crux_conv* conv);
 int64_t crux_conv_out_features(const crux_conv* conv);
 /* Flux's glorot_uniform for Conv: weights U(+-sqrt(6 / (k1 k2 cin + k1 k2 cout))), zero biases. Draw convention (crux_rng.h, as crux_mlp_init_glorot): weight number n of

@@ -24,7 +24,10 @@ outputs at the same shapes, B = 32 and 128. Writes profiles/conv_gauss_bench.txt
 by member (crux_conv_forward_cached, crux_mlp_forward_cached, crux_mlp_backward with d_dx, crux_conv_backward); and, at the small shape, the whole crux_conv_ensemble_step beside
 those passes plus crux_adam_apply per handle (the baseline has no entry for the loss head, the norms or the gate: it does less; it pays one device-to-device copy of the
 features per member, because crux_mlp_forward_cached reads them from a caller's buffer: both are said in the output lines). The Atari head is a wide handle, which the step
-refuses, so the Atari step is not measured. Writes profiles/conv_ensemble_bench.txt with --save."""
+refuses, so the Atari step is not measured. Writes profiles/conv_ensemble_bench.txt with --save.
+
+--pool: the textbook image network's trunk, 28x28x1 -> Conv((3,3), 1=>8, relu, pad=1) -> MaxPool((2,2)) -> Conv((3,3), 8=>16, relu, pad=1) -> MaxPool((2,2)) -> flatten (784
+features), forward + backward (csrc/conv_pool.hip beside the conv kernels) at B = 32 and 128, beside torch-ROCm eager. Writes profiles/conv_pool_bench.txt with --save."""
 import argparse
 import ctypes as C
 import json
@@ -93,9 +96,56 @@ def torch_atari_step(B, x_host, clip):
     return step, torch.cuda.synchronize
 
 
+def torch_pool(B, x_host):
+    import torch
+    dev = torch.device("cuda")
+    net = torch.nn.Sequential(torch.nn.Conv2d(1, 8, 3, 1, 1), torch.nn.ReLU(), torch.nn.MaxPool2d(2), torch.nn.Conv2d(8, 16, 3, 1, 1), torch.nn.ReLU(), torch.nn.MaxPool2d(2), torch.nn.Flatten()).to(dev)
+    x = torch.tensor(x_host.T.reshape(B, 1, 28, 28).copy(), device=dev); dy = torch.ones(B, 784, device=dev)
+
+    def passes():
+        net.zero_grad(set_to_none=True); net(x * (1.0 / 255.0)).backward(dy)
+    return passes, torch.cuda.synchronize
+
+
+def pool(a, crux, L):
+    ctx = crux.default_context(); rng = np.random.default_rng(0); lines = []
+    spec = crux.Chain(crux.Scale(1.0 / 255.0), crux.Conv((3, 3), 1, 8, "relu", pad=1), crux.MaxPool((2, 2)), crux.Conv((3, 3), 8, 16, "relu", pad=1), crux.MaxPool((2, 2)), crux.flatten,
+                      crux.Dense(784, 10), input=(28, 28, 1)).conv
+    ours = {}
+    for B in (32, 128):
+        x = np.asfortranarray(rng.integers(0, 256, (784, B)).astype(np.float32))
+        t = crux.ConvTrunk(spec, ctx=ctx, seed=1); F = t.spec.out_features
+        d_x, d_dy = ctx.alloc(x.nbytes), ctx.alloc(4 * F * B); ctx.h2d(d_x, x); ctx.h2d(d_dy, np.ones((F, B), np.float32))
+        fwd = lambda: ctx.check(ctx.lib.crux_conv_forward_cached(t.h, t.p.h, d_x, B, None))                                   # noqa: E731
+        bwd = lambda: ctx.check(ctx.lib.crux_conv_backward(t.h, t.p.h, d_x, B, d_dy, 1.0, 1, None))                           # noqa: E731
+        both = lambda: (fwd(), bwd())                                                                                          # noqa: E731
+        ours[B] = (median_window(fwd, ctx.sync, a.n, a.reps), median_window(bwd, ctx.sync, a.n, a.reps), median_window(both, ctx.sync, a.n, a.reps))
+        ctx.free(d_x); ctx.free(d_dy)
+    ctx.sync()
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-child", "--pool", "--n", str(a.n), "--reps", str(a.reps)], capture_output=True, text=True, timeout=300)
+    try:
+        tor = json.loads(child.stdout.strip().splitlines()[-1])
+    except Exception:      # noqa: BLE001
+        tor = None; sys.stderr.write(child.stderr[-2000:])
+    for B in (32, 128):
+        tf, tb, tw = ours[B]
+        tt = "torch eager: not measured (the torch child process failed)" if tor is None else "torch eager forward + backward %.1f us (%.1f .. %.1f); ratio torch / ours %.2f" % (
+            tor["pool%d" % B][0], tor["pool%d" % B][1], tor["pool%d" % B][2], tor["pool%d" % B][0] / tw[0])
+        lines.append("trunk 28x28x1 -> 8@3/1 pad 1 -> MaxPool 2 -> 16@3/1 pad 1 -> MaxPool 2 (784 features)  B %3d: forward (4 launches) %.1f us, backward (7 launches: 2 x k_pool_bwd, "
+                     "2 x (wgrad + combine), 1 dgrad) %.1f us, forward + backward %.1f us (%.1f .. %.1f); %s" % (B, tf[0], tb[0], tw[0], tw[1], tw[2], tt))
+    txt = "# tools/conv_bench.py --pool: one MI355X, f32, median of %d windows of %d calls (min .. max), host clock around synchronised windows\n" % (a.reps, a.n) + "\n".join(lines) + "\n"
+    print(txt)
+    if a.save:
+        open(os.path.join(ROOT, "profiles", "conv_pool_bench.txt"), "w").write(txt)
+
+
 def torch_child(a):
     """the torch figures of both shapes and batch sizes as one JSON line"""
     rng = np.random.default_rng(0); out = {}
+    if a.pool:
+        for B in (32, 128):
+            out["pool%d" % B] = median_window(*torch_pool(B, np.asfortranarray(rng.integers(0, 256, (784, B)).astype(np.float32))), a.n, a.reps)
+        print(json.dumps(out)); return
     if a.atari:
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, 32)).astype(np.float32))
         for clip in (0, 1):
@@ -313,7 +363,7 @@ def ensemble(a, crux, L):
 
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=200); ap.add_argument("--reps", type=int, default=7); ap.add_argument("--save", action="store_true")
-    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--pg-gauss", action="store_true"); ap.add_argument("--ensemble", action="store_true")
+    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--pg-gauss", action="store_true"); ap.add_argument("--ensemble", action="store_true"); ap.add_argument("--pool", action="store_true")
     a = ap.parse_args()
     if a.torch_child:
         return torch_child(a)
@@ -328,6 +378,8 @@ def main():
         return pg_gauss(a, crux, L)
     if a.ensemble:
         return ensemble(a, crux, L)
+    if a.pool:
+        return pool(a, crux, L)
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
     for B in (32, 128):
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
