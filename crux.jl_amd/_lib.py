@@ -243,6 +243,8 @@ SIGNATURES = {
     "crux_conv_backward_pair": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, i32, vp, vp]),
     "crux_conv_pg_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, f32, vp, vp]),
     "crux_conv_pg_step_gauss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, i32, f32, f32, f32, vp, vp]),
+    "crux_conv_bc_step": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, f32, vp]),
+    "crux_conv_bc_loss": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i32, f32, vp]),
     "crux_conv_ensemble_forward": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, i64, vp, vp, vp, vp]),
     "crux_conv_ensemble_logpdf": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, vp, i64, vp]),
     "crux_conv_ensemble_step": (i32, [P(vp), P(vp), P(vp), i32, i32, vp, vp, vp, i64, vp]),

@@ -218,4 +218,55 @@ def CQL(pi, S, D_train, CQL_alpha=1.0, CQL_is_distribution=None, CQL_alpha_thres
     return BatchSAC(pi, S, D_train, a_opt=a_opt, c_opt=c, P=P, param_optimizers=pos, **kw)
 
 
+# --------------------------------------------------------------------------------------------------------------
+# BC for a conv policy: the actor-only BatchSolver over trunk + head (csrc/conv_bc.hip)
+# --------------------------------------------------------------------------------------------------------------
+def _conv_bc_args(pi, p, D, who):
+    """(trunk, trunk parameters, head), the action column's width in rows and in bytes, for a conv policy under one of BC's two losses; everything else refuses by name"""
+    from .core import CustomLoss, DiscreteNetwork, _uses_seam, refuse_conv
+    if isinstance(p.loss, CustomLoss) or p.loss.name not in ("logpdf_bc", "mse_action"):
+        refuse_conv(pi, "%s with %s" % (who, "a CustomLoss" if isinstance(p.loss, CustomLoss) else p.loss.name + "_loss"))
+    if _uses_seam(p):
+        refuse_conv(pi, "%s with a regularizer or an early_stopping function in its TrainingParams" % who)
+    if getattr(p.optimizer, "clip", None) is not None:
+        refuse_conv(pi, "%s with Optimiser(ClipValue, Adam)" % who)
+    gauss = isinstance(pi, GaussianPolicy) and pi.n_extra > 0 and not pi.ascale_or_zero and not getattr(pi, "two_headed", False)
+    if not (isinstance(pi, DiscreteNetwork) or type(pi) is ContinuousNetwork or gauss) or (p.loss.name == "logpdf_bc" and type(pi) is ContinuousNetwork) or (p.loss.name == "mse_action" and isinstance(pi, DiscreteNetwork)):
+        refuse_conv(pi, "%s (%s_loss on a %s: logpdf_bc_loss takes a conv DiscreteNetwork or constant-logSigma GaussianPolicy, mse_action_loss a conv ContinuousNetwork or GaussianPolicy)"
+                    % (who, p.loss.name, "two-headed actor" if getattr(pi, "two_headed", False) else type(pi).__name__))
+    n = len(pi.outputs) if isinstance(pi, DiscreteNetwork) else pi.network.dims[-1]
+    if D.obs_dim != pi.trunk.spec.in_features or D.act_dim != n or (D.act_kind == L.ACTION_DISCRETE) != isinstance(pi, DiscreteNetwork):
+        raise ValueError("%s: the buffer has %d observation and %d action rows, the conv policy takes W H C = %d and %d (%s)" % (
+            who, D.obs_dim, D.act_dim, pi.trunk.spec.in_features, n, "one-hot" if isinstance(pi, DiscreteNetwork) else "Float32"))
+    return (pi.trunk.h, pi.trunk.p.h, pi.head_h), n, (n if isinstance(pi, DiscreteNetwork) else 4 * n)
+
+
+def _conv_bc_epoch(pi, p, P, D):
+    """One epoch of batch_train!(pi, p, P, D) (training.jl:28-55) for a conv policy: shuffle!(D) on the device, then crux_conv_bc_step on each partition of batch_size
+    contiguous rows (the last may be short), reading the buffer's s and a columns in place. The info is the epoch's last minibatch's, as batch_train_ with epochs = 1 leaves it."""
+    from .core import _info_dict
+    h, n, abytes = _conv_bc_args(pi, p, D, "BC")
+    _ensure_opt(pi, p)
+    ctx, N, od = D.ctx, len(D), pi.trunk.spec.in_features
+    shuffle_device_(D, p.shuffle_seed, p.shuffle_counter); p.shuffle_counter += 1
+    ps, pa = D.column_ptr("s"), D.column_ptr("a")
+    raw, nb = np.zeros(L.INFO_N, np.float32), 0
+    for s0 in range(0, N, p.batch_size):
+        B = min(p.batch_size, N - s0)
+        ctx.check(ctx.lib.crux_conv_bc_step(*h, ps + 4 * od * s0, pa + abytes * s0, n, B, L.LOSS[p.loss.name], float(P.get("lambda_e", 0.1)), _vp(raw)))
+        nb += 1
+        if p.max_batches not in (None, np.inf) and nb >= p.max_batches:      # training.jl:45
+            break
+    info = _info_dict(p, raw); info[p.name + "batches_trained"] = nb
+    return info
+
+
+def _conv_bc_loss_value(pi, p, P, D):
+    """loss(pi, P, D) over the whole buffer, forward only (crux_conv_bc_loss in chunks of batch_size rows): the validation error of stop_on_validation_increase"""
+    h, n, _ = _conv_bc_args(pi, p, D, "loss_value")
+    out = np.zeros(3, np.float32)
+    D.ctx.check(D.ctx.lib.crux_conv_bc_loss(*h, D.column_ptr("s"), D.column_ptr("a"), n, len(D), p.batch_size, L.LOSS[p.loss.name], float(P.get("lambda_e", 0.1)), _vp(out)))
+    return float(out[0])
+
+
 __all__ = ["BatchSAC", "CQL", "UniformBox", "cql_alpha_loss", "cql_critic_loss"]

@@ -11,7 +11,8 @@ images (a flattened observation has index w + W (h + H c)), (k1, k2, cin, cout) 
 What takes a conv policy: value / forward, the parameter and optimiser accessors (trunk first, then head: Flux.params order), polyak_average_, copyto_, clone_policy,
 policy_explore on the host seam (a HostMDP: pixel environments live on the host), DQN through solve, and PPO / A2C / REINFORCE for a conv DiscreteNetwork actor or a conv
 GaussianPolicy actor with a constant logSigma (with a conv ContinuousNetwork critic in an ActorCritic: on_policy._conv_policy_gradient_training over csrc/conv_pair.hip and,
-for the Gaussian actor, csrc/conv_gauss.hip; its action / logpdf / entropy take host observations). Everything else refuses it by name (core.refuse_conv); a
+for the Gaussian actor, csrc/conv_gauss.hip; its action / logpdf / entropy take host observations), and BC with logpdf_bc_loss / mse_action_loss for a conv DiscreteNetwork,
+ContinuousNetwork or constant-logSigma GaussianPolicy (batch._conv_bc_epoch and loss_value over csrc/conv_bc.hip). Everything else refuses it by name (core.refuse_conv); a
 SquashedGaussianPolicy or a two-headed GaussianPolicy over a conv chain is refused where it is built."""
 import ctypes as C
 

@@ -669,9 +669,9 @@ def refuse_spectral(pi, who):
 def refuse_conv(pi, who):
     """A conv policy (convolutional trunk + dense head, conv.py) is taken by value / forward, the parameter accessors, polyak_average_, copyto_, clone_policy, policy_explore on
     a HostMDP, DQN, and -- as a conv DiscreteNetwork or constant-logSigma GaussianPolicy actor with (PPO, A2C) a conv ContinuousNetwork critic in an ActorCritic -- PPO, A2C
-    and REINFORCE (on_policy.py). The
+    and REINFORCE (on_policy.py), and BC with logpdf_bc_loss / mse_action_loss (imitation.BC, batch._conv_bc_epoch). The
     entry points that take a network call this and refuse by their own name before any device call: the other solver constructors (by name: LagrangePPO, SAC, SoftQ, DDPG,
-    TD3; BC, the GAIL family and the rest through PolicyParams), PPO / A2C / REINFORCE for an actor / critic pair of which only one is conv (a squashed or two-headed conv
+    TD3; the GAIL family and the rest through PolicyParams; BC for what its conv path does not take), PPO / A2C / REINFORCE for an actor / critic pair of which only one is conv (a squashed or two-headed conv
     Gaussian actor is refused where it is built), a
     Sampler on a device MDP, train! / batch_train!, fill_gae!, the GAIL discriminator steps and reward, the replica-group and multi-seed learners, EWC, and
     Optimiser(ClipValue, Adam) outside DQN (refuse_chain_params). Behind them stands NetworkPolicy.h itself: a conv policy has no whole-network handle, so any other path that reads
@@ -680,7 +680,8 @@ def refuse_conv(pi, who):
     for q in ([] if pi is None else _leaves(pi)):
         if getattr(q, "is_conv", None):
             raise NotImplementedError("%s: a policy with a convolutional trunk (Conv layers in its Chain) is implemented on a HostMDP for DQN and for PPO / A2C / REINFORCE "
-                                      "(a conv DiscreteNetwork or constant-logSigma GaussianPolicy actor; PPO and A2C with a conv ContinuousNetwork critic, in an ActorCritic) only; "
+                                      "(a conv DiscreteNetwork or constant-logSigma GaussianPolicy actor; PPO and A2C with a conv ContinuousNetwork critic, in an ActorCritic) "
+                                      "and for BC (logpdf_bc_loss / mse_action_loss on one conv network) only; "
                                       "this path would treat the dense head as the whole network" % who)
 
 

@@ -429,10 +429,11 @@ struct GailRewardOp { static constexpr int max_threads = 256; static __device__ 
 } };
 
 // partials: the squared norm arrives as Sumsq2Op's per-block partials in d_ssq[1..] (finalised by the info op into d_ssq[0]); false: d_ssq[0] was written directly
-static int32_t adam_gated(crux_mlp* n, const double* d_ssq, int32_t* d_status, bool partials = true, hipStream_t strm = nullptr) {
+// lead (>= 0): only the first `lead` parameters are updated (conv_bc.hip: the layers of a GaussianPolicy handle under mse_action_loss, whose logSigma extras get no gradient)
+static int32_t adam_gated(crux_mlp* n, const double* d_ssq, int32_t* d_status, bool partials = true, hipStream_t strm = nullptr, int64_t lead = -1) {
   crux_ctx* c = n->ctx; if (!strm) strm = c->stream;
   if (!n->has_adam) return crux_fail(c, CRUX_EINVAL, "train!: crux_adam_init was not called on this handle");
-  const int64_t cnt = n->nd.n_params;
+  const int64_t cnt = lead >= 0 ? lead : n->nd.n_params;
   if (crux_exec_recording(c)) {      // fused sequence: at most one round of blocks, beta powers advanced by a one-thread op of the next phase (no device-scope fence per block)
     CRUX_NO_CLIP("adam_gated inside a recorded sequence (crux_exec_recording)", n);
     const unsigned nbk = (unsigned)((cnt + 255) / 256);

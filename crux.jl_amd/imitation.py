@@ -278,6 +278,9 @@ mse_action_loss, logpdf_bc_loss = _Loss("mse_action"), _Loss("logpdf_bc")   # sr
 
 def loss_value(pi, p, P, D):
     """loss(pi, P, D) evaluated on the whole buffer, no update (the validation error of stop_on_validation_increase, src/utils.jl:59-72)."""
+    if getattr(pi, "is_conv", None):      # trunk + head, forward only, in chunks of a_opt.batch_size rows (csrc/conv_bc.hip); other losses refuse by name there
+        from .batch import _conv_bc_loss_value
+        return _conv_bc_loss_value(pi, p, P, D)
     refuse_conv(pi, "loss_value")
     _ensure_opt(pi, p)
     cfg = _train_cfg(pi, p, P); n = len(D)
@@ -313,10 +316,13 @@ def _solve_batch(solver, mdp=None):
         return _solve_batch_ac(solver, mdp)
     A, p = actor(solver.agent.pi), solver.a_opt
     e_total, first = p.epochs, solver.epoch
+    train_epoch = batch_train_
+    if getattr(A, "is_conv", None):      # a conv policy: the same epoch over trunk + head (batch._conv_bc_epoch, csrc/conv_bc.hip)
+        from .batch import _conv_bc_epoch as train_epoch
     try:
         p.epochs = 1
         for solver.epoch in range(first, first + e_total + 1):
-            info = batch_train_(A, p, solver.P, solver.D_train)
+            info = train_epoch(A, p, solver.P, solver.D_train)
             solver.history.append({k: v for k, v in info.items() if not k.startswith("_")})
             if solver.early_stopping and solver.early_stopping(solver.history):
                 break
@@ -342,6 +348,10 @@ def BC(pi, S, D_demo, normalize_demo=True, loss=None, validation_fraction=0.3, w
     """BC(; pi, S, D_demo, normalize_demo, loss, validation_fraction=0.3, window=100, lambda_e=1f-3, opt) (src/model_free/il/bc.jl:37-70):
     mse_action_loss for a ContinuousNetwork, logpdf_bc_loss otherwise; the demonstrations are normalised, shuffled once and split into
     training / validation parts; early stopping on the validation error. shuffle_perm: optional 1-based permutation for the initial shuffle!."""
+    conv = any(getattr(q, "is_conv", None) for q in _leaves(pi))      # a conv DiscreteNetwork / ContinuousNetwork / constant-logSigma GaussianPolicy: batch._conv_bc_epoch
+    if conv and (not getattr(pi, "is_conv", None) or getattr(pi, "two_headed", False) or kw.get("early_stopping") is not None):
+        refuse_conv(pi, "BC (%s)" % ("a two-headed actor" if getattr(pi, "two_headed", False) else "an early_stopping function of the caller's" if kw.get("early_stopping") is not None
+                                     else "the policy must be one conv network, not a pair"))
     require_two_headed_opt_in(actor(pi), "BC", two_headed)      # (two_headed=True: a two-headed Gaussian actor with logpdf_bc_loss; without the keyword it is refused as before -- the keyword's only purpose, see core.require_two_headed_opt_in)
     loss = loss or (mse_action_loss if type(pi) is ContinuousNetwork else logpdf_bc_loss)
     if getattr(actor(pi), "two_headed", False) and (isinstance(loss, CustomLoss) or loss.name != "logpdf_bc"):      # a two-headed actor: logpdf_bc_loss only (k_pg_head_sigma)
@@ -358,5 +368,10 @@ def BC(pi, S, D_demo, normalize_demo=True, loss=None, validation_fraction=0.3, w
     P = {"lambda_e": lambda_e, "lambda_p": 1.0}
     o = dict(opt or {}); o.setdefault("name", "")
     p = TrainingParams(loss=loss, **o)
-    return BatchSolver(agent=PolicyParams(pi), S=S, D_train=D_train, a_opt=p, P=P,
-                       early_stopping=stop_on_validation_increase(pi, P, D_val, p, window=window), **kw)
+    if conv:      # every refusal of the conv path by BC's name, before the solver exists
+        from .batch import _conv_bc_args
+        _conv_bc_args(pi, p, D_train, "BC")
+    sv = BatchSolver(agent=PolicyParams(pi, conv_ok=conv), S=S, D_train=D_train, a_opt=p, P=P,
+                     early_stopping=stop_on_validation_increase(pi, P, D_val, p, window=window), **kw)
+    sv.D_val = D_val      # the validation split the early stopping evaluates (loss_value(pi, a_opt, P, D_val))
+    return sv

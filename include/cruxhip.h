@@ -1114,6 +1114,26 @@ int32_t crux_conv_pg_step(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp
 int32_t crux_conv_pg_step_gauss(crux_conv* actor_conv, crux_mlp* actor_trunk, crux_mlp* actor_head, crux_conv* critic_conv, crux_mlp* critic_trunk, crux_mlp* critic_head,
                                 const float* d_s, const float* d_a, int32_t act_dim, const float* d_adv, const float* d_ret, const float* d_old_logprob, int64_t B,
                                 int32_t loss, float eps_clip, float lambda_p, float lambda_e, float* info_out, float* critic_out);
+/* Behaviour cloning from pixels (src/model_free/il/bc.jl; csrc/conv_bc.hip): one trunk + dense head (the head may be a wide handle), no critic. loss is
+ * CRUX_LOSS_LOGPDF_BC or CRUX_LOSS_MSE_ACTION; the head handle selects the form:
+ *   logpdf_bc, no extras        categorical (conv DiscreteNetwork): d_a [n x B] one-hot bytes, loss = lambda_e (-mean H) - mean log(sum p a), H with the reference's eps
+ *   logpdf_bc, ad extras        Gaussian (conv GaussianPolicy, constant logSigma, ad <= 32): d_a [ad x B] Float32, loss = -mean logpdf - lambda_e (1.4189385 + sum logSigma);
+ *                               d(loss)/d(logSigma) as Float64 block sums added in block order, into the head handle's extras gradient
+ *   mse_action                  Flux.mse(mu, a) over all ad B elements (conv ContinuousNetwork; a GaussianPolicy handle, whose action is mu: its logSigma gradient is
+ *                               written as zero and Adam stops in front of the extras, so logSigma and its moments come out bit-unchanged)
+ * crux_conv_bc_step: one minibatch of train! -- trunk forward, head forward, one column-head launch (one thread per column, Float64 block partials, a finishing launch adds
+ * them in block order), head backward, trunk backward (parameter gradients only), ONE norm over trunk and head, ONE gate over both Adam updates (crux_adam_init on both
+ * first): a NaN norm leaves trunk, head, extras and Adam state untouched and returns CRUX_ENAN. One host synchronisation. info_out (host [CRUX_INFO_N]): LOSS, GRAD_NORM
+ * and for logpdf_bc ENTROPY and, in the KL slot, -mean logpdf (where crux_batch_train leaves info[:logpdf]). Two identical calls give identical bits.
+ * crux_conv_bc_loss: the same loss over n rows, forward only, in chunks of at most `chunk` rows (the workspaces are sized for a chunk; the last may be short, n < chunk is
+ * legal). No parameter, gradient or Adam state changes. Every chunk's block partials go to a running offset of one array, one finishing launch adds them in index order
+ * and divides by n; one synchronisation, one read-back. out (host [3]): loss, entropy, -mean logpdf (the last two 0 for mse_action).
+ * CRUX_EUNSUP, before anything is enqueued: a call while the fused executor records, DenseSN layers in the head, a two-headed (crux_mlp_set_sigma_head) or squashed head,
+ * a head whose input is not flatten's width, ad > 32 extras, and (step) a ClipValue prelude on either handle. CRUX_EINVAL: another loss, a head whose last width is not
+ * ad_or_nout or whose extras are neither 0 nor ad_or_nout.                                                                                                              */
+int32_t crux_conv_bc_step(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, const float* d_s, const void* d_a, int32_t ad_or_nout, int64_t B, int32_t loss, float lambda_e, float* info_out);
+int32_t crux_conv_bc_loss(crux_conv* conv, crux_mlp* trunk, crux_mlp* head, const float* d_s, const void* d_a, int32_t ad_or_nout, int64_t n, int64_t chunk, int32_t loss, float lambda_e,
+                          float* out);
 /* DeepEnsemble / DeepClassificationEnsemble whose members are conv chains (src/extras/deep_ensembles.jl:3, :41: generator() may return any Flux chain; here
  * Chain([x -> c x,] Conv..., flatten, Dense...)): the counterparts of crux_ensemble_forward / _logpdf / _step / _train / _passes. Member m is convs[m] (its layer table and
  * workspace), trunks[m] (its bare-vector parameter handle) and heads[m] (the dense layers behind flatten); M in 1..16. d_x is [W H C x B]; kinds, outputs, the info row

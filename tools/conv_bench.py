@@ -27,7 +27,10 @@ features per member, because crux_mlp_forward_cached reads them from a caller's 
 refuses, so the Atari step is not measured. Writes profiles/conv_ensemble_bench.txt with --save.
 
 --pool: the textbook image network's trunk, 28x28x1 -> Conv((3,3), 1=>8, relu, pad=1) -> MaxPool((2,2)) -> Conv((3,3), 8=>16, relu, pad=1) -> MaxPool((2,2)) -> flatten (784
-features), forward + backward (csrc/conv_pool.hip beside the conv kernels) at B = 32 and 128, beside torch-ROCm eager. Writes profiles/conv_pool_bench.txt with --save."""
+features), forward + backward (csrc/conv_pool.hip beside the conv kernels) at B = 32 and 128, beside torch-ROCm eager. Writes profiles/conv_pool_bench.txt with --save.
+
+--bc: behaviour cloning at the Atari trunk with a 2048-256-6 head (csrc/conv_bc.hip), B = 32 and 128: crux_conv_bc_step (logpdf_bc_loss, categorical) and crux_conv_bc_loss over
+1024 rows in chunks of B, beside the same step and the same forward-only loss (no_grad, the same chunks, one .item()) in torch-ROCm eager. Writes profiles/conv_bc_bench.txt with --save."""
 import argparse
 import ctypes as C
 import json
@@ -146,6 +149,12 @@ def torch_child(a):
         for B in (32, 128):
             out["pool%d" % B] = median_window(*torch_pool(B, np.asfortranarray(rng.integers(0, 256, (784, B)).astype(np.float32))), a.n, a.reps)
         print(json.dumps(out)); return
+    if a.bc:
+        x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, 1024)).astype(np.float32)); act = rng.integers(0, 6, 1024)
+        for B in (32, 128):
+            step, loss_pass, sync = torch_bc(B, x, act)
+            out["step%d" % B] = median_window(step, sync, a.n, a.reps); out["loss%d" % B] = median_window(loss_pass, sync, max(a.n // 10, 1), a.reps)
+        print(json.dumps(out)); return
     if a.atari:
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, 32)).astype(np.float32))
         for clip in (0, 1):
@@ -237,6 +246,60 @@ def torch_pg(B, x_host):
         oa.zero_grad(set_to_none=True); ov.zero_grad(set_to_none=True); xs = x * (1.0 / 255.0)
         A[:5](xs).backward(dy); V[:5](xs).backward(dy)
     return step, passes, torch.cuda.synchronize
+
+
+def torch_bc(B, x_host, a_host):
+    """crux_conv_bc_step restated (logpdf_bc_loss on a categorical head, the norm, one Adam step, the loss read by the host), and the forward-only loss over all rows in chunks of B"""
+    import torch
+    dev = torch.device("cuda")
+    net = torch.nn.Sequential(torch.nn.Conv2d(4, 16, 8, 4), torch.nn.ReLU(), torch.nn.Conv2d(16, 32, 4, 2), torch.nn.ReLU(), torch.nn.Flatten(), torch.nn.Linear(2048, 256), torch.nn.ReLU(),
+                              torch.nn.Linear(256, 6)).to(dev)
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    x = torch.tensor(x_host.T.reshape(-1, 4, 80, 80).copy(), device=dev); act = torch.tensor(a_host, dtype=torch.long, device=dev)
+
+    def sums(xs, ac):
+        p = torch.softmax(net(xs * (1.0 / 255.0)), 1)
+        return torch.log(p.gather(1, ac[:, None])[:, 0]).sum(), (p * torch.log(p + 1.1920929e-07)).sum()
+
+    def step():
+        opt.zero_grad(set_to_none=True); lp, nh = sums(x[:B], act[:B])
+        loss = (-lp + 1e-3 * nh) / B; loss.backward()
+        torch.nn.utils.clip_grad_norm_(net.parameters(), float("inf")); opt.step(); return loss.item()
+
+    def loss_pass():
+        with torch.no_grad():
+            tot = 0.0
+            for r0 in range(0, x.shape[0], B):
+                lp, nh = sums(x[r0:r0 + B], act[r0:r0 + B]); tot = tot + (-lp + 1e-3 * nh)
+            return (tot / x.shape[0]).item()
+    return step, loss_pass, torch.cuda.synchronize
+
+
+def bc(a, crux, L):
+    """--bc: crux_conv_bc_step and crux_conv_bc_loss over 1024 rows beside torch eager; Atari trunk, 2048-256-6 head"""
+    ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours, N = [], {}, 1024; vp = lambda v: v.ctypes.data_as(C.c_void_p); f = lambda t: "%.1f us (%.1f .. %.1f)" % tuple(t)      # noqa: E731
+    x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, N)).astype(np.float32)); act = rng.integers(0, 6, N)
+    d_x, d_a = ctx.alloc(x.nbytes), ctx.alloc(6 * N); ctx.h2d(d_x, x); ctx.h2d(d_a, np.asfortranarray(np.eye(6, dtype=np.uint8)[:, act]))
+    for B in (32, 128):
+        pi = crux.DiscreteNetwork(chain(32, 256), list(range(6)), seed=2, ctx=ctx); pi.attach_optimizer(crux.Adam(np.float32(1e-3)))
+        h = (pi.trunk.h, pi.trunk.p.h, pi.head_h); raw, out = np.zeros(L.INFO_N, np.float32), np.zeros(3, np.float32)
+        step = lambda: ctx.check(ctx.lib.crux_conv_bc_step(*h, d_x, d_a, 6, B, L.LOSS["logpdf_bc"], 1e-3, vp(raw)))                 # noqa: E731
+        loss = lambda: ctx.check(ctx.lib.crux_conv_bc_loss(*h, d_x, d_a, 6, N, B, L.LOSS["logpdf_bc"], 1e-3, vp(out)))              # noqa: E731
+        ours[B] = (median_window(step, ctx.sync, a.n, a.reps), median_window(loss, ctx.sync, max(a.n // 10, 1), a.reps))
+    ctx.free(d_x); ctx.free(d_a); ctx.sync()
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-child", "--bc", "--n", str(a.n), "--reps", str(a.reps)], capture_output=True, text=True, timeout=300)
+    try:
+        tor = json.loads(child.stdout.strip().splitlines()[-1])
+    except Exception:      # noqa: BLE001
+        tor = None; sys.stderr.write(child.stderr[-2000:])
+    for B in (32, 128):
+        for k, name, o in (("step", "crux_conv_bc_step (logpdf_bc_loss, 2048-256-6 head)", ours[B][0]), ("loss", "crux_conv_bc_loss over %d rows in chunks of %d" % (N, B), ours[B][1])):
+            tt = "torch eager: not measured (the torch child process failed)" if tor is None else "torch eager %s; ratio torch / ours %.2f" % (f(tor["%s%d" % (k, B)]), tor["%s%d" % (k, B)][0] / o[0])
+            lines.append("%s, B %3d: %s; %s" % (name, B, f(o), tt))
+    txt = "# tools/conv_bench.py --bc: one MI355X, f32, median of %d windows of %d calls (%d for the loss pass) (min .. max), host clock around synchronised windows\n" % (a.reps, a.n, max(a.n // 10, 1)) + "\n".join(lines) + "\n"
+    print(txt)
+    if a.save:
+        open(os.path.join(ROOT, "profiles", "conv_bc_bench.txt"), "w").write(txt)
 
 
 def pg(a, crux, L):
@@ -363,7 +426,7 @@ def ensemble(a, crux, L):
 
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--n", type=int, default=200); ap.add_argument("--reps", type=int, default=7); ap.add_argument("--save", action="store_true")
-    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--pg-gauss", action="store_true"); ap.add_argument("--ensemble", action="store_true"); ap.add_argument("--pool", action="store_true")
+    ap.add_argument("--torch-child", action="store_true"); ap.add_argument("--atari", action="store_true"); ap.add_argument("--pg", action="store_true"); ap.add_argument("--pg-gauss", action="store_true"); ap.add_argument("--ensemble", action="store_true"); ap.add_argument("--pool", action="store_true"); ap.add_argument("--bc", action="store_true")
     a = ap.parse_args()
     if a.torch_child:
         return torch_child(a)
@@ -380,6 +443,8 @@ def main():
         return ensemble(a, crux, L)
     if a.pool:
         return pool(a, crux, L)
+    if a.bc:
+        return bc(a, crux, L)
     ctx = crux.default_context(); rng = np.random.default_rng(0); lines, ours = [], {}
     for B in (32, 128):
         x = np.asfortranarray(rng.integers(0, 256, (80 * 80 * 4, B)).astype(np.float32))
