@@ -257,6 +257,46 @@ def grid_cases():
     return cs
 
 
+# ---- the edges of tests/test_gpu_conv_edges.py: branches of the kernels and of the host drivers that no grid case reaches --------------------------------------------------
+# The emulated kernel order over these cases stays inside the grid's margin (tests/test_conv_reference.py measures it): worst ratio 4.53 (db1 of VECOFF: 140 columns in the
+# four lane-group chains), next dW0 of VECOFF 4.19 and db0 of L3 3.54, every other tensor 2.70 or less, against M_EMULATED_WORST = 4.70. M_MARGIN is the grid's and does not move.
+L3 = spec(12, 10, 2, [layer((3, 3), 2, 5, "relu"), layer((2, 2), 5, 7, "tanh", 2), layer((2, 2), 7, 4, "identity")])
+L4 = spec(11, 9, 1, [layer((3, 3), 1, 3, "tanh", 1, 1), layer((2, 2), 3, 4, "relu"), layer((3, 2), 4, 6, "tanh", (2, 1)), layer((2, 2), 6, 5, "relu")])
+CIN = spec(6, 5, 20, [layer((3, 3), 20, 18, "tanh", 1, 1), layer((2, 2), 18, 3, "relu")])
+VECPAD = spec(8, 6, 3, [layer((4, 3), 3, 5, "relu", (4, 1), (0, 1))])
+VECIN = spec(16, 8, 2, [layer((1, 1), 2, 4, "tanh"), layer((4, 2), 4, 6, "relu", (4, 1))])
+VECOFF = spec(16, 8, 2, [layer((1, 1), 2, 3, "tanh"), layer((4, 2), 3, 6, "relu", (4, 1))])
+PADSTR = spec(9, 8, 2, [layer((3, 4), 2, 6, "tanh", (2, 3), (1, 2))])
+ROW = spec(13, 1, 3, [layer((3, 1), 3, 4, "relu", (2, 1), (1, 0))])
+FULL = spec(5, 4, 1, [layer((3, 3), 1, 3, "tanh", 1, 2)])
+K1 = spec(7, 7, 2, [layer((1, 3), 2, 4, "relu")])
+
+
+def edge_cases():
+    return [(L3, 5),          # three layers, identity last: the delta buffers rotate without the first swap
+            (L4, 3),          # CRUX_CONV_MAXL layers, the other parity of the rotation
+            (CIN, 3),         # cin = 20 and 18: two row tiles in the data gradient of layer 0 (d_dx) and of layer 1 (act' from the cached output)
+            (VECPAD, 5),      # the vector-load forward with padding along H (its own ih mask) and K = 36, no multiple of 64
+            (VECIN, 5),       # the vector-load forward at an inner layer: weight offset 12
+            (VECOFF, 5),      # the same shape conditions at weight offset 9: the host must take the dword form
+            (PADSTR, 7),      # asymmetric padding with stride > 1, the last rows and columns dropped
+            (ROW, 4),         # H = 1
+            (FULL, 2),        # pad = k - 1: windows that lie mostly in padding
+            (K1, 3)]          # k1 = 1
+
+
+def fwd_vec_expected(sp, l):
+    """the host's choice of the vector-load forward kernel for layer l (csrc/conv.hip: conv_fwd_vec) as far as the layer table decides it: k1, s1 and IW multiples of 4, no
+    padding along W, and the layer's weights 16 bytes into the parameter vector (the vector's and the image's own base are aligned allocations)"""
+    ly = sp["layers"][l]
+    return ly["k"][0] % 4 == 0 and ly["stride"][0] % 4 == 0 and ly["pad"][0] == 0 and extents(sp)[l][0] % 4 == 0 and layer_offsets(sp)[l][0] % 4 == 0
+
+
+def dgrad_row_tiles(sp, l):
+    """tiles of 16 rows in the data gradient of layer l (conv_dgrad_body: M = cin)"""
+    return (sp["layers"][l]["cin"] + 15) >> 4
+
+
 def case_id(case):
     sp, B = case
     return "%dx%dx%d_%s_B%d" % (sp["W"], sp["H"], sp["C"], "_".join("%d@%dx%ds%dx%dp%dx%d%s" % ((ly["cout"],) + ly["k"] + ly["stride"] + ly["pad"] + (ly["act"][0],)) for ly in sp["layers"]), B)

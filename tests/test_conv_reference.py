@@ -40,7 +40,7 @@ def _torch_trunk(p, sp, x, dy):
 SCALED = (CR.spec(8, 8, 2, [CR.layer((4, 4), 2, 3, "tanh", 2), CR.layer((2, 2), 3, 2, "relu", 1)], scale=1.0 / 255.0), 3)      # the input-scale path (forward, and dx times scale) on pixel values
 
 
-@pytest.mark.parametrize("case", CR.grid_cases()[:-1] + [SCALED, (CR.ATARI, 1)], ids=CR.case_id)
+@pytest.mark.parametrize("case", CR.grid_cases()[:-1] + [SCALED, (CR.ATARI, 1)] + CR.edge_cases(), ids=CR.case_id)
 def test_float64_reference_matches_torch_conv2d_and_autograd(case):
     sp, B = case
     p, x, dy = CR.case_inputs(case)
@@ -81,6 +81,35 @@ def test_emulated_kernel_order_sets_the_margin():
     print("EMUL worst ratio %.3f at %s" % (worst, where))
     assert worst <= CR.M_EMULATED_WORST + 0.005 and where == CR.M_EMULATED_WORST_CASE, (worst, where)
     assert CR.M_MARGIN == 2 * CR.M_EMULATED_WORST
+
+
+def test_edge_cases_are_what_they_claim():
+    """the branches tests/test_gpu_conv_edges.py is there for, read off the layer tables"""
+    assert [len(sp["layers"]) for sp in (CR.L3, CR.L4)] == [3, 4] and CR.L3["layers"][-1]["act"] == "identity"
+    assert CR.fwd_vec_expected(CR.VECPAD, 0) and CR.VECPAD["layers"][0]["pad"][1] > 0 and CR.VECPAD["layers"][0]["k"][0] * CR.VECPAD["layers"][0]["k"][1] * CR.VECPAD["C"] == 36
+    assert not CR.fwd_vec_expected(CR.VECIN, 0) and CR.fwd_vec_expected(CR.VECIN, 1) and CR.layer_offsets(CR.VECIN)[1][0] == 12
+    assert not CR.fwd_vec_expected(CR.VECOFF, 1) and CR.layer_offsets(CR.VECOFF)[1][0] == 9
+    ly = CR.VECOFF["layers"][1]      # ... on its offset only: the shape conditions are VECIN's
+    assert ly["k"][0] % 4 == 0 and ly["stride"][0] % 4 == 0 and ly["pad"][0] == 0 and CR.extents(CR.VECOFF)[1][0] % 4 == 0
+    assert [CR.dgrad_row_tiles(CR.CIN, l) for l in (0, 1)] == [2, 2]
+    assert all(CR.dgrad_row_tiles(sp, l) == 1 for sp, _ in CR.grid_cases() for l in range(len(sp["layers"])))
+
+
+def test_emulated_kernel_order_fits_the_margin_on_the_edge_cases():
+    """the edge cases are held to the grid's margin: the emulated kernel order stays within M_EMULATED_WORST on every tensor of every case, and no tensor is all zero"""
+    worst, where = 0.0, None
+    for case in CR.edge_cases():
+        sp, B = case; p, x, dy = CR.case_inputs(case)
+        r64, r32, rem = CR.trunk_reference(p, sp, x, dy), CR.trunk_reference(p, sp, x, dy, np.float32), CR.emulated_reference(p, sp, x, dy)
+        for (name, t64), (_, t32), (_, tem) in zip(tensors(r64, sp), tensors(r32, sp), tensors(rem, sp)):
+            assert np.any(t64), (CR.case_id(case), name)
+            e32, eem = CR.rel_err(t32, t64), CR.rel_err(tem, t64); ratio = eem / max(e32, CR.U32)
+            print("EMUL %s %s e32_u %.3f emul_u %.3f ratio %.3f" % (CR.case_id(case), name, e32 / CR.U32, eem / CR.U32, ratio))
+            if ratio > worst:
+                worst, where = ratio, (CR.case_id(case), name)
+    print("EMUL edges worst ratio %.3f at %s" % (worst, where))
+    assert worst <= CR.M_EMULATED_WORST, (worst, where)
+    assert CR.M_MARGIN == 2 * 4.70
 
 
 def test_scale_prelude_is_one_float32_multiply():
